@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- BCn block-transform hot path on MI355X: GiB/s of BC blocks transformed (forward + inverse).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--full] [--dump-outputs DIR]
 
 `python bench.py --gpus N` with N > 1 and no launcher environment starts
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py <same args>` as a
@@ -23,12 +23,18 @@ HBM.  `value` counts the block bytes fed to each direction: (len + len) * steps 
 Either way there is no data-path collective: torch.distributed (backend nccl = RCCL) carries the barrier and the
 MAX-over-ranks of the elapsed time only.
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps and prints the line (`ms_per_step` = wall clock of one timed step).
+--dump-outputs DIR then writes what the last timed step computed (the transformed and the restored buffer, a fixed
+seeded sample of each) as DIR/<name>.npy in float32, so that two builds can be compared output for output.  --full
+adds everything else: the exact round trip and an oracle window checked on every rank, the other single-GPU
+configurations as `legs`, and the figures below.
+
+The JSON line carries
   roofline            for the dominant kernel (BC1 forward, fwd_tiled): algorithmic bytes = 16 B/block = 2*len per
                       launch, divided by the launch's average duration measured with HIP events on the launch stream
-  cpu_baseline        the CPU port of the reference's algorithm timed on this box's host cores on a bounded sample of
+  cpu_baseline        (--full) the CPU port of the reference's algorithm timed on this box's host cores on a bounded sample of
                       the same workload, rank 0 at N=1 only
-  sharded_host_array  north_star's "shard by contiguous range across the GPUs, concatenate on the host": ONE host
+  sharded_host_array  (--full) north_star's "shard by contiguous range across the GPUs, concatenate on the host": ONE host
                       resident array, one call (dxtlt_transform_sharded) that splits it by block range over all N
                       devices and places every shard's stream slices at their final host offsets.  PCIe included,
                       reported beside `value`, never as `value`.
@@ -284,7 +290,7 @@ def parse_args():
     p.add_argument("--small-legs", action="store_true", help=argparse.SUPPRESS)   # CLI test: legs on a sub-4-GiB buffer
     p.add_argument("--leg-steps", type=int, default=10,
                    help="timed steps of each extra leg (BC3 8 GiB, BC7 4 GiB uniform + skewed, archive slice) that the "
-                        "default single-GPU BC1 run reports under `legs`; 0 = no legs")
+                        "single-GPU BC1 --full run reports under `legs`; 0 = no legs")
     p.add_argument("--cpu-sample-mib", type=int, default=1024)
     p.add_argument("--settings", default="", help="variant,split_alpha,split_colour (e.g. 0,0,1) instead of the "
                    "format's default settings; a sweep knob, the headline run uses the defaults")
@@ -292,7 +298,38 @@ def parse_args():
                    "(an odd count exercises the shifted-tile kernels)")
     p.add_argument("--force-path", type=int, default=0, help="experiment: 1 = element-granular kernel, 2 = shifted tiles")
     p.add_argument("--tile-threads", type=int, default=0, help="tuning experiment: tile workgroup size 256 (default) or 512")
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beside the headline figure: exactness checks against the round trip and the "
+                        "oracle, the legs, the link ceiling, the sharded host-array leg and the CPU baseline of the bc1/bc2/bc3 "
+                        "buffer workload (off: set up, warm up, time --steps steps, print the line); --format bc7 and "
+                        "--workload archive check their results either way")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32; a fixed, "
+                        "seeded sample of at most %d MiB in all when the outputs are larger)" % (DUMP_BYTES >> 20))
     return p.parse_args()
+
+
+DUMP_BYTES = 48 << 20       # float32 bytes of all --dump-outputs arrays together
+DUMP_SEED = 0xD0D0D0
+
+
+def dump_outputs(torch, out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: every tensor of `arrays` (name -> device tensor of bytes) as out_dir/<name>.npy in float32.  A tensor that
+    does not fit its share of DUMP_BYTES is sampled at the same seeded, sorted byte offsets on every run (numpy's default_rng of
+    DUMP_SEED and the tensor's length), so two builds given the same arguments write comparable files."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTES // 4 // max(1, len(arrays))
+    for name, t in arrays.items():
+        flat = t.reshape(-1)
+        n = int(flat.numel())
+        if n <= share:
+            vals = flat
+        else:
+            idx = np.sort(np.random.default_rng([DUMP_SEED, n]).integers(0, n, share, dtype=np.int64))
+            vals = flat[torch.from_numpy(idx).to(flat.device)]
+        np.save(os.path.join(out_dir, f"{name}.npy"), vals.to(torch.float32).cpu().numpy())
 
 
 def physical_cores() -> int:
@@ -942,6 +979,8 @@ def bc7_main(args) -> None:
     elapsed = R.max_over_ranks(elapsed_here)
     fwd_ms = sum(e[0].elapsed_time(e[1]) for e in ev) / args.steps
     inv_ms = sum(e[1].elapsed_time(e[2]) for e in ev) / args.steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, args.dump_outputs, {"transformed": y, "restored": z})
     round_trip_exact = bool(torch.equal(z, x))
     cpu = None
     import numpy as np
@@ -1046,7 +1085,7 @@ def archive_main(args) -> None:
         fmts = ["bc1" if i % 2 == 0 else "bc3" for i in range(k)]
         plans = [pkg.plan_shards(tex_bytes // pkg.BLOCK_BYTES[f], world)[rank] for f in fmts]
         xs = [torch.empty(n * pkg.BLOCK_BYTES[f], dtype=torch.uint8, device=dev) for f, (_, n) in zip(fmts, plans)]
-        ys = [torch.empty(tex_bytes, dtype=torch.uint8, device=dev) for _ in range(k)]
+        ys = [torch.zeros(tex_bytes, dtype=torch.uint8, device=dev) for _ in range(k)]    # other ranks' slices stay 0
         zs = [torch.empty_like(x) for x in xs]
         for i, x in enumerate(xs):
             first = plans[i][0]
@@ -1090,6 +1129,9 @@ def archive_main(args) -> None:
     barrier()
     elapsed_here = time.perf_counter() - t0
     elapsed = R.max_over_ranks(elapsed_here)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, args.dump_outputs, {**{f"transformed_{i:03d}": t for i, t in enumerate(ys)},
+                                                **{f"restored_{i:03d}": t for i, t in enumerate(zs)}})
     round_trip_exact = all(bool(torch.equal(z, x)) for x, z in zip(xs, zs))
     ok = True
     win = 1 << 15
@@ -1371,7 +1413,10 @@ def main() -> None:
     # The link's ceiling for the host-array leg is taken FIRST, while the host is as the process found it: measured at the end
     # of a full run -- 24 GiB of host arrays first-touched next to the device, the legs' CPU baselines behind it -- the same
     # pinned pair lands on far memory and reads 27 instead of 45 GiB/s per direction (profiles/r04_channel_map.txt, item 4).
-    host_gib = args.host_array_gib if args.host_array_gib is not None else min(args.size_gib, 8.0)
+    # (--full only, like every figure beside the headline)
+    host_gib = 0.0
+    if args.full:
+        host_gib = args.host_array_gib if args.host_array_gib is not None else min(args.size_gib, 8.0)
     ceiling = None
     if rank == 0 and host_gib > 0 and not args.drop_blocks:
         try:
@@ -1385,7 +1430,7 @@ def main() -> None:
     pkg.fill_splitmix64(x, seed, first * block // 8)
     if strong:
         # the WHOLE transformed buffer; the range calls touch only this rank's slice of every stream
-        y = torch.empty(total_blocks * block, dtype=torch.uint8, device=dev)
+        y = torch.zeros(total_blocks * block, dtype=torch.uint8, device=dev)     # other ranks' slices stay 0
         y_total, y_first = total_blocks, first
 
         def fwd():
@@ -1434,32 +1479,41 @@ def main() -> None:
 
     fwd_ms = sum(e[0].elapsed_time(e[1]) for e in ev) / args.steps
     inv_ms = sum(e[1].elapsed_time(e[2]) for e in ev) / args.steps
-    # correctness inside the run, on EVERY rank (rank r's blocks are its own: fill_splitmix64(x, seed, first * block / 8)): exact round
-    # trip, and one window of the rank's own block range against the oracle; the flags ride in per_rank and the line's flag is their AND
-    import numpy as np
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives: the transformed buffer and the restored one
+        dump_outputs(torch, args.dump_outputs, {"transformed": y, "restored": z})
 
-    if rank == 0:
+    bit_exact = None
+    if args.full:
+        # correctness inside the run, on EVERY rank (rank r's blocks are its own: fill_splitmix64(x, seed, first * block / 8)): exact
+        # round trip, and one window of the rank's own block range against the oracle; the flags ride in per_rank and the line's flag is
+        # their AND
+        import numpy as np
+
+        if rank == 0:
+            from oracle import oracle_c
+
+            oracle_c.lib()          # one process brings the checker's .so up to date before the others load it
+        R.cpu_barrier()
         from oracle import oracle_c
 
-        oracle_c.lib()          # one process brings the checker's .so up to date before the others load it
-    R.cpu_barrier()
-    from oracle import oracle_c
-
-    round_trip_exact = bool(torch.equal(z, x))
-    win = min(1 << 16, blocks)
-    lf = min(blocks // 2 + 4097, blocks - win)
-    xin = x[lf * block:(lf + win) * block].cpu().numpy()
-    want = oracle_c.transform(fmt, xin, int(settings.decorrelation_mode), settings.split_colour_endpoints,
-                              getattr(settings, "split_alpha_endpoints", True))
-    got = np.empty_like(want)
-    for off, w in pkg.stream_table(fmt, settings):
-        lo = off * y_total + w * (y_first + lf)
-        got[off * win: off * win + w * win] = y[lo: lo + w * win].cpu().numpy()
-    oracle_window_exact = bool(np.array_equal(got, want))
-    per_rank = per_rank_record(R, fwd_ms, inv_ms, elapsed_here,
-                               {"round_trip_exact": round_trip_exact, "oracle_window_exact": oracle_window_exact})
-    bit_exact = all_ranks_exact(per_rank, ("round_trip_exact", "oracle_window_exact"))
-    assert bit_exact, f"GPU result differs from the oracle / round trip failed: {per_rank['per_rank']}"
+        round_trip_exact = bool(torch.equal(z, x))
+        win = min(1 << 16, blocks)
+        lf = min(blocks // 2 + 4097, blocks - win)
+        xin = x[lf * block:(lf + win) * block].cpu().numpy()
+        want = oracle_c.transform(fmt, xin, int(settings.decorrelation_mode), settings.split_colour_endpoints,
+                                  getattr(settings, "split_alpha_endpoints", True))
+        got = np.empty_like(want)
+        for off, w in pkg.stream_table(fmt, settings):
+            lo = off * y_total + w * (y_first + lf)
+            got[off * win: off * win + w * win] = y[lo: lo + w * win].cpu().numpy()
+        oracle_window_exact = bool(np.array_equal(got, want))
+        per_rank = per_rank_record(R, fwd_ms, inv_ms, elapsed_here,
+                                   {"round_trip_exact": round_trip_exact, "oracle_window_exact": oracle_window_exact})
+        bit_exact = all_ranks_exact(per_rank, ("round_trip_exact", "oracle_window_exact"))
+        assert bit_exact, f"GPU result differs from the oracle / round trip failed: {per_rank['per_rank']}"
+    else:
+        per_rank = per_rank_record(R, fwd_ms, inv_ms, elapsed_here)
 
     if rank != 0:
         # rank 0 still drives every device for the sharded_host_array leg; stay out of its way, then leave together
@@ -1531,7 +1585,7 @@ def main() -> None:
                                "frac": round(achieved_inv / HBM_PEAK_GBPS, 4)},
         },
     }
-    default_run = (world == 1 and fmt == "bc1" and not args.settings and not args.drop_blocks and not args.force_path
+    default_run = (args.full and world == 1 and fmt == "bc1" and not args.settings and not args.drop_blocks and not args.force_path
                    and not args.tile_threads and not strong and (nbytes >= (4 << 30) or args.small_legs))
     if default_run and args.leg_steps > 0:
         # the other single-GPU configurations of BASELINE.json, on the same three device buffers (x is overwritten)
@@ -1555,7 +1609,7 @@ def main() -> None:
         except Exception as e:  # noqa: BLE001
             out["sharded_host_array"] = {"error": f"{type(e).__name__}: {e}"}
     R.cpu_barrier()
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         s = (int(settings.decorrelation_mode), bool(getattr(settings, "split_alpha_endpoints", True)),
              bool(settings.split_colour_endpoints))
         out["cpu_baseline"] = cpu_baseline(fmt, s, args.cpu_sample_mib)

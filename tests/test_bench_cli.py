@@ -10,7 +10,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_help_lists_the_contract_flags():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stderr
-    for flag in ("--gpus", "--steps", "--warmup", "--format", "--workload", "--size-gib", "--no-cpu-baseline"):
+    for flag in ("--gpus", "--steps", "--warmup", "--format", "--workload", "--size-gib", "--no-cpu-baseline", "--full",
+                 "--dump-outputs"):
         assert flag in r.stdout, flag
     assert "bc7" in r.stdout and "archive" in r.stdout
 
@@ -25,6 +26,7 @@ def test_bench_defaults():
     finally:
         sys.argv = argv
     assert (a.gpus, a.format, a.workload) == (1, "bc1", "buffer") and a.steps > 0 and a.warmup >= 0
+    assert a.full is False and a.dump_outputs is None          # a plain run measures the headline only and writes nothing
 
 
 def test_graft_entry_has_build_and_smoke():
@@ -106,13 +108,14 @@ def test_bench_refuses_a_world_size_that_contradicts_gpus():
 import pytest  # noqa: E402
 
 
-def _run_bench(extra, env=None, timeout=600):
+def _run_bench(extra, env=None, timeout=600, full=True):
     import json
 
     e = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     e.update(env or {})
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-                        "--size-gib", "0.25", *extra], capture_output=True, text=True, timeout=timeout, env=e)
+                        "--size-gib", "0.25", *(["--full"] if full else []), *extra], capture_output=True, text=True,
+                       timeout=timeout, env=e)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
     assert len(lines) == 1, r.stdout
@@ -132,6 +135,37 @@ def test_bench_line_has_the_contract_fields_and_the_host_array_leg():
     assert d["roofline"]["traffic"] is None and d["roofline"]["traffic_source"] is None
     h = d["sharded_host_array"]
     assert h["devices"] >= 1 and h["bit_exact_roundtrip_and_oracle_windows_across_shard_boundaries"] is True
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_the_last_steps_outputs(tmp_path):
+    """Without --full the line has the headline and nothing measured beside it; --steps is the number of timed steps, and
+    --dump-outputs writes the transformed and restored buffers of the last step -- the same bytes for the same arguments."""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+    from oracle import oracle_c
+
+    dumps = []
+    for run in range(2):
+        out = tmp_path / f"run{run}"
+        d = _run_bench(["--steps", "3", "--size-gib", "0.125", "--dump-outputs", str(out)], full=False)
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in d, k
+        assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["value"] > 0 and d["dtype"] == "u8"
+        assert "legs" not in d and "cpu_baseline" not in d and "sharded_host_array" not in d
+        assert sorted(p.name for p in out.iterdir()) == ["restored.npy", "transformed.npy"]
+        dumps.append({n: np.load(out / f"{n}.npy") for n in ("transformed", "restored")})
+    a, b = dumps
+    assert all(v.dtype == np.float32 and v.size > 0 for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert all(np.array_equal(a[n], b[n]) for n in a)
+    # the restored buffer is the input: fill_splitmix64 of the BC1 seed, at the same sample offsets
+    n = int(0.125 * 2**30)
+    idx = np.sort(np.random.default_rng([bench.DUMP_SEED, n]).integers(0, n, a["restored"].size, dtype=np.int64))
+    want = oracle_c.fill_splitmix64(n, 0x0BC10002)[idx].astype(np.float32)
+    assert np.array_equal(a["restored"], want)
 
 
 @pytest.mark.gpu

@@ -22,7 +22,8 @@ for f in "$SRC"/*.cpp; do
 done
 wait
 for f in "$ROOT"/build/obj/*.hip.o; do objs+=("$f"); done
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -fsanitize=address,undefined -shared-libsan "${objs[@]}" \
+# host side only: -fno-gpu-sanitize keeps the device code of the .hip objects uninstrumented (they were built without sanitizers)
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -fno-gpu-sanitize -shared -fPIC -fsanitize=address,undefined -shared-libsan "${objs[@]}" \
     -o "$OUT/libdxtlt_gfx950_asan.so" -lpthread
 echo "built $OUT/libdxtlt_gfx950_asan.so"
 # the oracle too (test infrastructure, but every parity claim and the cpu_baseline legs stand on it): same sources, same flags
@@ -34,7 +35,10 @@ echo "built $OUT/libdxtlt_gfx950_asan.so"
 echo "built $OUT/libdxtlt_oracle_asan.so"
 cd "$ROOT"
 export DXTLT_ORACLE_SO="$OUT/libdxtlt_oracle_asan.so"
-DXTLT_LIB_PATH="$OUT/libdxtlt_gfx950_asan.so" LD_PRELOAD="$RT" \
+# the lane is a CPU one on every machine: no device is visible to it, so a box with a GPU runs the same no-device paths as one
+# without; the sanitizer runtime goes first in LD_PRELOAD, in front of whatever the environment already preloads
+HIP_VISIBLE_DEVICES=-1 ROCR_VISIBLE_DEVICES=-1 \
+DXTLT_LIB_PATH="$OUT/libdxtlt_gfx950_asan.so" LD_PRELOAD="$RT${LD_PRELOAD:+:$LD_PRELOAD}" \
     ASAN_OPTIONS=detect_leaks=0:abort_on_error=1:halt_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 \
     python3 -m pytest -q -m "not gpu" -p no:cacheprovider \
     tests/test_cabi_load.py tests/test_cabi_reference_surface.py tests/test_file_formats.py tests/test_bc7_sharded.py \

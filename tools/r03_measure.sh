@@ -11,20 +11,20 @@ mkdir -p $O
 step() { echo "== $*"; }
 
 step "bench, driver command"
-timeout -k 10 400 python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_bc1.json 2> $O/bench_bc1.err || exit 1
+timeout -k 10 400 python3 $R/bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_bc1.json 2> $O/bench_bc1.err || exit 1
 step "kernel trace"
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_kt -- python3 $R/bench.py --steps 20 --warmup 5 --host-array-gib 0 --no-cpu-baseline > $O/prof_kt.json 2> $O/prof_kt.err || exit 1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_kt -- python3 $R/bench.py --full --steps 20 --warmup 5 --host-array-gib 0 --no-cpu-baseline > $O/prof_kt.json 2> $O/prof_kt.err || exit 1
 for pass in "prof_fetch FETCH_SIZE" "prof_write WRITE_SIZE"; do
   set -- $pass; d=$1; shift
   step "pmc $*"
-  timeout -k 10 400 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $O/$d -- python3 $R/bench.py --steps 3 --warmup 1 --leg-steps 2 --no-cpu-baseline --host-array-gib 0 > $O/$d.json 2> $O/$d.err || exit 1
+  timeout -k 10 400 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $O/$d -- python3 $R/bench.py --full --steps 3 --warmup 1 --leg-steps 2 --no-cpu-baseline --host-array-gib 0 > $O/$d.json 2> $O/$d.err || exit 1
 done
 step "stand-alone lines"
-timeout -k 10 300 python3 $R/bench.py --format bc2 > $O/bench_bc2.json 2> $O/bench_bc2.err || exit 1
-timeout -k 10 300 python3 $R/bench.py --format bc3 > $O/bench_bc3.json 2> $O/bench_bc3.err || exit 1
-timeout -k 10 300 python3 $R/bench.py --format bc7 > $O/bench_bc7.json 2> $O/bench_bc7.err || exit 1
-timeout -k 10 300 python3 $R/bench.py --workload archive > $O/bench_archive.json 2> $O/bench_archive.err || exit 1
+timeout -k 10 300 python3 $R/bench.py --full --format bc2 > $O/bench_bc2.json 2> $O/bench_bc2.err || exit 1
+timeout -k 10 300 python3 $R/bench.py --full --format bc3 > $O/bench_bc3.json 2> $O/bench_bc3.err || exit 1
+timeout -k 10 300 python3 $R/bench.py --full --format bc7 > $O/bench_bc7.json 2> $O/bench_bc7.err || exit 1
+timeout -k 10 300 python3 $R/bench.py --full --workload archive > $O/bench_archive.json 2> $O/bench_archive.err || exit 1
 step "N = 2 rehearsals on one GPU (gloo): self-launch, weak and strong"
-DXTLT_BENCH_BACKEND=gloo timeout -k 10 300 python3 $R/bench.py --gpus 2 --size-gib 4 --steps 10 > $O/bench_gpus2_weak_gloo.json 2> $O/bench_gpus2_weak.err || exit 1
-DXTLT_BENCH_BACKEND=gloo timeout -k 10 300 python3 $R/bench.py --gpus 2 --scaling strong --steps 10 > $O/bench_gpus2_strong_gloo.json 2> $O/bench_gpus2_strong.err || exit 1
+DXTLT_BENCH_BACKEND=gloo timeout -k 10 300 python3 $R/bench.py --full --gpus 2 --size-gib 4 --steps 10 > $O/bench_gpus2_weak_gloo.json 2> $O/bench_gpus2_weak.err || exit 1
+DXTLT_BENCH_BACKEND=gloo timeout -k 10 300 python3 $R/bench.py --full --gpus 2 --scaling strong --steps 10 > $O/bench_gpus2_strong_gloo.json 2> $O/bench_gpus2_strong.err || exit 1
 step done

@@ -9,7 +9,7 @@ mkdir -p $O
 export DXTLT_BENCH_FORCE_DIST=1
 run() { name=$1; shift
   timeout -k 10 300 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 \
-      $R/bench.py --gpus 1 "$@" > $O/$name.json 2> $O/$name.err || { echo "$name failed"; tail -5 $O/$name.err; exit 1; }
+      $R/bench.py --full --gpus 1 "$@" > $O/$name.json 2> $O/$name.err || { echo "$name failed"; tail -5 $O/$name.err; exit 1; }
   python3 - "$O/$name.json" <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith('{"metric"')][0])

@@ -5,8 +5,8 @@
 
 Inputs (produced on the GPU box by tools/r02_measure.sh, see profiles/README.md for the exact commands), under
 gpurun_out/ or the given sub-directory:
-  gpurun_out/prof_kt     --kernel-trace --stats            of `python3 bench.py --steps 20 --warmup 3`
-  gpurun_out/prof_fetch  --pmc FETCH_SIZE --kernel-trace   of `python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline`
+  <dir>/prof_kt          --kernel-trace --stats            of `python3 bench.py --full --steps 20 --warmup 3`
+  <dir>/prof_fetch       --pmc FETCH_SIZE --kernel-trace   of `python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline`
   gpurun_out/prof_write  --pmc WRITE_SIZE --kernel-trace   (same command)
   gpurun_out/prof_req    --pmc TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum TCC_EA0_RDREQ_32B_sum
 
