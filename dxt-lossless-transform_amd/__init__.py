@@ -6,6 +6,8 @@ The names follow the reference's core crates (paths under /root/reference/src/co
   Bc1TransformSettings             dxt-lossless-transform-bc1/src/transform/settings.rs:16-43
   Bc2TransformSettings             dxt-lossless-transform-bc2/src/transform/settings.rs:16
   Bc3TransformSettings             dxt-lossless-transform-bc3/src/transform/settings.rs:16-48
+  Bc4TransformSettings / Bc5...    api/dxt-lossless-transform-file-formats-api/src/embed/formats/bc4.rs, bc5.rs (placeholder
+                                   settings, one field); the transform itself is this build's (docs/BC45_FORMAT.md)
   transform_bcN_with_settings      .../safe/transform_with_settings.rs:88  (validated slice API)
   untransform_bcN_with_settings    .../safe/transform_with_settings.rs:192
   BcNValidationError               .../safe/transform_with_settings.rs:18-31
@@ -36,10 +38,13 @@ __all__ = [
     "transform_bc3_with_settings", "untransform_bc3_with_settings",
     "transform_range", "transform_sharded", "fill_splitmix64", "build", "load", "set_tuning",
     "stream_table", "plan_shards", "BLOCK_BYTES",
+    "Bc4TransformSettings", "Bc5TransformSettings",
+    "transform_bc4_with_settings", "untransform_bc4_with_settings",
+    "transform_bc5_with_settings", "untransform_bc5_with_settings",
 ]
 
-BLOCK_BYTES = {"bc1": 8, "bc2": 16, "bc3": 16}
-_FMT_ID = {"bc1": 1, "bc2": 2, "bc3": 3}
+BLOCK_BYTES = {"bc1": 8, "bc2": 16, "bc3": 16, "bc4": 8, "bc5": 16}
+_FMT_ID = {"bc1": 1, "bc2": 2, "bc3": 3, "bc4": 4, "bc5": 5}
 
 
 class YCoCgVariant(enum.IntEnum):
@@ -88,6 +93,29 @@ class Bc3TransformSettings:
             for sa in (True, False):
                 for sc in (True, False):
                     yield Bc3TransformSettings(v, sa, sc)
+
+
+@dataclasses.dataclass(frozen=True)
+class Bc4TransformSettings:
+    """embed/formats/bc4.rs: one setting.  False (upstream's Bc4TransformSettings::new()): endpoint pairs in one stream; True:
+    a0 and a1 in two streams.  Layout: docs/BC45_FORMAT.md."""
+    split_endpoints: bool = False
+
+    @staticmethod
+    def all_combinations() -> Iterator["Bc4TransformSettings"]:
+        for s in (False, True):
+            yield Bc4TransformSettings(s)
+
+
+@dataclasses.dataclass(frozen=True)
+class Bc5TransformSettings:
+    """embed/formats/bc5.rs: one setting, applied to the red and the green half alike (docs/BC45_FORMAT.md)."""
+    split_endpoints: bool = False
+
+    @staticmethod
+    def all_combinations() -> Iterator["Bc5TransformSettings"]:
+        for s in (False, True):
+            yield Bc5TransformSettings(s)
 
 
 # bc1 settings.rs:33: the untransform settings are the same type
@@ -189,6 +217,8 @@ def _check(rc: int) -> None:
 
 
 def _settings_tuple(fmt: str, settings):
+    if fmt in ("bc4", "bc5"):   # no colour endpoints: split_endpoints travels as the alpha split (include/dxtlt_bc45.h)
+        return 0, bool(settings.split_endpoints), False
     mode = int(settings.decorrelation_mode)
     sa = bool(getattr(settings, "split_alpha_endpoints", False)) if fmt == "bc3" else False
     return mode, sa, bool(settings.split_colour_endpoints)
@@ -209,7 +239,10 @@ def _call(fmt: str, inverse: bool, input, output, settings) -> None:
     d = "untransform" if inverse else "transform"
     if src.device is None:
         f = getattr(l, f"dxtlt_{d}_{fmt}_with_settings")
-        rc = f(src.ptr, dst.ptr, src.nbytes, mode, sa, sc) if fmt == "bc3" else f(src.ptr, dst.ptr, src.nbytes, mode, sc)
+        if fmt in ("bc4", "bc5"):
+            rc = f(src.ptr, dst.ptr, src.nbytes, sa)
+        else:
+            rc = f(src.ptr, dst.ptr, src.nbytes, mode, sa, sc) if fmt == "bc3" else f(src.ptr, dst.ptr, src.nbytes, mode, sc)
     else:
         import torch
 
@@ -218,7 +251,9 @@ def _call(fmt: str, inverse: bool, input, output, settings) -> None:
         with torch.cuda.device(src.device):
             stream = torch.cuda.current_stream().cuda_stream
             f = getattr(l, f"dxtlt_{d}_{fmt}_with_settings_device")
-            if fmt == "bc3":
+            if fmt in ("bc4", "bc5"):
+                rc = f(src.ptr, dst.ptr, src.nbytes, sa, stream)
+            elif fmt == "bc3":
                 rc = f(src.ptr, dst.ptr, src.nbytes, mode, sa, sc, stream)
             else:
                 rc = f(src.ptr, dst.ptr, src.nbytes, mode, sc, stream)
@@ -247,6 +282,22 @@ def transform_bc3_with_settings(input, output, settings: Bc3TransformSettings = 
 
 def untransform_bc3_with_settings(input, output, settings: Bc3TransformSettings = Bc3TransformSettings()) -> None:
     _call("bc3", True, input, output, settings)
+
+
+def transform_bc4_with_settings(input, output, settings: Bc4TransformSettings = Bc4TransformSettings()) -> None:
+    _call("bc4", False, input, output, settings)
+
+
+def untransform_bc4_with_settings(input, output, settings: Bc4TransformSettings = Bc4TransformSettings()) -> None:
+    _call("bc4", True, input, output, settings)
+
+
+def transform_bc5_with_settings(input, output, settings: Bc5TransformSettings = Bc5TransformSettings()) -> None:
+    _call("bc5", False, input, output, settings)
+
+
+def untransform_bc5_with_settings(input, output, settings: Bc5TransformSettings = Bc5TransformSettings()) -> None:
+    _call("bc5", True, input, output, settings)
 
 
 def transform_range(fmt: str, inverse: bool, src, dst, total_blocks: int, first_block: int, num_blocks: int,
@@ -331,13 +382,16 @@ def stream_table(fmt: str, settings) -> list[tuple[int, int]]:
     `width` bytes per block (csrc/bcn_launch.h make_streams)."""
     _, sa, sc = _settings_tuple(fmt, settings)
     widths: list[int] = []
+    if fmt in ("bc4", "bc5"):   # one / two BC3 alpha halves: endpoints (1 + 1 or 2), indices 6
+        widths = ([1, 1, 6] if sa else [2, 6]) * (2 if fmt == "bc5" else 1)
     if fmt == "bc3":
         widths += [1, 1] if sa else [2]
         widths += [6]
     if fmt == "bc2":
         widths += [8]
-    widths += [2, 2] if sc else [4]
-    widths += [4]
+    if fmt in ("bc1", "bc2", "bc3"):
+        widths += [2, 2] if sc else [4]
+        widths += [4]
     out, off = [], 0
     for w in widths:
         out.append((off, w))

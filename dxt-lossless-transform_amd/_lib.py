@@ -32,6 +32,12 @@ def _declare(l: C.CDLL) -> None:
         f.argtypes, f.restype = [vp, vp, sz, u8, b, b], i32
         f = getattr(l, f"dxtlt_{d}_bc3_with_settings_device")
         f.argtypes, f.restype = [vp, vp, sz, u8, b, b, vp], i32
+    for n in ("bc4", "bc5") if hasattr(l, "dxtlt_transform_bc4_with_settings") else ():   # include/dxtlt_bc45.h
+        for d in ("transform", "untransform"):
+            f = getattr(l, f"dxtlt_{d}_{n}_with_settings")
+            f.argtypes, f.restype = [vp, vp, sz, b], i32
+            f = getattr(l, f"dxtlt_{d}_{n}_with_settings_device")
+            f.argtypes, f.restype = [vp, vp, sz, b, vp], i32
     l.dxtlt_transform_range_device.argtypes = [i32, b, vp, vp, u64, u64, u64, u8, b, b, vp]
     l.dxtlt_transform_range_device.restype = i32
     l.dxtlt_transform_sharded.argtypes = [i32, b, vp, vp, sz, u8, b, b, i32]

@@ -28,6 +28,7 @@
 #include <thread>
 #include <vector>
 
+#include "../../include/dxtlt_bc45.h"
 #include "../../include/dxtlt_gfx950.h"
 #include "auto_launch.h"
 #include "bcn_launch.h"
@@ -463,7 +464,175 @@ int32_t dxtlt_host::transform_auto(int32_t format, const uint8_t* in, uint8_t* o
     return kOk;
 }
 
+// BC4 / BC5 (include/dxtlt_bc45.h): two candidates, split_endpoints = false then true.  Both forward transforms go into a device
+// arena of 2 x len (one upload, two launches); the estimator sees each candidate's endpoint section(s) -- BC4 [0, 2N), BC5 red
+// [0, 2N) then green [8N, 10N), added -- and the winner's arena copy is what is downloaded.  Without the arena the candidates run one
+// at a time through d_out, as the BC1-3 fallback does.
+int32_t dxtlt_host::transform_auto_bc45(int32_t format, const uint8_t* in, uint8_t* out, size_t len, const DltSizeEstimator* est,
+                                        AutoChoice* choice)
+{
+    if (format != 4 && format != 5)
+        return fail(kInvalidArgument, "format must be 4 (BC4) or 5 (BC5)");
+    const size_t block = format == 4 ? 8 : 16;
+    if (len % block != 0)
+        return fail(kInvalidLength, "len is not a multiple of the block size");
+    if (est == nullptr || est->MaxCompressedSize == nullptr || est->EstimateCompressedSize == nullptr || choice == nullptr)
+        return fail(kInvalidArgument, "NULL estimator / choice");
+    if (len > 0 && (in == nullptr || out == nullptr))
+        return fail(kInvalidArgument, "NULL buffer with len > 0");
+
+    const uint64_t blocks = len / block;
+    const int n_sections = format == 5 ? 2 : 1;
+    const size_t section_len = (size_t)blocks * 2;              // every section: one endpoint pair (or a0 run + a1 run) per block
+    const size_t section_off[2] = {0, (size_t)blocks * 8};      // BC5: red endpoints, green endpoints
+    constexpr bool kCandidates[2] = {false, true};
+    choice->mode = 0;
+    choice->split_colour = false;
+    choice->split_alpha = false;
+    choice->estimator_error = 0;
+
+    size_t max_comp = 0;
+    uint32_t rc_est = est->MaxCompressedSize(est->Context, section_len, &max_comp);
+    if (rc_est != 0) {
+        choice->estimator_error = rc_est;
+        return fail(kEstimator, "size estimator: max_compressed_size failed");
+    }
+    uint8_t* scratch = nullptr;
+    if (max_comp != 0) {
+        scratch = static_cast<uint8_t*>(std::aligned_alloc(64, (max_comp + 63) / 64 * 64));
+        if (scratch == nullptr)
+            return fail(kAllocation, "estimator scratch allocation failed");
+    }
+    void *d_in = nullptr, *d_out = nullptr;
+    hipStream_t st = nullptr;
+    uint8_t* arena = nullptr;
+    if (len > 0) {
+        int32_t rc = acquire_staging(len, &d_in, &d_out, &st);
+        if (rc != kOk) {
+            std::free(scratch);
+            return rc;
+        }
+        HIP_TRY_AUTO(hipMemcpyAsync(d_in, in, len, hipMemcpyHostToDevice, st), "H2D copy");
+        arena = static_cast<uint8_t*>(g_arena.get(2 * len));
+        for (int k = 0; k < 2 && arena != nullptr; ++k) {
+            const int32_t rc2 = enqueue(format, false, d_in, arena + (size_t)k * len, blocks, 0, kCandidates[k], false, st);
+            if (rc2 != kOk) {
+                (void)hipStreamSynchronize(st);
+                std::free(scratch);
+                return rc2;
+            }
+        }
+    }
+    auto fail_estimate = [&](uint32_t bad) {
+        if (st) (void)hipStreamSynchronize(st);
+        std::free(scratch);
+        choice->estimator_error = bad;
+        return fail(kEstimator, "size estimator: estimate_compressed_size failed");
+    };
+
+    int est_threads = g_estimator_threads.load(std::memory_order_relaxed);
+    if (t_estimator_threads_cap > 0 && est_threads > t_estimator_threads_cap)
+        est_threads = t_estimator_threads_cap;
+    int best = 0;
+    size_t best_size = SIZE_MAX;
+    if (est_threads > 1 && arena != nullptr) {
+        // every section of both candidates at once; combined in the sequential order below
+        std::vector<Section> sections;
+        for (int k = 0; k < 2; ++k)
+            for (int h = 0; h < n_sections; ++h)
+                sections.push_back(Section{arena + (size_t)k * len + section_off[h], section_len});
+        hipError_t herr = hipSuccess;
+        if (!estimate_sections_parallel(sections, est, max_comp, est_threads, st, &herr))
+            HIP_TRY_AUTO(herr == hipSuccess ? hipErrorUnknown : herr, "parallel estimation (staging / download)");
+        for (int k = 0; k < 2; ++k) {
+            size_t total = 0;
+            for (int h = 0; h < n_sections; ++h) {
+                const Section& sec = sections[(size_t)(k * n_sections + h)];
+                if (sec.rc != 0)
+                    return fail_estimate(sec.rc);
+                total += sec.size;
+            }
+            if (total < best_size) {
+                best_size = total;
+                best = k;
+            }
+        }
+    } else {
+        int last = -1;   // the candidate whose transform is in d_out (no arena)
+        for (int k = 0; k < 2; ++k) {
+            if (len > 0) {
+                const uint8_t* src = arena;
+                if (arena != nullptr) {
+                    src = arena + (size_t)k * len;
+                } else {
+                    const int32_t rc = enqueue(format, false, d_in, d_out, blocks, 0, kCandidates[k], false, st);
+                    if (rc != kOk) {
+                        (void)hipStreamSynchronize(st);
+                        std::free(scratch);
+                        return rc;
+                    }
+                    src = static_cast<const uint8_t*>(d_out);
+                    last = k;
+                }
+                // the section(s) travel into the output buffer at the offsets they are estimated at
+                for (int h = 0; h < n_sections; ++h)
+                    HIP_TRY_AUTO(hipMemcpyAsync(out + section_off[h], src + section_off[h], section_len, hipMemcpyDeviceToHost, st),
+                                 "D2H endpoint section");
+                HIP_TRY_AUTO(hipStreamSynchronize(st), "stream synchronize");
+            }
+            size_t total = 0;
+            for (int h = 0; h < n_sections; ++h) {
+                size_t part = 0;
+                rc_est = est->EstimateCompressedSize(est->Context, out + section_off[h], section_len, scratch, max_comp, &part);
+                if (rc_est != 0)
+                    return fail_estimate(rc_est);
+                total += part;
+            }
+            if (total < best_size) {
+                best_size = total;
+                best = k;
+            }
+        }
+        if (len > 0 && arena == nullptr && last != best) {
+            const int32_t rc = enqueue(format, false, d_in, d_out, blocks, 0, kCandidates[best], false, st);
+            if (rc != kOk) {
+                (void)hipStreamSynchronize(st);
+                std::free(scratch);
+                return rc;
+            }
+        }
+    }
+    if (len > 0) {
+        const void* result = arena != nullptr ? static_cast<const void*>(arena + (size_t)best * len) : d_out;
+        HIP_TRY_AUTO(hipMemcpyAsync(out, result, len, hipMemcpyDeviceToHost, st), "D2H result");
+        HIP_TRY_AUTO(hipStreamSynchronize(st), "stream synchronize");
+    }
+    std::free(scratch);
+    choice->split_alpha = kCandidates[best];
+    return kOk;
+}
+
 extern "C" {
+
+int32_t dxtlt_transform_bc4_auto(const uint8_t* input_ptr, uint8_t* output_ptr, size_t len, const DltSizeEstimator* estimator,
+                                 bool* out_split_endpoints)
+{
+    dxtlt_host::AutoChoice c{};
+    const int32_t rc = dxtlt_host::transform_auto_bc45(4, input_ptr, output_ptr, len, estimator, &c);
+    if (rc == DXTLT_OK && out_split_endpoints)
+        *out_split_endpoints = c.split_alpha;
+    return rc;
+}
+
+int32_t dxtlt_transform_bc5_auto(const uint8_t* input_ptr, uint8_t* output_ptr, size_t len, const DltSizeEstimator* estimator,
+                                 bool* out_split_endpoints)
+{
+    dxtlt_host::AutoChoice c{};
+    const int32_t rc = dxtlt_host::transform_auto_bc45(5, input_ptr, output_ptr, len, estimator, &c);
+    if (rc == DXTLT_OK && out_split_endpoints)
+        *out_split_endpoints = c.split_alpha;
+    return rc;
+}
 
 int32_t dxtlt_transform_bc1_auto(const uint8_t* input_ptr, uint8_t* output_ptr, size_t len,
                                  const DltSizeEstimator* estimator, bool use_all_decorrelation_modes,

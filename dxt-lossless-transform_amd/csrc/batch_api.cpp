@@ -32,6 +32,9 @@ namespace {
 using namespace dxtlt_host;
 using dxtlt::BatchEntry;
 
+// bytes per block of a batch item's format (1..5, 7)
+inline uint32_t item_block_bytes(uint8_t format) { return format == 1 || format == 4 ? 8u : 16u; }
+
 // Table staging: a ring of pinned host buffers with device twins.  A slot is reused only after the copy and the kernels that last
 // read it have finished (its event).  A call takes exactly ONE slot -- the tables of its two BC7 launches and of all its BC1-3
 // groups share one staged buffer and one upload -- so it never waits for its own work, and its acquire blocks the host only when
@@ -137,11 +140,11 @@ extern "C" int32_t dxtlt_transform_batch_device(const DxtltBatchItem* items, siz
     // validate everything first: a batch is enqueued whole or not at all
     for (size_t i = 0; i < count; ++i) {
         const DxtltBatchItem& it = items[i];
-        if ((it.format < 1 || it.format > 3) && it.format != 7)
-            return fail(kInvalidArgument, "batch item: format must be 1 (BC1), 2 (BC2), 3 (BC3) or 7 (BC7, this build's own format)");
-        if (it.len % (it.format == 1 ? 8u : 16u) != 0)
+        if ((it.format < 1 || it.format > 5) && it.format != 7)
+            return fail(kInvalidArgument, "batch item: format must be 1..5 (BC1..BC5) or 7 (BC7, this build's own format)");
+        if (it.len % item_block_bytes(it.format) != 0)
             return fail(kInvalidLength, "batch item: len is not a multiple of the block size");
-        if (it.decorrelation_mode > 3 && it.format != 7)
+        if (it.decorrelation_mode > 3 && dxtlt::format_has_colour(it.format))
             return fail(kInvalidArgument, "batch item: decorrelation_mode must be 0..3");
         if (it.len > 0 && (it.d_input == nullptr || it.d_output == nullptr))
             return fail(kInvalidArgument, "batch item: NULL device buffer with len > 0");
@@ -167,7 +170,7 @@ extern "C" int32_t dxtlt_transform_batch_device(const DxtltBatchItem* items, siz
         uint32_t uniform_wgs = 0;   // workgroups per buffer while all buffers own the same number
         bool uniform = true;
     };
-    constexpr int kGroups = 3 * 2 * 16;   // format, direction, variant x split_alpha x split_colour
+    constexpr int kGroups = 5 * 2 * 16;   // format, direction, variant x split_alpha x split_colour
     std::vector<Group> groups(kGroups);
     auto group_settings = [](int gi) {
         dxtlt::Settings s{};
@@ -183,13 +186,16 @@ extern "C" int32_t dxtlt_transform_batch_device(const DxtltBatchItem* items, siz
             continue;
         if (it.len >= (size_t(64) << 30))
             return fail(kInvalidArgument, "batch item of 64 GiB or more: use the single-buffer entry point");
-        const int sa = it.format == 3 && it.split_alpha_endpoints ? 1 : 0, sc = it.split_colour_endpoints ? 1 : 0;
-        const int gi = (((it.format - 1) * 2 + (it.inverse ? 1 : 0)) << 4) | (it.decorrelation_mode << 2) | (sa << 1) | sc;
+        // (BC4 / BC5: no variant, no colour split -- their items fall into the group of variant 0 without it)
+        const bool colour = dxtlt::format_has_colour(it.format);
+        const int sa = dxtlt::format_has_alpha_split(it.format) && it.split_alpha_endpoints ? 1 : 0;
+        const int sc = colour && it.split_colour_endpoints ? 1 : 0, mode = colour ? it.decorrelation_mode : 0;
+        const int gi = (((it.format - 1) * 2 + (it.inverse ? 1 : 0)) << 4) | (mode << 2) | (sa << 1) | sc;
         Group& g = groups[gi];
         BatchEntry e{};
         e.src = static_cast<const uint8_t*>(it.d_input);
         e.dst = static_cast<uint8_t*>(it.d_output);
-        e.blocks = it.len / (it.format == 1 ? 8u : 16u);
+        e.blocks = it.len / item_block_bytes(it.format);
         e.first_wg = g.wgs;
         const uint32_t wgs = dxtlt::plan_batch_entry((dxtlt::Format)it.format, it.inverse != 0, group_settings(gi), e);
         if (wgs == 0xFFFFFFFFu) {
@@ -339,9 +345,10 @@ extern "C" int32_t dxtlt_transform_batch_device(const DxtltBatchItem* items, siz
         const DxtltBatchItem& it = items[i];
         dxtlt::Settings s{};
         s.variant = it.decorrelation_mode;
-        s.split_alpha = it.format == 3 && it.split_alpha_endpoints;
+        s.split_alpha = it.split_alpha_endpoints != 0;
         s.split_colour = it.split_colour_endpoints != 0;
-        const uint64_t blocks = it.len / (it.format == 1 ? 8u : 16u);
+        s = dxtlt::effective_settings((dxtlt::Format)it.format, s);
+        const uint64_t blocks = it.len / item_block_bytes(it.format);
         const hipError_t e = dxtlt::launch_transform((dxtlt::Format)it.format, it.inverse != 0, s, it.d_input, it.d_output,
                                                      dxtlt::Range{blocks, 0, blocks}, user);
         if (e != hipSuccess)
@@ -362,12 +369,13 @@ extern "C" uint32_t dxtlt_debug_plan_batch(int32_t format, int32_t inverse, int3
 {
     if (index_is_wide_out)
         *index_is_wide_out = 0;
-    if (format < 1 || format > 3 || (count != 0 && (!src_addresses || !dst_addresses || !blocks || !entries_out)))
+    if (format < 1 || format > 5 || (count != 0 && (!src_addresses || !dst_addresses || !blocks || !entries_out)))
         return 0xFFFFFFFFu;
     dxtlt::Settings s{};
     s.variant = variant;
-    s.split_alpha = format == 3 && split_alpha != 0;
+    s.split_alpha = split_alpha != 0;
     s.split_colour = split_colour != 0;
+    s = dxtlt::effective_settings((dxtlt::Format)format, s);
     std::vector<BatchEntry> entries;
     uint32_t total = 0;
     for (size_t i = 0; i < count; ++i) {
@@ -497,11 +505,11 @@ extern "C" int32_t dxtlt_transform_batch_host(const DxtltBatchItem* items, size_
     uint64_t total = 0;
     for (size_t i = 0; i < count; ++i) {
         const DxtltBatchItem& it = items[i];
-        if ((it.format < 1 || it.format > 3) && it.format != 7)
-            return fail(kInvalidArgument, "batch item: format must be 1 (BC1), 2 (BC2), 3 (BC3) or 7 (BC7, this build's own format)");
-        if (it.len % (it.format == 1 ? 8u : 16u) != 0)
+        if ((it.format < 1 || it.format > 5) && it.format != 7)
+            return fail(kInvalidArgument, "batch item: format must be 1..5 (BC1..BC5) or 7 (BC7, this build's own format)");
+        if (it.len % item_block_bytes(it.format) != 0)
             return fail(kInvalidLength, "batch item: len is not a multiple of the block size");
-        if (it.decorrelation_mode > 3 && it.format != 7)
+        if (it.decorrelation_mode > 3 && dxtlt::format_has_colour(it.format))
             return fail(kInvalidArgument, "batch item: decorrelation_mode must be 0..3");
         if (it.len > 0 && (it.d_input == nullptr || it.d_output == nullptr))
             return fail(kInvalidArgument, "batch item: NULL buffer with len > 0");
@@ -532,7 +540,7 @@ extern "C" int32_t dxtlt_transform_batch_host(const DxtltBatchItem* items, size_
         else
             rc = dxtlt_host::transform(it.format, it.inverse != 0, static_cast<const uint8_t*>(it.d_input),
                                        static_cast<uint8_t*>(it.d_output), it.len, it.decorrelation_mode,
-                                       it.format == 3 && it.split_alpha_endpoints, it.split_colour_endpoints != 0);
+                                       dxtlt::format_has_alpha_split(it.format) && it.split_alpha_endpoints, it.split_colour_endpoints != 0);
         if (rc != kOk)
             return rc;
     }

@@ -273,11 +273,11 @@ uint32_t plan_batch_entry(Format fmt, bool inverse, const Settings& s, BatchEntr
 {
     if (e.blocks == 0)
         return 0;
-    const bool sa = fmt == kBc3 && s.split_alpha;
-    const Streams S = make_streams(fmt, sa, s.split_colour);
+    const Settings es = effective_settings(fmt, s);
+    const Streams S = make_streams(fmt, es.split_alpha, es.split_colour);
     const void* soa = inverse ? (const void*)e.src : (const void*)e.dst;
     // any AoS alignment: unaligned 16-byte vector accesses are exact and cheap on gfx950 (launch_transform)
-    const uint64_t T = (uint64_t)tile_blocks(fmt, batch_tile_threads(fmt, s.split_colour, inverse));
+    const uint64_t T = (uint64_t)tile_blocks(fmt, batch_tile_threads(fmt, es.split_colour, inverse));
     const uint64_t tiles = e.blocks / T, rest = e.blocks % T;
     // The tile forms of launch_transform: aligned tiles when every stream base is on a 128-byte line; otherwise forward halo
     // tiles (windows moved back to a 64-byte boundary) and inverse shifted tiles (slices displaced by the base modulo 16).
@@ -360,6 +360,13 @@ BatchFn batch_splits(bool sa, bool sc, bool inverse)
     return sc ? batch_fn<FMT, VARIANT, false, true>(inverse) : batch_fn<FMT, VARIANT, false, false>(inverse);
 }
 
+// BC4 / BC5: VARIANT 0 and no colour split only; the endpoint split picks the kernel
+template <int FMT>
+BatchFn batch_bc45(bool split_endpoints, bool inverse)
+{
+    return split_endpoints ? batch_fn<FMT, kNone, true, false>(inverse) : batch_fn<FMT, kNone, false, false>(inverse);
+}
+
 template <int FMT>
 BatchFn batch_variant(int variant, bool sa, bool sc, bool inverse)
 {
@@ -402,12 +409,15 @@ hipError_t launch_batch(Format fmt, bool inverse, const Settings& s, const Batch
         strided.dst_stride = dst_stride;
         strided.on = 1;
     }
-    const bool sa = fmt == kBc3 && s.split_alpha, sc = s.split_colour;
+    const Settings es = effective_settings(fmt, s);
+    const bool sa = es.split_alpha, sc = es.split_colour;
     BatchFn k = nullptr;
     switch (fmt) {
-    case kBc1: k = batch_variant<kBc1>(s.variant, false, sc, inverse); break;
-    case kBc2: k = batch_variant<kBc2>(s.variant, false, sc, inverse); break;
-    case kBc3: k = batch_variant<kBc3>(s.variant, sa, sc, inverse); break;
+    case kBc1: k = batch_variant<kBc1>(es.variant, false, sc, inverse); break;
+    case kBc2: k = batch_variant<kBc2>(es.variant, false, sc, inverse); break;
+    case kBc3: k = batch_variant<kBc3>(es.variant, sa, sc, inverse); break;
+    case kBc4: k = batch_bc45<kBc4>(sa, inverse); break;
+    case kBc5: k = batch_bc45<kBc5>(sa, inverse); break;
     default: return hipErrorInvalidValue;
     }
     hipLaunchKernelGGL(k, dim3(total_wgs), dim3(batch_tile_threads(fmt, sc, inverse)), 0, stream, d_entries, d_index,

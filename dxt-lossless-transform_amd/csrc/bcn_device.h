@@ -32,10 +32,11 @@ constexpr int kThreads = 256;        // element-granular / fill kernels
 //   BC2  64: .80/.81   128: .83/.82   256: .84/.82   512: .82/.79
 //   BC3  64: .71/.72   128: .80/.78   256: .84/.81   512: .82/.80
 // (with plain `nt` stores the optimum was smaller for the inverse: profiles/r01_g_tile_threads_sweep.txt)
+// BC4 (8-byte blocks) starts from BC1's width, BC5 (16-byte blocks, BC3's alpha layout twice) from BC3's (profiles/r07_bc45_*).
 constexpr int default_tile_threads(int fmt, bool inverse)
 {
     (void)inverse;
-    return fmt == kBc1 ? 128 : 256;
+    return fmt == kBc1 || fmt == kBc4 ? 128 : 256;
 }
 
 #ifndef DXTLT_NONTEMPORAL
@@ -124,7 +125,7 @@ __device__ __forceinline__ void for_this_wave(int t, F&& f)
     for_this_wave_from<0, WAVES>(__builtin_amdgcn_readfirstlane(t >> 6), f);
 }
 
-__host__ __device__ constexpr int fmt_block(int fmt) { return fmt == kBc1 ? 8 : 16; }
+__host__ __device__ constexpr int fmt_block(int fmt) { return fmt == kBc1 || fmt == kBc4 ? 8 : 16; }
 // one 16-byte vector per lane: a THREADS-wide workgroup owns THREADS*16 bytes of blocks
 __host__ __device__ constexpr int tile_blocks(int fmt, int threads) { return threads * 16 / fmt_block(fmt); }
 
@@ -190,7 +191,7 @@ __device__ __forceinline__ uint64_t soa_offset_of_lane(int t, uint64_t total_blo
 
 // ------------------------------------------------------------------------------------------------
 // LDS image <-> block registers.  `u` is the index of the lane's 16-byte vector inside the tile.
-// BC1: the vector holds blocks 2u and 2u+1; BC2/BC3: block u.
+// BC1 / BC4: the vector holds blocks 2u and 2u+1; BC2 / BC3 / BC5: block u.
 // ------------------------------------------------------------------------------------------------
 template <typename T>
 __device__ __forceinline__ T& lds_at(uint8_t* lds, int byte_off)
@@ -251,10 +252,53 @@ __device__ __forceinline__ void lds_get_record6(uint8_t* lds, int addr, uint32_t
 #endif
 }
 
+// One BC4 block (an 8-byte BC3 alpha half: a0 a1 i0 i1 | i2 i3 i4 i5 = lo, hi) into the image of a stream table whose endpoint
+// stream(s) start at E * T and whose index stream at (E + 2) * T; `b` = block index inside the tile.  The index record is BC3's.
+template <bool SA, int T, int E>
+__device__ __forceinline__ void scatter_bc4_half(uint8_t* lds, int b, uint32_t lo, uint32_t hi)
+{
+    if constexpr (SA) {
+        lds_at<uint8_t>(lds, E * T + b) = (uint8_t)lo;
+        lds_at<uint8_t>(lds, (E + 1) * T + b) = (uint8_t)(lo >> 8);
+    } else {
+        lds_at<uint16_t>(lds, E * T + 2 * b) = (uint16_t)lo;
+    }
+    lds_put_record6(lds, (E + 2) * T + 6 * b, lo >> 16, hi);
+}
+
+template <bool SA, int T, int E>
+__device__ __forceinline__ void gather_bc4_half(uint8_t* lds, int b, uint32_t& lo, uint32_t& hi)
+{
+    uint32_t a01;
+    if constexpr (SA)
+        a01 = (uint32_t)lds_at<uint8_t>(lds, E * T + b) | ((uint32_t)lds_at<uint8_t>(lds, (E + 1) * T + b) << 8);
+    else
+        a01 = lds_at<uint16_t>(lds, E * T + 2 * b);
+    uint32_t i01;
+    lds_get_record6(lds, (E + 2) * T + 6 * b, i01, hi);
+    lo = a01 | (i01 << 16);
+}
+
 template <int FMT, int VARIANT, bool SA, bool SC, int T>
 __device__ __forceinline__ void scatter_to_image(uint8_t* lds, int u, u32x4 q)
 {
-    if constexpr (FMT == kBc1) {
+    if constexpr (FMT == kBc4) {
+        // q = { block 2u: a0 a1 i0 i1, i2..i5, block 2u+1: a0 a1 i0 i1, i2..i5 }
+        if constexpr (SA) {
+            lds_at<uint16_t>(lds, 0 * T + 2 * u) = (uint16_t)((q.x & 0xFFu) | ((q.z & 0xFFu) << 8));
+            lds_at<uint16_t>(lds, 1 * T + 2 * u) = (uint16_t)(((q.x >> 8) & 0xFFu) | (q.z & 0xFF00u));
+        } else {
+            lds_at<uint32_t>(lds, 0 * T + 4 * u) = (q.x & 0xFFFFu) | (q.z << 16);
+        }
+        // the two 6-byte records are 12 contiguous, 4-byte aligned bytes: three aligned dwords
+        lds_at<uint32_t>(lds, 2 * T + 12 * u + 0) = (q.x >> 16) | (q.y << 16);
+        lds_at<uint32_t>(lds, 2 * T + 12 * u + 4) = (q.y >> 16) | (q.z & 0xFFFF0000u);
+        lds_at<uint32_t>(lds, 2 * T + 12 * u + 8) = q.w;
+    } else if constexpr (FMT == kBc5) {
+        // q = { red: a0 a1 i0 i1, i2..i5, green: a0 a1 i0 i1, i2..i5 }
+        scatter_bc4_half<SA, T, 0>(lds, u, q.x, q.y);
+        scatter_bc4_half<SA, T, 8>(lds, u, q.z, q.w);
+    } else if constexpr (FMT == kBc1) {
         // q = { colours A, indices A, colours B, indices B }
         const uint32_t ca = decorrelate2<VARIANT>(q.x);
         const uint32_t cb = decorrelate2<VARIANT>(q.z);
@@ -300,7 +344,27 @@ template <int FMT, int VARIANT, bool SA, bool SC, int T>
 __device__ __forceinline__ u32x4 gather_from_image(uint8_t* lds, int u)
 {
     u32x4 q;
-    if constexpr (FMT == kBc1) {
+    if constexpr (FMT == kBc4) {
+        uint32_t e;   // endpoints of block 2u (low half) and 2u+1 (high half)
+        if constexpr (SA) {
+            const uint32_t a0 = lds_at<uint16_t>(lds, 0 * T + 2 * u), a1 = lds_at<uint16_t>(lds, 1 * T + 2 * u);
+            e = (a0 & 0xFFu) | ((a1 & 0xFFu) << 8) | ((a0 & 0xFF00u) << 8) | ((a1 & 0xFF00u) << 16);
+        } else {
+            e = lds_at<uint32_t>(lds, 0 * T + 4 * u);
+        }
+        const uint32_t r0 = lds_at<uint32_t>(lds, 2 * T + 12 * u + 0);
+        const uint32_t r1 = lds_at<uint32_t>(lds, 2 * T + 12 * u + 4);
+        const uint32_t r2 = lds_at<uint32_t>(lds, 2 * T + 12 * u + 8);
+        q.x = (e & 0xFFFFu) | (r0 << 16);
+        q.y = (r0 >> 16) | (r1 << 16);
+        q.z = (e >> 16) | (r1 & 0xFFFF0000u);
+        q.w = r2;
+    } else if constexpr (FMT == kBc5) {
+        uint32_t rlo, rhi, glo, ghi;
+        gather_bc4_half<SA, T, 0>(lds, u, rlo, rhi);
+        gather_bc4_half<SA, T, 8>(lds, u, glo, ghi);
+        q = u32x4{rlo, rhi, glo, ghi};
+    } else if constexpr (FMT == kBc1) {
         uint32_t ca, cb;
         if constexpr (SC) {
             const uint32_t c0 = lds_at<uint32_t>(lds, 0 * T + 4 * u);
@@ -698,7 +762,52 @@ struct FieldStreams {
     static constexpr int col = FMT == kBc1 ? 0 : FMT == kBc2 ? 1 : (SA ? 3 : 2);  // c0 or (c0,c1)
     static constexpr int c1 = col + 1;                                    // split colours
     static constexpr int idx = col + (SC ? 2 : 1);
+    // BC4 / BC5: the (red) half uses alpha, a1, aidx; BC5's green half these
+    static constexpr int galpha = aidx + 1;
+    static constexpr int ga1 = galpha + 1;
+    static constexpr int gaidx = SA ? galpha + 2 : galpha + 1;
 };
+
+// One BC4 block (lo, hi as in scatter_bc4_half) into the shifted image, at block index `b`; stream indices ALPHA, A1, AIDX.
+// NAT: every shift a multiple of its element width (the 2-byte endpoint pair and the index record's halfwords are then aligned).
+template <bool SA, bool NAT, int ALPHA, int A1, int AIDX>
+__device__ __forceinline__ void scatter_shifted_bc4_block(uint8_t* lds, int b, uint32_t lo, uint32_t hi, const int (&base)[6])
+{
+    if constexpr (SA) {
+        lds_put<1>(lds, base[ALPHA] + b, lo & 0xFF);
+        lds_put<1>(lds, base[A1] + b, (lo >> 8) & 0xFF);
+    } else {
+        lds_put<2, NAT>(lds, base[ALPHA] + 2 * b, lo & 0xFFFF);
+    }
+    if constexpr (NAT && DXTLT_BC3_RECORD6) {
+        lds_put_record6(lds, base[AIDX] + 6 * b, lo >> 16, hi);   // (an even address: the shift is natural)
+    } else {
+        lds_put<2, NAT>(lds, base[AIDX] + 6 * b + 0, lo >> 16);
+        lds_put<2, NAT>(lds, base[AIDX] + 6 * b + 2, hi & 0xFFFF);
+        lds_put<2, NAT>(lds, base[AIDX] + 6 * b + 4, hi >> 16);
+    }
+}
+
+template <bool SA, bool NAT, int ALPHA, int A1, int AIDX>
+__device__ __forceinline__ void gather_shifted_bc4_block(uint8_t* lds, int b, uint32_t& lo, uint32_t& hi, const int (&base)[6])
+{
+    uint32_t a01;
+    if constexpr (SA)
+        a01 = (uint32_t)lds_get<1>(lds, base[ALPHA] + b) | ((uint32_t)lds_get<1>(lds, base[A1] + b) << 8);
+    else
+        a01 = (uint32_t)lds_get<2, NAT>(lds, base[ALPHA] + 2 * b);
+    if constexpr (NAT && DXTLT_BC3_RECORD6) {
+        uint32_t i01;
+        lds_get_record6(lds, base[AIDX] + 6 * b, i01, hi);   // (reads up to 2 bytes past the record: the next record or the padding)
+        lo = a01 | (i01 << 16);
+    } else {
+        const uint32_t i01 = (uint32_t)lds_get<2, NAT>(lds, base[AIDX] + 6 * b + 0);
+        const uint32_t i23 = (uint32_t)lds_get<2, NAT>(lds, base[AIDX] + 6 * b + 2);
+        const uint32_t i45 = (uint32_t)lds_get<2, NAT>(lds, base[AIDX] + 6 * b + 4);
+        lo = a01 | (i01 << 16);
+        hi = i23 | (i45 << 16);
+    }
+}
 
 // NAT (Shifts::natural): every stream's shift is a multiple of its element width, so each element goes out as one aligned
 // DS instruction and the per-access alignment switch disappears.  BC1 then writes its two blocks' fields separately
@@ -707,7 +816,13 @@ template <int FMT, int VARIANT, bool SA, bool SC, bool NAT>
 __device__ __forceinline__ void scatter_shifted(uint8_t* lds, int u, u32x4 q, const int (&base)[6])
 {
     using F = FieldStreams<FMT, SA, SC>;
-    if constexpr (FMT == kBc1) {
+    if constexpr (FMT == kBc4) {
+        scatter_shifted_bc4_block<SA, NAT, F::alpha, F::a1, F::aidx>(lds, 2 * u, q.x, q.y, base);
+        scatter_shifted_bc4_block<SA, NAT, F::alpha, F::a1, F::aidx>(lds, 2 * u + 1, q.z, q.w, base);
+    } else if constexpr (FMT == kBc5) {
+        scatter_shifted_bc4_block<SA, NAT, F::alpha, F::a1, F::aidx>(lds, u, q.x, q.y, base);
+        scatter_shifted_bc4_block<SA, NAT, F::galpha, F::ga1, F::gaidx>(lds, u, q.z, q.w, base);
+    } else if constexpr (FMT == kBc1) {
         const uint32_t ca = decorrelate2<VARIANT>(q.x);
         const uint32_t cb = decorrelate2<VARIANT>(q.z);
         if constexpr (NAT) {
@@ -765,7 +880,17 @@ __device__ __forceinline__ u32x4 gather_shifted(uint8_t* lds, int u, const int (
 {
     using F = FieldStreams<FMT, SA, SC>;
     u32x4 q;
-    if constexpr (FMT == kBc1) {
+    if constexpr (FMT == kBc4 || FMT == kBc5) {
+        // BC4: blocks 2u and 2u + 1 of one stream table half; BC5: block u's red half, then its green half
+        constexpr bool two = FMT == kBc4;
+        uint32_t alo, ahi, blo, bhi;
+        gather_shifted_bc4_block<SA, NAT, F::alpha, F::a1, F::aidx>(lds, two ? 2 * u : u, alo, ahi, base);
+        if constexpr (two)
+            gather_shifted_bc4_block<SA, NAT, F::alpha, F::a1, F::aidx>(lds, 2 * u + 1, blo, bhi, base);
+        else
+            gather_shifted_bc4_block<SA, NAT, F::galpha, F::ga1, F::gaidx>(lds, u, blo, bhi, base);
+        q = u32x4{alo, ahi, blo, bhi};
+    } else if constexpr (FMT == kBc1) {
         uint32_t ca, cb;
         uint64_t idx;
         if constexpr (NAT) {

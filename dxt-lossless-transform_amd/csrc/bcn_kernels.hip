@@ -170,6 +170,13 @@ KernelSet bc1_norm_kernels()
     return ks;
 }
 
+// BC4 / BC5: no decorrelation, no colour split, no normalisation -- VARIANT 0 and SC false only, the endpoint split picks the kernels
+template <int FMT>
+KernelSet pick_bc45(bool split_endpoints, bool inverse)
+{
+    return split_endpoints ? kernels_for<FMT, kNone, true, false>(inverse) : kernels_for<FMT, kNone, false, false>(inverse);
+}
+
 template <int NORM>
 KernelSet pick_bc1_norm(int variant, bool sc)
 {
@@ -322,9 +329,11 @@ int aligned_tile_threads(Format fmt, bool inverse, bool normalizing, const Launc
 int debug_plan_transform(Format fmt, bool inverse, const Settings& s, uint64_t src_address, uint64_t dst_address, const Range& r,
                          const LaunchTuning* tuning, DebugPlannedLaunch* out, int cap)
 {
-    if (s.variant < 0 || s.variant > 3 || r.first_block + r.num_blocks > r.total_blocks || (fmt != kBc1 && fmt != kBc2 && fmt != kBc3))
+    if (s.variant < 0 || s.variant > 3 || r.first_block + r.num_blocks > r.total_blocks ||
+        (fmt != kBc1 && fmt != kBc2 && fmt != kBc3 && fmt != kBc4 && fmt != kBc5))
         return -1;
-    const bool sa = fmt == kBc3 && s.split_alpha, sc = s.split_colour;
+    const Settings es = effective_settings(fmt, s);
+    const bool sa = es.split_alpha, sc = es.split_colour;
     const int force_bits = (tuning ? tuning->force_generic : 0) & kForceMask & (2 | 0x20);   // (the product's levers)
     const void* soa = reinterpret_cast<const void*>(static_cast<uintptr_t>(inverse ? src_address : dst_address));
     int n = 0;
@@ -357,11 +366,12 @@ int debug_plan_transform(Format fmt, bool inverse, const Settings& s, uint64_t s
     return n;
 }
 
-hipError_t launch_transform(Format fmt, bool inverse, const Settings& s, const void* src, void* dst,
+hipError_t launch_transform(Format fmt, bool inverse, const Settings& s_arg, const void* src, void* dst,
                             const Range& r, hipStream_t stream, const LaunchTuning* tuning)
 {
     if (r.num_blocks == 0)
         return hipSuccess;
+    const Settings s = effective_settings(fmt, s_arg);   // (BC4 / BC5: variant and colour split do not apply)
     if (s.variant < 0 || s.variant > 3 || r.first_block + r.num_blocks > r.total_blocks)
         return hipErrorInvalidValue;
     if (s.normalize != kNormNone && (fmt != kBc1 || inverse || s.normalize < 0 || s.normalize > kNormTransparentOnly))
@@ -380,7 +390,7 @@ hipError_t launch_transform(Format fmt, bool inverse, const Settings& s, const v
         return hipSuccess;
     }
 
-    const bool sa = (fmt == kBc3) && s.split_alpha;
+    const bool sa = s.split_alpha;
     const bool sc = s.split_colour;
     const bool normalizing = s.normalize != kNormNone;
     KernelSet ks;
@@ -393,6 +403,8 @@ hipError_t launch_transform(Format fmt, bool inverse, const Settings& s, const v
         break;
     case kBc2: ks = pick_variant<kBc2>(s.variant, false, sc, inverse); break;
     case kBc3: ks = pick_variant<kBc3>(s.variant, sa, sc, inverse); break;
+    case kBc4: ks = pick_bc45<kBc4>(sa, inverse); break;
+    case kBc5: ks = pick_bc45<kBc5>(sa, inverse); break;
     default: return hipErrorInvalidValue;
     }
 
@@ -514,21 +526,24 @@ hipError_t launch_transform(Format fmt, bool inverse, const Settings& s, const v
 // decode are scalar instructions every wave of a workgroup executes on the one scalar unit a CU's four SIMDs share: 0.80
 // against 0.835 of peak on one 1 GiB BC3 buffer, profiles/r03_batch_spacing.txt).  Returns hipErrorNotSupported when the
 // array does not fit that shape (the caller then takes the batch kernel).
-hipError_t launch_tiled_array(Format fmt, bool inverse, const Settings& s, const void* first_src, void* first_dst,
+hipError_t launch_tiled_array(Format fmt, bool inverse, const Settings& s_arg, const void* first_src, void* first_dst,
                               uint64_t blocks, uint32_t n_buffers, int64_t src_stride, int64_t dst_stride, hipStream_t stream)
 {
+    const Settings s = effective_settings(fmt, s_arg);
     const int threads = default_tile_threads(fmt, inverse);
     const uint64_t T = (uint64_t)tile_blocks(fmt, threads);
     // (HIP refuses a launch of 2^32 threads or more)
     if (n_buffers == 0 || n_buffers > 65535 || blocks == 0 || blocks % T != 0 || blocks / T > 0x7FFFFFFFull ||
         (blocks / T) * n_buffers * (uint64_t)threads >= (1ull << 32))
         return hipErrorNotSupported;
-    const bool sa = fmt == kBc3 && s.split_alpha, sc = s.split_colour;
+    const bool sa = s.split_alpha, sc = s.split_colour;
     KernelSet ks;
     switch (fmt) {
     case kBc1: ks = pick_variant<kBc1>(s.variant, false, sc, inverse); break;
     case kBc2: ks = pick_variant<kBc2>(s.variant, false, sc, inverse); break;
     case kBc3: ks = pick_variant<kBc3>(s.variant, sa, sc, inverse); break;
+    case kBc4: ks = pick_bc45<kBc4>(sa, inverse); break;
+    case kBc5: ks = pick_bc45<kBc5>(sa, inverse); break;
     default: return hipErrorInvalidValue;
     }
     hipLaunchKernelGGL(ks.tiled[threads_slot(threads)], dim3((unsigned)(blocks / T), n_buffers), dim3(threads), 0, stream,

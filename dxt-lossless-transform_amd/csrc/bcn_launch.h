@@ -20,12 +20,14 @@ inline const char* experiment_env(const char* name)
 #endif
 }
 
-enum Format : int { kBc1 = 1, kBc2 = 2, kBc3 = 3 };
+// kBc4 / kBc5: this build's BC4 / BC5 layout (docs/BC45_FORMAT.md) -- a BC4 block is the alpha half of a BC3 block, a BC5 block
+// two of them (red, green)
+enum Format : int { kBc1 = 1, kBc2 = 2, kBc3 = 3, kBc4 = 4, kBc5 = 5 };
 
 struct Settings {
-    int variant;        // core YCoCgVariant numbering: 0 None, 1..3
-    bool split_alpha;   // BC3 only
-    bool split_colour;
+    int variant;        // core YCoCgVariant numbering: 0 None, 1..3 (BC4 / BC5: ignored, always 0)
+    bool split_alpha;   // BC3; BC4 / BC5: split_endpoints
+    bool split_colour;  // BC1 / BC2 / BC3 only
     int normalize = 0;  // BC1 forward only: ColorNormalizationMode 0 None, 1 Color0Only, 2 ReplicateColor (fused)
 };
 
@@ -180,7 +182,23 @@ bool build_batch_index(const BatchEntry* entries, size_t n_entries, uint32_t tot
 hipError_t launch_tiled_array(Format fmt, bool inverse, const Settings& s, const void* first_src, void* first_dst,
                               uint64_t blocks, uint32_t n_buffers, int64_t src_stride, int64_t dst_stride, hipStream_t stream);
 
-inline int block_bytes(Format f) { return f == kBc1 ? 8 : 16; }
+inline int block_bytes(Format f) { return f == kBc1 || f == kBc4 ? 8 : 16; }
+
+// The formats whose settings carry an alpha-endpoint split (BC4 / BC5: split_endpoints travels in the same field) and the formats
+// with colour endpoints (a colour split and a decorrelation mode).  BC4 / BC5 run with VARIANT 0, no colour split, no normalisation.
+constexpr bool format_has_alpha_split(int fmt) { return fmt == kBc3 || fmt == kBc4 || fmt == kBc5; }
+constexpr bool format_has_colour(int fmt) { return fmt == kBc1 || fmt == kBc2 || fmt == kBc3; }
+// The settings a format's kernels are instantiated with: what does not apply to the format is cleared
+inline Settings effective_settings(Format f, const Settings& s)
+{
+    Settings e = s;
+    e.split_alpha = format_has_alpha_split(f) && s.split_alpha;
+    if (!format_has_colour(f)) {
+        e.variant = 0;
+        e.split_colour = false;
+    }
+    return e;
+}
 
 // ------------------------------------------------------------------------------------------------
 // Stream table.  A transformed buffer is a concatenation of streams; stream s holds `width` bytes per
@@ -189,7 +207,9 @@ inline int block_bytes(Format f) { return f == kBc1 ? 8 : 16; }
 //   BC1  split: c0 2@0, c1 2@2, idx 4@4          no split: colours 4@0, idx 4@4
 //   BC2  alpha 8@0, then colours at 8 (2+2 or 4), idx 4@12
 //   BC3  alpha endpoints at 0 (1+1 or 2), alpha indices 6@2, colours at 8 (2+2 or 4), idx 4@12
-// (reference: bc1 transform_with_settings.rs:43-58, bc2 :43-46, bc3 :54-56,76-80)
+//   BC4  endpoints at 0 (1+1 or 2), indices 6@2
+//   BC5  red endpoints at 0 (1+1 or 2), red indices 6@2, green endpoints at 8 (1+1 or 2), green indices 6@10
+// (reference: bc1 transform_with_settings.rs:43-58, bc2 :43-46, bc3 :54-56,76-80; BC4 / BC5: docs/BC45_FORMAT.md)
 // ------------------------------------------------------------------------------------------------
 struct Streams {
     int n;
@@ -201,6 +221,19 @@ constexpr Streams make_streams(int fmt, bool split_alpha, bool split_colour)
 {
     Streams s{};
     int n = 0, off = 0;
+    if (fmt == kBc4 || fmt == kBc5) {   // one or two BC3 alpha halves, nothing else
+        for (int h = 0; h < (fmt == kBc5 ? 2 : 1); ++h) {
+            if (split_alpha) {
+                s.width[n] = 1; s.off[n] = off; off += 1; ++n;
+                s.width[n] = 1; s.off[n] = off; off += 1; ++n;
+            } else {
+                s.width[n] = 2; s.off[n] = off; off += 2; ++n;
+            }
+            s.width[n] = 6; s.off[n] = off; off += 6; ++n;
+        }
+        s.n = n;
+        return s;
+    }
     if (fmt == kBc3) {
         if (split_alpha) {
             s.width[n] = 1; s.off[n] = off; off += 1; ++n;

@@ -2,6 +2,7 @@
 // host-pointer staging path, the device-pointer path and the single-process multi-GPU shard path.
 // All arithmetic lives in bcn_kernels.hip; nothing here touches block bytes on the CPU.
 #include "../../include/dxtlt_gfx950.h"
+#include "../../include/dxtlt_bc45.h"
 
 #include <hip/hip_runtime_api.h>
 
@@ -66,13 +67,16 @@ dxtlt::LaunchTuning current_tuning()
     return t;
 }
 
+// BC4 / BC5 (formats 4, 5; include/dxtlt_bc45.h) have no colour endpoints: their decorrelation mode and colour split are ignored
+inline bool ignores_colour_settings(int32_t format) { return !dxtlt::format_has_colour(format); }
+
 int32_t check_common(int32_t format, size_t len, uint8_t mode, const void* a, const void* b)
 {
-    if (format < 1 || format > 3)
-        return fail(DXTLT_E_INVALID_ARGUMENT, "format must be 1 (BC1), 2 (BC2) or 3 (BC3)");
+    if (format < 1 || format > 5)
+        return fail(DXTLT_E_INVALID_ARGUMENT, "format must be 1 (BC1), 2 (BC2), 3 (BC3), 4 (BC4) or 5 (BC5)");
     if (len % (size_t)dxtlt::block_bytes((Format)format) != 0)
         return fail(DXTLT_E_INVALID_LENGTH, "len is not a multiple of the block size");
-    if (mode > 3)
+    if (mode > 3 && !ignores_colour_settings(format))
         return fail(DXTLT_E_INVALID_ARGUMENT, "decorrelation_mode must be 0..3");
     if (len > 0 && (a == nullptr || b == nullptr))
         return fail(DXTLT_E_INVALID_ARGUMENT, "NULL buffer with len > 0");
@@ -82,8 +86,10 @@ int32_t check_common(int32_t format, size_t len, uint8_t mode, const void* a, co
 int32_t device_range(int32_t format, bool inverse, const void* d_src, void* d_dst, uint64_t total, uint64_t first,
                      uint64_t num, uint8_t mode, bool sa, bool sc, hipStream_t stream, uint8_t normalize = 0)
 {
-    if (format < 1 || format > 3)
-        return fail(DXTLT_E_INVALID_ARGUMENT, "format must be 1 (BC1), 2 (BC2) or 3 (BC3)");
+    if (format < 1 || format > 5)
+        return fail(DXTLT_E_INVALID_ARGUMENT, "format must be 1 (BC1), 2 (BC2), 3 (BC3), 4 (BC4) or 5 (BC5)");
+    if (ignores_colour_settings(format))
+        mode = 0, sc = false;
     if (mode > 3)
         return fail(DXTLT_E_INVALID_ARGUMENT, "decorrelation_mode must be 0..3");
     if (first > total || num > total - first)
@@ -241,7 +247,7 @@ inline uint64_t pipeline_chunk_bytes(uint64_t len, int32_t format)
 {
     if (kPipelineChunkOverride)
         return kPipelineChunkOverride;
-    return (format == 3 || len >= (256ull << 20)) ? (32ull << 20) : (16ull << 20);
+    return (format >= 3 || len >= (256ull << 20)) ? (32ull << 20) : (16ull << 20);   // (BC4 / BC5: streams of 1/8 of the data too)
 }
 std::atomic<int> g_host_pipeline{1};
 
@@ -291,7 +297,8 @@ int32_t pipelined_range(const PipeJob& j)
             S.width[s] = width[s];
         }
     } else {
-        const dxtlt::Streams bs = dxtlt::make_streams(j.format, j.format == 3 && j.sa, j.sc);
+        const dxtlt::Streams bs = dxtlt::make_streams(j.format, dxtlt::format_has_alpha_split(j.format) && j.sa,
+                                                      dxtlt::format_has_colour(j.format) && j.sc);
         S.n = bs.n;
         for (int s = 0; s < bs.n; ++s) {
             S.off[s] = bs.off[s];
@@ -688,7 +695,7 @@ int32_t shard_worker(int dev, int32_t format, bool inverse, const uint8_t* in, u
         return DXTLT_OK;
     const uint64_t B = (uint64_t)dxtlt::block_bytes((Format)format);
     const size_t bytes = (size_t)(sp.count * B);
-    const dxtlt::Streams S = dxtlt::make_streams(format, format == 3 && sa, sc);
+    const dxtlt::Streams S = dxtlt::make_streams(format, dxtlt::format_has_alpha_split(format) && sa, dxtlt::format_has_colour(format) && sc);
     HIP_TRY(hipSetDevice(dev), "hipSetDevice");
     hipError_t acquire_err = hipSuccess;
     ShardCtx* ctx = shard_ctx_acquire(dev, bytes, &acquire_err);
@@ -853,6 +860,40 @@ int32_t dxtlt_transform_range_device(int32_t format, bool inverse, const void* d
                         (hipStream_t)stream);
 }
 
+// ---- BC4 / BC5 (include/dxtlt_bc45.h): formats 4 and 5 of the same paths, split_endpoints in the alpha split ----------
+int32_t dxtlt_transform_bc4_with_settings(const uint8_t* i, uint8_t* o, size_t len, bool split_endpoints)
+{
+    return host_call(4, false, i, o, len, 0, split_endpoints, false);
+}
+int32_t dxtlt_untransform_bc4_with_settings(const uint8_t* i, uint8_t* o, size_t len, bool split_endpoints)
+{
+    return host_call(4, true, i, o, len, 0, split_endpoints, false);
+}
+int32_t dxtlt_transform_bc5_with_settings(const uint8_t* i, uint8_t* o, size_t len, bool split_endpoints)
+{
+    return host_call(5, false, i, o, len, 0, split_endpoints, false);
+}
+int32_t dxtlt_untransform_bc5_with_settings(const uint8_t* i, uint8_t* o, size_t len, bool split_endpoints)
+{
+    return host_call(5, true, i, o, len, 0, split_endpoints, false);
+}
+int32_t dxtlt_transform_bc4_with_settings_device(const void* i, void* o, size_t len, bool split_endpoints, void* st)
+{
+    return device_whole(4, false, i, o, len, 0, split_endpoints, false, st);
+}
+int32_t dxtlt_untransform_bc4_with_settings_device(const void* i, void* o, size_t len, bool split_endpoints, void* st)
+{
+    return device_whole(4, true, i, o, len, 0, split_endpoints, false, st);
+}
+int32_t dxtlt_transform_bc5_with_settings_device(const void* i, void* o, size_t len, bool split_endpoints, void* st)
+{
+    return device_whole(5, false, i, o, len, 0, split_endpoints, false, st);
+}
+int32_t dxtlt_untransform_bc5_with_settings_device(const void* i, void* o, size_t len, bool split_endpoints, void* st)
+{
+    return device_whole(5, true, i, o, len, 0, split_endpoints, false, st);
+}
+
 // ---- single-process multi-GPU ---------------------------------------------------------------------------
 int32_t dxtlt_transform_sharded(int32_t format, bool inverse, const uint8_t* in, uint8_t* out, size_t len,
                                 uint8_t mode, bool sa, bool sc, int32_t num_devices)
@@ -972,7 +1013,7 @@ int32_t dxtlt_debug_plan_transform(int32_t format, int32_t inverse, int32_t vari
                                    uint64_t src_address, uint64_t dst_address, uint64_t total_blocks, uint64_t first_block,
                                    uint64_t num_blocks, DxtltDebugPlannedLaunch* out, int32_t cap)
 {
-    if (format < 1 || format > 3 || cap < 0 || (cap > 0 && out == nullptr) || first_block > total_blocks || num_blocks > total_blocks - first_block)
+    if (format < 1 || format > 5 || cap < 0 || (cap > 0 && out == nullptr) || first_block > total_blocks || num_blocks > total_blocks - first_block)
         return -1;
     std::vector<dxtlt::DebugPlannedLaunch> tmp((size_t)cap);
     const Settings s{variant, split_alpha != 0, split_colour != 0, 0};

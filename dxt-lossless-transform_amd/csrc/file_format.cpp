@@ -204,6 +204,39 @@ constexpr uint32_t kBc7VendorTag = 0xD175u;    // data bits 27..12
 constexpr uint32_t kBc7FormatVersion = 2u;     // data bits 11..0: docs/BC7_FORMAT.md version
 constexpr uint32_t kBc7PrivateHeader = (uint32_t)DXTLT_TF_BC7 | (((kBc7VendorTag << 12) | kBc7FormatVersion) << 4);
 
+// BC4 / BC5 payloads: refused as upstream unless the caller opts in to this build's layout (include/dxtlt_bc45.h,
+// docs/BC45_FORMAT.md).  Upstream has reserved TransformFormat::Bc4 = 8 / Bc5 = 9 with placeholder data bits (version:2 |
+// split_endpoints:1 | reserved:25), so the word written here sets reserved bits -- a layout version and the vendor tag of the
+// BC7 words -- that upstream's unpack refuses: such a file is rejected there, never misread.
+std::atomic<bool> g_bc45_enabled{false};
+constexpr uint32_t kBc45VendorTag = 0xD175u;   // data bits 27..12
+constexpr uint32_t kBc45LayoutVersion = 1u;    // data bits 11..3: docs/BC45_FORMAT.md version
+inline uint32_t bc45_header(int32_t code, bool split)
+{
+    return (uint32_t)code | (((kBc45VendorTag << 12) | (kBc45LayoutVersion << 3) | ((split ? 1u : 0u) << 2)) << 4);
+}
+// the library's format code (4 / 5) of a BC4 / BC5 DDS payload with the switch on, else 0
+int dds_to_bc45(uint8_t fmt)
+{
+    if (!g_bc45_enabled.load(std::memory_order_relaxed))
+        return 0;
+    return fmt == BC4 ? 4 : fmt == BC5 ? 5 : 0;
+}
+// a header this build wrote for a BC4 / BC5 payload (switch on): the library's format code and split_endpoints.  0: not such a
+// format code (or the switch is off); -1: a BC4 / BC5 code whose data bits are not one of the two tagged words
+int bc45_of_header(uint32_t header, bool* split)
+{
+    const uint32_t code = header & 0xFu;
+    if (!g_bc45_enabled.load(std::memory_order_relaxed) || (code != DXTLT_TF_BC4 && code != DXTLT_TF_BC5))
+        return 0;
+    for (int k = 0; k < 2; ++k)
+        if (header == bc45_header((int32_t)code, k != 0)) {
+            *split = k != 0;
+            return code == DXTLT_TF_BC4 ? 4 : 5;
+        }
+    return -1;
+}
+
 int32_t dds_transform_common(const uint8_t* input, size_t input_len, uint8_t* output, size_t output_len,
                              const DltSizeEstimator* estimator, bool use_all, uint8_t mode, bool sa, bool sc)
 {
@@ -228,6 +261,25 @@ int32_t dds_transform_common(const uint8_t* input, size_t input_len, uint8_t* ou
         if (input_len > off + length)
             std::memcpy(output + off + length, input + off + length, input_len - off - length);
         wr32(output, kBc7PrivateHeader);
+        return DXTLT_FF_OK;
+    }
+    if (const int f45 = dds_to_bc45(info.Format); f45 != 0) {
+        if (length % (f45 == 4 ? 8 : 16) != 0)
+            return DXTLT_FF_INVALID_DATA_ALIGNMENT;
+        std::memcpy(output, input, off);
+        int32_t st45;
+        if (estimator != nullptr) {
+            dxtlt_host::AutoChoice c{};
+            st45 = dxtlt_host::transform_auto_bc45(f45, input + off, output + off, length, estimator, &c);
+            sa = c.split_alpha;
+        } else {
+            st45 = dxtlt_host::transform(f45, false, input + off, output + off, length, 0, sa, false);
+        }
+        if (st45 != dxtlt_host::kOk)
+            return map_device_status(st45);
+        if (input_len > off + length)
+            std::memcpy(output + off + length, input + off + length, input_len - off - length);
+        wr32(output, bc45_header(f45 == 4 ? DXTLT_TF_BC4 : DXTLT_TF_BC5, sa));
         return DXTLT_FF_OK;
     }
     const int bcn = dds_to_bcn(info.Format);
@@ -349,6 +401,15 @@ int32_t dxtlt_transform_header_unpack_reserved_format(uint32_t header, int32_t* 
 
 void dxtlt_file_formats_enable_bc7(bool enabled) { g_bc7_enabled.store(enabled, std::memory_order_relaxed); }
 
+void dxtlt_file_formats_enable_bc45(bool enabled) { g_bc45_enabled.store(enabled, std::memory_order_relaxed); }
+
+uint32_t dxtlt_transform_header_pack_bc45(int32_t transform_format, bool split_endpoints)
+{
+    if (transform_format != DXTLT_TF_BC4 && transform_format != DXTLT_TF_BC5)
+        return 0;
+    return bc45_header(transform_format, split_endpoints);
+}
+
 bool is_dds(const uint8_t* ptr, size_t len)
 {
     if (ptr == nullptr || len == 0)
@@ -418,6 +479,21 @@ int32_t dxtlt_dds_untransform(const uint8_t* input, size_t input_len, uint8_t* o
             std::memcpy(output + off + length, input + off + length, input_len - off - length);
         return DXTLT_FF_OK;
     }
+    bool split45 = false;
+    if (const int f45 = bc45_of_header(header, &split45); f45 != 0) {
+        if (f45 < 0)
+            return DXTLT_FF_CORRUPTED_EMBEDDED_DATA;   // not one of this build's two words (upstream's layouts are its own to assign)
+        if (length % (f45 == 4 ? 8 : 16) != 0)
+            return DXTLT_FF_INVALID_DATA_ALIGNMENT;
+        wr32(output, kDdsMagic);
+        std::memcpy(output + 4, input + 4, off - 4);
+        const int32_t st45 = dxtlt_host::transform(f45, true, input + off, output + off, length, 0, split45, false);
+        if (st45 != dxtlt_host::kOk)
+            return map_device_status(st45);
+        if (input_len > off + length)
+            std::memcpy(output + off + length, input + off + length, input_len - off - length);
+        return DXTLT_FF_OK;
+    }
     if ((header & 0xF) > DXTLT_TF_BC3)
         return DXTLT_FF_UNKNOWN_TRANSFORM_FORMAT;
     int32_t rc = dxtlt_transform_header_unpack(header, &tf, &mode, &sa, &sc);
@@ -478,7 +554,13 @@ size_t dxtlt_dds_transform_batch(DxtltDdsBatchItem* items, size_t count, bool in
         uint32_t first_word;
         if (!inverse) {
             bcn = dds_to_bcn(info.Format);
-            if (info.Format == BC7 && g_bc7_enabled.load(std::memory_order_relaxed)) {
+            if (const int f45 = dds_to_bc45(info.Format); f45 != 0) {
+                bcn = f45;   // opt-in: this build's BC4 / BC5 layout; split_alpha_endpoints carries split_endpoints
+                if (length % (f45 == 4 ? 8 : 16) != 0) { reject(DXTLT_FF_INVALID_DATA_ALIGNMENT); continue; }
+                mode = 0;
+                sc = false;
+                first_word = bc45_header(f45 == 4 ? DXTLT_TF_BC4 : DXTLT_TF_BC5, sa);
+            } else if (info.Format == BC7 && g_bc7_enabled.load(std::memory_order_relaxed)) {
                 bcn = 7;   // opt-in: this build's own format, no settings; rides in the same batch
                 if (length % 16 != 0) { reject(DXTLT_FF_INVALID_DATA_ALIGNMENT); continue; }
                 mode = 0;
@@ -494,7 +576,16 @@ size_t dxtlt_dds_transform_batch(DxtltDdsBatchItem* items, size_t count, bool in
             }
         } else {
             const uint32_t header = rd32(it.input);
-            if ((header & 0xF) == DXTLT_TF_BC7 && g_bc7_enabled.load(std::memory_order_relaxed)) {
+            bool split45 = false;
+            const int f45 = bc45_of_header(header, &split45);
+            if (f45 < 0) { reject(DXTLT_FF_CORRUPTED_EMBEDDED_DATA); continue; }
+            if (f45 != 0) {
+                if (length % (f45 == 4 ? 8 : 16) != 0) { reject(DXTLT_FF_INVALID_DATA_ALIGNMENT); continue; }
+                bcn = f45;
+                mode = 0;
+                sa = split45;
+                sc = false;
+            } else if ((header & 0xF) == DXTLT_TF_BC7 && g_bc7_enabled.load(std::memory_order_relaxed)) {
                 if (header != kBc7PrivateHeader) { reject(DXTLT_FF_CORRUPTED_EMBEDDED_DATA); continue; }
                 if (length % 16 != 0) { reject(DXTLT_FF_INVALID_DATA_ALIGNMENT); continue; }
                 bcn = 7;

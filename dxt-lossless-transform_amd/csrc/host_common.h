@@ -94,5 +94,8 @@ struct AutoChoice {
 // transform_bcN_auto on host pointers (see auto_transform.cpp).
 int32_t transform_auto(int32_t format, const uint8_t* in, uint8_t* out, size_t len, const DltSizeEstimator* estimator,
                        bool use_all_decorrelation_modes, AutoChoice* choice);
+// dxtlt_transform_bc{4,5}_auto on host pointers, format 4 or 5 (auto_transform.cpp): choice->split_alpha = split_endpoints
+int32_t transform_auto_bc45(int32_t format, const uint8_t* in, uint8_t* out, size_t len, const DltSizeEstimator* estimator,
+                            AutoChoice* choice);
 
 }  // namespace dxtlt_host

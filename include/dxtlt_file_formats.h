@@ -138,6 +138,20 @@ int32_t dxtlt_dds_untransform(const uint8_t *input, size_t input_len, uint8_t *o
  * build can read such files back. */
 void dxtlt_file_formats_enable_bc7(bool enabled);
 
+/* ADDITIVE, off by default (process-wide), like the BC7 switch.  Upstream reserves TransformFormat::Bc4 = 8 / Bc5 = 9 and a
+ * placeholder settings struct (embed/formats/bc4.rs, bc5.rs: split_endpoints) but defines no transform; with this switch off the
+ * DDS calls refuse BC4 / BC5 payloads (DXTLT_FF_UNKNOWN_TRANSFORM_FORMAT) exactly as before.  With it on, dxtlt_dds_transform,
+ * _auto, _untransform and dxtlt_dds_transform_batch take BC4 (ATI1, BC4U, BC4S, DXGI 79-81) and BC5 (ATI2, BC5U, BC5S, DXGI 82-84)
+ * payloads through this build's layout (dxtlt_bc45.h, docs/BC45_FORMAT.md); `split_alpha_endpoints` carries split_endpoints and
+ * the decorrelation mode and colour split are ignored.  The header's 28 data bits follow the BC7 precedent so that upstream never
+ * misreads such a file: bits 0-1 upstream's placeholder version 0, bit 2 split_endpoints, bits 11..3 this build's layout version
+ * (1), bits 27..12 the vendor tag 0xD175.  Upstream's unpack -- and dxtlt_transform_header_unpack_reserved_format -- reject the
+ * word (its reserved bits are not zero); dxtlt_dds_untransform accepts exactly the two tagged words per format and nothing else
+ * (DXTLT_FF_CORRUPTED_EMBEDDED_DATA).  Only this build can read such files back. */
+void dxtlt_file_formats_enable_bc45(bool enabled);
+/* The tagged header word of a BC4 (DXTLT_TF_BC4) or BC5 (DXTLT_TF_BC5) file written with this layout; 0 for any other code. */
+uint32_t dxtlt_transform_header_pack_bc45(int32_t transform_format, bool split_endpoints);
+
 /* ADDITIVE: many DDS files per call -- the file-after-file loop of the reference's CLI
  * (tools/dxt-lossless-transform-cli/src/commands/transform/mod.rs:154-199) over ONE pinned upload / launch / download
  * pipeline (dxtlt_transform_batch_host, dxtlt_gfx950.h) instead of a PCIe round trip per file.  Every item is checked
@@ -153,7 +167,7 @@ typedef struct DxtltDdsBatchItem {
     uint8_t *output;
     size_t output_len;               /* >= input_len */
     uint8_t decorrelation_mode;      /* core numbering; forward only */
-    bool split_alpha_endpoints;      /* BC3, forward only */
+    bool split_alpha_endpoints;      /* BC3 (BC4 / BC5: split_endpoints, with the switch above on), forward only */
     bool split_colour_endpoints;     /* forward only */
     int32_t status;                  /* out: DXTLT_FF_* */
 } DxtltDdsBatchItem;
