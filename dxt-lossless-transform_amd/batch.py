@@ -1,6 +1,7 @@
 """Many device-resident buffers in one call (dxtlt_transform_batch_device, include/dxtlt_gfx950.h): one kernel launch per
 (format, direction) present in the batch, enqueued on torch's current stream.  fmt "bc7" (this build's own format,
-docs/BC7_FORMAT.md; settings ignored, pass None) rides along: its granules in one launch, its tail parts in another."""
+docs/BC7_FORMAT.md; settings ignored, pass None) rides along: its granules in one launch, its tail parts in another; fmt
+"bc6h" (docs/BC6H_FORMAT.md; settings ignored) the same, in launches of its own."""
 from __future__ import annotations
 
 import ctypes as C
@@ -15,6 +16,8 @@ def _item_fields(fmt, settings):
 
     if fmt == "bc7":
         return 7, 16, 0, False, False
+    if fmt == "bc6h":
+        return 6, 16, 0, False, False
     mode, sa, sc = _settings_tuple(fmt, settings)
     return _FMT_ID[fmt], BLOCK_BYTES[fmt], mode, sa, sc
 

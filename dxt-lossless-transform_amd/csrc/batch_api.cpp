@@ -21,8 +21,10 @@
 #include <thread>
 #include <vector>
 
+#include "../../include/dxtlt_bc6h.h"
 #include "../../include/dxtlt_bc7.h"
 #include "../../include/dxtlt_gfx950.h"
+#include "bc6h_launch.h"
 #include "bc7_launch.h"
 #include "bcn_launch.h"
 #include "host_common.h"
@@ -32,7 +34,7 @@ namespace {
 using namespace dxtlt_host;
 using dxtlt::BatchEntry;
 
-// bytes per block of a batch item's format (1..5, 7)
+// bytes per block of a batch item's format (1..7)
 inline uint32_t item_block_bytes(uint8_t format) { return format == 1 || format == 4 ? 8u : 16u; }
 
 // Table staging: a ring of pinned host buffers with device twins.  A slot is reused only after the copy and the kernels that last
@@ -140,8 +142,9 @@ extern "C" int32_t dxtlt_transform_batch_device(const DxtltBatchItem* items, siz
     // validate everything first: a batch is enqueued whole or not at all
     for (size_t i = 0; i < count; ++i) {
         const DxtltBatchItem& it = items[i];
-        if ((it.format < 1 || it.format > 5) && it.format != 7)
-            return fail(kInvalidArgument, "batch item: format must be 1..5 (BC1..BC5) or 7 (BC7, this build's own format)");
+        if (it.format < 1 || it.format > 7)
+            return fail(kInvalidArgument, "batch item: format must be 1..5 (BC1..BC5), 6 (BC6H) or 7 (BC7; 6 and 7 are this build's "
+                                          "own formats)");
         if (it.len % item_block_bytes(it.format) != 0)
             return fail(kInvalidLength, "batch item: len is not a multiple of the block size");
         if (it.decorrelation_mode > 3 && dxtlt::format_has_colour(it.format))
@@ -149,15 +152,17 @@ extern "C" int32_t dxtlt_transform_batch_device(const DxtltBatchItem* items, siz
         if (it.len > 0 && (it.d_input == nullptr || it.d_output == nullptr))
             return fail(kInvalidArgument, "batch item: NULL device buffer with len > 0");
     }
-    // one launch holds fewer than 2^32 threads = 2^24 workgroups of 256 lanes: for BC7 that is 256 GiB of granules per
-    // direction.  Checked here, before anything is enqueued (a batch goes out whole or not at all).
+    // one launch holds fewer than 2^32 threads = 2^24 workgroups of 256 lanes: for BC7 (or BC6H) that is 256 GiB of granules
+    // per direction.  Checked here, before anything is enqueued (a batch goes out whole or not at all).
     {
-        uint64_t granules[2] = {0, 0};
+        uint64_t granules[4] = {0, 0, 0, 0};
         for (size_t i = 0; i < count; ++i)
-            if (items[i].format == 7)
-                granules[items[i].inverse ? 1 : 0] += items[i].len / 16 / 1024;
+            if (items[i].format == 7 || items[i].format == 6)
+                granules[(items[i].format == 6 ? 2 : 0) + (items[i].inverse ? 1 : 0)] += items[i].len / 16 / 1024;
         if (granules[0] > 0xFFFFFFull || granules[1] > 0xFFFFFFull)
             return fail(kInvalidArgument, "batch too large for one launch (256 GiB or more of BC7 in one direction)");
+        if (granules[2] > 0xFFFFFFull || granules[3] > 0xFFFFFFull)
+            return fail(kInvalidArgument, "batch too large for one launch (256 GiB or more of BC6H in one direction)");
     }
     hipStream_t user = static_cast<hipStream_t>(hip_stream);
 
@@ -182,7 +187,7 @@ extern "C" int32_t dxtlt_transform_batch_device(const DxtltBatchItem* items, siz
     std::vector<size_t> singles;   // items the batch kernel does not take (plan_batch_entry): launched alone, behind the batches
     for (size_t i = 0; i < count; ++i) {
         const DxtltBatchItem& it = items[i];
-        if (it.len == 0 || it.format == 7)
+        if (it.len == 0 || it.format == 7 || it.format == 6)
             continue;
         if (it.len >= (size_t(64) << 30))
             return fail(kInvalidArgument, "batch item of 64 GiB or more: use the single-buffer entry point");
@@ -218,20 +223,22 @@ extern "C" int32_t dxtlt_transform_batch_device(const DxtltBatchItem* items, siz
     static const bool no_strided = dxtlt::experiment_env("DXTLT_BATCH_NO_STRIDED") != nullptr;
 
     // BC7 items (format 7; no settings): their granules in one launch per direction, their tail parts in a second one.  Planned
-    // here, staged and launched below with everything else.
+    // here, staged and launched below with everything else.  BC6H items (format 6) the same, in launches of their own: plans
+    // 0, 1 = BC7 forward, inverse; 2, 3 = BC6H forward, inverse.
     struct Bc7Plan {
         std::vector<dxtlt::bc7::BatchEntry> entries, tails;
         std::vector<uint32_t> coarse;
         uint64_t wgs = 0;
         size_t at = 0, entry_bytes = 0, tail_bytes = 0, bytes = 0;
     };
-    Bc7Plan bc7_plans[2];
+    Bc7Plan bc7_plans[4];
     size_t table_bytes = 0;
-    for (int inverse = 0; inverse < 2; ++inverse) {
-        Bc7Plan& p = bc7_plans[inverse];
+    for (int q = 0; q < 4; ++q) {
+        Bc7Plan& p = bc7_plans[q];
+        const int inverse = q & 1, format = q < 2 ? 7 : 6;
         for (size_t i = 0; i < count; ++i) {
             const DxtltBatchItem& it = items[i];
-            if (it.format != 7 || it.len == 0 || (it.inverse != 0) != (inverse != 0))
+            if (it.format != format || it.len == 0 || (it.inverse != 0) != (inverse != 0))
                 continue;
             const uint64_t blocks = it.len / 16, tail = blocks % 1024, main = blocks - tail;
             const uint8_t* src = static_cast<const uint8_t*>(it.d_input);
@@ -300,17 +307,19 @@ extern "C" int32_t dxtlt_transform_batch_device(const DxtltBatchItem* items, siz
         }
         e = upload_table(slot, table_bytes, user);
         const char* what = "batch table copy / launch";
-        for (int inverse = 0; inverse < 2 && e == hipSuccess; ++inverse) {
-            const Bc7Plan& p = bc7_plans[inverse];
+        for (int q = 0; q < 4 && e == hipSuccess; ++q) {
+            const Bc7Plan& p = bc7_plans[q];
+            const int inverse = q & 1;
             if (p.bytes == 0)
                 continue;
             const uint8_t* d = static_cast<const uint8_t*>(slot->dev) + p.at;
-            e = dxtlt::bc7::launch_batch(inverse != 0, reinterpret_cast<const dxtlt::bc7::BatchEntry*>(d),
+            const auto launch_batch = q < 2 ? dxtlt::bc7::launch_batch : dxtlt::bc6h::launch_batch;
+            e = launch_batch(inverse != 0, reinterpret_cast<const dxtlt::bc7::BatchEntry*>(d),
                                          reinterpret_cast<const uint32_t*>(d + p.entry_bytes + p.tail_bytes), (uint32_t)p.entries.size(),
                                          (uint32_t)p.wgs, reinterpret_cast<const dxtlt::bc7::BatchEntry*>(d + p.entry_bytes),
                                          (uint32_t)p.tails.size(), user);
             if (e != hipSuccess)
-                what = "BC7 batch table copy / launch";
+                what = q < 2 ? "BC7 batch table copy / launch" : "BC6H batch table copy / launch";
         }
         for (size_t k = 0; k < placed.size() && e == hipSuccess; ++k) {
             const int gi = placed[k].gi;
@@ -505,8 +514,9 @@ extern "C" int32_t dxtlt_transform_batch_host(const DxtltBatchItem* items, size_
     uint64_t total = 0;
     for (size_t i = 0; i < count; ++i) {
         const DxtltBatchItem& it = items[i];
-        if ((it.format < 1 || it.format > 5) && it.format != 7)
-            return fail(kInvalidArgument, "batch item: format must be 1..5 (BC1..BC5) or 7 (BC7, this build's own format)");
+        if (it.format < 1 || it.format > 7)
+            return fail(kInvalidArgument, "batch item: format must be 1..5 (BC1..BC5), 6 (BC6H) or 7 (BC7; 6 and 7 are this build's "
+                                          "own formats)");
         if (it.len % item_block_bytes(it.format) != 0)
             return fail(kInvalidLength, "batch item: len is not a multiple of the block size");
         if (it.decorrelation_mode > 3 && dxtlt::format_has_colour(it.format))
@@ -537,6 +547,9 @@ extern "C" int32_t dxtlt_transform_batch_host(const DxtltBatchItem* items, size_
         if (it.format == 7)
             rc = it.inverse ? dxtlt_untransform_bc7(static_cast<const uint8_t*>(it.d_input), static_cast<uint8_t*>(it.d_output), it.len)
                             : dxtlt_transform_bc7(static_cast<const uint8_t*>(it.d_input), static_cast<uint8_t*>(it.d_output), it.len);
+        else if (it.format == 6)
+            rc = it.inverse ? dxtlt_untransform_bc6h(static_cast<const uint8_t*>(it.d_input), static_cast<uint8_t*>(it.d_output), it.len)
+                            : dxtlt_transform_bc6h(static_cast<const uint8_t*>(it.d_input), static_cast<uint8_t*>(it.d_output), it.len);
         else
             rc = dxtlt_host::transform(it.format, it.inverse != 0, static_cast<const uint8_t*>(it.d_input),
                                        static_cast<uint8_t*>(it.d_output), it.len, it.decorrelation_mode,

@@ -6,16 +6,31 @@
 
 #include <cstring>
 
+#include "bc6h_launch.h"
 #include "bc7_launch.h"
 #include "host_common.h"
 
 namespace {
 
-int32_t host_call(bool inverse, const uint8_t* in, uint8_t* out, size_t len)
+// format 7 = BC7, 6 = BC6H (include/dxtlt_bc6h.h): the same granules and streams, their own kernels
+hipError_t launch(int format, bool inverse, const void* src, void* dst, uint64_t n_blocks, hipStream_t stream)
+{
+    return format == 6 ? dxtlt::bc6h::launch(inverse, src, dst, n_blocks, stream) : dxtlt::bc7::launch(inverse, src, dst, n_blocks, stream);
+}
+
+const char* length_message(int format)
+{
+    return format == 6 ? "len is not a multiple of 16 (BC6H block size)" : "len is not a multiple of 16 (BC7 block size)";
+}
+
+}  // namespace
+
+int32_t dxtlt_host::granule_host_call(int format, bool inverse, const uint8_t* in, uint8_t* out, size_t len)
 {
     using namespace dxtlt_host;
+    const char* what = format == 6 ? "BC6H transform" : "BC7 transform";
     if (len % 16 != 0)
-        return fail(kInvalidLength, "len is not a multiple of 16 (BC7 block size)");
+        return fail(kInvalidLength, length_message(format));
     if (len == 0)
         return kOk;
     if (in == nullptr || out == nullptr)
@@ -24,10 +39,10 @@ int32_t host_call(bool inverse, const uint8_t* in, uint8_t* out, size_t len)
     // overlap), then the tail part -- a BC7 buffer of its own -- through the one-shot path below
     const uint64_t blocks = len / 16, main_blocks = blocks - blocks % 1024;
     int32_t prc = kOk;
-    if (pipelined_bc7_main(inverse, in, out, main_blocks, &prc)) {
+    if (pipelined_bc7_main(inverse, in, out, main_blocks, &prc, format)) {
         if (prc != kOk || main_blocks == blocks)
             return prc;
-        return host_call(inverse, in + main_blocks * 16, out + main_blocks * 16, (size_t)((blocks - main_blocks) * 16));
+        return granule_host_call(format, inverse, in + main_blocks * 16, out + main_blocks * 16, (size_t)((blocks - main_blocks) * 16));
     }
     // small buffers: the kernel reads and writes mapped pinned staging itself (no copy-engine hand-overs)
     MappedStaging m;
@@ -36,12 +51,12 @@ int32_t host_call(bool inverse, const uint8_t* in, uint8_t* out, size_t len)
         return rc;
     if (m.usable) {
         std::memcpy(m.h_in, in, len);
-        hipError_t e = dxtlt::bc7::launch(inverse, m.d_in, m.d_out, len / 16, m.stream);
+        hipError_t e = launch(format, inverse, m.d_in, m.d_out, len / 16, m.stream);
         const hipError_t drained = hipStreamSynchronize(m.stream);
         if (e == hipSuccess)
             e = drained;
         if (e != hipSuccess)
-            return fail(kDevice, "BC7 transform", e);
+            return fail(kDevice, what, e);
         std::memcpy(out, m.h_out, len);
         return kOk;
     }
@@ -52,7 +67,7 @@ int32_t host_call(bool inverse, const uint8_t* in, uint8_t* out, size_t len)
         return rc;
     hipError_t e = hipMemcpyAsync(d_in, in, len, hipMemcpyHostToDevice, st);
     if (e == hipSuccess)
-        e = dxtlt::bc7::launch(inverse, d_in, d_out, len / 16, st);
+        e = launch(format, inverse, d_in, d_out, len / 16, st);
     if (e == hipSuccess)
         e = hipMemcpyAsync(out, d_out, len, hipMemcpyDeviceToHost, st);
     // drained on every exit: the staging buffers belong to this thread's next call
@@ -60,31 +75,47 @@ int32_t host_call(bool inverse, const uint8_t* in, uint8_t* out, size_t len)
     if (e == hipSuccess)
         e = drained;
     if (e != hipSuccess)
-        return fail(kDevice, "BC7 transform", e);
+        return fail(kDevice, what, e);
     return kOk;
 }
 
-int32_t device_range(bool inverse, const void* d_src, void* d_dst, uint64_t total, uint64_t first, uint64_t num, void* stream)
+int32_t dxtlt_host::granule_device_range(int format, bool inverse, const void* d_src, void* d_dst, uint64_t total, uint64_t first,
+                                         uint64_t num, void* stream)
 {
     using namespace dxtlt_host;
     if (num == 0)
         return kOk;
     if (d_src == nullptr || d_dst == nullptr)
         return fail(kInvalidArgument, "NULL device buffer");
-    hipError_t e = dxtlt::bc7::launch_range(inverse, d_src, d_dst, total, first, num, (hipStream_t)stream);
+    const hipError_t e = format == 6 ? dxtlt::bc6h::launch_range(inverse, d_src, d_dst, total, first, num, (hipStream_t)stream)
+                                     : dxtlt::bc7::launch_range(inverse, d_src, d_dst, total, first, num, (hipStream_t)stream);
     if (e == hipErrorInvalidValue)
-        return fail(kInvalidArgument, "BC7: a range starts on a sort granule (1024 blocks) and ends on one or at the end of the "
-                                      "array");
+        return fail(kInvalidArgument, format == 6 ? "BC6H: a range starts on a sort granule (1024 blocks) and ends on one or at "
+                                                    "the end of the array"
+                                                  : "BC7: a range starts on a sort granule (1024 blocks) and ends on one or at the "
+                                                    "end of the array");
     if (e != hipSuccess)
-        return fail(kDevice, "BC7 kernel launch", e);
+        return fail(kDevice, format == 6 ? "BC6H kernel launch" : "BC7 kernel launch", e);
     return kOk;
+}
+
+namespace {
+
+int32_t host_call(bool inverse, const uint8_t* in, uint8_t* out, size_t len)
+{
+    return dxtlt_host::granule_host_call(7, inverse, in, out, len);
+}
+
+int32_t device_range(bool inverse, const void* d_src, void* d_dst, uint64_t total, uint64_t first, uint64_t num, void* stream)
+{
+    return dxtlt_host::granule_device_range(7, inverse, d_src, d_dst, total, first, num, stream);
 }
 
 int32_t device_call(bool inverse, const void* d_in, void* d_out, size_t len, void* stream)
 {
     using namespace dxtlt_host;
     if (len % 16 != 0)
-        return fail(kInvalidLength, "len is not a multiple of 16 (BC7 block size)");
+        return fail(kInvalidLength, length_message(7));
     return device_range(inverse, d_in, d_out, len / 16, 0, len / 16, stream);
 }
 

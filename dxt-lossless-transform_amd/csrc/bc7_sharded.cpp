@@ -15,6 +15,7 @@
 #include "../../include/dxtlt_bc7.h"
 #include "../../include/dxtlt_gfx950.h"
 #include "bc7_fields.h"
+#include "bc6h_launch.h"
 #include "bc7_launch.h"
 #include "host_common.h"
 
@@ -31,12 +32,21 @@ struct Piece {
 };
 
 // pieces 0..7: the shard's slice of every main stream; piece 8: the tail part (last shard only, else empty)
-int32_t pieces_for(uint64_t total_blocks, uint64_t first_block, uint64_t num_blocks, Piece (&p)[9])
+// format 7 = BC7, 6 = BC6H (include/dxtlt_bc6h.h): the same granules and streams, their own kernels
+const char* name_of(int format) { return format == 6 ? "BC6H" : "BC7"; }
+
+hipError_t launch(int format, bool inverse, const void* src, void* dst, uint64_t n_blocks, hipStream_t stream)
+{
+    return format == 6 ? dxtlt::bc6h::launch(inverse, src, dst, n_blocks, stream) : dxtlt::bc7::launch(inverse, src, dst, n_blocks, stream);
+}
+
+int32_t pieces_for(int format, uint64_t total_blocks, uint64_t first_block, uint64_t num_blocks, Piece (&p)[9])
 {
     const uint64_t main_total = total_blocks - total_blocks % kT;
     if (first_block % kT != 0 || first_block > total_blocks || num_blocks > total_blocks - first_block ||
         ((first_block + num_blocks) % kT != 0 && first_block + num_blocks != total_blocks))
-        return fail(kInvalidArgument, "BC7 shard: a shard starts on a sort granule (1024 blocks) and ends on one or at the end");
+        return fail(kInvalidArgument, (std::string(name_of(format)) +
+                                       " shard: a shard starts on a sort granule (1024 blocks) and ends on one or at the end").c_str());
     const uint64_t end = first_block + num_blocks;
     const uint64_t main_count = first_block >= main_total ? 0 : (end > main_total ? main_total : end) - first_block;
     for (int s = 0; s < 8; ++s)
@@ -65,12 +75,12 @@ std::vector<Shard> plan(uint64_t total_blocks, int shards)
     return p;
 }
 
-int32_t shard_worker(int dev, bool inverse, const uint8_t* in, uint8_t* out, uint64_t total_blocks, Shard sh)
+int32_t shard_worker(int format, int dev, bool inverse, const uint8_t* in, uint8_t* out, uint64_t total_blocks, Shard sh)
 {
     if (sh.count == 0)
         return kOk;
     Piece pc[9];
-    if (int32_t rc = pieces_for(total_blocks, sh.first, sh.count, pc); rc != kOk)
+    if (int32_t rc = pieces_for(format, total_blocks, sh.first, sh.count, pc); rc != kOk)
         return rc;
     const size_t bytes = (size_t)sh.count * 16;
     hipError_t e = hipSetDevice(dev);
@@ -93,7 +103,7 @@ int32_t shard_worker(int dev, bool inverse, const uint8_t* in, uint8_t* out, uin
     const uint64_t main_total = total_blocks - total_blocks % 1024;
     const uint64_t in_main = sh.first >= main_total ? 0 : std::min<uint64_t>(sh.first + sh.count, main_total) - sh.first;
     int32_t prc = kOk;
-    if (in_main != 0 && pipelined_bc7_shard(sb, dev, inverse, in, out, main_total, sh.first, in_main, &prc)) {
+    if (in_main != 0 && pipelined_bc7_shard(sb, dev, inverse, in, out, main_total, sh.first, in_main, &prc, format)) {
         if (prc != kOk)
             return done(prc);
         const uint64_t tail = sh.count - in_main;   // blocks of the array's tail part
@@ -102,20 +112,20 @@ int32_t shard_worker(int dev, bool inverse, const uint8_t* in, uint8_t* out, uin
             uint8_t* dst = out + main_total * 16;
             e = hipMemcpyAsync(d_a, src, (size_t)tail * 16, hipMemcpyHostToDevice, st);
             if (e == hipSuccess)
-                e = dxtlt::bc7::launch(inverse, d_a, d_b, tail, st);
+                e = launch(format, inverse, d_a, d_b, tail, st);
             if (e == hipSuccess)
                 e = hipMemcpyAsync(dst, d_b, (size_t)tail * 16, hipMemcpyDeviceToHost, st);
             if (e == hipSuccess)
                 e = hipStreamSynchronize(st);
             if (e != hipSuccess)
-                return done(fail(kDevice, "BC7 shard tail part", e));
+                return done(fail(kDevice, format == 6 ? "BC6H shard tail part" : "BC7 shard tail part", e));
         }
         return done(kOk);
     }
     if (!inverse) {
         e = hipMemcpyAsync(d_a, in + sh.first * 16, bytes, hipMemcpyHostToDevice, st);
         if (e == hipSuccess)
-            e = dxtlt::bc7::launch(false, d_a, d_b, sh.count, st);   // stand-alone: its streams are the shard's slices, packed
+            e = launch(format, false, d_a, d_b, sh.count, st);   // stand-alone: its streams are the shard's slices, packed
         for (int p = 0; p < 9 && e == hipSuccess; ++p)
             if (pc[p].bytes)
                 e = hipMemcpyAsync(out + pc[p].global_off, (const uint8_t*)d_b + pc[p].local_off, (size_t)pc[p].bytes,
@@ -126,21 +136,23 @@ int32_t shard_worker(int dev, bool inverse, const uint8_t* in, uint8_t* out, uin
                 e = hipMemcpyAsync((uint8_t*)d_a + pc[p].local_off, in + pc[p].global_off, (size_t)pc[p].bytes,
                                    hipMemcpyHostToDevice, st);
         if (e == hipSuccess)
-            e = dxtlt::bc7::launch(true, d_a, d_b, sh.count, st);
+            e = launch(format, true, d_a, d_b, sh.count, st);
         if (e == hipSuccess)
             e = hipMemcpyAsync(out + sh.first * 16, d_b, bytes, hipMemcpyDeviceToHost, st);
     }
     if (e == hipSuccess)
         e = hipStreamSynchronize(st);
     if (e != hipSuccess)
-        return done(fail(kDevice, "BC7 shard copy/launch", e));
+        return done(fail(kDevice, format == 6 ? "BC6H shard copy/launch" : "BC7 shard copy/launch", e));
     return done(kOk);
 }
 
-int32_t sharded(bool inverse, const uint8_t* in, uint8_t* out, size_t len, int32_t num_shards)
+}  // namespace
+
+int32_t dxtlt_host::granule_sharded(int format, bool inverse, const uint8_t* in, uint8_t* out, size_t len, int32_t num_shards)
 {
     if (len % 16 != 0)
-        return fail(kInvalidLength, "len is not a multiple of 16 (BC7 block size)");
+        return fail(kInvalidLength, format == 6 ? "len is not a multiple of 16 (BC6H block size)" : "len is not a multiple of 16 (BC7 block size)");
     if (len == 0)
         return kOk;
     if (in == nullptr || out == nullptr)
@@ -166,7 +178,7 @@ int32_t sharded(bool inverse, const uint8_t* in, uint8_t* out, size_t len, int32
         try {
             threads.emplace_back([&, s] {
                 (void)dxtlt_host::bind_this_thread_near_device(s % count);   // the library's own thread: next to its device
-                codes[(size_t)s] = shard_worker(s % count, inverse, in, out, total, pl[(size_t)s]);
+                codes[(size_t)s] = shard_worker(format, s % count, inverse, in, out, total, pl[(size_t)s]);
                 if (codes[(size_t)s] != kOk)
                     msgs[(size_t)s] = dxtlt_last_error();
             });
@@ -186,27 +198,13 @@ int32_t sharded(bool inverse, const uint8_t* in, uint8_t* out, size_t len, int32
     return kOk;
 }
 
-}  // namespace
-
-extern "C" {
-
-int32_t dxtlt_transform_bc7_sharded(const uint8_t* input_ptr, uint8_t* output_ptr, size_t len, int32_t num_shards)
-{
-    return sharded(false, input_ptr, output_ptr, len, num_shards);
-}
-
-int32_t dxtlt_untransform_bc7_sharded(const uint8_t* input_ptr, uint8_t* output_ptr, size_t len, int32_t num_shards)
-{
-    return sharded(true, input_ptr, output_ptr, len, num_shards);
-}
-
-int32_t dxtlt_bc7_shard_pieces(uint64_t total_blocks, uint64_t first_block, uint64_t num_blocks, uint64_t* global_off,
-                               uint64_t* local_off, uint64_t* bytes)
+int32_t dxtlt_host::granule_shard_pieces(int format, uint64_t total_blocks, uint64_t first_block, uint64_t num_blocks,
+                                         uint64_t* global_off, uint64_t* local_off, uint64_t* bytes)
 {
     if (global_off == nullptr || local_off == nullptr || bytes == nullptr)
-        return fail(kInvalidArgument, "dxtlt_bc7_shard_pieces: NULL output array");
+        return fail(kInvalidArgument, format == 6 ? "dxtlt_bc6h_shard_pieces: NULL output array" : "dxtlt_bc7_shard_pieces: NULL output array");
     Piece pc[9];
-    if (int32_t rc = pieces_for(total_blocks, first_block, num_blocks, pc); rc != kOk)
+    if (int32_t rc = pieces_for(format, total_blocks, first_block, num_blocks, pc); rc != kOk)
         return rc;
     for (int p = 0; p < 9; ++p) {
         global_off[p] = pc[p].global_off;
@@ -214,6 +212,24 @@ int32_t dxtlt_bc7_shard_pieces(uint64_t total_blocks, uint64_t first_block, uint
         bytes[p] = pc[p].bytes;
     }
     return kOk;
+}
+
+extern "C" {
+
+int32_t dxtlt_transform_bc7_sharded(const uint8_t* input_ptr, uint8_t* output_ptr, size_t len, int32_t num_shards)
+{
+    return dxtlt_host::granule_sharded(7, false, input_ptr, output_ptr, len, num_shards);
+}
+
+int32_t dxtlt_untransform_bc7_sharded(const uint8_t* input_ptr, uint8_t* output_ptr, size_t len, int32_t num_shards)
+{
+    return dxtlt_host::granule_sharded(7, true, input_ptr, output_ptr, len, num_shards);
+}
+
+int32_t dxtlt_bc7_shard_pieces(uint64_t total_blocks, uint64_t first_block, uint64_t num_blocks, uint64_t* global_off,
+                               uint64_t* local_off, uint64_t* bytes)
+{
+    return dxtlt_host::granule_shard_pieces(7, total_blocks, first_block, num_blocks, global_off, local_off, bytes);
 }
 
 uint32_t dxtlt_bc7_sort_granule(void) { return (uint32_t)kT; }

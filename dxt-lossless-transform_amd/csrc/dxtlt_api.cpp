@@ -19,6 +19,7 @@
 #include <thread>
 #include <vector>
 
+#include "bc6h_launch.h"
 #include "bc7_launch.h"
 #include "bcn_launch.h"
 #include "host_common.h"
@@ -282,8 +283,9 @@ struct PipeJob {
 int32_t pipelined_range(const PipeJob& j)
 {
     // format 7 = the main part of a BC7 buffer (include/dxtlt_bc7.h): eight streams over whole 1024-block granules, chunks
-    // are granule multiples, the kernels are the BC7 range launches; everything else is the same pipeline
-    const bool bc7 = j.format == 7;
+    // are granule multiples, the kernels are the BC7 range launches; everything else is the same pipeline.  Format 6 = the
+    // same for BC6H (include/dxtlt_bc6h.h), with its own kernels
+    const bool bc7 = j.format == 7 || j.format == 6;
     const uint64_t B = bc7 ? 16 : (uint64_t)dxtlt::block_bytes((Format)j.format);
     struct {
         int n;
@@ -308,6 +310,10 @@ int32_t pipelined_range(const PipeJob& j)
     auto launch = [&](bool inv, const void* src, void* dst, uint64_t range_total, uint64_t range_first, uint64_t range_count) -> int32_t {
         if (!bc7)
             return device_range(j.format, inv, src, dst, range_total, range_first, range_count, j.mode, j.sa, j.sc, j.up, inv ? 0 : j.normalize);
+        if (j.format == 6) {
+            const hipError_t e = dxtlt::bc6h::launch_range(inv, src, dst, range_total, range_first, range_count, j.up);
+            return e == hipSuccess ? DXTLT_OK : fail(DXTLT_E_DEVICE, "BC6H kernel launch", e);
+        }
         const hipError_t e = dxtlt::bc7::launch_range(inv, src, dst, range_total, range_first, range_count, j.up);
         return e == hipSuccess ? DXTLT_OK : fail(DXTLT_E_DEVICE, "BC7 kernel launch", e);
     };
@@ -423,7 +429,7 @@ int32_t pipelined_transform(HostCtx& c, int32_t format, bool inverse, const uint
 }  // namespace
 
 // The main part (whole granules) of a large BC7 host buffer through the chunked pipeline; false = too small / switched off
-bool dxtlt_host::pipelined_bc7_main(bool inverse, const uint8_t* in, uint8_t* out, uint64_t main_blocks, int32_t* rc)
+bool dxtlt_host::pipelined_bc7_main(bool inverse, const uint8_t* in, uint8_t* out, uint64_t main_blocks, int32_t* rc, int format)
 {
     const uint64_t bytes = main_blocks * 16;
     if (bytes < kPipelineMinBytes || g_host_pipeline.load(std::memory_order_relaxed) == 0)
@@ -436,7 +442,7 @@ bool dxtlt_host::pipelined_bc7_main(bool inverse, const uint8_t* in, uint8_t* ou
     // one-shot path below 1 GiB; 32 MiB: 30 / 34 / 37 GiB/s at 128 / 256 / 512 MiB; 64 MiB: 40-41 from 1 GiB up;
     // tools/bc7_host_bench.py)
     const uint64_t chunk = kPipelineChunkOverride ? kPipelineChunkOverride : bytes >= (1ull << 30) ? (64ull << 20) : (32ull << 20);
-    PipeJob j{c.device, c.stream, c.d_in, c.d_out, 7, inverse, in, out, main_blocks, 0, main_blocks, 0, false, false, 0, chunk};
+    PipeJob j{c.device, c.stream, c.d_in, c.d_out, (int32_t)format, inverse, in, out, main_blocks, 0, main_blocks, 0, false, false, 0, chunk};
     *rc = pipelined_range(j);
     return true;
 }
@@ -774,13 +780,13 @@ void dxtlt_host::init_runtime_for_devices(int devices)
 }
 
 bool dxtlt_host::pipelined_bc7_shard(const ShardBuffers& sb, int dev, bool inverse, const uint8_t* in, uint8_t* out,
-                                     uint64_t total_main, uint64_t first, uint64_t count, int32_t* rc)
+                                     uint64_t total_main, uint64_t first, uint64_t count, int32_t* rc, int format)
 {
     const uint64_t bytes = count * 16;
     if (bytes < kPipelineMinBytes || g_host_pipeline.load(std::memory_order_relaxed) == 0)
         return false;
     const uint64_t chunk = kPipelineChunkOverride ? kPipelineChunkOverride : bytes >= (1ull << 30) ? (64ull << 20) : (32ull << 20);
-    PipeJob j{dev, sb.stream, sb.a, sb.b, 7, inverse, in, out, total_main, first, count, 0, false, false, 0, chunk};
+    PipeJob j{dev, sb.stream, sb.a, sb.b, (int32_t)format, inverse, in, out, total_main, first, count, 0, false, false, 0, chunk};
     *rc = pipelined_range(j);
     return true;
 }

@@ -10,6 +10,7 @@
 #include "../../include/dxtlt_gfx950.h"
 
 #include "host_common.h"
+#include "../../include/dxtlt_bc6h.h"
 #include "../../include/dxtlt_bc7.h"
 
 namespace {
@@ -204,6 +205,23 @@ constexpr uint32_t kBc7VendorTag = 0xD175u;    // data bits 27..12
 constexpr uint32_t kBc7FormatVersion = 2u;     // data bits 11..0: docs/BC7_FORMAT.md version
 constexpr uint32_t kBc7PrivateHeader = (uint32_t)DXTLT_TF_BC7 | (((kBc7VendorTag << 12) | kBc7FormatVersion) << 4);
 
+// BC6H payloads (DXGI 94-96): refused as upstream (its handler answers FormatNotImplemented(Bc6H)) unless the caller opts in
+// to this build's own format (include/dxtlt_bc6h.h, docs/BC6H_FORMAT.md).  The header word follows the BC7 scheme:
+// TransformFormat::Bc6H = 4, the vendor tag in data bits 27..12 and the layout version in bits 11..0; nothing else is
+// accepted on the way back.
+std::atomic<bool> g_bc6h_enabled{false};
+constexpr uint32_t kBc6hLayoutVersion = 1u;    // data bits 11..0: docs/BC6H_FORMAT.md version
+constexpr uint32_t kBc6hPrivateHeader = (uint32_t)DXTLT_TF_BC6H | (((kBc7VendorTag << 12) | kBc6hLayoutVersion) << 4);
+// BC6H (6) or BC7 (7) for a DDS payload format whose switch is on, else 0
+int dds_to_granule_format(uint8_t fmt)
+{
+    if (fmt == BC7 && g_bc7_enabled.load(std::memory_order_relaxed))
+        return 7;
+    if (fmt == BC6H && g_bc6h_enabled.load(std::memory_order_relaxed))
+        return 6;
+    return 0;
+}
+
 // BC4 / BC5 payloads: refused as upstream unless the caller opts in to this build's layout (include/dxtlt_bc45.h,
 // docs/BC45_FORMAT.md).  Upstream has reserved TransformFormat::Bc4 = 8 / Bc5 = 9 with placeholder data bits (version:2 |
 // split_endpoints:1 | reserved:25), so the word written here sets reserved bits -- a layout version and the vendor tag of the
@@ -250,17 +268,18 @@ int32_t dds_transform_common(const uint8_t* input, size_t input_len, uint8_t* ou
     const size_t off = info.DataOffset, length = info.DataLength;
     if (input_len < off + length)
         return DXTLT_FF_INPUT_TOO_SHORT;
-    if (info.Format == BC7 && g_bc7_enabled.load(std::memory_order_relaxed)) {
-        // no settings and nothing to estimate: the format has one layout
+    if (const int g = dds_to_granule_format(info.Format); g != 0) {
+        // BC7 / BC6H: no settings and nothing to estimate, the format has one layout
         if (length % 16 != 0)
             return DXTLT_FF_INVALID_DATA_ALIGNMENT;
         std::memcpy(output, input, off);
-        const int32_t st7 = dxtlt_transform_bc7(input + off, output + off, length);
+        const int32_t st7 = g == 6 ? dxtlt_transform_bc6h(input + off, output + off, length)
+                                   : dxtlt_transform_bc7(input + off, output + off, length);
         if (st7 != dxtlt_host::kOk)
             return map_device_status(st7);
         if (input_len > off + length)
             std::memcpy(output + off + length, input + off + length, input_len - off - length);
-        wr32(output, kBc7PrivateHeader);
+        wr32(output, g == 6 ? kBc6hPrivateHeader : kBc7PrivateHeader);
         return DXTLT_FF_OK;
     }
     if (const int f45 = dds_to_bc45(info.Format); f45 != 0) {
@@ -401,6 +420,10 @@ int32_t dxtlt_transform_header_unpack_reserved_format(uint32_t header, int32_t* 
 
 void dxtlt_file_formats_enable_bc7(bool enabled) { g_bc7_enabled.store(enabled, std::memory_order_relaxed); }
 
+void dxtlt_file_formats_enable_bc6h(bool enabled) { g_bc6h_enabled.store(enabled, std::memory_order_relaxed); }
+
+uint32_t dxtlt_transform_header_pack_bc6h(void) { return kBc6hPrivateHeader; }
+
 void dxtlt_file_formats_enable_bc45(bool enabled) { g_bc45_enabled.store(enabled, std::memory_order_relaxed); }
 
 uint32_t dxtlt_transform_header_pack_bc45(int32_t transform_format, bool split_endpoints)
@@ -465,14 +488,16 @@ int32_t dxtlt_dds_untransform(const uint8_t* input, size_t input_len, uint8_t* o
     uint8_t mode = 0;
     bool sa = false, sc = false;
     // dispatch_untransform (handlers/dispatch.rs:39-): format first, then the details, then the alignment
-    if ((header & 0xF) == DXTLT_TF_BC7 && g_bc7_enabled.load(std::memory_order_relaxed)) {
-        if (header != kBc7PrivateHeader)
+    const bool bc6h = (header & 0xF) == DXTLT_TF_BC6H && g_bc6h_enabled.load(std::memory_order_relaxed);
+    if (bc6h || ((header & 0xF) == DXTLT_TF_BC7 && g_bc7_enabled.load(std::memory_order_relaxed))) {
+        if (header != (bc6h ? kBc6hPrivateHeader : kBc7PrivateHeader))
             return DXTLT_FF_CORRUPTED_EMBEDDED_DATA;  // not this build's tag + version (all-zero data bits: upstream's to assign)
         if (length % 16 != 0)
             return DXTLT_FF_INVALID_DATA_ALIGNMENT;
         wr32(output, kDdsMagic);
         std::memcpy(output + 4, input + 4, off - 4);
-        const int32_t st7 = dxtlt_untransform_bc7(input + off, output + off, length);
+        const int32_t st7 = bc6h ? dxtlt_untransform_bc6h(input + off, output + off, length)
+                                 : dxtlt_untransform_bc7(input + off, output + off, length);
         if (st7 != dxtlt_host::kOk)
             return map_device_status(st7);
         if (input_len > off + length)
@@ -518,8 +543,8 @@ int32_t dxtlt_dds_untransform(const uint8_t* input, size_t input_len, uint8_t* o
 // commands/transform/mod.rs:154-199) with ONE upload / launch / download pipeline under it (dxtlt_transform_batch_host)
 // instead of a PCIe round trip per file.  Every item is checked exactly like the single-file calls and gets their
 // status; items that pass have their header and trailing bytes copied, their payloads go through the batch together,
-// and their TransformHeader (or 'DDS ' magic) is written once the batch has succeeded.  BC7 files (with the switch on)
-// ride in the same batch as format 7.
+// and their TransformHeader (or 'DDS ' magic) is written once the batch has succeeded.  BC7 and BC6H files (with their
+// switches on) ride in the same batch as formats 7 and 6.
 // ---------------------------------------------------------------------------------------------------------------
 size_t dxtlt_dds_transform_batch(DxtltDdsBatchItem* items, size_t count, bool inverse)
 {
@@ -560,12 +585,12 @@ size_t dxtlt_dds_transform_batch(DxtltDdsBatchItem* items, size_t count, bool in
                 mode = 0;
                 sc = false;
                 first_word = bc45_header(f45 == 4 ? DXTLT_TF_BC4 : DXTLT_TF_BC5, sa);
-            } else if (info.Format == BC7 && g_bc7_enabled.load(std::memory_order_relaxed)) {
-                bcn = 7;   // opt-in: this build's own format, no settings; rides in the same batch
+            } else if (const int g = dds_to_granule_format(info.Format); g != 0) {
+                bcn = g;   // opt-in: this build's own BC7 / BC6H format, no settings; rides in the same batch
                 if (length % 16 != 0) { reject(DXTLT_FF_INVALID_DATA_ALIGNMENT); continue; }
                 mode = 0;
                 sa = sc = false;
-                first_word = kBc7PrivateHeader;
+                first_word = g == 6 ? kBc6hPrivateHeader : kBc7PrivateHeader;
             } else {
                 if (bcn == 0) { reject(DXTLT_FF_UNKNOWN_TRANSFORM_FORMAT); continue; }
                 if (length % (bcn == 1 ? 8 : 16) != 0) { reject(DXTLT_FF_INVALID_DATA_ALIGNMENT); continue; }
@@ -585,10 +610,11 @@ size_t dxtlt_dds_transform_batch(DxtltDdsBatchItem* items, size_t count, bool in
                 mode = 0;
                 sa = split45;
                 sc = false;
-            } else if ((header & 0xF) == DXTLT_TF_BC7 && g_bc7_enabled.load(std::memory_order_relaxed)) {
-                if (header != kBc7PrivateHeader) { reject(DXTLT_FF_CORRUPTED_EMBEDDED_DATA); continue; }
+            } else if (const bool bc6h = (header & 0xF) == DXTLT_TF_BC6H && g_bc6h_enabled.load(std::memory_order_relaxed);
+                       bc6h || ((header & 0xF) == DXTLT_TF_BC7 && g_bc7_enabled.load(std::memory_order_relaxed))) {
+                if (header != (bc6h ? kBc6hPrivateHeader : kBc7PrivateHeader)) { reject(DXTLT_FF_CORRUPTED_EMBEDDED_DATA); continue; }
                 if (length % 16 != 0) { reject(DXTLT_FF_INVALID_DATA_ALIGNMENT); continue; }
-                bcn = 7;
+                bcn = bc6h ? 6 : 7;
                 mode = 0;
                 sa = sc = false;
             } else {

@@ -28,6 +28,7 @@
 
 #include "dxtlt_bc1_normalize.h"
 #include "dxtlt_bc23_normalize.h"
+#include "dxtlt_bc6h.h"
 #include "dxtlt_bc7.h"
 #include "dxtlt_color565.h"
 #include "dxtlt_decode.h"
@@ -578,6 +579,30 @@ private:
         if (e.is_err())
             return e;
         detail::check_device(inverse ? dxtlt_untransform_bc7(input, output, input_len) : dxtlt_transform_bc7(input, output, input_len));
+        return e;
+    }
+};
+
+// ADDITIVE: the same builder shape for this build's BC6H transform (docs/BC6H_FORMAT.md; upstream has no BC6H transform).
+// The format has no settings, hence no setters and no auto builder.
+class Bc6hManualTransformBuilder {
+public:
+    Error transform(const uint8_t* input, size_t input_len, uint8_t* output, size_t output_len) const
+    {
+        return run(false, input, input_len, output, output_len);
+    }
+    Error untransform(const uint8_t* input, size_t input_len, uint8_t* output, size_t output_len) const
+    {
+        return run(true, input, input_len, output, output_len);
+    }
+
+private:
+    static Error run(bool inverse, const uint8_t* input, size_t input_len, uint8_t* output, size_t output_len)
+    {
+        Error e = Error::from(core::detail_safe::validate(input_len, output_len, 16));
+        if (e.is_err())
+            return e;
+        detail::check_device(inverse ? dxtlt_untransform_bc6h(input, output, input_len) : dxtlt_transform_bc6h(input, output, input_len));
         return e;
     }
 };

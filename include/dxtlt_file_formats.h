@@ -138,6 +138,17 @@ int32_t dxtlt_dds_untransform(const uint8_t *input, size_t input_len, uint8_t *o
  * build can read such files back. */
 void dxtlt_file_formats_enable_bc7(bool enabled);
 
+/* ADDITIVE, off by default (process-wide), like the BC7 switch.  Upstream parses BC6H DDS files (DXGI 94-96) but its handler
+ * answers FormatNotImplemented(Bc6H); with this switch off the DDS calls refuse BC6H payloads
+ * (DXTLT_FF_UNKNOWN_TRANSFORM_FORMAT) exactly as before.  With it on, dxtlt_dds_transform, _auto, _untransform and
+ * dxtlt_dds_transform_batch take UF16, SF16 and typeless BC6H payloads through this build's own format (dxtlt_bc6h.h,
+ * docs/BC6H_FORMAT.md; no settings, so _auto uses the one layout).  The header carries TransformFormat::Bc6H = 4 with the
+ * BC7 scheme's data bits: vendor tag 0xD175 (bits 27..12) and layout version 1 (bits 11..0); dxtlt_dds_untransform accepts
+ * exactly that word (else DXTLT_FF_CORRUPTED_EMBEDDED_DATA).  Only this build can read such files back. */
+void dxtlt_file_formats_enable_bc6h(bool enabled);
+/* The header word of a BC6H file written with this build's format. */
+uint32_t dxtlt_transform_header_pack_bc6h(void);
+
 /* ADDITIVE, off by default (process-wide), like the BC7 switch.  Upstream reserves TransformFormat::Bc4 = 8 / Bc5 = 9 and a
  * placeholder settings struct (embed/formats/bc4.rs, bc5.rs: split_endpoints) but defines no transform; with this switch off the
  * DDS calls refuse BC4 / BC5 payloads (DXTLT_FF_UNKNOWN_TRANSFORM_FORMAT) exactly as before.  With it on, dxtlt_dds_transform,

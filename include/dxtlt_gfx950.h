@@ -166,7 +166,9 @@ typedef struct DxtltBatchItem {
     void *d_output;
     uint64_t len;                   /* bytes, a multiple of the block size */
     uint8_t format;                 /* 1, 2, 3 = BC1, BC2, BC3; 7 = BC7 in this build's own format (dxtlt_bc7.h; settings ignored):
-                                       its granules go in one launch per direction, its tail parts in a second one */
+                                       its granules go in one launch per direction, its tail parts in a second one;
+                                       6 = BC6H in this build's own format (dxtlt_bc6h.h; settings ignored), the same
+                                       way in launches of its own */
     uint8_t inverse;                /* 0 = transform, 1 = untransform */
     uint8_t decorrelation_mode;     /* core numbering */
     uint8_t split_alpha_endpoints;  /* BC3 only */
