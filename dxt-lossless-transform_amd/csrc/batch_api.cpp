@@ -21,12 +21,9 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/dxtlt_bc6h.h"
-#include "../../include/dxtlt_bc7.h"
 #include "../../include/dxtlt_gfx950.h"
-#include "bc6h_launch.h"
-#include "bc7_launch.h"
 #include "bcn_launch.h"
+#include "granule_launch.h"
 #include "host_common.h"
 
 namespace {
@@ -154,15 +151,13 @@ extern "C" int32_t dxtlt_transform_batch_device(const DxtltBatchItem* items, siz
     }
     // one launch holds fewer than 2^32 threads = 2^24 workgroups of 256 lanes: for BC7 (or BC6H) that is 256 GiB of granules
     // per direction.  Checked here, before anything is enqueued (a batch goes out whole or not at all).
-    {
-        uint64_t granules[4] = {0, 0, 0, 0};
+    for (const int format : {7, 6}) {
+        uint64_t granules[2] = {0, 0};
         for (size_t i = 0; i < count; ++i)
-            if (items[i].format == 7 || items[i].format == 6)
-                granules[(items[i].format == 6 ? 2 : 0) + (items[i].inverse ? 1 : 0)] += items[i].len / 16 / 1024;
+            if (items[i].format == format)
+                granules[items[i].inverse ? 1 : 0] += items[i].len / 16 / 1024;
         if (granules[0] > 0xFFFFFFull || granules[1] > 0xFFFFFFull)
-            return fail(kInvalidArgument, "batch too large for one launch (256 GiB or more of BC7 in one direction)");
-        if (granules[2] > 0xFFFFFFull || granules[3] > 0xFFFFFFull)
-            return fail(kInvalidArgument, "batch too large for one launch (256 GiB or more of BC6H in one direction)");
+            return fail(kInvalidArgument, dxtlt::granule::named(format, "batch too large for one launch (256 GiB or more of ", " in one direction)"));
     }
     hipStream_t user = static_cast<hipStream_t>(hip_stream);
 
@@ -187,7 +182,7 @@ extern "C" int32_t dxtlt_transform_batch_device(const DxtltBatchItem* items, siz
     std::vector<size_t> singles;   // items the batch kernel does not take (plan_batch_entry): launched alone, behind the batches
     for (size_t i = 0; i < count; ++i) {
         const DxtltBatchItem& it = items[i];
-        if (it.len == 0 || it.format == 7 || it.format == 6)
+        if (it.len == 0 || dxtlt::granule::is_granule_format(it.format))
             continue;
         if (it.len >= (size_t(64) << 30))
             return fail(kInvalidArgument, "batch item of 64 GiB or more: use the single-buffer entry point");
@@ -225,16 +220,17 @@ extern "C" int32_t dxtlt_transform_batch_device(const DxtltBatchItem* items, siz
     // BC7 items (format 7; no settings): their granules in one launch per direction, their tail parts in a second one.  Planned
     // here, staged and launched below with everything else.  BC6H items (format 6) the same, in launches of their own: plans
     // 0, 1 = BC7 forward, inverse; 2, 3 = BC6H forward, inverse.
-    struct Bc7Plan {
-        std::vector<dxtlt::bc7::BatchEntry> entries, tails;
+    using GranuleEntry = dxtlt::granule::BatchEntry;
+    struct GranulePlan {
+        std::vector<GranuleEntry> entries, tails;
         std::vector<uint32_t> coarse;
         uint64_t wgs = 0;
         size_t at = 0, entry_bytes = 0, tail_bytes = 0, bytes = 0;
     };
-    Bc7Plan bc7_plans[4];
+    GranulePlan granule_plans[4];
     size_t table_bytes = 0;
     for (int q = 0; q < 4; ++q) {
-        Bc7Plan& p = bc7_plans[q];
+        GranulePlan& p = granule_plans[q];
         const int inverse = q & 1, format = q < 2 ? 7 : 6;
         for (size_t i = 0; i < count; ++i) {
             const DxtltBatchItem& it = items[i];
@@ -259,8 +255,8 @@ extern "C" int32_t dxtlt_transform_batch_device(const DxtltBatchItem* items, siz
                 ++cur;
             p.coarse[k] = (uint32_t)cur;
         }
-        p.entry_bytes = p.entries.size() * sizeof(dxtlt::bc7::BatchEntry);
-        p.tail_bytes = p.tails.size() * sizeof(dxtlt::bc7::BatchEntry);
+        p.entry_bytes = p.entries.size() * sizeof(GranuleEntry);
+        p.tail_bytes = p.tails.size() * sizeof(GranuleEntry);
         p.bytes = (p.entry_bytes + p.tail_bytes + p.coarse.size() * sizeof(uint32_t) + 15) & ~(size_t)15;
         p.at = table_bytes;
         table_bytes += p.bytes;
@@ -290,7 +286,7 @@ extern "C" int32_t dxtlt_transform_batch_device(const DxtltBatchItem* items, siz
         hipError_t e = g_ring.acquire(table_bytes, &slot);
         if (e != hipSuccess)
             return fail(kDevice, "batch table staging", e);
-        for (const Bc7Plan& p : bc7_plans) {
+        for (const GranulePlan& p : granule_plans) {
             if (p.bytes == 0)
                 continue;
             uint8_t* h = static_cast<uint8_t*>(slot->host) + p.at;
@@ -308,18 +304,17 @@ extern "C" int32_t dxtlt_transform_batch_device(const DxtltBatchItem* items, siz
         e = upload_table(slot, table_bytes, user);
         const char* what = "batch table copy / launch";
         for (int q = 0; q < 4 && e == hipSuccess; ++q) {
-            const Bc7Plan& p = bc7_plans[q];
-            const int inverse = q & 1;
+            const GranulePlan& p = granule_plans[q];
+            const int inverse = q & 1, format = q < 2 ? 7 : 6;
             if (p.bytes == 0)
                 continue;
             const uint8_t* d = static_cast<const uint8_t*>(slot->dev) + p.at;
-            const auto launch_batch = q < 2 ? dxtlt::bc7::launch_batch : dxtlt::bc6h::launch_batch;
-            e = launch_batch(inverse != 0, reinterpret_cast<const dxtlt::bc7::BatchEntry*>(d),
-                                         reinterpret_cast<const uint32_t*>(d + p.entry_bytes + p.tail_bytes), (uint32_t)p.entries.size(),
-                                         (uint32_t)p.wgs, reinterpret_cast<const dxtlt::bc7::BatchEntry*>(d + p.entry_bytes),
-                                         (uint32_t)p.tails.size(), user);
+            e = dxtlt::granule::launch_batch(format, inverse != 0, reinterpret_cast<const GranuleEntry*>(d),
+                                             reinterpret_cast<const uint32_t*>(d + p.entry_bytes + p.tail_bytes), (uint32_t)p.entries.size(),
+                                             (uint32_t)p.wgs, reinterpret_cast<const GranuleEntry*>(d + p.entry_bytes),
+                                             (uint32_t)p.tails.size(), user);
             if (e != hipSuccess)
-                what = q < 2 ? "BC7 batch table copy / launch" : "BC6H batch table copy / launch";
+                what = format == 7 ? "BC7 batch table copy / launch" : "BC6H batch table copy / launch";
         }
         for (size_t k = 0; k < placed.size() && e == hipSuccess; ++k) {
             const int gi = placed[k].gi;
@@ -544,12 +539,9 @@ extern "C" int32_t dxtlt_transform_batch_host(const DxtltBatchItem* items, size_
             continue;
         }
         int32_t rc;
-        if (it.format == 7)
-            rc = it.inverse ? dxtlt_untransform_bc7(static_cast<const uint8_t*>(it.d_input), static_cast<uint8_t*>(it.d_output), it.len)
-                            : dxtlt_transform_bc7(static_cast<const uint8_t*>(it.d_input), static_cast<uint8_t*>(it.d_output), it.len);
-        else if (it.format == 6)
-            rc = it.inverse ? dxtlt_untransform_bc6h(static_cast<const uint8_t*>(it.d_input), static_cast<uint8_t*>(it.d_output), it.len)
-                            : dxtlt_transform_bc6h(static_cast<const uint8_t*>(it.d_input), static_cast<uint8_t*>(it.d_output), it.len);
+        if (dxtlt::granule::is_granule_format(it.format))
+            rc = dxtlt_host::granule_host_call(it.format, it.inverse != 0, static_cast<const uint8_t*>(it.d_input),
+                                               static_cast<uint8_t*>(it.d_output), it.len);
         else
             rc = dxtlt_host::transform(it.format, it.inverse != 0, static_cast<const uint8_t*>(it.d_input),
                                        static_cast<uint8_t*>(it.d_output), it.len, it.decorrelation_mode,

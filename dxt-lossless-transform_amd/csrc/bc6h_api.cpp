@@ -1,6 +1,6 @@
 // bc6h_api.cpp -- C ABI of the BC6H granule-sorted field split, layout version 1 (include/dxtlt_bc6h.h,
 // docs/BC6H_FORMAT.md).  The host, device, range and sharded paths are BC7's (bc7_api.cpp, bc7_sharded.cpp) with format
-// code 6, which selects the BC6H kernels (bc6h_kernels.hip).
+// code 6, which selects the BC6H kernels (granule_launch.h, bc6h_kernels.hip).
 #include "../../include/dxtlt_bc6h.h"
 
 #include "host_common.h"

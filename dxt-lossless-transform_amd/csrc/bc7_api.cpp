@@ -6,29 +6,20 @@
 
 #include <cstring>
 
-#include "bc6h_launch.h"
-#include "bc7_launch.h"
+#include "granule_launch.h"
 #include "host_common.h"
+
+using dxtlt::granule::named;
 
 namespace {
 
-// format 7 = BC7, 6 = BC6H (include/dxtlt_bc6h.h): the same granules and streams, their own kernels
-hipError_t launch(int format, bool inverse, const void* src, void* dst, uint64_t n_blocks, hipStream_t stream)
-{
-    return format == 6 ? dxtlt::bc6h::launch(inverse, src, dst, n_blocks, stream) : dxtlt::bc7::launch(inverse, src, dst, n_blocks, stream);
-}
-
-const char* length_message(int format)
-{
-    return format == 6 ? "len is not a multiple of 16 (BC6H block size)" : "len is not a multiple of 16 (BC7 block size)";
-}
+const char* length_message(int format) { return named(format, "len is not a multiple of 16 (", " block size)"); }
 
 }  // namespace
 
 int32_t dxtlt_host::granule_host_call(int format, bool inverse, const uint8_t* in, uint8_t* out, size_t len)
 {
     using namespace dxtlt_host;
-    const char* what = format == 6 ? "BC6H transform" : "BC7 transform";
     if (len % 16 != 0)
         return fail(kInvalidLength, length_message(format));
     if (len == 0)
@@ -39,7 +30,7 @@ int32_t dxtlt_host::granule_host_call(int format, bool inverse, const uint8_t* i
     // overlap), then the tail part -- a BC7 buffer of its own -- through the one-shot path below
     const uint64_t blocks = len / 16, main_blocks = blocks - blocks % 1024;
     int32_t prc = kOk;
-    if (pipelined_bc7_main(inverse, in, out, main_blocks, &prc, format)) {
+    if (pipelined_granule_main(format, inverse, in, out, main_blocks, &prc)) {
         if (prc != kOk || main_blocks == blocks)
             return prc;
         return granule_host_call(format, inverse, in + main_blocks * 16, out + main_blocks * 16, (size_t)((blocks - main_blocks) * 16));
@@ -51,12 +42,12 @@ int32_t dxtlt_host::granule_host_call(int format, bool inverse, const uint8_t* i
         return rc;
     if (m.usable) {
         std::memcpy(m.h_in, in, len);
-        hipError_t e = launch(format, inverse, m.d_in, m.d_out, len / 16, m.stream);
+        hipError_t e = dxtlt::granule::launch(format, inverse, m.d_in, m.d_out, len / 16, m.stream);
         const hipError_t drained = hipStreamSynchronize(m.stream);
         if (e == hipSuccess)
             e = drained;
         if (e != hipSuccess)
-            return fail(kDevice, what, e);
+            return fail(kDevice, named(format, "", " transform"), e);
         std::memcpy(out, m.h_out, len);
         return kOk;
     }
@@ -67,7 +58,7 @@ int32_t dxtlt_host::granule_host_call(int format, bool inverse, const uint8_t* i
         return rc;
     hipError_t e = hipMemcpyAsync(d_in, in, len, hipMemcpyHostToDevice, st);
     if (e == hipSuccess)
-        e = launch(format, inverse, d_in, d_out, len / 16, st);
+        e = dxtlt::granule::launch(format, inverse, d_in, d_out, len / 16, st);
     if (e == hipSuccess)
         e = hipMemcpyAsync(out, d_out, len, hipMemcpyDeviceToHost, st);
     // drained on every exit: the staging buffers belong to this thread's next call
@@ -75,7 +66,7 @@ int32_t dxtlt_host::granule_host_call(int format, bool inverse, const uint8_t* i
     if (e == hipSuccess)
         e = drained;
     if (e != hipSuccess)
-        return fail(kDevice, what, e);
+        return fail(kDevice, named(format, "", " transform"), e);
     return kOk;
 }
 
@@ -87,16 +78,12 @@ int32_t dxtlt_host::granule_device_range(int format, bool inverse, const void* d
         return kOk;
     if (d_src == nullptr || d_dst == nullptr)
         return fail(kInvalidArgument, "NULL device buffer");
-    const hipError_t e = format == 6 ? dxtlt::bc6h::launch_range(inverse, d_src, d_dst, total, first, num, (hipStream_t)stream)
-                                     : dxtlt::bc7::launch_range(inverse, d_src, d_dst, total, first, num, (hipStream_t)stream);
+    const hipError_t e = dxtlt::granule::launch_range(format, inverse, d_src, d_dst, total, first, num, (hipStream_t)stream);
+    if (e == hipSuccess)
+        return kOk;
     if (e == hipErrorInvalidValue)
-        return fail(kInvalidArgument, format == 6 ? "BC6H: a range starts on a sort granule (1024 blocks) and ends on one or at "
-                                                    "the end of the array"
-                                                  : "BC7: a range starts on a sort granule (1024 blocks) and ends on one or at the "
-                                                    "end of the array");
-    if (e != hipSuccess)
-        return fail(kDevice, format == 6 ? "BC6H kernel launch" : "BC7 kernel launch", e);
-    return kOk;
+        return fail(kInvalidArgument, named(format, "", ": a range starts on a sort granule (1024 blocks) and ends on one or at the end of the array"));
+    return fail(kDevice, named(format, "", " kernel launch"), e);
 }
 
 namespace {

@@ -6,8 +6,9 @@
 // dxtlt_bc7_shard_pieces is that placement table on its own (pure host code; the CPU tests drive it with the oracle).
 #include <hip/hip_runtime_api.h>
 
-#include <string>
 #include <algorithm>
+#include <cstdio>
+#include <string>
 #include <exception>
 #include <thread>
 #include <vector>
@@ -15,8 +16,7 @@
 #include "../../include/dxtlt_bc7.h"
 #include "../../include/dxtlt_gfx950.h"
 #include "bc7_fields.h"
-#include "bc6h_launch.h"
-#include "bc7_launch.h"
+#include "granule_launch.h"
 #include "host_common.h"
 
 namespace {
@@ -32,21 +32,16 @@ struct Piece {
 };
 
 // pieces 0..7: the shard's slice of every main stream; piece 8: the tail part (last shard only, else empty)
-// format 7 = BC7, 6 = BC6H (include/dxtlt_bc6h.h): the same granules and streams, their own kernels
-const char* name_of(int format) { return format == 6 ? "BC6H" : "BC7"; }
-
-hipError_t launch(int format, bool inverse, const void* src, void* dst, uint64_t n_blocks, hipStream_t stream)
-{
-    return format == 6 ? dxtlt::bc6h::launch(inverse, src, dst, n_blocks, stream) : dxtlt::bc7::launch(inverse, src, dst, n_blocks, stream);
-}
+// format 7 = BC7, 6 = BC6H (include/dxtlt_bc6h.h): the same granules and streams, their own kernels (granule_launch.h)
+using dxtlt::granule::launch;
+using dxtlt::granule::named;
 
 int32_t pieces_for(int format, uint64_t total_blocks, uint64_t first_block, uint64_t num_blocks, Piece (&p)[9])
 {
     const uint64_t main_total = total_blocks - total_blocks % kT;
     if (first_block % kT != 0 || first_block > total_blocks || num_blocks > total_blocks - first_block ||
         ((first_block + num_blocks) % kT != 0 && first_block + num_blocks != total_blocks))
-        return fail(kInvalidArgument, (std::string(name_of(format)) +
-                                       " shard: a shard starts on a sort granule (1024 blocks) and ends on one or at the end").c_str());
+        return fail(kInvalidArgument, named(format, "", " shard: a shard starts on a sort granule (1024 blocks) and ends on one or at the end"));
     const uint64_t end = first_block + num_blocks;
     const uint64_t main_count = first_block >= main_total ? 0 : (end > main_total ? main_total : end) - first_block;
     for (int s = 0; s < 8; ++s)
@@ -103,7 +98,7 @@ int32_t shard_worker(int format, int dev, bool inverse, const uint8_t* in, uint8
     const uint64_t main_total = total_blocks - total_blocks % 1024;
     const uint64_t in_main = sh.first >= main_total ? 0 : std::min<uint64_t>(sh.first + sh.count, main_total) - sh.first;
     int32_t prc = kOk;
-    if (in_main != 0 && pipelined_bc7_shard(sb, dev, inverse, in, out, main_total, sh.first, in_main, &prc, format)) {
+    if (in_main != 0 && pipelined_granule_shard(format, sb, dev, inverse, in, out, main_total, sh.first, in_main, &prc)) {
         if (prc != kOk)
             return done(prc);
         const uint64_t tail = sh.count - in_main;   // blocks of the array's tail part
@@ -118,7 +113,7 @@ int32_t shard_worker(int format, int dev, bool inverse, const uint8_t* in, uint8
             if (e == hipSuccess)
                 e = hipStreamSynchronize(st);
             if (e != hipSuccess)
-                return done(fail(kDevice, format == 6 ? "BC6H shard tail part" : "BC7 shard tail part", e));
+                return done(fail(kDevice, named(format, "", " shard tail part"), e));
         }
         return done(kOk);
     }
@@ -143,7 +138,7 @@ int32_t shard_worker(int format, int dev, bool inverse, const uint8_t* in, uint8
     if (e == hipSuccess)
         e = hipStreamSynchronize(st);
     if (e != hipSuccess)
-        return done(fail(kDevice, format == 6 ? "BC6H shard copy/launch" : "BC7 shard copy/launch", e));
+        return done(fail(kDevice, named(format, "", " shard copy/launch"), e));
     return done(kOk);
 }
 
@@ -152,7 +147,7 @@ int32_t shard_worker(int format, int dev, bool inverse, const uint8_t* in, uint8
 int32_t dxtlt_host::granule_sharded(int format, bool inverse, const uint8_t* in, uint8_t* out, size_t len, int32_t num_shards)
 {
     if (len % 16 != 0)
-        return fail(kInvalidLength, format == 6 ? "len is not a multiple of 16 (BC6H block size)" : "len is not a multiple of 16 (BC7 block size)");
+        return fail(kInvalidLength, named(format, "len is not a multiple of 16 (", " block size)"));
     if (len == 0)
         return kOk;
     if (in == nullptr || out == nullptr)
@@ -201,8 +196,11 @@ int32_t dxtlt_host::granule_sharded(int format, bool inverse, const uint8_t* in,
 int32_t dxtlt_host::granule_shard_pieces(int format, uint64_t total_blocks, uint64_t first_block, uint64_t num_blocks,
                                          uint64_t* global_off, uint64_t* local_off, uint64_t* bytes)
 {
-    if (global_off == nullptr || local_off == nullptr || bytes == nullptr)
-        return fail(kInvalidArgument, format == 6 ? "dxtlt_bc6h_shard_pieces: NULL output array" : "dxtlt_bc7_shard_pieces: NULL output array");
+    if (global_off == nullptr || local_off == nullptr || bytes == nullptr) {
+        char text[64];
+        std::snprintf(text, sizeof text, "dxtlt_%s_shard_pieces: NULL output array", dxtlt::granule::format_symbol(format));
+        return fail(kInvalidArgument, text);
+    }
     Piece pc[9];
     if (int32_t rc = pieces_for(format, total_blocks, first_block, num_blocks, pc); rc != kOk)
         return rc;

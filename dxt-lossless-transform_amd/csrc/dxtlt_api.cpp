@@ -19,8 +19,7 @@
 #include <thread>
 #include <vector>
 
-#include "bc6h_launch.h"
-#include "bc7_launch.h"
+#include "granule_launch.h"
 #include "bcn_launch.h"
 #include "host_common.h"
 
@@ -285,13 +284,13 @@ int32_t pipelined_range(const PipeJob& j)
     // format 7 = the main part of a BC7 buffer (include/dxtlt_bc7.h): eight streams over whole 1024-block granules, chunks
     // are granule multiples, the kernels are the BC7 range launches; everything else is the same pipeline.  Format 6 = the
     // same for BC6H (include/dxtlt_bc6h.h), with its own kernels
-    const bool bc7 = j.format == 7 || j.format == 6;
-    const uint64_t B = bc7 ? 16 : (uint64_t)dxtlt::block_bytes((Format)j.format);
+    const bool granule = dxtlt::granule::is_granule_format(j.format);
+    const uint64_t B = granule ? 16 : (uint64_t)dxtlt::block_bytes((Format)j.format);
     struct {
         int n;
         int off[8], width[8];
     } S{};
-    if (bc7) {
+    if (granule) {
         const int off[8] = {0, 8, 10, 11, 12, 13, 14, 15}, width[8] = {8, 2, 1, 1, 1, 1, 1, 1};
         S.n = 8;
         for (int s = 0; s < 8; ++s) {
@@ -308,14 +307,10 @@ int32_t pipelined_range(const PipeJob& j)
         }
     }
     auto launch = [&](bool inv, const void* src, void* dst, uint64_t range_total, uint64_t range_first, uint64_t range_count) -> int32_t {
-        if (!bc7)
+        if (!granule)
             return device_range(j.format, inv, src, dst, range_total, range_first, range_count, j.mode, j.sa, j.sc, j.up, inv ? 0 : j.normalize);
-        if (j.format == 6) {
-            const hipError_t e = dxtlt::bc6h::launch_range(inv, src, dst, range_total, range_first, range_count, j.up);
-            return e == hipSuccess ? DXTLT_OK : fail(DXTLT_E_DEVICE, "BC6H kernel launch", e);
-        }
-        const hipError_t e = dxtlt::bc7::launch_range(inv, src, dst, range_total, range_first, range_count, j.up);
-        return e == hipSuccess ? DXTLT_OK : fail(DXTLT_E_DEVICE, "BC7 kernel launch", e);
+        const hipError_t e = dxtlt::granule::launch_range(j.format, inv, src, dst, range_total, range_first, range_count, j.up);
+        return e == hipSuccess ? DXTLT_OK : fail(DXTLT_E_DEVICE, dxtlt::granule::named(j.format, "", " kernel launch"), e);
     };
     const uint64_t chunk_blocks = j.chunk_bytes / B;  // a multiple of every tile size (and of the BC7 granule)
     const int nchunks = (int)((j.count + chunk_blocks - 1) / chunk_blocks);
@@ -428,8 +423,8 @@ int32_t pipelined_transform(HostCtx& c, int32_t format, bool inverse, const uint
 
 }  // namespace
 
-// The main part (whole granules) of a large BC7 host buffer through the chunked pipeline; false = too small / switched off
-bool dxtlt_host::pipelined_bc7_main(bool inverse, const uint8_t* in, uint8_t* out, uint64_t main_blocks, int32_t* rc, int format)
+// The main part (whole granules) of a large BC7 or BC6H host buffer through the chunked pipeline; false = too small / switched off
+bool dxtlt_host::pipelined_granule_main(int format, bool inverse, const uint8_t* in, uint8_t* out, uint64_t main_blocks, int32_t* rc)
 {
     const uint64_t bytes = main_blocks * 16;
     if (bytes < kPipelineMinBytes || g_host_pipeline.load(std::memory_order_relaxed) == 0)
@@ -779,8 +774,8 @@ void dxtlt_host::init_runtime_for_devices(int devices)
     (void)hipSetDevice(prev);
 }
 
-bool dxtlt_host::pipelined_bc7_shard(const ShardBuffers& sb, int dev, bool inverse, const uint8_t* in, uint8_t* out,
-                                     uint64_t total_main, uint64_t first, uint64_t count, int32_t* rc, int format)
+bool dxtlt_host::pipelined_granule_shard(int format, const ShardBuffers& sb, int dev, bool inverse, const uint8_t* in, uint8_t* out,
+                                         uint64_t total_main, uint64_t first, uint64_t count, int32_t* rc)
 {
     const uint64_t bytes = count * 16;
     if (bytes < kPipelineMinBytes || g_host_pipeline.load(std::memory_order_relaxed) == 0)

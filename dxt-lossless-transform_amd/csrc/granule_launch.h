@@ -1,0 +1,58 @@
+// granule_launch.h -- internal launch interface of the granule-sorted field splits: BC7, version 2 (docs/BC7_FORMAT.md),
+// and BC6H, layout version 1 (docs/BC6H_FORMAT.md).  The two formats share the granule, the streams and the batch table,
+// and differ only in the record inside a block; `format` picks the kernels: 7 = BC7, 6 = BC6H.
+#pragma once
+#include <hip/hip_runtime_api.h>
+#include <stddef.h>
+#include <stdint.h>
+
+namespace dxtlt {
+
+namespace granule {
+
+inline bool is_granule_format(int format) { return format == 7 || format == 6; }
+const char* format_name(int format);     // "BC7" / "BC6H": the format in error texts
+const char* format_symbol(int format);   // "bc7" / "bc6h": the format in the C ABI's function names
+// `before` + format_name(format) + `after`: an error text, in a buffer of the calling thread (valid until its next call)
+const char* named(int format, const char* before, const char* after);
+
+// Whole buffer.  Forward: src = blocks, dst = transformed; inverse: the other way round.  Device pointers of any alignment
+// (16-byte aligned ones are the fast case).  One or two kernels on `stream`, no workspace, no synchronisation.
+hipError_t launch(int format, bool inverse, const void* src, void* dst, uint64_t n_blocks, hipStream_t stream);
+
+// One block range of an array of `total_blocks` blocks.  The AoS-side pointer is the range's first block, the SoA-side
+// pointer byte 0 of the WHOLE transformed buffer.  first_block must be a multiple of the sort granule (1024) and the
+// range must end on one or at the end of the array (hipErrorInvalidValue otherwise).
+hipError_t launch_range(int format, bool inverse, const void* src, void* dst, uint64_t total_blocks, uint64_t first_block,
+                        uint64_t num_blocks, hipStream_t stream);
+
+// Many buffers per launch.  One entry per buffer with full granules (src / dst: the buffer's first byte on both sides;
+// first_wg: its first workgroup in the granule launch, entries in ascending order) and one per buffer with a tail part
+// (src / dst: the tail part's first byte on both sides).  `d_coarse[k]` = the entry that owns workgroup 64 k.
+struct BatchEntry {
+    const uint8_t* src;
+    uint8_t* dst;
+    uint64_t main_blocks;   // blocks of the main part (a multiple of 1024)
+    uint32_t first_wg;
+    uint32_t tail;          // blocks of the tail part (tail entries)
+};
+hipError_t launch_batch(int format, bool inverse, const BatchEntry* d_entries, const uint32_t* d_coarse, uint32_t n_entries,
+                        uint32_t granule_wgs, const BatchEntry* d_tails, uint32_t n_tails, hipStream_t stream);
+
+}  // namespace granule
+
+// What the calls above dispatch to: each format's kernels file (bc7_kernels.hip, bc6h_kernels.hip) defines these two.
+namespace bc7 {
+hipError_t launch_range(bool inverse, const void* src, void* dst, uint64_t total_blocks, uint64_t first_block, uint64_t num_blocks,
+                        hipStream_t stream);
+hipError_t launch_batch(bool inverse, const granule::BatchEntry* d_entries, const uint32_t* d_coarse, uint32_t n_entries,
+                        uint32_t granule_wgs, const granule::BatchEntry* d_tails, uint32_t n_tails, hipStream_t stream);
+}  // namespace bc7
+namespace bc6h {
+hipError_t launch_range(bool inverse, const void* src, void* dst, uint64_t total_blocks, uint64_t first_block, uint64_t num_blocks,
+                        hipStream_t stream);
+hipError_t launch_batch(bool inverse, const granule::BatchEntry* d_entries, const uint32_t* d_coarse, uint32_t n_entries,
+                        uint32_t granule_wgs, const granule::BatchEntry* d_tails, uint32_t n_tails, hipStream_t stream);
+}  // namespace bc6h
+
+}  // namespace dxtlt

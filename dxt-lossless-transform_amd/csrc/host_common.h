@@ -44,10 +44,10 @@ struct MappedStaging {
 };
 int32_t acquire_mapped_staging(size_t bytes, MappedStaging* out);
 
-// Large BC7 host buffers: the main part (whole 1024-block granules) through the chunked upload | kernel | download
-// pipeline of the BC1-3 host path.  Returns false when the buffer is below the pipeline's threshold (nothing done).
-// format: 7 = BC7, 6 = BC6H (the same granules and streams, bc6h_launch.h).
-bool pipelined_bc7_main(bool inverse, const uint8_t* in, uint8_t* out, uint64_t main_blocks, int32_t* rc, int format = 7);
+// Large BC7 or BC6H host buffers (format: 7 = BC7, 6 = BC6H; the same granules and streams, granule_launch.h): the main
+// part (whole 1024-block granules) through the chunked upload | kernel | download pipeline of the BC1-3 host path.
+// Returns false when the buffer is below the pipeline's threshold (nothing done).
+bool pipelined_granule_main(int format, bool inverse, const uint8_t* in, uint8_t* out, uint64_t main_blocks, int32_t* rc);
 
 // Per-device shard contexts of the sharded entry points (a stream and two device buffers of at least `bytes`), kept
 // across calls; the calling thread has made `dev` current.  release_shard_buffers hands the context back (the stream
@@ -66,12 +66,12 @@ void release_shard_buffers(const ShardBuffers& sb);
 // hipFree synchronises the device).
 void init_runtime_for_devices(int devices);
 void trim_idle_shard_buffers();
-// Blocks [first, first + count) of the main part (total_main blocks, whole granules) of a BC7 host array through the
-// chunked pipeline on the shard's buffers; false = below the pipeline's threshold (nothing done).
-bool pipelined_bc7_shard(const ShardBuffers& sb, int dev, bool inverse, const uint8_t* in, uint8_t* out, uint64_t total_main,
-                         uint64_t first, uint64_t count, int32_t* rc, int format = 7);
+// Blocks [first, first + count) of the main part (total_main blocks, whole granules) of a BC7 or BC6H host array through
+// the chunked pipeline on the shard's buffers; false = below the pipeline's threshold (nothing done).
+bool pipelined_granule_shard(int format, const ShardBuffers& sb, int dev, bool inverse, const uint8_t* in, uint8_t* out,
+                             uint64_t total_main, uint64_t first, uint64_t count, int32_t* rc);
 
-// The BC7 host, device and sharded calls (bc7_api.cpp, bc7_sharded.cpp) for either granule format: 7 = BC7, 6 = BC6H.
+// The host, device and sharded calls of the granule formats (bc7_api.cpp, bc7_sharded.cpp): 7 = BC7, 6 = BC6H.
 int32_t granule_host_call(int format, bool inverse, const uint8_t* in, uint8_t* out, size_t len);
 int32_t granule_device_range(int format, bool inverse, const void* d_src, void* d_dst, uint64_t total, uint64_t first,
                              uint64_t num, void* stream);
