@@ -402,7 +402,7 @@ def stream_table(fmt: str, settings) -> list[tuple[int, int]]:
 
 def plan_shards(total_blocks: int, shards: int, align_blocks: int = 2048) -> list[tuple[int, int]]:
     """Contiguous (first_block, num_blocks) per shard; equal shares rounded down to `align_blocks`, the last
-    shard takes the remainder (same rule as dxtlt_api.cpp plan_shards)."""
+    shard takes the remainder (same rule as plan_shards in csrc/host_sharded.cpp)."""
     share = total_blocks // shards
     share -= share % align_blocks
     plan, at = [], 0

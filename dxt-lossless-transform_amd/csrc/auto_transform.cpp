@@ -60,7 +60,7 @@ bool same(const Candidate& a, const Candidate& b)
 }
 
 // every failure exit drains the stream first: the staging buffers and the arena belong to this thread's next call
-#define HIP_TRY_AUTO(expr, what)                                        \
+#define AUTO_TRY(expr, what)                                            \
     do {                                                                \
         hipError_t e_ = (expr);                                         \
         if (e_ != hipSuccess) {                                         \
@@ -303,13 +303,13 @@ int32_t dxtlt_host::transform_auto(int32_t format, const uint8_t* in, uint8_t* o
             std::free(scratch);
             return rc;
         }
-        HIP_TRY_AUTO(hipMemcpyAsync(d_in, in, len, hipMemcpyHostToDevice, st), "H2D copy");
+        AUTO_TRY(hipMemcpyAsync(d_in, in, len, hipMemcpyHostToDevice, st), "H2D copy");
         static const bool fused = [] { const char* v = dxtlt::experiment_env("DXTLT_AUTO_FUSED"); return !(v && v[0] == '0'); }();
         if (fused)
             arena = static_cast<uint8_t*>(g_arena.get((size_t)dxtlt::auto_arena_bytes((dxtlt::Format)format, use_all, blocks)));
         if (arena != nullptr)
-            HIP_TRY_AUTO(dxtlt::launch_auto_candidates((dxtlt::Format)format, use_all, d_in, arena, blocks, st),
-                         "candidate kernel launch");
+            AUTO_TRY(dxtlt::launch_auto_candidates((dxtlt::Format)format, use_all, d_in, arena, blocks, st),
+                     "candidate kernel launch");
     }
 
     const Candidate* order;
@@ -339,7 +339,7 @@ int32_t dxtlt_host::transform_auto(int32_t format, const uint8_t* in, uint8_t* o
                 sections.push_back(Section{arena + dxtlt::auto_alpha_section_offset(blocks, sp != 0), alpha_len});
         hipError_t herr = hipSuccess;
         if (!estimate_sections_parallel(sections, est, max_comp, est_threads, st, &herr))
-            HIP_TRY_AUTO(herr == hipSuccess ? hipErrorUnknown : herr, "parallel estimation (staging / download)");
+            AUTO_TRY(herr == hipSuccess ? hipErrorUnknown : herr, "parallel estimation (staging / download)");
         for (int i = 0; i < count; ++i) {
             const Candidate c = order[i];
             size_t total = 0;
@@ -384,16 +384,16 @@ int32_t dxtlt_host::transform_auto(int32_t format, const uint8_t* in, uint8_t* o
         return e;
     };
     if (stage != nullptr)
-        HIP_TRY_AUTO(issue_sections(0), "D2H candidate sections");
+        AUTO_TRY(issue_sections(0), "D2H candidate sections");
 
     for (int i = 0; i < count && !parallel; ++i) {
         const Candidate c = order[i];
         const uint8_t* shown_alpha = out;
         const uint8_t* shown_colour = out + colour_off;
         if (stage != nullptr) {
-            HIP_TRY_AUTO(hipStreamSynchronize(st), "stream synchronize");   // candidate i has arrived
+            AUTO_TRY(hipStreamSynchronize(st), "stream synchronize");   // candidate i has arrived
             if (i + 1 < count)
-                HIP_TRY_AUTO(issue_sections(i + 1), "D2H candidate sections");
+                AUTO_TRY(issue_sections(i + 1), "D2H candidate sections");
             shown_alpha = stage + (size_t)(i & 1) * slot_bytes;
             shown_colour = shown_alpha + alpha_slot;
         } else if (len > 0) {
@@ -412,10 +412,10 @@ int32_t dxtlt_host::transform_auto(int32_t format, const uint8_t* in, uint8_t* o
                 last = c;
             }
             if (alpha_len)
-                HIP_TRY_AUTO(hipMemcpyAsync(out, alpha_src, alpha_len, hipMemcpyDeviceToHost, st), "D2H alpha endpoints");
-            HIP_TRY_AUTO(hipMemcpyAsync(out + colour_off, colour_src, colour_len, hipMemcpyDeviceToHost, st),
-                         "D2H colour endpoints");
-            HIP_TRY_AUTO(hipStreamSynchronize(st), "stream synchronize");
+                AUTO_TRY(hipMemcpyAsync(out, alpha_src, alpha_len, hipMemcpyDeviceToHost, st), "D2H alpha endpoints");
+            AUTO_TRY(hipMemcpyAsync(out + colour_off, colour_src, colour_len, hipMemcpyDeviceToHost, st),
+                     "D2H colour endpoints");
+            AUTO_TRY(hipStreamSynchronize(st), "stream synchronize");
         } else {
             last = c;
         }
@@ -454,8 +454,8 @@ int32_t dxtlt_host::transform_auto(int32_t format, const uint8_t* in, uint8_t* o
                 return rc;
             }
         }
-        HIP_TRY_AUTO(hipMemcpyAsync(out, d_out, len, hipMemcpyDeviceToHost, st), "D2H result");
-        HIP_TRY_AUTO(hipStreamSynchronize(st), "stream synchronize");
+        AUTO_TRY(hipMemcpyAsync(out, d_out, len, hipMemcpyDeviceToHost, st), "D2H result");
+        AUTO_TRY(hipStreamSynchronize(st), "stream synchronize");
     }
     std::free(scratch);
     choice->mode = best.mode;
@@ -512,7 +512,7 @@ int32_t dxtlt_host::transform_auto_bc45(int32_t format, const uint8_t* in, uint8
             std::free(scratch);
             return rc;
         }
-        HIP_TRY_AUTO(hipMemcpyAsync(d_in, in, len, hipMemcpyHostToDevice, st), "H2D copy");
+        AUTO_TRY(hipMemcpyAsync(d_in, in, len, hipMemcpyHostToDevice, st), "H2D copy");
         arena = static_cast<uint8_t*>(g_arena.get(2 * len));
         for (int k = 0; k < 2 && arena != nullptr; ++k) {
             const int32_t rc2 = enqueue(format, false, d_in, arena + (size_t)k * len, blocks, 0, kCandidates[k], false, st);
@@ -543,7 +543,7 @@ int32_t dxtlt_host::transform_auto_bc45(int32_t format, const uint8_t* in, uint8
                 sections.push_back(Section{arena + (size_t)k * len + section_off[h], section_len});
         hipError_t herr = hipSuccess;
         if (!estimate_sections_parallel(sections, est, max_comp, est_threads, st, &herr))
-            HIP_TRY_AUTO(herr == hipSuccess ? hipErrorUnknown : herr, "parallel estimation (staging / download)");
+            AUTO_TRY(herr == hipSuccess ? hipErrorUnknown : herr, "parallel estimation (staging / download)");
         for (int k = 0; k < 2; ++k) {
             size_t total = 0;
             for (int h = 0; h < n_sections; ++h) {
@@ -576,9 +576,9 @@ int32_t dxtlt_host::transform_auto_bc45(int32_t format, const uint8_t* in, uint8
                 }
                 // the section(s) travel into the output buffer at the offsets they are estimated at
                 for (int h = 0; h < n_sections; ++h)
-                    HIP_TRY_AUTO(hipMemcpyAsync(out + section_off[h], src + section_off[h], section_len, hipMemcpyDeviceToHost, st),
-                                 "D2H endpoint section");
-                HIP_TRY_AUTO(hipStreamSynchronize(st), "stream synchronize");
+                    AUTO_TRY(hipMemcpyAsync(out + section_off[h], src + section_off[h], section_len, hipMemcpyDeviceToHost, st),
+                             "D2H endpoint section");
+                AUTO_TRY(hipStreamSynchronize(st), "stream synchronize");
             }
             size_t total = 0;
             for (int h = 0; h < n_sections; ++h) {
@@ -604,8 +604,8 @@ int32_t dxtlt_host::transform_auto_bc45(int32_t format, const uint8_t* in, uint8
     }
     if (len > 0) {
         const void* result = arena != nullptr ? static_cast<const void*>(arena + (size_t)best * len) : d_out;
-        HIP_TRY_AUTO(hipMemcpyAsync(out, result, len, hipMemcpyDeviceToHost, st), "D2H result");
-        HIP_TRY_AUTO(hipStreamSynchronize(st), "stream synchronize");
+        AUTO_TRY(hipMemcpyAsync(out, result, len, hipMemcpyDeviceToHost, st), "D2H result");
+        AUTO_TRY(hipStreamSynchronize(st), "stream synchronize");
     }
     std::free(scratch);
     choice->split_alpha = kCandidates[best];

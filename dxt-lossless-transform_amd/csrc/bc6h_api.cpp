@@ -1,23 +1,13 @@
 // bc6h_api.cpp -- C ABI of the BC6H granule-sorted field split, layout version 1 (include/dxtlt_bc6h.h,
-// docs/BC6H_FORMAT.md).  The host, device, range and sharded paths are BC7's (bc7_api.cpp, bc7_sharded.cpp) with format
+// docs/BC6H_FORMAT.md).  The host, device, range and sharded paths are the granule formats' (granule_host.cpp) with format
 // code 6, which selects the BC6H kernels (granule_launch.h, bc6h_kernels.hip).
 #include "../../include/dxtlt_bc6h.h"
 
 #include "host_common.h"
 
 namespace {
-
 constexpr int kFormat = 6;
-
-int32_t device_call(bool inverse, const void* d_in, void* d_out, size_t len, void* stream)
-{
-    using namespace dxtlt_host;
-    if (len % 16 != 0)
-        return fail(kInvalidLength, "len is not a multiple of 16 (BC6H block size)");
-    return granule_device_range(kFormat, inverse, d_in, d_out, len / 16, 0, len / 16, stream);
 }
-
-}  // namespace
 
 extern "C" {
 
@@ -31,11 +21,11 @@ int32_t dxtlt_untransform_bc6h(const uint8_t* input_ptr, uint8_t* output_ptr, si
 }
 int32_t dxtlt_transform_bc6h_device(const void* d_input, void* d_output, size_t len, void* hip_stream)
 {
-    return device_call(false, d_input, d_output, len, hip_stream);
+    return dxtlt_host::granule_device_call(kFormat, false, d_input, d_output, len, hip_stream);
 }
 int32_t dxtlt_untransform_bc6h_device(const void* d_input, void* d_output, size_t len, void* hip_stream)
 {
-    return device_call(true, d_input, d_output, len, hip_stream);
+    return dxtlt_host::granule_device_call(kFormat, true, d_input, d_output, len, hip_stream);
 }
 int32_t dxtlt_transform_bc6h_range_device(bool inverse, const void* d_src, void* d_dst, uint64_t total_blocks,
                                           uint64_t first_block, uint64_t num_blocks, void* hip_stream)

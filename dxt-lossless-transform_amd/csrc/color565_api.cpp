@@ -17,20 +17,13 @@ using dxtlt_host::kOk;
 
 namespace {
 
-#define HIP_TRY_C(expr, what)                   \
-    do {                                        \
-        hipError_t e_ = (expr);                 \
-        if (e_ != hipSuccess)                   \
-            return fail(kDevice, what, e_);     \
-    } while (0)
-
 int32_t ycocg_device(bool inverse, const void* src, void* dst, size_t n, uint8_t variant, void* stream)
 {
     if (variant > 3)
         return fail(kInvalidArgument, "variant must be 0..3");
     if (n > 0 && (src == nullptr || dst == nullptr))
         return fail(kInvalidArgument, "NULL device buffer with num_items > 0");
-    HIP_TRY_C(dxtlt::launch_color565_ycocg(inverse, src, dst, n, variant, static_cast<hipStream_t>(stream)), "kernel launch");
+    HIP_TRY(dxtlt::launch_color565_ycocg(inverse, src, dst, n, variant, static_cast<hipStream_t>(stream)), "kernel launch");
     return kOk;
 }
 
@@ -51,10 +44,10 @@ int32_t ycocg_host(bool inverse, const uint16_t* src, uint16_t* dst, size_t n, u
     hipStream_t st = nullptr;
     if (int32_t rc = dxtlt_host::acquire_staging(n * 2, &d_a, &d_b, &st); rc != kOk)
         return rc;
-    HIP_TRY_C(hipMemcpyAsync(d_a, src, n * 2, hipMemcpyHostToDevice, st), "H2D copy");
-    HIP_TRY_C(dxtlt::launch_color565_ycocg(inverse, d_a, d_a, n, variant, st), "kernel launch");
-    HIP_TRY_C(hipMemcpyAsync(dst, d_a, n * 2, hipMemcpyDeviceToHost, st), "D2H copy");
-    HIP_TRY_C(hipStreamSynchronize(st), "stream synchronize");
+    HIP_TRY(hipMemcpyAsync(d_a, src, n * 2, hipMemcpyHostToDevice, st), "H2D copy");
+    HIP_TRY(dxtlt::launch_color565_ycocg(inverse, d_a, d_a, n, variant, st), "kernel launch");
+    HIP_TRY(hipMemcpyAsync(dst, d_a, n * 2, hipMemcpyDeviceToHost, st), "D2H copy");
+    HIP_TRY(hipStreamSynchronize(st), "stream synchronize");
     return kOk;
 }
 
@@ -81,7 +74,7 @@ int32_t dxtlt_color565_recorrelate_ycocg_r_split_device(const void* s0, const vo
         return fail(kInvalidLength, "num_items must be even for split operations");
     if (n > 0 && (s0 == nullptr || s1 == nullptr || d == nullptr))
         return fail(kInvalidArgument, "NULL device buffer with num_items > 0");
-    HIP_TRY_C(dxtlt::launch_color565_recorrelate_split(s0, s1, d, n, v, static_cast<hipStream_t>(st)), "kernel launch");
+    HIP_TRY(dxtlt::launch_color565_recorrelate_split(s0, s1, d, n, v, static_cast<hipStream_t>(st)), "kernel launch");
     return kOk;
 }
 
@@ -102,11 +95,11 @@ int32_t dxtlt_color565_recorrelate_ycocg_r_split(const uint16_t* s0, const uint1
     if (int32_t rc = dxtlt_host::acquire_staging(off1 + half > 2 * n ? off1 + half : 2 * n, &d_src, &d_dst, &st); rc != kOk)
         return rc;
     uint8_t* p = static_cast<uint8_t*>(d_src);
-    HIP_TRY_C(hipMemcpyAsync(p, s0, half, hipMemcpyHostToDevice, st), "H2D copy");
-    HIP_TRY_C(hipMemcpyAsync(p + off1, s1, half, hipMemcpyHostToDevice, st), "H2D copy");
-    HIP_TRY_C(dxtlt::launch_color565_recorrelate_split(p, p + off1, d_dst, n, v, st), "kernel launch");
-    HIP_TRY_C(hipMemcpyAsync(d, d_dst, 2 * n, hipMemcpyDeviceToHost, st), "D2H copy");
-    HIP_TRY_C(hipStreamSynchronize(st), "stream synchronize");
+    HIP_TRY(hipMemcpyAsync(p, s0, half, hipMemcpyHostToDevice, st), "H2D copy");
+    HIP_TRY(hipMemcpyAsync(p + off1, s1, half, hipMemcpyHostToDevice, st), "H2D copy");
+    HIP_TRY(dxtlt::launch_color565_recorrelate_split(p, p + off1, d_dst, n, v, st), "kernel launch");
+    HIP_TRY(hipMemcpyAsync(d, d_dst, 2 * n, hipMemcpyDeviceToHost, st), "D2H copy");
+    HIP_TRY(hipStreamSynchronize(st), "stream synchronize");
     return kOk;
 }
 
@@ -116,7 +109,7 @@ int32_t dxtlt_split_565_color_endpoints_device(const void* c, void* o, size_t le
         return fail(kInvalidLength, "colors_len_bytes is not a multiple of 4");
     if (len > 0 && (c == nullptr || o == nullptr))
         return fail(kInvalidArgument, "NULL device buffer with colors_len_bytes > 0");
-    HIP_TRY_C(dxtlt::launch_split_565_color_endpoints(c, o, len, static_cast<hipStream_t>(st)), "kernel launch");
+    HIP_TRY(dxtlt::launch_split_565_color_endpoints(c, o, len, static_cast<hipStream_t>(st)), "kernel launch");
     return kOk;
 }
 
@@ -132,10 +125,10 @@ int32_t dxtlt_split_565_color_endpoints(const uint16_t* c, uint16_t* o, size_t l
     hipStream_t st = nullptr;
     if (int32_t rc = dxtlt_host::acquire_staging(len, &d_a, &d_b, &st); rc != kOk)
         return rc;
-    HIP_TRY_C(hipMemcpyAsync(d_a, c, len, hipMemcpyHostToDevice, st), "H2D copy");
-    HIP_TRY_C(dxtlt::launch_split_565_color_endpoints(d_a, d_b, len, st), "kernel launch");
-    HIP_TRY_C(hipMemcpyAsync(o, d_b, len, hipMemcpyDeviceToHost, st), "D2H copy");
-    HIP_TRY_C(hipStreamSynchronize(st), "stream synchronize");
+    HIP_TRY(hipMemcpyAsync(d_a, c, len, hipMemcpyHostToDevice, st), "H2D copy");
+    HIP_TRY(dxtlt::launch_split_565_color_endpoints(d_a, d_b, len, st), "kernel launch");
+    HIP_TRY(hipMemcpyAsync(o, d_b, len, hipMemcpyDeviceToHost, st), "D2H copy");
+    HIP_TRY(hipStreamSynchronize(st), "stream synchronize");
     return kOk;
 }
 

@@ -16,13 +16,6 @@ using dxtlt_host::kOk;
 
 namespace {
 
-#define HIP_TRY_C(expr, what)                   \
-    do {                                        \
-        hipError_t e_ = (expr);                 \
-        if (e_ != hipSuccess)                   \
-            return fail(kDevice, what, e_);     \
-    } while (0)
-
 constexpr size_t kSliceBlocks = size_t(4) << 20;   // 256 MiB of pixels per slice
 
 inline size_t block_bytes(int fmt) { return fmt == 1 ? 8 : 16; }
@@ -43,7 +36,7 @@ int32_t decode_device(int fmt, const void* in, size_t len, void* out, size_t out
 {
     if (int32_t rc = check_decode(fmt, in, len, out, out_len); rc != kOk)
         return rc;
-    HIP_TRY_C(dxtlt::launch_decode_blocks(fmt, in, out, len / block_bytes(fmt), static_cast<hipStream_t>(stream)), "kernel launch");
+    HIP_TRY(dxtlt::launch_decode_blocks(fmt, in, out, len / block_bytes(fmt), static_cast<hipStream_t>(stream)), "kernel launch");
     return kOk;
 }
 
@@ -61,12 +54,12 @@ int32_t decode_host(int fmt, const uint8_t* in, size_t len, uint8_t* out, size_t
         return rc;
     for (size_t first = 0; first < n; first += slice) {
         const size_t m = n - first < slice ? n - first : slice;
-        HIP_TRY_C(hipMemcpyAsync(d_in, in + first * bs, m * bs, hipMemcpyHostToDevice, st), "H2D copy");
-        HIP_TRY_C(dxtlt::launch_decode_blocks(fmt, d_in, d_out, m, st), "kernel launch");
-        HIP_TRY_C(hipMemcpyAsync(out + first * DXTLT_DECODED_BLOCK_BYTES, d_out, m * DXTLT_DECODED_BLOCK_BYTES, hipMemcpyDeviceToHost, st),
-                  "D2H copy");
+        HIP_TRY(hipMemcpyAsync(d_in, in + first * bs, m * bs, hipMemcpyHostToDevice, st), "H2D copy");
+        HIP_TRY(dxtlt::launch_decode_blocks(fmt, d_in, d_out, m, st), "kernel launch");
+        HIP_TRY(hipMemcpyAsync(out + first * DXTLT_DECODED_BLOCK_BYTES, d_out, m * DXTLT_DECODED_BLOCK_BYTES, hipMemcpyDeviceToHost, st),
+                "D2H copy");
     }
-    HIP_TRY_C(hipStreamSynchronize(st), "stream synchronize");
+    HIP_TRY(hipStreamSynchronize(st), "stream synchronize");
     return kOk;
 }
 
@@ -108,8 +101,8 @@ int32_t dxtlt_count_pixel_differences_device(int32_t fmt, const void* a, const v
 {
     if (int32_t rc = check_difference(fmt, a, b, len, d_count); rc != kOk)
         return rc;
-    HIP_TRY_C(dxtlt::launch_count_pixel_differences(fmt, a, b, len / block_bytes(fmt), d_count, static_cast<hipStream_t>(st)),
-              "kernel launch");
+    HIP_TRY(dxtlt::launch_count_pixel_differences(fmt, a, b, len / block_bytes(fmt), d_count, static_cast<hipStream_t>(st)),
+            "kernel launch");
     return kOk;
 }
 
@@ -131,11 +124,11 @@ int32_t dxtlt_count_pixel_differences(int32_t fmt, const uint8_t* a, const uint8
     for (size_t off = 0; off < len; off += slice) {
         const size_t m = len - off < slice ? len - off : slice;
         uint64_t part = 0;
-        HIP_TRY_C(hipMemcpyAsync(d_a, a + off, m, hipMemcpyHostToDevice, st), "H2D copy");
-        HIP_TRY_C(hipMemcpyAsync(d_b, b + off, m, hipMemcpyHostToDevice, st), "H2D copy");
-        HIP_TRY_C(dxtlt::launch_count_pixel_differences(fmt, d_a, d_b, m / block_bytes(fmt), d_count, st), "kernel launch");
-        HIP_TRY_C(hipMemcpyAsync(&part, d_count, sizeof part, hipMemcpyDeviceToHost, st), "D2H copy");
-        HIP_TRY_C(hipStreamSynchronize(st), "stream synchronize");
+        HIP_TRY(hipMemcpyAsync(d_a, a + off, m, hipMemcpyHostToDevice, st), "H2D copy");
+        HIP_TRY(hipMemcpyAsync(d_b, b + off, m, hipMemcpyHostToDevice, st), "H2D copy");
+        HIP_TRY(dxtlt::launch_count_pixel_differences(fmt, d_a, d_b, m / block_bytes(fmt), d_count, st), "kernel launch");
+        HIP_TRY(hipMemcpyAsync(&part, d_count, sizeof part, hipMemcpyDeviceToHost, st), "D2H copy");
+        HIP_TRY(hipStreamSynchronize(st), "stream synchronize");
         total += part;
     }
     *out_count = total;

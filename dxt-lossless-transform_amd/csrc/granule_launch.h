@@ -16,6 +16,13 @@ const char* format_symbol(int format);   // "bc7" / "bc6h": the format in the C 
 // `before` + format_name(format) + `after`: an error text, in a buffer of the calling thread (valid until its next call)
 const char* named(int format, const char* before, const char* after);
 
+// The eight streams of a transformed buffer's main part (its whole granules, N blocks): stream s starts at byte
+// kStreamOff[s] * N and holds kStreamWidth[s] bytes per block (Q8, Q2, B0..B4, F; docs/BC7_FORMAT.md).  The tail part
+// (N blocks onwards) is a buffer of its own behind them.  Host-side placement only: the kernels have their own constants.
+constexpr int kStreams = 8;
+constexpr uint64_t kStreamOff[kStreams] = {0, 8, 10, 11, 12, 13, 14, 15};
+constexpr uint64_t kStreamWidth[kStreams] = {8, 2, 1, 1, 1, 1, 1, 1};
+
 // Whole buffer.  Forward: src = blocks, dst = transformed; inverse: the other way round.  Device pointers of any alignment
 // (16-byte aligned ones are the fast case).  One or two kernels on `stream`, no workspace, no synchronisation.
 hipError_t launch(int format, bool inverse, const void* src, void* dst, uint64_t n_blocks, hipStream_t stream);

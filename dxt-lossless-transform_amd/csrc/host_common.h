@@ -1,11 +1,16 @@
-// host_common.h -- internal interface between the C ABI translation units (dxtlt_api.cpp, auto_transform.cpp,
-// c_api_core.cpp, c_api_stable.cpp).  Not installed.
+// host_common.h -- internal interface between the host translation units: the C ABI files (dxtlt_api.cpp, bc7_api.cpp,
+// bc6h_api.cpp, c_api_*.cpp, ...), the host-pointer staging paths (host_staging.cpp) and the sharded path
+// (host_sharded.cpp).  Not installed.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stddef.h>
 #include <stdint.h>
 
+#include <functional>
+#include <vector>
+
 #include "../../include/dlt_size_estimator.h"
+#include "../../include/dxtlt_gfx950.h"
 
 namespace dxtlt_host {
 
@@ -22,12 +27,49 @@ enum : int32_t {
 
 // Records the failure text for dxtlt_last_error() on this thread and returns `code`.
 int32_t fail(int32_t code, const char* what, hipError_t e = hipSuccess);
+// The same with a complete text, recorded as it is: a worker thread's dxtlt_last_error() carried to the caller's thread.
+int32_t fail_verbatim(int32_t code, const char* text);
+
+// A failed HIP call leaves the calling function with DXTLT_E_DEVICE and the call's name in the error text.
+#define HIP_TRY(expr, what)                                             \
+    do {                                                                \
+        hipError_t e_ = (expr);                                         \
+        if (e_ != hipSuccess)                                           \
+            return dxtlt_host::fail(dxtlt_host::kDevice, what, e_);     \
+    } while (0)
+
+// ---------------------------------------------------------------------------------------------------
+// What the host-pointer paths know about a format family: where a block range's bytes live on the transformed side,
+// and how to launch its kernels.
+// ---------------------------------------------------------------------------------------------------
+// Stream s of a transformed array of N blocks starts at byte off[s] * N and holds width[s] bytes per block, so blocks
+// [first, first + count) own bytes [off[s] * N + width[s] * first, ... + width[s] * count) of it.  Formats 1-5 fill this in
+// from dxtlt::make_streams and their settings (block_layout, dxtlt_api.cpp), formats 6-7 from the granule formats' one
+// table (granule_layout, granule_host.cpp), where N is the array's main part (whole granules): the tail part behind the
+// streams is a buffer of its own and never passes through a layout.
+struct StreamLayout {
+    int format;              // 1..7: picks the pipeline's chunk-size rule
+    int n;                   // streams
+    uint64_t off[8], width[8];
+    uint64_t block_bytes;
+    uint64_t align_blocks;   // a shard and a pipeline chunk start on a multiple of this (2048 / the sort granule)
+    uint64_t shard_unit;     // a call has at most one shard per `shard_unit` blocks (1 / the sort granule)
+};
+StreamLayout block_layout(int32_t format, bool split_alpha, bool split_colour);
+StreamLayout granule_layout(int format);
+
+// Enqueues the transform of blocks [first, first + count) of an array of `total` blocks (dxtlt_transform_range_device
+// semantics: the AoS-side pointer is the range's first block, the SoA-side pointer the whole transformed array) and
+// returns a status, the error text recorded.  The format and its settings are bound in.
+using Launch = std::function<int32_t(bool inverse, const void* d_src, void* d_dst, uint64_t total, uint64_t first,
+                                     uint64_t count, hipStream_t stream)>;
 
 // Host pointers in/out, whole buffer, synchronous (H2D + kernel + D2H on the current device).
 // `normalize` (BC1 forward only): ColorNormalizationMode fused into the transform, 0 = none.
 int32_t transform(int32_t format, bool inverse, const uint8_t* in, uint8_t* out, size_t len, uint8_t mode,
                   bool split_alpha, bool split_colour, uint8_t normalize = 0);
 
+// ---- host_staging.cpp -------------------------------------------------------------------------------
 // This thread's staging context on the current device: two device buffers of at least `bytes` and a stream.
 int32_t acquire_staging(size_t bytes, void** d_in, void** d_out, hipStream_t* stream);
 
@@ -44,35 +86,42 @@ struct MappedStaging {
 };
 int32_t acquire_mapped_staging(size_t bytes, MappedStaging* out);
 
-// Large BC7 or BC6H host buffers (format: 7 = BC7, 6 = BC6H; the same granules and streams, granule_launch.h): the main
-// part (whole 1024-block granules) through the chunked upload | kernel | download pipeline of the BC1-3 host path.
-// Returns false when the buffer is below the pipeline's threshold (nothing done).
-bool pipelined_granule_main(int format, bool inverse, const uint8_t* in, uint8_t* out, uint64_t main_blocks, int32_t* rc);
-
-// Per-device shard contexts of the sharded entry points (a stream and two device buffers of at least `bytes`), kept
-// across calls; the calling thread has made `dev` current.  release_shard_buffers hands the context back (the stream
-// must be drained).
-struct ShardBuffers {
-    hipStream_t stream;
-    void* a;
-    void* b;
-    void* handle;
+// One whole array of `blocks` blocks from host memory to host memory on the current device: through the mapped pair,
+// the chunked pipeline or one H2D + launch + D2H, by size.  The stream is drained on every exit.
+int32_t host_round_trip(const StreamLayout& L, const Launch& launch, bool inverse, const uint8_t* in, uint8_t* out,
+                        uint64_t blocks);
+// Whether a transfer of `bytes` is large enough for the chunked pipeline (DXTLT_PIPELINE_MIN_BYTES).
+bool pipeline_pays(uint64_t bytes);
+// Blocks [first, first + count) of a host-resident array of `total` blocks through the chunked upload | kernel | download
+// pipeline, on device `dev` with its stream `up` and two device buffers of count * block_bytes.
+struct DeviceStaging {
+    int dev;
+    hipStream_t up;
+    void* d_in;
+    void* d_out;
 };
-int32_t acquire_shard_buffers(int dev, size_t bytes, ShardBuffers* out);
-void release_shard_buffers(const ShardBuffers& sb);
-// A sharded call, before it starts its workers: the HIP runtime brought up for devices [0, devices) on the CALLER's thread
-// (workers narrow their affinity before their first HIP call; runtime threads started lazily from one would inherit the mask).
-// After its workers have joined: idle contexts beyond the per-device cap are freed (never on a shard's completion path:
-// hipFree synchronises the device).
-void init_runtime_for_devices(int devices);
-void trim_idle_shard_buffers();
-// Blocks [first, first + count) of the main part (total_main blocks, whole granules) of a BC7 or BC6H host array through
-// the chunked pipeline on the shard's buffers; false = below the pipeline's threshold (nothing done).
-bool pipelined_granule_shard(int format, const ShardBuffers& sb, int dev, bool inverse, const uint8_t* in, uint8_t* out,
-                             uint64_t total_main, uint64_t first, uint64_t count, int32_t* rc);
+int32_t pipelined_range(const StreamLayout& L, const Launch& launch, const DeviceStaging& d, bool inverse, const uint8_t* in,
+                        uint8_t* out, uint64_t total, uint64_t first, uint64_t count);
+void release_thread_staging();   // of dxtlt_release_thread_resources()
 
-// The host, device and sharded calls of the granule formats (bc7_api.cpp, bc7_sharded.cpp): 7 = BC7, 6 = BC6H.
+// ---- host_sharded.cpp -------------------------------------------------------------------------------
+// A host array of `total` blocks -- the last `tail` of them a part of its own behind the streams (granule formats; 0
+// otherwise) -- in contiguous shards over the node's devices, one bound worker thread per shard.  The arguments are
+// valid and the array is not empty.  `stats` (optional) receives one record per shard once the workers have joined.
+int32_t run_sharded(const StreamLayout& L, const Launch& launch, bool inverse, const uint8_t* in, uint8_t* out, uint64_t total,
+                    uint64_t tail, int32_t num_shards, std::vector<DxtltShardStat>* stats);
+// Where a shard's transformed bytes live: slice s < L.n is its `in_main` blocks' share of stream s of an array whose
+// streams hold `main_total` blocks, slice L.n its `tail` blocks of the part behind the streams.  host_off: in the whole
+// transformed array; dev_off: in the shard transformed as a stand-alone buffer.
+struct Slice {
+    uint64_t host_off, dev_off, bytes;
+};
+void shard_slices(const StreamLayout& L, uint64_t main_total, uint64_t first, uint64_t in_main, uint64_t tail, Slice* out);
+void release_idle_shard_contexts();   // process-wide; of dxtlt_release_thread_resources()
+
+// ---- granule_host.cpp: the host, device and sharded calls of the granule formats, 7 = BC7, 6 = BC6H ----
 int32_t granule_host_call(int format, bool inverse, const uint8_t* in, uint8_t* out, size_t len);
+int32_t granule_device_call(int format, bool inverse, const void* d_in, void* d_out, size_t len, void* stream);
 int32_t granule_device_range(int format, bool inverse, const void* d_src, void* d_dst, uint64_t total, uint64_t first,
                              uint64_t num, void* stream);
 int32_t granule_sharded(int format, bool inverse, const uint8_t* in, uint8_t* out, size_t len, int32_t num_shards);
@@ -88,7 +137,6 @@ int32_t enqueue(int32_t format, bool inverse, const void* d_src, void* d_dst, ui
                 bool split_alpha, bool split_colour, hipStream_t stream, uint8_t normalize = 0);
 
 // Per-thread device resources of the other translation units, freed by dxtlt_release_thread_resources().
-void release_bc7_thread_scratch();      // bc7_api.cpp
 void release_normalize_thread_flag();   // normalize_api.cpp
 void release_batch_thread_tables();     // batch_api.cpp
 void release_auto_thread_arena();       // auto_transform.cpp

@@ -18,13 +18,6 @@ using dxtlt_host::kOk;
 
 namespace {
 
-#define HIP_TRY_23(expr, what)                  \
-    do {                                        \
-        hipError_t e_ = (expr);                 \
-        if (e_ != hipSuccess)                   \
-            return fail(kDevice, what, e_);     \
-    } while (0)
-
 int32_t check_modes(int fmt, uint8_t alpha_mode, uint8_t color_mode)
 {
     if (color_mode > 2)
@@ -42,9 +35,9 @@ int32_t blocks_device(int fmt, const void* d_in, void* d_out, size_t len, uint8_
         return rc;
     if (len > 0 && (d_in == nullptr || d_out == nullptr))
         return fail(kInvalidArgument, "NULL device buffer with len > 0");
-    HIP_TRY_23(dxtlt::launch_normalize_bc23_blocks(fmt, d_in, d_out, len / 16, alpha_mode, color_mode,
-                                                   static_cast<hipStream_t>(stream)),
-               "kernel launch");
+    HIP_TRY(dxtlt::launch_normalize_bc23_blocks(fmt, d_in, d_out, len / 16, alpha_mode, color_mode,
+                                                static_cast<hipStream_t>(stream)),
+            "kernel launch");
     return kOk;
 }
 
@@ -67,10 +60,10 @@ int32_t blocks_host(int fmt, const uint8_t* in, uint8_t* out, size_t len, uint8_
     hipStream_t st = nullptr;
     if (int32_t rc = dxtlt_host::acquire_staging(len, &d_a, &d_b, &st); rc != kOk)
         return rc;
-    HIP_TRY_23(hipMemcpyAsync(d_a, in, len, hipMemcpyHostToDevice, st), "H2D copy");
-    HIP_TRY_23(dxtlt::launch_normalize_bc23_blocks(fmt, d_a, d_a, len / 16, alpha_mode, color_mode, st), "kernel launch");
-    HIP_TRY_23(hipMemcpyAsync(out, d_a, len, hipMemcpyDeviceToHost, st), "D2H copy");
-    HIP_TRY_23(hipStreamSynchronize(st), "stream synchronize");
+    HIP_TRY(hipMemcpyAsync(d_a, in, len, hipMemcpyHostToDevice, st), "H2D copy");
+    HIP_TRY(dxtlt::launch_normalize_bc23_blocks(fmt, d_a, d_a, len / 16, alpha_mode, color_mode, st), "kernel launch");
+    HIP_TRY(hipMemcpyAsync(out, d_a, len, hipMemcpyDeviceToHost, st), "D2H copy");
+    HIP_TRY(hipStreamSynchronize(st), "stream synchronize");
     return kOk;
 }
 
@@ -88,8 +81,8 @@ int32_t all_modes_device(int fmt, const void* d_in, void* const* d_outs, size_t 
             if (d_outs[i] == nullptr)
                 return fail(kInvalidArgument, "NULL device output buffer with len > 0");
     }
-    HIP_TRY_23(dxtlt::launch_normalize_bc23_all_modes(fmt, d_in, d_outs, len / 16, static_cast<hipStream_t>(stream)),
-               "kernel launch");
+    HIP_TRY(dxtlt::launch_normalize_bc23_all_modes(fmt, d_in, d_outs, len / 16, static_cast<hipStream_t>(stream)),
+            "kernel launch");
     return kOk;
 }
 
@@ -121,11 +114,11 @@ int32_t all_modes_host(int fmt, const uint8_t* in, uint8_t* const* outs, size_t 
         d_outs[i] = slot < half ? static_cast<uint8_t*>(d_a) + (size_t)slot * padded
                                 : static_cast<uint8_t*>(d_b) + (size_t)(slot - half) * padded;
     }
-    HIP_TRY_23(hipMemcpyAsync(d_a, in, len, hipMemcpyHostToDevice, st), "H2D copy");
-    HIP_TRY_23(dxtlt::launch_normalize_bc23_all_modes(fmt, d_a, d_outs, len / 16, st), "kernel launch");
+    HIP_TRY(hipMemcpyAsync(d_a, in, len, hipMemcpyHostToDevice, st), "H2D copy");
+    HIP_TRY(dxtlt::launch_normalize_bc23_all_modes(fmt, d_a, d_outs, len / 16, st), "kernel launch");
     for (int i = 0; i < count; ++i)
-        HIP_TRY_23(hipMemcpyAsync(outs[i], d_outs[i], len, hipMemcpyDeviceToHost, st), "D2H copy");
-    HIP_TRY_23(hipStreamSynchronize(st), "stream synchronize");
+        HIP_TRY(hipMemcpyAsync(outs[i], d_outs[i], len, hipMemcpyDeviceToHost, st), "D2H copy");
+    HIP_TRY(hipStreamSynchronize(st), "stream synchronize");
     return kOk;
 }
 
@@ -173,8 +166,8 @@ int32_t dxtlt_bc2_normalize_split_blocks_in_place_device(void* d_colors, void* d
         return rc;
     if (num_blocks > 0 && (d_colors == nullptr || d_indices == nullptr))
         return fail(kInvalidArgument, "NULL device buffer with num_blocks > 0");
-    HIP_TRY_23(dxtlt::launch_normalize_bc2_split(d_colors, d_indices, num_blocks, color_mode, static_cast<hipStream_t>(st)),
-               "kernel launch");
+    HIP_TRY(dxtlt::launch_normalize_bc2_split(d_colors, d_indices, num_blocks, color_mode, static_cast<hipStream_t>(st)),
+            "kernel launch");
     return kOk;
 }
 
@@ -185,9 +178,9 @@ int32_t dxtlt_bc3_normalize_split_blocks_in_place_device(void* d_aep, void* d_ai
         return rc;
     if (num_blocks > 0 && (d_aep == nullptr || d_aidx == nullptr || d_cep == nullptr || d_cidx == nullptr))
         return fail(kInvalidArgument, "NULL device buffer with num_blocks > 0");
-    HIP_TRY_23(dxtlt::launch_normalize_bc3_split(d_aep, d_aidx, d_cep, d_cidx, num_blocks, alpha_mode, color_mode,
-                                                 static_cast<hipStream_t>(st)),
-               "kernel launch");
+    HIP_TRY(dxtlt::launch_normalize_bc3_split(d_aep, d_aidx, d_cep, d_cidx, num_blocks, alpha_mode, color_mode,
+                                              static_cast<hipStream_t>(st)),
+            "kernel launch");
     return kOk;
 }
 
@@ -206,12 +199,12 @@ int32_t dxtlt_bc2_normalize_split_blocks_in_place(const uint8_t* alpha_ptr, uint
     hipStream_t st = nullptr;
     if (int32_t rc = dxtlt_host::acquire_staging(half, &d_c, &d_i, &st); rc != kOk)
         return rc;
-    HIP_TRY_23(hipMemcpyAsync(d_c, colors_ptr, half, hipMemcpyHostToDevice, st), "H2D copy");
-    HIP_TRY_23(hipMemcpyAsync(d_i, indices_ptr, half, hipMemcpyHostToDevice, st), "H2D copy");
-    HIP_TRY_23(dxtlt::launch_normalize_bc2_split(d_c, d_i, num_blocks, color_mode, st), "kernel launch");
-    HIP_TRY_23(hipMemcpyAsync(colors_ptr, d_c, half, hipMemcpyDeviceToHost, st), "D2H copy");
-    HIP_TRY_23(hipMemcpyAsync(indices_ptr, d_i, half, hipMemcpyDeviceToHost, st), "D2H copy");
-    HIP_TRY_23(hipStreamSynchronize(st), "stream synchronize");
+    HIP_TRY(hipMemcpyAsync(d_c, colors_ptr, half, hipMemcpyHostToDevice, st), "H2D copy");
+    HIP_TRY(hipMemcpyAsync(d_i, indices_ptr, half, hipMemcpyHostToDevice, st), "H2D copy");
+    HIP_TRY(dxtlt::launch_normalize_bc2_split(d_c, d_i, num_blocks, color_mode, st), "kernel launch");
+    HIP_TRY(hipMemcpyAsync(colors_ptr, d_c, half, hipMemcpyDeviceToHost, st), "D2H copy");
+    HIP_TRY(hipMemcpyAsync(indices_ptr, d_i, half, hipMemcpyDeviceToHost, st), "D2H copy");
+    HIP_TRY(hipStreamSynchronize(st), "stream synchronize");
     return kOk;
 }
 
@@ -233,17 +226,17 @@ int32_t dxtlt_bc3_normalize_split_blocks_in_place(uint8_t* aep, uint8_t* aidx, u
         return rc;
     uint8_t* da = static_cast<uint8_t*>(d_a);
     uint8_t* dc = static_cast<uint8_t*>(d_c);
-    HIP_TRY_23(hipMemcpyAsync(da, aep, 2 * n, hipMemcpyHostToDevice, st), "H2D copy");
-    HIP_TRY_23(hipMemcpyAsync(da + off_aidx, aidx, 6 * n, hipMemcpyHostToDevice, st), "H2D copy");
-    HIP_TRY_23(hipMemcpyAsync(dc, cep, 4 * n, hipMemcpyHostToDevice, st), "H2D copy");
-    HIP_TRY_23(hipMemcpyAsync(dc + off_cidx, cidx, 4 * n, hipMemcpyHostToDevice, st), "H2D copy");
-    HIP_TRY_23(dxtlt::launch_normalize_bc3_split(da, da + off_aidx, dc, dc + off_cidx, n, alpha_mode, color_mode, st),
-               "kernel launch");
-    HIP_TRY_23(hipMemcpyAsync(aep, da, 2 * n, hipMemcpyDeviceToHost, st), "D2H copy");
-    HIP_TRY_23(hipMemcpyAsync(aidx, da + off_aidx, 6 * n, hipMemcpyDeviceToHost, st), "D2H copy");
-    HIP_TRY_23(hipMemcpyAsync(cep, dc, 4 * n, hipMemcpyDeviceToHost, st), "D2H copy");
-    HIP_TRY_23(hipMemcpyAsync(cidx, dc + off_cidx, 4 * n, hipMemcpyDeviceToHost, st), "D2H copy");
-    HIP_TRY_23(hipStreamSynchronize(st), "stream synchronize");
+    HIP_TRY(hipMemcpyAsync(da, aep, 2 * n, hipMemcpyHostToDevice, st), "H2D copy");
+    HIP_TRY(hipMemcpyAsync(da + off_aidx, aidx, 6 * n, hipMemcpyHostToDevice, st), "H2D copy");
+    HIP_TRY(hipMemcpyAsync(dc, cep, 4 * n, hipMemcpyHostToDevice, st), "H2D copy");
+    HIP_TRY(hipMemcpyAsync(dc + off_cidx, cidx, 4 * n, hipMemcpyHostToDevice, st), "H2D copy");
+    HIP_TRY(dxtlt::launch_normalize_bc3_split(da, da + off_aidx, dc, dc + off_cidx, n, alpha_mode, color_mode, st),
+            "kernel launch");
+    HIP_TRY(hipMemcpyAsync(aep, da, 2 * n, hipMemcpyDeviceToHost, st), "D2H copy");
+    HIP_TRY(hipMemcpyAsync(aidx, da + off_aidx, 6 * n, hipMemcpyDeviceToHost, st), "D2H copy");
+    HIP_TRY(hipMemcpyAsync(cep, dc, 4 * n, hipMemcpyDeviceToHost, st), "D2H copy");
+    HIP_TRY(hipMemcpyAsync(cidx, dc + off_cidx, 4 * n, hipMemcpyDeviceToHost, st), "D2H copy");
+    HIP_TRY(hipStreamSynchronize(st), "stream synchronize");
     return kOk;
 }
 

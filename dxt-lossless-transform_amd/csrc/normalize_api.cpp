@@ -32,13 +32,6 @@ using dxtlt_host::kOk;
 
 namespace {
 
-#define HIP_TRY_N(expr, what)                   \
-    do {                                        \
-        hipError_t e_ = (expr);                 \
-        if (e_ != hipSuccess)                   \
-            return fail(kDevice, what, e_);     \
-    } while (0)
-
 int32_t check_mode(uint8_t color_mode)
 {
     if (color_mode > DXTLT_NORMALIZE_REPLICATE_COLOR)
@@ -65,11 +58,11 @@ struct FlagWord {
     int32_t get(uint32_t** out)
     {
         int dev = 0;
-        HIP_TRY_N(hipGetDevice(&dev), "hipGetDevice");
+        HIP_TRY(hipGetDevice(&dev), "hipGetDevice");
         if (dev != device) {
             if (d) (void)hipFree(d);
             d = nullptr;
-            HIP_TRY_N(hipMalloc(reinterpret_cast<void**>(&d), 256), "hipMalloc(flag)");
+            HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), 256), "hipMalloc(flag)");
             device = dev;
         }
         *out = d;
@@ -98,8 +91,8 @@ int32_t dxtlt_bc1_normalize_blocks_device(const void* d_input, void* d_output, s
         return rc;
     if (len > 0 && (d_input == nullptr || d_output == nullptr))
         return fail(kInvalidArgument, "NULL device buffer with len > 0");
-    HIP_TRY_N(dxtlt::launch_normalize_bc1_blocks(d_input, d_output, len / 8, color_mode, static_cast<hipStream_t>(hip_stream)),
-              "kernel launch");
+    HIP_TRY(dxtlt::launch_normalize_bc1_blocks(d_input, d_output, len / 8, color_mode, static_cast<hipStream_t>(hip_stream)),
+            "kernel launch");
     return kOk;
 }
 
@@ -110,9 +103,9 @@ int32_t dxtlt_bc1_normalize_split_blocks_in_place_device(void* d_colors, void* d
         return rc;
     if (num_blocks > 0 && (d_colors == nullptr || d_indices == nullptr))
         return fail(kInvalidArgument, "NULL device buffer with num_blocks > 0");
-    HIP_TRY_N(dxtlt::launch_normalize_bc1_split(d_colors, d_indices, num_blocks, color_mode,
-                                                static_cast<hipStream_t>(hip_stream)),
-              "kernel launch");
+    HIP_TRY(dxtlt::launch_normalize_bc1_split(d_colors, d_indices, num_blocks, color_mode,
+                                              static_cast<hipStream_t>(hip_stream)),
+            "kernel launch");
     return kOk;
 }
 
@@ -125,9 +118,9 @@ int32_t dxtlt_bc1_normalize_blocks_all_modes_device(const void* d_input, void* c
         return fail(kInvalidArgument, "NULL output pointer array");
     if (len > 0 && (d_input == nullptr || d_outputs[0] == nullptr || d_outputs[1] == nullptr || d_outputs[2] == nullptr))
         return fail(kInvalidArgument, "NULL device buffer with len > 0");
-    HIP_TRY_N(dxtlt::launch_normalize_bc1_all_modes(d_input, d_outputs, len / 8, d_any_normalized,
-                                                    static_cast<hipStream_t>(hip_stream)),
-              "kernel launch");
+    HIP_TRY(dxtlt::launch_normalize_bc1_all_modes(d_input, d_outputs, len / 8, d_any_normalized,
+                                                  static_cast<hipStream_t>(hip_stream)),
+            "kernel launch");
     return kOk;
 }
 
@@ -166,10 +159,10 @@ int32_t dxtlt_bc1_normalize_blocks(const uint8_t* input_ptr, uint8_t* output_ptr
     hipStream_t st = nullptr;
     if (int32_t rc = dxtlt_host::acquire_staging(len, &d_in, &d_out, &st); rc != kOk)
         return rc;
-    HIP_TRY_N(hipMemcpyAsync(d_in, input_ptr, len, hipMemcpyHostToDevice, st), "H2D copy");
-    HIP_TRY_N(dxtlt::launch_normalize_bc1_blocks(d_in, d_in, len / 8, color_mode, st), "kernel launch");
-    HIP_TRY_N(hipMemcpyAsync(output_ptr, d_in, len, hipMemcpyDeviceToHost, st), "D2H copy");
-    HIP_TRY_N(hipStreamSynchronize(st), "stream synchronize");
+    HIP_TRY(hipMemcpyAsync(d_in, input_ptr, len, hipMemcpyHostToDevice, st), "H2D copy");
+    HIP_TRY(dxtlt::launch_normalize_bc1_blocks(d_in, d_in, len / 8, color_mode, st), "kernel launch");
+    HIP_TRY(hipMemcpyAsync(output_ptr, d_in, len, hipMemcpyDeviceToHost, st), "D2H copy");
+    HIP_TRY(hipStreamSynchronize(st), "stream synchronize");
     return kOk;
 }
 
@@ -187,12 +180,12 @@ int32_t dxtlt_bc1_normalize_split_blocks_in_place(uint8_t* colors_ptr, uint8_t* 
     hipStream_t st = nullptr;
     if (int32_t rc = dxtlt_host::acquire_staging(half, &d_col, &d_idx, &st); rc != kOk)
         return rc;
-    HIP_TRY_N(hipMemcpyAsync(d_col, colors_ptr, half, hipMemcpyHostToDevice, st), "H2D copy");
-    HIP_TRY_N(hipMemcpyAsync(d_idx, indices_ptr, half, hipMemcpyHostToDevice, st), "H2D copy");
-    HIP_TRY_N(dxtlt::launch_normalize_bc1_split(d_col, d_idx, num_blocks, color_mode, st), "kernel launch");
-    HIP_TRY_N(hipMemcpyAsync(colors_ptr, d_col, half, hipMemcpyDeviceToHost, st), "D2H copy");
-    HIP_TRY_N(hipMemcpyAsync(indices_ptr, d_idx, half, hipMemcpyDeviceToHost, st), "D2H copy");
-    HIP_TRY_N(hipStreamSynchronize(st), "stream synchronize");
+    HIP_TRY(hipMemcpyAsync(d_col, colors_ptr, half, hipMemcpyHostToDevice, st), "H2D copy");
+    HIP_TRY(hipMemcpyAsync(d_idx, indices_ptr, half, hipMemcpyHostToDevice, st), "H2D copy");
+    HIP_TRY(dxtlt::launch_normalize_bc1_split(d_col, d_idx, num_blocks, color_mode, st), "kernel launch");
+    HIP_TRY(hipMemcpyAsync(colors_ptr, d_col, half, hipMemcpyDeviceToHost, st), "D2H copy");
+    HIP_TRY(hipMemcpyAsync(indices_ptr, d_idx, half, hipMemcpyDeviceToHost, st), "D2H copy");
+    HIP_TRY(hipStreamSynchronize(st), "stream synchronize");
     return kOk;
 }
 
@@ -222,13 +215,13 @@ int32_t dxtlt_bc1_normalize_blocks_all_modes(const uint8_t* input_ptr, uint8_t* 
         return rc;
     void* outs[3] = {d_a, static_cast<uint8_t*>(d_a) + padded, d_b};
     uint32_t any = 0;
-    HIP_TRY_N(hipMemsetAsync(d_flag, 0, sizeof(uint32_t), st), "memset flag");
-    HIP_TRY_N(hipMemcpyAsync(d_a, input_ptr, len, hipMemcpyHostToDevice, st), "H2D copy");
-    HIP_TRY_N(dxtlt::launch_normalize_bc1_all_modes(d_a, outs, len / 8, d_flag, st), "kernel launch");
+    HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof(uint32_t), st), "memset flag");
+    HIP_TRY(hipMemcpyAsync(d_a, input_ptr, len, hipMemcpyHostToDevice, st), "H2D copy");
+    HIP_TRY(dxtlt::launch_normalize_bc1_all_modes(d_a, outs, len / 8, d_flag, st), "kernel launch");
     for (int m = 0; m < 3; ++m)
-        HIP_TRY_N(hipMemcpyAsync(output_ptrs[m], outs[m], len, hipMemcpyDeviceToHost, st), "D2H copy");
-    HIP_TRY_N(hipMemcpyAsync(&any, d_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, st), "D2H flag");
-    HIP_TRY_N(hipStreamSynchronize(st), "stream synchronize");
+        HIP_TRY(hipMemcpyAsync(output_ptrs[m], outs[m], len, hipMemcpyDeviceToHost, st), "D2H copy");
+    HIP_TRY(hipMemcpyAsync(&any, d_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, st), "D2H flag");
+    HIP_TRY(hipStreamSynchronize(st), "stream synchronize");
     if (out_any_normalized)
         *out_any_normalized = any != 0;
     return kOk;
@@ -276,11 +269,11 @@ int32_t dxtlt_transform_bc1_auto_with_normalization(const uint8_t* input_ptr, ui
         uint32_t* d_flag = nullptr;
         if (int32_t rc = g_flag.get(&d_flag); rc != kOk)
             return rc;
-        HIP_TRY_N(hipMemsetAsync(d_flag, 0, sizeof(uint32_t), st), "memset flag");
-        HIP_TRY_N(hipMemcpyAsync(d_in, input_ptr, len, hipMemcpyHostToDevice, st), "H2D copy");
-        HIP_TRY_N(dxtlt::launch_bc1_any_normalizable(d_in, len / 8, d_flag, st), "kernel launch");
-        HIP_TRY_N(hipMemcpyAsync(&any, d_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, st), "D2H flag");
-        HIP_TRY_N(hipStreamSynchronize(st), "stream synchronize");
+        HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof(uint32_t), st), "memset flag");
+        HIP_TRY(hipMemcpyAsync(d_in, input_ptr, len, hipMemcpyHostToDevice, st), "H2D copy");
+        HIP_TRY(dxtlt::launch_bc1_any_normalizable(d_in, len / 8, d_flag, st), "kernel launch");
+        HIP_TRY(hipMemcpyAsync(&any, d_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, st), "D2H flag");
+        HIP_TRY(hipStreamSynchronize(st), "stream synchronize");
     }
     if (any == 0) {
         // transform.rs:321-331: nothing to normalise -> the regular brute force, mode None
@@ -352,8 +345,8 @@ int32_t dxtlt_transform_bc1_auto_with_normalization(const uint8_t* input_ptr, ui
         if (rc != kOk)
             return rc;
     }
-    HIP_TRY_N(hipMemcpyAsync(output_ptr, d_out, len, hipMemcpyDeviceToHost, st), "D2H result");
-    HIP_TRY_N(hipStreamSynchronize(st), "stream synchronize");
+    HIP_TRY(hipMemcpyAsync(output_ptr, d_out, len, hipMemcpyDeviceToHost, st), "D2H result");
+    HIP_TRY(hipStreamSynchronize(st), "stream synchronize");
     if (out_color_mode) *out_color_mode = best.norm;
     if (out_decorrelation_mode) *out_decorrelation_mode = best.variant;
     if (out_split_colour_endpoints) *out_split_colour_endpoints = best.split;

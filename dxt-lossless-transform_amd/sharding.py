@@ -1,4 +1,4 @@
-"""Host-side placement logic for block-range shards (mirrors shard_worker in csrc/dxtlt_api.cpp).
+"""Host-side placement logic for block-range shards (mirrors shard_slices / shard_worker in csrc/host_sharded.cpp).
 
 The transformed buffer is SoA over the WHOLE block array, so a shard's result is not one contiguous span: for each
 stream s (offset multiplier `off`, `w` bytes per block) the shard [first, first+count) owns bytes

@@ -1,7 +1,7 @@
 """N > 1 path on CPU: two and four gloo ranks, contiguous block-range shards, no data-path collective.
 
 What is under test is the host logic the multi-GPU paths share -- shard planning (plan_shards), the stream table and
-the per-stream placement of a shard's result (sharding.py, mirrored by shard_worker in csrc/dxtlt_api.cpp) -- plus
+the per-stream placement of a shard's result (sharding.py, mirrored by shard_worker in csrc/host_sharded.cpp) -- plus
 the bench's rendezvous pattern (barrier, MAX-reduce of the elapsed time).  The per-shard transform itself is done by
 the CPU oracle here (no GPU in this container); on the GPU box the same composition is exercised with the HIP kernels
 by tests/test_gpu_parity.py::test_range_calls_compose_to_the_whole_buffer and ::test_sharded_entry_point_on_one_gpu.
