@@ -461,6 +461,87 @@ def test_many_mixed_batch_calls_in_flight_share_the_table_ring(pkg, oracle):
         assert np.array_equal(h[:n], want) and (h[n:] == 0x5A).all(), (c, k, fmt, n)
 
 
+@pytest.mark.gpu
+def test_mixed_batch_in_one_arena_with_guards(pkg, oracle):
+    """200 items of all seven formats, forward and inverse mixed, 1 to ~20 000 blocks biased to tile and granule boundaries, in
+    ONE call: every input inside one device tensor and every output inside another, each item at a byte offset from {0, 1, 2, 4,
+    8, 16, 148} past a 0..3-byte gap behind its neighbour (so items sit at odd addresses with little or nothing between them),
+    the gaps and 256 bytes at either end of the output arena pre-filled with 0xA5.  Every output against the CPU statement of
+    its format, every gap byte still 0xA5; then the same plan through the host batch call on one host arena."""
+    import bc45_ref
+    import bc6h_ref
+    import granule_patterns as P
+    from dxt_lossless_transform_amd import batch
+
+    dev = torch.device("cuda:0")
+    rng = np.random.default_rng(0xA7E4A)
+    formats = ("bc1", "bc2", "bc3", "bc4", "bc5", "bc6h", "bc7")
+    unit = {"bc1": 512, "bc2": 256, "bc3": 256, "bc4": 512, "bc5": 256, "bc6h": 1024, "bc7": 1024}   # tile / granule, in blocks
+
+    def statement(fmt, x, inverse, v, sa, sc):
+        if fmt in ("bc4", "bc5"):
+            return (bc45_ref.untransform if inverse else bc45_ref.transform)(fmt, x, bool(sa))
+        if fmt == "bc6h":
+            return (bc6h_ref.untransform if inverse else bc6h_ref.transform)(x)
+        if fmt == "bc7":
+            return oracle.transform_bc7(x, inverse=inverse)
+        return oracle.transform(fmt, x, v, bool(sc), bool(sa), inverse=inverse)
+
+    plan = []
+    for k in range(200):
+        fmt = formats[int(rng.integers(0, 7))]
+        kind = int(rng.integers(0, 3))
+        n = (int(rng.integers(1, 70)) if kind == 0 else int(rng.integers(1, 20_000)) if kind == 1 else
+             max(1, int(rng.integers(1, 20_000 // unit[fmt] + 1)) * unit[fmt] + int(rng.integers(-17, 18))))
+        inverse = bool(rng.integers(0, 2))
+        v, sa, sc = int(rng.integers(0, 4)), int(rng.integers(0, 2)), int(rng.integers(0, 2))
+        if fmt in ("bc6h", "bc7"):
+            settings = None
+            x = (rng.integers(0, 256, 16 * n, dtype=np.uint8) if k % 3 == 0 else
+                 P.BLOCKS_WITH_CLASSES[fmt](rng.integers(0, P.CLASSES[fmt], n), k))
+        else:
+            B = pkg.BLOCK_BYTES[fmt]
+            x = rng.integers(0, 256, n * B, dtype=np.uint8)
+            settings = ((pkg.Bc4TransformSettings if fmt == "bc4" else pkg.Bc5TransformSettings)(bool(sa)) if fmt in ("bc4", "bc5")
+                        else settings_for(pkg, fmt, v, sa, sc))
+        if inverse:
+            x = statement(fmt, x, False, v, sa, sc)
+        plan.append((fmt, inverse, x, statement(fmt, x, inverse, v, sa, sc), settings))
+
+    def place(seed):
+        r = np.random.default_rng(seed)
+        offs, at = [], 256
+        for _, _, x, _, _ in plan:
+            at += int(r.integers(0, 4)) + int(r.choice([0, 1, 2, 4, 8, 16, 148]))
+            offs.append(at)
+            at += x.size
+        return offs, at + 256
+
+    in_offs, in_size = place(1)
+    out_offs, out_size = place(2)
+    h_in = np.zeros(in_size, dtype=np.uint8)
+    for (_, _, x, _, _), o in zip(plan, in_offs):
+        h_in[o:o + x.size] = x
+
+    def check(got, label):
+        inside = np.zeros(out_size, dtype=bool)
+        for k, ((fmt, inverse, x, want, _), o) in enumerate(zip(plan, out_offs)):
+            assert np.array_equal(got[o:o + x.size], want), (label, k, fmt, inverse, x.size, in_offs[k] % 256, o % 256)
+            inside[o:o + x.size] = True
+        assert (got[~inside] == 0xA5).all(), (label, "a gap byte changed", np.nonzero((got != 0xA5) & ~inside)[0][:8].tolist())
+
+    d_in = torch.from_numpy(h_in).to(dev)
+    d_out = torch.full((out_size,), 0xA5, dtype=torch.uint8, device=dev)
+    batch.transform_batch([(fmt, inverse, d_in[i:i + x.size], d_out[o:o + x.size], st)
+                           for (fmt, inverse, x, _, st), i, o in zip(plan, in_offs, out_offs)])
+    torch.cuda.synchronize()
+    check(d_out.cpu().numpy(), "device")
+    h_out = np.full(out_size, 0xA5, dtype=np.uint8)
+    batch.transform_batch_host([(fmt, inverse, h_in[i:i + x.size], h_out[o:o + x.size], st)
+                                for (fmt, inverse, x, _, st), i, o in zip(plan, in_offs, out_offs)])
+    check(h_out, "host")
+
+
 _SPAWN_FAILURE_SCRIPT = r'''
 import os, resource, sys, time
 sys.path.insert(0, sys.argv[1])

@@ -48,6 +48,77 @@ def test_device_buffers_match_reference(pkg, dev, fmt, split, n):
     assert torch.equal(z, x)
 
 
+# Blocks per tile = tile_blocks(fmt, lanes) = lanes * 16 / block bytes (csrc/bcn_device.h).  BC5 launches every tile form with 256
+# lanes: 256 blocks.  BC4 launches its aligned tiles with 128 lanes (default_tile_threads: 256 blocks) and its halo, shifted and edge
+# tiles with 256 (shift_tile_threads / halo_tile_threads, plan_launches in csrc/bcn_kernels.hip: 512 blocks); the batch launch takes
+# 256 lanes for all of them (batch_tile_threads).  The table holds the larger figure, so "four tiles" covers four of either.
+TILE = {"bc4": 512, "bc5": 256}
+
+
+@pytest.mark.parametrize("fmt", FORMATS)
+@pytest.mark.parametrize("split", [False, True])
+def test_every_n_through_four_tiles(pkg, dev, fmt, split):
+    """Every block count from 1 through four tiles + 17 (every alignment class of the stream bases, every fill of the edge tile):
+    forward == bc45_ref.transform, inverse of that == input.  All counts through the batch call, a few hundred buffers per
+    call in one arena with 64 guard bytes behind each, and a seeded sample of 200 counts through the single-buffer call; then
+    the sample once more with halo / shifted tiles forced."""
+    import torch
+
+    from dxt_lossless_transform_amd import batch
+
+    B = bc45_ref.BLOCK[fmt]
+    st = settings_of(pkg, fmt, split)
+    top = 4 * TILE[fmt] + 17
+    counts = list(range(1, top + 1))
+    pool = data(fmt, top + 64, 0xE4E7 + (fmt == "bc5") + 2 * split)
+    xs = {n: pool[(n % 64) * B:(n % 64 + n) * B] for n in counts}      # no two neighbours start alike
+    wants = {n: bc45_ref.transform(fmt, xs[n], split) for n in counts}
+    sample = sorted(np.random.default_rng(0x5A4D + len(fmt) + split).choice(counts, size=200, replace=False).tolist())
+    guard = 64
+
+    def through_the_batch_call(tag):
+        for lo in range(0, len(counts), 300):
+            chunk = counts[lo:lo + 300]
+            offs, at = [], guard
+            for n in chunk:
+                offs.append(at)
+                at += n * B + guard
+            for inverse, srcs, expect, fill in ((False, xs, wants, 0xA5), (True, wants, xs, 0x5A)):
+                h = np.zeros(at, dtype=np.uint8)
+                for n, o in zip(chunk, offs):
+                    h[o:o + n * B] = srcs[n]
+                src = torch.from_numpy(h).to(dev)
+                dst = torch.full((at,), fill, dtype=torch.uint8, device=dev)
+                batch.transform_batch([(fmt, inverse, src[o:o + n * B], dst[o:o + n * B], st) for n, o in zip(chunk, offs)])
+                torch.cuda.synchronize()
+                got = dst.cpu().numpy()
+                assert (got[:guard] == fill).all(), (tag, inverse, chunk[0])
+                for n, o in zip(chunk, offs):
+                    assert np.array_equal(got[o:o + n * B], expect[n]), (tag, "batch", inverse, n)
+                    assert (got[o + n * B:o + n * B + guard] == fill).all(), (tag, "batch wrote outside", inverse, n)
+
+    def through_the_single_call(tag):
+        for n in sample:
+            dst = torch.full((n * B + 2 * guard,), 0xA5, dtype=torch.uint8, device=dev)
+            back = torch.full((n * B + 2 * guard,), 0x5A, dtype=torch.uint8, device=dev)
+            getattr(pkg, f"transform_{fmt}_with_settings")(torch.from_numpy(xs[n]).to(dev), dst[guard:guard + n * B], st)
+            getattr(pkg, f"untransform_{fmt}_with_settings")(torch.from_numpy(wants[n]).to(dev), back[guard:guard + n * B], st)
+            torch.cuda.synchronize()
+            got, rt = dst.cpu().numpy(), back.cpu().numpy()
+            assert np.array_equal(got[guard:guard + n * B], wants[n]), (tag, "forward", n)
+            assert (got[:guard] == 0xA5).all() and (got[guard + n * B:] == 0xA5).all(), (tag, "forward wrote outside", n)
+            assert np.array_equal(rt[guard:guard + n * B], xs[n]), (tag, "inverse", n)
+            assert (rt[:guard] == 0x5A).all() and (rt[guard + n * B:] == 0x5A).all(), (tag, "inverse wrote outside", n)
+
+    through_the_batch_call("default")
+    through_the_single_call("default")
+    try:
+        pkg.set_tuning(0, 2)          # halo / shifted tiles always (the batch call plans per buffer and does not read the lever)
+        through_the_single_call("forced")
+    finally:
+        pkg.set_tuning(0, 0)
+
+
 @pytest.mark.parametrize("fmt", FORMATS)
 @pytest.mark.parametrize("split", [False, True])
 @pytest.mark.parametrize("n", [1, 129, (1 << 16) + 1, 1_000_003])
