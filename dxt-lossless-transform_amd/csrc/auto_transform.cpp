@@ -21,6 +21,11 @@
 // reference's bytes.  One transform launch with the winning settings and one download of the whole result finish the
 // call.  If the arena (2-4 x len) cannot be allocated the candidates are produced one full transform at a time, as in
 // round 1 (same results, len x 2 of traffic per candidate).
+//
+// The built-in estimator (include/dxtlt_estimator.h, estimate_kernels.hip) is recognised by the identity of its function
+// pointers and never called: auto_on_device() estimates every distinct section where the candidate kernel left it, with one
+// launch, reads back 6 / 10 counters and applies the same order, additions and strict `<`.  No section crosses PCIe.  The same
+// function serves dxtlt_transform_bcN_auto_device, where the input and the result stay on the device as well.
 #include <algorithm>
 #include <atomic>
 #include <cstdlib>
@@ -29,6 +34,7 @@
 #include <vector>
 
 #include "../../include/dxtlt_bc45.h"
+#include "../../include/dxtlt_estimator.h"
 #include "../../include/dxtlt_gfx950.h"
 #include "auto_launch.h"
 #include "bcn_launch.h"
@@ -102,6 +108,28 @@ struct Arena {
     }
 };
 thread_local Arena g_arena;
+
+// dxtlt_debug_auto_last_estimation: what the last auto call of this thread downloaded and called for its estimates
+thread_local uint64_t t_section_bytes_downloaded = 0, t_estimator_callbacks = 0;
+thread_local bool t_no_arena = false;   // dxtlt_debug_auto_use_arena(0): the built-in path as if the arena could not be allocated
+
+uint32_t call_max(const DltSizeEstimator* est, size_t len, size_t* out)
+{
+    ++t_estimator_callbacks;
+    return est->MaxCompressedSize(est->Context, len, out);
+}
+
+uint32_t call_estimate(const DltSizeEstimator* est, const uint8_t* in, size_t len, uint8_t* scratch, size_t max_comp, size_t* out)
+{
+    ++t_estimator_callbacks;
+    return est->EstimateCompressedSize(est->Context, in, len, scratch, max_comp, out);
+}
+
+hipError_t download_section(void* dst, const void* src, size_t len, hipStream_t st)
+{
+    t_section_bytes_downloaded += len;
+    return hipMemcpyAsync(dst, src, len, hipMemcpyDeviceToHost, st);
+}
 
 // ---------------------------------------------------------------------------------------------------------------
 // Opt-in: the estimator on several host threads (dxtlt_set_auto_estimator_threads).  The reference evaluates its
@@ -195,7 +223,7 @@ bool estimate_sections_parallel(std::vector<Section>& sections, const DltSizeEst
         }
         for (size_t i = first; i < last && ok; ++i)
             if (sections[i].len) {
-                *hip_error = hipMemcpyAsync(stage + sections[i].slot, sections[i].d_src, sections[i].len, hipMemcpyDeviceToHost, st);
+                *hip_error = download_section(stage + sections[i].slot, sections[i].d_src, sections[i].len, st);
                 ok = *hip_error == hipSuccess;
             }
         if (ok) {
@@ -227,6 +255,7 @@ bool estimate_sections_parallel(std::vector<Section>& sections, const DltSizeEst
         worker(0);
         for (auto& t : pool)
             t.join();
+        t_estimator_callbacks += last - first;   // (the workers have counters of their own)
         first = last;
     }
     for (auto p : scratch)
@@ -234,6 +263,139 @@ bool estimate_sections_parallel(std::vector<Section>& sections, const DltSizeEst
     return ok;
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------
+// The built-in estimator: everything on the device.
+// ---------------------------------------------------------------------------------------------------------------
+struct Order {
+    const Candidate* order;
+    int count;
+};
+
+Order candidates_of(int32_t format, bool use_all)
+{
+    static const Candidate k45[] = {{0, false, false}, {0, true, false}};   // split_endpoints = false, then true
+    if (format >= 4)
+        return {k45, 2};
+    if (format == 3)
+        return {use_all ? kAll3 : kFast3, use_all ? 16 : 8};
+    return {use_all ? kAll12 : kFast12, use_all ? 8 : 4};
+}
+
+// Chooses among the candidates of `format` (1..5) for the `len` > 0 bytes at d_in with the built-in estimator and leaves the
+// transform with *best enqueued from d_in into d_out.  Enqueues on `st` and waits for it once, for the counters: when it returns
+// nothing in flight reads or writes this thread's arena or counters any more (the pending transform reads d_in alone), so the
+// thread's next auto call may use them at once, on any stream.  The same candidates, the same order, the same sums and strict `<`
+// as the callback flow below.
+int32_t auto_on_device(int32_t format, const void* d_in, void* d_out, size_t len, bool use_all, hipStream_t st, Candidate* best)
+{
+    using namespace dxtlt_host;
+    const Order o = candidates_of(format, use_all);
+    const uint64_t blocks = len / (format == 1 || format == 4 ? 8 : 16);
+    uint8_t* out8 = static_cast<uint8_t*>(d_out);
+    // the section(s) of a transformed buffer at `base` the estimator is shown, in the order their sizes are added
+    auto shown = [&](const uint8_t* base, dxtlt::EstimateSection* secs) -> int {
+        switch (format) {
+        case 1: secs[0] = {base, len / 2}; return 1;
+        case 2: secs[0] = {base + len / 2, len / 4}; return 1;
+        case 3: secs[0] = {base, blocks * 2}; secs[1] = {base + len / 2, blocks * 4}; return 2;
+        case 4: secs[0] = {base, blocks * 2}; return 1;
+        default: secs[0] = {base, blocks * 2}; secs[1] = {base + blocks * 8, blocks * 2}; return 2;
+        }
+    };
+    uint64_t sizes[kMaxCounters];
+    uint64_t total[16];
+    int last = -1;   // the candidate whose transform is in d_out
+
+    uint8_t* arena = nullptr;
+    if (!t_no_arena)
+        arena = static_cast<uint8_t*>(g_arena.get(format >= 4 ? 2 * len : (size_t)dxtlt::auto_arena_bytes((dxtlt::Format)format, use_all, blocks)));
+    if (arena != nullptr && format <= 3) {
+        // one read of the input -> every distinct section: colour (variant, split) pairs, then BC3's two alpha-endpoint sections
+        HIP_TRY(dxtlt::launch_auto_candidates((dxtlt::Format)format, use_all, d_in, arena, blocks, st), "candidate kernel launch");
+        const int variants = use_all ? 4 : 2;
+        const size_t colour_len = format == 1 ? len / 2 : len / 4;
+        dxtlt::EstimateSection secs[10];
+        int n = 0;
+        for (int m = 0; m < variants; ++m)
+            for (int sp = 0; sp < 2; ++sp)
+                secs[n++] = {arena + dxtlt::auto_section_offset((dxtlt::Format)format, blocks, m, sp != 0), colour_len};
+        const int alpha_first = n;
+        if (format == 3)
+            for (int sp = 0; sp < 2; ++sp)
+                secs[n++] = {arena + dxtlt::auto_alpha_section_offset(blocks, sp != 0), blocks * 2};
+        if (int32_t rc = estimate_enqueue(secs, (size_t)n, st, 0))
+            return rc;
+        if (int32_t rc = estimate_read_back((size_t)n, st, sizes))
+            return rc;
+        for (int i = 0; i < o.count; ++i) {
+            const Candidate c = o.order[i];
+            total[i] = (format == 3 ? sizes[alpha_first + (c.split_alpha ? 1 : 0)] : 0) + sizes[c.mode * 2 + (c.split_colour ? 1 : 0)];
+        }
+    } else {
+        // BC4 / BC5 with the arena: both transforms side by side (the winner is transformed once more, into d_out: a copy out of
+        // the arena would still be reading it when this thread's next call fills it).  Without it: one full transform per
+        // candidate into d_out, estimated there before the next one overwrites it (stream order); the counters come back once.
+        int shown_per = 1;
+        for (int i = 0; i < o.count; ++i) {
+            const Candidate c = o.order[i];
+            uint8_t* dst = arena != nullptr ? arena + (size_t)i * len : out8;
+            if (int32_t rc = enqueue(format, false, d_in, dst, blocks, c.mode, c.split_alpha, c.split_colour, st))
+                return rc;
+            if (arena == nullptr)
+                last = i;
+            dxtlt::EstimateSection secs[2];
+            shown_per = shown(dst, secs);
+            if (int32_t rc = estimate_enqueue(secs, (size_t)shown_per, st, (size_t)(i * 2)))
+                return rc;
+        }
+        if (int32_t rc = estimate_read_back((size_t)o.count * 2, st, sizes))
+            return rc;
+        for (int i = 0; i < o.count; ++i)
+            total[i] = sizes[2 * i] + (shown_per == 2 ? sizes[2 * i + 1] : 0);
+    }
+
+    int pick = 0;
+    for (int i = 1; i < o.count; ++i)
+        if (total[i] < total[pick])   // strict: the first best wins
+            pick = i;
+    *best = o.order[pick];
+    if (pick != last)
+        return enqueue(format, false, d_in, d_out, blocks, best->mode, best->split_alpha, best->split_colour, st);
+    return kOk;
+}
+
+void report(const Candidate& c, dxtlt_host::AutoChoice* choice)
+{
+    choice->mode = c.mode;
+    choice->split_alpha = c.split_alpha;
+    choice->split_colour = c.split_colour;
+    choice->estimator_error = 0;
+}
+
+// dxtlt_host::transform_auto / transform_auto_bc45 given the built-in estimator (arguments validated by the caller)
+int32_t auto_builtin_host(int32_t format, const uint8_t* in, uint8_t* out, size_t len, bool use_all, dxtlt_host::AutoChoice* choice)
+{
+    using namespace dxtlt_host;
+    Candidate best = candidates_of(format, use_all).order[0];   // every estimate of an empty buffer is 0: the first candidate stays
+    if (len > 0) {
+        void *d_in = nullptr, *d_out = nullptr;
+        hipStream_t st = nullptr;
+        if (int32_t rc = acquire_staging(len, &d_in, &d_out, &st))
+            return rc;
+        hipError_t e = hipMemcpyAsync(d_in, in, len, hipMemcpyHostToDevice, st);
+        int32_t rc = e == hipSuccess ? auto_on_device(format, d_in, d_out, len, use_all, st, &best) : fail(kDevice, "H2D copy", e);
+        if (rc == kOk && (e = hipMemcpyAsync(out, d_out, len, hipMemcpyDeviceToHost, st)) != hipSuccess)
+            rc = fail(kDevice, "D2H result", e);
+        e = hipStreamSynchronize(st);   // on every exit: the staging buffers and the arena belong to this thread's next call
+        if (rc == kOk && e != hipSuccess)
+            rc = fail(kDevice, "stream synchronize", e);
+        if (rc != kOk)
+            return rc;
+    }
+    report(best, choice);
+    return kOk;
+}
 }  // namespace
 
 extern "C" void dxtlt_set_auto_estimator_threads(int32_t threads)
@@ -254,6 +416,7 @@ void dxtlt_host::release_auto_thread_arena()
 {
     g_arena.release();
     g_stage.release();
+    release_estimate_thread_counters();
 }
 
 int32_t dxtlt_host::transform_auto(int32_t format, const uint8_t* in, uint8_t* out, size_t len,
@@ -269,6 +432,10 @@ int32_t dxtlt_host::transform_auto(int32_t format, const uint8_t* in, uint8_t* o
     if (len > 0 && (in == nullptr || out == nullptr))
         return fail(kInvalidArgument, "NULL buffer with len > 0");
 
+    t_section_bytes_downloaded = t_estimator_callbacks = 0;
+    if (is_builtin_estimator(est))
+        return auto_builtin_host(format, in, out, len, use_all, choice);
+
     const uint64_t blocks = len / block;
     // defaults: Bc1/Bc2 {Variant1, split}, Bc3 {Variant1, split alphas, split colours}
     Candidate best{1, format == 3, true};
@@ -282,7 +449,7 @@ int32_t dxtlt_host::transform_auto(int32_t format, const uint8_t* in, uint8_t* o
     const size_t alpha_len = format == 3 ? (size_t)blocks * 2 : 0;
 
     size_t max_comp = 0;
-    uint32_t rc_est = est->MaxCompressedSize(est->Context, format == 1 ? len / 2 : len / 4, &max_comp);
+    uint32_t rc_est = call_max(est, format == 1 ? len / 2 : len / 4, &max_comp);
     if (rc_est != 0) {
         choice->estimator_error = rc_est;
         return fail(kEstimator, "size estimator: max_compressed_size failed");
@@ -377,10 +544,10 @@ int32_t dxtlt_host::transform_auto(int32_t format, const uint8_t* in, uint8_t* o
         uint8_t* slot = stage + (size_t)(i & 1) * slot_bytes;
         hipError_t e = hipSuccess;
         if (alpha_len)
-            e = hipMemcpyAsync(slot, arena + dxtlt::auto_alpha_section_offset(blocks, c.split_alpha), alpha_len, hipMemcpyDeviceToHost, st);
+            e = download_section(slot, arena + dxtlt::auto_alpha_section_offset(blocks, c.split_alpha), alpha_len, st);
         if (e == hipSuccess)
-            e = hipMemcpyAsync(slot + alpha_slot, arena + dxtlt::auto_section_offset((dxtlt::Format)format, blocks, c.mode, c.split_colour),
-                               colour_len, hipMemcpyDeviceToHost, st);
+            e = download_section(slot + alpha_slot, arena + dxtlt::auto_section_offset((dxtlt::Format)format, blocks, c.mode, c.split_colour),
+                                 colour_len, st);
         return e;
     };
     if (stage != nullptr)
@@ -412,9 +579,8 @@ int32_t dxtlt_host::transform_auto(int32_t format, const uint8_t* in, uint8_t* o
                 last = c;
             }
             if (alpha_len)
-                AUTO_TRY(hipMemcpyAsync(out, alpha_src, alpha_len, hipMemcpyDeviceToHost, st), "D2H alpha endpoints");
-            AUTO_TRY(hipMemcpyAsync(out + colour_off, colour_src, colour_len, hipMemcpyDeviceToHost, st),
-                     "D2H colour endpoints");
+                AUTO_TRY(download_section(out, alpha_src, alpha_len, st), "D2H alpha endpoints");
+            AUTO_TRY(download_section(out + colour_off, colour_src, colour_len, st), "D2H colour endpoints");
             AUTO_TRY(hipStreamSynchronize(st), "stream synchronize");
         } else {
             last = c;
@@ -422,15 +588,15 @@ int32_t dxtlt_host::transform_auto(int32_t format, const uint8_t* in, uint8_t* o
 
         size_t total = 0, part = 0;
         if (format == 3) {
-            rc_est = est->EstimateCompressedSize(est->Context, shown_alpha, alpha_len, scratch, max_comp, &part);
+            rc_est = call_estimate(est, shown_alpha, alpha_len, scratch, max_comp, &part);
             if (rc_est == 0) {
                 total = part;
                 part = 0;
-                rc_est = est->EstimateCompressedSize(est->Context, shown_colour, colour_len, scratch, max_comp, &part);
+                rc_est = call_estimate(est, shown_colour, colour_len, scratch, max_comp, &part);
                 total += part;
             }
         } else {
-            rc_est = est->EstimateCompressedSize(est->Context, shown_colour, colour_len, scratch, max_comp, &total);
+            rc_est = call_estimate(est, shown_colour, colour_len, scratch, max_comp, &total);
         }
         if (rc_est != 0) {
             if (st) (void)hipStreamSynchronize(st);   // a download of the next candidate may be in flight
@@ -464,6 +630,36 @@ int32_t dxtlt_host::transform_auto(int32_t format, const uint8_t* in, uint8_t* o
     return kOk;
 }
 
+int32_t dxtlt_host::transform_auto_device(int32_t format, const void* d_in, void* d_out, size_t len, bool use_all, hipStream_t st,
+                                          AutoChoice* choice)
+{
+    if (format < 1 || format > 5)
+        return fail(kInvalidArgument, "format must be 1..5 (BC1..BC5)");
+    if (len % (format == 1 || format == 4 ? 8 : 16) != 0)
+        return fail(kInvalidLength, "len is not a multiple of the block size");
+    if (choice == nullptr)
+        return fail(kInvalidArgument, "NULL choice");
+    if (len > 0 && (d_in == nullptr || d_out == nullptr))
+        return fail(kInvalidArgument, "NULL buffer with len > 0");
+    t_section_bytes_downloaded = t_estimator_callbacks = 0;
+    use_all = use_all && format <= 3;
+    Candidate best = candidates_of(format, use_all).order[0];
+    if (len > 0) {
+        int count = 0;
+        hipError_t e = hipGetDeviceCount(&count);
+        if (e != hipSuccess || count <= 0)
+            return fail(kNoDevice, "no HIP device available (this library has no CPU fallback)", e);
+        if (stream_is_capturing(st))
+            return fail(kInvalidArgument, "the auto transforms read their estimates back and wait for the stream: not capturable");
+        if (int32_t rc = auto_on_device(format, d_in, d_out, len, use_all, st, &best)) {
+            (void)hipStreamSynchronize(st);   // the arena belongs to this thread's next call
+            return rc;
+        }
+    }
+    report(best, choice);
+    return kOk;
+}
+
 // BC4 / BC5 (include/dxtlt_bc45.h): two candidates, split_endpoints = false then true.  Both forward transforms go into a device
 // arena of 2 x len (one upload, two launches); the estimator sees each candidate's endpoint section(s) -- BC4 [0, 2N), BC5 red
 // [0, 2N) then green [8N, 10N), added -- and the winner's arena copy is what is downloaded.  Without the arena the candidates run one
@@ -481,6 +677,10 @@ int32_t dxtlt_host::transform_auto_bc45(int32_t format, const uint8_t* in, uint8
     if (len > 0 && (in == nullptr || out == nullptr))
         return fail(kInvalidArgument, "NULL buffer with len > 0");
 
+    t_section_bytes_downloaded = t_estimator_callbacks = 0;
+    if (is_builtin_estimator(est))
+        return auto_builtin_host(format, in, out, len, false, choice);
+
     const uint64_t blocks = len / block;
     const int n_sections = format == 5 ? 2 : 1;
     const size_t section_len = (size_t)blocks * 2;              // every section: one endpoint pair (or a0 run + a1 run) per block
@@ -492,7 +692,7 @@ int32_t dxtlt_host::transform_auto_bc45(int32_t format, const uint8_t* in, uint8
     choice->estimator_error = 0;
 
     size_t max_comp = 0;
-    uint32_t rc_est = est->MaxCompressedSize(est->Context, section_len, &max_comp);
+    uint32_t rc_est = call_max(est, section_len, &max_comp);
     if (rc_est != 0) {
         choice->estimator_error = rc_est;
         return fail(kEstimator, "size estimator: max_compressed_size failed");
@@ -576,14 +776,13 @@ int32_t dxtlt_host::transform_auto_bc45(int32_t format, const uint8_t* in, uint8
                 }
                 // the section(s) travel into the output buffer at the offsets they are estimated at
                 for (int h = 0; h < n_sections; ++h)
-                    AUTO_TRY(hipMemcpyAsync(out + section_off[h], src + section_off[h], section_len, hipMemcpyDeviceToHost, st),
-                             "D2H endpoint section");
+                    AUTO_TRY(download_section(out + section_off[h], src + section_off[h], section_len, st), "D2H endpoint section");
                 AUTO_TRY(hipStreamSynchronize(st), "stream synchronize");
             }
             size_t total = 0;
             for (int h = 0; h < n_sections; ++h) {
                 size_t part = 0;
-                rc_est = est->EstimateCompressedSize(est->Context, out + section_off[h], section_len, scratch, max_comp, &part);
+                rc_est = call_estimate(est, out + section_off[h], section_len, scratch, max_comp, &part);
                 if (rc_est != 0)
                     return fail_estimate(rc_est);
                 total += part;
@@ -678,6 +877,94 @@ int32_t dxtlt_transform_bc3_auto(const uint8_t* input_ptr, uint8_t* output_ptr, 
         if (out_split_colour_endpoints) *out_split_colour_endpoints = c.split_colour;
     }
     return rc;
+}
+
+// ---- include/dxtlt_estimator.h: device pointers, the built-in estimator ------------------------------------------------------
+int32_t dxtlt_transform_bc1_auto_device(const void* d_input, void* d_output, size_t len, bool use_all_decorrelation_modes,
+                                        void* hip_stream, uint8_t* out_decorrelation_mode, bool* out_split_colour_endpoints)
+{
+    dxtlt_host::AutoChoice c{};
+    const int32_t rc = dxtlt_host::transform_auto_device(1, d_input, d_output, len, use_all_decorrelation_modes,
+                                                         static_cast<hipStream_t>(hip_stream), &c);
+    if (rc == DXTLT_OK) {
+        if (out_decorrelation_mode) *out_decorrelation_mode = c.mode;
+        if (out_split_colour_endpoints) *out_split_colour_endpoints = c.split_colour;
+    }
+    return rc;
+}
+
+int32_t dxtlt_transform_bc2_auto_device(const void* d_input, void* d_output, size_t len, bool use_all_decorrelation_modes,
+                                        void* hip_stream, uint8_t* out_decorrelation_mode, bool* out_split_colour_endpoints)
+{
+    dxtlt_host::AutoChoice c{};
+    const int32_t rc = dxtlt_host::transform_auto_device(2, d_input, d_output, len, use_all_decorrelation_modes,
+                                                         static_cast<hipStream_t>(hip_stream), &c);
+    if (rc == DXTLT_OK) {
+        if (out_decorrelation_mode) *out_decorrelation_mode = c.mode;
+        if (out_split_colour_endpoints) *out_split_colour_endpoints = c.split_colour;
+    }
+    return rc;
+}
+
+int32_t dxtlt_transform_bc3_auto_device(const void* d_input, void* d_output, size_t len, bool use_all_decorrelation_modes,
+                                        void* hip_stream, uint8_t* out_decorrelation_mode, bool* out_split_alpha_endpoints,
+                                        bool* out_split_colour_endpoints)
+{
+    dxtlt_host::AutoChoice c{};
+    const int32_t rc = dxtlt_host::transform_auto_device(3, d_input, d_output, len, use_all_decorrelation_modes,
+                                                         static_cast<hipStream_t>(hip_stream), &c);
+    if (rc == DXTLT_OK) {
+        if (out_decorrelation_mode) *out_decorrelation_mode = c.mode;
+        if (out_split_alpha_endpoints) *out_split_alpha_endpoints = c.split_alpha;
+        if (out_split_colour_endpoints) *out_split_colour_endpoints = c.split_colour;
+    }
+    return rc;
+}
+
+int32_t dxtlt_transform_bc4_auto_device(const void* d_input, void* d_output, size_t len, bool use_all_decorrelation_modes,
+                                        void* hip_stream, bool* out_split_endpoints)
+{
+    dxtlt_host::AutoChoice c{};
+    const int32_t rc = dxtlt_host::transform_auto_device(4, d_input, d_output, len, use_all_decorrelation_modes,
+                                                         static_cast<hipStream_t>(hip_stream), &c);
+    if (rc == DXTLT_OK && out_split_endpoints)
+        *out_split_endpoints = c.split_alpha;
+    return rc;
+}
+
+int32_t dxtlt_transform_bc5_auto_device(const void* d_input, void* d_output, size_t len, bool use_all_decorrelation_modes,
+                                        void* hip_stream, bool* out_split_endpoints)
+{
+    dxtlt_host::AutoChoice c{};
+    const int32_t rc = dxtlt_host::transform_auto_device(5, d_input, d_output, len, use_all_decorrelation_modes,
+                                                         static_cast<hipStream_t>(hip_stream), &c);
+    if (rc == DXTLT_OK && out_split_endpoints)
+        *out_split_endpoints = c.split_alpha;
+    return rc;
+}
+
+void dxtlt_debug_auto_last_estimation(uint64_t* out_section_bytes_downloaded, uint64_t* out_estimator_callbacks)
+{
+    if (out_section_bytes_downloaded) *out_section_bytes_downloaded = t_section_bytes_downloaded;
+    if (out_estimator_callbacks) *out_estimator_callbacks = t_estimator_callbacks;
+}
+
+void dxtlt_debug_auto_use_arena(int32_t on) { t_no_arena = on == 0; }
+
+int32_t dxtlt_debug_auto_candidates_device(int32_t format, bool use_all_decorrelation_modes, const void* d_input, size_t len,
+                                           void* hip_stream)
+{
+    using namespace dxtlt_host;
+    if (format < 1 || format > 3 || d_input == nullptr || len == 0 || len % (format == 1 ? 8 : 16) != 0)
+        return fail(kInvalidArgument, "format 1..3, a non-empty whole number of blocks");
+    const uint64_t blocks = len / (format == 1 ? 8 : 16);
+    void* arena = g_arena.get((size_t)dxtlt::auto_arena_bytes((dxtlt::Format)format, use_all_decorrelation_modes, blocks));
+    if (arena == nullptr)
+        return fail(kDevice, "candidate arena allocation failed", hipErrorOutOfMemory);
+    HIP_TRY(dxtlt::launch_auto_candidates((dxtlt::Format)format, use_all_decorrelation_modes, d_input, arena, blocks,
+                                          static_cast<hipStream_t>(hip_stream)),
+            "candidate kernel launch");
+    return kOk;
 }
 
 }  // extern "C"

@@ -1,0 +1,258 @@
+// estimate_api.cpp -- C ABI of the built-in size estimator (include/dxtlt_estimator.h) over estimate_kernels.hip, and the
+// per-thread counter block the auto transforms read their estimates back through (auto_transform.cpp).
+#include "../../include/dxtlt_estimator.h"
+#include "estimate_launch.h"
+#include "host_common.h"
+
+namespace {
+
+// this thread's counters on the current device and their pinned host copy (grow-never: kMaxCounters of 8 bytes each)
+struct Counters {
+    uint64_t* d = nullptr;
+    uint64_t* h = nullptr;
+    int device = -1;
+    ~Counters() { release(); }
+    void release()
+    {
+        if (d) (void)hipFree(d);
+        if (h) (void)hipHostFree(h);
+        d = h = nullptr;
+        device = -1;
+    }
+    bool get()
+    {
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess)
+            return false;
+        if (dev != device || d == nullptr) {
+            release();
+            if (hipMalloc(reinterpret_cast<void**>(&d), dxtlt_host::kMaxCounters * sizeof(uint64_t)) != hipSuccess ||
+                hipHostMalloc(reinterpret_cast<void**>(&h), dxtlt_host::kMaxCounters * sizeof(uint64_t), hipHostMallocDefault) != hipSuccess) {
+                (void)hipGetLastError();
+                release();
+                return false;
+            }
+            device = dev;
+        }
+        return true;
+    }
+};
+thread_local Counters g_counters;
+
+// dxtlt_estimate_size's own upload buffer and stream (grow-only, per thread and device).  NOT the staging of the host-pointer
+// transforms: this call is what an estimator callback makes from INSIDE an auto transform of the same thread, which keeps its
+// uploaded input in that staging for the whole call.
+struct UploadStage {
+    void* ptr = nullptr;
+    size_t cap = 0;
+    hipStream_t stream = nullptr;
+    int device = -1;
+    ~UploadStage() { release(); }
+    void release()
+    {
+        if (ptr) (void)hipFree(ptr);
+        if (stream) (void)hipStreamDestroy(stream);
+        ptr = nullptr;
+        stream = nullptr;
+        cap = 0;
+        device = -1;
+    }
+    hipError_t get(size_t bytes)
+    {
+        int dev = 0;
+        hipError_t e = hipGetDevice(&dev);
+        if (e != hipSuccess)
+            return e;
+        if (dev != device)
+            release();
+        if (stream == nullptr) {
+            if ((e = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking)) != hipSuccess) {
+                stream = nullptr;
+                return e;
+            }
+            device = dev;
+        }
+        if (bytes > cap) {
+            if (ptr) (void)hipFree(ptr);
+            ptr = nullptr;
+            cap = 0;
+            if ((e = hipMalloc(&ptr, bytes)) != hipSuccess) {
+                ptr = nullptr;
+                return e;
+            }
+            cap = bytes;
+        }
+        return hipSuccess;
+    }
+};
+thread_local UploadStage g_upload;
+
+int32_t need_device()
+{
+    int count = 0;
+    hipError_t e = hipGetDeviceCount(&count);
+    if (e != hipSuccess || count <= 0)
+        return dxtlt_host::fail(dxtlt_host::kNoDevice, "no HIP device available (this library has no CPU fallback)", e);
+    return dxtlt_host::kOk;
+}
+
+uint32_t builtin_max_compressed_size(void*, size_t, size_t* out_size)
+{
+    if (out_size)
+        *out_size = 0;
+    return 0;
+}
+
+uint32_t builtin_estimate_compressed_size(void*, const uint8_t* input_ptr, size_t len_bytes, uint8_t*, size_t, size_t* out_size)
+{
+    uint64_t v = 0;
+    const int32_t rc = dxtlt_estimate_size(input_ptr, len_bytes, &v);
+    if (rc == DXTLT_OK && out_size)
+        *out_size = static_cast<size_t>(v);
+    return static_cast<uint32_t>(rc);
+}
+
+const DltSizeEstimator kBuiltin = {nullptr, builtin_max_compressed_size, builtin_estimate_compressed_size};
+
+}  // namespace
+
+void dxtlt_host::release_estimate_thread_counters()
+{
+    g_counters.release();
+    g_upload.release();
+}
+
+bool dxtlt_host::is_builtin_estimator(const DltSizeEstimator* est)
+{
+    return est != nullptr && est->MaxCompressedSize == builtin_max_compressed_size &&
+           est->EstimateCompressedSize == builtin_estimate_compressed_size;
+}
+
+int32_t dxtlt_host::estimate_enqueue(const dxtlt::EstimateSection* sections, size_t count, hipStream_t st, size_t first_counter)
+{
+    if (first_counter + count > kMaxCounters)
+        return fail(kInvalidArgument, "more estimates than this thread's counter block holds");
+    if (!g_counters.get())
+        return fail(kDevice, "estimator counters: allocation failed", hipErrorOutOfMemory);
+    hipError_t e = dxtlt::launch_estimate(sections, count, g_counters.d + first_counter, st);
+    if (e == hipErrorInvalidValue)
+        return fail(kInvalidArgument, "a section of more than 2^31 - 1 windows");
+    HIP_TRY(e, "estimator launch");
+    return kOk;
+}
+
+int32_t dxtlt_host::estimate_read_back(size_t count, hipStream_t st, uint64_t* out)
+{
+    if (count > kMaxCounters || !g_counters.get())
+        return fail(kInvalidArgument, "estimator counters: nothing to read");
+    HIP_TRY(hipMemcpyAsync(g_counters.h, g_counters.d, count * sizeof(uint64_t), hipMemcpyDeviceToHost, st), "D2H estimates");
+    HIP_TRY(hipStreamSynchronize(st), "stream synchronize");
+    for (size_t i = 0; i < count; ++i)
+        out[i] = g_counters.h[i];
+    return kOk;
+}
+
+bool dxtlt_host::stream_is_capturing(hipStream_t st)
+{
+    hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &status) != hipSuccess) {
+        // e.g. the legacy default stream while another stream captures in global mode: not provably outside a capture
+        (void)hipGetLastError();
+        return true;
+    }
+    return status != hipStreamCaptureStatusNone;
+}
+
+extern "C" {
+
+uint32_t dxtlt_estimator_version(void) { return dxtlt::kEstimatorVersion; }
+
+const DltSizeEstimator* dxtlt_builtin_size_estimator(void) { return &kBuiltin; }
+
+int32_t dxtlt_debug_estimate_sizes_shape(const DxtltEstimateSection* sections, size_t count, void* hip_stream, uint64_t* d_out,
+                                         int32_t lanes, uint32_t window, uint32_t bits)
+{
+    using namespace dxtlt_host;
+    if (count == 0)
+        return kOk;
+    if (sections == nullptr || d_out == nullptr || reinterpret_cast<uintptr_t>(d_out) % 8 != 0)
+        return fail(kInvalidArgument, "NULL sections / d_out with count > 0, or d_out not 8-byte aligned");
+    if (int32_t rc = need_device())
+        return rc;
+    hipError_t e = dxtlt::launch_estimate_shape(reinterpret_cast<const dxtlt::EstimateSection*>(sections), count, d_out,
+                                                static_cast<hipStream_t>(hip_stream), lanes, window, bits);
+    if (e == hipErrorInvalidValue)
+        return fail(kInvalidArgument, "lanes / window / bits not compiled in, or a section of more than 2^31 - 1 windows");
+    HIP_TRY(e, "estimator launch");
+    return kOk;
+}
+
+int32_t dxtlt_estimate_sizes_device(const DxtltEstimateSection* sections, size_t count, void* hip_stream, uint64_t* d_out)
+{
+    using namespace dxtlt_host;
+    if (count == 0)
+        return kOk;
+    if (sections == nullptr || d_out == nullptr)
+        return fail(kInvalidArgument, "NULL sections / d_out with count > 0");
+    if (reinterpret_cast<uintptr_t>(d_out) % 8 != 0)
+        return fail(kInvalidArgument, "d_out is not 8-byte aligned");
+    if (int32_t rc = need_device())
+        return rc;
+    static_assert(sizeof(DxtltEstimateSection) == sizeof(dxtlt::EstimateSection), "one layout");
+    hipError_t e = dxtlt::launch_estimate(reinterpret_cast<const dxtlt::EstimateSection*>(sections), count, d_out,
+                                          static_cast<hipStream_t>(hip_stream));
+    if (e == hipErrorInvalidValue)
+        return fail(kInvalidArgument, "a section of more than 2^31 - 1 windows");
+    HIP_TRY(e, "estimator launch");
+    return kOk;
+}
+
+int32_t dxtlt_estimate_size_device(const void* d_ptr, size_t len, void* hip_stream, uint64_t* out)
+{
+    using namespace dxtlt_host;
+    if (out == nullptr)
+        return fail(kInvalidArgument, "NULL out");
+    if (d_ptr == nullptr || len < 4) {   // no gram (docs/ESTIMATOR.md): nothing to ask a device
+        *out = len;
+        return kOk;
+    }
+    if (int32_t rc = need_device())
+        return rc;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    if (stream_is_capturing(st))
+        return fail(kInvalidArgument, "dxtlt_estimate_size_device waits for its stream: not capturable (dxtlt_estimate_sizes_device is)");
+    const dxtlt::EstimateSection s{d_ptr, len};
+    if (int32_t rc = estimate_enqueue(&s, 1, st, 0))
+        return rc;
+    return estimate_read_back(1, st, out);
+}
+
+int32_t dxtlt_estimate_size(const uint8_t* host_ptr, size_t len, uint64_t* out)
+{
+    using namespace dxtlt_host;
+    if (out == nullptr)
+        return fail(kInvalidArgument, "NULL out");
+    if (host_ptr == nullptr || len < 4) {
+        *out = len;
+        return kOk;
+    }
+    if (int32_t rc = need_device())
+        return rc;
+    HIP_TRY(g_upload.get(len), "estimator upload buffer / stream");
+    hipStream_t st = g_upload.stream;
+    hipError_t e = hipMemcpyAsync(g_upload.ptr, host_ptr, len, hipMemcpyHostToDevice, st);
+    int32_t rc = kOk;
+    if (e != hipSuccess) {
+        rc = fail(kDevice, "H2D copy", e);
+    } else {
+        const dxtlt::EstimateSection s{g_upload.ptr, len};
+        rc = estimate_enqueue(&s, 1, st, 0);
+        if (rc == kOk)
+            rc = estimate_read_back(1, st, out);
+    }
+    if (rc != kOk)
+        (void)hipStreamSynchronize(st);   // the upload buffer belongs to this thread's next call
+    return rc;
+}
+
+}  // extern "C"

@@ -11,6 +11,7 @@
 
 #include "../../include/dlt_size_estimator.h"
 #include "../../include/dxtlt_gfx950.h"
+#include "estimate_launch.h"
 
 namespace dxtlt_host {
 
@@ -154,5 +155,21 @@ int32_t transform_auto(int32_t format, const uint8_t* in, uint8_t* out, size_t l
 // dxtlt_transform_bc{4,5}_auto on host pointers, format 4 or 5 (auto_transform.cpp): choice->split_alpha = split_endpoints
 int32_t transform_auto_bc45(int32_t format, const uint8_t* in, uint8_t* out, size_t len, const DltSizeEstimator* estimator,
                             AutoChoice* choice);
+
+// dxtlt_transform_bcN_auto_device (include/dxtlt_estimator.h), format 1..5: device pointers, the built-in estimator, one small
+// readback; the winning transform is left enqueued on `stream`.
+int32_t transform_auto_device(int32_t format, const void* d_in, void* d_out, size_t len, bool use_all_decorrelation_modes,
+                              hipStream_t stream, AutoChoice* choice);
+
+// ---- estimate_api.cpp: the built-in estimator (include/dxtlt_estimator.h) -----------------------------------------
+bool is_builtin_estimator(const DltSizeEstimator* estimator);   // by the identity of its two function pointers
+// This thread's counter block on the current device: kMaxCounters estimates (BC3 with every mode, one full transform per
+// candidate: 16 x 2).  estimate_enqueue puts the estimates of `count` sections into counters [first_counter, + count) on
+// `stream`; estimate_read_back copies counters [0, count) to `out` and waits for the stream.
+constexpr size_t kMaxCounters = 32;
+int32_t estimate_enqueue(const dxtlt::EstimateSection* sections, size_t count, hipStream_t stream, size_t first_counter);
+int32_t estimate_read_back(size_t count, hipStream_t stream, uint64_t* out);
+bool stream_is_capturing(hipStream_t stream);
+void release_estimate_thread_counters();   // of dxtlt_release_thread_resources(), through release_auto_thread_arena()
 
 }  // namespace dxtlt_host

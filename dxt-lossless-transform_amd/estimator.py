@@ -1,0 +1,162 @@
+"""The built-in, device-resident size estimator (docs/ESTIMATOR.md, version 1) and the auto transforms that use it without
+moving a section over PCIe.  Thin ctypes layer over include/dxtlt_estimator.h, the same buffer conventions as bc6h.py: host
+buffers (bytes, numpy) or contiguous uint8 torch CUDA tensors."""
+from __future__ import annotations
+
+import ctypes as C
+
+from . import _lib
+
+MAXFN = C.CFUNCTYPE(C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t))
+ESTFN = C.CFUNCTYPE(C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t))
+
+
+class DltSizeEstimator(C.Structure):            # include/dlt_size_estimator.h
+    _fields_ = [("Context", C.c_void_p), ("MaxCompressedSize", MAXFN), ("EstimateCompressedSize", ESTFN)]
+
+
+class Section(C.Structure):                     # DxtltEstimateSection
+    _fields_ = [("d_ptr", C.c_void_p), ("len", C.c_uint64)]
+
+
+_own = None
+
+
+def _l():
+    """A ctypes handle of this module's own on the loaded library: the argument types declared here (the host-pointer auto calls
+    among them) are not shared with other declarations of the same symbols."""
+    global _own
+    if _own is None:
+        _lib.load()
+        l = C.CDLL(_lib.lib_path(), mode=C.RTLD_GLOBAL)
+        vp, sz, i32, b = C.c_void_p, C.c_size_t, C.c_int32, C.c_bool
+        u8p, bp, u64p = C.POINTER(C.c_uint8), C.POINTER(C.c_bool), C.POINTER(C.c_uint64)
+        l.dxtlt_estimator_version.argtypes, l.dxtlt_estimator_version.restype = [], C.c_uint32
+        l.dxtlt_estimate_sizes_device.argtypes, l.dxtlt_estimate_sizes_device.restype = [C.POINTER(Section), sz, vp, vp], i32
+        l.dxtlt_estimate_size_device.argtypes, l.dxtlt_estimate_size_device.restype = [vp, sz, vp, u64p], i32
+        l.dxtlt_estimate_size.argtypes, l.dxtlt_estimate_size.restype = [vp, sz, u64p], i32
+        l.dxtlt_builtin_size_estimator.argtypes, l.dxtlt_builtin_size_estimator.restype = [], C.POINTER(DltSizeEstimator)
+        for n in ("bc1", "bc2"):
+            f = getattr(l, f"dxtlt_transform_{n}_auto_device")
+            f.argtypes, f.restype = [vp, vp, sz, b, vp, u8p, bp], i32
+            f = getattr(l, f"dxtlt_transform_{n}_auto")
+            f.argtypes, f.restype = [vp, vp, sz, C.POINTER(DltSizeEstimator), b, u8p, bp, C.POINTER(C.c_uint32)], i32
+        l.dxtlt_transform_bc3_auto_device.argtypes, l.dxtlt_transform_bc3_auto_device.restype = [vp, vp, sz, b, vp, u8p, bp, bp], i32
+        l.dxtlt_transform_bc3_auto.argtypes = [vp, vp, sz, C.POINTER(DltSizeEstimator), b, u8p, bp, bp, C.POINTER(C.c_uint32)]
+        l.dxtlt_transform_bc3_auto.restype = i32
+        for n in ("bc4", "bc5"):
+            f = getattr(l, f"dxtlt_transform_{n}_auto_device")
+            f.argtypes, f.restype = [vp, vp, sz, b, vp, bp], i32
+            f = getattr(l, f"dxtlt_transform_{n}_auto")
+            f.argtypes, f.restype = [vp, vp, sz, C.POINTER(DltSizeEstimator), bp], i32
+        l.dxtlt_debug_auto_last_estimation.argtypes, l.dxtlt_debug_auto_last_estimation.restype = [u64p, u64p], None
+        l.dxtlt_debug_auto_use_arena.argtypes, l.dxtlt_debug_auto_use_arena.restype = [i32], None
+        l.dxtlt_debug_estimate_sizes_shape.argtypes = [C.POINTER(Section), sz, vp, vp, i32, C.c_uint32, C.c_uint32]
+        l.dxtlt_debug_estimate_sizes_shape.restype = i32
+        l.dxtlt_debug_auto_candidates_device.argtypes, l.dxtlt_debug_auto_candidates_device.restype = [i32, b, vp, sz, vp], i32
+        _own = l
+    return _own
+
+
+def _check(rc: int) -> None:
+    from . import DeviceError
+
+    if rc != _lib.OK:
+        raise DeviceError(rc, _lib.last_error())
+
+
+def version() -> int:
+    return int(_l().dxtlt_estimator_version())
+
+
+def builtin_size_estimator():
+    """Pointer to the process-lifetime DltSizeEstimator; hand it to any *_auto entry point."""
+    return _l().dxtlt_builtin_size_estimator()
+
+
+def estimate_size(data) -> int:
+    """The estimate of one section: a host buffer (uploaded) or a device tensor (current stream; waits for it)."""
+    from . import _Buf
+
+    src = _Buf(data, False)
+    out = C.c_uint64()
+    l = _l()
+    if src.device is None:
+        _check(l.dxtlt_estimate_size(src.ptr, src.nbytes, C.byref(out)))
+    else:
+        import torch
+
+        with torch.cuda.device(src.device):
+            _check(l.dxtlt_estimate_size_device(src.ptr, src.nbytes, torch.cuda.current_stream().cuda_stream, C.byref(out)))
+    return int(out.value)
+
+
+def estimate_sizes(sections, out, shape=None) -> None:
+    """dxtlt_estimate_sizes_device: `sections` are device tensors, `out` an int64 / uint64 device tensor of as many elements.
+    Enqueues on the current stream and returns; nothing is synchronised.  `shape` = (lanes, window, bits) goes through the
+    test / bench hook dxtlt_debug_estimate_sizes_shape instead."""
+    import torch
+
+    from . import _Buf
+
+    bufs = [_Buf(s, False) for s in sections]
+    if any(b.device is None for b in bufs) or not out.is_cuda:
+        raise TypeError("estimate_sizes takes device tensors")
+    if out.element_size() != 8 or out.numel() < len(bufs) or not out.is_contiguous():
+        raise TypeError("out must be a contiguous 8-byte integer tensor with one element per section")
+    table = (Section * max(1, len(bufs)))()
+    for t, b in zip(table, bufs):
+        t.d_ptr, t.len = b.ptr, b.nbytes
+    with torch.cuda.device(out.device):
+        stream = torch.cuda.current_stream().cuda_stream
+        if shape is None:
+            _check(_l().dxtlt_estimate_sizes_device(table, len(bufs), stream, out.data_ptr()))
+        else:
+            _check(_l().dxtlt_debug_estimate_sizes_shape(table, len(bufs), stream, out.data_ptr(), *[int(v) for v in shape]))
+
+
+def transform_auto(fmt: str, input, output, use_all_decorrelation_modes: bool = False):
+    """transform_bcN_auto with the built-in estimator, fmt in bc1..bc5, on host buffers or device tensors.  Returns the
+    chosen settings object (Bc1TransformSettings ...); `output` holds the data transformed with them."""
+    from . import (BLOCK_BYTES, Bc1TransformSettings, Bc2TransformSettings, Bc3TransformSettings, Bc4TransformSettings,
+                   Bc5TransformSettings, InvalidLength, OutputBufferTooSmall, YCoCgVariant, _Buf)
+
+    src, dst = _Buf(input, False), _Buf(output, True)
+    if src.nbytes % BLOCK_BYTES[fmt] != 0:
+        raise InvalidLength(src.nbytes)
+    if dst.nbytes < src.nbytes:
+        raise OutputBufferTooSmall(src.nbytes, dst.nbytes)
+    if (src.device is None) != (dst.device is None):
+        raise TypeError("input and output must both be host buffers or both be device tensors")
+    l = _l()
+    mode, sa, sc = C.c_uint8(), C.c_bool(), C.c_bool()
+    outs = {"bc1": (C.byref(mode), C.byref(sc)), "bc2": (C.byref(mode), C.byref(sc)), "bc3": (C.byref(mode), C.byref(sa), C.byref(sc)),
+            "bc4": (C.byref(sa),), "bc5": (C.byref(sa),)}[fmt]
+    use_all = bool(use_all_decorrelation_modes)
+    if src.device is None:
+        f = getattr(l, f"dxtlt_transform_{fmt}_auto")
+        if fmt in ("bc4", "bc5"):
+            rc = f(src.ptr, dst.ptr, src.nbytes, builtin_size_estimator(), *outs)
+        else:
+            rc = f(src.ptr, dst.ptr, src.nbytes, builtin_size_estimator(), use_all, *outs, None)
+    else:
+        import torch
+
+        with torch.cuda.device(src.device):
+            rc = getattr(l, f"dxtlt_transform_{fmt}_auto_device")(src.ptr, dst.ptr, src.nbytes, use_all,
+                                                                  torch.cuda.current_stream().cuda_stream, *outs)
+    _check(rc)
+    if fmt == "bc1":
+        return Bc1TransformSettings(YCoCgVariant(mode.value), sc.value)
+    if fmt == "bc2":
+        return Bc2TransformSettings(YCoCgVariant(mode.value), sc.value)
+    if fmt == "bc3":
+        return Bc3TransformSettings(YCoCgVariant(mode.value), sa.value, sc.value)
+    return (Bc4TransformSettings if fmt == "bc4" else Bc5TransformSettings)(sa.value)
+
+
+def last_auto_estimation() -> tuple[int, int]:
+    """(section bytes downloaded, estimator callbacks) of the last auto transform called from this thread."""
+    a, b = C.c_uint64(), C.c_uint64()
+    _l().dxtlt_debug_auto_last_estimation(C.byref(a), C.byref(b))
+    return int(a.value), int(b.value)

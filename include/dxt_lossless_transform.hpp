@@ -32,6 +32,7 @@
 #include "dxtlt_bc7.h"
 #include "dxtlt_color565.h"
 #include "dxtlt_decode.h"
+#include "dxtlt_estimator.h"
 #include "dxtlt_gfx950.h"
 
 namespace dxt_lossless_transform {
@@ -261,6 +262,81 @@ std::pair<Bc3TransformSettings, DetermineBestTransformError> transform_bc3_auto(
 // safe to call from several threads at once.  Process-wide; 1 restores the reference's sequence of calls.
 inline void set_auto_estimator_threads(int threads) { dxtlt_set_auto_estimator_threads(threads); }
 inline int auto_estimator_threads() { return dxtlt_get_auto_estimator_threads(); }
+
+// ---- the built-in, device-resident size estimator (dxtlt_estimator.h, docs/ESTIMATOR.md; additive) ---------------
+// An estimator type for EstimateSettings<E>: transform_bcN_auto(.., EstimateSettings<BuiltinSizeEstimator>&) hands the library
+// its own vtable (the make_vtable specialisation below), which the auto transforms recognise -- every candidate section is
+// estimated on the device and no callback runs.  Its two methods serve any other caller of the estimator concept.
+struct BuiltinSizeEstimator {
+    bool max_compressed_size(size_t, size_t& out) const { out = 0; return true; }
+    bool estimate_compressed_size(const uint8_t* in, size_t len, uint8_t*, size_t, size_t& out) const
+    {
+        uint64_t v = 0;
+        if (dxtlt_estimate_size(in, len, &v) != DXTLT_OK) return false;
+        out = static_cast<size_t>(v);
+        return true;
+    }
+    static const DltSizeEstimator* vtable() { return dxtlt_builtin_size_estimator(); }
+    static uint32_t version() { return dxtlt_estimator_version(); }
+};
+namespace detail_auto {
+template <>
+inline DltSizeEstimator make_vtable<BuiltinSizeEstimator>(BuiltinSizeEstimator&)
+{
+    return *dxtlt_builtin_size_estimator();   // a copy keeps the two function pointers the library recognises
+}
+}  // namespace detail_auto
+inline uint64_t estimate_size(const uint8_t* host_ptr, size_t len)
+{
+    uint64_t v = 0;
+    detail::check_device(dxtlt_estimate_size(host_ptr, len, &v));
+    return v;
+}
+inline uint64_t estimate_size_device(const void* d_ptr, size_t len, void* hip_stream)
+{
+    uint64_t v = 0;
+    detail::check_device(dxtlt_estimate_size_device(d_ptr, len, hip_stream, &v));
+    return v;
+}
+inline void estimate_sizes_device(const DxtltEstimateSection* sections, size_t count, void* hip_stream, uint64_t* d_out)
+{
+    detail::check_device(dxtlt_estimate_sizes_device(sections, count, hip_stream, d_out));
+}
+// transform_bcN_auto on device pointers with the built-in estimator: waits for the stream once (not capturable)
+inline Bc1TransformSettings transform_bc1_auto_device(const void* d_input, void* d_output, size_t len, bool use_all, void* hip_stream)
+{
+    uint8_t mode = 1;
+    bool sc = true;
+    detail::check_device(dxtlt_transform_bc1_auto_device(d_input, d_output, len, use_all, hip_stream, &mode, &sc));
+    return Bc1TransformSettings{static_cast<YCoCgVariant>(mode), sc};
+}
+inline Bc2TransformSettings transform_bc2_auto_device(const void* d_input, void* d_output, size_t len, bool use_all, void* hip_stream)
+{
+    uint8_t mode = 1;
+    bool sc = true;
+    detail::check_device(dxtlt_transform_bc2_auto_device(d_input, d_output, len, use_all, hip_stream, &mode, &sc));
+    return Bc2TransformSettings{static_cast<YCoCgVariant>(mode), sc};
+}
+inline Bc3TransformSettings transform_bc3_auto_device(const void* d_input, void* d_output, size_t len, bool use_all, void* hip_stream)
+{
+    uint8_t mode = 1;
+    bool sa = true, sc = true;
+    detail::check_device(dxtlt_transform_bc3_auto_device(d_input, d_output, len, use_all, hip_stream, &mode, &sa, &sc));
+    return Bc3TransformSettings{static_cast<YCoCgVariant>(mode), sa, sc};
+}
+// BC4 / BC5 (dxtlt_bc45.h): returns split_endpoints
+inline bool transform_bc4_auto_device(const void* d_input, void* d_output, size_t len, void* hip_stream)
+{
+    bool split = false;
+    detail::check_device(dxtlt_transform_bc4_auto_device(d_input, d_output, len, false, hip_stream, &split));
+    return split;
+}
+inline bool transform_bc5_auto_device(const void* d_input, void* d_output, size_t len, void* hip_stream)
+{
+    bool split = false;
+    detail::check_device(dxtlt_transform_bc5_auto_device(d_input, d_output, len, false, hip_stream, &split));
+    return split;
+}
 
 // ---- dxt_lossless_transform_bc1::experimental::normalize_blocks (normalize.rs, transform.rs, mod.rs) ------------
 namespace experimental {

@@ -139,9 +139,58 @@ impl Drop for SerialEstimatorCalls {
 }
 
 pub(crate) fn vtable<T: SizeEstimationOperations>(bridge: &EstimatorBridge<T>) -> DltSizeEstimator {
+    // The library's own estimator travels as the library's own vtable: the auto transforms recognise its two function pointers
+    // and estimate on the device without a callback.  (No specialisation on stable Rust, and `T` need not be `'static`: the
+    // unit type is told by its size and its name.)
+    if core::mem::size_of::<T>() == 0 && core::any::type_name::<T>() == core::any::type_name::<BuiltinSizeEstimator>() {
+        // SAFETY: a process-lifetime object of three plain words
+        return unsafe { core::ptr::read(BuiltinSizeEstimator::c_vtable()) };
+    }
     DltSizeEstimator {
         context: bridge as *const EstimatorBridge<T> as *mut c_void,
         max_compressed_size: max_compressed_size::<T>,
         estimate_compressed_size: estimate_compressed_size::<T>,
+    }
+}
+
+// ---- the library's own estimator (include/dxtlt_estimator.h, docs/ESTIMATOR.md) -----------------------------------------
+
+/// The built-in, device-resident size estimator as a `SizeEstimationOperations`: no state, so a unit type, and `Sync` --
+/// every call is one reentrant FFI call.  `vtable::<BuiltinSizeEstimator>` above hands the auto bodies the library's own
+/// vtable, so the library recognises its estimator and estimates every candidate section where the candidate kernel left it;
+/// the trait methods below serve any other user of `SizeEstimationOperations` (each section is uploaded into a buffer of the
+/// call's own and estimated on the device, which is safe from inside an auto transform of the same thread too).
+#[derive(Clone, Copy, Debug, Default)]
+pub struct BuiltinSizeEstimator;
+
+// SAFETY: no data; `dxtlt_estimate_size` keeps its staging per calling thread.
+unsafe impl Sync for BuiltinSizeEstimator {}
+
+impl BuiltinSizeEstimator {
+    /// The process-lifetime C vtable the library recognises by identity.
+    pub fn c_vtable() -> *const DltSizeEstimator {
+        unsafe { dxtlt_gfx950_sys::dxtlt_builtin_size_estimator() }
+    }
+    /// 1: the definition in docs/ESTIMATOR.md.
+    pub fn version() -> u32 {
+        unsafe { dxtlt_gfx950_sys::dxtlt_estimator_version() }
+    }
+}
+
+impl SizeEstimationOperations for BuiltinSizeEstimator {
+    /// the `DXTLT_E_*` status of the failed call
+    type Error = i32;
+
+    fn max_compressed_size(&self, _len_bytes: usize) -> Result<usize, Self::Error> {
+        Ok(0)
+    }
+
+    unsafe fn estimate_compressed_size(&self, input_ptr: *const u8, len_bytes: usize, _output_ptr: *mut u8,
+        _output_len: usize) -> Result<usize, Self::Error> {
+        let mut size = 0u64;
+        match dxtlt_gfx950_sys::dxtlt_estimate_size(input_ptr, len_bytes, &mut size) {
+            0 => Ok(size as usize),
+            rc => Err(rc),
+        }
     }
 }

@@ -130,3 +130,36 @@ pub struct DxtltShardStat {
     pub blocks: u64,
     pub seconds: f64,
 }
+
+/// `DxtltEstimateSection` of include/dxtlt_estimator.h
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct DxtltEstimateSection {
+    pub d_ptr: *const c_void,
+    pub len: u64,
+}
+
+// ---- include/dxtlt_estimator.h: the built-in, device-resident size estimator (docs/ESTIMATOR.md) and the auto transforms
+// on device pointers.  (A block of its own: the first block mirrors include/dxtlt_gfx950.h alone.)
+extern "C" {
+    pub fn dxtlt_estimator_version() -> u32;
+    pub fn dxtlt_estimate_sizes_device(sections: *const DxtltEstimateSection, count: usize, hip_stream: *mut c_void,
+        d_out: *mut u64) -> i32;
+    pub fn dxtlt_estimate_size_device(d_ptr: *const c_void, len: usize, hip_stream: *mut c_void, out: *mut u64) -> i32;
+    pub fn dxtlt_estimate_size(host_ptr: *const u8, len: usize, out: *mut u64) -> i32;
+    /// process-lifetime vtable; the library's auto transforms recognise it and estimate on the device
+    pub fn dxtlt_builtin_size_estimator() -> *const DltSizeEstimator;
+    pub fn dxtlt_transform_bc1_auto_device(d_input: *const c_void, d_output: *mut c_void, len: usize,
+        use_all_decorrelation_modes: bool, hip_stream: *mut c_void, out_decorrelation_mode: *mut u8,
+        out_split_colour_endpoints: *mut bool) -> i32;
+    pub fn dxtlt_transform_bc2_auto_device(d_input: *const c_void, d_output: *mut c_void, len: usize,
+        use_all_decorrelation_modes: bool, hip_stream: *mut c_void, out_decorrelation_mode: *mut u8,
+        out_split_colour_endpoints: *mut bool) -> i32;
+    pub fn dxtlt_transform_bc3_auto_device(d_input: *const c_void, d_output: *mut c_void, len: usize,
+        use_all_decorrelation_modes: bool, hip_stream: *mut c_void, out_decorrelation_mode: *mut u8,
+        out_split_alpha_endpoints: *mut bool, out_split_colour_endpoints: *mut bool) -> i32;
+    pub fn dxtlt_transform_bc4_auto_device(d_input: *const c_void, d_output: *mut c_void, len: usize,
+        use_all_decorrelation_modes: bool, hip_stream: *mut c_void, out_split_endpoints: *mut bool) -> i32;
+    pub fn dxtlt_transform_bc5_auto_device(d_input: *const c_void, d_output: *mut c_void, len: usize,
+        use_all_decorrelation_modes: bool, hip_stream: *mut c_void, out_split_endpoints: *mut bool) -> i32;
+}
