@@ -112,6 +112,9 @@ thread_local Arena g_arena;
 // dxtlt_debug_auto_last_estimation: what the last auto call of this thread downloaded and called for its estimates
 thread_local uint64_t t_section_bytes_downloaded = 0, t_estimator_callbacks = 0;
 thread_local bool t_no_arena = false;   // dxtlt_debug_auto_use_arena(0): the built-in path as if the arena could not be allocated
+// dxtlt_debug_auto_last_totals: the totals the last built-in-estimator auto call of this thread compared, in candidate order
+thread_local uint64_t t_last_totals[16];
+thread_local int t_last_total_count = 0;
 
 uint32_t call_max(const DltSizeEstimator* est, size_t len, size_t* out)
 {
@@ -307,8 +310,11 @@ int32_t auto_on_device(int32_t format, const void* d_in, void* d_out, size_t len
     uint64_t total[16];
     int last = -1;   // the candidate whose transform is in d_out
 
+    // BC1-3: the candidate kernel reads the input as 16-byte vectors; an input off a 16-byte boundary takes the no-arena route,
+    // whose transform kernels take any alignment (one full transform per candidate instead of one read)
+    const bool vector_aligned = (reinterpret_cast<uintptr_t>(d_in) & 15) == 0;
     uint8_t* arena = nullptr;
-    if (!t_no_arena)
+    if (!t_no_arena && (format >= 4 || vector_aligned))
         arena = static_cast<uint8_t*>(g_arena.get(format >= 4 ? 2 * len : (size_t)dxtlt::auto_arena_bytes((dxtlt::Format)format, use_all, blocks)));
     if (arena != nullptr && format <= 3) {
         // one read of the input -> every distinct section: colour (variant, split) pairs, then BC3's two alpha-endpoint sections
@@ -360,8 +366,12 @@ int32_t auto_on_device(int32_t format, const void* d_in, void* d_out, size_t len
         if (total[i] < total[pick])   // strict: the first best wins
             pick = i;
     *best = o.order[pick];
-    if (pick != last)
-        return enqueue(format, false, d_in, d_out, blocks, best->mode, best->split_alpha, best->split_colour, st);
+    if (pick != last) {
+        if (int32_t rc = enqueue(format, false, d_in, d_out, blocks, best->mode, best->split_alpha, best->split_colour, st))
+            return rc;
+    }
+    std::copy(total, total + o.count, t_last_totals);
+    t_last_total_count = o.count;
     return kOk;
 }
 
@@ -390,8 +400,10 @@ int32_t auto_builtin_host(int32_t format, const uint8_t* in, uint8_t* out, size_
         e = hipStreamSynchronize(st);   // on every exit: the staging buffers and the arena belong to this thread's next call
         if (rc == kOk && e != hipSuccess)
             rc = fail(kDevice, "stream synchronize", e);
-        if (rc != kOk)
+        if (rc != kOk) {
+            t_last_total_count = 0;
             return rc;
+        }
     }
     report(best, choice);
     return kOk;
@@ -422,6 +434,7 @@ void dxtlt_host::release_auto_thread_arena()
 int32_t dxtlt_host::transform_auto(int32_t format, const uint8_t* in, uint8_t* out, size_t len,
                                    const DltSizeEstimator* est, bool use_all, AutoChoice* choice)
 {
+    t_last_total_count = 0;   // whatever this call does next: no totals of an earlier one
     if (format < 1 || format > 3)
         return fail(kInvalidArgument, "format must be 1 (BC1), 2 (BC2) or 3 (BC3)");
     const size_t block = format == 1 ? 8 : 16;
@@ -633,6 +646,7 @@ int32_t dxtlt_host::transform_auto(int32_t format, const uint8_t* in, uint8_t* o
 int32_t dxtlt_host::transform_auto_device(int32_t format, const void* d_in, void* d_out, size_t len, bool use_all, hipStream_t st,
                                           AutoChoice* choice)
 {
+    t_last_total_count = 0;   // whatever this call does next: no totals of an earlier one
     if (format < 1 || format > 5)
         return fail(kInvalidArgument, "format must be 1..5 (BC1..BC5)");
     if (len % (format == 1 || format == 4 ? 8 : 16) != 0)
@@ -667,6 +681,7 @@ int32_t dxtlt_host::transform_auto_device(int32_t format, const void* d_in, void
 int32_t dxtlt_host::transform_auto_bc45(int32_t format, const uint8_t* in, uint8_t* out, size_t len, const DltSizeEstimator* est,
                                         AutoChoice* choice)
 {
+    t_last_total_count = 0;   // whatever this call does next: no totals of an earlier one
     if (format != 4 && format != 5)
         return fail(kInvalidArgument, "format must be 4 (BC4) or 5 (BC5)");
     const size_t block = format == 4 ? 8 : 16;
@@ -947,6 +962,13 @@ void dxtlt_debug_auto_last_estimation(uint64_t* out_section_bytes_downloaded, ui
 {
     if (out_section_bytes_downloaded) *out_section_bytes_downloaded = t_section_bytes_downloaded;
     if (out_estimator_callbacks) *out_estimator_callbacks = t_estimator_callbacks;
+}
+
+int32_t dxtlt_debug_auto_last_totals(uint64_t* out_totals, int32_t cap)
+{
+    for (int i = 0; out_totals != nullptr && i < t_last_total_count && i < cap; ++i)
+        out_totals[i] = t_last_totals[i];
+    return t_last_total_count;
 }
 
 void dxtlt_debug_auto_use_arena(int32_t on) { t_no_arena = on == 0; }

@@ -50,6 +50,7 @@ def _l():
             f = getattr(l, f"dxtlt_transform_{n}_auto")
             f.argtypes, f.restype = [vp, vp, sz, C.POINTER(DltSizeEstimator), bp], i32
         l.dxtlt_debug_auto_last_estimation.argtypes, l.dxtlt_debug_auto_last_estimation.restype = [u64p, u64p], None
+        l.dxtlt_debug_auto_last_totals.argtypes, l.dxtlt_debug_auto_last_totals.restype = [u64p, i32], i32
         l.dxtlt_debug_auto_use_arena.argtypes, l.dxtlt_debug_auto_use_arena.restype = [i32], None
         l.dxtlt_debug_estimate_sizes_shape.argtypes = [C.POINTER(Section), sz, vp, vp, i32, C.c_uint32, C.c_uint32]
         l.dxtlt_debug_estimate_sizes_shape.restype = i32
@@ -160,3 +161,10 @@ def last_auto_estimation() -> tuple[int, int]:
     a, b = C.c_uint64(), C.c_uint64()
     _l().dxtlt_debug_auto_last_estimation(C.byref(a), C.byref(b))
     return int(a.value), int(b.value)
+
+
+def last_auto_totals() -> list[int]:
+    """The totals the last built-in-estimator auto transform called from this thread compared, in candidate order."""
+    buf = (C.c_uint64 * 16)()
+    n = _l().dxtlt_debug_auto_last_totals(buf, 16)
+    return [int(v) for v in buf[:n]]

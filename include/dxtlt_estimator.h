@@ -63,7 +63,11 @@ const DltSizeEstimator *dxtlt_builtin_size_estimator(void);
  * dxtlt_release_thread_resources).  The choice is made on the host from one readback of at most 32 counters, so these calls WAIT
  * for `hip_stream` once and are NOT capturable into a HIP graph: on a capturing stream they return DXTLT_E_INVALID_ARGUMENT
  * without enqueueing or synchronising anything (so does a stream whose capture state cannot be queried).  The winning transform
- * reads d_input only and is enqueued, not waited for. */
+ * reads d_input only and is enqueued, not waited for.
+ *
+ * d_input and d_output may have any alignment.  BC1 / BC2 / BC3 read a d_input on a 16-byte boundary once for all candidates;
+ * a d_input off a 16-byte boundary costs one full transform per candidate (4 / 8, BC3 8 / 16) into d_output, each estimated
+ * there in stream order -- the same choice and bytes, and still nothing downloaded.  BC4 / BC5 run both transforms either way. */
 int32_t dxtlt_transform_bc1_auto_device(const void *d_input, void *d_output, size_t len, bool use_all_decorrelation_modes,
                                         void *hip_stream, uint8_t *out_decorrelation_mode, bool *out_split_colour_endpoints);
 int32_t dxtlt_transform_bc2_auto_device(const void *d_input, void *d_output, size_t len, bool use_all_decorrelation_modes,
@@ -82,6 +86,10 @@ int32_t dxtlt_transform_bc5_auto_device(const void *d_input, void *d_output, siz
  * (MaxCompressedSize and EstimateCompressedSize).  Both are 0 with the built-in estimator.  Either pointer may be NULL. */
 void dxtlt_debug_auto_last_estimation(uint64_t *out_section_bytes_downloaded, uint64_t *out_estimator_callbacks);
 
+/* Test hook: the totals the last built-in-estimator auto transform of this thread compared, in candidate order;
+ * returns how many there were (0 after a callback-route call, an empty buffer or a failed call); writes at most cap. */
+int32_t dxtlt_debug_auto_last_totals(uint64_t *out_totals, int32_t cap);
+
 /* Test hook, per calling thread: 0 = the built-in path of the auto transforms behaves as if its candidate arena could not be
  * allocated (one full transform per candidate into the output buffer, estimated there); anything else = normal. */
 void dxtlt_debug_auto_use_arena(int32_t on);
@@ -94,7 +102,8 @@ int32_t dxtlt_debug_estimate_sizes_shape(const DxtltEstimateSection *sections, s
                                          int32_t lanes, uint32_t window, uint32_t bits);
 
 /* Bench hook: the fused candidate kernel of the auto transforms alone -- every candidate section of format 1..3 from the `len`
- * bytes at d_input into the calling thread's arena, enqueued on `hip_stream`. */
+ * bytes at d_input into the calling thread's arena, enqueued on `hip_stream`.  Unlike the auto transforms it takes the kernel as
+ * it is: d_input must be 16-byte aligned (DXTLT_E_DEVICE otherwise). */
 int32_t dxtlt_debug_auto_candidates_device(int32_t format, bool use_all_decorrelation_modes, const void *d_input, size_t len,
                                            void *hip_stream);
 

@@ -62,7 +62,7 @@ def test_every_declared_symbol_is_exported(lib):
     names = declared_functions()
     assert len(names) == len(set(names)) >= 13
     for n in ("dxtlt_estimate_sizes_device", "dxtlt_estimate_size_device", "dxtlt_estimate_size", "dxtlt_estimator_version",
-              "dxtlt_builtin_size_estimator", "dxtlt_debug_auto_last_estimation") + tuple(f"dxtlt_transform_bc{k}_auto_device" for k in range(1, 6)):
+              "dxtlt_builtin_size_estimator", "dxtlt_debug_auto_last_estimation", "dxtlt_debug_auto_last_totals") + tuple(f"dxtlt_transform_bc{k}_auto_device" for k in range(1, 6)):
         assert n in names, n
     for n in names:
         assert hasattr(lib, n), n
@@ -107,8 +107,12 @@ def test_without_a_device_the_calls_say_so(lib):
     m = C.c_uint8(9)
     lib.dxtlt_transform_bc3_auto_device.argtypes = [vp, vp, sz, C.c_bool, vp, vp, vp, vp]
     assert lib.dxtlt_transform_bc3_auto_device(None, None, 0, True, None, C.byref(m), None, None) == 0 and m.value == 2   # kAll3[0]
+    totals = (u64 * 16)(*([7] * 16))
+    lib.dxtlt_debug_auto_last_totals.argtypes, lib.dxtlt_debug_auto_last_totals.restype = [C.POINTER(u64), C.c_int32], C.c_int32
+    assert lib.dxtlt_debug_auto_last_totals(totals, 16) == 0 and lib.dxtlt_debug_auto_last_totals(None, 0) == 0   # an empty buffer
     y = np.zeros_like(x)
     assert lib.dxtlt_transform_bc3_auto_device(x.ctypes.data, y.ctypes.data, 24, True, None, None, None, None) == 1
+    assert lib.dxtlt_debug_auto_last_totals(totals, 16) == 0 and list(totals) == [7] * 16                          # a refused call
     if pkg_has_device(lib):
         return          # with a device the answers are numbers: tests/test_estimator_gpu.py
     assert lib.dxtlt_estimate_size(x.ctypes.data, x.size, C.byref(out)) == 3                        # DXTLT_E_NO_DEVICE
@@ -127,6 +131,7 @@ def test_without_a_device_the_calls_say_so(lib):
     lib.dxtlt_transform_bc1_auto.argtypes = [vp, vp, sz, vp, C.c_bool, vp, vp, vp]
     assert lib.dxtlt_transform_bc1_auto(x.ctypes.data, y.ctypes.data, x.size, est, False, None, None, None) == 3
     assert lib.dxtlt_transform_bc3_auto_device(x.ctypes.data, y.ctypes.data, x.size, True, None, None, None, None) == 3
+    assert lib.dxtlt_debug_auto_last_totals(totals, 16) == 0 and list(totals) == [7] * 16                          # no device, no totals
 
 
 def pkg_has_device(lib):

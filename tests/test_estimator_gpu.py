@@ -178,6 +178,35 @@ def test_many_sections_in_one_call(E, dev, count):
         assert int(got[guard + k]) == R.estimate(pool[o:o + n]), (k, o, n)
 
 
+def test_every_head_residue_with_every_short_length_and_window_edge(E, dev):
+    """The kernel's first and last vectors are masked by the pointer's residue mod 16 and by (residue + length) mod 16 together:
+    all 16 residues with every length 0..40 and the lengths around one and two windows, in one table."""
+    import torch
+
+    pool = np.random.default_rng(0xD17).integers(0, 3, 2 * W + 32, dtype=np.uint8)      # three byte values: matches everywhere
+    d = torch.from_numpy(pool).to(dev)
+    assert d.data_ptr() % 16 == 0                                                        # h below is the pointer's residue
+    short = list(range(0, 41))
+    lengths = short + list(range(W - 3, W + 4)) + list(range(2 * W - 3, 2 * W + 4))
+    secs = [(h, n) for n in lengths for h in range(16)]
+    want = [R.estimate(pool[h:h + n]) for h, n in secs]
+    assert len(secs) == 55 * 16 and all(w < n for (h, n), w in zip(secs, want) if n >= 16)  # matches are counted, not lengths alone
+    guard = 8
+
+    def check(count, shape):
+        out = torch.full((count + 2 * guard,), 0x5A5A5A5A5A5A5A5A, dtype=torch.int64, device=dev)
+        E.estimate_sizes([d[h:h + n] for h, n in secs[:count]], out[guard:guard + count], shape=shape)
+        torch.cuda.synchronize()
+        got = out.cpu().numpy()
+        assert (got[:guard] == 0x5A5A5A5A5A5A5A5A).all() and (got[guard + count:] == 0x5A5A5A5A5A5A5A5A).all(), shape
+        bad = [(secs[k], int(got[guard + k]), want[k]) for k in range(count) if int(got[guard + k]) != want[k]]
+        assert not bad, (shape, len(bad), bad[:8])
+
+    check(len(secs), None)
+    for lanes in (256, 512):                                  # the other workgroup sizes: the same masks over another stride
+        check(len(short) * 16, (lanes, W, R.BITS))
+
+
 def test_host_pointer_call_and_vtable_callback(E, lib):
     est = lib.dxtlt_builtin_size_estimator().contents
     size = C.c_size_t(123)
@@ -246,6 +275,8 @@ def auto_inputs(fmt, oracle):
     for n in (2, 255, 8191, 33_333):
         x = rng.integers(0, 256, n * block, dtype=np.uint8).reshape(n, block)
         x[:, :block // 2] = (np.arange(n)[:, None] // (7 + n % 5) + np.arange(block // 2)[None, :] * 3) & 0xFF   # endpoints that repeat
+        if fmt in ("bc2", "bc3"):
+            x[:, 8:12] = x[:, 0:4] * 5 + 1                        # their colour endpoints too, or every colour section estimates alike
         xs.append(x.reshape(-1))
     return xs
 
