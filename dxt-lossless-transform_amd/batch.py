@@ -119,3 +119,11 @@ def transform_batch_host(items: Sequence[Tuple[str, bool, object, object, object
     if not items:
         return
     run_prepared_batch_host(prepare_batch_host(items))
+
+
+def transform_batch_auto(items):
+    """items: (fmt, input tensor, output tensor, use_all_decorrelation_modes): the best settings chosen per item on the device and
+    every item transformed with them, in one call (estimator.transform_batch_auto).  Returns the chosen settings objects."""
+    from . import estimator
+
+    return estimator.transform_batch_auto(items)

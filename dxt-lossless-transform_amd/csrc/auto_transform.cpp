@@ -429,6 +429,23 @@ void dxtlt_host::release_auto_thread_arena()
     g_arena.release();
     g_stage.release();
     release_estimate_thread_counters();
+    release_batch_auto_thread_buffers();
+}
+
+int dxtlt_host::auto_candidate_order(int32_t format, bool use_all, AutoChoice* out)
+{
+    const Order o = candidates_of(format, use_all);
+    for (int i = 0; i < o.count; ++i)
+        out[i] = AutoChoice{o.order[i].mode, o.order[i].split_alpha, o.order[i].split_colour, 0};
+    return o.count;
+}
+
+void* dxtlt_host::auto_thread_arena(size_t bytes) { return g_arena.get(bytes); }
+
+void dxtlt_host::auto_begin_device_call()
+{
+    t_last_total_count = 0;
+    t_section_bytes_downloaded = t_estimator_callbacks = 0;
 }
 
 int32_t dxtlt_host::transform_auto(int32_t format, const uint8_t* in, uint8_t* out, size_t len,

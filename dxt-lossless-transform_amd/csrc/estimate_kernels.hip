@@ -123,6 +123,98 @@ __global__ void __launch_bounds__(T) estimate_kernel(const EstimateTable tab)
         atomicAdd(tab.out + s, (unsigned long long)(w - wg_matches));
 }
 
+// The same windows from a section table in DEVICE memory with any number of entries (the batched auto transform: thousands of
+// sections in one launch).  Entries are in workgroup order; entry e owns workgroups [end_wg of entry e - 1, end_wg) and adds into
+// counters[counter].  A workgroup finds its entry by bisection over end_wg -- uniform: scalar loads and compares -- and then runs
+// estimate_kernel's steps on its window, statement for statement.  (A copy, not a shared function: moving the steps into one
+// changes the block placement and scalar registers of estimate_kernel's own code, and that kernel's code is pinned.)
+template <int T, uint32_t W, uint32_t BITS>
+__global__ void __launch_bounds__(T)
+estimate_table_kernel(const EstimateTableEntry* __restrict__ tab, uint32_t entries, unsigned long long* __restrict__ counters)
+{
+    constexpr uint32_t kSlots = 1u << BITS;
+    constexpr uint32_t kWindowDwords = W / 4 + 8;
+    auto slot_of = [](uint32_t gram) { return (gram * 2654435761u) >> (32 - BITS); };
+    __shared__ __attribute__((aligned(16))) uint32_t win[kWindowDwords];
+    __shared__ __attribute__((aligned(16))) uint32_t first[kSlots];
+    __shared__ uint32_t wg_matches;
+
+    const uint32_t wg = blockIdx.x, tid = threadIdx.x;
+    uint32_t lo = 0, hi = entries - 1;   // the first entry whose end_wg is above wg: in [lo, hi] (the grid ends at the last end_wg)
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (tab[mid].end_wg > wg)
+            hi = mid;
+        else
+            lo = mid + 1;
+    }
+    const uint32_t begin = lo == 0 ? 0u : tab[lo - 1].end_wg;
+    const uint8_t* base = tab[lo].base;
+    const uint64_t len = tab[lo].len;
+    unsigned long long* out = counters + tab[lo].counter;
+    const uint64_t off = uint64_t(wg - begin) * W;
+    const uint32_t w = len - off < W ? uint32_t(len - off) : W;
+
+    if (base == nullptr || w < 4) {   // no gram: every byte counts
+        if (tid == 0)
+            atomicAdd(out, (unsigned long long)w);
+        return;
+    }
+
+    const uintptr_t a = reinterpret_cast<uintptr_t>(base) + off;
+    const uint32_t head = uint32_t(a & 15);
+    typedef const u32x4 __attribute__((address_space(1))) * GlobalVec;
+    const GlobalVec src = reinterpret_cast<GlobalVec>(a - head);
+    const uint32_t nvec = (head + w + 15) >> 4;
+    for (uint32_t v = tid; v < nvec; v += T)
+        reinterpret_cast<u32x4*>(win)[v] = __builtin_nontemporal_load(src + v);
+    for (uint32_t i = tid; i < kSlots / 4; i += T)
+        reinterpret_cast<u32x4*>(first)[i] = u32x4{~0u, ~0u, ~0u, ~0u};
+    if (tid == 0)
+        wg_matches = 0;
+    __syncthreads();
+
+    const uint32_t lo_q = head, hi_q = head + w - 3;
+    const uint32_t ndw = (hi_q + 3) >> 2;
+    for (uint32_t d = tid; d < ndw; d += T) {
+        const uint32_t x = win[d], y = win[d + 1];
+        const uint32_t g[4] = {x, __builtin_amdgcn_alignbyte(y, x, 1), __builtin_amdgcn_alignbyte(y, x, 2),
+                               __builtin_amdgcn_alignbyte(y, x, 3)};
+#pragma unroll
+        for (uint32_t k = 0; k < 4; ++k) {
+            const uint32_t q = 4 * d + k;
+            if (q >= lo_q && q < hi_q)
+                atomicMin(&first[slot_of(g[k])], q);
+        }
+    }
+    __syncthreads();
+
+    uint32_t matches = 0;
+    for (uint32_t d = tid; d < ndw; d += T) {
+        const uint32_t x = win[d], y = win[d + 1];
+        const uint32_t g[4] = {x, __builtin_amdgcn_alignbyte(y, x, 1), __builtin_amdgcn_alignbyte(y, x, 2),
+                               __builtin_amdgcn_alignbyte(y, x, 3)};
+#pragma unroll
+        for (uint32_t k = 0; k < 4; ++k) {
+            const uint32_t q = 4 * d + k;
+            if (q >= lo_q && q < hi_q) {
+                const uint32_t f = first[slot_of(g[k])];
+                if (f < q) {
+                    const uint32_t fd = f >> 2;
+                    matches += __builtin_amdgcn_alignbyte(win[fd + 1], win[fd], f & 3) == g[k];
+                }
+            }
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1)
+        matches += __shfl_down(matches, o);
+    if ((tid & 63) == 0 && matches != 0)
+        atomicAdd(&wg_matches, matches);
+    __syncthreads();
+    if (tid == 0)
+        atomicAdd(out, (unsigned long long)(w - wg_matches));
+}
+
 template <uint32_t W, uint32_t BITS>
 hipError_t launch_shape(const EstimateSection* sections, size_t count, uint64_t* d_out, hipStream_t stream, int lanes)
 {
@@ -172,6 +264,18 @@ hipError_t launch_shape(const EstimateSection* sections, size_t count, uint64_t*
 hipError_t launch_estimate(const EstimateSection* sections, size_t count, uint64_t* d_out, hipStream_t stream)
 {
     return launch_shape<kEstimatorWindow, kEstimatorBits>(sections, count, d_out, stream, 1024);
+}
+
+hipError_t launch_estimate_table(const EstimateTableEntry* d_table, uint32_t entries, uint32_t workgroups, uint64_t* d_counters,
+                                 hipStream_t stream)
+{
+    if (entries == 0 || workgroups == 0)
+        return hipSuccess;
+    if (workgroups > 0x7FFFFFFFu)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL((estimate_table_kernel<1024, kEstimatorWindow, kEstimatorBits>), dim3(workgroups), dim3(1024), 0, stream, d_table,
+                       entries, reinterpret_cast<unsigned long long*>(d_counters));
+    return hipGetLastError();
 }
 
 hipError_t launch_estimate_shape(const EstimateSection* sections, size_t count, uint64_t* d_out, hipStream_t stream, int lanes,

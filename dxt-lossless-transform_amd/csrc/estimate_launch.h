@@ -21,6 +21,22 @@ struct EstimateSection {
 // hipErrorInvalidValue: a section of more than 2^31 - 1 windows.
 hipError_t launch_estimate(const EstimateSection* sections, size_t count, uint64_t* d_out, hipStream_t stream);
 
+// One section of a table in device memory (launch_estimate_table): entries in workgroup order, entry e owning workgroups
+// [end_wg of entry e - 1, end_wg) -- one per 32 KiB window, so an entry has len > 0 -- and adding into counters[counter].
+struct EstimateTableEntry {
+    const uint8_t* base;   // any alignment
+    uint64_t len;
+    uint32_t end_wg;
+    uint32_t counter;
+};
+static_assert(sizeof(EstimateTableEntry) == 24, "EstimateTableEntry layout is shared between host and device");
+
+// The estimates of any number of sections in ONE launch: `d_table` (device memory, `entries` entries) as above, `workgroups` =
+// the last entry's end_wg (at most 2^31 - 1: hipErrorInvalidValue beyond).  Adds into d_counters, which the caller has zeroed on
+// `stream`; several entries may share a counter.  Enqueues only.
+hipError_t launch_estimate_table(const EstimateTableEntry* d_table, uint32_t entries, uint32_t workgroups, uint64_t* d_counters,
+                                 hipStream_t stream);
+
 // The same launch with `lanes` per workgroup (256, 512, 1024) and another (window, bits) pair -- (32768, 14), (32768, 13),
 // (16384, 13), (8192, 12) are compiled; anything else: hipErrorInvalidValue.  For the shape sweep of tools/estimator_bench.py
 // and the tests; only (32768, 14) is the product's estimator, and its result does not depend on `lanes`.

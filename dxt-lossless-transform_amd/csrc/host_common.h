@@ -161,6 +161,16 @@ int32_t transform_auto_bc45(int32_t format, const uint8_t* in, uint8_t* out, siz
 int32_t transform_auto_device(int32_t format, const void* d_in, void* d_out, size_t len, bool use_all_decorrelation_modes,
                               hipStream_t stream, AutoChoice* choice);
 
+// ---- auto_transform.cpp, for the batched call (batch_auto_api.cpp) ----
+// The candidates of `format` (1..5) in the order they are compared, into out[0 .. 16); returns how many (candidates_of).
+int auto_candidate_order(int32_t format, bool use_all_decorrelation_modes, AutoChoice* out);
+// This thread's candidate arena on the current device, grown to at least `bytes`; nullptr when it cannot be allocated.
+void* auto_thread_arena(size_t bytes);
+// An auto call that downloads no section and makes no callback begins: dxtlt_debug_auto_last_estimation reports (0, 0) and
+// dxtlt_debug_auto_last_totals nothing until the next single-buffer call.
+void auto_begin_device_call();
+void release_batch_auto_thread_buffers();   // batch_auto_api.cpp; through release_auto_thread_arena()
+
 // ---- estimate_api.cpp: the built-in estimator (include/dxtlt_estimator.h) -----------------------------------------
 bool is_builtin_estimator(const DltSizeEstimator* estimator);   // by the identity of its two function pointers
 // This thread's counter block on the current device: kMaxCounters estimates (BC3 with every mode, one full transform per

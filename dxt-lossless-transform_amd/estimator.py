@@ -19,6 +19,12 @@ class Section(C.Structure):                     # DxtltEstimateSection
     _fields_ = [("d_ptr", C.c_void_p), ("len", C.c_uint64)]
 
 
+class BatchAutoItem(C.Structure):               # DxtltBatchAutoItem
+    _fields_ = [("d_input", C.c_void_p), ("d_output", C.c_void_p), ("len", C.c_uint64), ("format", C.c_uint8),
+                ("use_all_decorrelation_modes", C.c_uint8), ("decorrelation_mode", C.c_uint8),
+                ("split_alpha_endpoints", C.c_uint8), ("split_colour_endpoints", C.c_uint8), ("reserved", C.c_uint8 * 3)]
+
+
 _own = None
 
 
@@ -55,6 +61,13 @@ def _l():
         l.dxtlt_debug_estimate_sizes_shape.argtypes = [C.POINTER(Section), sz, vp, vp, i32, C.c_uint32, C.c_uint32]
         l.dxtlt_debug_estimate_sizes_shape.restype = i32
         l.dxtlt_debug_auto_candidates_device.argtypes, l.dxtlt_debug_auto_candidates_device.restype = [i32, b, vp, sz, vp], i32
+        l.dxtlt_transform_batch_auto_device.argtypes = [C.POINTER(BatchAutoItem), sz, vp]
+        l.dxtlt_transform_batch_auto_device.restype = i32
+        l.dxtlt_debug_batch_auto_last.argtypes, l.dxtlt_debug_batch_auto_last.restype = [u64p], None
+        l.dxtlt_debug_batch_auto_last_totals.argtypes, l.dxtlt_debug_batch_auto_last_totals.restype = [sz, u64p, i32], i32
+        l.dxtlt_debug_batch_auto_arena_cap.argtypes, l.dxtlt_debug_batch_auto_arena_cap.restype = [C.c_uint64], None
+        l.dxtlt_debug_batch_auto_time_phases.argtypes, l.dxtlt_debug_batch_auto_time_phases.restype = [i32], None
+        l.dxtlt_debug_batch_auto_last_phase_ms.argtypes, l.dxtlt_debug_batch_auto_last_phase_ms.restype = [C.POINTER(C.c_double)], None
         _own = l
     return _own
 
@@ -154,6 +167,59 @@ def transform_auto(fmt: str, input, output, use_all_decorrelation_modes: bool = 
     if fmt == "bc3":
         return Bc3TransformSettings(YCoCgVariant(mode.value), sa.value, sc.value)
     return (Bc4TransformSettings if fmt == "bc4" else Bc5TransformSettings)(sa.value)
+
+
+def _settings_of(fmt: str, mode: int, sa: int, sc: int):
+    from . import (Bc1TransformSettings, Bc2TransformSettings, Bc3TransformSettings, Bc4TransformSettings, Bc5TransformSettings,
+                   YCoCgVariant)
+
+    if fmt == "bc1":
+        return Bc1TransformSettings(YCoCgVariant(mode), bool(sc))
+    if fmt == "bc2":
+        return Bc2TransformSettings(YCoCgVariant(mode), bool(sc))
+    if fmt == "bc3":
+        return Bc3TransformSettings(YCoCgVariant(mode), bool(sa), bool(sc))
+    return (Bc4TransformSettings if fmt == "bc4" else Bc5TransformSettings)(bool(sa))
+
+
+def transform_batch_auto(items):
+    """dxtlt_transform_batch_auto_device: items are (fmt, input tensor, output tensor, use_all_decorrelation_modes) with fmt in
+    bc1..bc5 and CUDA uint8 tensors on one device.  Chooses the best settings for every item with the built-in estimator and
+    transforms them all on torch's current stream: one stream wait and a launch count that does not grow with the number of
+    items.  Returns the list of chosen settings objects, one per item; the transforms are enqueued, not waited for."""
+    import torch
+
+    from . import _FMT_ID, BLOCK_BYTES, InvalidLength, OutputBufferTooSmall, _Buf
+
+    if not items:
+        return []
+    arr = (BatchAutoItem * len(items))()
+    device, keep = None, []
+    for k, (fmt, src, dst, use_all) in enumerate(items):
+        s, d = _Buf(src, False), _Buf(dst, True)
+        if s.device is None or d.device is None:
+            raise TypeError("transform_batch_auto takes device tensors")
+        device = s.device if device is None else device
+        if s.device != device or d.device != device:
+            raise ValueError("all tensors of a batch must live on one device")
+        if s.nbytes % BLOCK_BYTES[fmt] != 0:
+            raise InvalidLength(s.nbytes)
+        if d.nbytes < s.nbytes:
+            raise OutputBufferTooSmall(s.nbytes, d.nbytes)
+        arr[k].d_input, arr[k].d_output, arr[k].len = s.ptr, d.ptr, s.nbytes
+        arr[k].format, arr[k].use_all_decorrelation_modes = _FMT_ID[fmt], int(bool(use_all))
+        keep.append((s, d))
+    with torch.cuda.device(device):
+        _check(_l().dxtlt_transform_batch_auto_device(arr, len(arr), torch.cuda.current_stream().cuda_stream))
+    return [_settings_of(fmt, a.decorrelation_mode, a.split_alpha_endpoints, a.split_colour_endpoints)
+            for (fmt, _s, _d, _u), a in zip(items, arr)]
+
+
+def last_batch_auto() -> tuple[int, int, int, int]:
+    """(stream waits, chunks, candidate launches, estimator launches) of the last transform_batch_auto of this thread."""
+    buf = (C.c_uint64 * 4)()
+    _l().dxtlt_debug_batch_auto_last(buf)
+    return tuple(int(v) for v in buf)
 
 
 def last_auto_estimation() -> tuple[int, int]:

@@ -338,6 +338,13 @@ inline bool transform_bc5_auto_device(const void* d_input, void* d_output, size_
     return split;
 }
 
+// The batched auto transform (dxtlt_transform_batch_auto_device): the best settings for every item of `items`, all of them
+// transformed, one stream wait and a launch count that does not grow with `count`.  The choices are written into the items.
+inline void transform_batch_auto_device(DxtltBatchAutoItem* items, size_t count, void* hip_stream)
+{
+    detail::check_device(dxtlt_transform_batch_auto_device(items, count, hip_stream));
+}
+
 // ---- dxt_lossless_transform_bc1::experimental::normalize_blocks (normalize.rs, transform.rs, mod.rs) ------------
 namespace experimental {
 

@@ -81,9 +81,104 @@ int32_t dxtlt_transform_bc4_auto_device(const void *d_input, void *d_output, siz
 int32_t dxtlt_transform_bc5_auto_device(const void *d_input, void *d_output, size_t len, bool use_all_decorrelation_modes,
                                         void *hip_stream, bool *out_split_endpoints);
 
+/* ---- the batched auto transform: many device-resident buffers, the best settings chosen for each, in one call ----------------
+ * For every item the choice (written into the item's result fields before the call returns) and the bytes in d_output are exactly
+ * what dxtlt_transform_bcN_auto_device(d_input, d_output, len, use_all_decorrelation_modes, ...) gives for that item alone: the
+ * same candidates in the same order, the same sections shown to the estimator, the same additions and strict `<`.  An empty item
+ * keeps the first candidate of its order and nothing is written for it.
+ *
+ * The whole batch is validated before anything is enqueued: NULL items with count > 0, a format outside 1..5 and a NULL buffer
+ * with len > 0 are DXTLT_E_INVALID_ARGUMENT, a len that is not a multiple of the block size DXTLT_E_INVALID_LENGTH, an item of
+ * 64 GiB or more and a d_output that overlaps any other d_output or any d_input of the batch DXTLT_E_INVALID_ARGUMENT (inputs
+ * may overlap one another).  On a capturing stream, or one whose capture state cannot be queried, the call returns
+ * DXTLT_E_INVALID_ARGUMENT and enqueues nothing.
+ *
+ * A batch whose winning transforms could not go out in one launch per (format, settings) is refused with the rest, before the
+ * choices are known: per format the items together may hold at most 2^24 - 1 tiles, counted as len / block size / 256 + 2 per
+ * item (about 32 GiB of BC1 / BC4 or 64 GiB of BC2 / BC3 / BC5 items): DXTLT_E_INVALID_ARGUMENT.
+ *
+ * The call WAITS for `hip_stream` exactly once, to read the counters back (at most 10 eight-byte counters per item), whatever
+ * the number of items; the number of launches does not grow with it either: per chunk one candidate launch per (format,
+ * use_all_decorrelation_modes) present and ONE estimator launch, then the winning transforms through the path of
+ * dxtlt_transform_batch_device, enqueued and not waited for.  They read the d_inputs only: when the call returns nothing in
+ * flight touches this thread's arena or counters.  Formats and use_all values may be mixed; d_input and d_output may have any
+ * alignment (a d_input off a 16-byte boundary is read with narrower loads: the same choice and bytes, no further wait).
+ * What the winners inherit from dxtlt_transform_batch_device: an item whose d_output is off an 8-byte boundary is transformed by
+ * a launch of its own (one more launch per such item, no wait), and that call's ring of four table slots makes the HOST wait for
+ * an earlier batch call of this thread when four of them are still in flight -- a wait for earlier work, not for this call's
+ * stream.  dxtlt_debug_batch_auto_last counts the waits and launches this call makes itself, not those.
+ *
+ * Chunks: every item owns a 16-byte aligned slice of the per-thread candidate arena -- 16 / 32 bytes per block for BC1 and BC2
+ * (fast / all modes), 20 / 36 for BC3, 4 for BC4, 8 for BC5.  A chunk is closed before the item that would push its slices past
+ * DXTLT_BATCH_AUTO_ARENA_CAP bytes; an item whose slice alone is larger is a chunk by itself.  The stream orders the reuse of
+ * the arena from chunk to chunk. */
+#define DXTLT_BATCH_AUTO_ARENA_CAP (256ull << 20)
+
+typedef struct DxtltBatchAutoItem {
+    const void *d_input;
+    void *d_output;                      /* len bytes, overlapping no input or output of the batch */
+    uint64_t len;                        /* a multiple of the block size; 0 is allowed */
+    uint8_t format;                      /* 1..5 = BC1..BC5 */
+    uint8_t use_all_decorrelation_modes; /* ignored for 4, 5 */
+    /* results, written before the call returns */
+    uint8_t decorrelation_mode;          /* core numbering; 0 for BC4 / BC5 */
+    uint8_t split_alpha_endpoints;       /* BC3; BC4 / BC5: split_endpoints */
+    uint8_t split_colour_endpoints;
+    uint8_t reserved[3];
+} DxtltBatchAutoItem;
+
+int32_t dxtlt_transform_batch_auto_device(DxtltBatchAutoItem *items, size_t count, void *hip_stream);
+
+/* Test hook, no device needed (addresses are numbers, nothing is dereferenced): the plan dxtlt_transform_batch_auto_device
+ * makes for `items` -- after the same validation, whose status it returns.  items_out: `count` records; chunks_out: up to
+ * chunk_capacity records (chunks beyond it are counted, not written); *out_chunks: the number of chunks.  A section's
+ * arena_offset counts from the arena's first byte; sections are listed in slice order: BC3's alpha pairs and alpha split, then
+ * per variant colour pairs and colour split; BC4 pairs, split; BC5 red pairs, red split, green pairs, green split.  A total is
+ * BC3: alpha + colour, BC5: red + green of the same kind, else one section. */
+typedef struct DxtltDebugBatchAutoSection {
+    uint64_t arena_offset;
+    uint64_t len;
+    uint32_t counter; /* index into the batch's counter buffer */
+    uint32_t reserved;
+} DxtltDebugBatchAutoSection;
+typedef struct DxtltDebugBatchAutoPlanItem {
+    uint32_t chunk;
+    uint32_t section_count;
+    uint64_t arena_offset; /* of the item's slice */
+    uint64_t arena_bytes;  /* of the item's slice, before it is padded to 16 */
+    DxtltDebugBatchAutoSection sections[10];
+} DxtltDebugBatchAutoPlanItem;
+typedef struct DxtltDebugBatchAutoPlanChunk {
+    uint64_t first_item;
+    uint64_t item_count;
+    uint64_t arena_bytes;
+    uint32_t candidate_launches;
+    uint32_t estimator_workgroups;
+} DxtltDebugBatchAutoPlanChunk;
+int32_t dxtlt_debug_plan_batch_auto(const DxtltBatchAutoItem *items, size_t count, DxtltDebugBatchAutoPlanItem *items_out,
+                                    DxtltDebugBatchAutoPlanChunk *chunks_out, size_t chunk_capacity, size_t *out_chunks);
+
+/* Test hook: of the last dxtlt_transform_batch_auto_device call of this thread: stream waits, chunks, candidate launches,
+ * estimator launches. */
+void dxtlt_debug_batch_auto_last(uint64_t out[4]);
+
+/* Test hook: the totals that call compared for item `item`, in candidate order; returns how many there were (0 for an item
+ * index out of range, a failed call or an empty item); writes at most cap. */
+int32_t dxtlt_debug_batch_auto_last_totals(size_t item, uint64_t *out, int32_t cap);
+
+/* Test hook, per calling thread: the chunk cap in bytes in place of DXTLT_BATCH_AUTO_ARENA_CAP; 0 restores the default. */
+void dxtlt_debug_batch_auto_arena_cap(uint64_t bytes);
+
+/* Bench hook, per calling thread: anything but 0 = dxtlt_transform_batch_auto_device records HIP events around the candidate
+ * launches and the estimator launch of every chunk (three events per chunk, created and destroyed by the call).
+ * dxtlt_debug_batch_auto_last_phase_ms then reports, for the last such call of this thread, the milliseconds between them summed
+ * over the chunks: out[0] candidate launches, out[1] estimator launches ({0, 0} after a call without the switch). */
+void dxtlt_debug_batch_auto_time_phases(int32_t on);
+void dxtlt_debug_batch_auto_last_phase_ms(double out[2]);
+
 /* Test hook: what the last auto transform called from this thread (host or device pointers, any format) moved and called for
  * its estimates: bytes of candidate sections copied to the host, and calls made through the estimator's vtable
- * (MaxCompressedSize and EstimateCompressedSize).  Both are 0 with the built-in estimator.  Either pointer may be NULL. */
+ * (MaxCompressedSize and EstimateCompressedSize).  Both are 0 with the built-in estimator and after the batched call.  Either pointer may be NULL. */
 void dxtlt_debug_auto_last_estimation(uint64_t *out_section_bytes_downloaded, uint64_t *out_estimator_callbacks);
 
 /* Test hook: the totals the last built-in-estimator auto transform of this thread compared, in candidate order;

@@ -139,6 +139,22 @@ pub struct DxtltEstimateSection {
     pub len: u64,
 }
 
+/// `DxtltBatchAutoItem` of include/dxtlt_estimator.h: one buffer of `dxtlt_transform_batch_auto_device`; the last three
+/// fields before `reserved` are results.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct DxtltBatchAutoItem {
+    pub d_input: *const c_void,
+    pub d_output: *mut c_void,
+    pub len: u64,
+    pub format: u8, // 1..5 = BC1..BC5
+    pub use_all_decorrelation_modes: u8,
+    pub decorrelation_mode: u8,
+    pub split_alpha_endpoints: u8,
+    pub split_colour_endpoints: u8,
+    pub reserved: [u8; 3],
+}
+
 // ---- include/dxtlt_estimator.h: the built-in, device-resident size estimator (docs/ESTIMATOR.md) and the auto transforms
 // on device pointers.  (A block of its own: the first block mirrors include/dxtlt_gfx950.h alone.)
 extern "C" {
@@ -162,4 +178,6 @@ extern "C" {
         use_all_decorrelation_modes: bool, hip_stream: *mut c_void, out_split_endpoints: *mut bool) -> i32;
     pub fn dxtlt_transform_bc5_auto_device(d_input: *const c_void, d_output: *mut c_void, len: usize,
         use_all_decorrelation_modes: bool, hip_stream: *mut c_void, out_split_endpoints: *mut bool) -> i32;
+    /// every item's best settings chosen and applied in one call: one stream wait, launches independent of `count`
+    pub fn dxtlt_transform_batch_auto_device(items: *mut DxtltBatchAutoItem, count: usize, hip_stream: *mut c_void) -> i32;
 }
