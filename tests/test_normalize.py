@@ -22,11 +22,12 @@ def u8(*v):
     return np.array(v, dtype=np.uint8)
 
 
-def crafted_blocks(oracle, n, seed=1):
-    """Random BC1 blocks with every normalisation case mixed in by block index modulo 8."""
+def blocks_of_cases(oracle, k, seed):
+    """Random BC1 blocks; block i is rewritten into normalisation case k[i] (0 and 7 are kept by every mode, 5 is fully transparent,
+    the others are solid in one way each)."""
+    n = len(k)
     x = oracle.fill_splitmix64(n * 8, 0x0BC1_4E00 + seed)
     b = x.reshape(-1, 8)
-    k = np.arange(n) % 8
     c0 = b[:, 0].astype(np.uint32) | (b[:, 1].astype(np.uint32) << 8)
     c1 = b[:, 2].astype(np.uint32) | (b[:, 3].astype(np.uint32) << 8)
     lo, hi = np.minimum(c0, c1), np.maximum(c0, c1)
@@ -51,6 +52,29 @@ def crafted_blocks(oracle, n, seed=1):
     set_colours(r7, lo, hi)
     b[r7, 4] = 0xF0
     return x
+
+
+def crafted_blocks(oracle, n, seed=1):
+    """Random BC1 blocks with every normalisation case mixed in by block index modulo 8."""
+    return blocks_of_cases(oracle, np.arange(n) % 8, seed)
+
+
+def slot_free_cases(n, seed):
+    """The case of each of n blocks, from a seeded permutation instead of the index: in every aligned run of 32 blocks the eight
+    positions of each i % 4 hold a permutation of the eight cases, so every case sits in every slot of a 2- or 4-block vector
+    and in both halves of every 64-lane wave, whatever the block count."""
+    rng = np.random.default_rng(0x51_07_00 + seed)
+    k = np.empty((n + 31) // 32 * 32, dtype=np.int64)
+    for run in k.reshape(-1, 8, 4):
+        for slot in range(4):
+            run[:, slot] = rng.permutation(8)
+    return k[:n]
+
+
+def permuted_blocks(oracle, n, seed=1):
+    """crafted_blocks with the case of block i taken from slot_free_cases; returns (blocks, cases)"""
+    k = slot_free_cases(n, seed)
+    return blocks_of_cases(oracle, k, seed), k
 
 
 # ---------------------------------------------------------------------------------------------------------------
