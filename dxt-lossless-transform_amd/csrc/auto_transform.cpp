@@ -111,7 +111,8 @@ thread_local Arena g_arena;
 
 // dxtlt_debug_auto_last_estimation: what the last auto call of this thread downloaded and called for its estimates
 thread_local uint64_t t_section_bytes_downloaded = 0, t_estimator_callbacks = 0;
-thread_local bool t_no_arena = false;   // dxtlt_debug_auto_use_arena(0): the built-in path as if the arena could not be allocated
+thread_local uint32_t t_last_estimator_error = 0;   // dxtlt_debug_auto_last_estimator_error
+thread_local bool t_no_arena = false;   // dxtlt_debug_auto_use_arena(0): every auto route as if the arena could not be allocated
 // dxtlt_debug_auto_last_totals: the totals the last built-in-estimator auto call of this thread compared, in candidate order
 thread_local uint64_t t_last_totals[16];
 thread_local int t_last_total_count = 0;
@@ -309,6 +310,7 @@ int32_t auto_on_device(int32_t format, const void* d_in, void* d_out, size_t len
     uint64_t sizes[kMaxCounters];
     uint64_t total[16];
     int last = -1;   // the candidate whose transform is in d_out
+    int pick = 0;
 
     // BC1-3: the candidate kernel reads the input as 16-byte vectors; an input off a 16-byte boundary takes the no-arena route,
     // whose transform kernels take any alignment (one full transform per candidate instead of one read)
@@ -326,7 +328,6 @@ int32_t auto_on_device(int32_t format, const void* d_in, void* d_out, size_t len
         for (int m = 0; m < variants; ++m)
             for (int sp = 0; sp < 2; ++sp)
                 secs[n++] = {arena + dxtlt::auto_section_offset((dxtlt::Format)format, blocks, m, sp != 0), colour_len};
-        const int alpha_first = n;
         if (format == 3)
             for (int sp = 0; sp < 2; ++sp)
                 secs[n++] = {arena + dxtlt::auto_alpha_section_offset(blocks, sp != 0), blocks * 2};
@@ -334,15 +335,11 @@ int32_t auto_on_device(int32_t format, const void* d_in, void* d_out, size_t len
             return rc;
         if (int32_t rc = estimate_read_back((size_t)n, st, sizes))
             return rc;
-        for (int i = 0; i < o.count; ++i) {
-            const Candidate c = o.order[i];
-            total[i] = (format == 3 ? sizes[alpha_first + (c.split_alpha ? 1 : 0)] : 0) + sizes[c.mode * 2 + (c.split_colour ? 1 : 0)];
-        }
+        pick = auto_pick_single(format, use_all, false, sizes, total);
     } else {
         // BC4 / BC5 with the arena: both transforms side by side (the winner is transformed once more, into d_out: a copy out of
         // the arena would still be reading it when this thread's next call fills it).  Without it: one full transform per
         // candidate into d_out, estimated there before the next one overwrites it (stream order); the counters come back once.
-        int shown_per = 1;
         for (int i = 0; i < o.count; ++i) {
             const Candidate c = o.order[i];
             uint8_t* dst = arena != nullptr ? arena + (size_t)i * len : out8;
@@ -351,20 +348,15 @@ int32_t auto_on_device(int32_t format, const void* d_in, void* d_out, size_t len
             if (arena == nullptr)
                 last = i;
             dxtlt::EstimateSection secs[2];
-            shown_per = shown(dst, secs);
+            const int shown_per = shown(dst, secs);
             if (int32_t rc = estimate_enqueue(secs, (size_t)shown_per, st, (size_t)(i * 2)))
                 return rc;
         }
         if (int32_t rc = estimate_read_back((size_t)o.count * 2, st, sizes))
             return rc;
-        for (int i = 0; i < o.count; ++i)
-            total[i] = sizes[2 * i] + (shown_per == 2 ? sizes[2 * i + 1] : 0);
+        pick = auto_pick_single(format, use_all, true, sizes, total);
     }
 
-    int pick = 0;
-    for (int i = 1; i < o.count; ++i)
-        if (total[i] < total[pick])   // strict: the first best wins
-            pick = i;
     *best = o.order[pick];
     if (pick != last) {
         if (int32_t rc = enqueue(format, false, d_in, d_out, blocks, best->mode, best->split_alpha, best->split_colour, st))
@@ -440,6 +432,25 @@ int dxtlt_host::auto_candidate_order(int32_t format, bool use_all, AutoChoice* o
     return o.count;
 }
 
+int dxtlt_host::auto_pick_single(int32_t format, bool use_all, bool per_candidate, const uint64_t* sizes, uint64_t* total)
+{
+    const Order o = candidates_of(format, use_all);
+    const int alpha_first = use_all ? 8 : 4;   // behind the colour sections
+    const bool two_shown = format == 3 || format == 5;
+    for (int i = 0; i < o.count; ++i) {
+        const Candidate c = o.order[i];
+        if (per_candidate)
+            total[i] = sizes[2 * i] + (two_shown ? sizes[2 * i + 1] : 0);
+        else
+            total[i] = (format == 3 ? sizes[alpha_first + (c.split_alpha ? 1 : 0)] : 0) + sizes[c.mode * 2 + (c.split_colour ? 1 : 0)];
+    }
+    int pick = 0;
+    for (int i = 1; i < o.count; ++i)
+        if (total[i] < total[pick])   // strict: the first best wins
+            pick = i;
+    return pick;
+}
+
 void* dxtlt_host::auto_thread_arena(size_t bytes) { return g_arena.get(bytes); }
 
 void dxtlt_host::auto_begin_device_call()
@@ -502,7 +513,7 @@ int32_t dxtlt_host::transform_auto(int32_t format, const uint8_t* in, uint8_t* o
         }
         AUTO_TRY(hipMemcpyAsync(d_in, in, len, hipMemcpyHostToDevice, st), "H2D copy");
         static const bool fused = [] { const char* v = dxtlt::experiment_env("DXTLT_AUTO_FUSED"); return !(v && v[0] == '0'); }();
-        if (fused)
+        if (fused && !t_no_arena)
             arena = static_cast<uint8_t*>(g_arena.get((size_t)dxtlt::auto_arena_bytes((dxtlt::Format)format, use_all, blocks)));
         if (arena != nullptr)
             AUTO_TRY(dxtlt::launch_auto_candidates((dxtlt::Format)format, use_all, d_in, arena, blocks, st),
@@ -745,7 +756,8 @@ int32_t dxtlt_host::transform_auto_bc45(int32_t format, const uint8_t* in, uint8
             return rc;
         }
         AUTO_TRY(hipMemcpyAsync(d_in, in, len, hipMemcpyHostToDevice, st), "H2D copy");
-        arena = static_cast<uint8_t*>(g_arena.get(2 * len));
+        if (!t_no_arena)
+            arena = static_cast<uint8_t*>(g_arena.get(2 * len));
         for (int k = 0; k < 2 && arena != nullptr; ++k) {
             const int32_t rc2 = enqueue(format, false, d_in, arena + (size_t)k * len, blocks, 0, kCandidates[k], false, st);
             if (rc2 != kOk) {
@@ -850,6 +862,7 @@ int32_t dxtlt_transform_bc4_auto(const uint8_t* input_ptr, uint8_t* output_ptr, 
 {
     dxtlt_host::AutoChoice c{};
     const int32_t rc = dxtlt_host::transform_auto_bc45(4, input_ptr, output_ptr, len, estimator, &c);
+    t_last_estimator_error = c.estimator_error;
     if (rc == DXTLT_OK && out_split_endpoints)
         *out_split_endpoints = c.split_alpha;
     return rc;
@@ -860,6 +873,7 @@ int32_t dxtlt_transform_bc5_auto(const uint8_t* input_ptr, uint8_t* output_ptr, 
 {
     dxtlt_host::AutoChoice c{};
     const int32_t rc = dxtlt_host::transform_auto_bc45(5, input_ptr, output_ptr, len, estimator, &c);
+    t_last_estimator_error = c.estimator_error;
     if (rc == DXTLT_OK && out_split_endpoints)
         *out_split_endpoints = c.split_alpha;
     return rc;
@@ -872,6 +886,7 @@ int32_t dxtlt_transform_bc1_auto(const uint8_t* input_ptr, uint8_t* output_ptr, 
 {
     dxtlt_host::AutoChoice c{};
     int32_t rc = dxtlt_host::transform_auto(1, input_ptr, output_ptr, len, estimator, use_all_decorrelation_modes, &c);
+    t_last_estimator_error = c.estimator_error;
     if (out_estimator_error) *out_estimator_error = c.estimator_error;
     if (rc == DXTLT_OK) {
         if (out_decorrelation_mode) *out_decorrelation_mode = c.mode;
@@ -887,6 +902,7 @@ int32_t dxtlt_transform_bc2_auto(const uint8_t* input_ptr, uint8_t* output_ptr, 
 {
     dxtlt_host::AutoChoice c{};
     int32_t rc = dxtlt_host::transform_auto(2, input_ptr, output_ptr, len, estimator, use_all_decorrelation_modes, &c);
+    t_last_estimator_error = c.estimator_error;
     if (out_estimator_error) *out_estimator_error = c.estimator_error;
     if (rc == DXTLT_OK) {
         if (out_decorrelation_mode) *out_decorrelation_mode = c.mode;
@@ -902,6 +918,7 @@ int32_t dxtlt_transform_bc3_auto(const uint8_t* input_ptr, uint8_t* output_ptr, 
 {
     dxtlt_host::AutoChoice c{};
     int32_t rc = dxtlt_host::transform_auto(3, input_ptr, output_ptr, len, estimator, use_all_decorrelation_modes, &c);
+    t_last_estimator_error = c.estimator_error;
     if (out_estimator_error) *out_estimator_error = c.estimator_error;
     if (rc == DXTLT_OK) {
         if (out_decorrelation_mode) *out_decorrelation_mode = c.mode;
@@ -989,6 +1006,8 @@ int32_t dxtlt_debug_auto_last_totals(uint64_t* out_totals, int32_t cap)
 }
 
 void dxtlt_debug_auto_use_arena(int32_t on) { t_no_arena = on == 0; }
+
+uint32_t dxtlt_debug_auto_last_estimator_error(void) { return t_last_estimator_error; }
 
 int32_t dxtlt_debug_auto_candidates_device(int32_t format, bool use_all_decorrelation_modes, const void* d_input, size_t len,
                                            void* hip_stream)

@@ -148,13 +148,13 @@ void make_plan(const DxtltBatchAutoItem* items, size_t count, Plan& plan)
         plan.arena_bytes = std::max(plan.arena_bytes, c.arena_bytes);
 }
 
-// the totals of item `p` in candidate order from its counters; returns the pick
-int pick_of(const DxtltBatchAutoItem& it, const uint64_t* sizes, const AutoChoice* order, int n, uint64_t* total)
+// the totals of an item of `format` in candidate order from its counters (batch_auto_sections' order); returns the pick
+int pick_of(int32_t format, const uint64_t* sizes, const AutoChoice* order, int n, uint64_t* total)
 {
     for (int i = 0; i < n; ++i) {
         const AutoChoice& c = order[i];
         const int sa = c.split_alpha ? 1 : 0, colour = c.mode * 2 + (c.split_colour ? 1 : 0);
-        switch (it.format) {
+        switch (format) {
         case 3: total[i] = sizes[sa] + sizes[2 + colour]; break;
         case 4: total[i] = sizes[sa]; break;
         case 5: total[i] = sizes[sa] + sizes[2 + sa]; break;
@@ -408,7 +408,7 @@ extern "C" int32_t dxtlt_transform_batch_auto_device(DxtltBatchAutoItem* items, 
         const PlannedItem& p = plan.items[i];
         int pick = 0;
         if (p.blocks != 0)
-            pick = pick_of(items[i], g_buffers.counters_host + p.first_counter, &orders[i * 16], order_counts[i], &totals[i * 16]);
+            pick = pick_of(items[i].format, g_buffers.counters_host + p.first_counter, &orders[i * 16], order_counts[i], &totals[i * 16]);
         report(i, pick);
         DxtltBatchItem& w = winners[i];
         std::memset(&w, 0, sizeof w);
@@ -464,6 +464,35 @@ extern "C" int32_t dxtlt_debug_plan_batch_auto(const DxtltBatchAutoItem* items, 
     }
     if (out_chunks)
         *out_chunks = plan.chunks.size();
+    return kOk;
+}
+
+extern "C" int32_t dxtlt_debug_auto_pick(int32_t route, int32_t format, bool use_all, const uint64_t* section_sizes, int32_t n_sizes,
+                                         uint64_t* totals_out, int32_t cap, uint8_t* mode, bool* split_alpha, bool* split_colour)
+{
+    if (format < 1 || format > 5 || route < 0 || route > 2 || section_sizes == nullptr)
+        return fail(kInvalidArgument, "auto pick: route 0..2, format 1..5, section sizes");
+    use_all = use_all && format <= 3;
+    AutoChoice order[16];
+    const int n = auto_candidate_order(format, use_all, order);
+    const bool per_candidate = route == 2 || (route == 0 && format >= 4);
+    int want = 2 * n;   // two slots per candidate
+    if (!per_candidate)
+        switch (format) {   // the distinct sections
+        case 3: want = (use_all ? 8 : 4) + 2; break;
+        case 4: want = 2; break;
+        case 5: want = 4; break;
+        default: want = use_all ? 8 : 4; break;
+        }
+    if (n_sizes != want)
+        return fail(kInvalidArgument, "auto pick: another number of section sizes than the route reads back");
+    uint64_t total[16];
+    const int pick = route == 1 ? pick_of(format, section_sizes, order, n, total) : auto_pick_single(format, use_all, per_candidate, section_sizes, total);
+    for (int i = 0; totals_out != nullptr && i < n && i < cap; ++i)
+        totals_out[i] = total[i];
+    if (mode) *mode = order[pick].mode;
+    if (split_alpha) *split_alpha = order[pick].split_alpha;
+    if (split_colour) *split_colour = order[pick].split_colour;
     return kOk;
 }
 

@@ -164,6 +164,10 @@ int32_t transform_auto_device(int32_t format, const void* d_in, void* d_out, siz
 // ---- auto_transform.cpp, for the batched call (batch_auto_api.cpp) ----
 // The candidates of `format` (1..5) in the order they are compared, into out[0 .. 16); returns how many (candidates_of).
 int auto_candidate_order(int32_t format, bool use_all_decorrelation_modes, AutoChoice* out);
+// What the single-buffer device route does with its counters after the readback: the candidates' totals in candidate order into
+// total[0 .. 16) and the pick, the first minimum of the order (strict `<`).  sizes: the distinct sections where the candidate kernel
+// left them -- colour (variant, split) pairs, then BC3's two alpha-endpoint sections -- or, per_candidate, two slots per candidate.
+int auto_pick_single(int32_t format, bool use_all_decorrelation_modes, bool per_candidate, const uint64_t* sizes, uint64_t* total);
 // This thread's candidate arena on the current device, grown to at least `bytes`; nullptr when it cannot be allocated.
 void* auto_thread_arena(size_t bytes);
 // An auto call that downloads no section and makes no callback begins: dxtlt_debug_auto_last_estimation reports (0, 0) and

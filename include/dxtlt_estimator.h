@@ -185,9 +185,26 @@ void dxtlt_debug_auto_last_estimation(uint64_t *out_section_bytes_downloaded, ui
  * returns how many there were (0 after a callback-route call, an empty buffer or a failed call); writes at most cap. */
 int32_t dxtlt_debug_auto_last_totals(uint64_t *out_totals, int32_t cap);
 
-/* Test hook, per calling thread: 0 = the built-in path of the auto transforms behaves as if its candidate arena could not be
- * allocated (one full transform per candidate into the output buffer, estimated there); anything else = normal. */
+/* Test hook, per calling thread: 0 = the auto transforms, with the built-in estimator or a caller's, behave as if their candidate
+ * arena could not be allocated (one full transform per candidate into the output buffer, estimated there or downloaded from
+ * there); anything else = normal. */
 void dxtlt_debug_auto_use_arena(int32_t on);
+
+/* Test hook: the code the estimator's callback returned in the last dxtlt_transform_bc{1..5}_auto call of this thread, 0 when none
+ * failed.  The BC4 / BC5 calls have no out parameter for it. */
+uint32_t dxtlt_debug_auto_last_estimator_error(void);
+
+/* Test hook, no device needed: the host-side pick of the device routes, on section sizes given by the caller instead of read back.
+ * It runs the function the route runs after its readback.  route 0: dxtlt_transform_bcN_auto_device -- BC1-3 the distinct sections
+ * in the candidate arena's order (per variant colour pairs, colour split; then BC3's alpha pairs, alpha split), BC4 / BC5 two
+ * slots per candidate (BC4 reads the first of each).  route 1: dxtlt_transform_batch_auto_device, the counters of one item in
+ * slice order (BC3 alpha pairs, alpha split, then the colour sections; BC4 pairs, split; BC5 red pairs, red split, green pairs,
+ * green split).  route 2: route 0 without its arena, two slots per candidate for every format (BC1, BC2 and BC4 read the first of
+ * each).  n_sizes must be what the route reads back (DXTLT_E_INVALID_ARGUMENT otherwise).  Writes at most cap candidate totals,
+ * in candidate order, and the settings of the pick (split_alpha = split_endpoints for BC4 / BC5); any output pointer may be NULL. */
+int32_t dxtlt_debug_auto_pick(int32_t route, int32_t format, bool use_all_decorrelation_modes, const uint64_t *section_sizes,
+                              int32_t n_sizes, uint64_t *totals_out, int32_t cap, uint8_t *mode, bool *split_alpha,
+                              bool *split_colour);
 
 /* Test / bench hook, stateless: dxtlt_estimate_sizes_device with `lanes` per workgroup (256, 512 or 1024) and another
  * (window, bits) pair of the definition -- (32768, 14) is the estimator, whose result does not depend on `lanes`; (32768, 13),

@@ -2,10 +2,13 @@
 
 Follows /root/reference/src/core/dxt-lossless-transform-bc1/src/transform/transform_auto.rs:200-270 (BC2 twin
 :196-, BC3 :196-294) with the test orders of settings.rs (bc1/bc2 :81-98, bc3 :91-121): full transform per
-candidate, estimator on the endpoint section(s) only, strict `<`, re-transform when the best was not the last."""
+candidate, estimator on the endpoint section(s) only, strict `<` against a best size that starts at usize::MAX with the
+default settings (bc1 :209-211, bc3 :205-207), re-transform when the best was not the last."""
 from __future__ import annotations
 
 from . import oracle_c
+
+SIZE_MAX = 2**64 - 1    # usize::MAX: the best size every search starts from, so a candidate that answers it never wins
 
 # (variant, split_alpha, split_colour), core numbering
 FAST_12 = [(0, 0, 0), (0, 0, 1), (1, 0, 0), (1, 0, 1)]
@@ -27,7 +30,7 @@ def transform_auto(fmt: str, data, estimate, use_all: bool):
     n = len(data)
     blocks = n // oracle_c.BLOCK[fmt]
     best = (1, 1 if fmt == "bc3" else 0, 1)
-    best_size = None
+    best_size = SIZE_MAX
     last = best
     out = None
     calls = []
@@ -45,7 +48,7 @@ def transform_auto(fmt: str, data, estimate, use_all: bool):
         for off, ln in sections:
             calls.append((off, ln))
             size += estimate(out[off:off + ln])
-        if best_size is None or size < best_size:
+        if size < best_size:
             best_size, best = size, cand
     if best != last:
         out = oracle_c.transform(fmt, data, best[0], best[2], best[1])
@@ -62,7 +65,7 @@ def transform_bc1_auto_with_normalization(data, estimate, use_all: bool):
     if not any_normalized:
         (v, _sa, sc), out, calls = transform_auto("bc1", data, estimate, use_all)
         return (0, v, sc), out, calls
-    best, best_size, calls = (0, 1, 1), None, []
+    best, best_size, calls = (0, 1, 1), SIZE_MAX, []
     for norm in range(3):
         for v, _sa, sc in test_order("bc1", use_all):
             cand = oracle_c.transform("bc1", outs[norm], v, sc)
@@ -71,7 +74,7 @@ def transform_bc1_auto_with_normalization(data, estimate, use_all: bool):
                 size = estimate(cand[: n // 2])
             except Exception:
                 continue
-            if best_size is None or size < best_size:
+            if size < best_size:
                 best_size, best = size, (norm, v, sc)
     out = oracle_c.transform_bc1_with_normalize_blocks(data, best[0], best[1], bool(best[2]))
     return best, out, calls

@@ -51,12 +51,13 @@ def endpoint_sections(fmt: str, n: int) -> list[tuple[int, int]]:
 
 
 def auto_choice(fmt: str, aos: np.ndarray, estimate) -> bool:
-    """split_endpoints the auto transform picks with `estimate(bytes) -> size`: candidates False, True, strict `<`"""
+    """split_endpoints the auto transform picks with `estimate(bytes) -> size`: candidates False, True, strict `<` against a best
+    that starts at "no split" with 2**64 - 1 (transform_auto_bc45), so a candidate that answers the maximum never wins"""
     n = aos.size // BLOCK[fmt]
-    best, best_size = False, None
+    best, best_size = False, 2**64 - 1
     for cand in (False, True):
         t = transform(fmt, aos, cand)
         size = sum(estimate(t[a:b].tobytes()) for a, b in endpoint_sections(fmt, n))
-        if best_size is None or size < best_size:
+        if size < best_size:
             best, best_size = cand, size
     return best

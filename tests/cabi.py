@@ -108,6 +108,136 @@ def make_estimator(kind: str, log=None):
     return est, py_estimate
 
 
+SIZE_MAX = 2**64 - 1
+
+
+class ScriptedFailure(Exception):
+    """what scripted_estimate raises where the C estimator returns an error code"""
+
+    def __init__(self, code):
+        super().__init__(code)
+        self.code = code
+
+
+def section_key(buf):
+    data = bytes(buf)
+    return len(data), zlib.crc32(data)
+
+
+def scripted_estimate(table, default, log=None, fail_at=None):
+    """estimate(bytes_like) -> size for the CPU statements: the answer table[(len, crc32)] (or `default`), a size or
+    ("fail", code), which raises ScriptedFailure(code).  fail_at = (k, code): call number k (from 0) fails whatever it shows --
+    for the sequential routes, where a section several candidates share is shown several times.  log receives the keys in call
+    order, the failing call's included."""
+    count = [0]
+
+    def estimate(buf):
+        key = section_key(buf)
+        k, count[0] = count[0], count[0] + 1
+        if log is not None:
+            log.append(key)
+        ans = ("fail", fail_at[1]) if fail_at is not None and fail_at[0] == k else table.get(key, default)
+        if isinstance(ans, tuple):
+            raise ScriptedFailure(ans[1])
+        return ans
+
+    return estimate
+
+
+def scripted_estimator(table, default, log=None, fail_at=None, max_extra=64):
+    """A DltSizeEstimator whose answers are scripted: scripted_estimate behind the C callbacks.  A section is known by its
+    (len, crc32(bytes)), not by the call's position: the parallel route estimates each distinct section once, in any order
+    (list.append and the counter run under the interpreter lock).  MaxCompressedSize answers n + max_extra, or 0 (no scratch
+    buffer) when max_extra is None."""
+    py = scripted_estimate(table, default, log, fail_at)
+
+    @MAXFN
+    def max_fn(ctx, n, out):
+        out[0] = 0 if max_extra is None else n + max_extra
+        return 0
+
+    @ESTFN
+    def est_fn(ctx, inp, n, scratch, scratch_len, out):
+        try:
+            out[0] = py(C.string_at(inp, n) if n else b"")
+        except ScriptedFailure as f:
+            return f.code
+        except Exception:               # a key the table does not know and no default: the call must not look like a success
+            return 0xBAD
+        return 0
+
+    est = DltSizeEstimator(None, max_fn, est_fn)
+    est._keep = (max_fn, est_fn)
+    return est
+
+
+def auto_candidates(fmt: str, use_all: bool):
+    """the candidates in the order they are compared, as (mode, split_alpha, split_colour); BC4 / BC5: (0, split_endpoints, 0)"""
+    from oracle import oracle_auto
+
+    if fmt in ("bc4", "bc5"):
+        return [(0, 0, 0), (0, 1, 0)]
+    return list(oracle_auto.test_order(fmt, use_all))
+
+
+def cpu_transform(fmt: str, x, cand):
+    """the CPU statement's transform of x with a candidate of auto_candidates"""
+    from oracle import oracle_c
+
+    import bc45_ref
+
+    if fmt in ("bc4", "bc5"):
+        return bc45_ref.transform(fmt, x, bool(cand[1]))
+    return oracle_c.transform(fmt, x, cand[0], cand[2], cand[1])
+
+
+def candidate_sections(fmt: str, x, use_all: bool):
+    """[(candidate, [(section id, key)])] for every candidate, in the order the reference tries them and shows their sections --
+    BC1 [0, n/2); BC2 [n/2, 3n/4); BC3 alpha [0, 2N) then colour [n/2, n/2 + 4N); BC4 [0, 2N); BC5 [0, 2N) then [8N, 10N) --
+    from the CPU statements alone.  A section id names a DISTINCT section: ("c", mode, split_colour), ("a", split_alpha),
+    ("e" / "r" / "g", split_endpoints); candidates that share settings share it."""
+    n = len(x)
+    blocks = n // (8 if fmt in ("bc1", "bc4") else 16)
+    out = []
+    for cand in auto_candidates(fmt, use_all):
+        mode, sa, sc = cand
+        t = cpu_transform(fmt, x, cand)
+        if fmt == "bc1":
+            spans = [(("c", mode, sc), 0, n // 2)]
+        elif fmt == "bc2":
+            spans = [(("c", mode, sc), n // 2, 3 * n // 4)]
+        elif fmt == "bc3":
+            spans = [(("a", sa), 0, 2 * blocks), (("c", mode, sc), n // 2, n // 2 + 4 * blocks)]
+        elif fmt == "bc4":
+            spans = [(("e", sa), 0, 2 * blocks)]
+        else:
+            spans = [(("r", sa), 0, 2 * blocks), (("g", sa), 8 * blocks, 10 * blocks)]
+        out.append((cand, [(sid, section_key(t[a:b])) for sid, a, b in spans]))
+    return out
+
+
+def distinct_sections(sections):
+    """{section id: key} of candidate_sections' result; asserts the condition every scripted table rests on: a section id has one
+    key, and the distinct sections of the input have pairwise different keys"""
+    keys = {}
+    for _cand, secs in sections:
+        for sid, key in secs:
+            assert keys.setdefault(sid, key) == key, sid
+    assert len(set(keys.values())) == len(keys), "two distinct sections with the same (len, crc32)"
+    return keys
+
+
+def normalization_sections(x, use_all: bool):
+    """[((norm, variant, split), key)] of transform_bc1_auto_with_normalization's 3 x 4 / 3 x 8 candidates in its order: the
+    colour section [0, n/2) of the transform of each buffer of normalize_blocks_all_modes"""
+    from oracle import oracle_auto, oracle_c
+
+    outs, any_normalized = oracle_c.normalize_bc1_blocks_all_modes(x)
+    assert any_normalized
+    return [((norm, v, sc), section_key(oracle_c.transform("bc1", outs[norm], v, sc)[: len(x) // 2]))
+            for norm in range(3) for v, _sa, sc in oracle_auto.test_order("bc1", use_all)]
+
+
 def zstd_c_estimator(level: int = 1):
     """(DltSizeEstimator, lib) over tests/cpp/zstd_estimator.c -- a thread-safe C estimator on the system libzstd that
     counts its calls and its highest concurrency; None when gcc or libzstd is missing."""

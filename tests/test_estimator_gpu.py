@@ -350,7 +350,9 @@ def test_auto_with_the_builtin_estimator(lib, dev, oracle, fmt, use_all):
         assert choice == want_choice and np.array_equal(got, want), (k, "callbacks", choice, want_choice)
         # the built-in estimator behind wrapped pointers: its host-pointer call runs inside the auto call, which keeps the input
         # in this thread's staging buffers the whole time -- also with the arena switched off, where every candidate is one more
-        # transform FROM that input, and with the estimator on several threads (one of them the calling thread)
+        # transform FROM that input, and with the estimator on several threads (one of them the calling thread).
+        # dxtlt_debug_auto_use_arena(0) reaches caller-supplied estimators too: (1, 0) is the sequential one-transform-per-candidate
+        # callback flow (without the arena there is no parallel flow, whatever the thread count)
         for threads, arena_on in ((1, 1), (1, 0), (4, 1)) if k % 2 == 0 or k < 2 else ((1, 1),):
             log = []
             lib.dxtlt_set_auto_estimator_threads(threads)
