@@ -10,43 +10,23 @@
 // (BC1, BC2) or 8 / 16 (BC3) candidates.  This kernel writes them all into an arena:
 //     [alpha pairs 2N][alpha split 2N]                         BC3 only
 //     for variant in (None, Variant1[, Variant2, Variant3]):  [colour pairs 4N][colour split 4N]
-// One 16-byte vector per lane (two BC1 blocks or one BC2 / BC3 block), no LDS: a lane's piece of every section is 2-8
-// contiguous bytes and a wave instruction writes 128-512 contiguous bytes of one section.  Traffic: len read once,
+// (auto_launch.h: auto_sections lists it).  One 16-byte vector per lane (two BC1 blocks or one BC2 / BC3 block), no LDS: a lane's
+// piece of every section is 2-8 contiguous bytes and a wave instruction writes 128-512 contiguous bytes of one section.  What a
+// lane does with its vector is auto_candidate_lanes.h, shared with the batched kernel.  Traffic: len read once,
 // (sections x 4 + 4 [BC3]) bytes per block written -- BC1, fast search: 3 x len against 8 x len for four full
 // transforms.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
+#include "auto_candidate_lanes.h"
 #include "auto_launch.h"
 #include "bcn_launch.h"
 #include "launch_grid.h"
-#include "ycocg_swar.h"
 
 namespace dxtlt {
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-
 namespace {
-
-template <int FMT, int VARIANT>
-__device__ __forceinline__ void colour_sections(uint8_t* __restrict__ pairs, uint64_t n, uint64_t lane_vec, uint32_t ca, uint32_t cb)
-{
-    // pairs: [c0 c1] dwords at 4 * block; split: c0 at 2 * block, c1 at 2 * n + 2 * block (behind the pairs section)
-    uint8_t* split = pairs + 4 * n;
-    const uint32_t da = decorrelate2<VARIANT>(ca);
-    if constexpr (FMT == kBc1) {
-        const uint32_t db = decorrelate2<VARIANT>(cb);
-        *reinterpret_cast<u32x2*>(pairs + 8 * lane_vec) = u32x2{da, db};
-        *reinterpret_cast<uint32_t*>(split + 4 * lane_vec) = (da & 0xFFFFu) | (db << 16);
-        *reinterpret_cast<uint32_t*>(split + 2 * n + 4 * lane_vec) = (da >> 16) | (db & 0xFFFF0000u);
-    } else {
-        *reinterpret_cast<uint32_t*>(pairs + 4 * lane_vec) = da;
-        *reinterpret_cast<uint16_t*>(split + 2 * lane_vec) = (uint16_t)da;
-        *reinterpret_cast<uint16_t*>(split + 2 * n + 2 * lane_vec) = (uint16_t)(da >> 16);
-    }
-}
 
 // n = blocks; the kernel covers the first `vectors` 16-byte vectors (BC1: an odd last block is handled by the caller's
 // tail launch with vectors = 0 semantics -- see launch_auto_candidates)
@@ -58,27 +38,7 @@ auto_candidates_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ are
     if (v >= vectors)
         return;
     const u32x4 q = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(in + 16 * v));
-    uint8_t* colour0 = arena;
-    uint32_t ca, cb = 0;
-    if constexpr (FMT == kBc1) {
-        ca = q.x;
-        cb = q.z;
-    } else {
-        ca = q.z;
-        if constexpr (FMT == kBc3) {
-            // alpha endpoints: pairs section, then split section
-            *reinterpret_cast<uint16_t*>(arena + 2 * v) = (uint16_t)q.x;
-            arena[2 * n + v] = (uint8_t)q.x;
-            arena[3 * n + v] = (uint8_t)(q.x >> 8);
-            colour0 = arena + 4 * n;
-        }
-    }
-    colour_sections<FMT, kNone>(colour0, n, v, ca, cb);
-    colour_sections<FMT, kVar1>(colour0 + 8 * n, n, v, ca, cb);
-    if constexpr (ALL) {
-        colour_sections<FMT, kVar2>(colour0 + 16 * n, n, v, ca, cb);
-        colour_sections<FMT, kVar3>(colour0 + 24 * n, n, v, ca, cb);
-    }
+    candidate_lane<FMT, ALL, false>(arena, n, v, q.x, q.z, false);
 }
 
 // the odd last block of a BC1 buffer (half a vector): one lane, scalar accesses
@@ -86,33 +46,10 @@ template <bool ALL>
 __global__ void auto_candidates_bc1_last_block(const uint8_t* __restrict__ in, uint8_t* __restrict__ arena, uint64_t n)
 {
     const uint64_t b = n - 1;
-    const uint32_t c = *reinterpret_cast<const uint32_t*>(in + 8 * b);
-    auto emit = [&](uint8_t* pairs, uint32_t d) {
-        *reinterpret_cast<uint32_t*>(pairs + 4 * b) = d;
-        *reinterpret_cast<uint16_t*>(pairs + 4 * n + 2 * b) = (uint16_t)d;
-        *reinterpret_cast<uint16_t*>(pairs + 6 * n + 2 * b) = (uint16_t)(d >> 16);
-    };
-    emit(arena, decorrelate2<kNone>(c));
-    emit(arena + 8 * n, decorrelate2<kVar1>(c));
-    if constexpr (ALL) {
-        emit(arena + 16 * n, decorrelate2<kVar2>(c));
-        emit(arena + 24 * n, decorrelate2<kVar3>(c));
-    }
+    candidate_lane<kBc1, ALL, true>(arena, n, b / 2, *reinterpret_cast<const uint32_t*>(in + 8 * b), 0, true);
 }
 
 }  // namespace
-
-uint64_t auto_arena_bytes(Format fmt, bool all_variants, uint64_t blocks)
-{
-    return ((fmt == kBc3 ? 4u : 0u) + (all_variants ? 32u : 16u)) * blocks;
-}
-
-uint64_t auto_section_offset(Format fmt, uint64_t blocks, int variant, bool split_colour)
-{
-    return ((fmt == kBc3 ? 4u : 0u) + 8u * (uint64_t)variant + (split_colour ? 4u : 0u)) * blocks;
-}
-
-uint64_t auto_alpha_section_offset(uint64_t blocks, bool split_alpha) { return split_alpha ? 2 * blocks : 0; }
 
 hipError_t launch_auto_candidates(Format fmt, bool all_variants, const void* d_in, void* d_arena, uint64_t blocks,
                                   hipStream_t stream)

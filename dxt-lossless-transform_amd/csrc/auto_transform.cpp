@@ -22,9 +22,20 @@
 // call.  If the arena (2-4 x len) cannot be allocated the candidates are produced one full transform at a time, as in
 // round 1 (same results, len x 2 of traffic per candidate).
 //
+//
+// BC4 / BC5 (include/dxtlt_bc45.h) go through the same flow with two candidates, split_endpoints = false then true: both full
+// transforms side by side in the arena (2 x len; one upload, two launches), the estimator is shown BC4 [0, 2N), BC5 red [0, 2N)
+// then green [8N, 10N), added, and the winner's arena copy is what is downloaded.
+//
+// The flow is written once, transform_auto(), over where a candidate's sections come from (Source): the fused arena, the full
+// transforms side by side, or one full transform per candidate through d_out.  Stated once and used by every route: the candidate
+// orders (candidates_of), the section(s) of a transformed buffer the estimator is shown (shown_sections), the distinct sections of
+// a candidate arena (dxtlt::auto_sections) with the ones a candidate is the sum of (sections_of) and the pick over them
+// (auto_pick), and the estimator thread count (estimator_threads).
+//
 // The built-in estimator (include/dxtlt_estimator.h, estimate_kernels.hip) is recognised by the identity of its function
 // pointers and never called: auto_on_device() estimates every distinct section where the candidate kernel left it, with one
-// launch, reads back 6 / 10 counters and applies the same order, additions and strict `<`.  No section crosses PCIe.  The same
+// launch, reads back 4 - 10 counters and applies the same order, additions and strict `<`.  No section crosses PCIe.  The same
 // function serves dxtlt_transform_bcN_auto_device, where the input and the result stay on the device as well.
 #include <algorithm>
 #include <atomic>
@@ -49,32 +60,94 @@ struct Candidate {
 };
 
 // bc1/bc2 settings.rs:81-86 and :89-98
-const Candidate kFast12[] = {{0, false, false}, {0, false, true}, {1, false, false}, {1, false, true}};
-const Candidate kAll12[] = {{2, false, false}, {0, false, false}, {0, false, true}, {3, false, false},
+constexpr Candidate kFast12[] = {{0, false, false}, {0, false, true}, {1, false, false}, {1, false, true}};
+constexpr Candidate kAll12[] = {{2, false, false}, {0, false, false}, {0, false, true}, {3, false, false},
                             {3, false, true},  {2, false, true},  {1, false, false}, {1, false, true}};
 // bc3 settings.rs:91-100 and :104-121  (variant, split_alphas, split_colours)
-const Candidate kFast3[] = {{1, true, false}, {1, true, true},  {0, true, false},  {0, false, true},
+constexpr Candidate kFast3[] = {{1, true, false}, {1, true, true},  {0, true, false},  {0, false, true},
                             {0, true, true},  {1, false, true}, {0, false, false}, {1, false, false}};
-const Candidate kAll3[] = {{2, true, false},  {2, true, true},  {3, true, true},   {3, true, false},
+constexpr Candidate kAll3[] = {{2, true, false},  {2, true, true},  {3, true, true},   {3, true, false},
                            {1, true, false},  {3, false, true}, {1, true, true},   {2, false, true},
                            {2, false, false}, {3, false, false}, {0, true, false}, {0, false, true},
                            {0, true, true},   {1, false, true}, {0, false, false}, {1, false, false}};
 
-bool same(const Candidate& a, const Candidate& b)
+struct Order {
+    const Candidate* order;
+    int count;
+    int defaults;   // index of the format's default settings: Bc1 / Bc2 {Variant1, split}, Bc3 {Variant1, split alphas, split colours};
+                    // BC4 / BC5: candidate 0.  The initial best of the callback flow, with size SIZE_MAX.
+};
+
+Order candidates_of(int32_t format, bool use_all)
 {
-    return a.mode == b.mode && a.split_alpha == b.split_alpha && a.split_colour == b.split_colour;
+    static const Candidate k45[] = {{0, false, false}, {0, true, false}};   // split_endpoints = false, then true
+    if (format >= 4)
+        return {k45, 2, 0};
+    if (format == 3)
+        return use_all ? Order{kAll3, 16, 6} : Order{kFast3, 8, 1};
+    return use_all ? Order{kAll12, 8, 7} : Order{kFast12, 4, 3};
 }
 
-// every failure exit drains the stream first: the staging buffers and the arena belong to this thread's next call
-#define AUTO_TRY(expr, what)                                            \
-    do {                                                                \
-        hipError_t e_ = (expr);                                         \
-        if (e_ != hipSuccess) {                                         \
-            if (st) (void)hipStreamSynchronize(st);                     \
-            std::free(scratch);                                         \
-            return dxtlt_host::fail(dxtlt_host::kDevice, what, e_);     \
-        }                                                               \
-    } while (0)
+constexpr bool is_default(const Candidate& c, bool bc3) { return c.mode == 1 && c.split_alpha == bc3 && c.split_colour; }
+static_assert(is_default(kFast12[3], false) && is_default(kAll12[7], false) && is_default(kFast3[1], true) && is_default(kAll3[6], true),
+              "candidates_of: the index of the default settings");
+
+// The section(s) of a transformed buffer of `len` bytes the estimator is shown, in the order their sizes are added: BC1 the colour
+// endpoints [0, len/2); BC2 [len/2, + len/4); BC3 alpha endpoints [0, 2N) then colour endpoints [len/2, + 4N); BC4 [0, 2N); BC5
+// red [0, 2N) then green [8N, + 2N).
+struct Shown {
+    int count;
+    size_t off[2], len[2];
+};
+
+Shown shown_sections(int32_t format, size_t len)
+{
+    switch (format) {
+    case 1: return {1, {0, 0}, {len / 2, 0}};
+    case 2: return {1, {len / 2, 0}, {len / 4, 0}};
+    case 3: return {2, {0, len / 2}, {len / 8, len / 4}};
+    case 4: return {1, {0, 0}, {len / 4, 0}};
+    default: return {2, {0, len / 2}, {len / 8, len / 8}};
+    }
+}
+
+// The distinct sections (indices into dxtlt::auto_sections) candidate c of `format` is the sum of, in shown_sections' order.
+void sections_of(int32_t format, const Candidate& c, int* idx)
+{
+    const int sa = c.split_alpha ? 1 : 0, colour = c.mode * 2 + (c.split_colour ? 1 : 0);
+    switch (format) {
+    case 3: idx[0] = sa; idx[1] = 2 + colour; break;
+    case 4: idx[0] = sa; break;
+    case 5: idx[0] = sa; idx[1] = 2 + sa; break;
+    default: idx[0] = colour; break;
+    }
+}
+
+// Estimator scratch of one thread: freed on every exit.
+struct HostScratch {
+    uint8_t* ptr = nullptr;
+    HostScratch() = default;
+    HostScratch(const HostScratch&) = delete;
+    ~HostScratch() { std::free(ptr); }
+    bool allocate(size_t max_comp)   // nothing for max_comp == 0
+    {
+        if (max_comp != 0)
+            ptr = static_cast<uint8_t*>(std::aligned_alloc(64, (max_comp + 63) / 64 * 64));
+        return max_comp == 0 || ptr != nullptr;
+    }
+};
+
+// THE invariant of every auto route: no exit returns while work that reads or writes this thread's staging buffers, pinned stage
+// or arena is in flight -- they belong to this thread's next call.  Armed once anything has been enqueued, the guard waits for the
+// stream on every exit; the success path waits itself (it has to report a failure of the wait) and disarms it.
+struct StreamDrain {
+    hipStream_t stream = nullptr;
+    bool armed = false;
+    ~StreamDrain()
+    {
+        if (armed) (void)hipStreamSynchronize(stream);
+    }
+};
 
 // per-thread candidate arena (grow-only, like the staging buffers)
 struct Arena {
@@ -153,6 +226,12 @@ std::atomic<int> g_estimator_threads{1};
 thread_local int t_estimator_threads_cap = 0;
 constexpr size_t kStageCapBytes = size_t(512) << 20;   // pinned staging per wave of sections (one section at least)
 
+int estimator_threads()
+{
+    const int threads = g_estimator_threads.load(std::memory_order_relaxed);
+    return t_estimator_threads_cap > 0 ? std::min(threads, t_estimator_threads_cap) : threads;
+}
+
 struct HostStage {
     void* ptr = nullptr;
     size_t cap = 0;
@@ -209,13 +288,10 @@ bool estimate_sections_parallel(std::vector<Section>& sections, const DltSizeEst
         return false;
     }
     threads = std::max(1, std::min<int>(threads, (int)sections.size()));
-    std::vector<uint8_t*> scratch((size_t)threads, nullptr);
+    std::vector<HostScratch> scratch((size_t)threads);
     bool ok = true;
-    if (max_comp != 0)
-        for (auto& p : scratch) {
-            p = static_cast<uint8_t*>(std::aligned_alloc(64, (max_comp + 63) / 64 * 64));
-            ok = ok && p != nullptr;
-        }
+    for (HostScratch& p : scratch)
+        ok = p.allocate(max_comp) && ok;
     *hip_error = ok ? hipSuccess : hipErrorOutOfMemory;
     size_t first = 0;
     while (ok && first < sections.size()) {
@@ -243,7 +319,7 @@ bool estimate_sections_parallel(std::vector<Section>& sections, const DltSizeEst
                 if (i >= last)
                     return;
                 Section& s = sections[i];
-                s.rc = est->EstimateCompressedSize(est->Context, stage + s.slot, s.len, scratch[(size_t)tid], max_comp, &s.size);
+                s.rc = est->EstimateCompressedSize(est->Context, stage + s.slot, s.len, scratch[(size_t)tid].ptr, max_comp, &s.size);
             }
         };
         // a thread that cannot be started (EAGAIN under a process limit) is simply not part of the pool: the sections are
@@ -262,8 +338,6 @@ bool estimate_sections_parallel(std::vector<Section>& sections, const DltSizeEst
         t_estimator_callbacks += last - first;   // (the workers have counters of their own)
         first = last;
     }
-    for (auto p : scratch)
-        std::free(p);
     return ok;
 }
 
@@ -271,21 +345,6 @@ bool estimate_sections_parallel(std::vector<Section>& sections, const DltSizeEst
 // ---------------------------------------------------------------------------------------------------------------
 // The built-in estimator: everything on the device.
 // ---------------------------------------------------------------------------------------------------------------
-struct Order {
-    const Candidate* order;
-    int count;
-};
-
-Order candidates_of(int32_t format, bool use_all)
-{
-    static const Candidate k45[] = {{0, false, false}, {0, true, false}};   // split_endpoints = false, then true
-    if (format >= 4)
-        return {k45, 2};
-    if (format == 3)
-        return {use_all ? kAll3 : kFast3, use_all ? 16 : 8};
-    return {use_all ? kAll12 : kFast12, use_all ? 8 : 4};
-}
-
 // Chooses among the candidates of `format` (1..5) for the `len` > 0 bytes at d_in with the built-in estimator and leaves the
 // transform with *best enqueued from d_in into d_out.  Enqueues on `st` and waits for it once, for the counters: when it returns
 // nothing in flight reads or writes this thread's arena or counters any more (the pending transform reads d_in alone), so the
@@ -297,16 +356,7 @@ int32_t auto_on_device(int32_t format, const void* d_in, void* d_out, size_t len
     const Order o = candidates_of(format, use_all);
     const uint64_t blocks = len / (format == 1 || format == 4 ? 8 : 16);
     uint8_t* out8 = static_cast<uint8_t*>(d_out);
-    // the section(s) of a transformed buffer at `base` the estimator is shown, in the order their sizes are added
-    auto shown = [&](const uint8_t* base, dxtlt::EstimateSection* secs) -> int {
-        switch (format) {
-        case 1: secs[0] = {base, len / 2}; return 1;
-        case 2: secs[0] = {base + len / 2, len / 4}; return 1;
-        case 3: secs[0] = {base, blocks * 2}; secs[1] = {base + len / 2, blocks * 4}; return 2;
-        case 4: secs[0] = {base, blocks * 2}; return 1;
-        default: secs[0] = {base, blocks * 2}; secs[1] = {base + blocks * 8, blocks * 2}; return 2;
-        }
-    };
+    const Shown shown = shown_sections(format, len);
     uint64_t sizes[kMaxCounters];
     uint64_t total[16];
     int last = -1;   // the candidate whose transform is in d_out
@@ -315,27 +365,21 @@ int32_t auto_on_device(int32_t format, const void* d_in, void* d_out, size_t len
     // BC1-3: the candidate kernel reads the input as 16-byte vectors; an input off a 16-byte boundary takes the no-arena route,
     // whose transform kernels take any alignment (one full transform per candidate instead of one read)
     const bool vector_aligned = (reinterpret_cast<uintptr_t>(d_in) & 15) == 0;
+    const dxtlt::AutoSections distinct = dxtlt::auto_sections((dxtlt::Format)format, use_all, blocks);
     uint8_t* arena = nullptr;
     if (!t_no_arena && (format >= 4 || vector_aligned))
-        arena = static_cast<uint8_t*>(g_arena.get(format >= 4 ? 2 * len : (size_t)dxtlt::auto_arena_bytes((dxtlt::Format)format, use_all, blocks)));
+        arena = static_cast<uint8_t*>(g_arena.get(format >= 4 ? 2 * len : (size_t)distinct.bytes));
     if (arena != nullptr && format <= 3) {
-        // one read of the input -> every distinct section: colour (variant, split) pairs, then BC3's two alpha-endpoint sections
+        // one read of the input -> every distinct section, estimated where it lies
         HIP_TRY(dxtlt::launch_auto_candidates((dxtlt::Format)format, use_all, d_in, arena, blocks, st), "candidate kernel launch");
-        const int variants = use_all ? 4 : 2;
-        const size_t colour_len = format == 1 ? len / 2 : len / 4;
         dxtlt::EstimateSection secs[10];
-        int n = 0;
-        for (int m = 0; m < variants; ++m)
-            for (int sp = 0; sp < 2; ++sp)
-                secs[n++] = {arena + dxtlt::auto_section_offset((dxtlt::Format)format, blocks, m, sp != 0), colour_len};
-        if (format == 3)
-            for (int sp = 0; sp < 2; ++sp)
-                secs[n++] = {arena + dxtlt::auto_alpha_section_offset(blocks, sp != 0), blocks * 2};
-        if (int32_t rc = estimate_enqueue(secs, (size_t)n, st, 0))
+        for (int k = 0; k < distinct.count; ++k)
+            secs[k] = {arena + distinct.off[k], distinct.len[k]};
+        if (int32_t rc = estimate_enqueue(secs, (size_t)distinct.count, st, 0))
             return rc;
-        if (int32_t rc = estimate_read_back((size_t)n, st, sizes))
+        if (int32_t rc = estimate_read_back((size_t)distinct.count, st, sizes))
             return rc;
-        pick = auto_pick_single(format, use_all, false, sizes, total);
+        pick = auto_pick(format, use_all, false, sizes, total);
     } else {
         // BC4 / BC5 with the arena: both transforms side by side (the winner is transformed once more, into d_out: a copy out of
         // the arena would still be reading it when this thread's next call fills it).  Without it: one full transform per
@@ -347,14 +391,13 @@ int32_t auto_on_device(int32_t format, const void* d_in, void* d_out, size_t len
                 return rc;
             if (arena == nullptr)
                 last = i;
-            dxtlt::EstimateSection secs[2];
-            const int shown_per = shown(dst, secs);
-            if (int32_t rc = estimate_enqueue(secs, (size_t)shown_per, st, (size_t)(i * 2)))
+            const dxtlt::EstimateSection secs[2] = {{dst + shown.off[0], shown.len[0]}, {dst + shown.off[1], shown.len[1]}};
+            if (int32_t rc = estimate_enqueue(secs, (size_t)shown.count, st, (size_t)(i * 2)))
                 return rc;
         }
         if (int32_t rc = estimate_read_back((size_t)o.count * 2, st, sizes))
             return rc;
-        pick = auto_pick_single(format, use_all, true, sizes, total);
+        pick = auto_pick(format, use_all, true, sizes, total);
     }
 
     *best = o.order[pick];
@@ -375,7 +418,7 @@ void report(const Candidate& c, dxtlt_host::AutoChoice* choice)
     choice->estimator_error = 0;
 }
 
-// dxtlt_host::transform_auto / transform_auto_bc45 given the built-in estimator (arguments validated by the caller)
+// dxtlt_host::transform_auto given the built-in estimator (arguments validated by the caller)
 int32_t auto_builtin_host(int32_t format, const uint8_t* in, uint8_t* out, size_t len, bool use_all, dxtlt_host::AutoChoice* choice)
 {
     using namespace dxtlt_host;
@@ -432,17 +475,35 @@ int dxtlt_host::auto_candidate_order(int32_t format, bool use_all, AutoChoice* o
     return o.count;
 }
 
-int dxtlt_host::auto_pick_single(int32_t format, bool use_all, bool per_candidate, const uint64_t* sizes, uint64_t* total)
+dxtlt::AutoSections dxtlt::auto_sections(Format fmt, bool all_variants, uint64_t blocks)
+{
+    AutoSections s{};
+    auto add = [&](int sections, uint64_t bytes_per_block) {
+        for (int k = 0; k < sections; ++k) {
+            s.off[s.count] = s.bytes;
+            s.len[s.count++] = bytes_per_block * blocks;
+            s.bytes += bytes_per_block * blocks;
+        }
+    };
+    if (fmt == kBc4 || fmt == kBc5)
+        add(fmt == kBc5 ? 4 : 2, 2);
+    else {
+        if (fmt == kBc3)
+            add(2, 2);
+        add(all_variants ? 8 : 4, 4);
+    }
+    return s;
+}
+
+int dxtlt_host::auto_pick(int32_t format, bool use_all, bool per_candidate, const uint64_t* sizes, uint64_t* total)
 {
     const Order o = candidates_of(format, use_all);
-    const int alpha_first = use_all ? 8 : 4;   // behind the colour sections
     const bool two_shown = format == 3 || format == 5;
     for (int i = 0; i < o.count; ++i) {
-        const Candidate c = o.order[i];
-        if (per_candidate)
-            total[i] = sizes[2 * i] + (two_shown ? sizes[2 * i + 1] : 0);
-        else
-            total[i] = (format == 3 ? sizes[alpha_first + (c.split_alpha ? 1 : 0)] : 0) + sizes[c.mode * 2 + (c.split_colour ? 1 : 0)];
+        int idx[2] = {2 * i, 2 * i + 1};
+        if (!per_candidate)
+            sections_of(format, o.order[i], idx);
+        total[i] = sizes[idx[0]] + (two_shown ? sizes[idx[1]] : 0);
     }
     int pick = 0;
     for (int i = 1; i < o.count; ++i)
@@ -459,215 +520,180 @@ void dxtlt_host::auto_begin_device_call()
     t_section_bytes_downloaded = t_estimator_callbacks = 0;
 }
 
+// Where the sections of the callback flow's candidates come from, and with them how the winner reaches the output.
+enum class Source {
+    kFused,        // BC1-3: every distinct section in the arena from one read (launch_auto_candidates); the winner is transformed once
+    kSideBySide,   // BC4 / BC5: both full transforms in the arena (2 x len); the winner's copy is downloaded
+    kOneByOne,     // no arena, or nothing to transform: one full transform per candidate into d_out, again for the winner unless it
+                   // was the last one tried
+};
+
 int32_t dxtlt_host::transform_auto(int32_t format, const uint8_t* in, uint8_t* out, size_t len,
                                    const DltSizeEstimator* est, bool use_all, AutoChoice* choice)
 {
     t_last_total_count = 0;   // whatever this call does next: no totals of an earlier one
-    if (format < 1 || format > 3)
-        return fail(kInvalidArgument, "format must be 1 (BC1), 2 (BC2) or 3 (BC3)");
-    const size_t block = format == 1 ? 8 : 16;
+    if (format < 1 || format > 5)
+        return fail(kInvalidArgument, "format must be 1..5 (BC1..BC5)");
+    const size_t block = format == 1 || format == 4 ? 8 : 16;
     if (len % block != 0)
         return fail(kInvalidLength, "len is not a multiple of the block size");
     if (est == nullptr || est->MaxCompressedSize == nullptr || est->EstimateCompressedSize == nullptr || choice == nullptr)
         return fail(kInvalidArgument, "NULL estimator / choice");
     if (len > 0 && (in == nullptr || out == nullptr))
         return fail(kInvalidArgument, "NULL buffer with len > 0");
+    use_all = use_all && format <= 3;
 
     t_section_bytes_downloaded = t_estimator_callbacks = 0;
     if (is_builtin_estimator(est))
         return auto_builtin_host(format, in, out, len, use_all, choice);
 
     const uint64_t blocks = len / block;
-    // defaults: Bc1/Bc2 {Variant1, split}, Bc3 {Variant1, split alphas, split colours}
-    Candidate best{1, format == 3, true};
-    Candidate last = best;
-    size_t best_size = SIZE_MAX;
+    const Order o = candidates_of(format, use_all);
+    const Shown shown = shown_sections(format, len);
     choice->estimator_error = 0;
+    auto fail_estimate = [&](uint32_t bad, const char* what) {
+        choice->estimator_error = bad;
+        return fail(kEstimator, what);
+    };
 
-    // the section(s) the estimator sees
-    const size_t colour_off = format == 1 ? 0 : len / 2;
-    const size_t colour_len = format == 1 ? len / 2 : len / 4;
-    const size_t alpha_len = format == 3 ? (size_t)blocks * 2 : 0;
-
-    size_t max_comp = 0;
-    uint32_t rc_est = call_max(est, format == 1 ? len / 2 : len / 4, &max_comp);
-    if (rc_est != 0) {
-        choice->estimator_error = rc_est;
-        return fail(kEstimator, "size estimator: max_compressed_size failed");
-    }
-    uint8_t* scratch = nullptr;
-    if (max_comp != 0) {
-        scratch = static_cast<uint8_t*>(std::aligned_alloc(64, (max_comp + 63) / 64 * 64));
-        if (scratch == nullptr)
-            return fail(kAllocation, "estimator scratch allocation failed");
-    }
+    size_t max_comp = 0;   // one query: len/2 for BC1, len/4 for BC2 / BC3, 2N for BC4 / BC5 -- the longest section shown
+    if (uint32_t bad = call_max(est, std::max(shown.len[0], shown.len[1]), &max_comp))
+        return fail_estimate(bad, "size estimator: max_compressed_size failed");
+    HostScratch scratch;
+    if (!scratch.allocate(max_comp))
+        return fail(kAllocation, "estimator scratch allocation failed");
 
     void *d_in = nullptr, *d_out = nullptr;
-    hipStream_t st = nullptr;
-    uint8_t* arena = nullptr;   // device: every candidate section, from one read of the input
+    StreamDrain drain;
+    hipStream_t& st = drain.stream;
+    uint8_t* arena = nullptr;
+    dxtlt::AutoSections distinct{};
     if (len > 0) {
-        int32_t rc = acquire_staging(len, &d_in, &d_out, &st);
-        if (rc != kOk) {
-            std::free(scratch);
+        if (int32_t rc = acquire_staging(len, &d_in, &d_out, &st))
             return rc;
-        }
-        AUTO_TRY(hipMemcpyAsync(d_in, in, len, hipMemcpyHostToDevice, st), "H2D copy");
+        drain.armed = true;
+        HIP_TRY(hipMemcpyAsync(d_in, in, len, hipMemcpyHostToDevice, st), "H2D copy");
         static const bool fused = [] { const char* v = dxtlt::experiment_env("DXTLT_AUTO_FUSED"); return !(v && v[0] == '0'); }();
-        if (fused && !t_no_arena)
-            arena = static_cast<uint8_t*>(g_arena.get((size_t)dxtlt::auto_arena_bytes((dxtlt::Format)format, use_all, blocks)));
-        if (arena != nullptr)
-            AUTO_TRY(dxtlt::launch_auto_candidates((dxtlt::Format)format, use_all, d_in, arena, blocks, st),
-                     "candidate kernel launch");
+        if (format >= 4 && !t_no_arena) {
+            arena = static_cast<uint8_t*>(g_arena.get(2 * len));
+            for (int i = 0; i < o.count && arena != nullptr; ++i)
+                if (int32_t rc = enqueue(format, false, d_in, arena + (size_t)i * len, blocks, 0, o.order[i].split_alpha, false, st))
+                    return rc;
+        } else if (format <= 3 && fused && !t_no_arena) {
+            distinct = dxtlt::auto_sections((dxtlt::Format)format, use_all, blocks);
+            arena = static_cast<uint8_t*>(g_arena.get((size_t)distinct.bytes));
+            if (arena != nullptr)
+                HIP_TRY(dxtlt::launch_auto_candidates((dxtlt::Format)format, use_all, d_in, arena, blocks, st), "candidate kernel launch");
+        }
     }
+    const Source source = arena == nullptr ? Source::kOneByOne : format >= 4 ? Source::kSideBySide : Source::kFused;
+    // section h of candidate i where the source holds it on the device (kOneByOne: once its transform has been enqueued)
+    auto device_section = [&](int i, int h) -> const uint8_t* {
+        if (source == Source::kFused) {
+            int idx[2];
+            sections_of(format, o.order[i], idx);
+            return arena + distinct.off[idx[h]];
+        }
+        return (source == Source::kSideBySide ? arena + (size_t)i * len : static_cast<const uint8_t*>(d_out)) + shown.off[h];
+    };
 
-    const Candidate* order;
-    int count;
-    if (format == 3) {
-        order = use_all ? kAll3 : kFast3;
-        count = use_all ? 16 : 8;
-    } else {
-        order = use_all ? kAll12 : kFast12;
-        count = use_all ? 8 : 4;
-    }
-
-    int est_threads = g_estimator_threads.load(std::memory_order_relaxed);
-    if (t_estimator_threads_cap > 0 && est_threads > t_estimator_threads_cap)
-        est_threads = t_estimator_threads_cap;
-    const bool parallel = est_threads > 1 && arena != nullptr && len > 0;
-    if (parallel) {
-        // distinct sections: colour (variant, split) pairs in the arena's order, then BC3's two alpha-endpoint sections
-        const int variants = use_all ? 4 : 2;
+    int best = o.defaults, last = -1;   // last: the candidate whose transform is in d_out (kOneByOne)
+    size_t best_size = SIZE_MAX;
+    const int est_threads = estimator_threads();
+    if (est_threads > 1 && arena != nullptr) {
+        // every distinct section (kFused) or every section of every candidate (kSideBySide) at once; combined in the sequential
+        // order, so that the failure reported is the one the sequential flow meets first
         std::vector<Section> sections;
-        for (int m = 0; m < variants; ++m)
-            for (int sp = 0; sp < 2; ++sp)
-                sections.push_back(Section{arena + dxtlt::auto_section_offset((dxtlt::Format)format, blocks, m, sp != 0), colour_len});
-        const size_t alpha_first = sections.size();
-        if (format == 3)
-            for (int sp = 0; sp < 2; ++sp)
-                sections.push_back(Section{arena + dxtlt::auto_alpha_section_offset(blocks, sp != 0), alpha_len});
+        for (int k = 0; k < distinct.count; ++k)
+            sections.push_back(Section{arena + distinct.off[k], (size_t)distinct.len[k]});
+        for (int i = 0; i < o.count && source == Source::kSideBySide; ++i)
+            for (int h = 0; h < shown.count; ++h)
+                sections.push_back(Section{device_section(i, h), shown.len[h]});
         hipError_t herr = hipSuccess;
         if (!estimate_sections_parallel(sections, est, max_comp, est_threads, st, &herr))
-            AUTO_TRY(herr == hipSuccess ? hipErrorUnknown : herr, "parallel estimation (staging / download)");
-        for (int i = 0; i < count; ++i) {
-            const Candidate c = order[i];
+            return fail(kDevice, "parallel estimation (staging / download)", herr == hipSuccess ? hipErrorUnknown : herr);
+        for (int i = 0; i < o.count; ++i) {
+            int idx[2] = {i * shown.count, i * shown.count + 1};
+            if (source == Source::kFused)
+                sections_of(format, o.order[i], idx);
             size_t total = 0;
-            uint32_t bad = 0;
-            if (format == 3) {   // the reference's order inside a candidate: alpha endpoints, then colour endpoints
-                const Section& a = sections[alpha_first + (c.split_alpha ? 1 : 0)];
-                bad = a.rc;
-                total = a.size;
-            }
-            const Section& col = sections[(size_t)c.mode * 2 + (c.split_colour ? 1 : 0)];
-            if (bad == 0)
-                bad = col.rc;
-            total += col.size;
-            if (bad != 0) {   // the sequential flow stops at the first candidate whose estimate fails
-                std::free(scratch);
-                choice->estimator_error = bad;
-                return fail(kEstimator, "size estimator: estimate_compressed_size failed");
+            for (int h = 0; h < shown.count; ++h) {
+                const Section& sec = sections[(size_t)idx[h]];
+                if (sec.rc != 0)
+                    return fail_estimate(sec.rc, "size estimator: estimate_compressed_size failed");
+                total += sec.size;
             }
             if (total < best_size) {
                 best_size = total;
-                best = c;
+                best = i;
             }
         }
-    }
+    } else {
+        // kFused: the sections of candidate i + 1 travel into the other half of a pinned staging buffer while the estimator works on
+        // candidate i -- the reference's sequence of calls and bytes, minus the wait for every download (and minus pageable-memory
+        // copies); the estimator is shown the staged bytes.  Otherwise, or when a slot would pass 512 MiB or cannot be allocated, a
+        // candidate's sections are downloaded into the output buffer at the offsets the reference estimates at, and waited for.
+        const size_t second = shown.count == 2 ? (shown.len[0] + 255) & ~size_t(255) : 0;   // of a slot's second section
+        const size_t slot_bytes = second + ((shown.len[shown.count - 1] + 255) & ~size_t(255));
+        uint8_t* stage = nullptr;
+        if (source == Source::kFused && slot_bytes <= kStageCapBytes)
+            stage = static_cast<uint8_t*>(g_stage.get(2 * slot_bytes));
+        auto download = [&](int i, uint8_t* first_to, uint8_t* second_to) -> hipError_t {
+            hipError_t e = download_section(first_to, device_section(i, 0), shown.len[0], st);
+            if (e == hipSuccess && shown.count == 2)
+                e = download_section(second_to, device_section(i, 1), shown.len[1], st);
+            return e;
+        };
+        auto slot = [&](int i) { return stage + (size_t)(i & 1) * slot_bytes; };
+        auto stage_candidate = [&](int i) { return download(i, slot(i), slot(i) + second); };
+        if (stage != nullptr)
+            HIP_TRY(stage_candidate(0), "D2H candidate sections");
 
-    // Sequential mode with the arena: the sections of candidate i + 1 travel into the other half of a pinned staging buffer
-    // while the estimator works on candidate i -- the reference's sequence of calls and bytes, minus the wait for every
-    // download (and minus pageable-memory copies).  The estimator is shown the staged bytes, not the output buffer.
-    const size_t alpha_slot = (alpha_len + 255) & ~size_t(255), slot_bytes = alpha_slot + ((colour_len + 255) & ~size_t(255));
-    uint8_t* stage = nullptr;
-    if (!parallel && arena != nullptr && len > 0 && slot_bytes <= (size_t(512) << 20))
-        stage = static_cast<uint8_t*>(g_stage.get(2 * slot_bytes));
-    auto issue_sections = [&](int i) -> hipError_t {
-        const Candidate c = order[i];
-        uint8_t* slot = stage + (size_t)(i & 1) * slot_bytes;
-        hipError_t e = hipSuccess;
-        if (alpha_len)
-            e = download_section(slot, arena + dxtlt::auto_alpha_section_offset(blocks, c.split_alpha), alpha_len, st);
-        if (e == hipSuccess)
-            e = download_section(slot + alpha_slot, arena + dxtlt::auto_section_offset((dxtlt::Format)format, blocks, c.mode, c.split_colour),
-                                 colour_len, st);
-        return e;
-    };
-    if (stage != nullptr)
-        AUTO_TRY(issue_sections(0), "D2H candidate sections");
-
-    for (int i = 0; i < count && !parallel; ++i) {
-        const Candidate c = order[i];
-        const uint8_t* shown_alpha = out;
-        const uint8_t* shown_colour = out + colour_off;
-        if (stage != nullptr) {
-            AUTO_TRY(hipStreamSynchronize(st), "stream synchronize");   // candidate i has arrived
-            if (i + 1 < count)
-                AUTO_TRY(issue_sections(i + 1), "D2H candidate sections");
-            shown_alpha = stage + (size_t)(i & 1) * slot_bytes;
-            shown_colour = shown_alpha + alpha_slot;
-        } else if (len > 0) {
-            const uint8_t* alpha_src = (const uint8_t*)d_out;
-            const uint8_t* colour_src = (const uint8_t*)d_out + colour_off;
-            if (arena != nullptr) {
-                alpha_src = arena + dxtlt::auto_alpha_section_offset(blocks, c.split_alpha);
-                colour_src = arena + dxtlt::auto_section_offset((dxtlt::Format)format, blocks, c.mode, c.split_colour);
-            } else {
-                int32_t rc = enqueue(format, false, d_in, d_out, blocks, c.mode, c.split_alpha, c.split_colour, st);
-                if (rc != kOk) {
-                    (void)hipStreamSynchronize(st);
-                    std::free(scratch);
-                    return rc;
+        for (int i = 0; i < o.count; ++i) {
+            const Candidate c = o.order[i];
+            const uint8_t* seen[2] = {out + shown.off[0], out + shown.off[1]};
+            if (stage != nullptr) {
+                HIP_TRY(hipStreamSynchronize(st), "stream synchronize");   // candidate i has arrived
+                if (i + 1 < o.count)
+                    HIP_TRY(stage_candidate(i + 1), "D2H candidate sections");
+                seen[0] = slot(i);
+                seen[1] = slot(i) + second;
+            } else if (len > 0) {
+                if (source == Source::kOneByOne) {
+                    if (int32_t rc = enqueue(format, false, d_in, d_out, blocks, c.mode, c.split_alpha, c.split_colour, st))
+                        return rc;
+                    last = i;
                 }
-                last = c;
+                HIP_TRY(download(i, out + shown.off[0], out + shown.off[1]), "D2H endpoint sections");
+                HIP_TRY(hipStreamSynchronize(st), "stream synchronize");
             }
-            if (alpha_len)
-                AUTO_TRY(download_section(out, alpha_src, alpha_len, st), "D2H alpha endpoints");
-            AUTO_TRY(download_section(out + colour_off, colour_src, colour_len, st), "D2H colour endpoints");
-            AUTO_TRY(hipStreamSynchronize(st), "stream synchronize");
-        } else {
-            last = c;
-        }
-
-        size_t total = 0, part = 0;
-        if (format == 3) {
-            rc_est = call_estimate(est, shown_alpha, alpha_len, scratch, max_comp, &part);
-            if (rc_est == 0) {
-                total = part;
-                part = 0;
-                rc_est = call_estimate(est, shown_colour, colour_len, scratch, max_comp, &part);
+            size_t total = 0;
+            for (int h = 0; h < shown.count; ++h) {   // a candidate's second estimate is not asked for when its first fails
+                size_t part = 0;
+                if (uint32_t bad = call_estimate(est, seen[h], shown.len[h], scratch.ptr, max_comp, &part))
+                    return fail_estimate(bad, "size estimator: estimate_compressed_size failed");
                 total += part;
             }
-        } else {
-            rc_est = call_estimate(est, shown_colour, colour_len, scratch, max_comp, &total);
-        }
-        if (rc_est != 0) {
-            if (st) (void)hipStreamSynchronize(st);   // a download of the next candidate may be in flight
-            std::free(scratch);
-            choice->estimator_error = rc_est;
-            return fail(kEstimator, "size estimator: estimate_compressed_size failed");
-        }
-        if (total < best_size) {
-            best_size = total;
-            best = c;
+            if (total < best_size) {
+                best_size = total;
+                best = i;
+            }
         }
     }
 
+    const Candidate won = o.order[best];
     if (len > 0) {
-        // with the arena no full transform has run yet; without it the last candidate's is in d_out
-        if (arena != nullptr || !same(best, last)) {
-            int32_t rc = enqueue(format, false, d_in, d_out, blocks, best.mode, best.split_alpha, best.split_colour, st);
-            if (rc != kOk) {
-                (void)hipStreamSynchronize(st);
-                std::free(scratch);
+        if (source == Source::kFused || (source == Source::kOneByOne && best != last))
+            if (int32_t rc = enqueue(format, false, d_in, d_out, blocks, won.mode, won.split_alpha, won.split_colour, st))
                 return rc;
-            }
-        }
-        AUTO_TRY(hipMemcpyAsync(out, d_out, len, hipMemcpyDeviceToHost, st), "D2H result");
-        AUTO_TRY(hipStreamSynchronize(st), "stream synchronize");
+        const void* result = source == Source::kSideBySide ? static_cast<const void*>(arena + (size_t)best * len) : d_out;
+        HIP_TRY(hipMemcpyAsync(out, result, len, hipMemcpyDeviceToHost, st), "D2H result");
+        HIP_TRY(hipStreamSynchronize(st), "stream synchronize");
+        drain.armed = false;
     }
-    std::free(scratch);
-    choice->mode = best.mode;
-    choice->split_alpha = best.split_alpha;
-    choice->split_colour = best.split_colour;
+    choice->mode = won.mode;
+    choice->split_alpha = won.split_alpha;
+    choice->split_colour = won.split_colour;
     return kOk;
 }
 
@@ -702,197 +728,49 @@ int32_t dxtlt_host::transform_auto_device(int32_t format, const void* d_in, void
     return kOk;
 }
 
-// BC4 / BC5 (include/dxtlt_bc45.h): two candidates, split_endpoints = false then true.  Both forward transforms go into a device
-// arena of 2 x len (one upload, two launches); the estimator sees each candidate's endpoint section(s) -- BC4 [0, 2N), BC5 red
-// [0, 2N) then green [8N, 10N), added -- and the winner's arena copy is what is downloaded.  Without the arena the candidates run one
-// at a time through d_out, as the BC1-3 fallback does.
-int32_t dxtlt_host::transform_auto_bc45(int32_t format, const uint8_t* in, uint8_t* out, size_t len, const DltSizeEstimator* est,
-                                        AutoChoice* choice)
+namespace {
+
+// the choice of a successful call through the out-parameters of a C entry point, every one of which may be NULL
+int32_t store_choice(int32_t rc, const dxtlt_host::AutoChoice& c, uint8_t* mode, bool* split_alpha, bool* split_colour)
 {
-    t_last_total_count = 0;   // whatever this call does next: no totals of an earlier one
-    if (format != 4 && format != 5)
-        return fail(kInvalidArgument, "format must be 4 (BC4) or 5 (BC5)");
-    const size_t block = format == 4 ? 8 : 16;
-    if (len % block != 0)
-        return fail(kInvalidLength, "len is not a multiple of the block size");
-    if (est == nullptr || est->MaxCompressedSize == nullptr || est->EstimateCompressedSize == nullptr || choice == nullptr)
-        return fail(kInvalidArgument, "NULL estimator / choice");
-    if (len > 0 && (in == nullptr || out == nullptr))
-        return fail(kInvalidArgument, "NULL buffer with len > 0");
-
-    t_section_bytes_downloaded = t_estimator_callbacks = 0;
-    if (is_builtin_estimator(est))
-        return auto_builtin_host(format, in, out, len, false, choice);
-
-    const uint64_t blocks = len / block;
-    const int n_sections = format == 5 ? 2 : 1;
-    const size_t section_len = (size_t)blocks * 2;              // every section: one endpoint pair (or a0 run + a1 run) per block
-    const size_t section_off[2] = {0, (size_t)blocks * 8};      // BC5: red endpoints, green endpoints
-    constexpr bool kCandidates[2] = {false, true};
-    choice->mode = 0;
-    choice->split_colour = false;
-    choice->split_alpha = false;
-    choice->estimator_error = 0;
-
-    size_t max_comp = 0;
-    uint32_t rc_est = call_max(est, section_len, &max_comp);
-    if (rc_est != 0) {
-        choice->estimator_error = rc_est;
-        return fail(kEstimator, "size estimator: max_compressed_size failed");
+    if (rc == DXTLT_OK) {
+        if (mode) *mode = c.mode;
+        if (split_alpha) *split_alpha = c.split_alpha;
+        if (split_colour) *split_colour = c.split_colour;
     }
-    uint8_t* scratch = nullptr;
-    if (max_comp != 0) {
-        scratch = static_cast<uint8_t*>(std::aligned_alloc(64, (max_comp + 63) / 64 * 64));
-        if (scratch == nullptr)
-            return fail(kAllocation, "estimator scratch allocation failed");
-    }
-    void *d_in = nullptr, *d_out = nullptr;
-    hipStream_t st = nullptr;
-    uint8_t* arena = nullptr;
-    if (len > 0) {
-        int32_t rc = acquire_staging(len, &d_in, &d_out, &st);
-        if (rc != kOk) {
-            std::free(scratch);
-            return rc;
-        }
-        AUTO_TRY(hipMemcpyAsync(d_in, in, len, hipMemcpyHostToDevice, st), "H2D copy");
-        if (!t_no_arena)
-            arena = static_cast<uint8_t*>(g_arena.get(2 * len));
-        for (int k = 0; k < 2 && arena != nullptr; ++k) {
-            const int32_t rc2 = enqueue(format, false, d_in, arena + (size_t)k * len, blocks, 0, kCandidates[k], false, st);
-            if (rc2 != kOk) {
-                (void)hipStreamSynchronize(st);
-                std::free(scratch);
-                return rc2;
-            }
-        }
-    }
-    auto fail_estimate = [&](uint32_t bad) {
-        if (st) (void)hipStreamSynchronize(st);
-        std::free(scratch);
-        choice->estimator_error = bad;
-        return fail(kEstimator, "size estimator: estimate_compressed_size failed");
-    };
-
-    int est_threads = g_estimator_threads.load(std::memory_order_relaxed);
-    if (t_estimator_threads_cap > 0 && est_threads > t_estimator_threads_cap)
-        est_threads = t_estimator_threads_cap;
-    int best = 0;
-    size_t best_size = SIZE_MAX;
-    if (est_threads > 1 && arena != nullptr) {
-        // every section of both candidates at once; combined in the sequential order below
-        std::vector<Section> sections;
-        for (int k = 0; k < 2; ++k)
-            for (int h = 0; h < n_sections; ++h)
-                sections.push_back(Section{arena + (size_t)k * len + section_off[h], section_len});
-        hipError_t herr = hipSuccess;
-        if (!estimate_sections_parallel(sections, est, max_comp, est_threads, st, &herr))
-            AUTO_TRY(herr == hipSuccess ? hipErrorUnknown : herr, "parallel estimation (staging / download)");
-        for (int k = 0; k < 2; ++k) {
-            size_t total = 0;
-            for (int h = 0; h < n_sections; ++h) {
-                const Section& sec = sections[(size_t)(k * n_sections + h)];
-                if (sec.rc != 0)
-                    return fail_estimate(sec.rc);
-                total += sec.size;
-            }
-            if (total < best_size) {
-                best_size = total;
-                best = k;
-            }
-        }
-    } else {
-        int last = -1;   // the candidate whose transform is in d_out (no arena)
-        for (int k = 0; k < 2; ++k) {
-            if (len > 0) {
-                const uint8_t* src = arena;
-                if (arena != nullptr) {
-                    src = arena + (size_t)k * len;
-                } else {
-                    const int32_t rc = enqueue(format, false, d_in, d_out, blocks, 0, kCandidates[k], false, st);
-                    if (rc != kOk) {
-                        (void)hipStreamSynchronize(st);
-                        std::free(scratch);
-                        return rc;
-                    }
-                    src = static_cast<const uint8_t*>(d_out);
-                    last = k;
-                }
-                // the section(s) travel into the output buffer at the offsets they are estimated at
-                for (int h = 0; h < n_sections; ++h)
-                    AUTO_TRY(download_section(out + section_off[h], src + section_off[h], section_len, st), "D2H endpoint section");
-                AUTO_TRY(hipStreamSynchronize(st), "stream synchronize");
-            }
-            size_t total = 0;
-            for (int h = 0; h < n_sections; ++h) {
-                size_t part = 0;
-                rc_est = call_estimate(est, out + section_off[h], section_len, scratch, max_comp, &part);
-                if (rc_est != 0)
-                    return fail_estimate(rc_est);
-                total += part;
-            }
-            if (total < best_size) {
-                best_size = total;
-                best = k;
-            }
-        }
-        if (len > 0 && arena == nullptr && last != best) {
-            const int32_t rc = enqueue(format, false, d_in, d_out, blocks, 0, kCandidates[best], false, st);
-            if (rc != kOk) {
-                (void)hipStreamSynchronize(st);
-                std::free(scratch);
-                return rc;
-            }
-        }
-    }
-    if (len > 0) {
-        const void* result = arena != nullptr ? static_cast<const void*>(arena + (size_t)best * len) : d_out;
-        AUTO_TRY(hipMemcpyAsync(out, result, len, hipMemcpyDeviceToHost, st), "D2H result");
-        AUTO_TRY(hipStreamSynchronize(st), "stream synchronize");
-    }
-    std::free(scratch);
-    choice->split_alpha = kCandidates[best];
-    return kOk;
+    return rc;
 }
+
+int32_t auto_host(int32_t format, const uint8_t* in, uint8_t* out, size_t len, const DltSizeEstimator* estimator, bool use_all,
+                  uint8_t* mode, bool* split_alpha, bool* split_colour, uint32_t* estimator_error)
+{
+    dxtlt_host::AutoChoice c{};
+    const int32_t rc = dxtlt_host::transform_auto(format, in, out, len, estimator, use_all, &c);
+    t_last_estimator_error = c.estimator_error;
+    if (estimator_error) *estimator_error = c.estimator_error;
+    return store_choice(rc, c, mode, split_alpha, split_colour);
+}
+
+int32_t auto_device(int32_t format, const void* d_in, void* d_out, size_t len, bool use_all, void* hip_stream, uint8_t* mode,
+                    bool* split_alpha, bool* split_colour)
+{
+    dxtlt_host::AutoChoice c{};
+    const int32_t rc = dxtlt_host::transform_auto_device(format, d_in, d_out, len, use_all, static_cast<hipStream_t>(hip_stream), &c);
+    return store_choice(rc, c, mode, split_alpha, split_colour);
+}
+
+}  // namespace
 
 extern "C" {
 
-int32_t dxtlt_transform_bc4_auto(const uint8_t* input_ptr, uint8_t* output_ptr, size_t len, const DltSizeEstimator* estimator,
-                                 bool* out_split_endpoints)
-{
-    dxtlt_host::AutoChoice c{};
-    const int32_t rc = dxtlt_host::transform_auto_bc45(4, input_ptr, output_ptr, len, estimator, &c);
-    t_last_estimator_error = c.estimator_error;
-    if (rc == DXTLT_OK && out_split_endpoints)
-        *out_split_endpoints = c.split_alpha;
-    return rc;
-}
-
-int32_t dxtlt_transform_bc5_auto(const uint8_t* input_ptr, uint8_t* output_ptr, size_t len, const DltSizeEstimator* estimator,
-                                 bool* out_split_endpoints)
-{
-    dxtlt_host::AutoChoice c{};
-    const int32_t rc = dxtlt_host::transform_auto_bc45(5, input_ptr, output_ptr, len, estimator, &c);
-    t_last_estimator_error = c.estimator_error;
-    if (rc == DXTLT_OK && out_split_endpoints)
-        *out_split_endpoints = c.split_alpha;
-    return rc;
-}
-
+// ---- include/dxtlt_gfx950.h, include/dxtlt_bc45.h: host pointers, the caller's estimator (split_endpoints travels as split_alpha) ----
 int32_t dxtlt_transform_bc1_auto(const uint8_t* input_ptr, uint8_t* output_ptr, size_t len,
                                  const DltSizeEstimator* estimator, bool use_all_decorrelation_modes,
                                  uint8_t* out_decorrelation_mode, bool* out_split_colour_endpoints,
                                  uint32_t* out_estimator_error)
 {
-    dxtlt_host::AutoChoice c{};
-    int32_t rc = dxtlt_host::transform_auto(1, input_ptr, output_ptr, len, estimator, use_all_decorrelation_modes, &c);
-    t_last_estimator_error = c.estimator_error;
-    if (out_estimator_error) *out_estimator_error = c.estimator_error;
-    if (rc == DXTLT_OK) {
-        if (out_decorrelation_mode) *out_decorrelation_mode = c.mode;
-        if (out_split_colour_endpoints) *out_split_colour_endpoints = c.split_colour;
-    }
-    return rc;
+    return auto_host(1, input_ptr, output_ptr, len, estimator, use_all_decorrelation_modes, out_decorrelation_mode, nullptr,
+                     out_split_colour_endpoints, out_estimator_error);
 }
 
 int32_t dxtlt_transform_bc2_auto(const uint8_t* input_ptr, uint8_t* output_ptr, size_t len,
@@ -900,15 +778,8 @@ int32_t dxtlt_transform_bc2_auto(const uint8_t* input_ptr, uint8_t* output_ptr, 
                                  uint8_t* out_decorrelation_mode, bool* out_split_colour_endpoints,
                                  uint32_t* out_estimator_error)
 {
-    dxtlt_host::AutoChoice c{};
-    int32_t rc = dxtlt_host::transform_auto(2, input_ptr, output_ptr, len, estimator, use_all_decorrelation_modes, &c);
-    t_last_estimator_error = c.estimator_error;
-    if (out_estimator_error) *out_estimator_error = c.estimator_error;
-    if (rc == DXTLT_OK) {
-        if (out_decorrelation_mode) *out_decorrelation_mode = c.mode;
-        if (out_split_colour_endpoints) *out_split_colour_endpoints = c.split_colour;
-    }
-    return rc;
+    return auto_host(2, input_ptr, output_ptr, len, estimator, use_all_decorrelation_modes, out_decorrelation_mode, nullptr,
+                     out_split_colour_endpoints, out_estimator_error);
 }
 
 int32_t dxtlt_transform_bc3_auto(const uint8_t* input_ptr, uint8_t* output_ptr, size_t len,
@@ -916,80 +787,55 @@ int32_t dxtlt_transform_bc3_auto(const uint8_t* input_ptr, uint8_t* output_ptr, 
                                  uint8_t* out_decorrelation_mode, bool* out_split_alpha_endpoints,
                                  bool* out_split_colour_endpoints, uint32_t* out_estimator_error)
 {
-    dxtlt_host::AutoChoice c{};
-    int32_t rc = dxtlt_host::transform_auto(3, input_ptr, output_ptr, len, estimator, use_all_decorrelation_modes, &c);
-    t_last_estimator_error = c.estimator_error;
-    if (out_estimator_error) *out_estimator_error = c.estimator_error;
-    if (rc == DXTLT_OK) {
-        if (out_decorrelation_mode) *out_decorrelation_mode = c.mode;
-        if (out_split_alpha_endpoints) *out_split_alpha_endpoints = c.split_alpha;
-        if (out_split_colour_endpoints) *out_split_colour_endpoints = c.split_colour;
-    }
-    return rc;
+    return auto_host(3, input_ptr, output_ptr, len, estimator, use_all_decorrelation_modes, out_decorrelation_mode,
+                     out_split_alpha_endpoints, out_split_colour_endpoints, out_estimator_error);
+}
+
+int32_t dxtlt_transform_bc4_auto(const uint8_t* input_ptr, uint8_t* output_ptr, size_t len, const DltSizeEstimator* estimator,
+                                 bool* out_split_endpoints)
+{
+    return auto_host(4, input_ptr, output_ptr, len, estimator, false, nullptr, out_split_endpoints, nullptr, nullptr);
+}
+
+int32_t dxtlt_transform_bc5_auto(const uint8_t* input_ptr, uint8_t* output_ptr, size_t len, const DltSizeEstimator* estimator,
+                                 bool* out_split_endpoints)
+{
+    return auto_host(5, input_ptr, output_ptr, len, estimator, false, nullptr, out_split_endpoints, nullptr, nullptr);
 }
 
 // ---- include/dxtlt_estimator.h: device pointers, the built-in estimator ------------------------------------------------------
 int32_t dxtlt_transform_bc1_auto_device(const void* d_input, void* d_output, size_t len, bool use_all_decorrelation_modes,
                                         void* hip_stream, uint8_t* out_decorrelation_mode, bool* out_split_colour_endpoints)
 {
-    dxtlt_host::AutoChoice c{};
-    const int32_t rc = dxtlt_host::transform_auto_device(1, d_input, d_output, len, use_all_decorrelation_modes,
-                                                         static_cast<hipStream_t>(hip_stream), &c);
-    if (rc == DXTLT_OK) {
-        if (out_decorrelation_mode) *out_decorrelation_mode = c.mode;
-        if (out_split_colour_endpoints) *out_split_colour_endpoints = c.split_colour;
-    }
-    return rc;
+    return auto_device(1, d_input, d_output, len, use_all_decorrelation_modes, hip_stream, out_decorrelation_mode, nullptr,
+                       out_split_colour_endpoints);
 }
 
 int32_t dxtlt_transform_bc2_auto_device(const void* d_input, void* d_output, size_t len, bool use_all_decorrelation_modes,
                                         void* hip_stream, uint8_t* out_decorrelation_mode, bool* out_split_colour_endpoints)
 {
-    dxtlt_host::AutoChoice c{};
-    const int32_t rc = dxtlt_host::transform_auto_device(2, d_input, d_output, len, use_all_decorrelation_modes,
-                                                         static_cast<hipStream_t>(hip_stream), &c);
-    if (rc == DXTLT_OK) {
-        if (out_decorrelation_mode) *out_decorrelation_mode = c.mode;
-        if (out_split_colour_endpoints) *out_split_colour_endpoints = c.split_colour;
-    }
-    return rc;
+    return auto_device(2, d_input, d_output, len, use_all_decorrelation_modes, hip_stream, out_decorrelation_mode, nullptr,
+                       out_split_colour_endpoints);
 }
 
 int32_t dxtlt_transform_bc3_auto_device(const void* d_input, void* d_output, size_t len, bool use_all_decorrelation_modes,
                                         void* hip_stream, uint8_t* out_decorrelation_mode, bool* out_split_alpha_endpoints,
                                         bool* out_split_colour_endpoints)
 {
-    dxtlt_host::AutoChoice c{};
-    const int32_t rc = dxtlt_host::transform_auto_device(3, d_input, d_output, len, use_all_decorrelation_modes,
-                                                         static_cast<hipStream_t>(hip_stream), &c);
-    if (rc == DXTLT_OK) {
-        if (out_decorrelation_mode) *out_decorrelation_mode = c.mode;
-        if (out_split_alpha_endpoints) *out_split_alpha_endpoints = c.split_alpha;
-        if (out_split_colour_endpoints) *out_split_colour_endpoints = c.split_colour;
-    }
-    return rc;
+    return auto_device(3, d_input, d_output, len, use_all_decorrelation_modes, hip_stream, out_decorrelation_mode,
+                       out_split_alpha_endpoints, out_split_colour_endpoints);
 }
 
 int32_t dxtlt_transform_bc4_auto_device(const void* d_input, void* d_output, size_t len, bool use_all_decorrelation_modes,
                                         void* hip_stream, bool* out_split_endpoints)
 {
-    dxtlt_host::AutoChoice c{};
-    const int32_t rc = dxtlt_host::transform_auto_device(4, d_input, d_output, len, use_all_decorrelation_modes,
-                                                         static_cast<hipStream_t>(hip_stream), &c);
-    if (rc == DXTLT_OK && out_split_endpoints)
-        *out_split_endpoints = c.split_alpha;
-    return rc;
+    return auto_device(4, d_input, d_output, len, use_all_decorrelation_modes, hip_stream, nullptr, out_split_endpoints, nullptr);
 }
 
 int32_t dxtlt_transform_bc5_auto_device(const void* d_input, void* d_output, size_t len, bool use_all_decorrelation_modes,
                                         void* hip_stream, bool* out_split_endpoints)
 {
-    dxtlt_host::AutoChoice c{};
-    const int32_t rc = dxtlt_host::transform_auto_device(5, d_input, d_output, len, use_all_decorrelation_modes,
-                                                         static_cast<hipStream_t>(hip_stream), &c);
-    if (rc == DXTLT_OK && out_split_endpoints)
-        *out_split_endpoints = c.split_alpha;
-    return rc;
+    return auto_device(5, d_input, d_output, len, use_all_decorrelation_modes, hip_stream, nullptr, out_split_endpoints, nullptr);
 }
 
 void dxtlt_debug_auto_last_estimation(uint64_t* out_section_bytes_downloaded, uint64_t* out_estimator_callbacks)
@@ -1016,7 +862,7 @@ int32_t dxtlt_debug_auto_candidates_device(int32_t format, bool use_all_decorrel
     if (format < 1 || format > 3 || d_input == nullptr || len == 0 || len % (format == 1 ? 8 : 16) != 0)
         return fail(kInvalidArgument, "format 1..3, a non-empty whole number of blocks");
     const uint64_t blocks = len / (format == 1 ? 8 : 16);
-    void* arena = g_arena.get((size_t)dxtlt::auto_arena_bytes((dxtlt::Format)format, use_all_decorrelation_modes, blocks));
+    void* arena = g_arena.get((size_t)dxtlt::auto_sections((dxtlt::Format)format, use_all_decorrelation_modes, blocks).bytes);
     if (arena == nullptr)
         return fail(kDevice, "candidate arena allocation failed", hipErrorOutOfMemory);
     HIP_TRY(dxtlt::launch_auto_candidates((dxtlt::Format)format, use_all_decorrelation_modes, d_input, arena, blocks,

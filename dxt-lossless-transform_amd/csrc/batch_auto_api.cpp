@@ -8,7 +8,7 @@
 //   upload    ONE table for the whole call: per chunk the candidate launches' entry tables and the estimator's section table
 //   per chunk one candidate launch per (format, use_all) present (batch_auto_kernels.hip) and one table-driven estimator launch
 //             (estimate_kernels.hip); the stream orders the reuse of the arena between chunks
-//   readback  all counters of the batch in one copy, ONE wait; the pick per item on the host (candidates_of's order, strict `<`)
+//   readback  all counters of the batch in one copy, ONE wait; the pick per item on the host (auto_pick: candidates_of's order, strict `<`)
 //   winners   dxtlt_transform_batch_device with the chosen per-item settings: enqueued, not waited for
 #include <algorithm>
 #include <cstring>
@@ -121,8 +121,11 @@ void make_plan(const DxtltBatchAutoItem* items, size_t count, Plan& plan)
         const dxtlt::Format fmt = (dxtlt::Format)it.format;
         const bool all = use_all_of(it);
         p.blocks = it.len / block_bytes_of(it.format);
-        p.slice_bytes = dxtlt::batch_auto_slice_bytes(fmt, all, p.blocks);
-        p.sections = dxtlt::batch_auto_sections(fmt, all, p.blocks, p.sec_off, p.sec_len);
+        const dxtlt::AutoSections secs = dxtlt::auto_sections(fmt, all, p.blocks);
+        p.slice_bytes = secs.bytes;
+        p.sections = secs.count;
+        std::copy(secs.off, secs.off + secs.count, p.sec_off);
+        std::copy(secs.len, secs.len + secs.count, p.sec_len);
         const uint64_t padded = (p.slice_bytes + 15) & ~uint64_t(15);
         // a chunk is closed BEFORE the item that would push it past the cap: it holds at most the cap, or one larger item
         if (cur.count > 0 && cur.arena_bytes + padded > cap) {
@@ -146,26 +149,6 @@ void make_plan(const DxtltBatchAutoItem* items, size_t count, Plan& plan)
     plan.chunks.push_back(cur);
     for (const PlannedChunk& c : plan.chunks)
         plan.arena_bytes = std::max(plan.arena_bytes, c.arena_bytes);
-}
-
-// the totals of an item of `format` in candidate order from its counters (batch_auto_sections' order); returns the pick
-int pick_of(int32_t format, const uint64_t* sizes, const AutoChoice* order, int n, uint64_t* total)
-{
-    for (int i = 0; i < n; ++i) {
-        const AutoChoice& c = order[i];
-        const int sa = c.split_alpha ? 1 : 0, colour = c.mode * 2 + (c.split_colour ? 1 : 0);
-        switch (format) {
-        case 3: total[i] = sizes[sa] + sizes[2 + colour]; break;
-        case 4: total[i] = sizes[sa]; break;
-        case 5: total[i] = sizes[sa] + sizes[2 + sa]; break;
-        default: total[i] = sizes[colour]; break;
-        }
-    }
-    int pick = 0;
-    for (int i = 1; i < n; ++i)
-        if (total[i] < total[pick])   // strict: the first best wins
-            pick = i;
-    return pick;
 }
 
 // this thread's table staging (mapped pinned host memory and its device twin) and counters (device and pinned host): grow-only.
@@ -408,7 +391,7 @@ extern "C" int32_t dxtlt_transform_batch_auto_device(DxtltBatchAutoItem* items, 
         const PlannedItem& p = plan.items[i];
         int pick = 0;
         if (p.blocks != 0)
-            pick = pick_of(items[i].format, g_buffers.counters_host + p.first_counter, &orders[i * 16], order_counts[i], &totals[i * 16]);
+            pick = auto_pick(items[i].format, use_all_of(items[i]), false, g_buffers.counters_host + p.first_counter, &totals[i * 16]);
         report(i, pick);
         DxtltBatchItem& w = winners[i];
         std::memset(&w, 0, sizeof w);
@@ -476,18 +459,11 @@ extern "C" int32_t dxtlt_debug_auto_pick(int32_t route, int32_t format, bool use
     AutoChoice order[16];
     const int n = auto_candidate_order(format, use_all, order);
     const bool per_candidate = route == 2 || (route == 0 && format >= 4);
-    int want = 2 * n;   // two slots per candidate
-    if (!per_candidate)
-        switch (format) {   // the distinct sections
-        case 3: want = (use_all ? 8 : 4) + 2; break;
-        case 4: want = 2; break;
-        case 5: want = 4; break;
-        default: want = use_all ? 8 : 4; break;
-        }
+    const int want = per_candidate ? 2 * n : dxtlt::auto_sections((dxtlt::Format)format, use_all, 0).count;
     if (n_sizes != want)
         return fail(kInvalidArgument, "auto pick: another number of section sizes than the route reads back");
     uint64_t total[16];
-    const int pick = route == 1 ? pick_of(format, section_sizes, order, n, total) : auto_pick_single(format, use_all, per_candidate, section_sizes, total);
+    const int pick = auto_pick(format, use_all, per_candidate, section_sizes, total);
     for (int i = 0; totals_out != nullptr && i < n && i < cap; ++i)
         totals_out[i] = total[i];
     if (mode) *mode = order[pick].mode;

@@ -289,7 +289,7 @@ int32_t dds_transform_common(const uint8_t* input, size_t input_len, uint8_t* ou
         int32_t st45;
         if (estimator != nullptr) {
             dxtlt_host::AutoChoice c{};
-            st45 = dxtlt_host::transform_auto_bc45(f45, input + off, output + off, length, estimator, &c);
+            st45 = dxtlt_host::transform_auto(f45, input + off, output + off, length, estimator, false, &c);
             sa = c.split_alpha;
         } else {
             st45 = dxtlt_host::transform(f45, false, input + off, output + off, length, 0, sa, false);

@@ -149,25 +149,23 @@ struct AutoChoice {
     uint32_t estimator_error;  // the callback's non-zero return when the status is kEstimator
 };
 
-// transform_bcN_auto on host pointers (see auto_transform.cpp).
+// transform_bcN_auto on host pointers, format 1..5 (see auto_transform.cpp).  BC4 / BC5: use_all_decorrelation_modes is ignored and
+// choice->split_alpha = split_endpoints.
 int32_t transform_auto(int32_t format, const uint8_t* in, uint8_t* out, size_t len, const DltSizeEstimator* estimator,
                        bool use_all_decorrelation_modes, AutoChoice* choice);
-// dxtlt_transform_bc{4,5}_auto on host pointers, format 4 or 5 (auto_transform.cpp): choice->split_alpha = split_endpoints
-int32_t transform_auto_bc45(int32_t format, const uint8_t* in, uint8_t* out, size_t len, const DltSizeEstimator* estimator,
-                            AutoChoice* choice);
 
 // dxtlt_transform_bcN_auto_device (include/dxtlt_estimator.h), format 1..5: device pointers, the built-in estimator, one small
 // readback; the winning transform is left enqueued on `stream`.
 int32_t transform_auto_device(int32_t format, const void* d_in, void* d_out, size_t len, bool use_all_decorrelation_modes,
                               hipStream_t stream, AutoChoice* choice);
 
-// ---- auto_transform.cpp, for the batched call (batch_auto_api.cpp) ----
+// ---- auto_transform.cpp, shared with the batched call (batch_auto_api.cpp) ----
 // The candidates of `format` (1..5) in the order they are compared, into out[0 .. 16); returns how many (candidates_of).
 int auto_candidate_order(int32_t format, bool use_all_decorrelation_modes, AutoChoice* out);
-// What the single-buffer device route does with its counters after the readback: the candidates' totals in candidate order into
-// total[0 .. 16) and the pick, the first minimum of the order (strict `<`).  sizes: the distinct sections where the candidate kernel
-// left them -- colour (variant, split) pairs, then BC3's two alpha-endpoint sections -- or, per_candidate, two slots per candidate.
-int auto_pick_single(int32_t format, bool use_all_decorrelation_modes, bool per_candidate, const uint64_t* sizes, uint64_t* total);
+// What every device route does with its counters after the readback: the candidates' totals in candidate order into total[0 .. 16)
+// and the pick, the first minimum of the order (strict `<`).  sizes: the distinct sections in dxtlt::auto_sections' order (auto_launch.h)
+// or, per_candidate, two slots per candidate (BC4 / BC5 on the single-buffer route, every format without the arena).
+int auto_pick(int32_t format, bool use_all_decorrelation_modes, bool per_candidate, const uint64_t* sizes, uint64_t* total);
 // This thread's candidate arena on the current device, grown to at least `bytes`; nullptr when it cannot be allocated.
 void* auto_thread_arena(size_t bytes);
 // An auto call that downloads no section and makes no callback begins: dxtlt_debug_auto_last_estimation reports (0, 0) and

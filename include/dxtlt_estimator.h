@@ -195,10 +195,10 @@ void dxtlt_debug_auto_use_arena(int32_t on);
 uint32_t dxtlt_debug_auto_last_estimator_error(void);
 
 /* Test hook, no device needed: the host-side pick of the device routes, on section sizes given by the caller instead of read back.
- * It runs the function the route runs after its readback.  route 0: dxtlt_transform_bcN_auto_device -- BC1-3 the distinct sections
- * in the candidate arena's order (per variant colour pairs, colour split; then BC3's alpha pairs, alpha split), BC4 / BC5 two
- * slots per candidate (BC4 reads the first of each).  route 1: dxtlt_transform_batch_auto_device, the counters of one item in
- * slice order (BC3 alpha pairs, alpha split, then the colour sections; BC4 pairs, split; BC5 red pairs, red split, green pairs,
+ * It runs the function the routes run after their readback.  route 0: dxtlt_transform_bcN_auto_device -- BC1-3 the distinct
+ * sections as route 1 takes them, BC4 / BC5 two slots per candidate (BC4 reads the first of each).  route 1:
+ * dxtlt_transform_batch_auto_device, the counters of one item -- the distinct sections in the order they lie in memory (BC3 alpha
+ * pairs, alpha split, then per variant colour pairs, colour split; BC4 pairs, split; BC5 red pairs, red split, green pairs,
  * green split).  route 2: route 0 without its arena, two slots per candidate for every format (BC1, BC2 and BC4 read the first of
  * each).  n_sizes must be what the route reads back (DXTLT_E_INVALID_ARGUMENT otherwise).  Writes at most cap candidate totals,
  * in candidate order, and the settings of the pick (split_alpha = split_endpoints for BC4 / BC5); any output pointer may be NULL. */

@@ -53,7 +53,7 @@ def make_items(specs):
 
 def shown_lengths(fmt, n, use_all):
     """lengths of the DISTINCT sections the candidates of (fmt, use_all) show the estimator for n bytes, in slice order: what
-    shown() of auto_on_device and the arena of the single-buffer path hold"""
+    auto_sections (csrc/auto_launch.h) lists: the arena of the single-buffer path and a batch item's slice"""
     blocks = n // BLOCK[fmt]
     variants = 4 if use_all else 2
     if fmt == "bc1":

@@ -52,7 +52,7 @@ def endpoint_sections(fmt: str, n: int) -> list[tuple[int, int]]:
 
 def auto_choice(fmt: str, aos: np.ndarray, estimate) -> bool:
     """split_endpoints the auto transform picks with `estimate(bytes) -> size`: candidates False, True, strict `<` against a best
-    that starts at "no split" with 2**64 - 1 (transform_auto_bc45), so a candidate that answers the maximum never wins"""
+    that starts at "no split" with 2**64 - 1 (transform_auto), so a candidate that answers the maximum never wins"""
     n = aos.size // BLOCK[fmt]
     best, best_size = False, 2**64 - 1
     for cand in (False, True):

@@ -212,7 +212,7 @@ def size_vector(route, fmt, use_all, sizes):
         return [sizes[("e", 0)], sizes[("e", 1)]]
     if fmt == "bc5":
         return [sizes[("r", 0)], sizes[("r", 1)], sizes[("g", 0)], sizes[("g", 1)]]
-    return colours + alphas if route == 0 else alphas + colours              # the arena's order; the batch slice's order
+    return alphas + colours                                                  # the arena's and the batch slice's order: memory order
 
 
 def check_pick(picker, fmt, use_all, sizes, what):

@@ -376,3 +376,75 @@ def test_two_calls_of_one_thread_on_two_streams_and_the_python_wrapper(lib, dev,
                int(getattr(c, "split_colour_endpoints", 0)))
         assert type(c).__name__ == f"Bc{s[0][2]}TransformSettings" and got == choice, (k, s)
         assert np.array_equal(o.cpu().numpy(), out), (k, s)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# The lane edges of the candidate kernels' one lane body (csrc/auto_candidate_lanes.h): the half lane of an odd BC1 / BC4 count
+# alone (1), as lane 255 of workgroup 0 (511) and as lane 0 of workgroup 1 (513), none (512); the last lane of a workgroup and the
+# first of the next for the formats of one block per lane.  Every case at 0, 4 and 1 bytes off a 16-byte boundary: the batched
+# kernel's vector, dword and byte loads; the single-buffer call takes its candidate kernels at 0 and one transform per candidate else.
+# ---------------------------------------------------------------------------------------------------------------
+EDGE_COUNTS = {"bc1": (1, 2, 3, 511, 512, 513), "bc4": (1, 2, 3, 511, 512, 513),
+               "bc2": (1, 255, 256, 257), "bc3": (1, 255, 256, 257), "bc5": (1, 255, 256, 257)}
+EDGE_OFFSETS = (0, 4, 1)
+
+
+def edge_cases():
+    """(spec, input offset) per (kind, count, offset); the styles and seeds were chosen on the CPU so that edge_batch's condition holds"""
+    return [((fmt, blocks, (i + j + k) % 4, 40 + k, use_all), off) for i, (fmt, use_all) in enumerate(KINDS)
+            for j, blocks in enumerate(EDGE_COUNTS[fmt]) for k, off in enumerate(EDGE_OFFSETS)]
+
+
+@pytest.fixture(scope="module")
+def edge_batch(dev, oracle):
+    cases = edge_cases()
+    assert len(cases) == sum(len(EDGE_COUNTS[f]) for f, _ in KINDS) * len(EDGE_OFFSETS)       # no case is left out
+    # stated on the CPU before the first device call: within every format and search depth the CPU statement makes at least two
+    # different choices -- a single block ties by construction and counts towards neither
+    seen = {}
+    for s, _ in cases:
+        if s[1] > 1:
+            seen.setdefault((s[0], s[4]), set()).add(cpu_auto(s, oracle)[1])
+    assert len(seen) == len(KINDS) and all(len(v) >= 2 for v in seen.values()), seen
+    return Batch(dev, [s for s, _ in cases], oracle, [off for _, off in cases])
+
+
+@pytest.fixture(scope="module")
+def edge_runs(lib, dev, edge_batch, pkg):
+    """ONE batched call over every case, then the single-buffer calls: the same inputs where they lie, into a pool of their own laid
+    out like the batch's.  -> per case (batched, single), each (choice, bytes, totals); the bytes around every output are checked"""
+    import torch
+
+    from dxt_lossless_transform_amd import estimator
+
+    b = edge_batch
+    assert all(it.d_input % 16 == off for it, off in zip(b.items, b.in_off))
+    b.reset()
+    assert b.call(lib) == 0, lib.dxtlt_last_error()
+    torch.cuda.synchronize()
+    batched = b.results(lib)
+    assert last(lib)[0] == 1
+    pool = torch.full((b.total,), FILL, dtype=torch.uint8, device=dev)
+    outside = np.ones(b.total, dtype=bool)
+    chosen = []
+    for spec, (x, *_), at, a in zip(b.specs, b.cpu, b.at, b.in_off):
+        s = estimator.transform_auto(spec[0], b.d_in[at + a:at + a + x.size], pool[at:at + x.size], spec[4])
+        chosen.append(((int(getattr(s, "decorrelation_mode", 0)), int(getattr(s, "split_alpha_endpoints", getattr(s, "split_endpoints", 0))),
+                        int(getattr(s, "split_colour_endpoints", 0))), estimator.last_auto_totals()))
+        outside[at:at + x.size] = False
+    torch.cuda.synchronize()
+    whole = pool.cpu().numpy()
+    assert (whole[outside] == FILL).all(), "a single-buffer call wrote outside its output"
+    return [(g, (c, whole[at:at + x.size], t)) for g, (c, t), (x, *_), at in zip(batched, chosen, b.cpu, b.at)]
+
+
+@pytest.mark.parametrize("fmt,use_all", KINDS)
+def test_lane_edges_batched_single_and_cpu_agree(edge_batch, edge_runs, fmt, use_all):
+    mine = [k for k, s in enumerate(edge_batch.specs) if (s[0], s[4]) == (fmt, use_all)]
+    assert len(mine) == len(EDGE_COUNTS[fmt]) * len(EDGE_OFFSETS)
+    for k in mine:
+        spec, (_x, choice, out, totals) = edge_batch.specs[k], edge_batch.cpu[k]
+        for route, (g_choice, g_out, g_totals) in zip(("batched", "single"), edge_runs[k]):
+            assert g_choice == choice, (route, spec, edge_batch.in_off[k], g_choice, choice)
+            assert g_totals == totals, (route, spec, edge_batch.in_off[k])
+            assert np.array_equal(g_out, out), (route, spec, edge_batch.in_off[k])
