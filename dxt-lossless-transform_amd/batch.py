@@ -1,7 +1,9 @@
 """Many device-resident buffers in one call (dxtlt_transform_batch_device, include/dxtlt_gfx950.h): one kernel launch per
 (format, direction) present in the batch, enqueued on torch's current stream.  fmt "bc7" (this build's own format,
 docs/BC7_FORMAT.md; settings ignored, pass None) rides along: its granules in one launch, its tail parts in another; fmt
-"bc6h" (docs/BC6H_FORMAT.md; settings ignored) the same, in launches of its own."""
+"bc6h" (docs/BC6H_FORMAT.md; settings ignored) the same, in launches of its own.  fmt "pixels4" / "pixels3" (uncompressed
+pixels of 4 / 3 bytes, docs/PIXEL_FORMAT.md; settings = (decorrelate, layout) or None) are taken by transform_batch_host only,
+one launch per item; the device batch call refuses them."""
 from __future__ import annotations
 
 import ctypes as C
@@ -18,6 +20,13 @@ def _item_fields(fmt, settings):
         return 7, 16, 0, False, False
     if fmt == "bc6h":
         return 6, 16, 0, False, False
+    if fmt in ("pixels4", "pixels3"):
+        # uncompressed pixels (pixels.py, docs/PIXEL_FORMAT.md): settings = (decorrelate, layout), None = the default
+        from . import pixels
+
+        decorrelate, layout = (True, pixels.PLANAR_DELTA) if settings is None else settings
+        mode, sa, sc = pixels.settings_triple(decorrelate, layout)
+        return (8, 4, mode, sa, sc) if fmt == "pixels4" else (9, 3, mode, sa, sc)
     mode, sa, sc = _settings_tuple(fmt, settings)
     return _FMT_ID[fmt], BLOCK_BYTES[fmt], mode, sa, sc
 

@@ -9,7 +9,8 @@
 // the caller's stream (a small kernel reads the mapped pinned slot: no copy-engine hand-over in front of the batch kernel) and
 // launches batch_kernel (batch_kernels.hip), in which every workgroup looks its buffer up and runs one tile -- aligned, halo
 // or shifted, as the single-buffer call would choose for that buffer -- or the buffer's edge tile.  Asynchronous and ordered
-// like a single call on the caller's stream.
+// like a single call on the caller's stream.  Uncompressed-pixel items (formats 8, 9: include/dxtlt_pixels.h) are taken by the
+// host batch only: checked with the rest there, they go out as one launch each, behind the batches of their chunk.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -31,8 +32,35 @@ namespace {
 using namespace dxtlt_host;
 using dxtlt::BatchEntry;
 
-// bytes per block of a batch item's format (1..7)
-inline uint32_t item_block_bytes(uint8_t format) { return format == 1 || format == 4 ? 8u : 16u; }
+// bytes per block (8, 9: per pixel) of a batch item's format (1..9)
+inline uint32_t item_block_bytes(uint8_t format)
+{
+    return is_pixel_format(format) ? (uint32_t)pixel_bytes_of(format) : format == 1 || format == 4 ? 8u : 16u;
+}
+
+// dxtlt_transform_batch_device takes 1..7, as before; dxtlt_transform_batch_host also 8 and 9
+const char* const kDeviceFormatText = "batch item: format must be 1..5 (BC1..BC5), 6 (BC6H) or 7 (BC7; 6 and 7 are this build's own formats; "
+                                      "pixel formats 8 and 9 go through dxtlt_transform_batch_host or the calls of dxtlt_pixels.h)";
+const char* const kHostFormatText = "batch item: format must be 1..5 (BC1..BC5), 6 (BC6H), 7 (BC7), 8 (4-byte pixels) or 9 (3-byte pixels; "
+                                    "6 to 9 are this build's own formats)";
+
+// Pixel items (8, 9; include/dxtlt_pixels.h) are checked with the rest and go out as one launch each: their input and output
+// must not overlap
+inline bool pixel_item_overlaps(const DxtltBatchItem& it)
+{
+    if (!is_pixel_format(it.format) || it.len == 0)
+        return false;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(it.d_input), b = reinterpret_cast<uintptr_t>(it.d_output);
+    return a < b + it.len && b < a + it.len;
+}
+
+int32_t launch_pixel_item(const DxtltBatchItem& it, void* stream)
+{
+    const uint64_t pixels = it.len / item_block_bytes(it.format);
+    return pixel_device_range(pixel_bytes_of(it.format), it.inverse != 0, it.d_input, it.d_output, pixels, 0, pixels,
+                              pixel_decorrelate_of(it.decorrelation_mode),
+                              pixel_layout_of(it.split_alpha_endpoints != 0, it.split_colour_endpoints != 0), stream);
+}
 
 // Table staging: a ring of pinned host buffers with device twins.  A slot is reused only after the copy and the kernels that last
 // read it have finished (its event).  A call takes exactly ONE slot -- the tables of its two BC7 launches and of all its BC1-3
@@ -128,9 +156,9 @@ hipError_t upload_table(TableSlot* slot, size_t bytes, hipStream_t stream)
     return dxtlt::launch_table_upload(slot->host_mapped, slot->dev, bytes, stream);
 }
 
-}  // namespace
-
-extern "C" int32_t dxtlt_transform_batch_device(const DxtltBatchItem* items, size_t count, void* hip_stream)
+// The device batch; `pixels_allowed`: items of formats 8 and 9 are taken too (the host batch's chunks: their buffers are this
+// library's own staging, checked by the host call) -- the public device call keeps refusing them.
+int32_t batch_device(const DxtltBatchItem* items, size_t count, void* hip_stream, bool pixels_allowed)
 {
     if (count == 0)
         return kOk;
@@ -139,15 +167,16 @@ extern "C" int32_t dxtlt_transform_batch_device(const DxtltBatchItem* items, siz
     // validate everything first: a batch is enqueued whole or not at all
     for (size_t i = 0; i < count; ++i) {
         const DxtltBatchItem& it = items[i];
-        if (it.format < 1 || it.format > 7)
-            return fail(kInvalidArgument, "batch item: format must be 1..5 (BC1..BC5), 6 (BC6H) or 7 (BC7; 6 and 7 are this build's "
-                                          "own formats)");
+        if (it.format < 1 || it.format > (pixels_allowed ? 9 : 7))
+            return fail(kInvalidArgument, kDeviceFormatText);
         if (it.len % item_block_bytes(it.format) != 0)
             return fail(kInvalidLength, "batch item: len is not a multiple of the block size");
         if (it.decorrelation_mode > 3 && dxtlt::format_has_colour(it.format))
             return fail(kInvalidArgument, "batch item: decorrelation_mode must be 0..3");
         if (it.len > 0 && (it.d_input == nullptr || it.d_output == nullptr))
             return fail(kInvalidArgument, "batch item: NULL device buffer with len > 0");
+        if (pixel_item_overlaps(it))
+            return fail(kInvalidArgument, "batch item: pixel input and output overlap");
     }
     // one launch holds fewer than 2^32 threads = 2^24 workgroups of 256 lanes: for BC7 (or BC6H) that is 256 GiB of granules
     // per direction.  Checked here, before anything is enqueued (a batch goes out whole or not at all).
@@ -182,7 +211,7 @@ extern "C" int32_t dxtlt_transform_batch_device(const DxtltBatchItem* items, siz
     std::vector<size_t> singles;   // items the batch kernel does not take (plan_batch_entry): launched alone, behind the batches
     for (size_t i = 0; i < count; ++i) {
         const DxtltBatchItem& it = items[i];
-        if (it.len == 0 || dxtlt::granule::is_granule_format(it.format))
+        if (it.len == 0 || dxtlt::granule::is_granule_format(it.format) || is_pixel_format(it.format))
             continue;
         if (it.len >= (size_t(64) << 30))
             return fail(kInvalidArgument, "batch item of 64 GiB or more: use the single-buffer entry point");
@@ -358,7 +387,19 @@ extern "C" int32_t dxtlt_transform_batch_device(const DxtltBatchItem* items, siz
         if (e != hipSuccess)
             return fail(kDevice, "batch item launch", e);
     }
+    // pixel items (formats 8, 9): one launch each, behind the rest
+    for (size_t i = 0; i < count; ++i)
+        if (is_pixel_format(items[i].format) && items[i].len != 0)
+            if (int32_t rc = launch_pixel_item(items[i], user); rc != kOk)
+                return rc;
     return kOk;
+}
+
+}  // namespace
+
+extern "C" int32_t dxtlt_transform_batch_device(const DxtltBatchItem* items, size_t count, void* hip_stream)
+{
+    return batch_device(items, count, hip_stream, false);
 }
 
 // Test hook (no device needed, nothing is dereferenced): plans buffers of one format, direction and settings exactly as
@@ -509,15 +550,16 @@ extern "C" int32_t dxtlt_transform_batch_host(const DxtltBatchItem* items, size_
     uint64_t total = 0;
     for (size_t i = 0; i < count; ++i) {
         const DxtltBatchItem& it = items[i];
-        if (it.format < 1 || it.format > 7)
-            return fail(kInvalidArgument, "batch item: format must be 1..5 (BC1..BC5), 6 (BC6H) or 7 (BC7; 6 and 7 are this build's "
-                                          "own formats)");
+        if (it.format < 1 || it.format > 9)
+            return fail(kInvalidArgument, kHostFormatText);
         if (it.len % item_block_bytes(it.format) != 0)
             return fail(kInvalidLength, "batch item: len is not a multiple of the block size");
         if (it.decorrelation_mode > 3 && dxtlt::format_has_colour(it.format))
             return fail(kInvalidArgument, "batch item: decorrelation_mode must be 0..3");
         if (it.len > 0 && (it.d_input == nullptr || it.d_output == nullptr))
             return fail(kInvalidArgument, "batch item: NULL buffer with len > 0");
+        if (pixel_item_overlaps(it))
+            return fail(kInvalidArgument, "batch item: pixel input and output overlap");
         if (it.len >= (size_t(4) << 30))
             return fail(kInvalidArgument, "batch item of 4 GiB or more: use the single-buffer entry point");
         total += (it.len + 255) & ~uint64_t(255);
@@ -539,7 +581,11 @@ extern "C" int32_t dxtlt_transform_batch_host(const DxtltBatchItem* items, size_
             continue;
         }
         int32_t rc;
-        if (dxtlt::granule::is_granule_format(it.format))
+        if (is_pixel_format(it.format))
+            rc = pixel_host_call(pixel_bytes_of(it.format), it.inverse != 0, static_cast<const uint8_t*>(it.d_input),
+                                 static_cast<uint8_t*>(it.d_output), it.len, pixel_decorrelate_of(it.decorrelation_mode),
+                                 pixel_layout_of(it.split_alpha_endpoints != 0, it.split_colour_endpoints != 0));
+        else if (dxtlt::granule::is_granule_format(it.format))
             rc = dxtlt_host::granule_host_call(it.format, it.inverse != 0, static_cast<const uint8_t*>(it.d_input),
                                                static_cast<uint8_t*>(it.d_output), it.len);
         else
@@ -776,7 +822,7 @@ extern "C" int32_t dxtlt_transform_batch_host(const DxtltBatchItem* items, size_
             it.d_output = dout + slot[i];
             dev_items.push_back(it);
         }
-        rc = dxtlt_transform_batch_device(dev_items.data(), dev_items.size(), up);
+        rc = batch_device(dev_items.data(), dev_items.size(), up, true);
         if (rc != kOk)
             break;
         err = hipEventRecord(ev_kernels(c), up);

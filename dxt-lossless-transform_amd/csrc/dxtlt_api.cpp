@@ -260,6 +260,10 @@ int32_t dxtlt_untransform_bc5_with_settings_device(const void* i, void* o, size_
 int32_t dxtlt_transform_sharded(int32_t format, bool inverse, const uint8_t* in, uint8_t* out, size_t len,
                                 uint8_t mode, bool sa, bool sc, int32_t num_devices)
 {
+    // 8 / 9: uncompressed pixels of 4 / 3 bytes (include/dxtlt_pixels.h), the settings triple read as pixel settings
+    if (dxtlt_host::is_pixel_format(format))
+        return dxtlt_host::pixel_sharded(dxtlt_host::pixel_bytes_of(format), inverse, in, out, len, dxtlt_host::pixel_decorrelate_of(mode),
+                                         dxtlt_host::pixel_layout_of(sa, sc), num_devices, &g_shard_stats);
     int32_t rc = check_common(format, len, mode, in, out);
     if (rc != DXTLT_OK)
         return rc;

@@ -12,6 +12,7 @@
 #include "host_common.h"
 #include "../../include/dxtlt_bc6h.h"
 #include "../../include/dxtlt_bc7.h"
+#include "../../include/dxtlt_pixels.h"
 
 namespace {
 
@@ -255,6 +256,41 @@ int bc45_of_header(uint32_t header, bool* split)
     return -1;
 }
 
+// RGBA8888 / BGRA8888 / BGR888 payloads: refused as upstream (no transform exists there) unless the caller opts in to this
+// build's layout (include/dxtlt_pixels.h, docs/PIXEL_FORMAT.md).  Upstream has reserved TransformFormat codes 5, 6, 7 with
+// placeholder data bits (version:2 | decorrelation:1 | reserved:25); the word written here keeps the flag where upstream has it
+// and sets reserved bits -- the layout in bits 4..3, this build's layout version in bits 11..5, the vendor tag of the BC7 words
+// above them -- that upstream's unpack refuses: such a file is rejected there, never misread.
+std::atomic<bool> g_pixels_enabled{false};
+constexpr uint32_t kPixelLayoutVersion = 1u;   // data bits 11..5: docs/PIXEL_FORMAT.md version
+inline uint32_t pixel_header(uint32_t code, bool decorrelate, uint32_t layout)
+{
+    return code | (((kBc7VendorTag << 12) | (kPixelLayoutVersion << 5) | (layout << 3) | ((decorrelate ? 1u : 0u) << 2)) << 4);
+}
+// the TransformFormat code (5, 6, 7) of an uncompressed DDS payload with the switch on, else -1
+int dds_to_pixel_code(uint8_t fmt)
+{
+    if (!g_pixels_enabled.load(std::memory_order_relaxed))
+        return -1;
+    return fmt == RGBA8888 ? DXTLT_TF_RGBA8888 : fmt == BGRA8888 ? DXTLT_TF_BGRA8888 : fmt == BGR888 ? DXTLT_TF_BGR888 : -1;
+}
+inline int pixel_code_bytes(int code) { return code == DXTLT_TF_BGR888 ? 3 : 4; }
+// a header this build wrote for a pixel payload (switch on): bytes per pixel and the settings.  0: not such a format code (or
+// the switch is off); -1: a pixel code whose data bits are not one of the six tagged words
+int pixels_of_header(uint32_t header, bool* decorrelate, uint8_t* layout)
+{
+    const uint32_t code = header & 0xFu;
+    if (!g_pixels_enabled.load(std::memory_order_relaxed) || code < DXTLT_TF_RGBA8888 || code > DXTLT_TF_BGR888)
+        return 0;
+    for (uint32_t k = 0; k < 6; ++k)
+        if (header == pixel_header(code, (k & 1) != 0, k >> 1)) {
+            *decorrelate = (k & 1) != 0;
+            *layout = (uint8_t)(k >> 1);
+            return pixel_code_bytes((int)code);
+        }
+    return -1;
+}
+
 int32_t dds_transform_common(const uint8_t* input, size_t input_len, uint8_t* output, size_t output_len,
                              const DltSizeEstimator* estimator, bool use_all, uint8_t mode, bool sa, bool sc)
 {
@@ -299,6 +335,23 @@ int32_t dds_transform_common(const uint8_t* input, size_t input_len, uint8_t* ou
         if (input_len > off + length)
             std::memcpy(output + off + length, input + off + length, input_len - off - length);
         wr32(output, bc45_header(f45 == 4 ? DXTLT_TF_BC4 : DXTLT_TF_BC5, sa));
+        return DXTLT_FF_OK;
+    }
+    if (const int code = dds_to_pixel_code(info.Format); code >= 0) {
+        // the settings triple read as the generic entry points read it; auto: the fixed setting (subtract-green, PLANAR_DELTA) --
+        // the estimator is never called (docs/PIXEL_FORMAT.md, "Out of scope")
+        const bool decorrelate = estimator != nullptr || dxtlt_host::pixel_decorrelate_of(mode);
+        const uint8_t layout = estimator != nullptr ? (uint8_t)DXTLT_PIXEL_LAYOUT_PLANAR_DELTA : dxtlt_host::pixel_layout_of(sa, sc);
+        const int B = pixel_code_bytes(code);
+        if (length % (size_t)B != 0)
+            return DXTLT_FF_INVALID_DATA_ALIGNMENT;
+        std::memcpy(output, input, off);
+        const int32_t stp = dxtlt_host::pixel_host_call(B, false, input + off, output + off, length, decorrelate, layout);
+        if (stp != dxtlt_host::kOk)
+            return map_device_status(stp);
+        if (input_len > off + length)
+            std::memcpy(output + off + length, input + off + length, input_len - off - length);
+        wr32(output, pixel_header((uint32_t)code, decorrelate, layout));
         return DXTLT_FF_OK;
     }
     const int bcn = dds_to_bcn(info.Format);
@@ -433,6 +486,15 @@ uint32_t dxtlt_transform_header_pack_bc45(int32_t transform_format, bool split_e
     return bc45_header(transform_format, split_endpoints);
 }
 
+void dxtlt_file_formats_enable_pixels(bool enabled) { g_pixels_enabled.store(enabled, std::memory_order_relaxed); }
+
+uint32_t dxtlt_transform_header_pack_pixels(int32_t transform_format, bool decorrelate, uint8_t layout)
+{
+    if (transform_format < DXTLT_TF_RGBA8888 || transform_format > DXTLT_TF_BGR888 || layout > 2)
+        return 0;
+    return pixel_header((uint32_t)transform_format, decorrelate, layout);
+}
+
 bool is_dds(const uint8_t* ptr, size_t len)
 {
     if (ptr == nullptr || len == 0)
@@ -519,6 +581,22 @@ int32_t dxtlt_dds_untransform(const uint8_t* input, size_t input_len, uint8_t* o
             std::memcpy(output + off + length, input + off + length, input_len - off - length);
         return DXTLT_FF_OK;
     }
+    bool pixel_decorrelate = false;
+    uint8_t pixel_layout = 0;
+    if (const int B = pixels_of_header(header, &pixel_decorrelate, &pixel_layout); B != 0) {
+        if (B < 0)
+            return DXTLT_FF_CORRUPTED_EMBEDDED_DATA;   // not one of this build's six words
+        if (length % (size_t)B != 0)
+            return DXTLT_FF_INVALID_DATA_ALIGNMENT;
+        wr32(output, kDdsMagic);
+        std::memcpy(output + 4, input + 4, off - 4);
+        const int32_t stp = dxtlt_host::pixel_host_call(B, true, input + off, output + off, length, pixel_decorrelate, pixel_layout);
+        if (stp != dxtlt_host::kOk)
+            return map_device_status(stp);
+        if (input_len > off + length)
+            std::memcpy(output + off + length, input + off + length, input_len - off - length);
+        return DXTLT_FF_OK;
+    }
     if ((header & 0xF) > DXTLT_TF_BC3)
         return DXTLT_FF_UNKNOWN_TRANSFORM_FORMAT;
     int32_t rc = dxtlt_transform_header_unpack(header, &tf, &mode, &sa, &sc);
@@ -591,6 +669,12 @@ size_t dxtlt_dds_transform_batch(DxtltDdsBatchItem* items, size_t count, bool in
                 mode = 0;
                 sa = sc = false;
                 first_word = g == 6 ? kBc6hPrivateHeader : kBc7PrivateHeader;
+            } else if (const int code = dds_to_pixel_code(info.Format); code >= 0) {
+                // opt-in: this build's pixel layout; rides in the same batch as format 8 / 9, which reads the triple the same way
+                const int B = pixel_code_bytes(code);
+                bcn = B == 4 ? DXTLT_FORMAT_PIXELS4 : DXTLT_FORMAT_PIXELS3;
+                if (length % (size_t)B != 0) { reject(DXTLT_FF_INVALID_DATA_ALIGNMENT); continue; }
+                first_word = pixel_header((uint32_t)code, dxtlt_host::pixel_decorrelate_of(mode), dxtlt_host::pixel_layout_of(sa, sc));
             } else {
                 if (bcn == 0) { reject(DXTLT_FF_UNKNOWN_TRANSFORM_FORMAT); continue; }
                 if (length % (bcn == 1 ? 8 : 16) != 0) { reject(DXTLT_FF_INVALID_DATA_ALIGNMENT); continue; }
@@ -601,7 +685,8 @@ size_t dxtlt_dds_transform_batch(DxtltDdsBatchItem* items, size_t count, bool in
             }
         } else {
             const uint32_t header = rd32(it.input);
-            bool split45 = false;
+            bool split45 = false, pixel_decorrelate = false;
+            uint8_t pixel_layout = 0;
             const int f45 = bc45_of_header(header, &split45);
             if (f45 < 0) { reject(DXTLT_FF_CORRUPTED_EMBEDDED_DATA); continue; }
             if (f45 != 0) {
@@ -617,6 +702,13 @@ size_t dxtlt_dds_transform_batch(DxtltDdsBatchItem* items, size_t count, bool in
                 bcn = bc6h ? 6 : 7;
                 mode = 0;
                 sa = sc = false;
+            } else if (const int B = pixels_of_header(header, &pixel_decorrelate, &pixel_layout); B != 0) {
+                if (B < 0) { reject(DXTLT_FF_CORRUPTED_EMBEDDED_DATA); continue; }
+                if (length % (size_t)B != 0) { reject(DXTLT_FF_INVALID_DATA_ALIGNMENT); continue; }
+                bcn = B == 4 ? DXTLT_FORMAT_PIXELS4 : DXTLT_FORMAT_PIXELS3;
+                mode = pixel_decorrelate ? 1 : 0;   // the triple the batch reads back as these settings
+                sc = pixel_layout != 0;
+                sa = pixel_layout == 2;
             } else {
                 if ((header & 0xF) > DXTLT_TF_BC3) { reject(DXTLT_FF_UNKNOWN_TRANSFORM_FORMAT); continue; }
                 int32_t tf = 0;

@@ -49,7 +49,7 @@ int32_t fail_verbatim(int32_t code, const char* text);
 // table (granule_layout, granule_host.cpp), where N is the array's main part (whole granules): the tail part behind the
 // streams is a buffer of its own and never passes through a layout.
 struct StreamLayout {
-    int format;              // 1..7: picks the pipeline's chunk-size rule
+    int format;              // 1..9: picks the pipeline's chunk-size rule
     int n;                   // streams
     uint64_t off[8], width[8];
     uint64_t block_bytes;
@@ -128,6 +128,20 @@ int32_t granule_device_range(int format, bool inverse, const void* d_src, void* 
 int32_t granule_sharded(int format, bool inverse, const uint8_t* in, uint8_t* out, size_t len, int32_t num_shards);
 int32_t granule_shard_pieces(int format, uint64_t total_blocks, uint64_t first_block, uint64_t num_blocks, uint64_t* global_off,
                              uint64_t* local_off, uint64_t* bytes);
+
+// ---- pixels_api.cpp: uncompressed pixels (include/dxtlt_pixels.h); generic format codes 8 = 4-byte, 9 = 3-byte pixels ----
+inline bool is_pixel_format(int format) { return format == 8 || format == 9; }
+inline int pixel_bytes_of(int format) { return format == 8 ? 4 : 3; }
+// the generic entry points' settings triple as pixel settings: any decorrelation mode = decorrelate; no colour split =
+// INTERLEAVED, colour split = PLANAR, colour and alpha split = PLANAR_DELTA
+inline bool pixel_decorrelate_of(uint8_t mode) { return mode != 0; }
+inline uint8_t pixel_layout_of(bool split_alpha, bool split_colour) { return !split_colour ? 0 : split_alpha ? 2 : 1; }
+StreamLayout pixel_layout(int pixel_bytes, uint8_t layout);
+int32_t pixel_host_call(int pixel_bytes, bool inverse, const uint8_t* in, uint8_t* out, size_t len, bool decorrelate, uint8_t layout);
+int32_t pixel_device_range(int pixel_bytes, bool inverse, const void* d_src, void* d_dst, uint64_t total, uint64_t first,
+                           uint64_t num, bool decorrelate, uint8_t layout, void* stream);
+int32_t pixel_sharded(int pixel_bytes, bool inverse, const uint8_t* in, uint8_t* out, size_t len, bool decorrelate, uint8_t layout,
+                      int32_t num_shards, std::vector<DxtltShardStat>* stats);
 
 // Binds the calling thread -- one this library created for `device` -- to the CPUs local to the device (numa_affinity.cpp).
 // Returns the number of CPUs bound to, 0 when nothing was changed.

@@ -192,7 +192,9 @@ int32_t dxtlt_host::pipelined_range(const StreamLayout& S, const Launch& launch,
                                     const uint8_t* in, uint8_t* out, uint64_t total, uint64_t base, uint64_t blocks)
 {
     const uint64_t B = S.block_bytes;
-    const uint64_t chunk_blocks = pipeline_chunk_bytes(S, blocks * B) / B;  // a multiple of every tile size (and of the sort granule)
+    // a multiple of every tile size (and of the sort granule); 3-byte pixels do not divide a power of two: rounded down
+    uint64_t chunk_blocks = pipeline_chunk_bytes(S, blocks * B) / B;
+    chunk_blocks -= chunk_blocks % S.align_blocks;
     const int nchunks = (int)((blocks + chunk_blocks - 1) / chunk_blocks);
     const int dev = d.dev;
 

@@ -1,0 +1,21 @@
+// pixel_launch.h -- internal launch interface between the C ABI layer (pixels_api.cpp) and the uncompressed-pixel kernels
+// (pixel_kernels.hip): RGBA8888 / BGRA8888 (4 bytes per pixel) and BGR888 (3), docs/PIXEL_FORMAT.md layout version 1.
+#pragma once
+#include <hip/hip_runtime_api.h>
+#include <stdint.h>
+
+namespace dxtlt {
+namespace pixels {
+
+constexpr uint64_t kTile = 4096;   // pixels per workgroup = bytes per plane segment (DXTLT_PIXEL_SEGMENT)
+enum Layout : int { kInterleaved = 0, kPlanar = 1, kPlanarDelta = 2 };
+
+// Pixels [first, first + num) of a buffer of `total` pixels of `pixel_bytes` (3 or 4) bytes.  The interleaved-side pointer is
+// the range's first pixel, the transformed-side pointer byte 0 of the whole transformed buffer; forward reads the former
+// and writes the latter, inverse the other way round.  `first` is a multiple of kTile.  Enqueues on `stream`;
+// hipErrorInvalidValue for arguments the kernels do not take (checked by the caller first), else the launch's error.
+hipError_t launch_range(int pixel_bytes, bool inverse, bool decorrelate, int layout, const void* src, void* dst, uint64_t total,
+                        uint64_t first, uint64_t num, hipStream_t stream);
+
+}  // namespace pixels
+}  // namespace dxtlt

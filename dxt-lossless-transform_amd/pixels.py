@@ -1,0 +1,118 @@
+"""Uncompressed pixels -- RGBA8888 / BGRA8888 (4 bytes per pixel) and BGR888 (3) -- in this build's layout, version 1
+(docs/PIXEL_FORMAT.md); upstream has no transform for them.  Thin Python layer over include/dxtlt_pixels.h, the same buffer
+conventions as bc6h.py: host buffers (numpy uint8 / bytes / bytearray) or CUDA uint8 tensors on torch's current stream."""
+from __future__ import annotations
+
+import ctypes as C
+
+from . import _lib
+
+INTERLEAVED, PLANAR, PLANAR_DELTA = 0, 1, 2
+SEGMENT = 4096
+
+_declared = False
+
+
+def _l():
+    global _declared
+    l = _lib.load()
+    if not _declared:
+        vp, sz, i32, b, u8, u64 = C.c_void_p, C.c_size_t, C.c_int32, C.c_bool, C.c_uint8, C.c_uint64
+        for n in ("dxtlt_transform_pixels", "dxtlt_untransform_pixels"):
+            getattr(l, n).argtypes, getattr(l, n).restype = [vp, vp, sz, i32, b, u8], i32
+        for n in ("dxtlt_transform_pixels_device", "dxtlt_untransform_pixels_device"):
+            getattr(l, n).argtypes, getattr(l, n).restype = [vp, vp, sz, i32, b, u8, vp], i32
+        l.dxtlt_transform_pixels_range_device.argtypes = [i32, b, vp, vp, u64, u64, u64, b, u8, vp]
+        l.dxtlt_transform_pixels_range_device.restype = i32
+        _declared = True
+    return l
+
+
+def _check_settings(pixel_bytes: int, layout: int) -> None:
+    if pixel_bytes not in (3, 4):
+        raise ValueError("pixel_bytes must be 4 (RGBA8888, BGRA8888) or 3 (BGR888)")
+    if layout not in (INTERLEAVED, PLANAR, PLANAR_DELTA):
+        raise ValueError("layout must be INTERLEAVED, PLANAR or PLANAR_DELTA")
+
+
+def _run(inverse: bool, input, output, pixel_bytes: int, decorrelate: bool, layout: int) -> None:
+    from . import DeviceError, InvalidLength, OutputBufferTooSmall, _Buf
+
+    _check_settings(pixel_bytes, layout)
+    src, dst = _Buf(input, False), _Buf(output, True)
+    if src.nbytes % pixel_bytes != 0:
+        raise InvalidLength(src.nbytes)
+    if dst.nbytes < src.nbytes:
+        raise OutputBufferTooSmall(src.nbytes, dst.nbytes)
+    if (src.device is None) != (dst.device is None):
+        raise TypeError("input and output must both be host buffers or both be device tensors")
+    l = _l()
+    name = "dxtlt_untransform_pixels" if inverse else "dxtlt_transform_pixels"
+    if src.device is None:
+        rc = getattr(l, name)(src.ptr, dst.ptr, src.nbytes, pixel_bytes, bool(decorrelate), layout)
+    else:
+        import torch
+
+        with torch.cuda.device(src.device):
+            stream = torch.cuda.current_stream().cuda_stream
+            rc = getattr(l, name + "_device")(src.ptr, dst.ptr, src.nbytes, pixel_bytes, bool(decorrelate), layout, stream)
+    if rc != _lib.OK:
+        raise DeviceError(rc, _lib.last_error())
+
+
+def transform_pixels(input, output, pixel_bytes: int = 4, decorrelate: bool = True, layout: int = PLANAR_DELTA) -> None:
+    _run(False, input, output, pixel_bytes, decorrelate, layout)
+
+
+def untransform_pixels(input, output, pixel_bytes: int = 4, decorrelate: bool = True, layout: int = PLANAR_DELTA) -> None:
+    _run(True, input, output, pixel_bytes, decorrelate, layout)
+
+
+def transform_pixels_range(inverse: bool, src, dst, total_pixels: int, first_pixel: int, num_pixels: int, pixel_bytes: int = 4,
+                           decorrelate: bool = True, layout: int = PLANAR_DELTA) -> None:
+    """dxtlt_transform_pixels_range_device on torch CUDA tensors: the interleaved-side tensor starts at pixel `first_pixel` (a
+    multiple of SEGMENT), the transformed-side tensor is the whole transformed buffer."""
+    import torch
+
+    from . import DeviceError, OutputBufferTooSmall, _Buf
+
+    _check_settings(pixel_bytes, layout)
+    s, d = _Buf(src, False), _Buf(dst, True)
+    if s.device is None or d.device is None:
+        raise TypeError("transform_pixels_range takes device tensors")
+    inter, trans = (d, s) if inverse else (s, d)
+    if inter.nbytes < num_pixels * pixel_bytes or trans.nbytes < total_pixels * pixel_bytes:
+        raise OutputBufferTooSmall(max(num_pixels, total_pixels) * pixel_bytes, min(inter.nbytes, trans.nbytes))
+    with torch.cuda.device(s.device):
+        stream = torch.cuda.current_stream().cuda_stream
+        rc = _l().dxtlt_transform_pixels_range_device(pixel_bytes, bool(inverse), s.ptr, d.ptr, total_pixels, first_pixel, num_pixels,
+                                                      bool(decorrelate), layout, stream)
+    if rc != _lib.OK:
+        raise DeviceError(rc, _lib.last_error())
+
+
+def settings_triple(decorrelate: bool, layout: int):
+    """(decorrelation_mode, split_alpha_endpoints, split_colour_endpoints) as the generic entry points -- the host batch call's
+    format codes 8 / 9, dxtlt_transform_sharded, the DDS calls -- read these settings"""
+    return (1 if decorrelate else 0), layout == PLANAR_DELTA, layout != INTERLEAVED
+
+
+def transform_pixels_sharded(input, output, pixel_bytes: int = 4, decorrelate: bool = True, layout: int = PLANAR_DELTA,
+                             num_shards: int = 0, inverse: bool = False) -> None:
+    """Host buffers, pixel range sharded on segments over the node's GPUs inside this process (dxtlt_transform_sharded with
+    format code 8 / 9).  ``num_shards`` <= 0: one shard per device; more shards than devices run round robin."""
+    from . import DeviceError, InvalidLength, OutputBufferTooSmall, _Buf
+
+    _check_settings(pixel_bytes, layout)
+    src, dst = _Buf(input, False), _Buf(output, True)
+    if src.device is not None or dst.device is not None:
+        raise TypeError("transform_pixels_sharded takes host buffers")
+    if src.nbytes % pixel_bytes != 0:
+        raise InvalidLength(src.nbytes)
+    if dst.nbytes < src.nbytes:
+        raise OutputBufferTooSmall(src.nbytes, dst.nbytes)
+    mode, sa, sc = settings_triple(decorrelate, layout)
+    rc = _l().dxtlt_transform_sharded(8 if pixel_bytes == 4 else 9, bool(inverse), src.ptr, dst.ptr, src.nbytes, mode, sa, sc,
+                                      int(num_shards))
+    if rc != _lib.OK:
+        raise DeviceError(rc, _lib.last_error())

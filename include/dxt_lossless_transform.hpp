@@ -29,6 +29,7 @@
 #include "dxtlt_bc1_normalize.h"
 #include "dxtlt_bc23_normalize.h"
 #include "dxtlt_bc6h.h"
+#include "dxtlt_pixels.h"
 #include "dxtlt_bc7.h"
 #include "dxtlt_color565.h"
 #include "dxtlt_decode.h"
@@ -688,6 +689,46 @@ private:
         detail::check_device(inverse ? dxtlt_untransform_bc6h(input, output, input_len) : dxtlt_transform_bc6h(input, output, input_len));
         return e;
     }
+};
+
+// ADDITIVE: the same builder shape for this build's uncompressed-pixel transform (docs/PIXEL_FORMAT.md; upstream has no
+// transform for RGBA8888 / BGRA8888 / BGR888).  pixel_bytes: 4 or 3.  Defaults: subtract-green, PLANAR_DELTA.  No auto builder:
+// the library's estimator misranks pixel layouts (see the document).
+class PixelManualTransformBuilder {
+public:
+    explicit PixelManualTransformBuilder(int32_t pixel_bytes) : pixel_bytes_(pixel_bytes) {}
+    PixelManualTransformBuilder& decorrelate(bool on)
+    {
+        decorrelate_ = on;
+        return *this;
+    }
+    PixelManualTransformBuilder& layout(uint8_t l)
+    {
+        layout_ = l;
+        return *this;
+    }
+    Error transform(const uint8_t* input, size_t input_len, uint8_t* output, size_t output_len) const
+    {
+        return run(false, input, input_len, output, output_len);
+    }
+    Error untransform(const uint8_t* input, size_t input_len, uint8_t* output, size_t output_len) const
+    {
+        return run(true, input, input_len, output, output_len);
+    }
+
+private:
+    Error run(bool inverse, const uint8_t* input, size_t input_len, uint8_t* output, size_t output_len) const
+    {
+        Error e = Error::from(core::detail_safe::validate(input_len, output_len, pixel_bytes_ == 3 ? 3 : 4));
+        if (e.is_err())
+            return e;
+        detail::check_device(inverse ? dxtlt_untransform_pixels(input, output, input_len, pixel_bytes_, decorrelate_, layout_)
+                                     : dxtlt_transform_pixels(input, output, input_len, pixel_bytes_, decorrelate_, layout_));
+        return e;
+    }
+    int32_t pixel_bytes_;
+    bool decorrelate_ = true;
+    uint8_t layout_ = DXTLT_PIXEL_LAYOUT_PLANAR_DELTA;
 };
 
 }  // namespace api

@@ -78,8 +78,9 @@ uint32_t dxtlt_transform_header_read(const uint8_t *ptr);
 
 /* Header data of the formats upstream keeps placeholders for (embed/formats/bc4.rs, bc5.rs: `split_endpoints`; rgba8888.rs,
  * bgra8888.rs, bgr888.rs: `decorrelation`): version:2 (only 0 valid) | flag:1 | reserved:25 (must be zero).  No transform
- * exists for them upstream or here -- the DDS calls answer DXTLT_FF_UNKNOWN_TRANSFORM_FORMAT -- but a tool that walks
- * headers can name them.  _unpack: DXTLT_FF_UNKNOWN_TRANSFORM_FORMAT for any other format code,
+ * exists for them upstream; this build's own (BC4 / BC5 and the pixel formats, behind the opt-in switches below) write
+ * tagged words that these two functions do not produce and refuse.  With the switches off the DDS calls answer
+ * DXTLT_FF_UNKNOWN_TRANSFORM_FORMAT -- but a tool that walks headers can name them.  _unpack: DXTLT_FF_UNKNOWN_TRANSFORM_FORMAT for any other format code,
  * DXTLT_FF_CORRUPTED_EMBEDDED_DATA for another version or non-zero reserved bits. */
 uint32_t dxtlt_transform_header_pack_reserved_format(int32_t transform_format, bool flag);
 int32_t dxtlt_transform_header_unpack_reserved_format(uint32_t header, int32_t *transform_format, bool *flag);
@@ -162,6 +163,25 @@ uint32_t dxtlt_transform_header_pack_bc6h(void);
 void dxtlt_file_formats_enable_bc45(bool enabled);
 /* The tagged header word of a BC4 (DXTLT_TF_BC4) or BC5 (DXTLT_TF_BC5) file written with this layout; 0 for any other code. */
 uint32_t dxtlt_transform_header_pack_bc45(int32_t transform_format, bool split_endpoints);
+
+/* ADDITIVE, off by default (process-wide), like the BC7 switch.  Upstream reserves TransformFormat::Rgba8888 = 5, Bgra8888 = 6 and
+ * Bgr888 = 7 with a placeholder settings struct (embed/formats/rgba8888.rs, bgra8888.rs, bgr888.rs: decorrelation) but defines no
+ * transform; with this switch off the DDS calls refuse these payloads and header codes (DXTLT_FF_UNKNOWN_TRANSFORM_FORMAT) exactly
+ * as before.  With it on, dxtlt_dds_transform, _auto, _untransform and dxtlt_dds_transform_batch take RGBA8888 (DXGI 27-32, legacy
+ * masks), BGRA8888 (DXGI 87, 90, 91, legacy masks) and BGR888 (legacy 24-bit masks) payloads through this build's layout
+ * (dxtlt_pixels.h, docs/PIXEL_FORMAT.md).  The settings triple is read as the generic entry points read it for format codes 8 / 9:
+ * decorrelation_mode != 0 is `decorrelate`; no colour split = INTERLEAVED, colour split alone = PLANAR, colour and alpha split =
+ * PLANAR_DELTA.  _auto applies the fixed setting (decorrelate, PLANAR_DELTA) and never calls the estimator: the built-in estimator
+ * ranks pixel layouts against what a compressor does with them (docs/PIXEL_FORMAT.md).  A payload length that is not a multiple
+ * of the pixel size is DXTLT_FF_INVALID_DATA_ALIGNMENT.  The header's 28 data bits: bits 0-1 upstream's placeholder version 0, bit
+ * 2 decorrelate, bits 4..3 the layout (0..2), bits 11..5 this build's layout version (1), bits 27..12 the vendor tag 0xD175.
+ * Upstream's unpack -- and dxtlt_transform_header_unpack_reserved_format -- reject the word (its reserved bits are not zero);
+ * dxtlt_dds_untransform accepts exactly the six tagged words per format code and nothing else (DXTLT_FF_CORRUPTED_EMBEDDED_DATA).
+ * Only this build can read such files back. */
+void dxtlt_file_formats_enable_pixels(bool enabled);
+/* The tagged header word of an RGBA8888 (5), BGRA8888 (6) or BGR888 (7) file written with this layout; 0 for any other code or
+ * layout > 2. */
+uint32_t dxtlt_transform_header_pack_pixels(int32_t transform_format, bool decorrelate, uint8_t layout);
 
 /* ADDITIVE: many DDS files per call -- the file-after-file loop of the reference's CLI
  * (tools/dxt-lossless-transform-cli/src/commands/transform/mod.rs:154-199) over ONE pinned upload / launch / download

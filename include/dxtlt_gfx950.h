@@ -168,7 +168,12 @@ typedef struct DxtltBatchItem {
     uint8_t format;                 /* 1, 2, 3 = BC1, BC2, BC3; 7 = BC7 in this build's own format (dxtlt_bc7.h; settings ignored):
                                        its granules go in one launch per direction, its tail parts in a second one;
                                        6 = BC6H in this build's own format (dxtlt_bc6h.h; settings ignored), the same
-                                       way in launches of its own */
+                                       way in launches of its own; dxtlt_transform_batch_host ONLY (the device call
+                                       answers DXTLT_E_INVALID_ARGUMENT for them, as before): 8 = 4-byte pixels (RGBA8888,
+                                       BGRA8888), 9 = 3-byte pixels (BGR888) in this build's pixel layout (dxtlt_pixels.h):
+                                       len a multiple of the pixel size, input and output must not overlap, one launch per item;
+                                       decorrelation_mode != 0 = decorrelate, no colour split = INTERLEAVED, colour split
+                                       alone = PLANAR, colour and alpha split = PLANAR_DELTA */
     uint8_t inverse;                /* 0 = transform, 1 = untransform */
     uint8_t decorrelation_mode;     /* core numbering */
     uint8_t split_alpha_endpoints;  /* BC3 only */
@@ -237,7 +242,10 @@ int32_t dxtlt_transform_batch_host(const DxtltBatchItem *items, size_t count);
  * every output stream is copied straight to its final place in `output_ptr` (no collective; see
  * DESIGN.md "Multi-GPU").  num_devices <= 0 means all visible devices; a number above the visible devices (at most
  * 64) is that many shards dealt round robin over them.  Shards of 96 MiB or more run as a chunked pipeline (upload,
- * kernel and the per-stream downloads of consecutive chunks overlap). */
+ * kernel and the per-stream downloads of consecutive chunks overlap).
+ * format: 1..5 = BC1..BC5; 8 / 9 = uncompressed pixels of 4 / 3 bytes (dxtlt_pixels.h), sharded on 4096-pixel segments, the
+ * settings triple read as DxtltBatchItem documents it.  (BC6H and BC7 have sharded calls of their own; the range, plan and
+ * auto calls of this header take 1..5 only.) */
 int32_t dxtlt_transform_sharded(int32_t format, bool inverse, const uint8_t *input_ptr, uint8_t *output_ptr,
                                 size_t len, uint8_t decorrelation_mode, bool split_alpha_endpoints,
                                 bool split_colour_endpoints, int32_t num_devices);
