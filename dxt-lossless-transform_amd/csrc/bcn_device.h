@@ -476,9 +476,36 @@ __device__ __forceinline__ void fwd_aligned_tile(const uint8_t* __restrict__ aos
     WG_MARK(4);
 }
 
-template <int FMT, int VARIANT, bool SA, bool SC, int THREADS>
+// Where an inverse tile's blocks go.  A SINK has two members, called by every lane that holds blocks, with the lane's vector q
+// (one BC2 / BC3 / BC5 block, two BC1 / BC4 blocks) of tile `tile`:
+//   store<FMT, THREADS>(aos, tile, t, q)              a whole tile: all THREADS lanes call it together
+//   store_edge<FMT, THREADS>(aos, tile, t, q, own)    the edge tile, whose first `own` blocks exist: only the lanes that hold
+//                                                     one call it (BC1 / BC4: the last of them perhaps with its first block alone)
+// AosSink, the default, is the block array itself; the image kernels (image_kernels.hip) decode q and write pixel rows instead.
+struct AosSink {
+    template <int FMT, int THREADS>
+    __device__ __forceinline__ void store(uint8_t* aos, uint64_t tile, int t, u32x4 q) const
+    {
+        gstore16_aos(aos, aos + tile * (THREADS * 16) + t * 16, q);
+    }
+    template <int FMT, int THREADS>
+    __device__ __forceinline__ void store_edge(uint8_t* aos, uint64_t tile, int t, u32x4 q, int own) const
+    {
+        // (address first, then the comparison: the statement order the edge tile had when the store was written out in it --
+        // with the comparison evaluated first the compiler schedules the kernels' last instructions differently)
+        constexpr int PV = 16 / fmt_block(FMT);
+        uint8_t* out = aos + tile * (THREADS * 16) + t * 16;
+        if ((t + 1) * PV <= own)
+            __builtin_nontemporal_store(q, reinterpret_cast<u32x4*>(out));
+        else   // BC1, odd count: only the vector's first block exists
+            __builtin_nontemporal_store(u32x2{q.x, q.y}, reinterpret_cast<u32x2*>(out));
+    }
+};
+
+template <int FMT, int VARIANT, bool SA, bool SC, int THREADS, typename SINK = AosSink>
 __device__ __forceinline__ void inv_aligned_tile(const uint8_t* __restrict__ soa, uint8_t* __restrict__ aos,
-                                                 uint64_t total_blocks, uint64_t first_block, uint64_t tile, uint8_t* lds)
+                                                 uint64_t total_blocks, uint64_t first_block, uint64_t tile, uint8_t* lds,
+                                                 const SINK& sink = SINK{})
 {
     constexpr int T = tile_blocks(FMT, THREADS);
     const int t = threadIdx.x;
@@ -486,7 +513,7 @@ __device__ __forceinline__ void inv_aligned_tile(const uint8_t* __restrict__ soa
     lds_at<u32x4>(lds, t * 16) = gload16(soa + o);
     __syncthreads();
     const u32x4 q = gather_from_image<FMT, VARIANT, SA, SC, T>(lds, t);
-    gstore16_aos(aos, aos + tile * (THREADS * 16) + t * 16, q);
+    sink.template store<FMT, THREADS>(aos, tile, t, q);
 }
 
 template <int FMT, int VARIANT, bool SA, bool SC, int THREADS, int NORM = kNormNone>
@@ -1470,10 +1497,10 @@ __device__ __forceinline__ void inv_shift_load_wave(const uint8_t* __restrict__ 
 }
 
 // one shifted tile, inverse; `lds`: shift_lds_bytes(1, THREADS)
-template <int FMT, int VARIANT, bool SA, bool SC, int THREADS = 256>
+template <int FMT, int VARIANT, bool SA, bool SC, int THREADS = 256, typename SINK = AosSink>
 __device__ __forceinline__ void inv_shift_tile(const uint8_t* __restrict__ soa, uint8_t* __restrict__ aos,
                                                uint64_t total_blocks, uint64_t /*first_block: in sh.gbase*/, const Shifts& sh, uint64_t tile,
-                                               uint8_t* lds)
+                                               uint8_t* lds, const SINK& sink = SINK{})
 {
     constexpr Streams S = make_streams(FMT, SA, SC);
     constexpr int T = tile_blocks(FMT, THREADS);
@@ -1501,15 +1528,16 @@ __device__ __forceinline__ void inv_shift_tile(const uint8_t* __restrict__ soa, 
     __syncthreads();
     const u32x4 q = sh.natural ? gather_shifted<FMT, VARIANT, SA, SC, true>(lds, t, base)
                                : gather_shifted<FMT, VARIANT, SA, SC, false>(lds, t, base);
-    gstore16_aos(aos, aos + tile * (THREADS * 16) + t * 16, q);
+    sink.template store<FMT, THREADS>(aos, tile, t, q);
 }
 
 // The inverse edge tile: shifted tile `tile` (= sh.full_tiles) of a range whose last 1 .. T - 1 blocks it owns.  A segment is
 // fetched when it holds bytes of those blocks' records: whole when it lies inside the transformed buffer (the bytes that
 // belong to the next stream land in LDS nobody reads), byte by byte where it pokes out of the buffer.
-template <int FMT, int VARIANT, bool SA, bool SC, int THREADS = 256>
+template <int FMT, int VARIANT, bool SA, bool SC, int THREADS = 256, typename SINK = AosSink>
 __device__ __forceinline__ void inv_shift_edge_tile(const uint8_t* __restrict__ soa, uint8_t* __restrict__ aos,
-                                                    uint64_t total_blocks, const Shifts& sh, uint64_t tile, uint8_t* lds)
+                                                    uint64_t total_blocks, const Shifts& sh, uint64_t tile, uint8_t* lds,
+                                                    const SINK& sink = SINK{})
 {
     constexpr Streams S = make_streams(FMT, SA, SC);
     constexpr int T = tile_blocks(FMT, THREADS);
@@ -1568,11 +1596,7 @@ __device__ __forceinline__ void inv_shift_edge_tile(const uint8_t* __restrict__ 
     if (t * PV < own) {
         const u32x4 q = sh.natural ? gather_shifted<FMT, VARIANT, SA, SC, true>(lds, t, base)
                                    : gather_shifted<FMT, VARIANT, SA, SC, false>(lds, t, base);
-        uint8_t* out = aos + tile * (THREADS * 16) + t * 16;
-        if ((t + 1) * PV <= own)
-            __builtin_nontemporal_store(q, reinterpret_cast<u32x4*>(out));
-        else   // BC1, odd count: only the vector's first block exists
-            __builtin_nontemporal_store(u32x2{q.x, q.y}, reinterpret_cast<u32x2*>(out));
+        sink.template store_edge<FMT, THREADS>(aos, tile, t, q, own);
     }
 }
 

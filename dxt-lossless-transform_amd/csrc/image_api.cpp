@@ -1,0 +1,154 @@
+// image_api.cpp -- C ABI of the image decoders (include/dxtlt_image.h); kernels in image_kernels.hip.  Every argument is
+// checked before a device is touched.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "../../include/dxtlt_gfx950.h"
+#include "../../include/dxtlt_image.h"
+#include "host_common.h"
+#include "image_launch.h"
+
+using dxtlt_host::fail;
+using dxtlt_host::kInvalidArgument;
+using dxtlt_host::kInvalidLength;
+using dxtlt_host::kOk;
+
+namespace {
+
+inline uint64_t block_bytes_of(int32_t fmt) { return fmt == 1 ? 8 : 16; }
+inline uint64_t blocks_of(uint32_t width, uint32_t height) { return (((uint64_t)width + 3) / 4) * (((uint64_t)height + 3) / 4); }
+
+int32_t check_format(int32_t fmt)
+{
+    if (fmt < 1 || fmt > 3)
+        return fail(kInvalidArgument, "format must be 1 (BC1), 2 (BC2) or 3 (BC3)");
+    return kOk;
+}
+
+// the checks every call shares, for a non-empty image, in the documented order
+int32_t check_image(const void* blocks, const void* pixels, uint32_t width, uint64_t pitch)
+{
+    if (blocks == nullptr || pixels == nullptr)
+        return fail(kInvalidArgument, "NULL pointer with a non-empty image");
+    if (pitch < 4 * (uint64_t)width)
+        return fail(kInvalidArgument, "pitch is smaller than 4 * width");
+    if ((pitch & 3) != 0 || (reinterpret_cast<uintptr_t>(pixels) & 3) != 0)
+        return fail(kInvalidArgument, "pitch and the pixel pointer must be multiples of 4");
+    return kOk;
+}
+
+int32_t check_range(uint8_t mode, uint64_t total_blocks, uint64_t first_block, uint64_t blocks)
+{
+    if (mode > 3)
+        return fail(kInvalidArgument, "decorrelation_mode must be 0..3");
+    if (first_block > total_blocks || blocks > total_blocks - first_block)
+        return fail(kInvalidArgument, "first_block + blocks of the image exceeds total_blocks");
+    return kOk;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t dxtlt_decode_image_device(int32_t format, const void* d_blocks, uint32_t width, uint32_t height, void* d_pixels,
+                                  uint64_t pitch, void* hip_stream)
+{
+    if (int32_t rc = check_format(format); rc != kOk)
+        return rc;
+    if (width == 0 || height == 0)
+        return kOk;
+    if (int32_t rc = check_image(d_blocks, d_pixels, width, pitch); rc != kOk)
+        return rc;
+    HIP_TRY(dxtlt::launch_decode_image(format, d_blocks, dxtlt::make_image_sink(d_pixels, pitch, width, height),
+                                       static_cast<hipStream_t>(hip_stream)),
+            "kernel launch");
+    return kOk;
+}
+
+int32_t dxtlt_untransform_decode_image_device(int32_t format, const void* d_transformed, uint64_t total_blocks, uint64_t first_block,
+                                              uint32_t width, uint32_t height, uint8_t decorrelation_mode,
+                                              bool split_alpha_endpoints, bool split_colour_endpoints, void* d_pixels,
+                                              uint64_t pitch, void* hip_stream)
+{
+    if (int32_t rc = check_format(format); rc != kOk)
+        return rc;
+    if (width == 0 || height == 0)
+        return kOk;
+    if (int32_t rc = check_image(d_transformed, d_pixels, width, pitch); rc != kOk)
+        return rc;
+    if (int32_t rc = check_range(decorrelation_mode, total_blocks, first_block, blocks_of(width, height)); rc != kOk)
+        return rc;
+    const dxtlt::Settings s{decorrelation_mode, split_alpha_endpoints, split_colour_endpoints};
+    HIP_TRY(dxtlt::launch_untransform_decode_image(static_cast<dxtlt::Format>(format), s, d_transformed, total_blocks, first_block,
+                                                   dxtlt::make_image_sink(d_pixels, pitch, width, height),
+                                                   static_cast<hipStream_t>(hip_stream)),
+            "kernel launch");
+    return kOk;
+}
+
+int32_t dxtlt_untransform_decode_image(int32_t format, const uint8_t* transformed, size_t len, uint64_t first_block, uint32_t width,
+                                       uint32_t height, uint8_t decorrelation_mode, bool split_alpha_endpoints,
+                                       bool split_colour_endpoints, uint8_t* pixels, uint64_t pitch)
+{
+    if (int32_t rc = check_format(format); rc != kOk)
+        return rc;
+    if (width == 0 || height == 0)
+        return kOk;
+    if (int32_t rc = check_image(transformed, pixels, width, pitch); rc != kOk)
+        return rc;
+    const uint64_t bs = block_bytes_of(format), total_blocks = len / bs;
+    if (int32_t rc = check_range(decorrelation_mode, total_blocks, first_block, blocks_of(width, height)); rc != kOk)
+        return rc;
+    if (len % bs != 0)
+        return fail(kInvalidLength, "len is not a multiple of the block size");
+
+    // one upload of the transformed buffer, the device call into tightly packed rows, one download of the rows
+    const uint64_t row_bytes = 4 * (uint64_t)width, d_pitch = (row_bytes + 15) & ~(uint64_t)15;
+    const uint64_t need = std::max<uint64_t>(len, d_pitch * height);
+    void *d_in = nullptr, *d_out = nullptr;
+    hipStream_t st = nullptr;
+    if (int32_t rc = dxtlt_host::acquire_staging((size_t)need, &d_in, &d_out, &st); rc != kOk)
+        return rc;
+    HIP_TRY(hipMemcpyAsync(d_in, transformed, len, hipMemcpyHostToDevice, st), "H2D copy");
+    const dxtlt::Settings s{decorrelation_mode, split_alpha_endpoints, split_colour_endpoints};
+    HIP_TRY(dxtlt::launch_untransform_decode_image(static_cast<dxtlt::Format>(format), s, d_in, total_blocks, first_block,
+                                                   dxtlt::make_image_sink(d_out, d_pitch, width, height), st),
+            "kernel launch");
+    HIP_TRY(hipMemcpy2DAsync(pixels, pitch, d_out, d_pitch, row_bytes, height, hipMemcpyDeviceToHost, st), "D2H copy");
+    HIP_TRY(hipStreamSynchronize(st), "stream synchronize");
+    return kOk;
+}
+
+int32_t dxtlt_image_mip_level(uint32_t width, uint32_t height, uint32_t mip_count, uint32_t level, uint32_t* level_width,
+                              uint32_t* level_height, uint64_t* first_block, uint64_t* num_blocks, uint64_t* total_blocks)
+{
+    if (width == 0 || height == 0 || mip_count == 0 || level >= mip_count)
+        return fail(kInvalidArgument, "mip level: zero width, height or mip_count, or level >= mip_count");
+    auto dim = [](uint32_t v, uint32_t k) { return k < 32 && (v >> k) > 0 ? v >> k : 1u; };
+    uint64_t before = 0, total = 0;
+    // levels 32 and up are 1 x 1 = one block each, whatever the size
+    const uint32_t walked = mip_count < 32 ? mip_count : 32;
+    for (uint32_t k = 0; k < walked; ++k) {
+        const uint64_t n = blocks_of(dim(width, k), dim(height, k));
+        if (k < level)
+            before += n;
+        total += n;
+    }
+    total += mip_count - walked;
+    if (level > walked)
+        before += level - walked;
+    if (level_width)
+        *level_width = dim(width, level);
+    if (level_height)
+        *level_height = dim(height, level);
+    if (first_block)
+        *first_block = before;
+    if (num_blocks)
+        *num_blocks = blocks_of(dim(width, level), dim(height, level));
+    if (total_blocks)
+        *total_blocks = total;
+    return kOk;
+}
+
+}  // extern "C"

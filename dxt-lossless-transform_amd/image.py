@@ -1,0 +1,125 @@
+"""BC1 / BC2 / BC3 blocks -> a row-major RGBA8888 image, over include/dxtlt_image.h (docs/IMAGE_DECODE.md).
+
+``decode_image`` decodes a block array in block order; ``untransform_decode_image`` decodes a block range of a TRANSFORMED
+buffer in one kernel (the untransformed blocks never touch memory); ``mip_level`` says which range a mip level is.  Pixel
+(x, y) is the bytes r, g, b, a at ``y * pitch + 4 * x`` of the output; nothing else of the output is written.
+1-D ``uint8`` numpy / bytes-like host buffers or CUDA ``torch.uint8`` tensors (torch's current stream).  No CPU fallback:
+``decode_image`` takes device tensors only, ``untransform_decode_image`` both kinds."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+
+_FMT = {"bc1": 1, "bc2": 2, "bc3": 3}
+_BLOCK = {"bc1": 8, "bc2": 16, "bc3": 16}
+_declared = False
+
+
+def _l():
+    global _declared
+    l = _lib.load()
+    if not _declared:
+        vp, i32, u32, u64, u8, b = C.c_void_p, C.c_int32, C.c_uint32, C.c_uint64, C.c_uint8, C.c_bool
+        l.dxtlt_decode_image_device.argtypes = [i32, vp, u32, u32, vp, u64, vp]
+        l.dxtlt_untransform_decode_image_device.argtypes = [i32, vp, u64, u64, u32, u32, u8, b, b, vp, u64, vp]
+        l.dxtlt_untransform_decode_image.argtypes = [i32, vp, C.c_size_t, u64, u32, u32, u8, b, b, vp, u64]
+        l.dxtlt_image_mip_level.argtypes = [u32, u32, u32, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(u64), C.POINTER(u64),
+                                            C.POINTER(u64)]
+        for f in (l.dxtlt_decode_image_device, l.dxtlt_untransform_decode_image_device, l.dxtlt_untransform_decode_image,
+                  l.dxtlt_image_mip_level):
+            f.restype = i32
+        _declared = True
+    return l
+
+
+def _check(rc: int) -> None:
+    from . import DeviceError
+
+    if rc != _lib.OK:
+        raise DeviceError(rc, _lib.last_error())
+
+
+def image_blocks(width: int, height: int) -> int:
+    return ((width + 3) // 4) * ((height + 3) // 4)
+
+
+def mip_level(width: int, height: int, mip_count: int, level: int):
+    """(level_width, level_height, first_block, num_blocks, total_blocks) of level ``level`` of a ``width`` x ``height``
+    texture whose ``mip_count`` levels are stored largest first.  No device needed."""
+    w, h = C.c_uint32(), C.c_uint32()
+    first, num, total = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    _check(_l().dxtlt_image_mip_level(width, height, mip_count, level, C.byref(w), C.byref(h), C.byref(first), C.byref(num),
+                                      C.byref(total)))
+    return w.value, h.value, first.value, num.value, total.value
+
+
+def _output(src, width, height, out, pitch):
+    """the output buffer (a new one on the source's side when ``out`` is None), its _Buf and the pitch"""
+    from . import OutputBufferTooSmall, _Buf
+
+    if pitch is None:
+        pitch = 4 * width
+    need = pitch * (height - 1) + 4 * width if width and height else 0
+    if out is None:
+        if src.device is None:
+            out = np.zeros(pitch * height, dtype=np.uint8)
+        else:
+            import torch
+
+            out = torch.zeros(pitch * height, dtype=torch.uint8, device=f"cuda:{src.device}")
+    dst = _Buf(out, True)
+    if dst.device != src.device:
+        raise TypeError("all buffers must be host buffers or all be tensors on one device")
+    if dst.nbytes < need:
+        raise OutputBufferTooSmall(need, dst.nbytes)
+    return out, dst, pitch
+
+
+def decode_image(fmt: str, blocks, width: int, height: int, out=None, pitch=None):
+    """``blocks``: ceil(width / 4) * ceil(height / 4) blocks in block order, a CUDA tensor.  Returns ``out`` (a new tensor of
+    ``pitch * height`` bytes when None); ``pitch`` defaults to ``4 * width``."""
+    from . import InvalidLength, _Buf
+
+    src = _Buf(blocks, False)
+    if src.device is None:
+        raise TypeError("decode_image takes device tensors (the library has no host-pointer form of it)")
+    if src.nbytes < image_blocks(width, height) * _BLOCK[fmt]:
+        raise InvalidLength(src.nbytes)
+    out, dst, pitch = _output(src, width, height, out, pitch)
+    import torch
+
+    with torch.cuda.device(src.device):
+        _check(_l().dxtlt_decode_image_device(_FMT[fmt], src.ptr, width, height, dst.ptr, pitch,
+                                              torch.cuda.current_stream(src.device).cuda_stream))
+    return out
+
+
+def untransform_decode_image(fmt: str, transformed, width: int, height: int, *, first_block: int = 0, total_blocks=None,
+                             decorrelation_mode, split_alpha_endpoints: bool, split_colour_endpoints: bool, out=None, pitch=None):
+    """``transformed``: the WHOLE transformed buffer of ``total_blocks`` blocks (default: its length); the image is its blocks
+    [first_block, first_block + ceil(width / 4) * ceil(height / 4)).  Returns ``out``."""
+    from . import InvalidLength, _Buf
+
+    src = _Buf(transformed, False)
+    if src.nbytes % _BLOCK[fmt] != 0:
+        raise InvalidLength(src.nbytes)
+    if total_blocks is None:
+        total_blocks = src.nbytes // _BLOCK[fmt]
+    if total_blocks * _BLOCK[fmt] > src.nbytes:
+        raise InvalidLength(src.nbytes)
+    out, dst, pitch = _output(src, width, height, out, pitch)
+    mode, sa, sc = int(decorrelation_mode), bool(split_alpha_endpoints), bool(split_colour_endpoints)
+    l = _l()
+    if src.device is None:
+        _check(l.dxtlt_untransform_decode_image(_FMT[fmt], src.ptr, total_blocks * _BLOCK[fmt], first_block, width, height, mode,
+                                                sa, sc, dst.ptr, pitch))
+        return out
+    import torch
+
+    with torch.cuda.device(src.device):
+        _check(l.dxtlt_untransform_decode_image_device(_FMT[fmt], src.ptr, total_blocks, first_block, width, height, mode, sa, sc,
+                                                       dst.ptr, pitch, torch.cuda.current_stream(src.device).cuda_stream))
+    return out

@@ -35,6 +35,7 @@
 #include "dxtlt_decode.h"
 #include "dxtlt_estimator.h"
 #include "dxtlt_gfx950.h"
+#include "dxtlt_image.h"
 
 namespace dxt_lossless_transform {
 
@@ -730,6 +731,48 @@ private:
     bool decorrelate_ = true;
     uint8_t layout_ = DXTLT_PIXEL_LAYOUT_PLANAR_DELTA;
 };
+
+// ADDITIVE: BC1 / BC2 / BC3 blocks -> a row-major RGBA8888 image (dxtlt_image.h, docs/IMAGE_DECODE.md; upstream decodes single
+// blocks in its tests only).  format = 1, 2, 3; pixel (x, y) = the bytes r, g, b, a at pixels + y * pitch + 4 * x.  A bad
+// argument or a device failure throws DeviceError.
+struct MipLevel {
+    uint32_t width = 0, height = 0;
+    uint64_t first_block = 0, num_blocks = 0, total_blocks = 0;
+};
+// level `level` of a width x height texture whose mip_count levels are stored largest first (no device needed)
+inline MipLevel image_mip_level(uint32_t width, uint32_t height, uint32_t mip_count, uint32_t level)
+{
+    MipLevel m;
+    detail::check_device(dxtlt_image_mip_level(width, height, mip_count, level, &m.width, &m.height, &m.first_block, &m.num_blocks,
+                                               &m.total_blocks));
+    return m;
+}
+// device pointers, asynchronous on `hip_stream`: a block array in block order
+inline void decode_image_device(int32_t format, const void* d_blocks, uint32_t width, uint32_t height, void* d_pixels,
+                                uint64_t pitch, void* hip_stream)
+{
+    detail::check_device(dxtlt_decode_image_device(format, d_blocks, width, height, d_pixels, pitch, hip_stream));
+}
+// device pointers, asynchronous on `hip_stream`: blocks [first_block, ...) of a whole transformed buffer of total_blocks
+inline void untransform_decode_image_device(int32_t format, const void* d_transformed, uint64_t total_blocks, uint64_t first_block,
+                                            uint32_t width, uint32_t height, YCoCgVariant decorrelation_mode,
+                                            bool split_alpha_endpoints, bool split_colour_endpoints, void* d_pixels,
+                                            uint64_t pitch, void* hip_stream)
+{
+    detail::check_device(dxtlt_untransform_decode_image_device(format, d_transformed, total_blocks, first_block, width, height,
+                                                               static_cast<uint8_t>(to_internal_variant(decorrelation_mode)),
+                                                               split_alpha_endpoints, split_colour_endpoints, d_pixels, pitch,
+                                                               hip_stream));
+}
+// host pointers, synchronous: `transformed` is the whole transformed buffer of `len` bytes
+inline void untransform_decode_image(int32_t format, const uint8_t* transformed, size_t len, uint64_t first_block, uint32_t width,
+                                     uint32_t height, YCoCgVariant decorrelation_mode, bool split_alpha_endpoints,
+                                     bool split_colour_endpoints, uint8_t* pixels, uint64_t pitch)
+{
+    detail::check_device(dxtlt_untransform_decode_image(format, transformed, len, first_block, width, height,
+                                                        static_cast<uint8_t>(to_internal_variant(decorrelation_mode)),
+                                                        split_alpha_endpoints, split_colour_endpoints, pixels, pitch));
+}
 
 }  // namespace api
 }  // namespace dxt_lossless_transform
