@@ -1,5 +1,5 @@
-// bcn_decode.h -- BC1 / BC2 / BC3 block -> sixteen RGBA8888 pixels, in registers (device code; also built for the host
-// by the tests).
+// bcn_decode.h -- BC1 / BC2 / BC3 block -> sixteen RGBA8888 pixels, BC4 / BC5 block -> sixteen R8 / RG8 pixels, in registers
+// (device code; also built for the host by the tests).
 //
 // Reference (paths under /root/reference/src/core/):
 //   dxt-lossless-transform-bc1/src/util/bc1_decode.rs:42-100   decode_bc1_block ("ideal" DX9 rounding: /3 and /2 on
@@ -148,6 +148,30 @@ __host__ __device__ inline void decode_bc3_block_px(const uint32_t q[4], uint32_
         weave_row(byte_perm(p.r, p.r, sel), byte_perm(p.g, p.g, sel), byte_perm(p.b, p.b, sel),
                   byte_perm(tab_hi, tab_lo, spread_3bit(a12)),
                   px + 4 * row);
+    }
+}
+
+// One BC4 block (lo, hi = its eight bytes: a0 a1 and 48 bits of 3-bit indices, byte for byte the alpha half of a BC3 block,
+// docs/BC45_FORMAT.md section 1) -> four R8 pixel rows: byte c of rows[r] is pixel (c, r), the alpha byte decode_bc3_block_px
+// gives that pixel.
+__host__ __device__ inline void decode_bc4_block_rows(uint32_t lo, uint32_t hi, uint32_t rows[4])
+{
+    uint32_t tab_lo, tab_hi;
+    bc3_alpha_table(lo & 0xFFu, (lo >> 8) & 0xFFu, tab_lo, tab_hi);
+    const uint64_t abits = (((uint64_t)hi << 32) | lo) >> 16;   // 48 bits, pixel i at [3i, 3i + 2]
+    for (int row = 0; row < 4; ++row)
+        rows[row] = byte_perm(tab_hi, tab_lo, spread_3bit((uint32_t)(abits >> (12 * row)) & 0xFFFu));
+}
+
+// One BC5 block (red half q[0], q[1], green half q[2], q[3]) -> four RG8 pixel rows of two dwords: r g r g | r g r g
+__host__ __device__ inline void decode_bc5_block_rows(const uint32_t q[4], uint32_t rows[4][2])
+{
+    uint32_t r4[4], g4[4];
+    decode_bc4_block_rows(q[0], q[1], r4);
+    decode_bc4_block_rows(q[2], q[3], g4);
+    for (int row = 0; row < 4; ++row) {
+        rows[row][0] = byte_perm(g4[row], r4[row], 0x05010400u);   // weave_row's first round
+        rows[row][1] = byte_perm(g4[row], r4[row], 0x07030602u);
     }
 }
 

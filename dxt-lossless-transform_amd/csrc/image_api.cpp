@@ -1,5 +1,5 @@
-// image_api.cpp -- C ABI of the image decoders (include/dxtlt_image.h); kernels in image_kernels.hip.  Every argument is
-// checked before a device is touched.
+// image_api.cpp -- C ABI of the image decoders (include/dxtlt_image.h): BC1 / BC2 / BC3 -> RGBA8888, BC4 / BC5 -> R8 / RG8; kernels
+// in image_kernels.hip.  Every argument is checked before a device is touched.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -44,6 +44,28 @@ int32_t check_range(uint8_t mode, uint64_t total_blocks, uint64_t first_block, u
         return fail(kInvalidArgument, "decorrelation_mode must be 0..3");
     if (first_block > total_blocks || blocks > total_blocks - first_block)
         return fail(kInvalidArgument, "first_block + blocks of the image exceeds total_blocks");
+    return kOk;
+}
+
+// ---- BC4 / BC5 -> R8 / RG8 ---------------------------------------------------------------------------------------------
+inline uint64_t channel_bpp(int32_t fmt) { return fmt == 4 ? 1 : 2; }
+
+int32_t check_channel_format(int32_t fmt)
+{
+    if (fmt != 4 && fmt != 5)
+        return fail(kInvalidArgument, "format must be 4 (BC4) or 5 (BC5)");
+    return kOk;
+}
+
+int32_t check_channel_image(int32_t fmt, const void* blocks, const void* pixels, uint32_t width, uint64_t pitch)
+{
+    const uint64_t bpp = channel_bpp(fmt);
+    if (blocks == nullptr || pixels == nullptr)
+        return fail(kInvalidArgument, "NULL pointer with a non-empty image");
+    if (pitch < bpp * (uint64_t)width)
+        return fail(kInvalidArgument, "pitch is smaller than the bytes of a pixel row");
+    if (pitch % bpp != 0 || reinterpret_cast<uintptr_t>(pixels) % bpp != 0)
+        return fail(kInvalidArgument, "pitch and the pixel pointer must be multiples of the bytes per pixel");
     return kOk;
 }
 
@@ -114,6 +136,73 @@ int32_t dxtlt_untransform_decode_image(int32_t format, const uint8_t* transforme
     const dxtlt::Settings s{decorrelation_mode, split_alpha_endpoints, split_colour_endpoints};
     HIP_TRY(dxtlt::launch_untransform_decode_image(static_cast<dxtlt::Format>(format), s, d_in, total_blocks, first_block,
                                                    dxtlt::make_image_sink(d_out, d_pitch, width, height), st),
+            "kernel launch");
+    HIP_TRY(hipMemcpy2DAsync(pixels, pitch, d_out, d_pitch, row_bytes, height, hipMemcpyDeviceToHost, st), "D2H copy");
+    HIP_TRY(hipStreamSynchronize(st), "stream synchronize");
+    return kOk;
+}
+
+int32_t dxtlt_decode_channel_image_device(int32_t format, const void* d_blocks, uint32_t width, uint32_t height, void* d_pixels,
+                                          uint64_t pitch, void* hip_stream)
+{
+    if (int32_t rc = check_channel_format(format); rc != kOk)
+        return rc;
+    if (width == 0 || height == 0)
+        return kOk;
+    if (int32_t rc = check_channel_image(format, d_blocks, d_pixels, width, pitch); rc != kOk)
+        return rc;
+    HIP_TRY(dxtlt::launch_decode_channel_image(format, d_blocks,
+                                               dxtlt::make_image_sink(d_pixels, pitch, width, height, (uint32_t)channel_bpp(format)),
+                                               static_cast<hipStream_t>(hip_stream)),
+            "kernel launch");
+    return kOk;
+}
+
+int32_t dxtlt_untransform_decode_channel_image_device(int32_t format, const void* d_transformed, uint64_t total_blocks,
+                                                      uint64_t first_block, uint32_t width, uint32_t height, bool split_endpoints,
+                                                      void* d_pixels, uint64_t pitch, void* hip_stream)
+{
+    if (int32_t rc = check_channel_format(format); rc != kOk)
+        return rc;
+    if (width == 0 || height == 0)
+        return kOk;
+    if (int32_t rc = check_channel_image(format, d_transformed, d_pixels, width, pitch); rc != kOk)
+        return rc;
+    if (int32_t rc = check_range(0, total_blocks, first_block, blocks_of(width, height)); rc != kOk)
+        return rc;
+    HIP_TRY(dxtlt::launch_untransform_decode_channel_image(
+                static_cast<dxtlt::Format>(format), split_endpoints, d_transformed, total_blocks, first_block,
+                dxtlt::make_image_sink(d_pixels, pitch, width, height, (uint32_t)channel_bpp(format)), static_cast<hipStream_t>(hip_stream)),
+            "kernel launch");
+    return kOk;
+}
+
+int32_t dxtlt_untransform_decode_channel_image(int32_t format, const uint8_t* transformed, size_t len, uint64_t first_block,
+                                               uint32_t width, uint32_t height, bool split_endpoints, uint8_t* pixels, uint64_t pitch)
+{
+    if (int32_t rc = check_channel_format(format); rc != kOk)
+        return rc;
+    if (width == 0 || height == 0)
+        return kOk;
+    if (int32_t rc = check_channel_image(format, transformed, pixels, width, pitch); rc != kOk)
+        return rc;
+    const uint64_t bs = format == 4 ? 8 : 16, total_blocks = len / bs;
+    if (int32_t rc = check_range(0, total_blocks, first_block, blocks_of(width, height)); rc != kOk)
+        return rc;
+    if (len % bs != 0)
+        return fail(kInvalidLength, "len is not a multiple of the block size");
+
+    // as dxtlt_untransform_decode_image: one upload, the device call into rows a multiple of 16 bytes apart, one download of the rows
+    const uint64_t bpp = channel_bpp(format), row_bytes = bpp * (uint64_t)width, d_pitch = (row_bytes + 15) & ~(uint64_t)15;
+    const uint64_t need = std::max<uint64_t>(len, d_pitch * height);
+    void *d_in = nullptr, *d_out = nullptr;
+    hipStream_t st = nullptr;
+    if (int32_t rc = dxtlt_host::acquire_staging((size_t)need, &d_in, &d_out, &st); rc != kOk)
+        return rc;
+    HIP_TRY(hipMemcpyAsync(d_in, transformed, len, hipMemcpyHostToDevice, st), "H2D copy");
+    HIP_TRY(dxtlt::launch_untransform_decode_channel_image(static_cast<dxtlt::Format>(format), split_endpoints, d_in, total_blocks,
+                                                           first_block,
+                                                           dxtlt::make_image_sink(d_out, d_pitch, width, height, (uint32_t)bpp), st),
             "kernel launch");
     HIP_TRY(hipMemcpy2DAsync(pixels, pitch, d_out, d_pitch, row_bytes, height, hipMemcpyDeviceToHost, st), "D2H copy");
     HIP_TRY(hipStreamSynchronize(st), "stream synchronize");

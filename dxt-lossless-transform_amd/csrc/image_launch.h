@@ -5,11 +5,16 @@
 
 namespace dxtlt {
 
-// fmt = 1, 2, 3.  Both enqueue on `stream` only, allocate nothing and do not synchronise.
+// fmt = 1, 2, 3 and an RGBA8888 image.  Both enqueue on `stream` only, allocate nothing and do not synchronise.
 // blocks: ceil(width / 4) * ceil(height / 4) blocks in block order, any alignment
 hipError_t launch_decode_image(int fmt, const void* blocks, const ImageSink& img, hipStream_t stream);
 // soa: byte 0 of a transformed buffer of `total_blocks`; the image is its blocks [first_block, first_block + image blocks)
 hipError_t launch_untransform_decode_image(Format fmt, const Settings& s, const void* soa, uint64_t total_blocks,
                                            uint64_t first_block, const ImageSink& img, hipStream_t stream);
+
+// The same for fmt = 4, 5 and an image of 1 / 2 bytes per pixel (img.bpp); one setting, split_endpoints
+hipError_t launch_decode_channel_image(int fmt, const void* blocks, const ImageSink& img, hipStream_t stream);
+hipError_t launch_untransform_decode_channel_image(Format fmt, bool split_endpoints, const void* soa, uint64_t total_blocks,
+                                                   uint64_t first_block, const ImageSink& img, hipStream_t stream);
 
 }  // namespace dxtlt

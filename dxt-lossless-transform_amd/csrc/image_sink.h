@@ -1,7 +1,8 @@
-// image_sink.h -- where the sixteen pixels of a decoded block go in a row-major RGBA8888 image (host and device code; the
-// tests build it for the host).  The image is width x height pixels, pixel (x, y) at pixels + y * pitch + 4 * x; its blocks
-// are numbered row-major over blocks_per_row = ceil(width / 4) columns and ceil(height / 4) rows.  A block of the last
-// column or row may reach over the image's edge: the columns and rows that do not exist are never written.
+// image_sink.h -- where the sixteen pixels of a decoded block go in a row-major image of bpp bytes per pixel: 4 (RGBA8888, the
+// default), 1 (R8, BC4) or 2 (RG8, BC5).  Host and device code; the tests build it for the host.  The image is width x height
+// pixels, pixel (x, y) at pixels + y * pitch + bpp * x; its blocks are numbered row-major over blocks_per_row = ceil(width / 4)
+// columns and ceil(height / 4) rows.  A block of the last column or row may reach over the image's edge: the columns and rows
+// that do not exist are never written.
 #pragma once
 #include <stdint.h>
 
@@ -21,11 +22,12 @@ struct ImageSink {
     uint64_t pitch;           // bytes from one pixel row to the next
     uint64_t blocks_per_row;  // ceil(width / 4)
     uint32_t width, height;   // pixels
+    uint32_t bpp;             // bytes per pixel
 };
 
-inline ImageSink make_image_sink(void* pixels, uint64_t pitch, uint32_t width, uint32_t height)
+inline ImageSink make_image_sink(void* pixels, uint64_t pitch, uint32_t width, uint32_t height, uint32_t bpp = 4)
 {
-    return ImageSink{static_cast<uint8_t*>(pixels), pitch, ((uint64_t)width + 3) / 4, width, height};
+    return ImageSink{static_cast<uint8_t*>(pixels), pitch, ((uint64_t)width + 3) / 4, width, height, bpp};
 }
 
 // blocks of the image
@@ -38,9 +40,12 @@ struct BlockPlace {
     uint32_t rows;     // 1..4: the same for its pixel rows
 };
 
-// block `b` < image_blocks(s)
+// block `b` < image_blocks(s).  BPP: the bytes per pixel when the caller knows them at compile time (the kernels, whose format
+// fixes them), 0 = s.bpp.
+template <int BPP = 0>
 __host__ __device__ inline BlockPlace place_block(const ImageSink& s, uint64_t b)
 {
+    const uint32_t block_row_bytes = 4u * (BPP != 0 ? (uint32_t)BPP : s.bpp);
     BlockPlace p;
     // (an image of 2^32 blocks or more is 64 Gpixel: the 64-bit division is for completeness)
     if ((b >> 32) == 0)
@@ -48,7 +53,7 @@ __host__ __device__ inline BlockPlace place_block(const ImageSink& s, uint64_t b
     else
         p.by = (uint32_t)(b / s.blocks_per_row);
     p.bx = (uint32_t)(b - (uint64_t)p.by * s.blocks_per_row);
-    p.offset = (uint64_t)p.by * 4u * s.pitch + (uint64_t)p.bx * 16u;
+    p.offset = (uint64_t)p.by * 4u * s.pitch + (uint64_t)p.bx * block_row_bytes;
     const uint32_t left_x = s.width - 4u * p.bx, left_y = s.height - 4u * p.by;
     p.cols = left_x < 4u ? left_x : 4u;
     p.rows = left_y < 4u ? left_y : 4u;

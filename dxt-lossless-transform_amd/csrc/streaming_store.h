@@ -28,4 +28,15 @@ __device__ __forceinline__ void store_streaming16(void* p, streaming_u32x4 v)
     asm volatile("global_store_dwordx4 %0, %1, off sc1 nt\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
 }
 
+// The 8-byte form, for lanes that own 8 consecutive bytes of a row (image_kernels.hip: the pixel rows of BC4 / BC5 blocks).  A
+// wave instruction then writes 512 consecutive bytes; on 16384 x 16384 R8 / RG8 images that ran at 0.81 of peak, the rate of the
+// 16-byte form in 1 KiB runs (profiles/channel_image_bench.json).  A store of 64 bits reads its data registers at issue: no
+// wait states behind it.
+typedef uint32_t streaming_u32x2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ void store_streaming8(void* p, streaming_u32x2 v)
+{
+    asm volatile("global_store_dwordx2 %0, %1, off sc1 nt" ::"v"(p), "v"(v) : "memory");
+}
+
 }  // namespace dxtlt

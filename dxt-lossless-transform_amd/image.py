@@ -1,10 +1,14 @@
-"""BC1 / BC2 / BC3 blocks -> a row-major RGBA8888 image, over include/dxtlt_image.h (docs/IMAGE_DECODE.md).
+"""BC1 / BC2 / BC3 blocks -> a row-major RGBA8888 image and BC4 / BC5 blocks -> a row-major R8 / RG8 image, over
+include/dxtlt_image.h (docs/IMAGE_DECODE.md).
 
 ``decode_image`` decodes a block array in block order; ``untransform_decode_image`` decodes a block range of a TRANSFORMED
 buffer in one kernel (the untransformed blocks never touch memory); ``mip_level`` says which range a mip level is.  Pixel
 (x, y) is the bytes r, g, b, a at ``y * pitch + 4 * x`` of the output; nothing else of the output is written.
 1-D ``uint8`` numpy / bytes-like host buffers or CUDA ``torch.uint8`` tensors (torch's current stream).  No CPU fallback:
-``decode_image`` takes device tensors only, ``untransform_decode_image`` both kinds."""
+``decode_image`` takes device tensors only, ``untransform_decode_image`` both kinds.
+
+``decode_channel_image`` and ``untransform_decode_channel_image`` are the same two calls for ``"bc4"`` / ``"bc5"``: a pixel is
+1 / 2 bytes (r, or r, g) at ``y * pitch + bpp * x``, the default pitch ``bpp * width``, the one setting ``split_endpoints``."""
 from __future__ import annotations
 
 import ctypes as C
@@ -15,6 +19,9 @@ from . import _lib
 
 _FMT = {"bc1": 1, "bc2": 2, "bc3": 3}
 _BLOCK = {"bc1": 8, "bc2": 16, "bc3": 16}
+_CHANNEL_FMT = {"bc4": 4, "bc5": 5}
+_CHANNEL_BLOCK = {"bc4": 8, "bc5": 16}
+_CHANNEL_BPP = {"bc4": 1, "bc5": 2}
 _declared = False
 
 
@@ -28,8 +35,12 @@ def _l():
         l.dxtlt_untransform_decode_image.argtypes = [i32, vp, C.c_size_t, u64, u32, u32, u8, b, b, vp, u64]
         l.dxtlt_image_mip_level.argtypes = [u32, u32, u32, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(u64), C.POINTER(u64),
                                             C.POINTER(u64)]
+        l.dxtlt_decode_channel_image_device.argtypes = [i32, vp, u32, u32, vp, u64, vp]
+        l.dxtlt_untransform_decode_channel_image_device.argtypes = [i32, vp, u64, u64, u32, u32, b, vp, u64, vp]
+        l.dxtlt_untransform_decode_channel_image.argtypes = [i32, vp, C.c_size_t, u64, u32, u32, b, vp, u64]
         for f in (l.dxtlt_decode_image_device, l.dxtlt_untransform_decode_image_device, l.dxtlt_untransform_decode_image,
-                  l.dxtlt_image_mip_level):
+                  l.dxtlt_image_mip_level, l.dxtlt_decode_channel_image_device, l.dxtlt_untransform_decode_channel_image_device,
+                  l.dxtlt_untransform_decode_channel_image):
             f.restype = i32
         _declared = True
     return l
@@ -56,13 +67,13 @@ def mip_level(width: int, height: int, mip_count: int, level: int):
     return w.value, h.value, first.value, num.value, total.value
 
 
-def _output(src, width, height, out, pitch):
+def _output(src, width, height, out, pitch, bpp=4):
     """the output buffer (a new one on the source's side when ``out`` is None), its _Buf and the pitch"""
     from . import OutputBufferTooSmall, _Buf
 
     if pitch is None:
-        pitch = 4 * width
-    need = pitch * (height - 1) + 4 * width if width and height else 0
+        pitch = bpp * width
+    need = pitch * (height - 1) + bpp * width if width and height else 0
     if out is None:
         if src.device is None:
             out = np.zeros(pitch * height, dtype=np.uint8)
@@ -122,4 +133,53 @@ def untransform_decode_image(fmt: str, transformed, width: int, height: int, *, 
     with torch.cuda.device(src.device):
         _check(l.dxtlt_untransform_decode_image_device(_FMT[fmt], src.ptr, total_blocks, first_block, width, height, mode, sa, sc,
                                                        dst.ptr, pitch, torch.cuda.current_stream(src.device).cuda_stream))
+    return out
+
+
+def decode_channel_image(fmt: str, blocks, width: int, height: int, out=None, pitch=None):
+    """``fmt``: ``"bc4"`` / ``"bc5"``.  ``blocks``: ceil(width / 4) * ceil(height / 4) blocks in block order, a CUDA tensor.
+    Returns ``out`` (a new tensor of ``pitch * height`` bytes when None); ``pitch`` defaults to ``bpp * width``."""
+    from . import InvalidLength, _Buf
+
+    code, bpp = _CHANNEL_FMT[fmt], _CHANNEL_BPP[fmt]
+    src = _Buf(blocks, False)
+    if src.device is None:
+        raise TypeError("decode_channel_image takes device tensors (the library has no host-pointer form of it)")
+    if src.nbytes < image_blocks(width, height) * _CHANNEL_BLOCK[fmt]:
+        raise InvalidLength(src.nbytes)
+    out, dst, pitch = _output(src, width, height, out, pitch, bpp)
+    import torch
+
+    with torch.cuda.device(src.device):
+        _check(_l().dxtlt_decode_channel_image_device(code, src.ptr, width, height, dst.ptr, pitch,
+                                                      torch.cuda.current_stream(src.device).cuda_stream))
+    return out
+
+
+def untransform_decode_channel_image(fmt: str, transformed, width: int, height: int, *, first_block: int = 0, total_blocks=None,
+                                     split_endpoints: bool, out=None, pitch=None):
+    """``fmt``: ``"bc4"`` / ``"bc5"``.  ``transformed``: the WHOLE transformed buffer of ``total_blocks`` blocks (default: its
+    length); the image is its blocks [first_block, first_block + ceil(width / 4) * ceil(height / 4)).  Returns ``out``."""
+    from . import InvalidLength, _Buf
+
+    code, bs = _CHANNEL_FMT[fmt], _CHANNEL_BLOCK[fmt]
+    src = _Buf(transformed, False)
+    if src.nbytes % bs != 0:
+        raise InvalidLength(src.nbytes)
+    if total_blocks is None:
+        total_blocks = src.nbytes // bs
+    if total_blocks * bs > src.nbytes:
+        raise InvalidLength(src.nbytes)
+    out, dst, pitch = _output(src, width, height, out, pitch, _CHANNEL_BPP[fmt])
+    l = _l()
+    if src.device is None:
+        _check(l.dxtlt_untransform_decode_channel_image(code, src.ptr, total_blocks * bs, first_block, width, height,
+                                                        bool(split_endpoints), dst.ptr, pitch))
+        return out
+    import torch
+
+    with torch.cuda.device(src.device):
+        _check(l.dxtlt_untransform_decode_channel_image_device(code, src.ptr, total_blocks, first_block, width, height,
+                                                               bool(split_endpoints), dst.ptr, pitch,
+                                                               torch.cuda.current_stream(src.device).cuda_stream))
     return out

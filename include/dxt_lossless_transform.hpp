@@ -774,5 +774,26 @@ inline void untransform_decode_image(int32_t format, const uint8_t* transformed,
                                                         split_alpha_endpoints, split_colour_endpoints, pixels, pitch));
 }
 
+// ADDITIVE: BC4 / BC5 blocks -> a row-major R8 / RG8 image (dxtlt_image.h, the *_channel_image calls).  format = 4, 5; pixel
+// (x, y) = the byte r, or the bytes r, g, at pixels + y * pitch + bpp * x; image_mip_level serves these formats as it stands.
+inline void decode_channel_image_device(int32_t format, const void* d_blocks, uint32_t width, uint32_t height, void* d_pixels,
+                                        uint64_t pitch, void* hip_stream)
+{
+    detail::check_device(dxtlt_decode_channel_image_device(format, d_blocks, width, height, d_pixels, pitch, hip_stream));
+}
+inline void untransform_decode_channel_image_device(int32_t format, const void* d_transformed, uint64_t total_blocks,
+                                                    uint64_t first_block, uint32_t width, uint32_t height, bool split_endpoints,
+                                                    void* d_pixels, uint64_t pitch, void* hip_stream)
+{
+    detail::check_device(dxtlt_untransform_decode_channel_image_device(format, d_transformed, total_blocks, first_block, width, height,
+                                                                       split_endpoints, d_pixels, pitch, hip_stream));
+}
+inline void untransform_decode_channel_image(int32_t format, const uint8_t* transformed, size_t len, uint64_t first_block,
+                                             uint32_t width, uint32_t height, bool split_endpoints, uint8_t* pixels, uint64_t pitch)
+{
+    detail::check_device(dxtlt_untransform_decode_channel_image(format, transformed, len, first_block, width, height, split_endpoints,
+                                                                pixels, pitch));
+}
+
 }  // namespace api
 }  // namespace dxt_lossless_transform
