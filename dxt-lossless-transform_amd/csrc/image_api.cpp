@@ -1,5 +1,5 @@
 // image_api.cpp -- C ABI of the image decoders (include/dxtlt_image.h): BC1 / BC2 / BC3 -> RGBA8888, BC4 / BC5 -> R8 / RG8; kernels
-// in image_kernels.hip.  Every argument is checked before a device is touched.
+// in image_kernels.hip and, for several images of one buffer, image_regions_kernels.hip.  Every argument is checked before a device is touched.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -18,6 +18,8 @@ namespace {
 
 inline uint64_t block_bytes_of(int32_t fmt) { return fmt == 1 ? 8 : 16; }
 inline uint64_t blocks_of(uint32_t width, uint32_t height) { return (((uint64_t)width + 3) / 4) * (((uint64_t)height + 3) / 4); }
+// side `v` of a texture at mip level k
+inline uint32_t mip_dim(uint32_t v, uint32_t k) { return k < 32 && (v >> k) > 0 ? v >> k : 1u; }
 
 int32_t check_format(int32_t fmt)
 {
@@ -67,6 +69,78 @@ int32_t check_channel_image(int32_t fmt, const void* blocks, const void* pixels,
     if (pitch % bpp != 0 || reinterpret_cast<uintptr_t>(pixels) % bpp != 0)
         return fail(kInvalidArgument, "pitch and the pixel pointer must be multiples of the bytes per pixel");
     return kOk;
+}
+
+
+// ---- several images of one buffer --------------------------------------------------------------------------------------
+inline uint64_t bpp_of(int32_t fmt) { return fmt <= 3 ? 4 : channel_bpp(fmt); }
+inline bool empty_region(const DxtltImageRegion& r) { return r.width == 0 || r.height == 0; }
+
+int32_t check_any_format(int32_t fmt)
+{
+    if (fmt < 1 || fmt > 5)
+        return fail(kInvalidArgument, "format must be 1 (BC1) .. 5 (BC5)");
+    return kOk;
+}
+
+// The checks of the image-region calls behind the format, in the documented order; *nothing = there is no non-empty region
+// (DXTLT_OK, nothing to do).  `mode`: the decorrelation mode, 0 for the call that has none.
+int32_t check_regions(int32_t fmt, const void* buffer, uint64_t total_blocks, const DxtltImageRegion* regions, size_t count,
+                      uint8_t mode, bool* nothing)
+{
+    *nothing = true;
+    if (count == 0)
+        return kOk;
+    if (regions == nullptr)
+        return fail(kInvalidArgument, "NULL regions pointer");
+    for (size_t i = 0; i < count && *nothing; ++i)
+        *nothing = empty_region(regions[i]);
+    if (*nothing)
+        return kOk;
+    if (buffer == nullptr)
+        return fail(kInvalidArgument, "NULL buffer with a non-empty region");
+    const uint64_t bpp = bpp_of(fmt), multiple = fmt <= 3 ? 4 : bpp;
+    uint64_t end = 0;   // of the previous non-empty region
+    for (size_t i = 0; i < count; ++i) {
+        const DxtltImageRegion& r = regions[i];
+        if (empty_region(r))
+            continue;
+        if (r.pixels == nullptr)
+            return fail(kInvalidArgument, "NULL pixels pointer of a non-empty region");
+        if (r.pitch < bpp * (uint64_t)r.width)
+            return fail(kInvalidArgument, "a region's pitch is smaller than the bytes of a pixel row");
+        if (r.pitch % multiple != 0 || reinterpret_cast<uintptr_t>(r.pixels) % multiple != 0)
+            return fail(kInvalidArgument, "a region's pitch and pixel pointer must be multiples of 4 (BC1 - BC3) or of the bytes per pixel");
+        if (r.first_block > total_blocks || blocks_of(r.width, r.height) > total_blocks - r.first_block)
+            return fail(kInvalidArgument, "first_block + blocks of a region exceeds total_blocks");
+        if (r.first_block < end)
+            return fail(kInvalidArgument, "regions must come in ascending block order and must not overlap");
+        end = r.first_block + blocks_of(r.width, r.height);
+    }
+    if (fmt <= 3 && mode > 3)
+        return fail(kInvalidArgument, "decorrelation_mode must be 0..3");
+    return kOk;
+}
+
+// The non-empty regions in groups of at most DXTLT_IMAGE_REGIONS_PER_LAUNCH consecutive ones: sink_of(i) is region i's image,
+// launch(table) enqueues one group
+template <typename SINK_OF, typename LAUNCH>
+hipError_t for_each_region_group(const DxtltImageRegion* regions, size_t count, const SINK_OF& sink_of, const LAUNCH& launch)
+{
+    static_assert(DXTLT_IMAGE_REGIONS_PER_LAUNCH == dxtlt::kImageRegionsPerLaunch, "the header's constant is the kernels'");
+    dxtlt::ImageRegionTable tab;
+    dxtlt::clear_regions(tab);
+    for (size_t i = 0; i < count; ++i) {
+        if (empty_region(regions[i]))
+            continue;
+        dxtlt::append_region(tab, sink_of(i), regions[i].first_block);
+        if (tab.count == (uint32_t)dxtlt::kImageRegionsPerLaunch) {
+            if (hipError_t e = launch(tab); e != hipSuccess)
+                return e;
+            dxtlt::clear_regions(tab);
+        }
+    }
+    return tab.count != 0 ? launch(tab) : hipSuccess;
 }
 
 }  // namespace
@@ -214,7 +288,7 @@ int32_t dxtlt_image_mip_level(uint32_t width, uint32_t height, uint32_t mip_coun
 {
     if (width == 0 || height == 0 || mip_count == 0 || level >= mip_count)
         return fail(kInvalidArgument, "mip level: zero width, height or mip_count, or level >= mip_count");
-    auto dim = [](uint32_t v, uint32_t k) { return k < 32 && (v >> k) > 0 ? v >> k : 1u; };
+    const auto dim = mip_dim;
     uint64_t before = 0, total = 0;
     // levels 32 and up are 1 x 1 = one block each, whatever the size
     const uint32_t walked = mip_count < 32 ? mip_count : 32;
@@ -237,6 +311,120 @@ int32_t dxtlt_image_mip_level(uint32_t width, uint32_t height, uint32_t mip_coun
         *num_blocks = blocks_of(dim(width, level), dim(height, level));
     if (total_blocks)
         *total_blocks = total;
+    return kOk;
+}
+
+int32_t dxtlt_untransform_decode_images_device(int32_t format, const void* d_transformed, uint64_t total_blocks,
+                                               const DxtltImageRegion* regions, size_t region_count, uint8_t decorrelation_mode,
+                                               bool split_alpha_endpoints, bool split_colour_endpoints, void* hip_stream)
+{
+    if (int32_t rc = check_any_format(format); rc != kOk)
+        return rc;
+    bool nothing = true;
+    if (int32_t rc = check_regions(format, d_transformed, total_blocks, regions, region_count, decorrelation_mode, &nothing);
+        rc != kOk || nothing)
+        return rc;
+    const dxtlt::Settings s{decorrelation_mode, split_alpha_endpoints, split_colour_endpoints};
+    const uint32_t bpp = (uint32_t)bpp_of(format);
+    HIP_TRY(for_each_region_group(
+                regions, region_count,
+                [&](size_t i) { return dxtlt::make_image_sink(regions[i].pixels, regions[i].pitch, regions[i].width, regions[i].height, bpp); },
+                [&](const dxtlt::ImageRegionTable& tab) {
+                    return dxtlt::launch_untransform_decode_image_regions(static_cast<dxtlt::Format>(format), s, d_transformed,
+                                                                          total_blocks, tab, static_cast<hipStream_t>(hip_stream));
+                }),
+            "kernel launch");
+    return kOk;
+}
+
+int32_t dxtlt_decode_images_device(int32_t format, const void* d_blocks, uint64_t total_blocks, const DxtltImageRegion* regions,
+                                   size_t region_count, void* hip_stream)
+{
+    if (int32_t rc = check_any_format(format); rc != kOk)
+        return rc;
+    bool nothing = true;
+    if (int32_t rc = check_regions(format, d_blocks, total_blocks, regions, region_count, 0, &nothing); rc != kOk || nothing)
+        return rc;
+    const uint32_t bpp = (uint32_t)bpp_of(format);
+    HIP_TRY(for_each_region_group(
+                regions, region_count,
+                [&](size_t i) { return dxtlt::make_image_sink(regions[i].pixels, regions[i].pitch, regions[i].width, regions[i].height, bpp); },
+                [&](const dxtlt::ImageRegionTable& tab) {
+                    return dxtlt::launch_decode_image_regions(format, d_blocks, total_blocks, tab, static_cast<hipStream_t>(hip_stream));
+                }),
+            "kernel launch");
+    return kOk;
+}
+
+int32_t dxtlt_untransform_decode_images(int32_t format, const uint8_t* transformed, size_t len, const DxtltImageRegion* regions,
+                                        size_t region_count, uint8_t decorrelation_mode, bool split_alpha_endpoints,
+                                        bool split_colour_endpoints)
+{
+    if (int32_t rc = check_any_format(format); rc != kOk)
+        return rc;
+    const uint64_t bs = format == 1 || format == 4 ? 8 : 16, total_blocks = len / bs;
+    bool nothing = true;
+    if (int32_t rc = check_regions(format, transformed, total_blocks, regions, region_count, decorrelation_mode, &nothing);
+        rc != kOk || nothing)
+        return rc;
+    if (len % bs != 0)
+        return fail(kInvalidLength, "len is not a multiple of the block size");
+
+    // one upload of the transformed buffer, the device call into staging -- region after region, every base a multiple of 16
+    // and its rows a multiple of 16 bytes apart -- and one download of the rows per region
+    const uint64_t bpp = bpp_of(format);
+    auto staged_pitch = [&](const DxtltImageRegion& r) { return (bpp * (uint64_t)r.width + 15) & ~(uint64_t)15; };
+    uint64_t out_bytes = 0;
+    for (size_t i = 0; i < region_count; ++i)
+        if (!empty_region(regions[i]))
+            out_bytes += staged_pitch(regions[i]) * regions[i].height;
+    void *d_in = nullptr, *d_out = nullptr;
+    hipStream_t st = nullptr;
+    if (int32_t rc = dxtlt_host::acquire_staging((size_t)std::max<uint64_t>(len, out_bytes), &d_in, &d_out, &st); rc != kOk)
+        return rc;
+    HIP_TRY(hipMemcpyAsync(d_in, transformed, len, hipMemcpyHostToDevice, st), "H2D copy");
+    const dxtlt::Settings s{decorrelation_mode, split_alpha_endpoints, split_colour_endpoints};
+    uint64_t at = 0;   // the regions are visited in list order, here and in the download below
+    HIP_TRY(for_each_region_group(
+                regions, region_count,
+                [&](size_t i) {
+                    const dxtlt::ImageSink img = dxtlt::make_image_sink(static_cast<uint8_t*>(d_out) + at, staged_pitch(regions[i]),
+                                                                        regions[i].width, regions[i].height, (uint32_t)bpp);
+                    at += staged_pitch(regions[i]) * regions[i].height;
+                    return img;
+                },
+                [&](const dxtlt::ImageRegionTable& tab) {
+                    return dxtlt::launch_untransform_decode_image_regions(static_cast<dxtlt::Format>(format), s, d_in, total_blocks, tab, st);
+                }),
+            "kernel launch");
+    at = 0;
+    for (size_t i = 0; i < region_count; ++i) {
+        const DxtltImageRegion& r = regions[i];
+        if (empty_region(r))
+            continue;
+        HIP_TRY(hipMemcpy2DAsync(r.pixels, r.pitch, static_cast<uint8_t*>(d_out) + at, staged_pitch(r), bpp * (uint64_t)r.width, r.height,
+                                 hipMemcpyDeviceToHost, st),
+                "D2H copy");
+        at += staged_pitch(r) * r.height;
+    }
+    HIP_TRY(hipStreamSynchronize(st), "stream synchronize");
+    return kOk;
+}
+
+int32_t dxtlt_image_mip_chain(uint32_t width, uint32_t height, uint32_t mip_count, uint64_t first_block, DxtltImageRegion* regions,
+                              uint64_t* total_blocks)
+{
+    if (width == 0 || height == 0 || mip_count == 0 || regions == nullptr)
+        return fail(kInvalidArgument, "mip chain: zero width, height or mip_count, or NULL regions");
+    uint64_t at = first_block;
+    for (uint32_t k = 0; k < mip_count; ++k) {
+        regions[k].first_block = at;
+        regions[k].width = mip_dim(width, k);
+        regions[k].height = mip_dim(height, k);
+        at += blocks_of(regions[k].width, regions[k].height);
+    }
+    if (total_blocks)
+        *total_blocks = at;
     return kOk;
 }
 

@@ -14,57 +14,13 @@
 // bpermute uses the LDS crossbar only, so bank conflicts do not arise).  A wave that straddles a block row writes two runs.
 // Stores: `sc1 nt` streaming stores (streaming_store.h) when the pixel pointer and the pitch are multiples of 16, plain
 // 4-byte aligned vector stores otherwise; a block clipped by the image's right or bottom edge is written pixel by pixel.
-#include "bcn_decode.h"
-#include "bcn_device.h"
 #include "image_launch.h"
+#include "image_planned_launch.h"
+#include "image_store.h"
 #include "launch_grid.h"
 
 namespace dxtlt {
 namespace {
-
-typedef uint32_t u32x4_align4 __attribute__((ext_vector_type(4), aligned(4)));
-typedef uint32_t u32x4_align8 __attribute__((ext_vector_type(4), aligned(8)));
-
-// the sixteen pixels of block `b` of the image into their rows
-__device__ __forceinline__ void store_block_pixels(const ImageSink& img, uint64_t b, const uint32_t (&px)[16])
-{
-    const BlockPlace p = place_block<4>(img, b);
-    const bool aligned16 = ((reinterpret_cast<uintptr_t>(img.pixels) | img.pitch) & 15) == 0;   // uniform
-    if (p.cols == 4 && p.rows == 4) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            uint8_t* row = block_row(img, p, r);
-            const u32x4 v = u32x4{px[4 * r], px[4 * r + 1], px[4 * r + 2], px[4 * r + 3]};
-            if (aligned16)
-                store_streaming16(row, v);
-            else
-                *reinterpret_cast<u32x4_align4*>(row) = v;
-        }
-    } else {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            uint32_t* row = reinterpret_cast<uint32_t*>(block_row(img, p, r));
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-                if ((uint32_t)r < p.rows && (uint32_t)c < p.cols)
-                    row[c] = px[4 * r + c];
-        }
-    }
-}
-
-template <int FMT>
-__device__ __forceinline__ void decode_and_store(const ImageSink& img, uint64_t b, uint32_t q0, uint32_t q1, uint32_t q2, uint32_t q3)
-{
-    const uint32_t q[4] = {q0, q1, q2, q3};
-    uint32_t px[16];
-    decode_block_px<FMT>(q, px);
-    store_block_pixels(img, b, px);
-}
-
-__device__ __forceinline__ uint32_t from_lane(uint32_t v, int lane)
-{
-    return (uint32_t)__builtin_amdgcn_ds_bpermute(lane * 4, (int)v);
-}
 
 // The sink of the inverse tiles (bcn_device.h, AosSink): the launch's first block is block `block0` of the image.
 struct PixelSink {
@@ -145,109 +101,6 @@ inv_tiled_shift_image(const uint8_t* __restrict__ soa_arg, PixelSink sink, uint6
 // (`sc1 nt` when they are multiples of 16, plain stores otherwise).  A lane that has not all of that writes every block for
 // itself, a row as dwords, halfwords or bytes -- the alignment the pixel pointer and the pitch have -- and a block clipped by
 // the right or bottom edge pixel by pixel.
-template <int FMT>
-struct ChannelFormat {
-    static_assert(FMT == kBc4 || FMT == kBc5, "one- and two-channel decoders exist for BC4 and BC5");
-    static constexpr int bpp = FMT == kBc4 ? 1 : 2;
-    static constexpr int per_vector = FMT == kBc4 ? 2 : 1;   // blocks in a lane's 16 bytes
-};
-
-// w[r] = the 8 bytes of pixel row r of the lane's vector (BC4: .x block 2t, .y block 2t + 1)
-template <int FMT>
-__device__ __forceinline__ void decode_channel_vector(u32x4 q, u32x2 (&w)[4])
-{
-    if constexpr (FMT == kBc4) {
-        uint32_t a[4], b[4];
-        decode_bc4_block_rows(q.x, q.y, a);
-        decode_bc4_block_rows(q.z, q.w, b);
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            w[r] = u32x2{a[r], b[r]};
-    } else {
-        const uint32_t qq[4] = {q.x, q.y, q.z, q.w};
-        uint32_t rows[4][2];
-        decode_bc5_block_rows(qq, rows);
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            w[r] = u32x2{rows[r][0], rows[r][1]};
-    }
-}
-
-// One block for itself: its row r is the low 4 * BPP bytes of rows[r]
-template <int BPP>
-__device__ __forceinline__ void store_channel_block(const ImageSink& img, const BlockPlace& p, const uint64_t (&rows)[4])
-{
-    const uintptr_t al = reinterpret_cast<uintptr_t>(img.pixels) | img.pitch;   // uniform; a block's offset in its row is a multiple of 4
-    if (p.cols == 4 && p.rows == 4) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            uint8_t* row = block_row(img, p, r);
-            if ((al & 3) == 0) {
-#pragma unroll
-                for (int i = 0; i < BPP; ++i)
-                    reinterpret_cast<uint32_t*>(row)[i] = (uint32_t)(rows[r] >> (32 * i));
-            } else if ((al & 1) == 0) {
-#pragma unroll
-                for (int i = 0; i < 2 * BPP; ++i)
-                    reinterpret_cast<uint16_t*>(row)[i] = (uint16_t)(rows[r] >> (16 * i));
-            } else if constexpr (BPP == 1) {   // (a two-byte pixel never sits at an odd address: the C ABI's checks)
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    row[i] = (uint8_t)(rows[r] >> (8 * i));
-            }
-        }
-    } else {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            uint8_t* row = block_row(img, p, r);
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-                if ((uint32_t)r < p.rows && (uint32_t)c < p.cols) {
-                    if constexpr (BPP == 1)
-                        row[c] = (uint8_t)(rows[r] >> (8 * c));
-                    else
-                        reinterpret_cast<uint16_t*>(row)[c] = (uint16_t)(rows[r] >> (16 * c));
-                }
-        }
-    }
-}
-
-// A lane for itself: the first `have` (1 .. per_vector) blocks of its vector, whose first block is block `first` of the image
-template <int FMT>
-__device__ __forceinline__ void store_channel_lane(const ImageSink& img, uint64_t first, const u32x2 (&w)[4], int have)
-{
-    constexpr int BPP = ChannelFormat<FMT>::bpp, PV = ChannelFormat<FMT>::per_vector;
-    const BlockPlace p = place_block<BPP>(img, first);
-    const uintptr_t al = reinterpret_cast<uintptr_t>(img.pixels) | img.pitch;   // uniform
-    // PV blocks from column p.bx on, whole, in this block row, their 8 bytes per pixel row on an 8-byte address
-    const bool rows8 = have == PV && (al & 7) == 0 && (p.bx & (PV - 1)) == 0 && 4 * ((uint64_t)p.bx + PV) <= img.width && p.rows == 4;
-    if (rows8) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            uint8_t* row = block_row(img, p, r);
-            if ((al & 15) == 0)
-                store_streaming8(row, w[r]);
-            else
-                *reinterpret_cast<u32x2*>(row) = w[r];
-        }
-        return;
-    }
-    if constexpr (FMT == kBc4) {
-        const uint64_t a[4] = {w[0].x, w[1].x, w[2].x, w[3].x};
-        store_channel_block<BPP>(img, p, a);
-        if (have == 2) {
-            const uint64_t b[4] = {w[0].y, w[1].y, w[2].y, w[3].y};
-            store_channel_block<BPP>(img, place_block<BPP>(img, first + 1), b);
-        }
-    } else {
-        uint64_t a[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            a[r] = ((uint64_t)w[r].y << 32) | w[r].x;
-        store_channel_block<BPP>(img, p, a);
-    }
-}
-
 // The sink of the inverse tiles for BC4 / BC5 (bcn_device.h, AosSink): the launch's first block is block `block0` of the image.
 struct ChannelSink {
     ImageSink img;
@@ -389,12 +242,7 @@ hipError_t decode_channel_image_fmt(const void* blocks, const ImageSink& img, hi
     return hipGetLastError();
 }
 
-// ---- host-side dispatch of the fused kernels -------------------------------------------------------------------------
-template <typename SINK>
-struct ImageKernelsOf {
-    void (*tiled)(const uint8_t*, SINK, uint64_t, uint64_t);             // default_tile_threads(fmt, true) lanes
-    void (*shifted)(const uint8_t*, SINK, uint64_t, uint64_t, Shifts);   // shift_tile_threads(fmt) lanes
-};
+// ---- host-side dispatch of the fused kernels (ImageKernelsOf, launch_planned_image: image_planned_launch.h) -------------
 using ImageKernels = ImageKernelsOf<PixelSink>;
 
 template <int FMT, int VARIANT, bool SA, bool SC>
@@ -435,55 +283,6 @@ ImageKernelsOf<ChannelSink> pick_channel_kernels(bool split_endpoints)
     return {inv_tiled_channel_image<FMT, false, TH>, inv_tiled_shift_channel_image<FMT, false, SH>};
 }
 
-constexpr uint64_t kMaxBlocksPerImageLaunch = 1ull << 31;   // launch_transform's sub-ranges
-
-// The launches of the inverse transform's own plan for blocks [first_block, first_block + n) -- `s` the format's effective
-// settings -- with the kernels `ks`, whose sink is SINK{img, the launch's first block in the image}
-template <typename SINK>
-hipError_t launch_planned_image(Format fmt, const Settings& s, const ImageKernelsOf<SINK>& ks, const void* soa, uint64_t total_blocks,
-                                uint64_t first_block, uint64_t n, const ImageSink& img, hipStream_t stream)
-{
-    const auto* soa8 = static_cast<const uint8_t*>(soa);
-    for (uint64_t off = 0; off < n; off += kMaxBlocksPerImageLaunch) {
-        const Range sub{total_blocks, first_block + off, std::min(kMaxBlocksPerImageLaunch, n - off)};
-        // the inverse transform's own plan for the sub-range (the block side's address plays no part in it): aligned tiles
-        // and an edge tile behind them, or shifted tiles with theirs
-        constexpr int kCap = 8;
-        DebugPlannedLaunch plan[kCap];
-        const int launches = debug_plan_transform(fmt, true, s, reinterpret_cast<uintptr_t>(soa), 0, sub, nullptr, plan, kCap);
-        if (launches < 0 || launches > kCap)
-            return hipErrorInvalidValue;
-        for (int i = 0; i < launches; ++i) {
-            const DebugPlannedLaunch& l = plan[i];
-            const SINK sink{img, off + l.aos_offset / (uint64_t)fmt_block(fmt)};
-            if (l.kind == 0) {
-                if (l.threads != default_tile_threads(fmt, true))
-                    return hipErrorInvalidValue;
-                hipLaunchKernelGGL(ks.tiled, dim3(l.workgroups), dim3(l.threads), 0, stream, soa8, sink, total_blocks, sub.first_block);
-            } else {
-                if (l.kind != 2 || l.threads != shift_tile_threads(fmt))
-                    return hipErrorInvalidValue;
-                Shifts sh{};
-                for (int k = 0; k < 6; ++k) {
-                    sh.d[k] = l.shift[k];
-                    sh.gbase[k] = l.gbase[k];
-                }
-                sh.natural = l.natural;
-                sh.halo_vecs = l.halo_vecs;
-                sh.full_tiles = l.full_tiles;
-                sh.range_blocks = l.range_blocks;
-#ifdef DXTLT_EXPERIMENTS
-                sh.xcd_remap = 1;
-#endif
-                hipLaunchKernelGGL(ks.shifted, dim3(l.workgroups), dim3(l.threads), 0, stream, soa8, sink, total_blocks, sub.first_block, sh);
-            }
-            if (hipError_t e = hipGetLastError(); e != hipSuccess)
-                return e;
-        }
-    }
-    return hipSuccess;
-}
-
 }  // namespace
 
 hipError_t launch_decode_image(int fmt, const void* blocks, const ImageSink& img, hipStream_t stream)
@@ -512,7 +311,7 @@ hipError_t launch_untransform_decode_image(Format fmt, const Settings& s_arg, co
     const ImageKernels ks = fmt == kBc1   ? pick_image_kernels<kBc1>(s.variant, false, s.split_colour)
                             : fmt == kBc2 ? pick_image_kernels<kBc2>(s.variant, false, s.split_colour)
                                           : pick_image_kernels<kBc3>(s.variant, s.split_alpha, s.split_colour);
-    return launch_planned_image(fmt, s, ks, soa, total_blocks, first_block, n, img, stream);
+    return launch_planned_image(fmt, s, ks, soa, total_blocks, first_block, n, stream, [&](uint64_t block0) { return PixelSink{img, block0}; });
 }
 
 hipError_t launch_decode_channel_image(int fmt, const void* blocks, const ImageSink& img, hipStream_t stream)
@@ -536,7 +335,7 @@ hipError_t launch_untransform_decode_channel_image(Format fmt, bool split_endpoi
         return hipErrorInvalidValue;
     const Settings s = effective_settings(fmt, Settings{0, split_endpoints, false});
     const ImageKernelsOf<ChannelSink> ks = fmt == kBc4 ? pick_channel_kernels<kBc4>(split_endpoints) : pick_channel_kernels<kBc5>(split_endpoints);
-    return launch_planned_image(fmt, s, ks, soa, total_blocks, first_block, n, img, stream);
+    return launch_planned_image(fmt, s, ks, soa, total_blocks, first_block, n, stream, [&](uint64_t block0) { return ChannelSink{img, block0}; });
 }
 
 }  // namespace dxtlt

@@ -8,7 +8,10 @@ buffer in one kernel (the untransformed blocks never touch memory); ``mip_level`
 ``decode_image`` takes device tensors only, ``untransform_decode_image`` both kinds.
 
 ``decode_channel_image`` and ``untransform_decode_channel_image`` are the same two calls for ``"bc4"`` / ``"bc5"``: a pixel is
-1 / 2 bytes (r, or r, g) at ``y * pitch + bpp * x``, the default pitch ``bpp * width``, the one setting ``split_endpoints``."""
+1 / 2 bytes (r, or r, g) at ``y * pitch + bpp * x``, the default pitch ``bpp * width``, the one setting ``split_endpoints``.
+
+``untransform_decode_images`` and ``decode_images`` write several images of one buffer in one call, for all five formats: a
+region is ``(first_block, width, height)``, and ``mip_chain`` lists the regions of a mip chain."""
 from __future__ import annotations
 
 import ctypes as C
@@ -22,7 +25,15 @@ _BLOCK = {"bc1": 8, "bc2": 16, "bc3": 16}
 _CHANNEL_FMT = {"bc4": 4, "bc5": 5}
 _CHANNEL_BLOCK = {"bc4": 8, "bc5": 16}
 _CHANNEL_BPP = {"bc4": 1, "bc5": 2}
+_ALL_FMT = {**_FMT, **_CHANNEL_FMT}
+_ALL_BLOCK = {**_BLOCK, **_CHANNEL_BLOCK}
+_ALL_BPP = {"bc1": 4, "bc2": 4, "bc3": 4, **_CHANNEL_BPP}
 _declared = False
+
+
+class ImageRegion(C.Structure):   # DxtltImageRegion, include/dxtlt_image.h
+    _fields_ = [("first_block", C.c_uint64), ("width", C.c_uint32), ("height", C.c_uint32), ("pixels", C.c_void_p),
+                ("pitch", C.c_uint64)]
 
 
 def _l():
@@ -38,6 +49,14 @@ def _l():
         l.dxtlt_decode_channel_image_device.argtypes = [i32, vp, u32, u32, vp, u64, vp]
         l.dxtlt_untransform_decode_channel_image_device.argtypes = [i32, vp, u64, u64, u32, u32, b, vp, u64, vp]
         l.dxtlt_untransform_decode_channel_image.argtypes = [i32, vp, C.c_size_t, u64, u32, u32, b, vp, u64]
+        rp = C.POINTER(ImageRegion)
+        l.dxtlt_untransform_decode_images_device.argtypes = [i32, vp, u64, rp, C.c_size_t, u8, b, b, vp]
+        l.dxtlt_decode_images_device.argtypes = [i32, vp, u64, rp, C.c_size_t, vp]
+        l.dxtlt_untransform_decode_images.argtypes = [i32, vp, C.c_size_t, rp, C.c_size_t, u8, b, b]
+        l.dxtlt_image_mip_chain.argtypes = [u32, u32, u32, u64, rp, C.POINTER(u64)]
+        for f in (l.dxtlt_untransform_decode_images_device, l.dxtlt_decode_images_device, l.dxtlt_untransform_decode_images,
+                  l.dxtlt_image_mip_chain):
+            f.restype = i32
         for f in (l.dxtlt_decode_image_device, l.dxtlt_untransform_decode_image_device, l.dxtlt_untransform_decode_image,
                   l.dxtlt_image_mip_level, l.dxtlt_decode_channel_image_device, l.dxtlt_untransform_decode_channel_image_device,
                   l.dxtlt_untransform_decode_channel_image):
@@ -183,3 +202,82 @@ def untransform_decode_channel_image(fmt: str, transformed, width: int, height: 
                                                                bool(split_endpoints), dst.ptr, pitch,
                                                                torch.cuda.current_stream(src.device).cuda_stream))
     return out
+
+
+# ---- several images of one buffer ---------------------------------------------------------------------------------------
+def mip_chain(width: int, height: int, mip_count: int, first_block: int = 0):
+    """``([(first_block, level_width, level_height), ...], total_blocks)`` of a ``width`` x ``height`` chain of ``mip_count``
+    levels whose level 0 starts at block ``first_block``; ``total_blocks`` is the block just behind the chain.  No device needed."""
+    regions = (ImageRegion * max(1, mip_count))()
+    total = C.c_uint64()
+    _check(_l().dxtlt_image_mip_chain(width, height, mip_count, first_block, regions, C.byref(total)))
+    return [(r.first_block, r.width, r.height) for r in regions[:mip_count]], total.value
+
+
+def _region_table(fmt, src, regions, outs, pitches):
+    """the outputs (new ones on the source's side where ``outs`` has none) and the DxtltImageRegion array"""
+    regions = list(regions)
+    outs = list(outs) if outs is not None else [None] * len(regions)
+    pitches = list(pitches) if pitches is not None else [None] * len(regions)
+    if len(outs) != len(regions) or len(pitches) != len(regions):
+        raise ValueError("outs and pitches must have one entry per region")
+    table, keep = (ImageRegion * max(1, len(regions)))(), []
+    for i, (first, width, height) in enumerate(regions):
+        outs[i], dst, pitch = _output(src, width, height, outs[i], pitches[i], _ALL_BPP[fmt])
+        keep.append(dst)
+        table[i] = ImageRegion(first, width, height, dst.ptr, pitch)
+    return outs, table, len(regions), keep
+
+
+def _whole_buffer(fmt, buffer, total_blocks):
+    from . import InvalidLength, _Buf
+
+    src, bs = _Buf(buffer, False), _ALL_BLOCK[fmt]
+    if src.nbytes % bs != 0:
+        raise InvalidLength(src.nbytes)
+    if total_blocks is None:
+        total_blocks = src.nbytes // bs
+    if total_blocks * bs > src.nbytes:
+        raise InvalidLength(src.nbytes)
+    return src, total_blocks
+
+
+def untransform_decode_images(fmt: str, transformed, regions, *, total_blocks=None, decorrelation_mode=0,
+                              split_alpha_endpoints: bool = False, split_colour_endpoints: bool = False, split_endpoints=None,
+                              outs=None, pitches=None):
+    """Every region ``(first_block, width, height)`` of the WHOLE transformed buffer ``transformed`` (``total_blocks`` blocks,
+    default: its length) to an image of its own, in one call: one or two launches per sixteen regions.  ``fmt`` is ``"bc1"`` ..
+    ``"bc5"``; ``"bc4"`` / ``"bc5"`` take ``split_endpoints`` (or ``split_alpha_endpoints``, as the C call does) and ignore the
+    other settings.  The regions ascend and do not overlap.  Returns the list of outputs: ``outs[i]``, or a new buffer of
+    ``pitch * height`` bytes where it is None; ``pitches[i]`` defaults to ``bpp * width``."""
+    src, total_blocks = _whole_buffer(fmt, transformed, total_blocks)
+    outs, table, count, keep = _region_table(fmt, src, regions, outs, pitches)
+    if fmt in _CHANNEL_FMT and split_endpoints is not None:
+        split_alpha_endpoints = split_endpoints
+    mode, sa, sc = int(decorrelation_mode), bool(split_alpha_endpoints), bool(split_colour_endpoints)
+    l = _l()
+    if src.device is None:
+        _check(l.dxtlt_untransform_decode_images(_ALL_FMT[fmt], src.ptr, total_blocks * _ALL_BLOCK[fmt], table, count, mode, sa, sc))
+        return outs
+    import torch
+
+    with torch.cuda.device(src.device):
+        _check(l.dxtlt_untransform_decode_images_device(_ALL_FMT[fmt], src.ptr, total_blocks, table, count, mode, sa, sc,
+                                                        torch.cuda.current_stream(src.device).cuda_stream))
+    del keep
+    return outs
+
+
+def decode_images(fmt: str, blocks, regions, *, total_blocks=None, outs=None, pitches=None):
+    """The same from a block array in block order, a CUDA tensor (the library has no host-pointer form of it)."""
+    src, total_blocks = _whole_buffer(fmt, blocks, total_blocks)
+    if src.device is None:
+        raise TypeError("decode_images takes device tensors (the library has no host-pointer form of it)")
+    outs, table, count, keep = _region_table(fmt, src, regions, outs, pitches)
+    import torch
+
+    with torch.cuda.device(src.device):
+        _check(_l().dxtlt_decode_images_device(_ALL_FMT[fmt], src.ptr, total_blocks, table, count,
+                                               torch.cuda.current_stream(src.device).cuda_stream))
+    del keep
+    return outs

@@ -795,5 +795,38 @@ inline void untransform_decode_channel_image(int32_t format, const uint8_t* tran
                                                                 pixels, pitch));
 }
 
+// ADDITIVE: several images of one buffer in one call (dxtlt_image.h, "several images of one buffer"): a mip chain, the faces of
+// a cube map.  format = 1 .. 5; the regions ascend and do not overlap; formats 4 / 5 take split_endpoints in
+// split_alpha_endpoints and ignore the other two settings.
+// first_block, width and height of a chain's levels, level 0 at `first_block`; pixels and pitch are the caller's to fill.
+// Returns the block just behind the chain.
+inline uint64_t image_mip_chain(uint32_t width, uint32_t height, uint32_t mip_count, uint64_t first_block, DxtltImageRegion* regions)
+{
+    uint64_t total_blocks = 0;
+    detail::check_device(dxtlt_image_mip_chain(width, height, mip_count, first_block, regions, &total_blocks));
+    return total_blocks;
+}
+inline void untransform_decode_images_device(int32_t format, const void* d_transformed, uint64_t total_blocks,
+                                             const DxtltImageRegion* regions, size_t region_count, YCoCgVariant decorrelation_mode,
+                                             bool split_alpha_endpoints, bool split_colour_endpoints, void* hip_stream)
+{
+    detail::check_device(dxtlt_untransform_decode_images_device(format, d_transformed, total_blocks, regions, region_count,
+                                                                static_cast<uint8_t>(to_internal_variant(decorrelation_mode)),
+                                                                split_alpha_endpoints, split_colour_endpoints, hip_stream));
+}
+inline void decode_images_device(int32_t format, const void* d_blocks, uint64_t total_blocks, const DxtltImageRegion* regions,
+                                 size_t region_count, void* hip_stream)
+{
+    detail::check_device(dxtlt_decode_images_device(format, d_blocks, total_blocks, regions, region_count, hip_stream));
+}
+inline void untransform_decode_images(int32_t format, const uint8_t* transformed, size_t len, const DxtltImageRegion* regions,
+                                      size_t region_count, YCoCgVariant decorrelation_mode, bool split_alpha_endpoints,
+                                      bool split_colour_endpoints)
+{
+    detail::check_device(dxtlt_untransform_decode_images(format, transformed, len, regions, region_count,
+                                                         static_cast<uint8_t>(to_internal_variant(decorrelation_mode)),
+                                                         split_alpha_endpoints, split_colour_endpoints));
+}
+
 }  // namespace api
 }  // namespace dxt_lossless_transform

@@ -93,6 +93,63 @@ int32_t dxtlt_untransform_decode_channel_image(int32_t format, const uint8_t *tr
                                                uint32_t width, uint32_t height, bool split_endpoints,
                                                uint8_t *pixels, uint64_t pitch);
 
+/* ---- several images of one buffer (format 1 .. 5; bpp = 4, 4, 4, 1, 2): docs/IMAGE_DECODE.md, "Several images of one buffer" ----
+ *
+ * An image region is one image and the block range it comes from: blocks [first_block, first_block + ceil(w/4)*ceil(h/4)) of
+ * the buffer, numbered inside the region as an image's blocks are.  One call writes every region's image -- a mip chain, the
+ * faces of a cube map -- with the pixel values, the partial blocks and the "nothing else is written" rule of the single-image
+ * call for the format.
+ *   regions   a HOST array, read during the call and never afterwards.  A region of zero width or height is skipped.  The
+ *             others must come in ascending block order and must not overlap; gaps between them are legal, and a block that
+ *             lies in no region is written nowhere.  The images must not overlap in memory (not checked).
+ *   settings  as in dxtlt_transform_range_device: formats 4 / 5 take split_endpoints in split_alpha_endpoints and ignore the
+ *             decorrelation mode and the colour split.
+ *   checks    in this order, before any device is touched: the format; region_count == 0 or every region empty is DXTLT_OK
+ *             and does nothing; a NULL buffer or `regions` pointer; for every non-empty region in list order a NULL `pixels`,
+ *             pitch < bpp * width, pitch or `pixels` not a multiple of 4 (formats 1 - 3) or of bpp (formats 4, 5),
+ *             first_block + blocks > total_blocks, a region that starts before the previous non-empty one ends; then
+ *             decorrelation_mode > 3 for formats 1 - 3 -- all DXTLT_E_INVALID_ARGUMENT -- and, host call only, len not a
+ *             multiple of the block size: DXTLT_E_INVALID_LENGTH.
+ *   launches  the non-empty regions are taken in groups of at most DXTLT_IMAGE_REGIONS_PER_LAUNCH consecutive ones; a group is
+ *             one plan of the inverse transform over the range from its first block to the end of its last region (one or
+ *             two launches), its table in the kernel arguments.  Blocks in gaps are loaded and dropped: a caller with a large
+ *             gap makes two calls.
+ *   device    the *_device calls enqueue on `hip_stream` only, allocate nothing, copy nothing to the device but kernel
+ *             arguments and do not synchronise: they can be captured into a HIP graph, the table frozen at capture.
+ */
+#define DXTLT_IMAGE_REGIONS_PER_LAUNCH 16
+
+typedef struct DxtltImageRegion {
+    uint64_t first_block;     /* index into the buffer's blocks */
+    uint32_t width, height;   /* pixels; a zero width or height: the region is skipped */
+    void    *pixels;          /* device (or, in the host call, host) pointer */
+    uint64_t pitch;
+} DxtltImageRegion;
+
+/* a TRANSFORMED device buffer of total_blocks, any alignment -> every region's device image */
+int32_t dxtlt_untransform_decode_images_device(int32_t format, const void *d_transformed, uint64_t total_blocks,
+                                               const DxtltImageRegion *regions, size_t region_count,
+                                               uint8_t decorrelation_mode, bool split_alpha_endpoints,
+                                               bool split_colour_endpoints, void *hip_stream);
+
+/* a device block array of total_blocks in block order, any alignment -> the same */
+int32_t dxtlt_decode_images_device(int32_t format, const void *d_blocks, uint64_t total_blocks,
+                                   const DxtltImageRegion *regions, size_t region_count, void *hip_stream);
+
+/* host pointers: one upload of the whole transformed buffer of len bytes, the same kernels into staging (every region's
+ * base a multiple of 16, its rows a multiple of 16 bytes apart), one strided download per region */
+int32_t dxtlt_untransform_decode_images(int32_t format, const uint8_t *transformed, size_t len,
+                                        const DxtltImageRegion *regions, size_t region_count,
+                                        uint8_t decorrelation_mode, bool split_alpha_endpoints,
+                                        bool split_colour_endpoints);
+
+/* pure host arithmetic, no device: first_block, width and height of regions[0 .. mip_count) for a width x height chain of
+ * mip_count levels whose level 0 starts at block first_block -- level k exactly as dxtlt_image_mip_level has it, first_block
+ * added.  `pixels` and `pitch` are left alone.  *total_blocks (may be NULL) = the block just behind the chain.  A zero width,
+ * height or mip_count, or a NULL `regions`, is DXTLT_E_INVALID_ARGUMENT. */
+int32_t dxtlt_image_mip_chain(uint32_t width, uint32_t height, uint32_t mip_count, uint64_t first_block,
+                              DxtltImageRegion *regions, uint64_t *total_blocks);
+
 #ifdef __cplusplus
 }
 #endif
