@@ -26,6 +26,7 @@
 #include "bcn_launch.h"
 #include "granule_launch.h"
 #include "host_common.h"
+#include "table_ring.h"
 
 namespace {
 
@@ -62,99 +63,25 @@ int32_t launch_pixel_item(const DxtltBatchItem& it, void* stream)
                               pixel_layout_of(it.split_alpha_endpoints != 0, it.split_colour_endpoints != 0), stream);
 }
 
-// Table staging: a ring of pinned host buffers with device twins.  A slot is reused only after the copy and the kernels that last
-// read it have finished (its event).  A call takes exactly ONE slot -- the tables of its two BC7 launches and of all its BC1-3
-// groups share one staged buffer and one upload -- so it never waits for its own work, and its acquire blocks the host only when
-// kSlots earlier calls of this thread are all still in flight.  (Until round 6 a call with BC7 forward, BC7 inverse and BC1-3
-// items took three slots: the next such call's second acquire landed on a slot the previous call had left pending and waited in
-// hipEventSynchronize for that call's kernels -- an "asynchronous" call that host-blocked with a single earlier call in flight,
-// which dxtlt_transform_batch_host hit on every chunk.  Sixteen mixed calls back to back: enqueued in 0.66 ms instead of 1.0 ms, finished
-// 20 % sooner: profiles/r06_batch_one_slot.txt.)
-constexpr int kSlots = 4;
-
-struct TableSlot {
-    void* host = nullptr;
-    void* host_mapped = nullptr;   // the device-side address of `host`
-    void* dev = nullptr;
-    size_t cap = 0;
-    hipEvent_t done = nullptr;
-    bool pending = false;
-};
-
-struct TableRing {
-    int device = -1;
-    TableSlot slots[kSlots];
-    int next = 0;
-
-    ~TableRing() { release(); }
-    void release()
-    {
-        if (device < 0)
-            return;
-        for (auto& s : slots) {
-            if (s.host) (void)hipHostFree(s.host);
-            if (s.dev) (void)hipFree(s.dev);
-            if (s.done) (void)hipEventDestroy(s.done);
-            s = TableSlot{};
-        }
-        device = -1;
-        next = 0;
-    }
-    hipError_t acquire(size_t bytes, TableSlot** out)
-    {
-        int dev = 0;
-        hipError_t e = hipGetDevice(&dev);
-        if (e != hipSuccess)
-            return e;
-        if (dev != device) {
-            release();
-            device = dev;
-        }
-        TableSlot& s = slots[next];
-        next = (next + 1) % kSlots;
-        if (s.pending) {
-            e = hipEventSynchronize(s.done);
-            if (e != hipSuccess)
-                return e;
-            s.pending = false;
-        }
-        if (s.done == nullptr) {
-            e = hipEventCreateWithFlags(&s.done, hipEventDisableTiming);
-            if (e != hipSuccess)
-                return e;
-        }
-        if (s.cap < bytes) {
-            if (s.host) (void)hipHostFree(s.host);
-            if (s.dev) (void)hipFree(s.dev);
-            s.host = s.dev = nullptr;
-            s.cap = 0;
-            const size_t want = bytes + bytes / 2 + 4096;
-            e = hipHostMalloc(&s.host, want, hipHostMallocMapped);
-            if (e == hipSuccess)
-                e = hipHostGetDevicePointer(&s.host_mapped, s.host, 0);
-            if (e == hipSuccess)
-                e = hipMalloc(&s.dev, want);
-            if (e != hipSuccess)
-                return e;
-            s.cap = want;
-        }
-        *out = &s;
-        return hipSuccess;
-    }
-};
-
-thread_local TableRing g_ring;
+// Table staging: table_ring.h (shared with the batch image call)
+thread_local dxtlt_host::TableRing g_ring;
 
 // DXTLT_BATCH_TABLE_COPY=1: the table travels by hipMemcpyAsync (the first version; kept for the comparison in
 // profiles/r02_m_batch_kernel.txt)
 const bool kTableByCopyEngine = dxtlt::experiment_env("DXTLT_BATCH_TABLE_COPY") != nullptr && dxtlt::experiment_env("DXTLT_BATCH_TABLE_COPY")[0] == '1';
 
-hipError_t upload_table(TableSlot* slot, size_t bytes, hipStream_t stream)
+}  // namespace
+
+dxtlt_host::TableRing& dxtlt_host::thread_table_ring() { return g_ring; }
+
+hipError_t dxtlt_host::upload_table(TableSlot* slot, size_t bytes, hipStream_t stream)
 {
     if (kTableByCopyEngine)
         return hipMemcpyAsync(slot->dev, slot->host, bytes, hipMemcpyHostToDevice, stream);
     return dxtlt::launch_table_upload(slot->host_mapped, slot->dev, bytes, stream);
 }
+
+namespace {
 
 // The device batch; `pixels_allowed`: items of formats 8 and 9 are taken too (the host batch's chunks: their buffers are this
 // library's own staging, checked by the host call) -- the public device call keeps refusing them.

@@ -20,6 +20,8 @@
 
 #include "bcn_device.h"
 
+#include "batch_lookup.h"
+
 namespace dxtlt {
 
 // A table entry as the workgroup sees it: everything arrives through scalar (dword) loads -- byte fields read one by
@@ -167,44 +169,8 @@ batch_kernel(const BatchEntry* __restrict__ entries_arg, const uint8_t* __restri
             en = load_batch_entry(entries + e);
         }
     } else {
-        // base[wg / 4096] + delta[wg / 64] = the entry that owns workgroup 64 * (wg / 64) (bcn_launch.h); an entry carries its own
-        // end, so a workgroup of a buffer of 64 workgroups or more is two dependent table loads away from its tile (three scalar
-        // round trips with the kernel arguments).  What was measured on the way here (profiles/r04_batch_edge_tiles.txt; one
-        // 2 GiB odd-count buffer or the corpus, forward): no table load 0.80, ONE load of an entry that thousands of workgroups
-        // share 0.80 -- a scalar-cache hit costs next to nothing -- but an index record that every workgroup of a CU sees for the
-        // first time 0.72-0.76 whatever it saves in round trips (a 144-byte record per 256 workgroups with the entry inline:
-        // 0.72; a 16-byte bit mask per 64: 0.76; 4 bytes per 64: 0.77).  So the index is as small as it can be -- one byte per 64
-        // workgroups, a cache line per 4096 -- and the entry, shared by all workgroups of its buffer, is what is fetched behind it.
-        // Wide form (bit 31 of n_base; build_batch_index): 16-bit deltas, for launches in which more than 255 entries begin inside
-        // one 4096-workgroup span -- thousands of buffers of one to three tiles -- where a byte would saturate and leave a walk of
-        // up to ~3800 entries.  Branch-free on purpose: both forms issue the same two index loads.
-        const uint32_t* base = reinterpret_cast<const uint32_t*>(index);
-        const uint32_t wide = n_base >> 31;
-        const uint8_t* delta = index + (n_base & 0x7FFFFFFFu) * 4;
-        e = base[wg >> 12];
-        const uint32_t dword = reinterpret_cast<const uint32_t*>(delta)[wg >> (8u - wide)];   // (a scalar load is a dword load)
-        e += (dword >> (((wg >> 6) & (3u >> wide)) << (3u + wide))) & (0xFFu | (wide * 0xFF00u));
-        en = load_batch_entry(entries + e);
-        // every field is needed HERE (empty non-volatile asm: the value becomes opaque, memory is untouched, the loads stay
-        // scalar): left alone the compiler fetches end_wg, runs the search and only then asks for the rest of the entry
-        pin_batch_view(en);
-        if (en.end_wg <= wg) {
-            // Only buffers of fewer than 64 workgroups take this: `e` owns workgroup 64 * (wg / 64), so the owner of `wg` is one of
-            // the next (wg & 63) entries.  Bisection over their end_wg fields -- at most six dependent dword loads, where walking
-            // on entry by entry took up to 63 loads of a whole 96-byte entry (`magic` carries the entry count in this mode).
-            uint32_t lo = e + 1, hi = e + (wg & 63u);
-            hi = hi < magic - 1u ? hi : magic - 1u;
-            while (lo < hi) {
-                const uint32_t mid = (lo + hi) >> 1;
-                const uint32_t end = reinterpret_cast<const uint32_t*>(entries + mid)[7];   // BatchEntry::end_wg
-                if (end <= wg)
-                    lo = mid + 1;
-                else
-                    hi = mid;
-            }
-            e = lo;
-            en = load_batch_entry(entries + e);
-        }
+        // through the workgroup index, then bisection (batch_lookup.h; `magic` carries the entry count in this mode)
+        e = batch_entry_of_workgroup(entries, index, n_base, magic, wg, en);
     }
     // Which of the buffer's tiles this workgroup takes.  Workgroups go to the eight XCDs round robin (wg % 8), and an edge tile
     // takes 1.2-1.9 x a whole tile's time (tools/wg_timing_probe.py): with buffers of 8 k workgroups each, launch order would put

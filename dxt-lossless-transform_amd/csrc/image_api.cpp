@@ -14,6 +14,48 @@ using dxtlt_host::kInvalidArgument;
 using dxtlt_host::kInvalidLength;
 using dxtlt_host::kOk;
 
+// The first defect of an image-region call's arguments in the documented order -- all of them DXTLT_E_INVALID_ARGUMENT -- or
+// nullptr; *nothing = there is no non-empty region.  (image_launch.h: the batch call runs the same checks per item.)
+const char* dxtlt_host::image_regions_defect(int32_t fmt, const void* buffer, uint64_t total_blocks, const DxtltImageRegion* regions,
+                                             size_t count, uint8_t mode, bool* nothing)
+{
+    *nothing = true;
+    if (fmt < 1 || fmt > 5)
+        return "format must be 1 (BC1) .. 5 (BC5)";
+    if (count == 0)
+        return nullptr;
+    if (regions == nullptr)
+        return "NULL regions pointer";
+    for (size_t i = 0; i < count && *nothing; ++i)
+        *nothing = regions[i].width == 0 || regions[i].height == 0;
+    if (*nothing)
+        return nullptr;
+    if (buffer == nullptr)
+        return "NULL buffer with a non-empty region";
+    const uint64_t bpp = fmt <= 3 ? 4 : fmt == 4 ? 1 : 2, multiple = fmt <= 3 ? 4 : bpp;
+    auto blocks_of = [](uint32_t width, uint32_t height) { return (((uint64_t)width + 3) / 4) * (((uint64_t)height + 3) / 4); };
+    uint64_t end = 0;   // of the previous non-empty region
+    for (size_t i = 0; i < count; ++i) {
+        const DxtltImageRegion& r = regions[i];
+        if (r.width == 0 || r.height == 0)
+            continue;
+        if (r.pixels == nullptr)
+            return "NULL pixels pointer of a non-empty region";
+        if (r.pitch < bpp * (uint64_t)r.width)
+            return "a region's pitch is smaller than the bytes of a pixel row";
+        if (r.pitch % multiple != 0 || reinterpret_cast<uintptr_t>(r.pixels) % multiple != 0)
+            return "a region's pitch and pixel pointer must be multiples of 4 (BC1 - BC3) or of the bytes per pixel";
+        if (r.first_block > total_blocks || blocks_of(r.width, r.height) > total_blocks - r.first_block)
+            return "first_block + blocks of a region exceeds total_blocks";
+        if (r.first_block < end)
+            return "regions must come in ascending block order and must not overlap";
+        end = r.first_block + blocks_of(r.width, r.height);
+    }
+    if (fmt <= 3 && mode > 3)
+        return "decorrelation_mode must be 0..3";
+    return nullptr;
+}
+
 namespace {
 
 inline uint64_t block_bytes_of(int32_t fmt) { return fmt == 1 ? 8 : 16; }
@@ -88,37 +130,8 @@ int32_t check_any_format(int32_t fmt)
 int32_t check_regions(int32_t fmt, const void* buffer, uint64_t total_blocks, const DxtltImageRegion* regions, size_t count,
                       uint8_t mode, bool* nothing)
 {
-    *nothing = true;
-    if (count == 0)
-        return kOk;
-    if (regions == nullptr)
-        return fail(kInvalidArgument, "NULL regions pointer");
-    for (size_t i = 0; i < count && *nothing; ++i)
-        *nothing = empty_region(regions[i]);
-    if (*nothing)
-        return kOk;
-    if (buffer == nullptr)
-        return fail(kInvalidArgument, "NULL buffer with a non-empty region");
-    const uint64_t bpp = bpp_of(fmt), multiple = fmt <= 3 ? 4 : bpp;
-    uint64_t end = 0;   // of the previous non-empty region
-    for (size_t i = 0; i < count; ++i) {
-        const DxtltImageRegion& r = regions[i];
-        if (empty_region(r))
-            continue;
-        if (r.pixels == nullptr)
-            return fail(kInvalidArgument, "NULL pixels pointer of a non-empty region");
-        if (r.pitch < bpp * (uint64_t)r.width)
-            return fail(kInvalidArgument, "a region's pitch is smaller than the bytes of a pixel row");
-        if (r.pitch % multiple != 0 || reinterpret_cast<uintptr_t>(r.pixels) % multiple != 0)
-            return fail(kInvalidArgument, "a region's pitch and pixel pointer must be multiples of 4 (BC1 - BC3) or of the bytes per pixel");
-        if (r.first_block > total_blocks || blocks_of(r.width, r.height) > total_blocks - r.first_block)
-            return fail(kInvalidArgument, "first_block + blocks of a region exceeds total_blocks");
-        if (r.first_block < end)
-            return fail(kInvalidArgument, "regions must come in ascending block order and must not overlap");
-        end = r.first_block + blocks_of(r.width, r.height);
-    }
-    if (fmt <= 3 && mode > 3)
-        return fail(kInvalidArgument, "decorrelation_mode must be 0..3");
+    if (const char* defect = dxtlt_host::image_regions_defect(fmt, buffer, total_blocks, regions, count, mode, nothing))
+        return fail(kInvalidArgument, defect);
     return kOk;
 }
 

@@ -27,3 +27,11 @@ hipError_t launch_untransform_decode_image_regions(Format fmt, const Settings& s
                                                    const ImageRegionTable& tab, hipStream_t stream);
 
 }  // namespace dxtlt
+
+struct DxtltImageRegion;
+namespace dxtlt_host {
+// image_api.cpp: the first defect of an image-region call's arguments in the documented order (the format first), or nullptr;
+// every defect is DXTLT_E_INVALID_ARGUMENT.  *nothing = there is no non-empty region.  The batch call checks every item with it.
+const char* image_regions_defect(int32_t fmt, const void* buffer, uint64_t total_blocks, const DxtltImageRegion* regions, size_t count,
+                                 uint8_t mode, bool* nothing);
+}  // namespace dxtlt_host

@@ -8,6 +8,8 @@
 #pragma once
 #include "image_sink.h"
 
+// The lookups are written once for every kind of table: a TABLE answers regions(), first_of(i), blocks_of(i) and image_of(i).
+//
 // Both lookups below are loops that stay loops.  Unrolled over the sixteen entries, the walks of one kernel read the table in
 // many hundreds of places, and from a few hundred on the compiler no longer reads a by-value kernel argument in place: it
 // copies the whole table to scratch memory first (seen in the BC1 and BC4 shifted kernels, whose two blocks per lane double the
@@ -28,6 +30,13 @@ struct ImageRegionTable {
     uint64_t first[kImageRegionsPerLaunch];
     uint64_t blocks[kImageRegionsPerLaunch];
     uint32_t count;
+
+    // what the lookups below ask of a table (image_batch_kernels.hip has the one that lives in device memory); the index keeps
+    // the type the lookup has it in
+    __host__ __device__ uint32_t regions() const { return count; }
+    template <typename I> __host__ __device__ uint64_t first_of(I i) const { return first[i]; }
+    template <typename I> __host__ __device__ uint64_t blocks_of(I i) const { return blocks[i]; }
+    template <typename I> __host__ __device__ const ImageSink& image_of(I i) const { return img[i]; }
 };
 static_assert(sizeof(ImageRegionTable) <= 1024, "the table travels in the kernel arguments");
 
@@ -51,24 +60,26 @@ inline void append_region(ImageRegionTable& t, const ImageSink& img, uint64_t fi
 
 // Is block `b` of the buffer in region i?  `local` = its number inside the region.  (b < first[i] wraps to a number that no
 // region has blocks for: one comparison.)
-__host__ __device__ inline bool in_region(const ImageRegionTable& t, int i, uint64_t b, uint64_t& local)
+template <typename TABLE>
+__host__ __device__ inline bool in_region(const TABLE& t, int i, uint64_t b, uint64_t& local)
 {
-    local = b - t.first[i];
-    return local < t.blocks[i];
+    local = b - t.first_of(i);
+    return local < t.blocks_of(i);
 }
 
 // The region that holds all of the blocks [b, b + n), n >= 1, or -1: these blocks straddle a boundary, or some lie in a gap.
 // `img` and `local` are then the region's image and the number of block `b` in it.  This is the question a wave asks about its
 // 64 or 128 consecutive blocks with `b` in scalar registers: every condition below is the same in all lanes, so what is found
 // stays in scalar registers and serves every lane.
-__host__ __device__ inline int region_of_run(const ImageRegionTable& t, uint64_t b, uint64_t n, ImageSink& img, uint64_t& local)
+template <typename TABLE>
+__host__ __device__ inline int region_of_run(const TABLE& t, uint64_t b, uint64_t n, ImageSink& img, uint64_t& local)
 {
     DXTLT_REGIONS_LOOP
-    for (uint32_t i = 0; i < t.count; ++i) {
+    for (uint32_t i = 0; i < t.regions(); ++i) {
         uint64_t d;
-        if (in_region(t, (int)i, b, d) && n <= t.blocks[i] - d) {
+        if (in_region(t, (int)i, b, d) && n <= t.blocks_of(i) - d) {
             local = d;
-            img = t.img[i];
+            img = t.image_of(i);
             return (int)i;
         }
     }
@@ -78,16 +89,17 @@ __host__ __device__ inline int region_of_run(const ImageRegionTable& t, uint64_t
 // The region of ONE block, each lane with a `b` of its own: -1 = the block lies in no region; otherwise `img` and `local` are
 // the region's image and the block's number in it.  The walk over the regions is uniform -- every lane compares with region i at
 // the same time and keeps what matches, field by field -- so the table is never indexed with a per-lane number.
-__host__ __device__ inline int region_of_block(const ImageRegionTable& t, uint64_t b, ImageSink& img, uint64_t& local)
+template <typename TABLE>
+__host__ __device__ inline int region_of_block(const TABLE& t, uint64_t b, ImageSink& img, uint64_t& local)
 {
     int found = -1;
     DXTLT_REGIONS_LOOP
-    for (uint32_t i = 0; i < t.count; ++i) {
+    for (uint32_t i = 0; i < t.regions(); ++i) {
         uint64_t d;
         if (in_region(t, (int)i, b, d)) {
             found = (int)i;
             local = d;
-            img = t.img[i];
+            img = t.image_of(i);
         }
     }
     return found;

@@ -11,7 +11,9 @@ buffer in one kernel (the untransformed blocks never touch memory); ``mip_level`
 1 / 2 bytes (r, or r, g) at ``y * pitch + bpp * x``, the default pitch ``bpp * width``, the one setting ``split_endpoints``.
 
 ``untransform_decode_images`` and ``decode_images`` write several images of one buffer in one call, for all five formats: a
-region is ``(first_block, width, height)``, and ``mip_chain`` lists the regions of a mip chain."""
+region is ``(first_block, width, height)``, and ``mip_chain`` lists the regions of a mip chain.
+``untransform_decode_images_batch`` does the same for MANY transformed device buffers in one call: one launch per (format,
+settings) present in the batch, whatever the number of buffers."""
 from __future__ import annotations
 
 import ctypes as C
@@ -29,6 +31,12 @@ _ALL_FMT = {**_FMT, **_CHANNEL_FMT}
 _ALL_BLOCK = {**_BLOCK, **_CHANNEL_BLOCK}
 _ALL_BPP = {"bc1": 4, "bc2": 4, "bc3": 4, **_CHANNEL_BPP}
 _declared = False
+
+
+class ImageBatchItem(C.Structure):   # DxtltImageBatchItem, include/dxtlt_image.h
+    _fields_ = [("d_transformed", C.c_void_p), ("total_blocks", C.c_uint64), ("regions", C.c_void_p), ("region_count", C.c_uint32),
+                ("format", C.c_uint8), ("decorrelation_mode", C.c_uint8), ("split_alpha_endpoints", C.c_uint8),
+                ("split_colour_endpoints", C.c_uint8)]
 
 
 class ImageRegion(C.Structure):   # DxtltImageRegion, include/dxtlt_image.h
@@ -54,8 +62,9 @@ def _l():
         l.dxtlt_decode_images_device.argtypes = [i32, vp, u64, rp, C.c_size_t, vp]
         l.dxtlt_untransform_decode_images.argtypes = [i32, vp, C.c_size_t, rp, C.c_size_t, u8, b, b]
         l.dxtlt_image_mip_chain.argtypes = [u32, u32, u32, u64, rp, C.POINTER(u64)]
+        l.dxtlt_untransform_decode_images_batch_device.argtypes = [C.POINTER(ImageBatchItem), C.c_size_t, vp]
         for f in (l.dxtlt_untransform_decode_images_device, l.dxtlt_decode_images_device, l.dxtlt_untransform_decode_images,
-                  l.dxtlt_image_mip_chain):
+                  l.dxtlt_image_mip_chain, l.dxtlt_untransform_decode_images_batch_device):
             f.restype = i32
         for f in (l.dxtlt_decode_image_device, l.dxtlt_untransform_decode_image_device, l.dxtlt_untransform_decode_image,
                   l.dxtlt_image_mip_level, l.dxtlt_decode_channel_image_device, l.dxtlt_untransform_decode_channel_image_device,
@@ -281,3 +290,46 @@ def decode_images(fmt: str, blocks, regions, *, total_blocks=None, outs=None, pi
                                                torch.cuda.current_stream(src.device).cuda_stream))
     del keep
     return outs
+
+
+# ---- many buffers in one call -------------------------------------------------------------------------------------------
+def untransform_decode_images_batch(items):
+    """The images of many transformed buffers in ONE call: one launch per (format, settings) present in ``items``.
+
+    An item is ``(fmt, transformed, regions)`` or ``(fmt, transformed, regions, settings)``, ``settings`` a dict of the
+    keyword arguments of ``untransform_decode_images`` (``total_blocks``, ``decorrelation_mode``, ``split_alpha_endpoints``,
+    ``split_colour_endpoints``, ``split_endpoints``, ``outs``, ``pitches``).  Every ``transformed`` is a CUDA ``torch.uint8``
+    tensor, all on one device; the call is enqueued on torch's current stream of that device.  Returns one list of outputs per
+    item, as ``untransform_decode_images`` returns them.  Items may mix formats, settings and sizes; the images must not
+    overlap."""
+    import torch
+
+    items = list(items)
+    table, keep, results, device = (ImageBatchItem * max(1, len(items)))(), [], [], None
+    for k, item in enumerate(items):
+        fmt, transformed, regions = item[0], item[1], item[2]
+        kw = dict(item[3]) if len(item) > 3 and item[3] is not None else {}
+        src, total_blocks = _whole_buffer(fmt, transformed, kw.pop("total_blocks", None))
+        if src.device is None:
+            raise TypeError("untransform_decode_images_batch takes device tensors (the library has no host-pointer form of it)")
+        if device is None:
+            device = src.device
+        if src.device != device:
+            raise TypeError("all buffers of a batch must be tensors on one device")
+        outs, regions_c, count, dsts = _region_table(fmt, src, regions, kw.pop("outs", None), kw.pop("pitches", None))
+        sa = kw.pop("split_alpha_endpoints", False)
+        split_endpoints = kw.pop("split_endpoints", None)
+        if fmt in _CHANNEL_FMT and split_endpoints is not None:
+            sa = split_endpoints
+        mode, sc = int(kw.pop("decorrelation_mode", 0)), bool(kw.pop("split_colour_endpoints", False))
+        if kw:
+            raise TypeError(f"unknown settings of batch item {k}: {sorted(kw)}")
+        table[k] = ImageBatchItem(src.ptr, total_blocks, C.cast(regions_c, C.c_void_p), count, _ALL_FMT[fmt], mode, int(bool(sa)), int(sc))
+        keep.append((src, regions_c, dsts))
+        results.append(outs)
+    if not items:
+        return results
+    with torch.cuda.device(device):
+        _check(_l().dxtlt_untransform_decode_images_batch_device(table, len(items), torch.cuda.current_stream(device).cuda_stream))
+    del keep
+    return results

@@ -814,6 +814,13 @@ inline void untransform_decode_images_device(int32_t format, const void* d_trans
                                                                 static_cast<uint8_t>(to_internal_variant(decorrelation_mode)),
                                                                 split_alpha_endpoints, split_colour_endpoints, hip_stream));
 }
+// ADDITIVE: the images of many transformed buffers in one call (dxtlt_image.h, "many buffers in one call"): one launch per
+// (format, settings) present in the batch.  An item's decorrelation_mode is the number the C call takes
+// (to_internal_variant(...) of a YCoCgVariant).  Asynchronous on hip_stream; not for capture into a HIP graph.
+inline void untransform_decode_images_batch_device(const DxtltImageBatchItem* items, size_t count, void* hip_stream)
+{
+    detail::check_device(dxtlt_untransform_decode_images_batch_device(items, count, hip_stream));
+}
 inline void decode_images_device(int32_t format, const void* d_blocks, uint64_t total_blocks, const DxtltImageRegion* regions,
                                  size_t region_count, void* hip_stream)
 {

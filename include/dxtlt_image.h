@@ -150,6 +150,69 @@ int32_t dxtlt_untransform_decode_images(int32_t format, const uint8_t *transform
 int32_t dxtlt_image_mip_chain(uint32_t width, uint32_t height, uint32_t mip_count, uint64_t first_block,
                               DxtltImageRegion *regions, uint64_t *total_blocks);
 
+/* ---- many buffers in one call (docs/IMAGE_DECODE.md, "Many buffers in one call") ----
+ *
+ * One item is one dxtlt_untransform_decode_images_device call: a transformed device buffer, its regions and its settings.  For
+ * every item the call writes exactly the bytes that call writes for the item alone -- pixel values, partial blocks, "nothing
+ * else is written", gaps, empty regions -- but a whole batch goes out as ONE launch per (format, decorrelation mode, alpha
+ * split, colour split) present in it, whatever the number of items: thousands of small mip chains cost one launch, not one
+ * each.
+ *   items     a HOST array, and every item's `regions` a host array, read during the call and never afterwards.  Items may mix
+ *             formats, settings, sizes and alignments; two items may name the same buffer (buffers are only read).  The
+ *             images of a batch must not overlap one another (not checked).
+ *   checks    the whole batch before anything is enqueued: it goes out whole or not at all.  count == 0 is DXTLT_OK; a NULL
+ *             `items` with count > 0 is DXTLT_E_INVALID_ARGUMENT; then the items in list order, each with the checks of
+ *             dxtlt_untransform_decode_images_device in that call's order.  The first failure is the answer, and
+ *             dxtlt_last_error() names the item's index.  An item without a non-empty region is skipped, its buffer pointer
+ *             unchecked, as in the single call.
+ *   launches  an item's non-empty regions are taken in groups of at most DXTLT_IMAGE_REGIONS_PER_LAUNCH, each group one range
+ *             of the inverse transform -- from its first block to the end of its last region -- planned for its address as the
+ *             single call plans it.  The groups of one format and settings share a launch, launches in the order in which
+ *             their settings first appear in the list.  A group of a buffer whose stream shifts are not multiples of the
+ *             stream element widths (a buffer address that is not a multiple of 8, say) goes out alone through the single
+ *             call's kernels, behind the batch launches.
+ *   limit     one launch holds at most 16777215 (2^24 - 1) tiles -- a tile is 256 lanes' worth of blocks: 512 BC1 / BC4
+ *             blocks, 256 of the others; every group takes ceil(range blocks / tile) of them.  A batch that needs more for
+ *             one format and settings is DXTLT_E_INVALID_ARGUMENT, and nothing is enqueued.
+ *   device    asynchronous on `hip_stream`, ordered like a single call.  The call stages its tables (entries, workgroup index,
+ *             region tables) in one of four pinned slots of the calling thread and uploads them on the stream, as
+ *             dxtlt_transform_batch_device does; it blocks the host only when four earlier batch calls of the thread are all
+ *             still in flight.  Capture into a HIP graph is NOT promised (the tables are staged per call), as for
+ *             dxtlt_transform_batch_device.
+ */
+typedef struct DxtltImageBatchItem {
+    const void *d_transformed;        /* byte 0 of the item's WHOLE transformed device buffer, any alignment */
+    uint64_t total_blocks;
+    const DxtltImageRegion *regions;  /* host array; pixels = device pointers; the rules of the *_images calls */
+    uint32_t region_count;
+    uint8_t format;                   /* 1..5 */
+    uint8_t decorrelation_mode;       /* as dxtlt_untransform_decode_images_device takes them */
+    uint8_t split_alpha_endpoints;    /* formats 4 / 5: split_endpoints */
+    uint8_t split_colour_endpoints;
+} DxtltImageBatchItem;
+
+int32_t dxtlt_untransform_decode_images_batch_device(const DxtltImageBatchItem *items, size_t count, void *hip_stream);
+
+/* Test hook, no device needed: what dxtlt_untransform_decode_images_batch_device would enqueue for the batch.  Addresses are
+ * numbers; nothing is dereferenced but `items` and the items' `regions`.  One record per entry -- a group of at most
+ * DXTLT_IMAGE_REGIONS_PER_LAUNCH non-empty regions of an item -- in list order; records beyond `cap` are counted, not written.
+ * Returns the number of entries, or -1 for a batch the call would refuse. */
+typedef struct DxtltDebugImageBatchEntry {
+    uint32_t item;            /* index of the entry's item */
+    uint32_t first_region;    /* index in the item's list of the group's first region */
+    uint32_t region_count;    /* non-empty regions of the group */
+    int32_t  launch;          /* number of the batch launch that holds the entry; -1: launched alone, behind them */
+    uint32_t first_wg, end_wg;/* its workgroups in that launch (both 0 for an entry launched alone) */
+    uint32_t full_tiles;      /* whole tiles among them; one more workgroup, if there is one, is the edge tile */
+    uint32_t form;            /* 1: every stream base of the range on a 128-byte line (aligned tiles); 0: shifted tiles */
+    uint64_t first_block;     /* the range: from the group's first block ... */
+    uint64_t range_blocks;    /* ... to the end of its last region */
+    uint32_t wide_index;      /* 1: the launch's workgroup index has the wide (16-bit) form */
+    uint32_t launch_wgs;      /* workgroups of the whole launch */
+} DxtltDebugImageBatchEntry;
+
+int32_t dxtlt_debug_plan_image_batch(const DxtltImageBatchItem *items, size_t count, DxtltDebugImageBatchEntry *out, size_t cap);
+
 #ifdef __cplusplus
 }
 #endif
