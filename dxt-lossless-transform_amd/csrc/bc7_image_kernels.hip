@@ -1,0 +1,276 @@
+// bc7_image_kernels.hip -- BC7 blocks -> RGBA8888 pixels on gfx950 (include/dxtlt_bc7_image.h; docs/IMAGE_DECODE.md, "BC7"):
+//   * decode_bc7_blocks_kernel: a block array -> one 64-byte Decoded4x4Block per block, in the store shape of bcn_decode.hip (the
+//     wave's 4 KiB of pixels through LDS, every store instruction 1 KiB of consecutive bytes);
+//   * decode_bc7_image_kernel: a block array in block order -> a row-major image, one block per lane, the stores of the BC2 / BC3
+//     plain decoder (store_block_pixels, image_store.h);
+//   * bc7_inverse_image: the inverse granule sort (granule_sort.h over Bc7Codec) with a staging sink (Bc7PixelSink) in the place
+//     of its block store: the blocks are decoded in the sorted domain, where the mode is wave-uniform, and their pixels go
+//     through LDS to block order, so that the untransformed blocks never touch memory.
+// The decoder is bc7_decode.h.  Its mode switch is per lane in the first two kernels, which decode in BLOCK order (a wave runs the
+// arm of every mode that occurs among its 64 blocks: on a buffer of mixed modes they are bound by instruction issue, not by
+// memory), and wave-uniform in the third.
+#include "bc7_decode.h"
+#include "bc7_granule_codec.h"
+#include "bc7_image_launch.h"
+#include "image_store.h"
+#include "launch_grid.h"
+
+namespace dxtlt {
+namespace bc7 {
+namespace {
+
+using granule::inverse_granule;
+using granule::kT;
+
+constexpr int kThreads = 256;
+constexpr int kRowStride = 64 + 4;            // u32x4 units: 64 lanes + 64 bytes of padding (bcn_decode.hip)
+constexpr int kWaveStage = 4 * kRowStride;    // four pixel rows per wave
+
+__device__ __forceinline__ void decode_px(u32x4 q, uint32_t (&px)[16])
+{
+    const B128 b = {{q.x, q.y, q.z, q.w}};
+    decode_bc7_block(b, px);
+}
+
+// block `b` of the array: a 16-byte load when the block pointer is a multiple of 16, byte loads otherwise
+template <bool ALIGNED>
+__device__ __forceinline__ u32x4 load_block(const uint8_t* __restrict__ in, uint64_t b)
+{
+    if constexpr (ALIGNED) {
+        return __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(in) + b);
+    } else {
+        uint32_t q[4] = {0, 0, 0, 0};
+        for (int i = 0; i < 16; ++i)
+            q[i >> 2] |= (uint32_t)in[16 * b + i] << (8 * (i & 3));
+        return u32x4{q[0], q[1], q[2], q[3]};
+    }
+}
+
+// ---- blocks -> Decoded4x4Block -----------------------------------------------------------------------------------------
+// `out` is a multiple of 16
+template <bool ALIGNED>
+__global__ void __launch_bounds__(kThreads)
+decode_bc7_blocks_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, uint64_t num_blocks)
+{
+    __shared__ u32x4 stage[(kThreads / 64) * kWaveStage];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t wave_first = workgroup_index() * kThreads + 64 * wave;
+    const uint64_t b = wave_first + lane;
+    u32x4* mine = stage + wave * kWaveStage;
+    if (b < num_blocks) {
+        uint32_t px[16];
+        decode_px(load_block<ALIGNED>(in, b), px);
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            mine[r * kRowStride + lane] = u32x4{px[4 * r], px[4 * r + 1], px[4 * r + 2], px[4 * r + 3]};
+    }
+    __syncthreads();
+    u32x4* dst = reinterpret_cast<u32x4*>(out) + 4 * wave_first;   // 16-byte chunk j of the wave = block j / 4, row j % 4
+    const uint64_t chunks = num_blocks > wave_first ? 4 * (num_blocks - wave_first) : 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int j = 64 * k + lane;
+        if ((uint64_t)j < chunks)
+            store_streaming16(dst + j, mine[(j & 3) * kRowStride + (j >> 2)]);
+    }
+}
+
+// any alignment of `out`: byte stores; one block per lane
+template <bool ALIGNED>
+__global__ void __launch_bounds__(kThreads)
+decode_bc7_blocks_bytes_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, uint64_t num_blocks)
+{
+    const uint64_t b = workgroup_index() * kThreads + threadIdx.x;
+    if (b >= num_blocks)
+        return;
+    uint32_t px[16];
+    decode_px(load_block<ALIGNED>(in, b), px);
+    uint8_t* o = out + 64 * b;
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+        for (int c = 0; c < 4; ++c)
+            o[4 * i + c] = (uint8_t)(px[i] >> (8 * c));
+}
+
+// ---- blocks in block order -> image, one block per lane ----------------------------------------------------------------
+template <bool ALIGNED>
+__global__ void __launch_bounds__(kThreads)
+decode_bc7_image_kernel(const uint8_t* __restrict__ in, ImageSink img, uint64_t num_blocks)
+{
+    const uint64_t b = workgroup_index() * kThreads + threadIdx.x;
+    if (b >= num_blocks)
+        return;
+    uint32_t px[16];
+    decode_px(load_block<ALIGNED>(in, b), px);
+    store_block_pixels(img, b, px);
+}
+
+// ---- the inverse granule sort with a pixel sink --------------------------------------------------------------------------
+// A staging sink of inverse_granule (granule_sort.h, BlockSink).  The inverse has every block twice: in the sorted domain, where
+// lane j holds sorted block j and a wave's 64 blocks are of one mode except where two classes meet, and -- behind its last
+// barrier -- in block order, where a wave's 64 lanes hold 64 consecutive blocks of the image.  The decoder's mode switch wants the
+// first, the stores want the second, so the pixels cross instead of the blocks: hold() decodes sorted block j into registers,
+// stage() puts two of its four pixel rows into LDS (row k of the part at k * 16 KiB + 16 j: consecutive lanes, consecutive 16
+// bytes), store_staged() fetches them for the lane's block-order block from its sorted position and stores them as the BC2 / BC3
+// decoders do, 1 KiB of consecutive bytes of a pixel row per wave instruction; then the other two rows take the same way.  By then
+// nothing else lives in LDS, so the 32 KiB of a part start at byte 0 and are the kernel's whole allocation.
+// Block `b` of the buffer is block b - first_block of the image when it lies in [first_block, first_block + blocks); every block
+// of a covered granule is decoded, the ones outside are dropped at the store.
+// What else was built and measured (16384 x 16384; ms on a buffer of mode 6 only / the uniform / the skewed mode mix;
+// profiles/bc7_image_bench.json, "ab"; docs/IMAGE_DECODE.md):
+//   * decode in block order behind the un-sort, the mode switch per lane, 19 KiB of LDS: 0.238 / 1.431 / 1.058 -- a wave ran the
+//     arm of every mode among its 64 blocks;
+//   * this sink with all four rows in one part, 64 KiB of LDS, two workgroups per CU: 0.290 / 0.476 / 0.452;
+//   * with one row per part, 19 KiB, six more barriers: 0.249 / 0.412 / 0.367;
+//   * two rows per part (here), 32 KiB, five workgroups per CU by the 95 VGPRs: 0.231 / 0.401 / 0.355.
+// rows [r0, r0 + ROWS) of block `b` of the image: store_block_pixels (image_store.h) for a part of a block
+template <int ROWS>
+__device__ __forceinline__ void store_block_rows(const ImageSink& img, uint64_t b, int r0, const u32x4 (&rows)[ROWS])
+{
+    const BlockPlace p = place_block<4>(img, b);
+    const bool aligned16 = ((reinterpret_cast<uintptr_t>(img.pixels) | img.pitch) & 15) == 0;   // uniform
+    if (p.cols == 4 && p.rows == 4) {
+#pragma unroll
+        for (int k = 0; k < ROWS; ++k) {
+            uint8_t* row = block_row(img, p, r0 + k);
+            if (aligned16)
+                store_streaming16(row, rows[k]);
+            else
+                *reinterpret_cast<u32x4_align4*>(row) = rows[k];
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < ROWS; ++k) {
+            uint32_t* row = reinterpret_cast<uint32_t*>(block_row(img, p, r0 + k));
+            const uint32_t px[4] = {rows[k].x, rows[k].y, rows[k].z, rows[k].w};
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                if ((uint32_t)(r0 + k) < p.rows && (uint32_t)c < p.cols)
+                    row[c] = px[c];
+        }
+    }
+}
+
+struct Bc7PixelSink {
+    static constexpr bool kStaged = true;
+    static constexpr int kParts = 2, kRows = 4 / kParts;   // pixel rows per part
+    static constexpr int kStageBytes = kRows * kT * 16;
+    struct Held {
+        uint32_t px[16];
+    };
+    ImageSink img;
+    uint64_t first_block, blocks;
+
+    __device__ __forceinline__ Held hold(const B128& b) const
+    {
+        Held h;
+        decode_bc7_block(b, h.px);
+        return h;
+    }
+
+    // row k of the part of sorted block j at k * 16 KiB + 16 j: consecutive lanes, consecutive 16 bytes
+    __device__ __forceinline__ void stage(uint8_t* lds, int j, const Held& h, int part) const
+    {
+#pragma unroll
+        for (int k = 0; k < kRows; ++k) {
+            const int r = part * kRows + k;
+            granule::lds_at<u32x4>(lds, k * (kT * 16) + 16 * j) = u32x4{h.px[4 * r], h.px[4 * r + 1], h.px[4 * r + 2], h.px[4 * r + 3]};
+        }
+    }
+
+    __device__ __forceinline__ void store_staged(uint8_t* lds, uint64_t b, int pos, int part) const
+    {
+        const uint64_t at = b - first_block;   // wraps for b < first_block
+        if (at >= blocks)
+            return;
+        u32x4 rows[kRows];
+#pragma unroll
+        for (int k = 0; k < kRows; ++k)
+            rows[k] = granule::lds_at<u32x4>(lds, k * (kT * 16) + 16 * pos);
+        store_block_rows<kRows>(img, at, part * kRows, rows);
+    }
+};
+
+// Full granules: workgroup g is granule first_granule_block / 1024 + g of the main part (part_blocks blocks, soa = its byte 0).
+// TAIL: one workgroup, soa = the tail part's byte 0, first_granule_block = the tail part's first block, n_tail its blocks.
+template <int LANES, bool TAIL>
+__global__ void __launch_bounds__(LANES)
+bc7_inverse_image(const uint8_t* __restrict__ soa, Bc7PixelSink sink, uint64_t part_blocks, uint64_t first_granule_block, int n_tail)
+{
+    const uint64_t granule = blockIdx.x;
+    inverse_granule<Bc7Codec, LANES, TAIL, Bc7PixelSink>(soa, nullptr, part_blocks, first_granule_block + granule * kT, n_tail, sink);
+}
+
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+}  // namespace
+
+hipError_t launch_decode_blocks(const void* blocks, void* pixels, uint64_t num_blocks, hipStream_t stream)
+{
+    if (num_blocks == 0)
+        return hipSuccess;
+    dim3 grid;
+    if (hipError_t e = grid_rows(num_blocks, kThreads, grid); e != hipSuccess)
+        return e;
+    const auto* in = static_cast<const uint8_t*>(blocks);
+    auto* out = static_cast<uint8_t*>(pixels);
+    const bool a = aligned16(blocks);
+    if (aligned16(pixels)) {
+        // six workgroups per CU, as the BC2 / BC3 block decoders (bcn_decode.hip, decode_fmt): the same 16 bytes in, 64 out
+        const unsigned pad = lds_pad_for_wgs_per_cu(wgs_per_cu_or(6), kThreads, (unsigned)((kThreads / 64) * kWaveStage * 16));
+        hipLaunchKernelGGL(a ? decode_bc7_blocks_kernel<true> : decode_bc7_blocks_kernel<false>, grid, dim3(kThreads), pad, stream, in, out,
+                           num_blocks);
+    } else {
+        hipLaunchKernelGGL(a ? decode_bc7_blocks_bytes_kernel<true> : decode_bc7_blocks_bytes_kernel<false>, grid, dim3(kThreads), 0,
+                           stream, in, out, num_blocks);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_decode_image(const void* blocks, const ImageSink& img, hipStream_t stream)
+{
+    const uint64_t n = image_blocks(img);
+    if (n == 0)
+        return hipSuccess;
+    dim3 grid;
+    if (hipError_t e = grid_rows(n, kThreads, grid); e != hipSuccess)
+        return e;
+    const auto* in = static_cast<const uint8_t*>(blocks);
+    hipLaunchKernelGGL(aligned16(blocks) ? decode_bc7_image_kernel<true> : decode_bc7_image_kernel<false>, grid, dim3(kThreads), 0, stream,
+                       in, img, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_untransform_decode_image(const void* soa_arg, uint64_t total_blocks, uint64_t first_block, const ImageSink& img,
+                                           hipStream_t stream)
+{
+    const uint64_t n = image_blocks(img);
+    if (n == 0)
+        return hipSuccess;
+    if (first_block > total_blocks || n > total_blocks - first_block)
+        return hipErrorInvalidValue;
+    const auto* soa = static_cast<const uint8_t*>(soa_arg);
+    const uint64_t main_blocks = total_blocks - total_blocks % kT, end = first_block + n;
+    const Bc7PixelSink sink{img, first_block, n};
+    if (first_block < main_blocks) {
+        // granules first_block / 1024 .. (end - 1) / 1024, bounded by the main part; at most 2^21 of them per launch (granule_sort.h)
+        const uint64_t g0 = first_block / kT, g1 = ((end < main_blocks ? end : main_blocks) - 1) / kT;
+        constexpr uint64_t kMaxGranules = 1ull << 21;
+        for (uint64_t g = g0; g <= g1; g += kMaxGranules) {
+            const uint64_t ng = g1 + 1 - g < kMaxGranules ? g1 + 1 - g : kMaxGranules;
+            hipLaunchKernelGGL((bc7_inverse_image<256, false>), dim3((unsigned)ng), dim3(256), 0, stream, soa, sink, main_blocks, g * kT, 0);
+            if (hipError_t e = hipGetLastError(); e != hipSuccess)
+                return e;
+        }
+    }
+    if (end > main_blocks) {
+        const uint64_t tail = total_blocks - main_blocks;
+        hipLaunchKernelGGL((bc7_inverse_image<256, true>), dim3(1), dim3(256), 0, stream, soa + main_blocks * 16, sink, tail, main_blocks,
+                           (int)tail);
+        return hipGetLastError();
+    }
+    return hipSuccess;
+}
+
+}  // namespace bc7
+}  // namespace dxtlt

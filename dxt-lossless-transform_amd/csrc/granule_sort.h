@@ -1,5 +1,6 @@
 // granule_sort.h -- the granule sort of the BC7 and BC6H field splits (docs/BC7_FORMAT.md, docs/BC6H_FORMAT.md), once,
-// as templates over a codec.  bc7_kernels.hip and bc6h_kernels.hip instantiate it; nothing else includes it.
+// as templates over a codec.  bc7_kernels.hip, bc6h_kernels.hip and bc7_image_kernels.hip (the inverse with a pixel sink)
+// instantiate it; nothing else includes it.
 //
 // What is computed.  The block array is cut into granules of 1024 blocks.  Inside a granule the blocks are ordered by
 // class (the format's modes, then its reserved encodings), blocks of one class keeping their order; a block's bit fields
@@ -8,7 +9,7 @@
 // the main part, whose streams start at multiples of the granule size (so every slice is 128-byte aligned whatever N
 // is); the last N % 1024 blocks form a tail part with the same streams over its own block count.
 //
-// A codec is a struct of static members (Bc7Codec in bc7_kernels.hip, Bc6hCodec in bc6h_kernels.hip):
+// A codec is a struct of static members (Bc7Codec in bc7_granule_codec.h, Bc6hCodec in bc6h_kernels.hip):
 //   kClasses (at most 15)        classes of the sort; a lane beyond a tail part's blocks has class kClasses
 //   kCountsSpare                 unused bytes behind the counts table in LDS
 //   block_class(byte0)           class of a block or a record from its byte 0
@@ -281,15 +282,37 @@ __device__ __forceinline__ void forward_granule(const uint8_t* __restrict__ src,
     }
 }
 
-// One granule, inverse: dst = where the granule's first block goes; the rest as above.
-template <typename Codec, int LANES, bool TAIL>
+// Where the inverse's blocks go.  store() receives, per block, the granule's `dst`, the block's index -- granule_first + j -- its
+// place j in the granule (or tail part) and its 16 bytes.  BlockSink: to dst in block order, the transform's own output.
+// A sink with kStaged takes the blocks in the SORTED domain instead, where a wave's blocks are of one class: hold(block) makes what
+// it wants of sorted block j (a Held, kept in registers), stage(lds, j, held, part) puts part `part` of kParts of it into LDS --
+// all of it is the sink's by then, kStageBytes of it -- and, behind a barrier, store_staged(lds, block index, sorted position,
+// part) writes that part out in block order.  bc7_image_kernels.hip has such a sink, which decodes the block and writes its
+// pixels (docs/IMAGE_DECODE.md, "BC7").
+struct BlockSink {
+    static constexpr bool kStaged = false;
+    __device__ __forceinline__ void store(uint8_t* dst, uint64_t, int j, u32x4 q) const { store_streaming16(dst + (uint64_t)j * 16, q); }
+};
+
+template <typename Sink>
+constexpr int sink_lds_bytes(int own)
+{
+    if constexpr (Sink::kStaged)
+        return own > Sink::kStageBytes ? own : Sink::kStageBytes;
+    else
+        return own;
+}
+
+// One granule, inverse: dst = where the granule's first block goes; the rest as above.  (TAIL reads granule_first for the sink's
+// block index only.)
+template <typename Codec, int LANES, bool TAIL, typename Sink = BlockSink>
 __device__ __forceinline__ void inverse_granule(const uint8_t* __restrict__ soa, uint8_t* __restrict__ dst,
-                                                uint64_t part_blocks, uint64_t granule_first, int n_tail)
+                                                uint64_t part_blocks, uint64_t granule_first, int n_tail, const Sink& sink = Sink())
 {
     constexpr int kClasses = Codec::kClasses;
     constexpr int V = kT / LANES, WAVES = LANES / 64;
     static_assert(V >= 1 && V <= 4 && V * LANES == kT, "four 16-lane rows per wave: at most four segments per wave");
-    __shared__ __attribute__((aligned(16))) uint8_t lds[lds_bytes<Codec, TAIL>()];
+    __shared__ __attribute__((aligned(16))) uint8_t lds[sink_lds_bytes<Sink>(lds_bytes<Codec, TAIL>())];
     const int t = threadIdx.x, lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int n = TAIL ? n_tail : kT;
@@ -364,22 +387,47 @@ __device__ __forceinline__ void inverse_granule(const uint8_t* __restrict__ soa,
             rec[v].d[3] = b1 | (b2 << 8) | (b3 << 16) | (b4 << 24);
         }
     }
-    if constexpr (!TAIL)
-        __syncthreads();   // the records are in registers: the image's region takes the blocks
+    if constexpr (Sink::kStaged) {
+        __syncthreads();   // the records are in registers: all of LDS is the sink's
+        typename Sink::Held held[V];
 #pragma unroll
-    for (int v = 0; v < V; ++v) {
-        const int j = v * LANES + t;
-        if (!TAIL || j < n) {
-            const B128 blk = Codec::block(rec[v], Codec::block_class(rec[v].d[0]));
-            lds_at<u32x4>(lds, kLdsRaw + 16 * j) = u32x4{blk.d[0], blk.d[1], blk.d[2], blk.d[3]};
+        for (int v = 0; v < V; ++v) {
+            held[v] = typename Sink::Held{};
+            if (!TAIL || v * LANES + t < n)
+                held[v] = sink.hold(Codec::block(rec[v], Codec::block_class(rec[v].d[0])));
         }
-    }
-    __syncthreads();
+#pragma unroll
+        for (int part = 0; part < Sink::kParts; ++part) {
+            if (part > 0)
+                __syncthreads();   // the part before this one has been fetched
+#pragma unroll
+            for (int v = 0; v < V; ++v)
+                if (!TAIL || v * LANES + t < n)
+                    sink.stage(lds, v * LANES + t, held[v], part);
+            __syncthreads();
+#pragma unroll
+            for (int v = 0; v < V; ++v)
+                if (cls[v] < kClasses)
+                    sink.store_staged(lds, granule_first + (uint64_t)(v * LANES + t), pos[v], part);
+        }
+    } else {
+        if constexpr (!TAIL)
+            __syncthreads();   // the records are in registers: the image's region takes the blocks
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            const int j = v * LANES + t;
+            if (!TAIL || j < n) {
+                const B128 blk = Codec::block(rec[v], Codec::block_class(rec[v].d[0]));
+                lds_at<u32x4>(lds, kLdsRaw + 16 * j) = u32x4{blk.d[0], blk.d[1], blk.d[2], blk.d[3]};
+            }
+        }
+        __syncthreads();
 
 #pragma unroll
-    for (int v = 0; v < V; ++v)
-        if (cls[v] < kClasses)
-            store_streaming16(dst + (uint64_t)(v * LANES + t) * 16, lds_at<u32x4>(lds, kLdsRaw + 16 * pos[v]));
+        for (int v = 0; v < V; ++v)
+            if (cls[v] < kClasses)
+                sink.store(dst, granule_first + (uint64_t)(v * LANES + t), v * LANES + t, lds_at<u32x4>(lds, kLdsRaw + 16 * pos[v]));
+    }
 }
 
 // ------------------------------------------------------------------------------------------------

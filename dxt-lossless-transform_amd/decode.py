@@ -3,7 +3,9 @@ bc1_decode.rs:42, bc2_decode.rs:44, bc3_decode.rs:43) as array operations over i
 
 ``decode_blocks`` writes one ``Decoded4x4Block`` (64 bytes: sixteen r, g, b, a pixels, row-major) per block;
 ``count_pixel_differences`` is the reference tests' "decode before == decode after" assertion as a count.
-1-D ``uint8`` numpy / bytes-like host buffers or CUDA ``torch.uint8`` tensors (torch's current stream).  No CPU fallback."""
+1-D ``uint8`` numpy / bytes-like host buffers or CUDA ``torch.uint8`` tensors (torch's current stream).  No CPU fallback.
+
+``decode_bc7_blocks`` is the same for BC7 (include/dxtlt_bc7_image.h), a format of this build's own."""
 from __future__ import annotations
 
 import ctypes as C
@@ -25,6 +27,9 @@ def _l():
             getattr(l, f"dxtlt_decode_{f}_blocks").argtypes = [vp, sz, vp, sz]
             getattr(l, f"dxtlt_decode_{f}_blocks_device").argtypes = [vp, sz, vp, sz, vp]
             getattr(l, f"dxtlt_decode_{f}_blocks").restype = getattr(l, f"dxtlt_decode_{f}_blocks_device").restype = i32
+        l.dxtlt_decode_bc7_blocks.argtypes = [vp, sz, vp, sz]
+        l.dxtlt_decode_bc7_blocks_device.argtypes = [vp, sz, vp, sz, vp]
+        l.dxtlt_decode_bc7_blocks.restype = l.dxtlt_decode_bc7_blocks_device.restype = i32
         l.dxtlt_count_pixel_differences.argtypes = [i32, vp, vp, sz, C.POINTER(C.c_uint64)]
         l.dxtlt_count_pixel_differences_device.argtypes = [i32, vp, vp, sz, vp, vp]
         l.dxtlt_count_pixel_differences.restype = l.dxtlt_count_pixel_differences_device.restype = i32
@@ -67,6 +72,27 @@ def decode_blocks(fmt: str, blocks, pixels) -> None:
     with torch.cuda.device(device):
         _check(getattr(l, f"dxtlt_decode_{fmt}_blocks_device")(s.ptr, s.nbytes, d.ptr, d.nbytes,
                                                                torch.cuda.current_stream(device).cuda_stream))
+
+
+def decode_bc7_blocks(blocks, pixels) -> None:
+    """BC7 (include/dxtlt_bc7_image.h): ``pixels`` receives 64 bytes per 16-byte block, the Direct3D 11 decoding; the reserved
+    encoding gives zeros.  Host buffers are decoded on the CPU by the code the kernels use, CUDA tensors on the device."""
+    from . import InvalidLength, OutputBufferTooSmall
+
+    (s, d), device = _bufs((blocks, pixels), (False, True))
+    if s.nbytes % 16 != 0:
+        raise InvalidLength(s.nbytes)
+    need = s.nbytes // 16 * DECODED_BLOCK_BYTES
+    if d.nbytes < need:
+        raise OutputBufferTooSmall(need, d.nbytes)
+    l = _l()
+    if device is None:
+        _check(l.dxtlt_decode_bc7_blocks(s.ptr, s.nbytes, d.ptr, d.nbytes))
+        return
+    import torch
+
+    with torch.cuda.device(device):
+        _check(l.dxtlt_decode_bc7_blocks_device(s.ptr, s.nbytes, d.ptr, d.nbytes, torch.cuda.current_stream(device).cuda_stream))
 
 
 def count_pixel_differences(fmt: str, blocks_a, blocks_b) -> int:

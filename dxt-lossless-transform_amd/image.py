@@ -10,6 +10,9 @@ buffer in one kernel (the untransformed blocks never touch memory); ``mip_level`
 ``decode_channel_image`` and ``untransform_decode_channel_image`` are the same two calls for ``"bc4"`` / ``"bc5"``: a pixel is
 1 / 2 bytes (r, or r, g) at ``y * pitch + bpp * x``, the default pitch ``bpp * width``, the one setting ``split_endpoints``.
 
+``decode_bc7_image`` and ``untransform_decode_bc7_image`` are the two calls for BC7 (include/dxtlt_bc7_image.h): RGBA8888, no
+settings, any ``first_block``.
+
 ``untransform_decode_images`` and ``decode_images`` write several images of one buffer in one call, for all five formats: a
 region is ``(first_block, width, height)``, and ``mip_chain`` lists the regions of a mip chain.
 ``untransform_decode_images_batch`` does the same for MANY transformed device buffers in one call: one launch per (format,
@@ -63,6 +66,11 @@ def _l():
         l.dxtlt_untransform_decode_images.argtypes = [i32, vp, C.c_size_t, rp, C.c_size_t, u8, b, b]
         l.dxtlt_image_mip_chain.argtypes = [u32, u32, u32, u64, rp, C.POINTER(u64)]
         l.dxtlt_untransform_decode_images_batch_device.argtypes = [C.POINTER(ImageBatchItem), C.c_size_t, vp]
+        l.dxtlt_decode_bc7_image_device.argtypes = [vp, u32, u32, vp, u64, vp]
+        l.dxtlt_untransform_decode_bc7_image_device.argtypes = [vp, u64, u64, u32, u32, vp, u64, vp]
+        l.dxtlt_untransform_decode_bc7_image.argtypes = [vp, C.c_size_t, u64, u32, u32, vp, u64]
+        for f in (l.dxtlt_decode_bc7_image_device, l.dxtlt_untransform_decode_bc7_image_device, l.dxtlt_untransform_decode_bc7_image):
+            f.restype = i32
         for f in (l.dxtlt_untransform_decode_images_device, l.dxtlt_decode_images_device, l.dxtlt_untransform_decode_images,
                   l.dxtlt_image_mip_chain, l.dxtlt_untransform_decode_images_batch_device):
             f.restype = i32
@@ -210,6 +218,50 @@ def untransform_decode_channel_image(fmt: str, transformed, width: int, height: 
         _check(l.dxtlt_untransform_decode_channel_image_device(code, src.ptr, total_blocks, first_block, width, height,
                                                                bool(split_endpoints), dst.ptr, pitch,
                                                                torch.cuda.current_stream(src.device).cuda_stream))
+    return out
+
+
+# ---- BC7 -> RGBA8888 (include/dxtlt_bc7_image.h) ---------------------------------------------------------------------------
+def decode_bc7_image(blocks, width: int, height: int, out=None, pitch=None):
+    """``blocks``: ceil(width / 4) * ceil(height / 4) BC7 blocks in block order, a CUDA tensor.  Returns ``out`` (a new tensor of
+    ``pitch * height`` bytes when None); ``pitch`` defaults to ``4 * width``."""
+    from . import InvalidLength, _Buf
+
+    src = _Buf(blocks, False)
+    if src.device is None:
+        raise TypeError("decode_bc7_image takes device tensors (the library has no host-pointer form of it)")
+    if src.nbytes < image_blocks(width, height) * 16:
+        raise InvalidLength(src.nbytes)
+    out, dst, pitch = _output(src, width, height, out, pitch)
+    import torch
+
+    with torch.cuda.device(src.device):
+        _check(_l().dxtlt_decode_bc7_image_device(src.ptr, width, height, dst.ptr, pitch, torch.cuda.current_stream(src.device).cuda_stream))
+    return out
+
+
+def untransform_decode_bc7_image(transformed, width: int, height: int, *, first_block: int = 0, total_blocks=None, out=None, pitch=None):
+    """``transformed``: the WHOLE buffer ``transform_bc7`` made, of ``total_blocks`` blocks (default: its length); the image is its
+    blocks [first_block, first_block + ceil(width / 4) * ceil(height / 4)), ``first_block`` any block.  Returns ``out``."""
+    from . import InvalidLength, _Buf
+
+    src = _Buf(transformed, False)
+    if src.nbytes % 16 != 0:
+        raise InvalidLength(src.nbytes)
+    if total_blocks is None:
+        total_blocks = src.nbytes // 16
+    if total_blocks * 16 > src.nbytes:
+        raise InvalidLength(src.nbytes)
+    out, dst, pitch = _output(src, width, height, out, pitch)
+    l = _l()
+    if src.device is None:
+        _check(l.dxtlt_untransform_decode_bc7_image(src.ptr, total_blocks * 16, first_block, width, height, dst.ptr, pitch))
+        return out
+    import torch
+
+    with torch.cuda.device(src.device):
+        _check(l.dxtlt_untransform_decode_bc7_image_device(src.ptr, total_blocks, first_block, width, height, dst.ptr, pitch,
+                                                           torch.cuda.current_stream(src.device).cuda_stream))
     return out
 
 

@@ -31,6 +31,7 @@
 #include "dxtlt_bc6h.h"
 #include "dxtlt_pixels.h"
 #include "dxtlt_bc7.h"
+#include "dxtlt_bc7_image.h"
 #include "dxtlt_color565.h"
 #include "dxtlt_decode.h"
 #include "dxtlt_estimator.h"
@@ -833,6 +834,29 @@ inline void untransform_decode_images(int32_t format, const uint8_t* transformed
     detail::check_device(dxtlt_untransform_decode_images(format, transformed, len, regions, region_count,
                                                          static_cast<uint8_t>(to_internal_variant(decorrelation_mode)),
                                                          split_alpha_endpoints, split_colour_endpoints));
+}
+
+// ADDITIVE: BC7 blocks -> RGBA8888 pixels (dxtlt_bc7_image.h; the Direct3D 11 decoder, the reserved encoding as zeros).  Blocks
+// to 64-byte Decoded4x4Block records, a block array in block order to a row-major image, and the same fused with the inverse of
+// dxtlt_transform_bc7: the image is the blocks [first_block, first_block + image blocks) of the transformed buffer, any first_block.
+inline void decode_bc7_blocks_device(const void* d_blocks, size_t len, void* d_pixels, size_t pixels_len, void* hip_stream)
+{
+    detail::check_device(dxtlt_decode_bc7_blocks_device(d_blocks, len, d_pixels, pixels_len, hip_stream));
+}
+inline void decode_bc7_image_device(const void* d_blocks, uint32_t width, uint32_t height, void* d_pixels, uint64_t pitch, void* hip_stream)
+{
+    detail::check_device(dxtlt_decode_bc7_image_device(d_blocks, width, height, d_pixels, pitch, hip_stream));
+}
+inline void untransform_decode_bc7_image_device(const void* d_transformed, uint64_t total_blocks, uint64_t first_block, uint32_t width,
+                                                uint32_t height, void* d_pixels, uint64_t pitch, void* hip_stream)
+{
+    detail::check_device(dxtlt_untransform_decode_bc7_image_device(d_transformed, total_blocks, first_block, width, height, d_pixels, pitch,
+                                                                   hip_stream));
+}
+inline void untransform_decode_bc7_image(const uint8_t* transformed, size_t len, uint64_t first_block, uint32_t width, uint32_t height,
+                                         uint8_t* pixels, uint64_t pitch)
+{
+    detail::check_device(dxtlt_untransform_decode_bc7_image(transformed, len, first_block, width, height, pixels, pitch));
 }
 
 }  // namespace api
