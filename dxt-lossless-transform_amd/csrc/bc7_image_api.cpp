@@ -1,5 +1,6 @@
-// bc7_image_api.cpp -- C ABI of the BC7 decoders (include/dxtlt_bc7_image.h); kernels in bc7_image_kernels.hip, the decoder itself
-// in bc7_decode.h.  Every argument is checked before a device is touched.
+// bc7_image_api.cpp -- C ABI of the BC7 decoders (include/dxtlt_bc7_image.h); kernels in bc7_image_kernels.hip and, for several
+// images of one buffer, bc7_image_regions_kernels.hip; the decoder itself in bc7_decode.h.  Every argument is checked before a
+// device is touched.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -10,8 +11,12 @@
 #include "bc7_decode.h"
 #include "bc7_image_launch.h"
 #include "host_common.h"
+#include "image_launch.h"   // image_regions_defect
+#include "image_region_groups.h"
 
+using dxtlt_host::empty_region;
 using dxtlt_host::fail;
+using dxtlt_host::for_each_region_group;
 using dxtlt_host::kInvalidArgument;
 using dxtlt_host::kInvalidLength;
 using dxtlt_host::kOk;
@@ -53,6 +58,18 @@ int32_t check_range(uint64_t total_blocks, uint64_t first_block, uint64_t blocks
         return fail(kInvalidArgument, "first_block + blocks of the image exceeds total_blocks");
     return kOk;
 }
+
+// ---- several images of one buffer --------------------------------------------------------------------------------------
+// the checks of the region calls, in the documented order: those of dxtlt_untransform_decode_images_device minus format and
+// settings; *nothing = there is no non-empty region (DXTLT_OK, nothing to do)
+int32_t check_regions(const void* buffer, uint64_t total_blocks, const DxtltImageRegion* regions, size_t count, bool* nothing)
+{
+    if (const char* defect = dxtlt_host::image_regions_defect(0, buffer, total_blocks, regions, count, 0, nothing, true))
+        return fail(kInvalidArgument, defect);
+    return kOk;
+}
+
+inline dxtlt::ImageSink sink_of(const DxtltImageRegion& r) { return dxtlt::make_image_sink(r.pixels, r.pitch, r.width, r.height); }
 
 }  // namespace
 
@@ -139,6 +156,119 @@ int32_t dxtlt_untransform_decode_bc7_image(const uint8_t* transformed, size_t le
     HIP_TRY(hipMemcpy2DAsync(pixels, pitch, d_out, d_pitch, row_bytes, height, hipMemcpyDeviceToHost, st), "D2H copy");
     HIP_TRY(hipStreamSynchronize(st), "stream synchronize");
     return kOk;
+}
+
+int32_t dxtlt_untransform_decode_bc7_images_device(const void* d_transformed, uint64_t total_blocks, const DxtltImageRegion* regions,
+                                                   size_t region_count, void* hip_stream)
+{
+    bool nothing = true;
+    if (int32_t rc = check_regions(d_transformed, total_blocks, regions, region_count, &nothing); rc != kOk || nothing)
+        return rc;
+    HIP_TRY(for_each_region_group(
+                regions, region_count, [&](size_t i) { return sink_of(regions[i]); },
+                [&](const dxtlt::ImageRegionTable& tab) {
+                    return dxtlt::bc7::launch_untransform_decode_image_regions(d_transformed, total_blocks, tab,
+                                                                               static_cast<hipStream_t>(hip_stream));
+                }),
+            "kernel launch");
+    return kOk;
+}
+
+int32_t dxtlt_decode_bc7_images_device(const void* d_blocks, uint64_t total_blocks, const DxtltImageRegion* regions, size_t region_count,
+                                       void* hip_stream)
+{
+    bool nothing = true;
+    if (int32_t rc = check_regions(d_blocks, total_blocks, regions, region_count, &nothing); rc != kOk || nothing)
+        return rc;
+    HIP_TRY(for_each_region_group(
+                regions, region_count, [&](size_t i) { return sink_of(regions[i]); },
+                [&](const dxtlt::ImageRegionTable& tab) {
+                    return dxtlt::bc7::launch_decode_image_regions(d_blocks, total_blocks, tab, static_cast<hipStream_t>(hip_stream));
+                }),
+            "kernel launch");
+    return kOk;
+}
+
+int32_t dxtlt_untransform_decode_bc7_images(const uint8_t* transformed, size_t len, const DxtltImageRegion* regions, size_t region_count)
+{
+    const uint64_t total_blocks = len / 16;
+    bool nothing = true;
+    if (int32_t rc = check_regions(transformed, total_blocks, regions, region_count, &nothing); rc != kOk || nothing)
+        return rc;
+    if (len % 16 != 0)
+        return fail(kInvalidLength, "len is not a multiple of the block size");
+
+    // as dxtlt_untransform_decode_images: one upload of the transformed buffer, the device path into staging -- region after
+    // region, every base a multiple of 16 and its rows a multiple of 16 bytes apart -- and one download of the rows per region
+    auto staged_pitch = [](const DxtltImageRegion& r) { return (4 * (uint64_t)r.width + 15) & ~(uint64_t)15; };
+    uint64_t out_bytes = 0;
+    for (size_t i = 0; i < region_count; ++i)
+        if (!empty_region(regions[i]))
+            out_bytes += staged_pitch(regions[i]) * regions[i].height;
+    void *d_in = nullptr, *d_out = nullptr;
+    hipStream_t st = nullptr;
+    if (int32_t rc = dxtlt_host::acquire_staging((size_t)std::max<uint64_t>(len, out_bytes), &d_in, &d_out, &st); rc != kOk)
+        return rc;
+    HIP_TRY(hipMemcpyAsync(d_in, transformed, len, hipMemcpyHostToDevice, st), "H2D copy");
+    uint64_t at = 0;   // the regions are visited in list order, here and in the download below
+    HIP_TRY(for_each_region_group(
+                regions, region_count,
+                [&](size_t i) {
+                    const dxtlt::ImageSink img = dxtlt::make_image_sink(static_cast<uint8_t*>(d_out) + at, staged_pitch(regions[i]),
+                                                                        regions[i].width, regions[i].height);
+                    at += staged_pitch(regions[i]) * regions[i].height;
+                    return img;
+                },
+                [&](const dxtlt::ImageRegionTable& tab) {
+                    return dxtlt::bc7::launch_untransform_decode_image_regions(d_in, total_blocks, tab, st);
+                }),
+            "kernel launch");
+    at = 0;
+    for (size_t i = 0; i < region_count; ++i) {
+        const DxtltImageRegion& r = regions[i];
+        if (empty_region(r))
+            continue;
+        HIP_TRY(hipMemcpy2DAsync(r.pixels, r.pitch, static_cast<uint8_t*>(d_out) + at, staged_pitch(r), 4 * (uint64_t)r.width, r.height,
+                                 hipMemcpyDeviceToHost, st),
+                "D2H copy");
+        at += staged_pitch(r) * r.height;
+    }
+    HIP_TRY(hipStreamSynchronize(st), "stream synchronize");
+    return kOk;
+}
+
+int32_t dxtlt_debug_plan_bc7_images(uint64_t total_blocks, const DxtltImageRegion* regions, size_t region_count,
+                                    DxtltBc7ImagesLaunch* out, size_t cap)
+{
+    // the device call's checks but for the buffer pointer, which this call does not have: any non-NULL address stands in
+    bool nothing = true;
+    if (check_regions(&nothing, total_blocks, regions, region_count, &nothing) != kOk)
+        return -1;
+    if (nothing)
+        return 0;
+    // the device call's walk: the same groups, the same plan of each group's covering range, records in the place of launches
+    size_t launches = 0, group_first = 0;
+    bool group_open = false;
+    const hipError_t e = for_each_region_group(
+        regions, region_count,
+        [&](size_t i) {
+            if (!group_open)
+                group_first = i, group_open = true;
+            return sink_of(regions[i]);
+        },
+        [&](const dxtlt::ImageRegionTable& tab) {
+            uint64_t first = 0, n = 0;
+            if (!dxtlt::covering_range(tab, total_blocks, first, n))
+                return hipErrorInvalidValue;
+            group_open = false;
+            return dxtlt::bc7::for_each_range_launch(total_blocks, first, first + n, [&](uint64_t granule, uint64_t granules, bool tail) {
+                if (out != nullptr && launches < cap)
+                    out[launches] = DxtltBc7ImagesLaunch{(uint32_t)group_first, tab.count, granule, granules, tail ? 1u : 0u, 0u};
+                ++launches;
+                return hipSuccess;
+            });
+        });
+    return e == hipSuccess ? (int32_t)launches : -1;
 }
 
 }  // extern "C"

@@ -3,15 +3,16 @@
 //     wave's 4 KiB of pixels through LDS, every store instruction 1 KiB of consecutive bytes);
 //   * decode_bc7_image_kernel: a block array in block order -> a row-major image, one block per lane, the stores of the BC2 / BC3
 //     plain decoder (store_block_pixels, image_store.h);
-//   * bc7_inverse_image: the inverse granule sort (granule_sort.h over Bc7Codec) with a staging sink (Bc7PixelSink) in the place
-//     of its block store: the blocks are decoded in the sorted domain, where the mode is wave-uniform, and their pixels go
-//     through LDS to block order, so that the untransformed blocks never touch memory.
+//   * bc7_inverse_image: the inverse granule sort (granule_sort.h over Bc7Codec) with a staging sink (Bc7PixelSink,
+//     bc7_image_sinks.h) in the place of its block store: the blocks are decoded in the sorted domain, where the mode is
+//     wave-uniform, and their pixels go through LDS to block order, so that the untransformed blocks never touch memory.
 // The decoder is bc7_decode.h.  Its mode switch is per lane in the first two kernels, which decode in BLOCK order (a wave runs the
 // arm of every mode that occurs among its 64 blocks: on a buffer of mixed modes they are bound by instruction issue, not by
 // memory), and wave-uniform in the third.
 #include "bc7_decode.h"
 #include "bc7_granule_codec.h"
 #include "bc7_image_launch.h"
+#include "bc7_image_sinks.h"
 #include "image_store.h"
 #include "launch_grid.h"
 
@@ -25,26 +26,6 @@ using granule::kT;
 constexpr int kThreads = 256;
 constexpr int kRowStride = 64 + 4;            // u32x4 units: 64 lanes + 64 bytes of padding (bcn_decode.hip)
 constexpr int kWaveStage = 4 * kRowStride;    // four pixel rows per wave
-
-__device__ __forceinline__ void decode_px(u32x4 q, uint32_t (&px)[16])
-{
-    const B128 b = {{q.x, q.y, q.z, q.w}};
-    decode_bc7_block(b, px);
-}
-
-// block `b` of the array: a 16-byte load when the block pointer is a multiple of 16, byte loads otherwise
-template <bool ALIGNED>
-__device__ __forceinline__ u32x4 load_block(const uint8_t* __restrict__ in, uint64_t b)
-{
-    if constexpr (ALIGNED) {
-        return __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(in) + b);
-    } else {
-        uint32_t q[4] = {0, 0, 0, 0};
-        for (int i = 0; i < 16; ++i)
-            q[i >> 2] |= (uint32_t)in[16 * b + i] << (8 * (i & 3));
-        return u32x4{q[0], q[1], q[2], q[3]};
-    }
-}
 
 // ---- blocks -> Decoded4x4Block -----------------------------------------------------------------------------------------
 // `out` is a multiple of 16
@@ -105,92 +86,7 @@ decode_bc7_image_kernel(const uint8_t* __restrict__ in, ImageSink img, uint64_t 
     store_block_pixels(img, b, px);
 }
 
-// ---- the inverse granule sort with a pixel sink --------------------------------------------------------------------------
-// A staging sink of inverse_granule (granule_sort.h, BlockSink).  The inverse has every block twice: in the sorted domain, where
-// lane j holds sorted block j and a wave's 64 blocks are of one mode except where two classes meet, and -- behind its last
-// barrier -- in block order, where a wave's 64 lanes hold 64 consecutive blocks of the image.  The decoder's mode switch wants the
-// first, the stores want the second, so the pixels cross instead of the blocks: hold() decodes sorted block j into registers,
-// stage() puts two of its four pixel rows into LDS (row k of the part at k * 16 KiB + 16 j: consecutive lanes, consecutive 16
-// bytes), store_staged() fetches them for the lane's block-order block from its sorted position and stores them as the BC2 / BC3
-// decoders do, 1 KiB of consecutive bytes of a pixel row per wave instruction; then the other two rows take the same way.  By then
-// nothing else lives in LDS, so the 32 KiB of a part start at byte 0 and are the kernel's whole allocation.
-// Block `b` of the buffer is block b - first_block of the image when it lies in [first_block, first_block + blocks); every block
-// of a covered granule is decoded, the ones outside are dropped at the store.
-// What else was built and measured (16384 x 16384; ms on a buffer of mode 6 only / the uniform / the skewed mode mix;
-// profiles/bc7_image_bench.json, "ab"; docs/IMAGE_DECODE.md):
-//   * decode in block order behind the un-sort, the mode switch per lane, 19 KiB of LDS: 0.238 / 1.431 / 1.058 -- a wave ran the
-//     arm of every mode among its 64 blocks;
-//   * this sink with all four rows in one part, 64 KiB of LDS, two workgroups per CU: 0.290 / 0.476 / 0.452;
-//   * with one row per part, 19 KiB, six more barriers: 0.249 / 0.412 / 0.367;
-//   * two rows per part (here), 32 KiB, five workgroups per CU by the 95 VGPRs: 0.231 / 0.401 / 0.355.
-// rows [r0, r0 + ROWS) of block `b` of the image: store_block_pixels (image_store.h) for a part of a block
-template <int ROWS>
-__device__ __forceinline__ void store_block_rows(const ImageSink& img, uint64_t b, int r0, const u32x4 (&rows)[ROWS])
-{
-    const BlockPlace p = place_block<4>(img, b);
-    const bool aligned16 = ((reinterpret_cast<uintptr_t>(img.pixels) | img.pitch) & 15) == 0;   // uniform
-    if (p.cols == 4 && p.rows == 4) {
-#pragma unroll
-        for (int k = 0; k < ROWS; ++k) {
-            uint8_t* row = block_row(img, p, r0 + k);
-            if (aligned16)
-                store_streaming16(row, rows[k]);
-            else
-                *reinterpret_cast<u32x4_align4*>(row) = rows[k];
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < ROWS; ++k) {
-            uint32_t* row = reinterpret_cast<uint32_t*>(block_row(img, p, r0 + k));
-            const uint32_t px[4] = {rows[k].x, rows[k].y, rows[k].z, rows[k].w};
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-                if ((uint32_t)(r0 + k) < p.rows && (uint32_t)c < p.cols)
-                    row[c] = px[c];
-        }
-    }
-}
-
-struct Bc7PixelSink {
-    static constexpr bool kStaged = true;
-    static constexpr int kParts = 2, kRows = 4 / kParts;   // pixel rows per part
-    static constexpr int kStageBytes = kRows * kT * 16;
-    struct Held {
-        uint32_t px[16];
-    };
-    ImageSink img;
-    uint64_t first_block, blocks;
-
-    __device__ __forceinline__ Held hold(const B128& b) const
-    {
-        Held h;
-        decode_bc7_block(b, h.px);
-        return h;
-    }
-
-    // row k of the part of sorted block j at k * 16 KiB + 16 j: consecutive lanes, consecutive 16 bytes
-    __device__ __forceinline__ void stage(uint8_t* lds, int j, const Held& h, int part) const
-    {
-#pragma unroll
-        for (int k = 0; k < kRows; ++k) {
-            const int r = part * kRows + k;
-            granule::lds_at<u32x4>(lds, k * (kT * 16) + 16 * j) = u32x4{h.px[4 * r], h.px[4 * r + 1], h.px[4 * r + 2], h.px[4 * r + 3]};
-        }
-    }
-
-    __device__ __forceinline__ void store_staged(uint8_t* lds, uint64_t b, int pos, int part) const
-    {
-        const uint64_t at = b - first_block;   // wraps for b < first_block
-        if (at >= blocks)
-            return;
-        u32x4 rows[kRows];
-#pragma unroll
-        for (int k = 0; k < kRows; ++k)
-            rows[k] = granule::lds_at<u32x4>(lds, k * (kT * 16) + 16 * pos);
-        store_block_rows<kRows>(img, at, part * kRows, rows);
-    }
-};
-
+// ---- the inverse granule sort with a pixel sink (Bc7PixelSink, bc7_image_sinks.h) -------------------------------------------
 // Full granules: workgroup g is granule first_granule_block / 1024 + g of the main part (part_blocks blocks, soa = its byte 0).
 // TAIL: one workgroup, soa = the tail part's byte 0, first_granule_block = the tail part's first block, n_tail its blocks.
 template <int LANES, bool TAIL>

@@ -45,6 +45,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <type_traits>
 
 #include "bc7_fields.h"   // B128, kGranule
 #include "granule_launch.h"
@@ -294,6 +295,18 @@ struct BlockSink {
     __device__ __forceinline__ void store(uint8_t* dst, uint64_t, int j, u32x4 q) const { store_streaming16(dst + (uint64_t)j * 16, q); }
 };
 
+// A staged sink may look at the granule as a whole before its parts: one that has a type Prepared answers prepare(the granule's
+// first block, its blocks) -- the same in every lane -- and gets the answer back as store_staged's last argument.
+struct NothingPrepared {};
+template <typename Sink, typename = void>
+struct PreparedOf {
+    using type = NothingPrepared;
+};
+template <typename Sink>
+struct PreparedOf<Sink, std::void_t<typename Sink::Prepared>> {
+    using type = typename Sink::Prepared;
+};
+
 template <typename Sink>
 constexpr int sink_lds_bytes(int own)
 {
@@ -388,6 +401,11 @@ __device__ __forceinline__ void inverse_granule(const uint8_t* __restrict__ soa,
         }
     }
     if constexpr (Sink::kStaged) {
+        using Prepared = typename PreparedOf<Sink>::type;
+        constexpr bool kPrepares = !std::is_same_v<Prepared, NothingPrepared>;
+        Prepared prepared{};
+        if constexpr (kPrepares)
+            prepared = sink.prepare(granule_first, (uint64_t)n);
         __syncthreads();   // the records are in registers: all of LDS is the sink's
         typename Sink::Held held[V];
 #pragma unroll
@@ -407,8 +425,12 @@ __device__ __forceinline__ void inverse_granule(const uint8_t* __restrict__ soa,
             __syncthreads();
 #pragma unroll
             for (int v = 0; v < V; ++v)
-                if (cls[v] < kClasses)
-                    sink.store_staged(lds, granule_first + (uint64_t)(v * LANES + t), pos[v], part);
+                if (cls[v] < kClasses) {
+                    if constexpr (kPrepares)
+                        sink.store_staged(lds, granule_first + (uint64_t)(v * LANES + t), pos[v], part, prepared);
+                    else
+                        sink.store_staged(lds, granule_first + (uint64_t)(v * LANES + t), pos[v], part);
+                }
         }
     } else {
         if constexpr (!TAIL)

@@ -8,19 +8,23 @@
 #include "../../include/dxtlt_image.h"
 #include "host_common.h"
 #include "image_launch.h"
+#include "image_region_groups.h"
 
+using dxtlt_host::empty_region;
 using dxtlt_host::fail;
+using dxtlt_host::for_each_region_group;
 using dxtlt_host::kInvalidArgument;
 using dxtlt_host::kInvalidLength;
 using dxtlt_host::kOk;
 
 // The first defect of an image-region call's arguments in the documented order -- all of them DXTLT_E_INVALID_ARGUMENT -- or
-// nullptr; *nothing = there is no non-empty region.  (image_launch.h: the batch call runs the same checks per item.)
+// nullptr; *nothing = there is no non-empty region.  (image_launch.h: the batch call runs the same checks per item; the BC7
+// region calls, which have no format argument and no settings, pass bc7.)
 const char* dxtlt_host::image_regions_defect(int32_t fmt, const void* buffer, uint64_t total_blocks, const DxtltImageRegion* regions,
-                                             size_t count, uint8_t mode, bool* nothing)
+                                             size_t count, uint8_t mode, bool* nothing, bool bc7)
 {
     *nothing = true;
-    if (fmt < 1 || fmt > 5)
+    if (!bc7 && (fmt < 1 || fmt > 5))
         return "format must be 1 (BC1) .. 5 (BC5)";
     if (count == 0)
         return nullptr;
@@ -32,7 +36,7 @@ const char* dxtlt_host::image_regions_defect(int32_t fmt, const void* buffer, ui
         return nullptr;
     if (buffer == nullptr)
         return "NULL buffer with a non-empty region";
-    const uint64_t bpp = fmt <= 3 ? 4 : fmt == 4 ? 1 : 2, multiple = fmt <= 3 ? 4 : bpp;
+    const uint64_t bpp = bc7 || fmt <= 3 ? 4 : fmt == 4 ? 1 : 2, multiple = bc7 || fmt <= 3 ? 4 : bpp;
     auto blocks_of = [](uint32_t width, uint32_t height) { return (((uint64_t)width + 3) / 4) * (((uint64_t)height + 3) / 4); };
     uint64_t end = 0;   // of the previous non-empty region
     for (size_t i = 0; i < count; ++i) {
@@ -51,7 +55,7 @@ const char* dxtlt_host::image_regions_defect(int32_t fmt, const void* buffer, ui
             return "regions must come in ascending block order and must not overlap";
         end = r.first_block + blocks_of(r.width, r.height);
     }
-    if (fmt <= 3 && mode > 3)
+    if (!bc7 && fmt <= 3 && mode > 3)
         return "decorrelation_mode must be 0..3";
     return nullptr;
 }
@@ -116,7 +120,6 @@ int32_t check_channel_image(int32_t fmt, const void* blocks, const void* pixels,
 
 // ---- several images of one buffer --------------------------------------------------------------------------------------
 inline uint64_t bpp_of(int32_t fmt) { return fmt <= 3 ? 4 : channel_bpp(fmt); }
-inline bool empty_region(const DxtltImageRegion& r) { return r.width == 0 || r.height == 0; }
 
 int32_t check_any_format(int32_t fmt)
 {
@@ -133,27 +136,6 @@ int32_t check_regions(int32_t fmt, const void* buffer, uint64_t total_blocks, co
     if (const char* defect = dxtlt_host::image_regions_defect(fmt, buffer, total_blocks, regions, count, mode, nothing))
         return fail(kInvalidArgument, defect);
     return kOk;
-}
-
-// The non-empty regions in groups of at most DXTLT_IMAGE_REGIONS_PER_LAUNCH consecutive ones: sink_of(i) is region i's image,
-// launch(table) enqueues one group
-template <typename SINK_OF, typename LAUNCH>
-hipError_t for_each_region_group(const DxtltImageRegion* regions, size_t count, const SINK_OF& sink_of, const LAUNCH& launch)
-{
-    static_assert(DXTLT_IMAGE_REGIONS_PER_LAUNCH == dxtlt::kImageRegionsPerLaunch, "the header's constant is the kernels'");
-    dxtlt::ImageRegionTable tab;
-    dxtlt::clear_regions(tab);
-    for (size_t i = 0; i < count; ++i) {
-        if (empty_region(regions[i]))
-            continue;
-        dxtlt::append_region(tab, sink_of(i), regions[i].first_block);
-        if (tab.count == (uint32_t)dxtlt::kImageRegionsPerLaunch) {
-            if (hipError_t e = launch(tab); e != hipSuccess)
-                return e;
-            dxtlt::clear_regions(tab);
-        }
-    }
-    return tab.count != 0 ? launch(tab) : hipSuccess;
 }
 
 }  // namespace

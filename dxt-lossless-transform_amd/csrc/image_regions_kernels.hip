@@ -209,26 +209,6 @@ ImageKernelsOf<RegionChannelSink> pick_region_channel_kernels(bool split_endpoin
     return {inv_tiled_regions_channel_image<FMT, false, TH>, inv_tiled_shift_regions_channel_image<FMT, false, SH>};
 }
 
-// the range that covers the table's regions; false when the table is not one the kernels take
-bool covering_range(const ImageRegionTable& tab, uint64_t total_blocks, uint64_t& first, uint64_t& n)
-{
-    if (tab.count == 0 || tab.count > (uint32_t)kImageRegionsPerLaunch)
-        return false;
-    uint64_t end = 0;
-    for (uint32_t i = 0; i < tab.count; ++i) {
-        if (tab.blocks[i] == 0 || tab.blocks[i] != image_blocks(tab.img[i]) || tab.first[i] < end || tab.first[i] > total_blocks ||
-            tab.blocks[i] > total_blocks - tab.first[i])
-            return false;
-        end = tab.first[i] + tab.blocks[i];
-    }
-    for (int i = (int)tab.count; i < kImageRegionsPerLaunch; ++i)
-        if (tab.blocks[i] != 0)
-            return false;
-    first = tab.first[0];
-    n = end - first;
-    return true;
-}
-
 }  // namespace
 
 hipError_t launch_decode_image_regions(int fmt, const void* blocks, uint64_t total_blocks, const ImageRegionTable& tab,

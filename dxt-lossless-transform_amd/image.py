@@ -15,6 +15,7 @@ settings, any ``first_block``.
 
 ``untransform_decode_images`` and ``decode_images`` write several images of one buffer in one call, for all five formats: a
 region is ``(first_block, width, height)``, and ``mip_chain`` lists the regions of a mip chain.
+``untransform_decode_bc7_images`` and ``decode_bc7_images`` are the same two calls for BC7 (no ``fmt``, no settings).
 ``untransform_decode_images_batch`` does the same for MANY transformed device buffers in one call: one launch per (format,
 settings) present in the batch, whatever the number of buffers."""
 from __future__ import annotations
@@ -33,6 +34,8 @@ _CHANNEL_BPP = {"bc4": 1, "bc5": 2}
 _ALL_FMT = {**_FMT, **_CHANNEL_FMT}
 _ALL_BLOCK = {**_BLOCK, **_CHANNEL_BLOCK}
 _ALL_BPP = {"bc1": 4, "bc2": 4, "bc3": 4, **_CHANNEL_BPP}
+_REGION_BLOCK = {**_ALL_BLOCK, "bc7": 16}   # the region helpers serve the BC7 calls too, which have entry points of their own
+_REGION_BPP = {**_ALL_BPP, "bc7": 4}
 _declared = False
 
 
@@ -69,7 +72,11 @@ def _l():
         l.dxtlt_decode_bc7_image_device.argtypes = [vp, u32, u32, vp, u64, vp]
         l.dxtlt_untransform_decode_bc7_image_device.argtypes = [vp, u64, u64, u32, u32, vp, u64, vp]
         l.dxtlt_untransform_decode_bc7_image.argtypes = [vp, C.c_size_t, u64, u32, u32, vp, u64]
-        for f in (l.dxtlt_decode_bc7_image_device, l.dxtlt_untransform_decode_bc7_image_device, l.dxtlt_untransform_decode_bc7_image):
+        l.dxtlt_untransform_decode_bc7_images_device.argtypes = [vp, u64, rp, C.c_size_t, vp]
+        l.dxtlt_decode_bc7_images_device.argtypes = [vp, u64, rp, C.c_size_t, vp]
+        l.dxtlt_untransform_decode_bc7_images.argtypes = [vp, C.c_size_t, rp, C.c_size_t]
+        for f in (l.dxtlt_decode_bc7_image_device, l.dxtlt_untransform_decode_bc7_image_device, l.dxtlt_untransform_decode_bc7_image,
+                  l.dxtlt_untransform_decode_bc7_images_device, l.dxtlt_decode_bc7_images_device, l.dxtlt_untransform_decode_bc7_images):
             f.restype = i32
         for f in (l.dxtlt_untransform_decode_images_device, l.dxtlt_decode_images_device, l.dxtlt_untransform_decode_images,
                   l.dxtlt_image_mip_chain, l.dxtlt_untransform_decode_images_batch_device):
@@ -284,7 +291,7 @@ def _region_table(fmt, src, regions, outs, pitches):
         raise ValueError("outs and pitches must have one entry per region")
     table, keep = (ImageRegion * max(1, len(regions)))(), []
     for i, (first, width, height) in enumerate(regions):
-        outs[i], dst, pitch = _output(src, width, height, outs[i], pitches[i], _ALL_BPP[fmt])
+        outs[i], dst, pitch = _output(src, width, height, outs[i], pitches[i], _REGION_BPP[fmt])
         keep.append(dst)
         table[i] = ImageRegion(first, width, height, dst.ptr, pitch)
     return outs, table, len(regions), keep
@@ -293,7 +300,7 @@ def _region_table(fmt, src, regions, outs, pitches):
 def _whole_buffer(fmt, buffer, total_blocks):
     from . import InvalidLength, _Buf
 
-    src, bs = _Buf(buffer, False), _ALL_BLOCK[fmt]
+    src, bs = _Buf(buffer, False), _REGION_BLOCK[fmt]
     if src.nbytes % bs != 0:
         raise InvalidLength(src.nbytes)
     if total_blocks is None:
@@ -340,6 +347,39 @@ def decode_images(fmt: str, blocks, regions, *, total_blocks=None, outs=None, pi
     with torch.cuda.device(src.device):
         _check(_l().dxtlt_decode_images_device(_ALL_FMT[fmt], src.ptr, total_blocks, table, count,
                                                torch.cuda.current_stream(src.device).cuda_stream))
+    del keep
+    return outs
+
+
+def untransform_decode_bc7_images(transformed, regions, *, total_blocks=None, outs=None, pitches=None):
+    """``untransform_decode_images`` for BC7 (include/dxtlt_bc7_image.h): every region ``(first_block, width, height)`` of the
+    WHOLE buffer ``transform_bc7`` made to an RGBA8888 image of its own, every granule un-sorted and decoded once.  Regions as
+    ``mip_chain`` returns them; host buffers or CUDA tensors (torch's current stream).  Returns the list of outputs."""
+    src, total_blocks = _whole_buffer("bc7", transformed, total_blocks)
+    outs, table, count, keep = _region_table("bc7", src, regions, outs, pitches)
+    l = _l()
+    if src.device is None:
+        _check(l.dxtlt_untransform_decode_bc7_images(src.ptr, total_blocks * 16, table, count))
+        return outs
+    import torch
+
+    with torch.cuda.device(src.device):
+        _check(l.dxtlt_untransform_decode_bc7_images_device(src.ptr, total_blocks, table, count,
+                                                            torch.cuda.current_stream(src.device).cuda_stream))
+    del keep
+    return outs
+
+
+def decode_bc7_images(blocks, regions, *, total_blocks=None, outs=None, pitches=None):
+    """The same from a BC7 block array in block order, a CUDA tensor (the library has no host-pointer form of it)."""
+    src, total_blocks = _whole_buffer("bc7", blocks, total_blocks)
+    if src.device is None:
+        raise TypeError("decode_bc7_images takes device tensors (the library has no host-pointer form of it)")
+    outs, table, count, keep = _region_table("bc7", src, regions, outs, pitches)
+    import torch
+
+    with torch.cuda.device(src.device):
+        _check(_l().dxtlt_decode_bc7_images_device(src.ptr, total_blocks, table, count, torch.cuda.current_stream(src.device).cuda_stream))
     del keep
     return outs
 
