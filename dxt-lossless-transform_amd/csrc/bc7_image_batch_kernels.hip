@@ -1,0 +1,109 @@
+// bc7_image_batch_kernels.hip -- the RGBA8888 images of MANY BC7 transformed buffers in at most two launches on gfx950
+// (dxtlt_untransform_decode_bc7_images_batch_device, include/dxtlt_bc7_image.h; docs/IMAGE_DECODE.md, "Many BC7 buffers in one
+// call").
+//
+// The lookup of the batch untransform (bc7_batch_granules / bc7_batch_tails, bc7_kernels.hip) in front of the fused kernels of one
+// buffer (bc7_inverse_images, bc7_image_regions_kernels.hip): workgroup b of the granule launch finds its entry -- a group of up
+// to sixteen regions of one buffer -- through coarse[b / 64] and a short scan, and un-sorts and decodes ONE granule of that buffer's
+// main part; the tail launch has one workgroup per entry whose range reaches its buffer's tail part.  Each block's pixels go to
+// whichever region of the entry's table owns the block (Bc7RegionPixelSinkOf, bc7_image_sinks.h).  The table lies in device memory
+// beside the entries (DeviceRegionTable, device_region_table.h); its address and everything else of the entry come out of scalar
+// loads, so the table is walked exactly as the kernel-argument table of the single-buffer kernels is: by the two loops of
+// image_regions.h, with the loop counter as the only index, on the scalar unit.  No lane and no workgroup leaves before
+// inverse_granule's barriers.
+#include <cstddef>
+
+#include "bc7_image_batch_launch.h"
+#include "bc7_image_sinks.h"
+#include "device_region_table.h"
+
+namespace dxtlt {
+namespace bc7 {
+namespace {
+
+using granule::inverse_granule;
+
+using BatchRegionPixelSink = Bc7RegionPixelSinkOf<DeviceRegionTable>;
+
+// An entry as the workgroup sees it: scalar loads (the entry's address is uniform), the buffer pointer tagged as global memory --
+// a pointer that was loaded from memory is a generic one to the compiler
+struct EntryView {
+    const uint8_t* src;
+    uint64_t regions_at, main_blocks, first_granule;
+    uint32_t first_wg, region_count, tail;
+};
+
+__device__ __forceinline__ EntryView load_entry(const ImageBatchEntry* entry)
+{
+    const uint64_t* q = reinterpret_cast<const uint64_t*>(entry);
+    const uint32_t* w = reinterpret_cast<const uint32_t*>(entry);
+    EntryView v;
+    v.src = (const uint8_t*)(global_cptr)q[0];
+    v.regions_at = q[1];
+    v.main_blocks = q[2];
+    v.first_granule = q[3];
+    v.first_wg = w[8];
+    v.region_count = w[9];
+    v.tail = w[10];
+    // everything of the entry stays on the scalar unit
+    uint64_t at = reinterpret_cast<uintptr_t>(v.src);
+    asm("" : "+s"(at), "+s"(v.regions_at), "+s"(v.main_blocks), "+s"(v.first_granule));
+    asm("" : "+s"(v.first_wg), "+s"(v.region_count), "+s"(v.tail));
+    v.src = (const uint8_t*)(global_cptr)at;
+    return v;
+}
+static_assert(offsetof(ImageBatchEntry, src) == 0 && offsetof(ImageBatchEntry, regions) == 8 && offsetof(ImageBatchEntry, main_blocks) == 16 &&
+                  offsetof(ImageBatchEntry, first_granule) == 24 && offsetof(ImageBatchEntry, first_wg) == 32 &&
+                  offsetof(ImageBatchEntry, region_count) == 36 && offsetof(ImageBatchEntry, tail) == 40,
+              "load_entry reads ImageBatchEntry by qword and dword offsets");
+
+// Workgroup b finds its entry as bc7_batch_granules does -- `coarse[b / 64]` is the entry of workgroup 64 * (b / 64), a short
+// scan from there, every load uniform -- and runs one granule of the entry's buffer.
+__global__ void __launch_bounds__(256)
+bc7_batch_inverse_images(const ImageBatchEntry* __restrict__ entries, const uint32_t* __restrict__ coarse, uint32_t n_entries)
+{
+    const uint32_t b = blockIdx.x;
+    uint32_t i = coarse[b >> 6];
+    while (i + 1 < n_entries && entries[i + 1].first_wg <= b)
+        ++i;
+    const EntryView e = load_entry(entries + i);
+    const BatchRegionPixelSink sink{DeviceRegionTable{e.regions_at, e.region_count}};
+    // The granule's first block, pinned to scalar registers: left to the compiler, the sum that makes it stayed split, one half in
+    // a vector register through the decode -- 97 VGPRs, the fifth wave per SIMD gone (docs/IMAGE_DECODE.md, "Many BC7 buffers in
+    // one call", resources).
+    uint64_t first = (e.first_granule + (b - e.first_wg)) * kT;
+    asm volatile("" : "+s"(first));
+    inverse_granule<Bc7Codec, 256, false, BatchRegionPixelSink>(e.src, nullptr, e.main_blocks, first, 0, sink);
+}
+
+// One workgroup per tail entry, with the arguments bc7_inverse_images<256, true> gets: the tail part's byte 0, its blocks, and
+// main_blocks as its first block
+__global__ void __launch_bounds__(256)
+bc7_batch_inverse_image_tails(const ImageBatchEntry* __restrict__ tails)
+{
+    const EntryView e = load_entry(tails + blockIdx.x);
+    const BatchRegionPixelSink sink{DeviceRegionTable{e.regions_at, e.region_count}};
+    inverse_granule<Bc7Codec, 256, true, BatchRegionPixelSink>(e.src, nullptr, e.tail, e.main_blocks, (int)e.tail, sink);
+}
+
+}  // namespace
+
+hipError_t launch_image_batch(const ImageBatchEntry* d_entries, const uint32_t* d_coarse, uint32_t n_entries, uint32_t granule_wgs,
+                              const ImageBatchEntry* d_tails, uint32_t n_tails, hipStream_t stream)
+{
+    if (granule_wgs > kMaxBatchWorkgroups || n_tails > kMaxBatchWorkgroups)
+        return hipErrorInvalidValue;
+    if (granule_wgs > 0 && n_entries > 0) {
+        hipLaunchKernelGGL(bc7_batch_inverse_images, dim3(granule_wgs), dim3(256), 0, stream, d_entries, d_coarse, n_entries);
+        if (hipError_t e = hipGetLastError(); e != hipSuccess)
+            return e;
+    }
+    if (n_tails > 0) {
+        hipLaunchKernelGGL(bc7_batch_inverse_image_tails, dim3(n_tails), dim3(256), 0, stream, d_tails);
+        return hipGetLastError();
+    }
+    return hipSuccess;
+}
+
+}  // namespace bc7
+}  // namespace dxtlt

@@ -1,7 +1,7 @@
 // bc7_image_sinks.h -- device code the BC7 image kernels share (bc7_image_kernels.hip: one image per call;
-// bc7_image_regions_kernels.hip: several images of one buffer): the block load and decode of the plain decoders, the stores of a
-// part of a block, and the staging sinks of the inverse granule sort -- Bc7PixelSink for one image, Bc7RegionPixelSink for the
-// images of a region table (image_regions.h).  docs/IMAGE_DECODE.md, "BC7" and "Several images of one BC7 buffer".
+// bc7_image_regions_kernels.hip: several images of one buffer; bc7_image_batch_kernels.hip: the images of many buffers): the block
+// load and decode of the plain decoders, the stores of a part of a block, and the staging sinks of the inverse granule sort --
+// Bc7PixelSink for one image, Bc7RegionPixelSinkOf for the images of a region table (image_regions.h).  docs/IMAGE_DECODE.md, "BC7" and "Several images of one BC7 buffer".
 #pragma once
 #include "bc7_decode.h"
 #include "bc7_granule_codec.h"
@@ -137,12 +137,14 @@ struct Bc7PixelSink {
 // -- would otherwise live through the second part's stage() beside the decoded pixels (docs/IMAGE_DECODE.md, "Several images
 // of one BC7 buffer", resources).
 // No lane leaves here before inverse_granule's barriers: a block without an image only skips its stores.
-struct Bc7RegionPixelSink {
+// Written once for every kind of table the lookups of image_regions.h take, as the BC1 - BC5 region sinks are.
+template <typename TABLE>
+struct Bc7RegionPixelSinkOf {
     static constexpr bool kStaged = Bc7PixelSink::kStaged;
     static constexpr int kParts = Bc7PixelSink::kParts, kRows = Bc7PixelSink::kRows;
     static constexpr int kStageBytes = Bc7PixelSink::kStageBytes;
     using Held = Bc7PixelSink::Held;
-    ImageRegionTable tab;
+    TABLE tab;
 
     // (the single-image sink's members do not read its fields)
     __device__ __forceinline__ Held hold(const B128& b) const { return Bc7PixelSink{}.hold(b); }
@@ -183,6 +185,9 @@ struct Bc7RegionPixelSink {
         }
     }
 };
+
+// the table in the kernel arguments (bc7_image_regions_kernels.hip); bc7_image_batch_kernels.hip has the one in device memory
+using Bc7RegionPixelSink = Bc7RegionPixelSinkOf<ImageRegionTable>;
 
 }  // namespace
 }  // namespace bc7

@@ -875,6 +875,10 @@ inline void untransform_decode_bc7_images(const uint8_t* transformed, size_t len
 {
     detail::check_device(dxtlt_untransform_decode_bc7_images(transformed, len, regions, region_count));
 }
+inline void untransform_decode_bc7_images_batch_device(const DxtltBc7ImageBatchItem* items, size_t count, void* hip_stream)
+{
+    detail::check_device(dxtlt_untransform_decode_bc7_images_batch_device(items, count, hip_stream));
+}
 
 }  // namespace api
 }  // namespace dxt_lossless_transform

@@ -44,6 +44,23 @@
  *   device    the *_device calls enqueue on `hip_stream` only, allocate nothing, copy nothing to the device but kernel
  *             arguments and do not synchronise: they can be captured into a HIP graph, the table frozen at capture.
  *
+ * The images of MANY BC7 transformed buffers in one call (docs/IMAGE_DECODE.md, "Many BC7 buffers in one call"):
+ * dxtlt_untransform_decode_bc7_images_batch_device takes one DxtltBc7ImageBatchItem per buffer and writes, for every item,
+ * exactly the bytes dxtlt_untransform_decode_bc7_images_device writes for that item alone.  Items may differ in size, alignment
+ * and region layout, and two items may name the same buffer; the images of a batch must not overlap (not checked).
+ *   checks    the whole batch before anything is enqueued -- it goes out whole or not at all: count == 0 is DXTLT_OK; a NULL
+ *             `items` with count > 0 is DXTLT_E_INVALID_ARGUMENT; then the items in list order, each with the checks of
+ *             dxtlt_untransform_decode_bc7_images_device in their order.  The first failure is the answer and
+ *             dxtlt_last_error() names the item ("bc7 image batch item 7: ...").  An item without a non-empty region is
+ *             skipped, its buffer pointer unchecked.  A batch that needs more than 16777215 granules (of 1024 blocks) or more
+ *             than 16777215 tail parts is DXTLT_E_INVALID_ARGUMENT.
+ *   launches  every group of at most DXTLT_IMAGE_REGIONS_PER_LAUNCH non-empty regions of an item is one entry, covered as the
+ *             single call covers it; all entries' granules go out in ONE launch and all their tail parts in a second one: at
+ *             most two launches, whatever the number of items.
+ *   device    asynchronous on `hip_stream`, ordered like a single call.  The call stages its tables in pinned memory of the
+ *             calling thread (dxtlt_release_thread_resources frees it)    and uploads them on the stream in front of the
+ *             launches; capture into a HIP graph is not promised.
+ *
  * The RGBA image calls of dxtlt_image.h (format 1..3) and its region and batch calls do not take BC7.
  */
 #ifndef DXTLT_BC7_IMAGE_H
@@ -98,6 +115,35 @@ typedef struct DxtltBc7ImagesLaunch {
 
 int32_t dxtlt_debug_plan_bc7_images(uint64_t total_blocks, const DxtltImageRegion *regions, size_t region_count,
                                     DxtltBc7ImagesLaunch *out, size_t cap);
+
+/* ---- many buffers in one call ------------------------------------------------------------------------------ */
+typedef struct DxtltBc7ImageBatchItem {
+    const void *d_transformed;        /* byte 0 of the item's WHOLE transformed BC7 device buffer, any alignment */
+    uint64_t total_blocks;
+    const DxtltImageRegion *regions;  /* host array; pixels = device pointers; the rules of the *_bc7_images calls */
+    uint32_t region_count;
+    uint32_t reserved;                /* 0 */
+} DxtltBc7ImageBatchItem;
+
+int32_t dxtlt_untransform_decode_bc7_images_batch_device(const DxtltBc7ImageBatchItem *items, size_t count, void *hip_stream);
+
+/* Test hook, no device needed: the entries the batch call would stage, in list order.  Addresses are numbers; nothing is
+ * dereferenced but `items` and their `regions`.  Records beyond `cap` are counted, not written.  Returns the number of entries,
+ * or -1 for a batch the call would refuse. */
+typedef struct DxtltDebugBc7ImageBatchEntry {
+    uint32_t item;           /* index of the entry's item */
+    uint32_t first_region;   /* index in the item's list of the group's first non-empty region */
+    uint32_t region_count;   /* non-empty regions of the group */
+    int32_t tail_index;      /* the entry's workgroup in the tail launch, or -1 */
+    uint64_t first_granule;  /* of the buffer's main part (0 when granule_count is 0) */
+    uint32_t granule_count;  /* the entry's workgroups in the granule launch, 0 if none */
+    uint32_t first_wg;       /* its first workgroup there: the workgroups of all entries before it */
+    uint32_t granule_wgs;    /* workgroups of the whole granule launch (0: not launched) */
+    uint32_t tail_wgs;       /* workgroups of the whole tail launch (0: not launched) */
+} DxtltDebugBc7ImageBatchEntry;
+
+int32_t dxtlt_debug_plan_bc7_image_batch(const DxtltBc7ImageBatchItem *items, size_t count, DxtltDebugBc7ImageBatchEntry *out,
+                                         size_t cap);
 
 #ifdef __cplusplus
 }
