@@ -1,10 +1,9 @@
 // bc6h_kernels.hip -- gfx950 kernels of the BC6H granule-sorted field split, layout version 1 (docs/BC6H_FORMAT.md).
 //
-// The granule sort of granule_sort.h (whose header comment has the reasoning) over BC6H's record codec (bc6h_fields.h):
+// The granule sort of granule_sort.h (whose header comment has the reasoning) over BC6H's record codec (bc6h_granule_codec.h):
 // 15 classes, so all four class bits are matched by ballots in every segment; each record permutation is a compile-time
 // list of bit runs.  256 lanes x 4 blocks per lane, 19 KiB of LDS per workgroup, eight granules resident per CU.
-#include "bc6h_fields.h"
-#include "granule_sort.h"
+#include "bc6h_granule_codec.h"
 
 namespace dxtlt {
 namespace bc6h {
@@ -13,20 +12,6 @@ using granule::BatchEntry;
 using granule::forward_granule;
 using granule::inverse_granule;
 using granule::kT;
-
-struct Bc6hCodec {
-    static constexpr int kClasses = bc6h::kClasses;
-    static constexpr int kCountsSpare = 0;
-    static constexpr auto& block_class = bc6h::block_class;
-    static constexpr auto& byte0 = bc6h_byte0;
-    static constexpr auto& record = bc6h_record_any;
-    static constexpr auto& block = bc6h_block_any;
-    template <bool TAIL>
-    static __device__ __forceinline__ void rank_and_count(uint8_t* lds, int cls, int lane, int segment, int& rank)
-    {
-        granule::rank_by_ballots<Bc6hCodec>(lds, cls, lane, segment, rank);
-    }
-};
 
 // Forward and inverse over a range of full granules (gridDim.x of them from first_block on, aos = the range's first
 // block) or, TAIL, over a tail part in one workgroup; the arguments are forward_granule's (granule_sort.h).

@@ -1,5 +1,5 @@
 // granule_sort.h -- the granule sort of the BC7 and BC6H field splits (docs/BC7_FORMAT.md, docs/BC6H_FORMAT.md), once,
-// as templates over a codec.  bc7_kernels.hip, bc6h_kernels.hip and bc7_image_kernels.hip (the inverse with a pixel sink)
+// as templates over a codec.  bc7_kernels.hip, bc6h_kernels.hip and the BC7 / BC6H image kernels (the inverse with a pixel sink)
 // instantiate it; nothing else includes it.
 //
 // What is computed.  The block array is cut into granules of 1024 blocks.  Inside a granule the blocks are ordered by
@@ -9,7 +9,7 @@
 // the main part, whose streams start at multiples of the granule size (so every slice is 128-byte aligned whatever N
 // is); the last N % 1024 blocks form a tail part with the same streams over its own block count.
 //
-// A codec is a struct of static members (Bc7Codec in bc7_granule_codec.h, Bc6hCodec in bc6h_kernels.hip):
+// A codec is a struct of static members (Bc7Codec in bc7_granule_codec.h, Bc6hCodec in bc6h_granule_codec.h):
 //   kClasses (at most 15)        classes of the sort; a lane beyond a tail part's blocks has class kClasses
 //   kCountsSpare                 unused bytes behind the counts table in LDS
 //   block_class(byte0)           class of a block or a record from its byte 0

@@ -5,7 +5,8 @@ bc1_decode.rs:42, bc2_decode.rs:44, bc3_decode.rs:43) as array operations over i
 ``count_pixel_differences`` is the reference tests' "decode before == decode after" assertion as a count.
 1-D ``uint8`` numpy / bytes-like host buffers or CUDA ``torch.uint8`` tensors (torch's current stream).  No CPU fallback.
 
-``decode_bc7_blocks`` is the same for BC7 (include/dxtlt_bc7_image.h), a format of this build's own."""
+``decode_bc7_blocks`` is the same for BC7 (include/dxtlt_bc7_image.h), a format of this build's own; ``decode_bc6h_blocks`` decodes
+BC6H (UF16) to 128 bytes per block, sixteen RGBA16F pixels (include/dxtlt_bc6h_image.h)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -13,6 +14,7 @@ import ctypes as C
 from . import _lib
 
 DECODED_BLOCK_BYTES = 64
+DECODED_BC6H_BLOCK_BYTES = 128
 _FMT = {"bc1": 1, "bc2": 2, "bc3": 3}
 _BLOCK = {"bc1": 8, "bc2": 16, "bc3": 16}
 _declared = False
@@ -30,6 +32,9 @@ def _l():
         l.dxtlt_decode_bc7_blocks.argtypes = [vp, sz, vp, sz]
         l.dxtlt_decode_bc7_blocks_device.argtypes = [vp, sz, vp, sz, vp]
         l.dxtlt_decode_bc7_blocks.restype = l.dxtlt_decode_bc7_blocks_device.restype = i32
+        l.dxtlt_decode_bc6h_blocks.argtypes = [vp, sz, vp, sz]
+        l.dxtlt_decode_bc6h_blocks_device.argtypes = [vp, sz, vp, sz, vp]
+        l.dxtlt_decode_bc6h_blocks.restype = l.dxtlt_decode_bc6h_blocks_device.restype = i32
         l.dxtlt_count_pixel_differences.argtypes = [i32, vp, vp, sz, C.POINTER(C.c_uint64)]
         l.dxtlt_count_pixel_differences_device.argtypes = [i32, vp, vp, sz, vp, vp]
         l.dxtlt_count_pixel_differences.restype = l.dxtlt_count_pixel_differences_device.restype = i32
@@ -93,6 +98,28 @@ def decode_bc7_blocks(blocks, pixels) -> None:
 
     with torch.cuda.device(device):
         _check(l.dxtlt_decode_bc7_blocks_device(s.ptr, s.nbytes, d.ptr, d.nbytes, torch.cuda.current_stream(device).cuda_stream))
+
+
+def decode_bc6h_blocks(blocks, pixels) -> None:
+    """BC6H, unsigned (include/dxtlt_bc6h_image.h): ``pixels`` receives 128 bytes per 16-byte block -- sixteen pixels of four
+    little-endian half-float bit patterns r, g, b, a, alpha 1.0 -- the Direct3D 11 UF16 decoding; the reserved mode values give
+    black.  Host buffers are decoded on the CPU by the code the kernels use, CUDA tensors on the device."""
+    from . import InvalidLength, OutputBufferTooSmall
+
+    (s, d), device = _bufs((blocks, pixels), (False, True))
+    if s.nbytes % 16 != 0:
+        raise InvalidLength(s.nbytes)
+    need = s.nbytes // 16 * DECODED_BC6H_BLOCK_BYTES
+    if d.nbytes < need:
+        raise OutputBufferTooSmall(need, d.nbytes)
+    l = _l()
+    if device is None:
+        _check(l.dxtlt_decode_bc6h_blocks(s.ptr, s.nbytes, d.ptr, d.nbytes))
+        return
+    import torch
+
+    with torch.cuda.device(device):
+        _check(l.dxtlt_decode_bc6h_blocks_device(s.ptr, s.nbytes, d.ptr, d.nbytes, torch.cuda.current_stream(device).cuda_stream))
 
 
 def count_pixel_differences(fmt: str, blocks_a, blocks_b) -> int:

@@ -11,7 +11,8 @@ buffer in one kernel (the untransformed blocks never touch memory); ``mip_level`
 1 / 2 bytes (r, or r, g) at ``y * pitch + bpp * x``, the default pitch ``bpp * width``, the one setting ``split_endpoints``.
 
 ``decode_bc7_image`` and ``untransform_decode_bc7_image`` are the two calls for BC7 (include/dxtlt_bc7_image.h): RGBA8888, no
-settings, any ``first_block``.
+settings, any ``first_block``.  ``decode_bc6h_image`` and ``untransform_decode_bc6h_image`` are the two calls for BC6H
+(include/dxtlt_bc6h_image.h): unsigned blocks to RGBA16F, 8 bytes per pixel, the default pitch ``8 * width``.
 
 ``untransform_decode_images`` and ``decode_images`` write several images of one buffer in one call, for all five formats: a
 region is ``(first_block, width, height)``, and ``mip_chain`` lists the regions of a mip chain.
@@ -82,6 +83,11 @@ def _l():
         l.dxtlt_decode_bc7_images_device.argtypes = [vp, u64, rp, C.c_size_t, vp]
         l.dxtlt_untransform_decode_bc7_images.argtypes = [vp, C.c_size_t, rp, C.c_size_t]
         l.dxtlt_untransform_decode_bc7_images_batch_device.argtypes = [C.POINTER(Bc7ImageBatchItem), C.c_size_t, vp]
+        l.dxtlt_decode_bc6h_image_device.argtypes = [vp, u32, u32, vp, u64, vp]
+        l.dxtlt_untransform_decode_bc6h_image_device.argtypes = [vp, u64, u64, u32, u32, vp, u64, vp]
+        l.dxtlt_untransform_decode_bc6h_image.argtypes = [vp, C.c_size_t, u64, u32, u32, vp, u64]
+        for f in (l.dxtlt_decode_bc6h_image_device, l.dxtlt_untransform_decode_bc6h_image_device, l.dxtlt_untransform_decode_bc6h_image):
+            f.restype = i32
         for f in (l.dxtlt_decode_bc7_image_device, l.dxtlt_untransform_decode_bc7_image_device, l.dxtlt_untransform_decode_bc7_image,
                   l.dxtlt_untransform_decode_bc7_images_device, l.dxtlt_decode_bc7_images_device, l.dxtlt_untransform_decode_bc7_images,
                   l.dxtlt_untransform_decode_bc7_images_batch_device):
@@ -277,6 +283,53 @@ def untransform_decode_bc7_image(transformed, width: int, height: int, *, first_
     with torch.cuda.device(src.device):
         _check(l.dxtlt_untransform_decode_bc7_image_device(src.ptr, total_blocks, first_block, width, height, dst.ptr, pitch,
                                                            torch.cuda.current_stream(src.device).cuda_stream))
+    return out
+
+
+# ---- BC6H -> RGBA16F (include/dxtlt_bc6h_image.h) --------------------------------------------------------------------------
+def decode_bc6h_image(blocks, width: int, height: int, out=None, pitch=None):
+    """``blocks``: ceil(width / 4) * ceil(height / 4) BC6H (UF16) blocks in block order, a CUDA tensor.  Returns ``out`` (a new
+    ``uint8`` tensor of ``pitch * height`` bytes when None); ``pitch`` defaults to ``8 * width``: a pixel is four half floats r, g, b,
+    a with a = 1.0, and ``out.view(torch.float16).reshape(height, width, 4)`` is the image when the pitch is the default."""
+    from . import InvalidLength, _Buf
+
+    src = _Buf(blocks, False)
+    if src.device is None:
+        raise TypeError("decode_bc6h_image takes device tensors (the library has no host-pointer form of it)")
+    if src.nbytes < image_blocks(width, height) * 16:
+        raise InvalidLength(src.nbytes)
+    out, dst, pitch = _output(src, width, height, out, pitch, 8)
+    import torch
+
+    with torch.cuda.device(src.device):
+        _check(_l().dxtlt_decode_bc6h_image_device(src.ptr, width, height, dst.ptr, pitch, torch.cuda.current_stream(src.device).cuda_stream))
+    return out
+
+
+def untransform_decode_bc6h_image(transformed, width: int, height: int, *, first_block: int = 0, total_blocks=None, out=None, pitch=None):
+    """``transformed``: the WHOLE buffer ``transform_bc6h`` made, of ``total_blocks`` blocks (default: its length); the image is its
+    blocks [first_block, first_block + ceil(width / 4) * ceil(height / 4)), ``first_block`` any block.  Returns ``out``, ``uint8``;
+    ``pitch`` defaults to ``8 * width``, and ``out.view(torch.float16).reshape(height, width, 4)`` is the image when the pitch is the
+    default (``out.view(np.float16)`` for a host buffer)."""
+    from . import InvalidLength, _Buf
+
+    src = _Buf(transformed, False)
+    if src.nbytes % 16 != 0:
+        raise InvalidLength(src.nbytes)
+    if total_blocks is None:
+        total_blocks = src.nbytes // 16
+    if total_blocks * 16 > src.nbytes:
+        raise InvalidLength(src.nbytes)
+    out, dst, pitch = _output(src, width, height, out, pitch, 8)
+    l = _l()
+    if src.device is None:
+        _check(l.dxtlt_untransform_decode_bc6h_image(src.ptr, total_blocks * 16, first_block, width, height, dst.ptr, pitch))
+        return out
+    import torch
+
+    with torch.cuda.device(src.device):
+        _check(l.dxtlt_untransform_decode_bc6h_image_device(src.ptr, total_blocks, first_block, width, height, dst.ptr, pitch,
+                                                            torch.cuda.current_stream(src.device).cuda_stream))
     return out
 
 

@@ -29,6 +29,7 @@
 #include "dxtlt_bc1_normalize.h"
 #include "dxtlt_bc23_normalize.h"
 #include "dxtlt_bc6h.h"
+#include "dxtlt_bc6h_image.h"
 #include "dxtlt_pixels.h"
 #include "dxtlt_bc7.h"
 #include "dxtlt_bc7_image.h"
@@ -878,6 +879,30 @@ inline void untransform_decode_bc7_images(const uint8_t* transformed, size_t len
 inline void untransform_decode_bc7_images_batch_device(const DxtltBc7ImageBatchItem* items, size_t count, void* hip_stream)
 {
     detail::check_device(dxtlt_untransform_decode_bc7_images_batch_device(items, count, hip_stream));
+}
+
+// ADDITIVE: BC6H (UF16) blocks -> RGBA16F pixels (dxtlt_bc6h_image.h; the Direct3D 11 decoder, eight bytes a pixel, alpha 1.0, the
+// reserved mode values as black).  Blocks to 128-byte records, a block array in block order to a row-major image, and the same
+// fused with the inverse of dxtlt_transform_bc6h: the image is the blocks [first_block, first_block + image blocks) of the
+// transformed buffer, any first_block.  No signedness argument: signed blocks are not decoded by these calls.
+inline void decode_bc6h_blocks_device(const void* d_blocks, size_t len, void* d_pixels, size_t pixels_len, void* hip_stream)
+{
+    detail::check_device(dxtlt_decode_bc6h_blocks_device(d_blocks, len, d_pixels, pixels_len, hip_stream));
+}
+inline void decode_bc6h_image_device(const void* d_blocks, uint32_t width, uint32_t height, void* d_pixels, uint64_t pitch, void* hip_stream)
+{
+    detail::check_device(dxtlt_decode_bc6h_image_device(d_blocks, width, height, d_pixels, pitch, hip_stream));
+}
+inline void untransform_decode_bc6h_image_device(const void* d_transformed, uint64_t total_blocks, uint64_t first_block, uint32_t width,
+                                                 uint32_t height, void* d_pixels, uint64_t pitch, void* hip_stream)
+{
+    detail::check_device(dxtlt_untransform_decode_bc6h_image_device(d_transformed, total_blocks, first_block, width, height, d_pixels, pitch,
+                                                                    hip_stream));
+}
+inline void untransform_decode_bc6h_image(const uint8_t* transformed, size_t len, uint64_t first_block, uint32_t width, uint32_t height,
+                                          uint8_t* pixels, uint64_t pitch)
+{
+    detail::check_device(dxtlt_untransform_decode_bc6h_image(transformed, len, first_block, width, height, pixels, pitch));
 }
 
 }  // namespace api
