@@ -119,27 +119,20 @@ hipError_t launch_untransform_decode_image(const void* soa_arg, uint64_t total_b
     if (first_block > total_blocks || n > total_blocks - first_block)
         return hipErrorInvalidValue;
     const auto* soa = static_cast<const uint8_t*>(soa_arg);
-    const uint64_t main_blocks = total_blocks - total_blocks % kT, end = first_block + n;
+    const uint64_t main_blocks = total_blocks - total_blocks % kT;
     const Bc6hPixelSink<false> sink{img, first_block, n};
     const Bc6hPixelSink<true> tail_sink{img, first_block, n};
-    if (first_block < main_blocks) {
-        // granules first_block / 1024 .. (end - 1) / 1024, bounded by the main part; at most 2^21 of them per launch (granule_sort.h)
-        const uint64_t g0 = first_block / kT, g1 = ((end < main_blocks ? end : main_blocks) - 1) / kT;
-        constexpr uint64_t kMaxGranules = 1ull << 21;
-        for (uint64_t g = g0; g <= g1; g += kMaxGranules) {
-            const uint64_t ng = g1 + 1 - g < kMaxGranules ? g1 + 1 - g : kMaxGranules;
-            hipLaunchKernelGGL((bc6h_inverse_image<256, false>), dim3((unsigned)ng), dim3(256), 0, stream, soa, sink, main_blocks, g * kT, 0);
-            if (hipError_t e = hipGetLastError(); e != hipSuccess)
-                return e;
+    return granule::for_each_range_launch(total_blocks, first_block, first_block + n, [&](uint64_t granule, uint64_t granules, bool tail) {
+        if (!tail) {
+            hipLaunchKernelGGL((bc6h_inverse_image<256, false>), dim3((unsigned)granules), dim3(256), 0, stream, soa, sink, main_blocks,
+                               granule * kT, 0);
+        } else {
+            const uint64_t n_tail = total_blocks - main_blocks;
+            hipLaunchKernelGGL((bc6h_inverse_image<256, true>), dim3(1), dim3(256), 0, stream, soa + main_blocks * 16, tail_sink, n_tail,
+                               main_blocks, (int)n_tail);
         }
-    }
-    if (end > main_blocks) {
-        const uint64_t tail = total_blocks - main_blocks;
-        hipLaunchKernelGGL((bc6h_inverse_image<256, true>), dim3(1), dim3(256), 0, stream, soa + main_blocks * 16, tail_sink, tail, main_blocks,
-                           (int)tail);
         return hipGetLastError();
-    }
-    return hipSuccess;
+    });
 }
 
 }  // namespace bc6h

@@ -1,5 +1,5 @@
-// bc6h_image_sinks.h -- device code of the BC6H image kernels (bc6h_image_kernels.hip): the block load and decode of the plain
-// decoders, the stores of a block's 32-byte pixel rows, and Bc6hPixelSink, the staging sink of the inverse granule sort.
+// bc6h_image_sinks.h -- device code of the BC6H image kernels (bc6h_image_kernels.hip): the block decode of the plain decoders
+// (their load is image_store.h's load_block), the stores of a block's 32-byte pixel rows, and Bc6hPixelSink, the staging sink of the inverse granule sort.
 // docs/IMAGE_DECODE.md, "BC6H blocks to a row-major RGBA16F image".
 #pragma once
 #include "bc6h_decode.h"
@@ -16,20 +16,6 @@ __device__ __forceinline__ Interp prepare_q(u32x4 q)
 {
     const B128 b = {{q.x, q.y, q.z, q.w}};
     return prepare_bc6h_block(b);
-}
-
-// block `b` of the array: a 16-byte load when the block pointer is a multiple of 16, byte loads otherwise
-template <bool ALIGNED>
-__device__ __forceinline__ u32x4 load_block(const uint8_t* __restrict__ in, uint64_t b)
-{
-    if constexpr (ALIGNED) {
-        return __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(in) + b);
-    } else {
-        uint32_t q[4] = {0, 0, 0, 0};
-        for (int i = 0; i < 16; ++i)
-            q[i >> 2] |= (uint32_t)in[16 * b + i] << (8 * (i & 3));
-        return u32x4{q[0], q[1], q[2], q[3]};
-    }
 }
 
 // pixel row `r` of block `b` of the image, row[0] = pixels 0 and 1, row[1] = pixels 2 and 3: whole blocks in two 16-byte stores on

@@ -2,10 +2,10 @@
 // "Many BC7 buffers in one call"): the images of many BC7 transformed device buffers in at most two launches.
 //
 // Planning is pure host arithmetic (plan_batch; dxtlt_debug_plan_bc7_image_batch exposes it to the tests on a machine without a
-// GPU): every item is checked as dxtlt_untransform_decode_bc7_images_device checks it (image_regions_defect); its non-empty
-// regions are cut into the single call's groups (for_each_region_group), each group one entry whose covering range is planned as
-// the single call plans it (for_each_range_launch): the main part's granules it touches go into the granule launch, its tail
-// part, if it reaches one, into the tail launch.  The call then stages every table of the batch -- region tables, granule
+// GPU): every item is checked as dxtlt_untransform_decode_bc7_images_device checks it (image_regions_defect, image_host.h); its
+// non-empty regions are cut into the single call's groups (for_each_region_group), each group one entry whose covering range is
+// planned as the single call plans it (for_each_range_launch, granule_launch.h): the main part's granules it touches go into the
+// granule launch, its tail part, if it reaches one, into the tail launch.  The call then stages every table of the batch -- region tables, granule
 // entries, tail entries, the coarse index -- in ONE slot of the batch calls' ring (table_ring.h) and uploads it on the caller's
 // stream in front of the launches, as image_batch_api.cpp does.
 #include <hip/hip_runtime_api.h>
@@ -17,10 +17,9 @@
 #include "../../include/dxtlt_bc7_image.h"
 #include "../../include/dxtlt_gfx950.h"
 #include "bc7_image_batch_launch.h"
-#include "bc7_image_launch.h"   // for_each_range_launch
+#include "granule_launch.h"   // for_each_range_launch
 #include "host_common.h"
-#include "image_launch.h"       // image_regions_defect
-#include "image_region_groups.h"
+#include "image_host.h"       // image_regions_defect
 #include "table_ring.h"
 
 namespace {
@@ -63,7 +62,7 @@ int32_t plan_batch(const DxtltBc7ImageBatchItem* items, size_t count, Bc7ImageBa
     for (size_t i = 0; i < count; ++i) {
         const DxtltBc7ImageBatchItem& it = items[i];
         bool nothing = true;
-        if (const char* why = image_regions_defect(0, it.d_transformed, it.total_blocks, it.regions, it.region_count, 0, &nothing, true))
+        if (const char* why = image_regions_defect(kRgba8888, it.d_transformed, it.total_blocks, it.regions, it.region_count, &nothing))
             return fail_item(i, why);
         if (nothing)
             continue;
@@ -89,7 +88,7 @@ int32_t plan_batch(const DxtltBc7ImageBatchItem* items, size_t count, Bc7ImageBa
                     plan.regions.push_back(dxtlt::make_batch_region(tab.img[k], tab.first[k]));
                 uint64_t granules = 0;
                 bool tail = false;
-                (void)dxtlt::bc7::for_each_range_launch(it.total_blocks, first, first + n, [&](uint64_t granule, uint64_t ng, bool is_tail) {
+                (void)dxtlt::granule::for_each_range_launch(it.total_blocks, first, first + n, [&](uint64_t granule, uint64_t ng, bool is_tail) {
                     // (the single call's launches over the main part follow one another: one run of granules here)
                     if (is_tail)
                         tail = true;

@@ -74,7 +74,7 @@ hipError_t launch_untransform_decode_image_regions(const void* soa_arg, uint64_t
     const auto* soa = static_cast<const uint8_t*>(soa_arg);
     const uint64_t main_blocks = total_blocks - total_blocks % kT;
     const Bc7RegionPixelSink sink{tab};
-    return for_each_range_launch(total_blocks, first, first + n, [&](uint64_t granule, uint64_t granules, bool tail) {
+    return granule::for_each_range_launch(total_blocks, first, first + n, [&](uint64_t granule, uint64_t granules, bool tail) {
         if (tail) {
             const uint64_t n_tail = total_blocks - main_blocks;
             hipLaunchKernelGGL((bc7_inverse_images<256, true>), dim3(1), dim3(256), 0, stream, soa + main_blocks * 16, sink, n_tail,

@@ -1,6 +1,6 @@
 // bc7_image_sinks.h -- device code the BC7 image kernels share (bc7_image_kernels.hip: one image per call;
 // bc7_image_regions_kernels.hip: several images of one buffer; bc7_image_batch_kernels.hip: the images of many buffers): the block
-// load and decode of the plain decoders, the stores of a part of a block, and the staging sinks of the inverse granule sort --
+// decode of the plain decoders (their load is image_store.h's load_block), the stores of a part of a block, and the staging sinks of the inverse granule sort --
 // Bc7PixelSink for one image, Bc7RegionPixelSinkOf for the images of a region table (image_regions.h).  docs/IMAGE_DECODE.md, "BC7" and "Several images of one BC7 buffer".
 #pragma once
 #include "bc7_decode.h"
@@ -19,20 +19,6 @@ __device__ __forceinline__ void decode_px(u32x4 q, uint32_t (&px)[16])
 {
     const B128 b = {{q.x, q.y, q.z, q.w}};
     decode_bc7_block(b, px);
-}
-
-// block `b` of the array: a 16-byte load when the block pointer is a multiple of 16, byte loads otherwise
-template <bool ALIGNED>
-__device__ __forceinline__ u32x4 load_block(const uint8_t* __restrict__ in, uint64_t b)
-{
-    if constexpr (ALIGNED) {
-        return __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(in) + b);
-    } else {
-        uint32_t q[4] = {0, 0, 0, 0};
-        for (int i = 0; i < 16; ++i)
-            q[i >> 2] |= (uint32_t)in[16 * b + i] << (8 * (i & 3));
-        return u32x4{q[0], q[1], q[2], q[3]};
-    }
 }
 
 // ---- the inverse granule sort with a pixel sink --------------------------------------------------------------------------

@@ -7,6 +7,7 @@
 #include "../../include/dxtlt_gfx950.h"
 #include "bcn_launch.h"
 #include "host_common.h"
+#include "image_host.h"   // check_decode
 
 using dxtlt_host::fail;
 using dxtlt_host::kDevice;
@@ -22,14 +23,8 @@ inline size_t block_bytes(int fmt) { return fmt == 1 ? 8 : 16; }
 
 int32_t check_decode(int fmt, const void* in, size_t len, const void* out, size_t out_len)
 {
-    if (len % block_bytes(fmt) != 0)
-        return fail(kInvalidLength, "len is not a multiple of the block size");
-    const size_t n = len / block_bytes(fmt);
-    if (n > 0 && (in == nullptr || out == nullptr))
-        return fail(kInvalidArgument, "NULL buffer with len > 0");
-    if (out_len / DXTLT_DECODED_BLOCK_BYTES < n)
-        return fail(kInvalidArgument, "pixels_len is smaller than 64 bytes per block");
-    return kOk;
+    return dxtlt_host::check_decode(in, len, block_bytes(fmt), out, out_len, DXTLT_DECODED_BLOCK_BYTES,
+                                    "pixels_len is smaller than 64 bytes per block");
 }
 
 int32_t decode_device(int fmt, const void* in, size_t len, void* out, size_t out_len, void* stream)

@@ -6,9 +6,13 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "bc7_fields.h"   // kGranule
+
 namespace dxtlt {
 
 namespace granule {
+
+constexpr int kT = bc7::kGranule;     // blocks per granule
 
 inline bool is_granule_format(int format) { return format == 7 || format == 6; }
 const char* format_name(int format);     // "BC7" / "BC6H": the format in error texts
@@ -32,6 +36,27 @@ hipError_t launch(int format, bool inverse, const void* src, void* dst, uint64_t
 // range must end on one or at the end of the array (hipErrorInvalidValue otherwise).
 hipError_t launch_range(int format, bool inverse, const void* src, void* dst, uint64_t total_blocks, uint64_t first_block,
                         uint64_t num_blocks, hipStream_t stream);
+
+// The plan of ANY block range [first, end), first < end <= total_blocks, of a transformed buffer -- what the fused image decoders
+// of both formats launch and what their batch and debug plans record: one launch over the main part's granules first / 1024 ..
+// (min(end, main_blocks) - 1) / 1024, split at 2^21 granules (a launch of 2^32 or more threads is refused), then the tail part's
+// launch if the range reaches it.  launch(first granule, granules, tail) enqueues one; the tail part is granule
+// main_blocks / 1024.  Host arithmetic only.
+template <typename LAUNCH>
+hipError_t for_each_range_launch(uint64_t total_blocks, uint64_t first, uint64_t end, const LAUNCH& launch)
+{
+    constexpr uint64_t kMaxGranules = 1ull << 21;
+    const uint64_t main_blocks = total_blocks - total_blocks % kT;
+    if (first < main_blocks) {
+        const uint64_t g0 = first / kT, g1 = ((end < main_blocks ? end : main_blocks) - 1) / kT;
+        for (uint64_t g = g0; g <= g1; g += kMaxGranules) {
+            const uint64_t ng = g1 + 1 - g < kMaxGranules ? g1 + 1 - g : kMaxGranules;
+            if (hipError_t e = launch(g, ng, false); e != hipSuccess)
+                return e;
+        }
+    }
+    return end > main_blocks ? launch(main_blocks / kT, (uint64_t)1, true) : hipSuccess;
+}
 
 // Many buffers per launch.  One entry per buffer with full granules (src / dst: the buffer's first byte on both sides;
 // first_wg: its first workgroup in the granule launch, entries in ascending order) and one per buffer with a tail part

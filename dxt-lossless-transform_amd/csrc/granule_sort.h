@@ -47,8 +47,8 @@
 #include <cstdint>
 #include <type_traits>
 
-#include "bc7_fields.h"   // B128, kGranule
-#include "granule_launch.h"
+#include "bc7_fields.h"   // B128
+#include "granule_launch.h"   // kT, the blocks per granule
 #include "streaming_store.h"
 
 namespace dxtlt {
@@ -59,7 +59,6 @@ using bc7::B128;
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
-constexpr int kT = bc7::kGranule;     // blocks per granule
 constexpr int kSegments = kT / 64;    // 16 runs of 64 consecutive blocks: one wave instruction's worth each
 static_assert(kT == 1024, "the copy-out assigns whole 64-block segments to streams");
 

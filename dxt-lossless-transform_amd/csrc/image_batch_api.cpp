@@ -2,8 +2,8 @@
 // in one call"): the images of many transformed device buffers in one launch per (format, settings) present in the batch.
 //
 // Planning is pure host arithmetic (plan_image_batch; dxtlt_debug_plan_image_batch exposes it to the tests on a machine without a
-// GPU): every item is checked as the single call checks it; its non-empty regions are cut into groups of at most sixteen, each
-// group one entry -- the inverse transform's plan for the range from the group's first block to the end of its last region
+// GPU): every item is checked as the single call checks it (image_regions_defect, image_host.h); its non-empty regions are cut
+// into groups of at most sixteen, each group one entry -- the inverse transform's plan for the range from the group's first block to the end of its last region
 // (plan_image_batch_entry) and the group's region table; entries of one format and settings share a launch.  The call then
 // stages every table of the batch -- region tables, entries, workgroup indexes -- in ONE slot of the batch calls' ring
 // (table_ring.h) and uploads it on the caller's stream in front of the launches, as dxtlt_transform_batch_device does.
@@ -17,6 +17,7 @@
 #include "../../include/dxtlt_image.h"
 #include "host_common.h"
 #include "image_batch_launch.h"
+#include "image_host.h"
 #include "image_launch.h"
 #include "table_ring.h"
 
@@ -26,8 +27,6 @@ using namespace dxtlt_host;
 using dxtlt::ImageBatchEntry;
 using dxtlt::ImageBatchRegion;
 
-inline bool empty_region(const DxtltImageRegion& r) { return r.width == 0 || r.height == 0; }
-inline uint32_t bpp_of(int fmt) { return fmt <= 3 ? 4u : fmt == 4 ? 1u : 2u; }
 
 // One entry: a group of at most DXTLT_IMAGE_REGIONS_PER_LAUNCH non-empty regions of an item
 struct PlannedEntry {
@@ -92,7 +91,7 @@ int32_t plan_image_batch(const DxtltImageBatchItem* items, size_t count, ImageBa
         s.split_colour = it.split_colour_endpoints != 0;
         s = dxtlt::effective_settings(fmt, s);
         const int key = ((it.format - 1) << 4) | (s.variant << 2) | ((s.split_alpha ? 1 : 0) << 1) | (s.split_colour ? 1 : 0);
-        const uint32_t bpp = bpp_of(it.format);
+        const uint32_t bpp = pixel_rule(it.format).bpp;
         for (uint32_t r = 0; r < it.region_count;) {
             // the next group: up to sixteen non-empty regions from region r on
             PlannedEntry pe{};

@@ -1,4 +1,5 @@
-// image_launch.h -- internal launch interface of the image decoders (image_kernels.hip) for image_api.cpp.
+// image_launch.h -- internal launch interface of the image decoders (image_kernels.hip, image_regions_kernels.hip) for image_api.cpp
+// and image_batch_api.cpp: kernel launches only; the calls' argument checks are image_host.h's.
 #pragma once
 #include "bcn_launch.h"
 #include "image_regions.h"
@@ -27,13 +28,3 @@ hipError_t launch_untransform_decode_image_regions(Format fmt, const Settings& s
                                                    const ImageRegionTable& tab, hipStream_t stream);
 
 }  // namespace dxtlt
-
-struct DxtltImageRegion;
-namespace dxtlt_host {
-// image_api.cpp: the first defect of an image-region call's arguments in the documented order (the format first), or nullptr;
-// every defect is DXTLT_E_INVALID_ARGUMENT.  *nothing = there is no non-empty region.  The batch call checks every item with it.
-// bc7: the list of a BC7 region call (bc7_image_api.cpp) -- RGBA8888 pixels, `fmt` and `mode` are not looked at; the answers for
-// formats 1 .. 5, and for every other format without it, are what they were.
-const char* image_regions_defect(int32_t fmt, const void* buffer, uint64_t total_blocks, const DxtltImageRegion* regions, size_t count,
-                                 uint8_t mode, bool* nothing, bool bc7 = false);
-}  // namespace dxtlt_host

@@ -1,6 +1,7 @@
 // image_store.h -- device helpers shared by the image kernels (image_kernels.hip: one image per call;
-// image_regions_kernels.hip: several images of one buffer): a decoded block's sixteen pixels into their rows of an ImageSink
-// (image_sink.h).  The notes on the store shapes are at the head of image_kernels.hip and at its "BC4 / BC5" section.
+// image_regions_kernels.hip: several images of one buffer; the BC7 and BC6H image kernels): a decoded block's sixteen pixels into
+// their rows of an ImageSink (image_sink.h), and the 16-byte block load of the plain BC7 and BC6H decoders.  The notes on the store
+// shapes are at the head of image_kernels.hip and at its "BC4 / BC5" section.
 #pragma once
 #include "bcn_decode.h"
 #include "bcn_device.h"
@@ -11,6 +12,21 @@ namespace {
 
 typedef uint32_t u32x4_align4 __attribute__((ext_vector_type(4), aligned(4)));
 typedef uint32_t u32x4_align8 __attribute__((ext_vector_type(4), aligned(8)));
+
+// 16-byte block `b` of a block array (the plain BC7 and BC6H decoders): a 16-byte load when the block pointer is a multiple of 16,
+// byte loads otherwise
+template <bool ALIGNED>
+__device__ __forceinline__ u32x4 load_block(const uint8_t* __restrict__ in, uint64_t b)
+{
+    if constexpr (ALIGNED) {
+        return __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(in) + b);
+    } else {
+        uint32_t q[4] = {0, 0, 0, 0};
+        for (int i = 0; i < 16; ++i)
+            q[i >> 2] |= (uint32_t)in[16 * b + i] << (8 * (i & 3));
+        return u32x4{q[0], q[1], q[2], q[3]};
+    }
+}
 
 // the sixteen pixels of block `b` of the image into their rows
 __device__ __forceinline__ void store_block_pixels(const ImageSink& img, uint64_t b, const uint32_t (&px)[16])

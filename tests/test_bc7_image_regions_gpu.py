@@ -248,16 +248,18 @@ def test_block_array_call(lib, dev, case, in_off):
 
 
 def test_host_call(lib):
-    x, px, t = reference(lib, "interleaved", TOTAL_256)
-    regions = [CHAIN_256[0], (2**63, 0, 7)] + CHAIN_256[2:]       # level 1 in a gap, an empty region in the list
-    pitches = [4 * w + 20 for _, w, h in regions]
-    hosts = [np.full(GUARD + p * h + GUARD, 0xA5, dtype=np.uint8) for (_, w, h), p in zip(regions, pitches)]
-    arr = region_array(regions, [b.ctypes.data + GUARD for b in hosts], pitches)
-    assert lib.dxtlt_untransform_decode_bc7_images(t.ctypes.data, t.size, arr, len(regions)) == OK
-    for i, (region, p, host) in enumerate(zip(regions, pitches, hosts)):
-        n = p * region[2]
-        assert (host[:GUARD] == 0xA5).all() and (host[GUARD + n:] == 0xA5).all(), i
-        assert np.array_equal(host[GUARD:GUARD + n], expected_buffer(px, region, p)), i
+    # level 1 in a gap and an empty region in the list; three regions 9 pixels wide, the middle one empty, the first from the main
+    # part into the tail part: rows of 36 bytes, staged 48 apart
+    for total, regions in ((TOTAL_256, [CHAIN_256[0], (2**63, 0, 7)] + CHAIN_256[2:]), (1100, [(1000, 9, 50), (2**63, 0, 7), (1050, 9, 14)])):
+        x, px, t = reference(lib, "interleaved", total)
+        pitches = [4 * w + 20 for _, w, h in regions]
+        hosts = [np.full(GUARD + p * h + GUARD, 0xA5, dtype=np.uint8) for (_, w, h), p in zip(regions, pitches)]
+        arr = region_array(regions, [b.ctypes.data + GUARD for b in hosts], pitches)
+        assert lib.dxtlt_untransform_decode_bc7_images(t.ctypes.data, t.size, arr, len(regions)) == OK
+        for i, (region, p, host) in enumerate(zip(regions, pitches, hosts)):
+            n = p * region[2]
+            assert (host[:GUARD] == 0xA5).all() and (host[GUARD + n:] == 0xA5).all(), (total, i)
+            assert np.array_equal(host[GUARD:GUARD + n], expected_buffer(px, region, p)), (total, i)
 
 
 def test_python_wrappers_on_tensors_and_host_buffers(pkg, lib, dev):

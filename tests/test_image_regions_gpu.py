@@ -187,30 +187,34 @@ def test_every_region_has_a_store_policy_of_its_own(lib, dev, oracle, fmt, in_of
 
 
 # ---- case 7: the three routes agree ------------------------------------------------------------------------------------
+# three regions, the middle one empty, 9 pixels wide: rows of 9, 18 and 36 bytes, which the host call stages 16, 32 and 48 apart
+NINE_WIDE, TOTAL_NINE = [(1000, 9, 50), (2**63, 0, 7), (1050, 9, 14)], 1100
+
+
 @pytest.mark.parametrize("fmt", FMTS)
 def test_fused_plain_and_host_calls_agree(lib, dev, oracle, fmt):
     settings = default_settings(fmt)
-    regions = CHAIN_260
-    pitches = [BPP[fmt] * w + 20 for _, w, _ in regions]
-    x, t = reference(oracle, fmt, TOTAL_260, settings)
-    want = wanted(oracle, fmt, TOTAL_260, regions, pitches)
-    fused = run_regions(lib, dev, fmt, t, TOTAL_260, regions, settings, pitches)
-    plain = run_regions(lib, dev, fmt, x, TOTAL_260, regions, None, pitches)
-    hosts = [np.full(GUARD + pitches[i] * h + GUARD, 0xA5, dtype=np.uint8) for i, (_, _, h) in enumerate(regions)]
-    src = np.full(GUARD + t.size + GUARD, 0xA5, dtype=np.uint8)
-    src[GUARD:GUARD + t.size] = t
-    arr = region_array(regions, [h.ctypes.data + GUARD for h in hosts], pitches)
-    rc = lib.dxtlt_untransform_decode_images(FMT_ID[fmt], src.ctypes.data + GUARD, t.size, arr, len(regions), settings[0], settings[1],
-                                             settings[2])
-    assert rc == OK
-    assert np.array_equal(src[GUARD:GUARD + t.size], t) and (src[:GUARD] == 0xA5).all() and (src[GUARD + t.size:] == 0xA5).all()
-    host = []
-    for i, h in enumerate(hosts):
-        assert (h[:GUARD] == 0xA5).all() and (h[len(h) - GUARD:] == 0xA5).all(), "guard bytes were written"
-        host.append(h[GUARD:len(h) - GUARD])
-    assert_all_equal(fused, want, "fused")
-    assert_all_equal(plain, want, "plain")
-    assert_all_equal(host, want, "host")
+    for regions, total in ((CHAIN_260, TOTAL_260), (NINE_WIDE, TOTAL_NINE)):
+        pitches = [BPP[fmt] * w + 20 for _, w, _ in regions]
+        x, t = reference(oracle, fmt, total, settings)
+        want = wanted(oracle, fmt, total, regions, pitches)
+        fused = run_regions(lib, dev, fmt, t, total, regions, settings, pitches)
+        plain = run_regions(lib, dev, fmt, x, total, regions, None, pitches)
+        hosts = [np.full(GUARD + (pitches[i] * h if w and h else 0) + GUARD, 0xA5, dtype=np.uint8) for i, (_, w, h) in enumerate(regions)]
+        src = np.full(GUARD + t.size + GUARD, 0xA5, dtype=np.uint8)
+        src[GUARD:GUARD + t.size] = t
+        arr = region_array(regions, [h.ctypes.data + GUARD for h in hosts], pitches)
+        rc = lib.dxtlt_untransform_decode_images(FMT_ID[fmt], src.ctypes.data + GUARD, t.size, arr, len(regions), settings[0], settings[1],
+                                                 settings[2])
+        assert rc == OK
+        assert np.array_equal(src[GUARD:GUARD + t.size], t) and (src[:GUARD] == 0xA5).all() and (src[GUARD + t.size:] == 0xA5).all()
+        host = []
+        for i, h in enumerate(hosts):
+            assert (h[:GUARD] == 0xA5).all() and (h[len(h) - GUARD:] == 0xA5).all(), "guard bytes were written"
+            host.append(h[GUARD:len(h) - GUARD])
+        assert_all_equal(fused, want, ("fused", total))
+        assert_all_equal(plain, want, ("plain", total))
+        assert_all_equal(host, want, ("host", total))
 
 
 # ---- case 8: graph capture ---------------------------------------------------------------------------------------------
