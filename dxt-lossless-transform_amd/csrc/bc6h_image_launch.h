@@ -1,10 +1,11 @@
-// bc6h_image_launch.h -- internal launch interface of the BC6H decoders (bc6h_image_kernels.hip) for bc6h_image_api.cpp.  Every
-// call enqueues on `stream` only, allocates nothing and does not synchronise.
+// bc6h_image_launch.h -- internal launch interface of the BC6H decoders (bc6h_image_kernels.hip, bc6h_image_regions_kernels.hip) for
+// bc6h_image_api.cpp.  Every call enqueues on `stream` only, allocates nothing and does not synchronise.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
+#include "image_regions.h"
 #include "image_sink.h"
 
 namespace dxtlt {
@@ -18,6 +19,14 @@ hipError_t launch_decode_image(const void* blocks, const ImageSink& img, hipStre
 // first_block
 hipError_t launch_untransform_decode_image(const void* soa, uint64_t total_blocks, uint64_t first_block, const ImageSink& img,
                                            hipStream_t stream);
+
+// Several images of one buffer (bc6h_image_regions_kernels.hip): `tab` holds 1 .. kImageRegionsPerLaunch non-empty RGBA16F regions
+// inside [0, total_blocks), ascending and disjoint (append_region).  `blocks` / `soa`: byte 0 of the whole block array /
+// transformed buffer.  The fused call goes out as granule::for_each_range_launch (granule_launch.h) plans the range that covers the
+// regions.
+hipError_t launch_decode_image_regions(const void* blocks, uint64_t total_blocks, const ImageRegionTable& tab, hipStream_t stream);
+hipError_t launch_untransform_decode_image_regions(const void* soa, uint64_t total_blocks, const ImageRegionTable& tab,
+                                                   hipStream_t stream);
 
 }  // namespace bc6h
 }  // namespace dxtlt

@@ -1,9 +1,13 @@
-// bc6h_image_sinks.h -- device code of the BC6H image kernels (bc6h_image_kernels.hip): the block decode of the plain decoders
-// (their load is image_store.h's load_block), the stores of a block's 32-byte pixel rows, and Bc6hPixelSink, the staging sink of the inverse granule sort.
-// docs/IMAGE_DECODE.md, "BC6H blocks to a row-major RGBA16F image".
+// bc6h_image_sinks.h -- device code the BC6H image kernels share (bc6h_image_kernels.hip: one image per call;
+// bc6h_image_regions_kernels.hip: several images of one buffer): the block decode of the plain decoders (their load is
+// image_store.h's load_block), the stores of a block's 32-byte pixel rows, and the staging sinks of the inverse granule sort --
+// Bc6hPixelSink for one image, Bc6hRegionPixelSinkOf for the images of a region table (image_regions.h).
+// docs/IMAGE_DECODE.md, "BC6H blocks to a row-major RGBA16F image" and "Several images of one BC6H buffer".
 #pragma once
 #include "bc6h_decode.h"
 #include "bc6h_granule_codec.h"
+#include "image_region_sinks.h"
+#include "image_regions.h"
 #include "image_store.h"
 
 namespace dxtlt {
@@ -143,6 +147,106 @@ struct Bc6hPixelSink {
         }
     }
 };
+
+// ---- the same sink for the images of a region table ----------------------------------------------------------------------
+// hold() and stage() are Bc6hPixelSink's: the blocks are prepared in the sorted domain and one pixel row per part crosses through
+// LDS exactly as for one image.  store_staged() differs in who owns a block: block `b` of the buffer belongs to whichever region
+// of `tab` holds it, and to none in a gap.  Three questions, the cheapest first, as in Bc7RegionPixelSinkOf (bc7_image_sinks.h):
+// prepare() asks once per granule (or tail part), before the decode, whether ONE region holds all of it -- its answer stays in
+// scalar registers, serves every store of the granule, and the stores are then the single-image sink's, the uniform `sc1 nt`-or-
+// plain choice included; otherwise the wave asks about its run of 64 (wave_run, image_region_sinks.h); otherwise the lanes ask
+// region_of_block, and the image, the store choice and the clipping are per lane.  The wave's and the lanes' answers are looked up
+// again for each of the four parts instead of being held across them: an ImageSink and a block number per stored block would
+// otherwise live through the next part's stage() beside the 36 registers of the held blocks.
+// What differs from BC7 is whose block a lane stores.  In a full granule lane l does not store the block it holds but halves
+// l & 1 of blocks l / 2 and 32 + l / 2 of its wave's run, after two cross-lane moves.  So
+//   * all 64 lanes take part in both moves before any lane finds that a block has no image: a block without one only skips its
+//     stores, and no lane leaves before a barrier of inverse_granule;
+//   * the ownership question is asked about the block a lane STORES, run_first + 32 q + l / 2, not about `b`, the block it holds.
+// TAIL, one workgroup: every lane fetches its own block's row, so the wave and then the lane ask about `b` itself, as the BC7
+// sink does; the tail part's last, partly filled wave reaches past the buffer's end and takes the per-lane path.
+// Written once for every kind of table the lookups of image_regions.h take.
+template <typename TABLE, bool TAIL>
+struct Bc6hRegionPixelSinkOf {
+    using One = Bc6hPixelSink<TAIL>;
+    static constexpr bool kStaged = One::kStaged;
+    static constexpr int kParts = One::kParts;
+    static constexpr int kStageBytes = One::kStageBytes;
+    using Held = typename One::Held;
+    TABLE tab;
+
+    // (the single-image sink's members do not read its fields)
+    __device__ __forceinline__ Held hold(const B128& b) const { return One{}.hold(b); }
+    __device__ __forceinline__ void stage(uint8_t* lds, int j, const Held& h, int part) const { One{}.stage(lds, j, h, part); }
+
+    // the region that holds the whole granule (tail part), if one does: most granules of a large image
+    using Prepared = WaveRun;
+    __device__ __forceinline__ Prepared prepare(uint64_t first, uint64_t n) const { return wave_run(tab, first, n); }
+
+    // full granules: half `half` of pixel row `part` of block `local` of `img`, staged at sorted position `pos`
+    __device__ __forceinline__ void fetch_and_store_half(uint8_t* lds, const ImageSink& img, uint64_t local, int pos, int part, int half) const
+    {
+        store_half_row(img, place_block<8>(img, local), part, half, granule::lds_at<u32x4>(lds, 32 * pos + 16 * half));
+    }
+
+    // TAIL: pixel row `part` of block `local` of `img`
+    __device__ __forceinline__ void fetch_and_store_row(uint8_t* lds, const ImageSink& img, uint64_t local, int pos, int part) const
+    {
+        const u32x4 row[2] = {granule::lds_at<u32x4>(lds, 32 * pos), granule::lds_at<u32x4>(lds, 32 * pos + 16)};
+        store_block_row(img, place_block<8>(img, local), part, row);
+    }
+
+    __device__ __forceinline__ void store_staged(uint8_t* lds, uint64_t b, int pos, int part, const Prepared& whole) const
+    {
+        static_assert(kT % 64 == 0, "a wave's 64 blocks start at a multiple of 64");
+        if constexpr (!TAIL) {
+            // every lane of the wave is here; a granule starts at a multiple of 1024 blocks, so the lane is b's low six bits and the
+            // wave's first block is b with them cleared
+            const int lane = (int)(b & 63u);
+            const uint64_t run_first = b & ~(uint64_t)63;
+            const int mine = lane >> 1, half = lane & 1;   // the lane stores halves `half` of blocks mine and 32 + mine of the run
+            const int pos_lo = __builtin_amdgcn_ds_bpermute(mine * 4, pos);
+            const int pos_hi = __builtin_amdgcn_ds_bpermute((32 + mine) * 4, pos);
+            if (whole.region >= 0) {
+                const uint64_t local = whole.local + (run_first - whole.first) + (uint64_t)mine;
+                fetch_and_store_half(lds, whole.img, local, pos_lo, part, half);
+                fetch_and_store_half(lds, whole.img, local + 32, pos_hi, part, half);
+                return;
+            }
+            const WaveRun run = wave_run(tab, run_first, 64);
+            if (run.region >= 0) {
+                fetch_and_store_half(lds, run.img, run.local + (uint64_t)mine, pos_lo, part, half);
+                fetch_and_store_half(lds, run.img, run.local + (uint64_t)(32 + mine), pos_hi, part, half);
+            } else {
+                DXTLT_REGIONS_LOOP
+                for (int q = 0; q < 2; ++q) {
+                    ImageSink img{nullptr, 0, 1, 0, 0, 8};
+                    uint64_t local = 0;
+                    if (region_of_block(tab, run_first + (uint64_t)(32 * q + mine), img, local) >= 0)
+                        fetch_and_store_half(lds, img, local, q ? pos_hi : pos_lo, part, half);
+                }
+            }
+        } else {
+            if (whole.region >= 0) {
+                fetch_and_store_row(lds, whole.img, whole.local + (b - whole.first), pos, part);
+                return;
+            }
+            const WaveRun run = wave_run(tab, b & ~(uint64_t)63, 64);
+            if (run.region >= 0) {
+                fetch_and_store_row(lds, run.img, run.local + (b & 63), pos, part);
+            } else {
+                ImageSink img{nullptr, 0, 1, 0, 0, 8};
+                uint64_t local = 0;
+                if (region_of_block(tab, b, img, local) >= 0)
+                    fetch_and_store_row(lds, img, local, pos, part);
+            }
+        }
+    }
+};
+
+// the table in the kernel arguments (bc6h_image_regions_kernels.hip)
+template <bool TAIL>
+using Bc6hRegionPixelSink = Bc6hRegionPixelSinkOf<ImageRegionTable, TAIL>;
 
 }  // namespace
 }  // namespace bc6h

@@ -10,7 +10,6 @@
 #include "../../include/dxtlt_gfx950.h"
 #include "bc7_decode.h"
 #include "bc7_image_launch.h"
-#include "granule_launch.h"   // for_each_range_launch
 #include "host_common.h"
 #include "image_host.h"
 
@@ -164,35 +163,8 @@ int32_t dxtlt_untransform_decode_bc7_images(const uint8_t* transformed, size_t l
 int32_t dxtlt_debug_plan_bc7_images(uint64_t total_blocks, const DxtltImageRegion* regions, size_t region_count,
                                     DxtltBc7ImagesLaunch* out, size_t cap)
 {
-    // the device call's checks but for the buffer pointer, which this call does not have: any non-NULL address stands in
-    bool nothing = true;
-    if (check_regions(&nothing, total_blocks, regions, region_count, &nothing) != kOk)
-        return -1;
-    if (nothing)
-        return 0;
-    // the device call's walk: the same groups, the same plan of each group's covering range, records in the place of launches
-    size_t launches = 0, group_first = 0;
-    bool group_open = false;
-    const hipError_t e = for_each_region_group(
-        regions, region_count,
-        [&](size_t i) {
-            if (!group_open)
-                group_first = i, group_open = true;
-            return sink_of(regions[i]);
-        },
-        [&](const dxtlt::ImageRegionTable& tab) {
-            uint64_t first = 0, n = 0;
-            if (!dxtlt::covering_range(tab, total_blocks, first, n))
-                return hipErrorInvalidValue;
-            group_open = false;
-            return dxtlt::granule::for_each_range_launch(total_blocks, first, first + n, [&](uint64_t granule, uint64_t granules, bool tail) {
-                if (out != nullptr && launches < cap)
-                    out[launches] = DxtltBc7ImagesLaunch{(uint32_t)group_first, tab.count, granule, granules, tail ? 1u : 0u, 0u};
-                ++launches;
-                return hipSuccess;
-            });
-        });
-    return e == hipSuccess ? (int32_t)launches : -1;
+    // the arithmetic is the BC6H debug call's too (image_host.h)
+    return dxtlt_host::plan_granule_region_launches(kRgba8888, total_blocks, regions, region_count, out, cap);
 }
 
 }  // extern "C"

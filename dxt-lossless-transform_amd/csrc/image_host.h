@@ -2,13 +2,14 @@
 // RGBA8888, BC4 / BC5 -> R8 / RG8), bc7_image_api.cpp, bc6h_image_api.cpp and the two batch calls (image_batch_api.cpp,
 // bc7_image_batch_api.cpp).  A family is a PixelRule; an entry point keeps the checks that are its own (format, decorrelation
 // mode) and a lambda that names its launcher.  The order of the checks is the documented one (docs/IMAGE_DECODE.md, the public
-// headers).  Not installed.
+// headers).  The launch plan the two granule formats' debug calls report is here too.  Not installed.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
 #include "../../include/dxtlt_image.h"
+#include "granule_launch.h"   // for_each_range_launch
 #include "host_common.h"
 #include "image_region_groups.h"
 #include "image_sink.h"
@@ -125,6 +126,47 @@ inline const char* image_regions_defect(int32_t fmt, const void* buffer, uint64_
     if (const char* defect = image_regions_defect(pixel_rule(fmt), buffer, total_blocks, regions, count, nothing))
         return defect;
     return !*nothing && fmt <= 3 && mode > 3 ? "decorrelation_mode must be 0..3" : nullptr;
+}
+
+// The launches a fused region call of a granule format (BC7, BC6H) enqueues, as records in the place of launches -- the body of
+// dxtlt_debug_plan_bc7_images and dxtlt_debug_plan_bc6h_images.  The device call's checks but for the buffer pointer, which a plan
+// does not have, then the device call's walk: the same groups (for_each_region_group), the same plan of each group's covering
+// range (granule::for_each_range_launch).  RECORD is {first region, region count, first granule, granule count, tail, reserved};
+// records beyond `cap` are counted, not written.  Returns the number of launches, or -1 for a list the call would refuse.
+template <typename RECORD>
+int32_t plan_granule_region_launches(const PixelRule& rule, uint64_t total_blocks, const DxtltImageRegion* regions, size_t count,
+                                     RECORD* out, size_t cap)
+{
+    bool nothing = true;
+    // any non-NULL address stands in for the buffer
+    if (const char* defect = image_regions_defect(rule, &nothing, total_blocks, regions, count, &nothing)) {
+        fail(kInvalidArgument, defect);
+        return -1;
+    }
+    if (nothing)
+        return 0;
+    size_t launches = 0, group_first = 0;
+    bool group_open = false;
+    const hipError_t e = for_each_region_group(
+        regions, count,
+        [&](size_t i) {
+            if (!group_open)
+                group_first = i, group_open = true;
+            return dxtlt::make_image_sink(regions[i].pixels, regions[i].pitch, regions[i].width, regions[i].height, rule.bpp);
+        },
+        [&](const dxtlt::ImageRegionTable& tab) {
+            uint64_t first = 0, n = 0;
+            if (!dxtlt::covering_range(tab, total_blocks, first, n))
+                return hipErrorInvalidValue;
+            group_open = false;
+            return dxtlt::granule::for_each_range_launch(total_blocks, first, first + n, [&](uint64_t granule, uint64_t granules, bool tail) {
+                if (out != nullptr && launches < cap)
+                    out[launches] = RECORD{(uint32_t)group_first, tab.count, granule, granules, tail ? 1u : 0u, 0u};
+                ++launches;
+                return hipSuccess;
+            });
+        });
+    return e == hipSuccess ? (int32_t)launches : -1;
 }
 
 // The host-pointer path of one image, its arguments checked: one upload of the transformed buffer, launch(d_in, staged image,

@@ -1,5 +1,5 @@
-// image_region_groups.h -- how the image-region calls (image_api.cpp: BC1 - BC5; bc7_image_api.cpp: BC7; both through image_host.h,
-// which also checks the list) walk their region list: host code beside image_regions.h.
+// image_region_groups.h -- how the image-region calls (image_api.cpp: BC1 - BC5; bc7_image_api.cpp: BC7; bc6h_image_api.cpp: BC6H;
+// all through image_host.h, which also checks the list) walk their region list: host code beside image_regions.h.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -16,7 +16,8 @@ settings, any ``first_block``.  ``decode_bc6h_image`` and ``untransform_decode_b
 
 ``untransform_decode_images`` and ``decode_images`` write several images of one buffer in one call, for all five formats: a
 region is ``(first_block, width, height)``, and ``mip_chain`` lists the regions of a mip chain.
-``untransform_decode_bc7_images`` and ``decode_bc7_images`` are the same two calls for BC7 (no ``fmt``, no settings).
+``untransform_decode_bc7_images`` and ``decode_bc7_images`` are the same two calls for BC7 (no ``fmt``, no settings),
+``untransform_decode_bc6h_images`` and ``decode_bc6h_images`` for BC6H (RGBA16F, the default pitch ``8 * width``).
 ``untransform_decode_images_batch`` does the same for MANY transformed device buffers in one call: one launch per (format,
 settings) present in the batch, whatever the number of buffers; ``untransform_decode_bc7_images_batch`` is that call for BC7:
 at most two launches, whatever the number of buffers."""
@@ -36,8 +37,8 @@ _CHANNEL_BPP = {"bc4": 1, "bc5": 2}
 _ALL_FMT = {**_FMT, **_CHANNEL_FMT}
 _ALL_BLOCK = {**_BLOCK, **_CHANNEL_BLOCK}
 _ALL_BPP = {"bc1": 4, "bc2": 4, "bc3": 4, **_CHANNEL_BPP}
-_REGION_BLOCK = {**_ALL_BLOCK, "bc7": 16}   # the region helpers serve the BC7 calls too, which have entry points of their own
-_REGION_BPP = {**_ALL_BPP, "bc7": 4}
+_REGION_BLOCK = {**_ALL_BLOCK, "bc7": 16, "bc6h": 16}   # the region helpers serve the BC7 and BC6H calls too, which have entry points of their own
+_REGION_BPP = {**_ALL_BPP, "bc7": 4, "bc6h": 8}
 _declared = False
 
 
@@ -86,7 +87,11 @@ def _l():
         l.dxtlt_decode_bc6h_image_device.argtypes = [vp, u32, u32, vp, u64, vp]
         l.dxtlt_untransform_decode_bc6h_image_device.argtypes = [vp, u64, u64, u32, u32, vp, u64, vp]
         l.dxtlt_untransform_decode_bc6h_image.argtypes = [vp, C.c_size_t, u64, u32, u32, vp, u64]
-        for f in (l.dxtlt_decode_bc6h_image_device, l.dxtlt_untransform_decode_bc6h_image_device, l.dxtlt_untransform_decode_bc6h_image):
+        l.dxtlt_untransform_decode_bc6h_images_device.argtypes = [vp, u64, rp, C.c_size_t, vp]
+        l.dxtlt_decode_bc6h_images_device.argtypes = [vp, u64, rp, C.c_size_t, vp]
+        l.dxtlt_untransform_decode_bc6h_images.argtypes = [vp, C.c_size_t, rp, C.c_size_t]
+        for f in (l.dxtlt_decode_bc6h_image_device, l.dxtlt_untransform_decode_bc6h_image_device, l.dxtlt_untransform_decode_bc6h_image,
+                  l.dxtlt_untransform_decode_bc6h_images_device, l.dxtlt_decode_bc6h_images_device, l.dxtlt_untransform_decode_bc6h_images):
             f.restype = i32
         for f in (l.dxtlt_decode_bc7_image_device, l.dxtlt_untransform_decode_bc7_image_device, l.dxtlt_untransform_decode_bc7_image,
                   l.dxtlt_untransform_decode_bc7_images_device, l.dxtlt_decode_bc7_images_device, l.dxtlt_untransform_decode_bc7_images,
@@ -441,6 +446,40 @@ def decode_bc7_images(blocks, regions, *, total_blocks=None, outs=None, pitches=
 
     with torch.cuda.device(src.device):
         _check(_l().dxtlt_decode_bc7_images_device(src.ptr, total_blocks, table, count, torch.cuda.current_stream(src.device).cuda_stream))
+    del keep
+    return outs
+
+
+def untransform_decode_bc6h_images(transformed, regions, *, total_blocks=None, outs=None, pitches=None):
+    """``untransform_decode_images`` for BC6H (include/dxtlt_bc6h_image.h): every region ``(first_block, width, height)`` of the
+    WHOLE buffer ``transform_bc6h`` made to an RGBA16F image of its own, every granule un-sorted and decoded once.  Regions as
+    ``mip_chain`` returns them; host buffers or CUDA tensors (torch's current stream).  Returns the list of outputs, ``uint8``;
+    ``pitches[i]`` defaults to ``8 * width``, and ``out.view(torch.float16).reshape(height, width, 4)`` is the image then."""
+    src, total_blocks = _whole_buffer("bc6h", transformed, total_blocks)
+    outs, table, count, keep = _region_table("bc6h", src, regions, outs, pitches)
+    l = _l()
+    if src.device is None:
+        _check(l.dxtlt_untransform_decode_bc6h_images(src.ptr, total_blocks * 16, table, count))
+        return outs
+    import torch
+
+    with torch.cuda.device(src.device):
+        _check(l.dxtlt_untransform_decode_bc6h_images_device(src.ptr, total_blocks, table, count,
+                                                             torch.cuda.current_stream(src.device).cuda_stream))
+    del keep
+    return outs
+
+
+def decode_bc6h_images(blocks, regions, *, total_blocks=None, outs=None, pitches=None):
+    """The same from a BC6H block array in block order, a CUDA tensor (the library has no host-pointer form of it)."""
+    src, total_blocks = _whole_buffer("bc6h", blocks, total_blocks)
+    if src.device is None:
+        raise TypeError("decode_bc6h_images takes device tensors (the library has no host-pointer form of it)")
+    outs, table, count, keep = _region_table("bc6h", src, regions, outs, pitches)
+    import torch
+
+    with torch.cuda.device(src.device):
+        _check(_l().dxtlt_decode_bc6h_images_device(src.ptr, total_blocks, table, count, torch.cuda.current_stream(src.device).cuda_stream))
     del keep
     return outs
 

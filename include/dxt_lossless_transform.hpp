@@ -904,6 +904,23 @@ inline void untransform_decode_bc6h_image(const uint8_t* transformed, size_t len
 {
     detail::check_device(dxtlt_untransform_decode_bc6h_image(transformed, len, first_block, width, height, pixels, pitch));
 }
+// ADDITIVE: several images of one BC6H buffer in one call (dxtlt_bc6h_image.h, "several images of one BC6H buffer"): every granule
+// of the transformed buffer is un-sorted and decoded once, whatever the number of regions that have blocks in it.  The regions
+// are dxtlt_image.h's (image_mip_chain fills them for a chain), ascend and do not overlap; a pixel is eight bytes.
+inline void untransform_decode_bc6h_images_device(const void* d_transformed, uint64_t total_blocks, const DxtltImageRegion* regions,
+                                                  size_t region_count, void* hip_stream)
+{
+    detail::check_device(dxtlt_untransform_decode_bc6h_images_device(d_transformed, total_blocks, regions, region_count, hip_stream));
+}
+inline void decode_bc6h_images_device(const void* d_blocks, uint64_t total_blocks, const DxtltImageRegion* regions, size_t region_count,
+                                      void* hip_stream)
+{
+    detail::check_device(dxtlt_decode_bc6h_images_device(d_blocks, total_blocks, regions, region_count, hip_stream));
+}
+inline void untransform_decode_bc6h_images(const uint8_t* transformed, size_t len, const DxtltImageRegion* regions, size_t region_count)
+{
+    detail::check_device(dxtlt_untransform_decode_bc6h_images(transformed, len, regions, region_count));
+}
 
 }  // namespace api
 }  // namespace dxt_lossless_transform

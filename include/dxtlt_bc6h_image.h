@@ -28,6 +28,26 @@
  *   6. host call only: len not a multiple of 16: DXTLT_E_INVALID_LENGTH (1).
  * The block calls: len not a multiple of 16: 1; a NULL pointer with len > 0, or pixels_len < 128 * blocks: 2.
  *
+ * Several images of one BC6H buffer -- a mip chain, the faces of a cube map, the slices of an array -- in one call
+ * (docs/IMAGE_DECODE.md, "Several images of one BC6H buffer"): the dxtlt_*_bc6h_images* calls take the DxtltImageRegion list of
+ * dxtlt_image.h ("several images of one buffer") with that section's rules -- the non-empty regions ascend and do not overlap,
+ * gaps are legal and a block in a gap is written nowhere, empty regions are skipped, a region's first_block may be any block --
+ * and write, for every region, exactly the bytes the single-image call above writes for that region alone (for a block array:
+ * dxtlt_decode_bc6h_image_device), clipped blocks and pitch padding included; nothing else is written.
+ *   checks    in this order, before any device is touched: region_count == 0 or every region empty is DXTLT_OK and does
+ *             nothing; a NULL buffer or `regions` pointer; for every non-empty region in list order a NULL `pixels`,
+ *             pitch < 8 * width, pitch or `pixels` not a multiple of 8, first_block + blocks > total_blocks (wrap-safe), a
+ *             region that starts before the previous non-empty one ends -- all DXTLT_E_INVALID_ARGUMENT -- and, host call
+ *             only, len not a multiple of 16: DXTLT_E_INVALID_LENGTH.
+ *   launches  the non-empty regions are taken in groups of at most DXTLT_IMAGE_REGIONS_PER_LAUNCH consecutive ones.  The fused
+ *             call covers a group's range, from its first block to the end of its last region, as the single-image call covers
+ *             one image: one launch over the main part's granules that the range touches (split at 2^21 granules) and one over
+ *             the tail part if the range reaches it.  Every granule is un-sorted and decoded once per group; blocks in gaps are
+ *             decoded and dropped.  The block-array call is one launch per group.
+ *   device    the *_device calls enqueue on `hip_stream` only, allocate nothing, copy nothing to the device but kernel
+ *             arguments and do not synchronise: they can be captured into a HIP graph, the table frozen at capture.
+ * There is no call over many BC6H buffers yet.
+ *
  * The RGBA image calls of dxtlt_image.h, their region and batch calls and the BC7 calls of dxtlt_bc7_image.h do not take BC6H.
  */
 #ifndef DXTLT_BC6H_IMAGE_H
@@ -35,6 +55,8 @@
 
 #include <stddef.h>
 #include <stdint.h>
+
+#include "dxtlt_image.h" /* DxtltImageRegion, DXTLT_IMAGE_REGIONS_PER_LAUNCH */
 
 #ifdef __cplusplus
 extern "C" {
@@ -52,6 +74,34 @@ int32_t dxtlt_decode_bc6h_image_device(const void *d_blocks, uint32_t width, uin
 int32_t dxtlt_untransform_decode_bc6h_image_device(const void *d_transformed, uint64_t total_blocks, uint64_t first_block,
                                                    uint32_t width, uint32_t height, void *d_pixels, uint64_t pitch,
                                                    void *hip_stream);
+
+/* ---- several images of one buffer ------------------------------------------------------------------------ */
+/* a TRANSFORMED device buffer of total_blocks, any alignment -> every region's device image */
+int32_t dxtlt_untransform_decode_bc6h_images_device(const void *d_transformed, uint64_t total_blocks,
+                                                    const DxtltImageRegion *regions, size_t region_count, void *hip_stream);
+/* a device block array of total_blocks in block order, any alignment -> the same */
+int32_t dxtlt_decode_bc6h_images_device(const void *d_blocks, uint64_t total_blocks, const DxtltImageRegion *regions,
+                                        size_t region_count, void *hip_stream);
+/* host pointers: one upload of the whole transformed buffer of len bytes, the same kernels into staging (every region's
+ * base a multiple of 16, its rows a multiple of 16 bytes apart), one strided download per region */
+int32_t dxtlt_untransform_decode_bc6h_images(const uint8_t *transformed, size_t len, const DxtltImageRegion *regions,
+                                             size_t region_count);
+
+/* Test hook, no device needed: the launches dxtlt_untransform_decode_bc6h_images_device would enqueue, in order -- the
+ * arithmetic of dxtlt_debug_plan_bc7_images (dxtlt_bc7_image.h) with the 8-byte pixel's checks.  Addresses are numbers; nothing
+ * is dereferenced but `regions`, and a NULL buffer is not an error here.  Records beyond `cap` are counted, not written.  Returns
+ * the number of launches (0 for a list without a non-empty region), or -1 for a list the call would refuse. */
+typedef struct DxtltBc6hImagesLaunch {
+    uint32_t first_region;   /* index in the list of the group's first non-empty region */
+    uint32_t region_count;   /* non-empty regions of the group */
+    uint64_t first_granule;  /* the launch's first 1024-block granule; the tail part counts as granule main_blocks / 1024 */
+    uint64_t granule_count;  /* its workgroups: granules of the main part, 1 for the tail launch */
+    uint32_t tail;           /* 1: the tail part's launch */
+    uint32_t reserved;       /* 0 */
+} DxtltBc6hImagesLaunch;
+
+int32_t dxtlt_debug_plan_bc6h_images(uint64_t total_blocks, const DxtltImageRegion *regions, size_t region_count,
+                                     DxtltBc6hImagesLaunch *out, size_t cap);
 
 #ifdef __cplusplus
 }
