@@ -1,6 +1,6 @@
 // bc6h_granule_codec.h -- BC6H's codec for the granule sort of granule_sort.h: the record codec of bc6h_fields.h over 15 classes
 // -- the 14 modes, then the reserved mode encodings -- so all four class bits are matched by ballots in every segment.  Included
-// by bc6h_kernels.hip (the transform) and bc6h_image_kernels.hip (the inverse with a pixel sink).
+// by bc6h_kernels.hip (the transform) and, through bc6h_image_sinks.h, by the image kernels (the inverse with a pixel sink).
 #pragma once
 #include "bc6h_fields.h"
 #include "granule_sort.h"

@@ -1,7 +1,7 @@
-// bc6h_image_sinks.h -- device code the BC6H image kernels share (bc6h_image_kernels.hip: one image per call;
-// bc6h_image_regions_kernels.hip: several images of one buffer): the block decode of the plain decoders (their load is
-// image_store.h's load_block), the stores of a block's 32-byte pixel rows, and the staging sinks of the inverse granule sort --
-// Bc6hPixelSink for one image, Bc6hRegionPixelSinkOf for the images of a region table (image_regions.h).
+// bc6h_image_sinks.h -- what is BC6H's own in its image kernels (granule_image.h writes the kernels once for BC7 and BC6H): the
+// block decode of the plain decoders (their load is image_store.h's load_block), the stores of a block's 32-byte pixel rows, the
+// staging sinks of the inverse granule sort -- Bc6hPixelSink for one image, Bc6hRegionPixelSinkOf for the images of a region table
+// (image_regions.h) -- and Bc6hImage, the family that names them all.
 // docs/IMAGE_DECODE.md, "BC6H blocks to a row-major RGBA16F image" and "Several images of one BC6H buffer".
 #pragma once
 #include "bc6h_decode.h"
@@ -244,10 +244,22 @@ struct Bc6hRegionPixelSinkOf {
     }
 };
 
-// the table in the kernel arguments (bc6h_image_regions_kernels.hip)
-template <bool TAIL>
-using Bc6hRegionPixelSink = Bc6hRegionPixelSinkOf<ImageRegionTable, TAIL>;
-
 }  // namespace
+
+// BC6H as the kernels and launchers of granule_image.h see it: the family of RGBA16F images
+struct Bc6hImage {
+    using Codec = Bc6hCodec;
+    template <bool TAIL>
+    using Sink = Bc6hPixelSink<TAIL>;
+    template <typename TABLE, bool TAIL>
+    using RegionSink = Bc6hRegionPixelSinkOf<TABLE, TAIL>;
+    static constexpr uint32_t kBpp = 8;
+    // the plain decoders: a block's prepared endpoints and indices, interpolated and stored a pixel row at a time -- plain stores,
+    // never `sc1 nt` (store_block_row says why)
+    using Decoded = Interp;
+    static __device__ __forceinline__ void decode(u32x4 q, Decoded& s) { s = prepare_q(q); }
+    static __device__ __forceinline__ void store(const ImageSink& img, uint64_t b, const Decoded& s) { store_block_pixels(img, b, s); }
+};
+
 }  // namespace bc6h
 }  // namespace dxtlt

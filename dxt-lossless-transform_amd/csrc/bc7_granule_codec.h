@@ -1,7 +1,7 @@
 // bc7_granule_codec.h -- BC7's codec for the granule sort of granule_sort.h: the record codec of bc7_fields.h over nine classes
 // -- mode 0..7 by trailing zeros of byte 0, then the reserved byte-0 == 0 encoding, which is rare, so the ranks of a segment
-// without it come from two wave scans instead of ballots.  Included by bc7_kernels.hip (the transform) and bc7_image_kernels.hip
-// (the inverse with a pixel sink).
+// without it come from two wave scans instead of ballots.  Included by bc7_kernels.hip (the transform) and, through bc7_image_sinks.h,
+// by the image kernels (the inverse with a pixel sink).
 #pragma once
 #include "bc7_fields.h"
 #include "granule_sort.h"

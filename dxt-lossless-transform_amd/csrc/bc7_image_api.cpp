@@ -1,46 +1,23 @@
-// bc7_image_api.cpp -- C ABI of the BC7 decoders (include/dxtlt_bc7_image.h); kernels in bc7_image_kernels.hip and, for several
-// images of one buffer, bc7_image_regions_kernels.hip; the decoder itself in bc7_decode.h.  Every argument is checked before a
-// device is touched.  The checks (an RGBA8888 image, no format, no settings), the defects of a region list and the host-pointer
-// paths are image_host.h's.
-#include <hip/hip_runtime.h>
-
-#include <cstring>
-
+// bc7_image_api.cpp -- C ABI of the BC7 decoders (include/dxtlt_bc7_image.h): BC7 as a family of granule_image_api.h, which has the
+// bodies, and one forward per entry point.  The kernels are granule_image.h's, instantiated in bc7_image_kernels.hip (which has the
+// block-array decoders too) and bc7_image_regions_kernels.hip; the decoder itself is bc7_decode.h.
 #include "../../include/dxtlt_bc7_image.h"
 #include "../../include/dxtlt_gfx950.h"
 #include "bc7_decode.h"
-#include "bc7_image_launch.h"
-#include "host_common.h"
-#include "image_host.h"
-
-using dxtlt_host::blocks_of;
-using dxtlt_host::check_block_range;
-using dxtlt_host::check_image;
-using dxtlt_host::fail;
-using dxtlt_host::for_each_region_group;
-using dxtlt_host::kInvalidArgument;
-using dxtlt_host::kOk;
-using dxtlt_host::kRgba8888;
+#include "granule_image_api.h"
 
 namespace {
 
-constexpr size_t kDecodedBlockBytes = 64;
+namespace api = dxtlt_host::granule_image;
 
-int32_t check_decode(const void* in, size_t len, const void* out, size_t out_len)
-{
-    return dxtlt_host::check_decode(in, len, 16, out, out_len, kDecodedBlockBytes, "pixels_len is smaller than 64 bytes per block");
-}
-
-// ---- several images of one buffer --------------------------------------------------------------------------------------
-// the checks of the region calls, in the documented order; *nothing = there is no non-empty region (DXTLT_OK, nothing to do)
-int32_t check_regions(const void* buffer, uint64_t total_blocks, const DxtltImageRegion* regions, size_t count, bool* nothing)
-{
-    if (const char* defect = dxtlt_host::image_regions_defect(kRgba8888, buffer, total_blocks, regions, count, nothing))
-        return fail(kInvalidArgument, defect);
-    return kOk;
-}
-
-inline dxtlt::ImageSink sink_of(const DxtltImageRegion& r) { return dxtlt::make_image_sink(r.pixels, r.pitch, r.width, r.height); }
+struct Bc7 {
+    static constexpr dxtlt_host::PixelRule rule = dxtlt_host::kRgba8888;   // RGBA8888
+    static constexpr size_t kDecodedBlockBytes = 64;
+    static constexpr const char* kTooSmall = "pixels_len is smaller than 64 bytes per block";
+    static void decode_block(const dxtlt::bc7::B128& b, uint32_t (&px)[16]) { dxtlt::bc7::decode_bc7_block(b, px); }
+    static constexpr auto& launch_decode_blocks = dxtlt::bc7::launch_decode_blocks;
+    using Launch = dxtlt::bc7::Bc7Image;
+};
 
 }  // namespace
 
@@ -48,123 +25,56 @@ extern "C" {
 
 int32_t dxtlt_decode_bc7_blocks(const uint8_t* blocks, size_t len, uint8_t* pixels, size_t pixels_len)
 {
-    if (int32_t rc = check_decode(blocks, len, pixels, pixels_len); rc != kOk)
-        return rc;
-    // on the CPU, with the decoder the kernels run (bc7_decode.h): a Decoded4x4Block per block needs no device
-    for (size_t i = 0; i < len / 16; ++i) {
-        dxtlt::bc7::B128 b;
-        std::memcpy(b.d, blocks + 16 * i, 16);
-        uint32_t px[16];
-        dxtlt::bc7::decode_bc7_block(b, px);
-        for (int k = 0; k < 16; ++k)
-            for (int c = 0; c < 4; ++c)
-                pixels[kDecodedBlockBytes * i + 4 * k + c] = (uint8_t)(px[k] >> (8 * c));
-    }
-    return kOk;
+    return api::decode_blocks<Bc7>(blocks, len, pixels, pixels_len);
 }
 
 int32_t dxtlt_decode_bc7_blocks_device(const void* d_blocks, size_t len, void* d_pixels, size_t pixels_len, void* hip_stream)
 {
-    if (int32_t rc = check_decode(d_blocks, len, d_pixels, pixels_len); rc != kOk)
-        return rc;
-    HIP_TRY(dxtlt::bc7::launch_decode_blocks(d_blocks, d_pixels, len / 16, static_cast<hipStream_t>(hip_stream)), "kernel launch");
-    return kOk;
+    return api::decode_blocks_device<Bc7>(d_blocks, len, d_pixels, pixels_len, hip_stream);
 }
 
 int32_t dxtlt_decode_bc7_image_device(const void* d_blocks, uint32_t width, uint32_t height, void* d_pixels, uint64_t pitch,
                                       void* hip_stream)
 {
-    if (width == 0 || height == 0)
-        return kOk;
-    if (int32_t rc = check_image(kRgba8888, d_blocks, d_pixels, width, pitch); rc != kOk)
-        return rc;
-    HIP_TRY(dxtlt::bc7::launch_decode_image(d_blocks, dxtlt::make_image_sink(d_pixels, pitch, width, height),
-                                            static_cast<hipStream_t>(hip_stream)),
-            "kernel launch");
-    return kOk;
+    return api::decode_image_device<Bc7>(d_blocks, width, height, d_pixels, pitch, hip_stream);
 }
 
 int32_t dxtlt_untransform_decode_bc7_image_device(const void* d_transformed, uint64_t total_blocks, uint64_t first_block, uint32_t width,
                                                   uint32_t height, void* d_pixels, uint64_t pitch, void* hip_stream)
 {
-    if (width == 0 || height == 0)
-        return kOk;
-    if (int32_t rc = check_image(kRgba8888, d_transformed, d_pixels, width, pitch); rc != kOk)
-        return rc;
-    if (int32_t rc = check_block_range(total_blocks, first_block, blocks_of(width, height)); rc != kOk)
-        return rc;
-    HIP_TRY(dxtlt::bc7::launch_untransform_decode_image(d_transformed, total_blocks, first_block,
-                                                        dxtlt::make_image_sink(d_pixels, pitch, width, height),
-                                                        static_cast<hipStream_t>(hip_stream)),
-            "kernel launch");
-    return kOk;
+    return api::untransform_decode_image_device<Bc7>(d_transformed, total_blocks, first_block, width, height, d_pixels, pitch, hip_stream);
 }
 
 int32_t dxtlt_untransform_decode_bc7_image(const uint8_t* transformed, size_t len, uint64_t first_block, uint32_t width, uint32_t height,
                                            uint8_t* pixels, uint64_t pitch)
 {
-    if (width == 0 || height == 0)
-        return kOk;
-    if (int32_t rc = check_image(kRgba8888, transformed, pixels, width, pitch); rc != kOk)
-        return rc;
-    if (int32_t rc = dxtlt_host::check_host_range(len, 16, first_block, blocks_of(width, height)); rc != kOk)
-        return rc;
-    return dxtlt_host::untransform_decode_host_image(
-        transformed, len, kRgba8888.bpp, width, height, pixels, pitch, [&](const void* d_in, const dxtlt::ImageSink& staged, hipStream_t st) {
-            return dxtlt::bc7::launch_untransform_decode_image(d_in, len / 16, first_block, staged, st);
-        });
+    return api::untransform_decode_image<Bc7>(transformed, len, first_block, width, height, pixels, pitch);
 }
 
 int32_t dxtlt_untransform_decode_bc7_images_device(const void* d_transformed, uint64_t total_blocks, const DxtltImageRegion* regions,
                                                    size_t region_count, void* hip_stream)
 {
-    bool nothing = true;
-    if (int32_t rc = check_regions(d_transformed, total_blocks, regions, region_count, &nothing); rc != kOk || nothing)
-        return rc;
-    HIP_TRY(for_each_region_group(
-                regions, region_count, [&](size_t i) { return sink_of(regions[i]); },
-                [&](const dxtlt::ImageRegionTable& tab) {
-                    return dxtlt::bc7::launch_untransform_decode_image_regions(d_transformed, total_blocks, tab,
-                                                                               static_cast<hipStream_t>(hip_stream));
-                }),
-            "kernel launch");
-    return kOk;
+    return api::decode_images_device<Bc7>(dxtlt::launch_untransform_decode_image_regions<Bc7::Launch>, d_transformed, total_blocks, regions,
+                                          region_count, hip_stream);
 }
 
 int32_t dxtlt_decode_bc7_images_device(const void* d_blocks, uint64_t total_blocks, const DxtltImageRegion* regions, size_t region_count,
                                        void* hip_stream)
 {
-    bool nothing = true;
-    if (int32_t rc = check_regions(d_blocks, total_blocks, regions, region_count, &nothing); rc != kOk || nothing)
-        return rc;
-    HIP_TRY(for_each_region_group(
-                regions, region_count, [&](size_t i) { return sink_of(regions[i]); },
-                [&](const dxtlt::ImageRegionTable& tab) {
-                    return dxtlt::bc7::launch_decode_image_regions(d_blocks, total_blocks, tab, static_cast<hipStream_t>(hip_stream));
-                }),
-            "kernel launch");
-    return kOk;
+    return api::decode_images_device<Bc7>(dxtlt::launch_decode_image_regions<Bc7::Launch>, d_blocks, total_blocks, regions, region_count,
+                                          hip_stream);
 }
 
 int32_t dxtlt_untransform_decode_bc7_images(const uint8_t* transformed, size_t len, const DxtltImageRegion* regions, size_t region_count)
 {
-    const uint64_t total_blocks = len / 16;
-    bool nothing = true;
-    if (int32_t rc = check_regions(transformed, total_blocks, regions, region_count, &nothing); rc != kOk || nothing)
-        return rc;
-    if (int32_t rc = dxtlt_host::check_len(len, 16); rc != kOk)
-        return rc;
-    return dxtlt_host::untransform_decode_host_regions(
-        transformed, len, regions, region_count, kRgba8888.bpp, [&](const void* d_in, const dxtlt::ImageRegionTable& tab, hipStream_t st) {
-            return dxtlt::bc7::launch_untransform_decode_image_regions(d_in, total_blocks, tab, st);
-        });
+    return api::untransform_decode_images<Bc7>(transformed, len, regions, region_count);
 }
 
 int32_t dxtlt_debug_plan_bc7_images(uint64_t total_blocks, const DxtltImageRegion* regions, size_t region_count,
                                     DxtltBc7ImagesLaunch* out, size_t cap)
 {
     // the arithmetic is the BC6H debug call's too (image_host.h)
-    return dxtlt_host::plan_granule_region_launches(kRgba8888, total_blocks, regions, region_count, out, cap);
+    return dxtlt_host::plan_granule_region_launches(Bc7::rule, total_blocks, regions, region_count, out, cap);
 }
 
 }  // extern "C"

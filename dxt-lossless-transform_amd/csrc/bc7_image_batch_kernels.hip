@@ -3,7 +3,7 @@
 // call").
 //
 // The lookup of the batch untransform (bc7_batch_granules / bc7_batch_tails, bc7_kernels.hip) in front of the fused kernels of one
-// buffer (bc7_inverse_images, bc7_image_regions_kernels.hip): workgroup b of the granule launch finds its entry -- a group of up
+// buffer (inverse_images, granule_image.h): workgroup b of the granule launch finds its entry -- a group of up
 // to sixteen regions of one buffer -- through coarse[b / 64] and a short scan, and un-sorts and decodes ONE granule of that buffer's
 // main part; the tail launch has one workgroup per entry whose range reaches its buffer's tail part.  Each block's pixels go to
 // whichever region of the entry's table owns the block (Bc7RegionPixelSinkOf, bc7_image_sinks.h).  The table lies in device memory
@@ -76,7 +76,7 @@ bc7_batch_inverse_images(const ImageBatchEntry* __restrict__ entries, const uint
     inverse_granule<Bc7Codec, 256, false, BatchRegionPixelSink>(e.src, nullptr, e.main_blocks, first, 0, sink);
 }
 
-// One workgroup per tail entry, with the arguments bc7_inverse_images<256, true> gets: the tail part's byte 0, its blocks, and
+// One workgroup per tail entry, with the arguments inverse_images<Bc7Image, 256, true> gets: the tail part's byte 0, its blocks, and
 // main_blocks as its first block
 __global__ void __launch_bounds__(256)
 bc7_batch_inverse_image_tails(const ImageBatchEntry* __restrict__ tails)

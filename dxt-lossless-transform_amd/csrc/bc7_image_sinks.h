@@ -1,7 +1,8 @@
-// bc7_image_sinks.h -- device code the BC7 image kernels share (bc7_image_kernels.hip: one image per call;
-// bc7_image_regions_kernels.hip: several images of one buffer; bc7_image_batch_kernels.hip: the images of many buffers): the block
-// decode of the plain decoders (their load is image_store.h's load_block), the stores of a part of a block, and the staging sinks of the inverse granule sort --
-// Bc7PixelSink for one image, Bc7RegionPixelSinkOf for the images of a region table (image_regions.h).  docs/IMAGE_DECODE.md, "BC7" and "Several images of one BC7 buffer".
+// bc7_image_sinks.h -- what is BC7's own in its image kernels (granule_image.h writes the kernels once for BC7 and BC6H;
+// bc7_image_batch_kernels.hip: the images of many buffers): the block decode of the plain decoders (their load is image_store.h's
+// load_block), the stores of a part of a block, the staging sinks of the inverse granule sort -- Bc7PixelSink for one image,
+// Bc7RegionPixelSinkOf for the images of a region table (image_regions.h) -- and Bc7Image, the family that names them all.
+// docs/IMAGE_DECODE.md, "BC7" and "Several images of one BC7 buffer".
 #pragma once
 #include "bc7_decode.h"
 #include "bc7_granule_codec.h"
@@ -172,9 +173,22 @@ struct Bc7RegionPixelSinkOf {
     }
 };
 
-// the table in the kernel arguments (bc7_image_regions_kernels.hip); bc7_image_batch_kernels.hip has the one in device memory
-using Bc7RegionPixelSink = Bc7RegionPixelSinkOf<ImageRegionTable>;
-
 }  // namespace
+
+// BC7 as the kernels and launchers of granule_image.h see it: the family of RGBA8888 images.  Neither sink differs for the tail
+// part.  The table of RegionSink is the one in the kernel arguments there; bc7_image_batch_kernels.hip has the one in device memory.
+struct Bc7Image {
+    using Codec = Bc7Codec;
+    template <bool TAIL>
+    using Sink = Bc7PixelSink;
+    template <typename TABLE, bool TAIL>
+    using RegionSink = Bc7RegionPixelSinkOf<TABLE>;
+    static constexpr uint32_t kBpp = 4;
+    // the plain decoders: a block's sixteen pixels, stored as the BC2 / BC3 plain decoder stores them (image_store.h)
+    using Decoded = uint32_t[16];
+    static __device__ __forceinline__ void decode(u32x4 q, Decoded& px) { decode_px(q, px); }
+    static __device__ __forceinline__ void store(const ImageSink& img, uint64_t b, const Decoded& px) { store_block_pixels(img, b, px); }
+};
+
 }  // namespace bc7
 }  // namespace dxtlt

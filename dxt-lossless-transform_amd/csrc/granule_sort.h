@@ -287,7 +287,7 @@ __device__ __forceinline__ void forward_granule(const uint8_t* __restrict__ src,
 // A sink with kStaged takes the blocks in the SORTED domain instead, where a wave's blocks are of one class: hold(block) makes what
 // it wants of sorted block j (a Held, kept in registers), stage(lds, j, held, part) puts part `part` of kParts of it into LDS --
 // all of it is the sink's by then, kStageBytes of it -- and, behind a barrier, store_staged(lds, block index, sorted position,
-// part) writes that part out in block order.  bc7_image_kernels.hip has such a sink, which decodes the block and writes its
+// part) writes that part out in block order.  bc7_image_sinks.h has such a sink, which decodes the block and writes its
 // pixels (docs/IMAGE_DECODE.md, "BC7").
 struct BlockSink {
     static constexpr bool kStaged = false;

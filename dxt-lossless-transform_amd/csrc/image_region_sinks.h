@@ -42,6 +42,27 @@ __device__ __forceinline__ WaveRun wave_run(const TABLE& tab, uint64_t first, ui
 
 __device__ __forceinline__ WaveRun no_wave_run() { return WaveRun{-1, ImageSink{nullptr, 0, 1, 0, 0, 0}, 0, 0}; }
 
+// The wave has asked, now the lane asks: decoded block `b` of the buffer goes to STORE::store(its image, its number in that image,
+// decoded) -- the image of the wave's run if the run found one, else the one the lane finds for itself (STORE::kBpp: its bytes per
+// pixel); a block in no region is dropped.  STORE is Rgba8888Store below or the image family of BC7 or BC6H (granule_image.h).
+template <typename STORE, typename TABLE, typename DECODED>
+__device__ __forceinline__ void put_in_region(const TABLE& tab, const WaveRun& run, uint64_t b, const DECODED& decoded)
+{
+    if (run.region >= 0) {
+        STORE::store(run.img, run.local + (b - run.first), decoded);
+    } else {
+        ImageSink img{nullptr, 0, 1, 0, 0, STORE::kBpp};
+        uint64_t local = 0;
+        if (region_of_block(tab, b, img, local) >= 0)
+            STORE::store(img, local, decoded);
+    }
+}
+
+struct Rgba8888Store {
+    static constexpr uint32_t kBpp = 4;
+    static __device__ __forceinline__ void store(const ImageSink& img, uint64_t b, const uint32_t (&px)[16]) { store_block_pixels(img, b, px); }
+};
+
 // The sink of the inverse tiles for BC1 / BC2 / BC3 (bcn_device.h, AosSink): the launch's first block is block `block0` of the
 // BUFFER.
 template <typename TABLE>
@@ -52,14 +73,7 @@ struct RegionPixelSinkOf {
     // block `b` of the buffer, decoded
     __device__ __forceinline__ void put(const WaveRun& run, uint64_t b, const uint32_t (&px)[16]) const
     {
-        if (run.region >= 0) {
-            store_block_pixels(run.img, run.local + (b - run.first), px);
-        } else {
-            ImageSink img{nullptr, 0, 1, 0, 0, 4};
-            uint64_t local = 0;
-            if (region_of_block(tab, b, img, local) >= 0)
-                store_block_pixels(img, local, px);
-        }
+        put_in_region<Rgba8888Store>(tab, run, b, px);
     }
 
     template <int FMT>

@@ -247,68 +247,62 @@ def untransform_decode_channel_image(fmt: str, transformed, width: int, height: 
     return out
 
 
-# ---- BC7 -> RGBA8888 (include/dxtlt_bc7_image.h) ---------------------------------------------------------------------------
-def decode_bc7_image(blocks, width: int, height: int, out=None, pitch=None):
-    """``blocks``: ceil(width / 4) * ceil(height / 4) BC7 blocks in block order, a CUDA tensor.  Returns ``out`` (a new tensor of
-    ``pitch * height`` bytes when None); ``pitch`` defaults to ``4 * width``."""
+# ---- BC7 -> RGBA8888 (include/dxtlt_bc7_image.h), BC6H -> RGBA16F (include/dxtlt_bc6h_image.h) ------------------------------
+def _stream(device):
+    import torch
+
+    return torch.cuda.current_stream(device).cuda_stream
+
+
+def _decode_granule_image(fmt, blocks, width, height, out, pitch):
+    """``decode_bc7_image`` / ``decode_bc6h_image``: ``fmt`` is ``"bc7"`` / ``"bc6h"``"""
     from . import InvalidLength, _Buf
 
     src = _Buf(blocks, False)
     if src.device is None:
-        raise TypeError("decode_bc7_image takes device tensors (the library has no host-pointer form of it)")
+        raise TypeError(f"decode_{fmt}_image takes device tensors (the library has no host-pointer form of it)")
     if src.nbytes < image_blocks(width, height) * 16:
         raise InvalidLength(src.nbytes)
-    out, dst, pitch = _output(src, width, height, out, pitch)
+    out, dst, pitch = _output(src, width, height, out, pitch, _REGION_BPP[fmt])
     import torch
 
     with torch.cuda.device(src.device):
-        _check(_l().dxtlt_decode_bc7_image_device(src.ptr, width, height, dst.ptr, pitch, torch.cuda.current_stream(src.device).cuda_stream))
+        _check(getattr(_l(), f"dxtlt_decode_{fmt}_image_device")(src.ptr, width, height, dst.ptr, pitch, _stream(src.device)))
     return out
+
+
+def _untransform_decode_granule_image(fmt, transformed, width, height, first_block, total_blocks, out, pitch):
+    """``untransform_decode_bc7_image`` / ``untransform_decode_bc6h_image``"""
+    src, total_blocks = _whole_buffer(fmt, transformed, total_blocks)
+    out, dst, pitch = _output(src, width, height, out, pitch, _REGION_BPP[fmt])
+    call = f"dxtlt_untransform_decode_{fmt}_image"
+    if src.device is None:
+        _check(getattr(_l(), call)(src.ptr, total_blocks * 16, first_block, width, height, dst.ptr, pitch))
+        return out
+    import torch
+
+    with torch.cuda.device(src.device):
+        _check(getattr(_l(), call + "_device")(src.ptr, total_blocks, first_block, width, height, dst.ptr, pitch, _stream(src.device)))
+    return out
+
+
+def decode_bc7_image(blocks, width: int, height: int, out=None, pitch=None):
+    """``blocks``: ceil(width / 4) * ceil(height / 4) BC7 blocks in block order, a CUDA tensor.  Returns ``out`` (a new tensor of
+    ``pitch * height`` bytes when None); ``pitch`` defaults to ``4 * width``."""
+    return _decode_granule_image("bc7", blocks, width, height, out, pitch)
 
 
 def untransform_decode_bc7_image(transformed, width: int, height: int, *, first_block: int = 0, total_blocks=None, out=None, pitch=None):
     """``transformed``: the WHOLE buffer ``transform_bc7`` made, of ``total_blocks`` blocks (default: its length); the image is its
     blocks [first_block, first_block + ceil(width / 4) * ceil(height / 4)), ``first_block`` any block.  Returns ``out``."""
-    from . import InvalidLength, _Buf
-
-    src = _Buf(transformed, False)
-    if src.nbytes % 16 != 0:
-        raise InvalidLength(src.nbytes)
-    if total_blocks is None:
-        total_blocks = src.nbytes // 16
-    if total_blocks * 16 > src.nbytes:
-        raise InvalidLength(src.nbytes)
-    out, dst, pitch = _output(src, width, height, out, pitch)
-    l = _l()
-    if src.device is None:
-        _check(l.dxtlt_untransform_decode_bc7_image(src.ptr, total_blocks * 16, first_block, width, height, dst.ptr, pitch))
-        return out
-    import torch
-
-    with torch.cuda.device(src.device):
-        _check(l.dxtlt_untransform_decode_bc7_image_device(src.ptr, total_blocks, first_block, width, height, dst.ptr, pitch,
-                                                           torch.cuda.current_stream(src.device).cuda_stream))
-    return out
+    return _untransform_decode_granule_image("bc7", transformed, width, height, first_block, total_blocks, out, pitch)
 
 
-# ---- BC6H -> RGBA16F (include/dxtlt_bc6h_image.h) --------------------------------------------------------------------------
 def decode_bc6h_image(blocks, width: int, height: int, out=None, pitch=None):
     """``blocks``: ceil(width / 4) * ceil(height / 4) BC6H (UF16) blocks in block order, a CUDA tensor.  Returns ``out`` (a new
     ``uint8`` tensor of ``pitch * height`` bytes when None); ``pitch`` defaults to ``8 * width``: a pixel is four half floats r, g, b,
     a with a = 1.0, and ``out.view(torch.float16).reshape(height, width, 4)`` is the image when the pitch is the default."""
-    from . import InvalidLength, _Buf
-
-    src = _Buf(blocks, False)
-    if src.device is None:
-        raise TypeError("decode_bc6h_image takes device tensors (the library has no host-pointer form of it)")
-    if src.nbytes < image_blocks(width, height) * 16:
-        raise InvalidLength(src.nbytes)
-    out, dst, pitch = _output(src, width, height, out, pitch, 8)
-    import torch
-
-    with torch.cuda.device(src.device):
-        _check(_l().dxtlt_decode_bc6h_image_device(src.ptr, width, height, dst.ptr, pitch, torch.cuda.current_stream(src.device).cuda_stream))
-    return out
+    return _decode_granule_image("bc6h", blocks, width, height, out, pitch)
 
 
 def untransform_decode_bc6h_image(transformed, width: int, height: int, *, first_block: int = 0, total_blocks=None, out=None, pitch=None):
@@ -316,26 +310,7 @@ def untransform_decode_bc6h_image(transformed, width: int, height: int, *, first
     blocks [first_block, first_block + ceil(width / 4) * ceil(height / 4)), ``first_block`` any block.  Returns ``out``, ``uint8``;
     ``pitch`` defaults to ``8 * width``, and ``out.view(torch.float16).reshape(height, width, 4)`` is the image when the pitch is the
     default (``out.view(np.float16)`` for a host buffer)."""
-    from . import InvalidLength, _Buf
-
-    src = _Buf(transformed, False)
-    if src.nbytes % 16 != 0:
-        raise InvalidLength(src.nbytes)
-    if total_blocks is None:
-        total_blocks = src.nbytes // 16
-    if total_blocks * 16 > src.nbytes:
-        raise InvalidLength(src.nbytes)
-    out, dst, pitch = _output(src, width, height, out, pitch, 8)
-    l = _l()
-    if src.device is None:
-        _check(l.dxtlt_untransform_decode_bc6h_image(src.ptr, total_blocks * 16, first_block, width, height, dst.ptr, pitch))
-        return out
-    import torch
-
-    with torch.cuda.device(src.device):
-        _check(l.dxtlt_untransform_decode_bc6h_image_device(src.ptr, total_blocks, first_block, width, height, dst.ptr, pitch,
-                                                            torch.cuda.current_stream(src.device).cuda_stream))
-    return out
+    return _untransform_decode_granule_image("bc6h", transformed, width, height, first_block, total_blocks, out, pitch)
 
 
 # ---- several images of one buffer ---------------------------------------------------------------------------------------
@@ -376,6 +351,44 @@ def _whole_buffer(fmt, buffer, total_blocks):
     return src, total_blocks
 
 
+def _symbol(fmt):
+    """what a region call's name has between ``decode_`` and ``images``, and its leading format argument: BC7 and BC6H have entry
+    points of their own"""
+    return ("", (_ALL_FMT[fmt],)) if fmt in _ALL_FMT else (fmt + "_", ())
+
+
+def _untransform_decode_regions(fmt, transformed, regions, total_blocks, outs, pitches, settings=()):
+    """the fused region call of every format; ``settings``: the call's arguments behind the region list"""
+    src, total_blocks = _whole_buffer(fmt, transformed, total_blocks)
+    outs, table, count, keep = _region_table(fmt, src, regions, outs, pitches)
+    symbol, head = _symbol(fmt)
+    call = f"dxtlt_untransform_decode_{symbol}images"
+    if src.device is None:
+        _check(getattr(_l(), call)(*head, src.ptr, total_blocks * _REGION_BLOCK[fmt], table, count, *settings))
+        return outs
+    import torch
+
+    with torch.cuda.device(src.device):
+        _check(getattr(_l(), call + "_device")(*head, src.ptr, total_blocks, table, count, *settings, _stream(src.device)))
+    del keep
+    return outs
+
+
+def _decode_regions(fmt, blocks, regions, total_blocks, outs, pitches):
+    """the plain region call of every format"""
+    src, total_blocks = _whole_buffer(fmt, blocks, total_blocks)
+    symbol, head = _symbol(fmt)
+    if src.device is None:
+        raise TypeError(f"decode_{symbol}images takes device tensors (the library has no host-pointer form of it)")
+    outs, table, count, keep = _region_table(fmt, src, regions, outs, pitches)
+    import torch
+
+    with torch.cuda.device(src.device):
+        _check(getattr(_l(), f"dxtlt_decode_{symbol}images_device")(*head, src.ptr, total_blocks, table, count, _stream(src.device)))
+    del keep
+    return outs
+
+
 def untransform_decode_images(fmt: str, transformed, regions, *, total_blocks=None, decorrelation_mode=0,
                               split_alpha_endpoints: bool = False, split_colour_endpoints: bool = False, split_endpoints=None,
                               outs=None, pitches=None):
@@ -384,70 +397,27 @@ def untransform_decode_images(fmt: str, transformed, regions, *, total_blocks=No
     ``"bc5"``; ``"bc4"`` / ``"bc5"`` take ``split_endpoints`` (or ``split_alpha_endpoints``, as the C call does) and ignore the
     other settings.  The regions ascend and do not overlap.  Returns the list of outputs: ``outs[i]``, or a new buffer of
     ``pitch * height`` bytes where it is None; ``pitches[i]`` defaults to ``bpp * width``."""
-    src, total_blocks = _whole_buffer(fmt, transformed, total_blocks)
-    outs, table, count, keep = _region_table(fmt, src, regions, outs, pitches)
     if fmt in _CHANNEL_FMT and split_endpoints is not None:
         split_alpha_endpoints = split_endpoints
-    mode, sa, sc = int(decorrelation_mode), bool(split_alpha_endpoints), bool(split_colour_endpoints)
-    l = _l()
-    if src.device is None:
-        _check(l.dxtlt_untransform_decode_images(_ALL_FMT[fmt], src.ptr, total_blocks * _ALL_BLOCK[fmt], table, count, mode, sa, sc))
-        return outs
-    import torch
-
-    with torch.cuda.device(src.device):
-        _check(l.dxtlt_untransform_decode_images_device(_ALL_FMT[fmt], src.ptr, total_blocks, table, count, mode, sa, sc,
-                                                        torch.cuda.current_stream(src.device).cuda_stream))
-    del keep
-    return outs
+    settings = (int(decorrelation_mode), bool(split_alpha_endpoints), bool(split_colour_endpoints))
+    return _untransform_decode_regions(fmt, transformed, regions, total_blocks, outs, pitches, settings)
 
 
 def decode_images(fmt: str, blocks, regions, *, total_blocks=None, outs=None, pitches=None):
     """The same from a block array in block order, a CUDA tensor (the library has no host-pointer form of it)."""
-    src, total_blocks = _whole_buffer(fmt, blocks, total_blocks)
-    if src.device is None:
-        raise TypeError("decode_images takes device tensors (the library has no host-pointer form of it)")
-    outs, table, count, keep = _region_table(fmt, src, regions, outs, pitches)
-    import torch
-
-    with torch.cuda.device(src.device):
-        _check(_l().dxtlt_decode_images_device(_ALL_FMT[fmt], src.ptr, total_blocks, table, count,
-                                               torch.cuda.current_stream(src.device).cuda_stream))
-    del keep
-    return outs
+    return _decode_regions(fmt, blocks, regions, total_blocks, outs, pitches)
 
 
 def untransform_decode_bc7_images(transformed, regions, *, total_blocks=None, outs=None, pitches=None):
     """``untransform_decode_images`` for BC7 (include/dxtlt_bc7_image.h): every region ``(first_block, width, height)`` of the
     WHOLE buffer ``transform_bc7`` made to an RGBA8888 image of its own, every granule un-sorted and decoded once.  Regions as
     ``mip_chain`` returns them; host buffers or CUDA tensors (torch's current stream).  Returns the list of outputs."""
-    src, total_blocks = _whole_buffer("bc7", transformed, total_blocks)
-    outs, table, count, keep = _region_table("bc7", src, regions, outs, pitches)
-    l = _l()
-    if src.device is None:
-        _check(l.dxtlt_untransform_decode_bc7_images(src.ptr, total_blocks * 16, table, count))
-        return outs
-    import torch
-
-    with torch.cuda.device(src.device):
-        _check(l.dxtlt_untransform_decode_bc7_images_device(src.ptr, total_blocks, table, count,
-                                                            torch.cuda.current_stream(src.device).cuda_stream))
-    del keep
-    return outs
+    return _untransform_decode_regions("bc7", transformed, regions, total_blocks, outs, pitches)
 
 
 def decode_bc7_images(blocks, regions, *, total_blocks=None, outs=None, pitches=None):
     """The same from a BC7 block array in block order, a CUDA tensor (the library has no host-pointer form of it)."""
-    src, total_blocks = _whole_buffer("bc7", blocks, total_blocks)
-    if src.device is None:
-        raise TypeError("decode_bc7_images takes device tensors (the library has no host-pointer form of it)")
-    outs, table, count, keep = _region_table("bc7", src, regions, outs, pitches)
-    import torch
-
-    with torch.cuda.device(src.device):
-        _check(_l().dxtlt_decode_bc7_images_device(src.ptr, total_blocks, table, count, torch.cuda.current_stream(src.device).cuda_stream))
-    del keep
-    return outs
+    return _decode_regions("bc7", blocks, regions, total_blocks, outs, pitches)
 
 
 def untransform_decode_bc6h_images(transformed, regions, *, total_blocks=None, outs=None, pitches=None):
@@ -455,33 +425,12 @@ def untransform_decode_bc6h_images(transformed, regions, *, total_blocks=None, o
     WHOLE buffer ``transform_bc6h`` made to an RGBA16F image of its own, every granule un-sorted and decoded once.  Regions as
     ``mip_chain`` returns them; host buffers or CUDA tensors (torch's current stream).  Returns the list of outputs, ``uint8``;
     ``pitches[i]`` defaults to ``8 * width``, and ``out.view(torch.float16).reshape(height, width, 4)`` is the image then."""
-    src, total_blocks = _whole_buffer("bc6h", transformed, total_blocks)
-    outs, table, count, keep = _region_table("bc6h", src, regions, outs, pitches)
-    l = _l()
-    if src.device is None:
-        _check(l.dxtlt_untransform_decode_bc6h_images(src.ptr, total_blocks * 16, table, count))
-        return outs
-    import torch
-
-    with torch.cuda.device(src.device):
-        _check(l.dxtlt_untransform_decode_bc6h_images_device(src.ptr, total_blocks, table, count,
-                                                             torch.cuda.current_stream(src.device).cuda_stream))
-    del keep
-    return outs
+    return _untransform_decode_regions("bc6h", transformed, regions, total_blocks, outs, pitches)
 
 
 def decode_bc6h_images(blocks, regions, *, total_blocks=None, outs=None, pitches=None):
     """The same from a BC6H block array in block order, a CUDA tensor (the library has no host-pointer form of it)."""
-    src, total_blocks = _whole_buffer("bc6h", blocks, total_blocks)
-    if src.device is None:
-        raise TypeError("decode_bc6h_images takes device tensors (the library has no host-pointer form of it)")
-    outs, table, count, keep = _region_table("bc6h", src, regions, outs, pitches)
-    import torch
-
-    with torch.cuda.device(src.device):
-        _check(_l().dxtlt_decode_bc6h_images_device(src.ptr, total_blocks, table, count, torch.cuda.current_stream(src.device).cuda_stream))
-    del keep
-    return outs
+    return _decode_regions("bc6h", blocks, regions, total_blocks, outs, pitches)
 
 
 # ---- many buffers in one call -------------------------------------------------------------------------------------------

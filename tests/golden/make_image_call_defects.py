@@ -63,6 +63,10 @@ SIGNATURES = {
     "dxtlt_decode_bc6h_image_device": [vp, u32, u32, vp, u64, vp],
     "dxtlt_untransform_decode_bc6h_image_device": [vp, u64, u64, u32, u32, vp, u64, vp],
     "dxtlt_untransform_decode_bc6h_image": [vp, sz, u64, u32, u32, vp, u64],
+    "dxtlt_untransform_decode_bc6h_images_device": [vp, u64, rp, sz, vp],
+    "dxtlt_decode_bc6h_images_device": [vp, u64, rp, sz, vp],
+    "dxtlt_untransform_decode_bc6h_images": [vp, sz, rp, sz],
+    "dxtlt_debug_plan_bc6h_images": [u64, rp, sz, vp, sz],
     "dxtlt_untransform_decode_images_batch_device": [C.POINTER(BatchItem), sz, vp],
     "dxtlt_debug_plan_image_batch": [C.POINTER(BatchItem), sz, vp, sz],
     "dxtlt_untransform_decode_bc7_images_batch_device": [C.POINTER(Bc7BatchItem), sz, vp],
@@ -180,26 +184,31 @@ def image_cases():
 
 
 # ---- several images of one buffer, and many buffers -------------------------------------------------------------------------------
-REGION_CALLS = [   # call, kind, formats (None: no format argument), has a mode
-    ("dxtlt_decode_images_device", "plain", (1, 3, 4, 5), False),
-    ("dxtlt_untransform_decode_images_device", "fused", (1, 3, 4, 5), True),
-    ("dxtlt_untransform_decode_images", "host", (1, 3, 4, 5), True),
-    ("dxtlt_decode_bc7_images_device", "plain", (None,), False),
-    ("dxtlt_untransform_decode_bc7_images_device", "fused", (None,), False),
-    ("dxtlt_untransform_decode_bc7_images", "host", (None,), False),
-    ("dxtlt_debug_plan_bc7_images", "plan", (None,), False),
+REGION_CALLS = [   # call, kind, formats (None: no format argument), has a mode, bytes per pixel of a call without a format
+    ("dxtlt_decode_images_device", "plain", (1, 3, 4, 5), False, 4),
+    ("dxtlt_untransform_decode_images_device", "fused", (1, 3, 4, 5), True, 4),
+    ("dxtlt_untransform_decode_images", "host", (1, 3, 4, 5), True, 4),
+    ("dxtlt_decode_bc7_images_device", "plain", (None,), False, 4),
+    ("dxtlt_untransform_decode_bc7_images_device", "fused", (None,), False, 4),
+    ("dxtlt_untransform_decode_bc7_images", "host", (None,), False, 4),
+    ("dxtlt_debug_plan_bc7_images", "plan", (None,), False, 4),
+    ("dxtlt_decode_bc6h_images_device", "plain", (None,), False, 8),
+    ("dxtlt_untransform_decode_bc6h_images_device", "fused", (None,), False, 8),
+    ("dxtlt_untransform_decode_bc6h_images", "host", (None,), False, 8),
+    ("dxtlt_debug_plan_bc6h_images", "plan", (None,), False, 8),
 ]
 
 
-def bpp_of(fmt):
-    return 4 if fmt is None or fmt <= 3 else fmt - 3
+def bpp_of(fmt, px=4):
+    """bytes per pixel and the multiple required of pitch and pointer; px: the bytes per pixel of a call without a format"""
+    if fmt is None:
+        return px, px
+    return (4, 4) if fmt <= 3 else (fmt - 3, fmt - 3)
 
 
-def region_defects(fmt, kind, has_mode):
+def region_defects(fmt, kind, has_mode, px=4):
     """the defects of a region list in the documented order; regions are [first_block, width, height, pixels, pitch]"""
-    bpp = mult = bpp_of(fmt)
-    if fmt is None or fmt <= 3:
-        mult = 4
+    bpp, mult = bpp_of(fmt, px)
     d = {}
     if fmt is not None:
         d["format"] = lambda s: s.update(fmt=0)
@@ -219,10 +228,8 @@ def region_defects(fmt, kind, has_mode):
     return d
 
 
-def region_variants(fmt, kind, has_mode):
-    bpp = mult = bpp_of(fmt)
-    if fmt is None or fmt <= 3:
-        mult = 4
+def region_variants(fmt, kind, has_mode, px=4):
+    bpp, mult = bpp_of(fmt, px)
 
     def set_region(k, i, value):
         return lambda s: s["regs"][k].__setitem__(i, value)
@@ -255,9 +262,9 @@ def region_nothing():
             "nothing to do, empty regions only": lambda s: s.update(regs=[[2**63, 0, 7, None, 0], [5, 3, 0, None, 1]], buf=None, mode=9, extra=5)}
 
 
-def region_base(fmt):
+def region_base(fmt, px=4):
     """two 8 x 8 regions, blocks 0 .. 3 and 4 .. 7 of 100"""
-    pitch = bpp_of(fmt) * 8
+    pitch = bpp_of(fmt, px)[0] * 8
     return dict(fmt=fmt, buf=SRC, total=100, regs=[[0, 8, 8, DST, pitch], [4, 8, 8, DST + 0x100000, pitch]], count=None, mode=1, extra=0)
 
 
@@ -281,30 +288,30 @@ def region_args(kind, has_mode, s, keep):
     return head + [s["buf"], s["total"], arr, count] + settings + [None]
 
 
-def region_scenarios(fmt, kind, has_mode):
+def region_scenarios(fmt, kind, has_mode, px=4):
     """(case name, scenario, has nothing to do)"""
     for name, change in region_nothing().items():
-        s = region_base(fmt)
+        s = region_base(fmt, px)
         change(s)
         yield name, s, True
-    defects = region_defects(fmt, kind, has_mode)
+    defects = region_defects(fmt, kind, has_mode, px)
     for names in [(n,) for n in defects] + list(itertools.combinations(defects, 2)) + [tuple(defects)]:
-        s = region_base(fmt)
+        s = region_base(fmt, px)
         # (a list that is NULL has no regions to spoil)
         for n in sorted(names, key=lambda n: n == "regions"):
             defects[n](s)
         yield " + ".join(names), s, False
-    for name, change in region_variants(fmt, kind, has_mode).items():
-        s = region_base(fmt)
+    for name, change in region_variants(fmt, kind, has_mode, px).items():
+        s = region_base(fmt, px)
         change(s)
         yield name, s, False
 
 
 def region_cases(keep):
-    for call, kind, fmts, has_mode in REGION_CALLS:
+    for call, kind, fmts, has_mode, px in REGION_CALLS:
         for fmt in fmts:
             tag = "" if fmt is None else f"format {fmt}: "
-            for name, s, nothing in region_scenarios(fmt, kind, has_mode):
+            for name, s, nothing in region_scenarios(fmt, kind, has_mode, px):
                 yield call, tag + name, region_args(kind, has_mode, s, keep), nothing
 
 
