@@ -123,6 +123,30 @@ def test_sink_clip_masks(sink):
     assert place(5, 7, 3) == (1, 1, 1, 3)
 
 
+@pytest.mark.parametrize("width", [20, 18])
+@pytest.mark.parametrize("pitch,height", [(2**30 + 48, 9), (2**32 + 48, 2), (2**30 + 47, 9), (2**32 + 47, 2)])
+def test_sink_offsets_beyond_32_bits(sink, pitch, height, width):
+    """The pitches of tests/test_wide_offsets_gpu.py: 4 * by * pitch passes 2^32 at block row 1 of a 20 x 9 image, and a pitch
+    of 2^32 + 48 does not fit 32 bits itself.  Every pixel address against y * pitch + 4 * x in Python integers, and the clip
+    of the last row (and, at width 18, of the last column)."""
+    base = 0x7F0000001000
+    blocks = 5 * ((height + 3) // 4)
+    assert sink.shim_image_blocks(width, height) == blocks
+    cap = width * height
+    address, block, pixel = np.zeros(cap, np.uint64), np.zeros(cap, np.uint64), np.zeros(cap, np.uint32)
+    n = sink.shim_image_sink_pixels(base, pitch, width, height, address.ctypes.data, block.ctypes.data, pixel.ctypes.data, cap)
+    assert n == cap
+    got = sorted((int(a), int(b), int(p)) for a, b, p in zip(address, block, pixel))
+    want = sorted((base + y * pitch + 4 * x, (y // 4) * 5 + x // 4, (y % 4) * 4 + x % 4) for y in range(height) for x in range(width))
+    assert got == want
+    assert max(a for a, _, _ in want) - base >= 2**32   # the case is what it says
+    out = (C.c_uint32 * 4)()
+    for b in range(blocks):
+        sink.shim_image_sink_place(pitch, width, height, b, out)
+        bx, by = b % 5, b // 5
+        assert tuple(out) == (bx, by, min(4, width - 4 * bx), min(4, height - 4 * by)), b
+
+
 # ---- argument checks: none of these may touch a device or an address ---------------------------------------------------
 SRC, DST = 0x7F1000000000, 0x7F2000000000   # made up
 
