@@ -351,6 +351,19 @@ def sharded_last_stats() -> list[dict]:
              "seconds": s.seconds} for s in buf[:n]]
 
 
+def host_route_counts() -> tuple[int, int, int, int, int]:
+    """Cumulative, process-wide counts of the routes the host-pointer and sharded calls have taken
+    (dxtlt_debug_host_route_counts): (mapped pair round trips, one-shot round trips, pipeline runs, pipeline chunks,
+    one-shot shard transfers).  Tests take the difference around a call."""
+    import ctypes as C
+
+    l = load()
+    l.dxtlt_debug_host_route_counts.argtypes, l.dxtlt_debug_host_route_counts.restype = [C.POINTER(C.c_uint64)], None
+    out = (C.c_uint64 * 5)()
+    l.dxtlt_debug_host_route_counts(out)
+    return tuple(int(v) for v in out)
+
+
 def device_local_cpulist(device: int) -> str:
     """CPUs local to a HIP device's PCI function ("" when the kernel does not say): dxtlt_device_local_cpulist."""
     import ctypes as C

@@ -105,6 +105,18 @@ int32_t pipelined_range(const StreamLayout& L, const Launch& launch, const Devic
                         uint8_t* out, uint64_t total, uint64_t first, uint64_t count);
 void release_thread_staging();   // of dxtlt_release_thread_resources()
 
+// The routes dxtlt_debug_host_route_counts reports, in its order: process-wide cumulative counters, bumped with relaxed
+// atomic adds (shard workers and the pipeline's downloader run on threads of their own).  Counting changes no route.
+enum HostRoute : int {
+    kRouteMapped = 0,          // host_round_trip through the mapped pinned pair
+    kRouteOneShot = 1,         // host_round_trip as one upload + launch + download
+    kRoutePipelinedRange = 2,  // calls of pipelined_range (whole buffers and shards)
+    kRoutePipelineChunk = 3,   // chunks pipelined_range has enqueued
+    kRouteShardOneShot = 4,    // one_shot transfers of host_sharded.cpp
+    kRouteCount = 5,
+};
+void count_route(HostRoute route);
+
 // ---- host_sharded.cpp -------------------------------------------------------------------------------
 // A host array of `total` blocks -- the last `tail` of them a part of its own behind the streams (granule formats; 0
 // otherwise) -- in contiguous shards over the node's devices, one bound worker thread per shard.  The arguments are

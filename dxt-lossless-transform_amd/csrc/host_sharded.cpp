@@ -161,6 +161,7 @@ int32_t one_shot(const ShardCtx& c, const Launch& launch, bool inverse, const ui
     const size_t bytes = (size_t)(count * B);
     hipError_t e = hipSuccess;
     int32_t rc = kOk;
+    count_route(kRouteShardOneShot);
     if (!inverse) {
         e = hipMemcpyAsync(c.a, in + aos_off, bytes, hipMemcpyHostToDevice, c.st);
         if (e == hipSuccess)

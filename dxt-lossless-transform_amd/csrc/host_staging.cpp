@@ -4,6 +4,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
+#include <atomic>
 #include <condition_variable>
 #include <cstdlib>
 #include <cstring>
@@ -164,6 +165,9 @@ uint64_t pipeline_chunk_bytes(const StreamLayout& L, uint64_t len)
     return dxtlt::granule::is_granule_format(L.format) ? granule_chunk_bytes(len) : block_chunk_bytes(len, L.format);
 }
 
+// dxtlt_debug_host_route_counts: which arm every host round trip and shard transfer of this process took (HostRoute)
+std::atomic<uint64_t> g_route_counts[kRouteCount];
+
 struct PipeShared {
     std::mutex m;
     std::condition_variable cv;
@@ -174,6 +178,14 @@ struct PipeShared {
 }  // namespace
 
 bool dxtlt_host::pipeline_pays(uint64_t bytes) { return bytes >= kPipelineMinBytes; }
+
+void dxtlt_host::count_route(HostRoute route) { g_route_counts[route].fetch_add(1, std::memory_order_relaxed); }
+
+extern "C" void dxtlt_debug_host_route_counts(uint64_t out[5])
+{
+    for (int r = 0; out != nullptr && r < kRouteCount; ++r)
+        out[r] = g_route_counts[r].load(std::memory_order_relaxed);
+}
 
 // ---------------------------------------------------------------------------------------------------
 // Chunked host path: H2D of chunk k+1, the kernel of chunk k and D2H of chunk k-1 overlap.
@@ -197,6 +209,7 @@ int32_t dxtlt_host::pipelined_range(const StreamLayout& S, const Launch& launch,
     chunk_blocks -= chunk_blocks % S.align_blocks;
     const int nchunks = (int)((blocks + chunk_blocks - 1) / chunk_blocks);
     const int dev = d.dev;
+    count_route(kRoutePipelinedRange);
 
     hipStream_t down = nullptr;
     HIP_TRY(hipStreamCreateWithFlags(&down, hipStreamNonBlocking), "hipStreamCreate(download)");
@@ -262,6 +275,8 @@ int32_t dxtlt_host::pipelined_range(const StreamLayout& S, const Launch& launch,
         }
         if (up_err == hipSuccess && rc == kOk)
             up_err = hipEventRecord(ev[(size_t)k], d.up);
+        if (up_err == hipSuccess && rc == kOk)
+            count_route(kRoutePipelineChunk);
         {
             std::lock_guard<std::mutex> lk(sh.m);
             if (up_err == hipSuccess && rc == kOk)
@@ -330,6 +345,7 @@ int32_t dxtlt_host::host_round_trip(const StreamLayout& L, const Launch& launch,
         return rc;
     if (m.usable) {
         // the kernel reads and writes mapped pinned staging itself (no copy-engine hand-overs)
+        count_route(kRouteMapped);
         std::memcpy(m.h_in, in, len);
         rc = launch(inverse, m.d_in, m.d_out, blocks, 0, blocks, m.stream);
         const hipError_t drained = hipStreamSynchronize(m.stream);
@@ -347,6 +363,7 @@ int32_t dxtlt_host::host_round_trip(const StreamLayout& L, const Launch& launch,
         return pipelined_range(L, launch, DeviceStaging{c.device, c.stream, c.d_in, c.d_out}, inverse, in, out, blocks, 0, blocks);
     // Every exit drains the stream first: the staging buffers belong to this thread's next call, which may free or
     // regrow them while an earlier copy or kernel of this one is still queued.
+    count_route(kRouteOneShot);
     hipError_t e = hipMemcpyAsync(c.d_in, in, len, hipMemcpyHostToDevice, c.stream);
     const char* what = "H2D copy";
     if (e == hipSuccess) {

@@ -312,6 +312,20 @@ const char *dxtlt_version(void);
  * across calls (sets in use by a call in flight are left alone).  Those sets are bounded without this call too: at most
  * two idle ones stay per device, i.e. at most 4 x the largest shard's bytes of HBM per device. */
 void dxtlt_release_thread_resources(void);
+/* Test hook: which way the host-pointer and sharded calls of this PROCESS have moved their buffers so far -- cumulative counts
+ * since the library was loaded, over all threads, formats and entry points (every format family shares these paths), never
+ * reset; read them before and after a call and subtract.  Counting changes no route.
+ *   out[0]  host round trips through the mapped pinned pair (buffers of up to 1 MiB, DXTLT_MAPPED_MAX_BYTES)
+ *   out[1]  host round trips as one upload + launch + download
+ *   out[2]  runs of the chunked pipeline: whole host buffers and shards of DXTLT_PIPELINE_MIN_BYTES (96 MiB) or more
+ *   out[3]  chunks those runs have enqueued: ceil(units / chunk) per run, where the chunk is DXTLT_PIPELINE_CHUNK_BYTES (or
+ *           the per-format default) divided by the block or pixel size, rounded down to a multiple of 2048 blocks (BC1-BC5),
+ *           1024 blocks (BC6H, BC7) or 4096 pixels
+ *   out[4]  one-shot shard transfers of the sharded calls: one per shard below the pipeline threshold, and one for the
+ *           tail part a pipelined BC6H / BC7 shard holds
+ * A host call of a format with a tail part (BC6H, BC7) that is large enough for the pipeline makes two round trips: its
+ * whole granules, then its tail. */
+void dxtlt_debug_host_route_counts(uint64_t out[5]);
 
 #ifdef __cplusplus
 }
