@@ -8,11 +8,9 @@ import numpy as np
 import pytest
 
 import pixels_ref as R
+from pixels_gpu_common import E_ARGUMENT, OK, Guarded, device_call
 
 pytestmark = pytest.mark.gpu
-
-GUARD = 64
-OK, E_ARGUMENT = 0, 2
 
 
 @pytest.fixture(scope="module")
@@ -29,39 +27,6 @@ def lib(pkg):
 
 def pixels(P, B, seed):
     return np.random.default_rng(seed).integers(0, 256, P * B, dtype=np.uint8)
-
-
-class Guarded:
-    """`n` device bytes at offset `off` from a 256-byte aligned address, GUARD + off bytes of 0xA5 in front and GUARD behind"""
-
-    def __init__(self, dev, n, off=0, data=None):
-        import torch
-
-        self.n, self.at = n, GUARD + off
-        self.base = torch.full((self.at + n + GUARD,), 0xA5, dtype=torch.uint8, device=dev)
-        assert self.base.data_ptr() % 256 == 0
-        if data is not None:
-            self.base[self.at:self.at + n].copy_(torch.from_numpy(np.ascontiguousarray(data)).to(dev))
-        self.ptr = self.base.data_ptr() + self.at
-
-    def bytes(self):
-        """the payload, after checking the guards"""
-        host = self.base.cpu().numpy()
-        assert (host[:self.at] == 0xA5).all() and (host[self.at + self.n:] == 0xA5).all(), "guard bytes were written"
-        return host[self.at:self.at + self.n]
-
-
-def device_call(lib, dev, inverse, data, B, decorrelate, layout, in_off=0, out_off=0):
-    import torch
-
-    src, dst = Guarded(dev, data.size, in_off, data), Guarded(dev, data.size, out_off)
-    f = lib.dxtlt_untransform_pixels_device if inverse else lib.dxtlt_transform_pixels_device
-    with torch.cuda.device(dev):
-        rc = f(src.ptr, dst.ptr, data.size, B, decorrelate, layout, torch.cuda.current_stream().cuda_stream)
-    assert rc == OK
-    torch.cuda.synchronize()
-    assert np.array_equal(src.bytes(), data)
-    return dst.bytes()
 
 
 def check_both_directions(lib, dev, data, B, decorrelate, layout, in_off=0, out_off=0):

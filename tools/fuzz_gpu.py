@@ -3,7 +3,9 @@ random settings, block counts (tiny, around tile multiples, up to a few million)
 of both device pointers; BC7 whole buffers and granule ranges; batch calls over 1..40 buffers of mixed formats (BC7
 included), directions and pointer offsets.  Guard bytes around every output.  Prints one line per
 100 cases and the failing case's parameters (re-runnable: `python tools/fuzz_gpu.py --seed S --only CASE`).
-Test tooling: imports oracle/.   usage: python tools/fuzz_gpu.py [--seconds 300] [--seed 1]"""
+`--pixels` runs the uncompressed-pixel transform instead: the draw of tests/test_pixels_sweep_gpu.py (B, settings, count, both
+pointer offsets 0..127, whole buffer or two ranges, four kinds of data) against tests/pixels_ref.py, for as long as asked.
+Test tooling: imports oracle/.   usage: python tools/fuzz_gpu.py [--seconds 300] [--seed 1] [--pixels]"""
 import argparse
 import os
 import sys
@@ -231,15 +233,54 @@ def uniform_batch_case(case, rng, dev):
     return True, dict(case=case, kind="uniform_batch", ranged=False)
 
 
+def pixels_campaign(args, dev):
+    """--pixels: the combination draw of tests/test_pixels_sweep_gpu.py (tests/pixels_gpu_common.py: draw_case), case k from the
+    generator seeded [seed, k], against tests/pixels_ref.py; 50 cases to an arena, and on a failure each case of that arena again
+    on its own so that the line printed is re-runnable with --only"""
+    import ctypes
+
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import pixels_gpu_common as G
+    import pixels_ref
+
+    lib = pixels_ref.declare(ctypes.CDLL(pkg._lib.lib_path()))
+    draw = lambda k: G.draw_case(np.random.default_rng([args.seed, k]))
+    if args.only >= 0:
+        G.run_jobs(lib, dev, G.case_jobs(draw(args.only), args.only))
+        print(f"case {args.only} ok: {draw(args.only)}", flush=True)
+        return
+    t0, case = time.time(), 0
+    while time.time() - t0 < args.seconds:
+        ks = range(case, case + 50)
+        try:
+            G.run_jobs(lib, dev, [j for k in ks for j in G.case_jobs(draw(k), k)])
+        except AssertionError as whole:
+            for k in ks:
+                try:
+                    G.run_jobs(lib, dev, G.case_jobs(draw(k), k))
+                except AssertionError as e:
+                    print("FAIL", e, flush=True)
+                    sys.exit(1)
+            print("FAIL (only with its neighbours in one arena)", whole, flush=True)
+            sys.exit(1)
+        case += 50
+        if case % 5000 == 0:
+            print(f"{case} pixel cases ok, {time.time() - t0:.0f} s", flush=True)
+    print(f"done: {case} pixel cases, all exact, seed {args.seed}", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=300)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--only", type=int, default=-1)
     ap.add_argument("--batch-only", action="store_true", help="batch cases only")
+    ap.add_argument("--pixels", action="store_true", help="uncompressed-pixel cases only (RGBA8888 / BGRA8888 / BGR888)")
     args = ap.parse_args()
     pkg.load()
     dev = torch.device("cuda:0")
+    if args.pixels:
+        return pixels_campaign(args, dev)
     t0 = time.time()
     case = 0
     counts = {"bcn": 0, "bcn_ranged": 0, "bc7": 0, "bc7_ranged": 0, "batch": 0, "uniform_batch": 0}
