@@ -11,6 +11,11 @@
 // or shifted, as the single-buffer call would choose for that buffer -- or the buffer's edge tile.  Asynchronous and ordered
 // like a single call on the caller's stream.  Uncompressed-pixel items (formats 8, 9: include/dxtlt_pixels.h) are taken by the
 // host batch only: checked with the rest there, they go out as one launch each, behind the batches of their chunk.
+//
+// Planning is pure host arithmetic: plan_batch checks the whole batch and says what the call enqueues -- the granule launches, the
+// tile launches, the items that go out alone, every table's place in the staged buffer -- without touching a device or an address;
+// fill_tables writes the tables.  The call (batch_device) and the test hooks (dxtlt_debug_plan_batch, dxtlt_debug_plan_batch_call)
+// run the same two functions; the call stages through StagedTables (batch_tables.h), as the two image batch calls do.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -23,10 +28,10 @@
 #include <vector>
 
 #include "../../include/dxtlt_gfx950.h"
+#include "batch_tables.h"
 #include "bcn_launch.h"
 #include "granule_launch.h"
 #include "host_common.h"
-#include "table_ring.h"
 
 namespace {
 
@@ -63,7 +68,7 @@ int32_t launch_pixel_item(const DxtltBatchItem& it, void* stream)
                               pixel_layout_of(it.split_alpha_endpoints != 0, it.split_colour_endpoints != 0), stream);
 }
 
-// Table staging: table_ring.h (shared with the batch image call)
+// Table staging: table_ring.h, batch_tables.h (shared with the image batch calls)
 thread_local dxtlt_host::TableRing g_ring;
 
 // DXTLT_BATCH_TABLE_COPY=1: the table travels by hipMemcpyAsync (the first version; kept for the comparison in
@@ -83,30 +88,89 @@ hipError_t dxtlt_host::upload_table(TableSlot* slot, size_t bytes, hipStream_t s
 
 namespace {
 
-// The device batch; `pixels_allowed`: items of formats 8 and 9 are taken too (the host batch's chunks: their buffers are this
-// library's own staging, checked by the host call) -- the public device call keeps refusing them.
-int32_t batch_device(const DxtltBatchItem* items, size_t count, void* hip_stream, bool pixels_allowed)
+// The per-item checks of both batch calls, in the order in which defects are reported.  `host_call`: the texts of
+// dxtlt_transform_batch_host, whose items also stay below 4 GiB.  kOk, or the failure as fail() recorded it.
+int32_t batch_item_defect(const DxtltBatchItem& it, int max_format, bool host_call)
+{
+    if (it.format < 1 || it.format > max_format)
+        return fail(kInvalidArgument, host_call ? kHostFormatText : kDeviceFormatText);
+    if (it.len % item_block_bytes(it.format) != 0)
+        return fail(kInvalidLength, "batch item: len is not a multiple of the block size");
+    if (it.decorrelation_mode > 3 && dxtlt::format_has_colour(it.format))
+        return fail(kInvalidArgument, "batch item: decorrelation_mode must be 0..3");
+    if (it.len > 0 && (it.d_input == nullptr || it.d_output == nullptr))
+        return fail(kInvalidArgument, host_call ? "batch item: NULL buffer with len > 0" : "batch item: NULL device buffer with len > 0");
+    if (pixel_item_overlaps(it))
+        return fail(kInvalidArgument, "batch item: pixel input and output overlap");
+    if (host_call && it.len >= (size_t(4) << 30))
+        return fail(kInvalidArgument, "batch item of 4 GiB or more: use the single-buffer entry point");
+    return kOk;
+}
+
+// the settings a BC1..BC5 item's kernels are instantiated with (BC4 / BC5: no variant, no colour split; BC1 / BC2: no alpha split)
+inline dxtlt::Settings item_settings(const DxtltBatchItem& it)
+{
+    dxtlt::Settings s{};
+    s.variant = it.decorrelation_mode;
+    s.split_alpha = it.split_alpha_endpoints != 0;
+    s.split_colour = it.split_colour_endpoints != 0;
+    return dxtlt::effective_settings((dxtlt::Format)it.format, s);
+}
+
+// One launch of batch_kernel: the BC1..BC5 items of one format, direction and settings code that the kernel takes.  The kernel is
+// instantiated per settings combination (no run-time switch in front of every tile): a corpus usually has one or two.
+struct TileLaunch {
+    int key = 0;                     // ((format - 1) * 2 + inverse) << 4 | settings_code
+    std::vector<BatchEntry> entries;
+    uint32_t wgs = 0;
+    uint32_t uniform_wgs = 0;        // workgroups per buffer when all buffers own the same number (the kernel then divides instead
+                                     // of looking the entry up), else 0
+    bool strided = false;            // a regular array of buffers: one size and tile form, pointers a constant stride apart
+    int64_t src_stride = 0, dst_stride = 0;
+    bool wide = false;               // the form of its workgroup index, known once fill_tables has built it
+    size_t at = 0, entry_bytes = 0;  // in the staged buffer: the entries, then the workgroup index
+
+    dxtlt::Format format() const { return (dxtlt::Format)((key >> 5) + 1); }
+    bool inverse() const { return ((key >> 4) & 1) != 0; }
+};
+
+// BC7 items (format 7; no settings): their granules in one launch per direction, their tail parts in a second one.  BC6H items
+// (format 6) the same, in launches of their own.
+using GranuleEntry = dxtlt::granule::BatchEntry;
+struct GranuleLaunch {
+    std::vector<GranuleEntry> entries, tails;
+    std::vector<uint32_t> coarse;
+    uint64_t wgs = 0;
+    size_t items = 0;
+    size_t at = 0, entry_bytes = 0, tail_bytes = 0, bytes = 0;   // in the staged buffer: entries, tails, coarse index
+};
+
+// What a call enqueues, in its order: granules[0..3] (BC7 forward, inverse; BC6H forward, inverse), the tile launches, the singles,
+// the pixel items.
+struct BatchPlan {
+    GranuleLaunch granules[4];
+    std::vector<TileLaunch> tiles;   // present groups only, in ascending key
+    std::vector<size_t> singles;     // items the batch kernel does not take (plan_batch_entry): launched alone, behind the batches
+    std::vector<size_t> pixels;      // non-empty items of formats 8, 9: one launch each, behind the rest
+    size_t table_bytes = 0;          // every table above at a 16-byte aligned offset of ONE staged buffer
+};
+inline int granule_format(int q) { return q < 2 ? 7 : 6; }
+
+// Validates the batch as a whole and plans it; nothing is enqueued, no device is touched, no address is dereferenced.
+// `pixels_allowed`: items of formats 8 and 9 are taken too (the host batch's chunks: their buffers are this library's own staging,
+// checked by the host call) -- the public device call keeps refusing them.
+int32_t plan_batch(const DxtltBatchItem* items, size_t count, bool pixels_allowed, BatchPlan& plan)
 {
     if (count == 0)
         return kOk;
     if (items == nullptr)
         return fail(kInvalidArgument, "NULL item array with count > 0");
     // validate everything first: a batch is enqueued whole or not at all
-    for (size_t i = 0; i < count; ++i) {
-        const DxtltBatchItem& it = items[i];
-        if (it.format < 1 || it.format > (pixels_allowed ? 9 : 7))
-            return fail(kInvalidArgument, kDeviceFormatText);
-        if (it.len % item_block_bytes(it.format) != 0)
-            return fail(kInvalidLength, "batch item: len is not a multiple of the block size");
-        if (it.decorrelation_mode > 3 && dxtlt::format_has_colour(it.format))
-            return fail(kInvalidArgument, "batch item: decorrelation_mode must be 0..3");
-        if (it.len > 0 && (it.d_input == nullptr || it.d_output == nullptr))
-            return fail(kInvalidArgument, "batch item: NULL device buffer with len > 0");
-        if (pixel_item_overlaps(it))
-            return fail(kInvalidArgument, "batch item: pixel input and output overlap");
-    }
+    for (size_t i = 0; i < count; ++i)
+        if (int32_t rc = batch_item_defect(items[i], pixels_allowed ? 9 : 7, false); rc != kOk)
+            return rc;
     // one launch holds fewer than 2^32 threads = 2^24 workgroups of 256 lanes: for BC7 (or BC6H) that is 256 GiB of granules
-    // per direction.  Checked here, before anything is enqueued (a batch goes out whole or not at all).
+    // per direction
     for (const int format : {7, 6}) {
         uint64_t granules[2] = {0, 0};
         for (size_t i = 0; i < count; ++i)
@@ -115,79 +179,69 @@ int32_t batch_device(const DxtltBatchItem* items, size_t count, void* hip_stream
         if (granules[0] > 0xFFFFFFull || granules[1] > 0xFFFFFFull)
             return fail(kInvalidArgument, dxtlt::granule::named(format, "batch too large for one launch (256 GiB or more of ", " in one direction)"));
     }
-    hipStream_t user = static_cast<hipStream_t>(hip_stream);
 
-    // one table per (format, direction, settings) group, planned (and checked against the launch limit) before anything is
-    // enqueued; the groups are launched one after the other on the caller's stream, behind the BC7 launches.  The kernel is
-    // instantiated per settings combination (no run-time switch in front of every tile): a corpus usually has one or two.
-    struct Group {
-        std::vector<BatchEntry> entries;
-        uint32_t wgs = 0;
-        uint32_t uniform_wgs = 0;   // workgroups per buffer while all buffers own the same number
-        bool uniform = true;
-    };
-    constexpr int kGroups = 5 * 2 * 16;   // format, direction, variant x split_alpha x split_colour
-    std::vector<Group> groups(kGroups);
-    auto group_settings = [](int gi) {
-        dxtlt::Settings s{};
-        s.variant = (gi >> 2) & 3;
-        s.split_alpha = ((gi >> 1) & 1) != 0;
-        s.split_colour = (gi & 1) != 0;
-        return s;
-    };
-    std::vector<size_t> singles;   // items the batch kernel does not take (plan_batch_entry): launched alone, behind the batches
+    int launch_of_key[5 * 2 * 16];   // format, direction, settings code
+    for (int& l : launch_of_key)
+        l = -1;
     for (size_t i = 0; i < count; ++i) {
         const DxtltBatchItem& it = items[i];
-        if (it.len == 0 || dxtlt::granule::is_granule_format(it.format) || is_pixel_format(it.format))
+        if (it.len == 0 || dxtlt::granule::is_granule_format(it.format))
             continue;
+        if (is_pixel_format(it.format)) {
+            plan.pixels.push_back(i);
+            continue;
+        }
         if (it.len >= (size_t(64) << 30))
             return fail(kInvalidArgument, "batch item of 64 GiB or more: use the single-buffer entry point");
-        // (BC4 / BC5: no variant, no colour split -- their items fall into the group of variant 0 without it)
-        const bool colour = dxtlt::format_has_colour(it.format);
-        const int sa = dxtlt::format_has_alpha_split(it.format) && it.split_alpha_endpoints ? 1 : 0;
-        const int sc = colour && it.split_colour_endpoints ? 1 : 0, mode = colour ? it.decorrelation_mode : 0;
-        const int gi = (((it.format - 1) * 2 + (it.inverse ? 1 : 0)) << 4) | (mode << 2) | (sa << 1) | sc;
-        Group& g = groups[gi];
+        const dxtlt::Settings s = item_settings(it);
+        const int key = (((it.format - 1) * 2 + (it.inverse ? 1 : 0)) << 4) | settings_code(s);
+        int li = launch_of_key[key];
         BatchEntry e{};
         e.src = static_cast<const uint8_t*>(it.d_input);
         e.dst = static_cast<uint8_t*>(it.d_output);
         e.blocks = it.len / item_block_bytes(it.format);
-        e.first_wg = g.wgs;
-        const uint32_t wgs = dxtlt::plan_batch_entry((dxtlt::Format)it.format, it.inverse != 0, group_settings(gi), e);
+        e.first_wg = li >= 0 ? plan.tiles[(size_t)li].wgs : 0;
+        const uint32_t wgs = dxtlt::plan_batch_entry((dxtlt::Format)it.format, it.inverse != 0, s, e);
         if (wgs == 0xFFFFFFFFu) {
-            singles.push_back(i);
+            plan.singles.push_back(i);
             continue;
         }
+        if (li < 0) {
+            li = launch_of_key[key] = (int)plan.tiles.size();
+            plan.tiles.emplace_back();
+            plan.tiles.back().key = key;
+            plan.tiles.back().uniform_wgs = wgs;
+        }
+        TileLaunch& l = plan.tiles[(size_t)li];
         // one launch holds fewer than 2^32 threads = 2^24 workgroups of 256 (64 GiB of blocks per format, direction and settings)
-        if ((uint64_t)g.wgs + wgs > 0xFFFFFFull)
+        if ((uint64_t)l.wgs + wgs > 0xFFFFFFull)
             return fail(kInvalidArgument, "batch too large for one launch (64 GiB or more of one format, direction and settings)");
-        g.wgs += wgs;
-        g.entries.push_back(e);
-        // buffers of one size: every entry owns the same number of workgroups -- the kernel then divides instead of looking
-        // the entry up
-        if (g.entries.size() == 1)
-            g.uniform_wgs = wgs;
-        else if (wgs != g.uniform_wgs)
-            g.uniform = false;
+        l.wgs += wgs;
+        l.entries.push_back(e);
+        if (wgs != l.uniform_wgs)
+            l.uniform_wgs = 0;   // (stays 0: no buffer owns 0 workgroups)
     }
+    std::sort(plan.tiles.begin(), plan.tiles.end(), [](const TileLaunch& a, const TileLaunch& b) { return a.key < b.key; });
     static const bool no_uniform = dxtlt::experiment_env("DXTLT_BATCH_NO_UNIFORM") != nullptr;   // A/B switches of the experiments build (tools/batch_kernel_probe.py)
     static const bool no_strided = dxtlt::experiment_env("DXTLT_BATCH_NO_STRIDED") != nullptr;
+    for (TileLaunch& l : plan.tiles) {
+        const size_t n = l.entries.size();
+        if (no_uniform)
+            l.uniform_wgs = 0;
+        l.strided = l.uniform_wgs != 0 && !no_strided;   // (one buffer is a regular array too)
+        l.src_stride = n >= 2 ? (int64_t)(l.entries[1].src - l.entries[0].src) : 0;
+        l.dst_stride = n >= 2 ? (int64_t)(l.entries[1].dst - l.entries[0].dst) : 0;
+        for (size_t i = 1; i < n && l.strided; ++i) {
+            const BatchEntry &a = l.entries[0], &b = l.entries[i];
+            l.strided = b.blocks == a.blocks && b.full_tiles == a.full_tiles && b.form == a.form && b.halo_vecs == a.halo_vecs &&
+                        std::memcmp(b.shift, a.shift, sizeof a.shift) == 0 && std::memcmp(b.gbase, a.gbase, sizeof a.gbase) == 0 &&
+                        b.src == a.src + (int64_t)i * l.src_stride && b.dst == a.dst + (int64_t)i * l.dst_stride;
+        }
+    }
 
-    // BC7 items (format 7; no settings): their granules in one launch per direction, their tail parts in a second one.  Planned
-    // here, staged and launched below with everything else.  BC6H items (format 6) the same, in launches of their own: plans
-    // 0, 1 = BC7 forward, inverse; 2, 3 = BC6H forward, inverse.
-    using GranuleEntry = dxtlt::granule::BatchEntry;
-    struct GranulePlan {
-        std::vector<GranuleEntry> entries, tails;
-        std::vector<uint32_t> coarse;
-        uint64_t wgs = 0;
-        size_t at = 0, entry_bytes = 0, tail_bytes = 0, bytes = 0;
-    };
-    GranulePlan granule_plans[4];
-    size_t table_bytes = 0;
     for (int q = 0; q < 4; ++q) {
-        GranulePlan& p = granule_plans[q];
-        const int inverse = q & 1, format = q < 2 ? 7 : 6;
+        GranuleLaunch& p = plan.granules[q];
+        const int inverse = q & 1, format = granule_format(q);
         for (size_t i = 0; i < count; ++i) {
             const DxtltBatchItem& it = items[i];
             if (it.format != format || it.len == 0 || (it.inverse != 0) != (inverse != 0))
@@ -195,6 +249,7 @@ int32_t batch_device(const DxtltBatchItem* items, size_t count, void* hip_stream
             const uint64_t blocks = it.len / 16, tail = blocks % 1024, main = blocks - tail;
             const uint8_t* src = static_cast<const uint8_t*>(it.d_input);
             uint8_t* dst = static_cast<uint8_t*>(it.d_output);
+            ++p.items;
             if (main != 0) {
                 p.entries.push_back({src, dst, main, (uint32_t)p.wgs, 0});
                 p.wgs += main / 1024;
@@ -202,125 +257,97 @@ int32_t batch_device(const DxtltBatchItem* items, size_t count, void* hip_stream
             if (tail != 0)
                 p.tails.push_back({src + main * 16, dst + main * 16, 0, 0, (uint32_t)tail});
         }
-        if (p.entries.empty() && p.tails.empty())
+        if (p.items == 0)
             continue;
-        p.coarse.resize(((size_t)p.wgs + 63) / 64);
-        size_t cur = 0;
-        for (size_t k = 0; k < p.coarse.size(); ++k) {
-            while (cur + 1 < p.entries.size() && p.entries[cur + 1].first_wg <= (uint32_t)(k * 64))
-                ++cur;
-            p.coarse[k] = (uint32_t)cur;
-        }
+        p.coarse.resize(coarse_index_count((uint32_t)p.wgs));
+        build_coarse_index(p.entries.data(), p.entries.size(), (uint32_t)p.wgs, p.coarse.data());
         p.entry_bytes = p.entries.size() * sizeof(GranuleEntry);
         p.tail_bytes = p.tails.size() * sizeof(GranuleEntry);
-        p.bytes = (p.entry_bytes + p.tail_bytes + p.coarse.size() * sizeof(uint32_t) + 15) & ~(size_t)15;
-        p.at = table_bytes;
-        table_bytes += p.bytes;
+        p.bytes = padded(p.entry_bytes + p.tail_bytes + p.coarse.size() * sizeof(uint32_t), 16);
+        p.at = plan.table_bytes;
+        plan.table_bytes += p.bytes;
     }
-
-    // Every table of the call -- the two BC7 tables above, then every group's (entries, then the workgroup index) -- goes into ONE
-    // staged buffer and ONE upload, at 16-byte aligned offsets: one ring slot per call.  (One slot per group made a call with many
+    // Every table of the call -- the granule tables above, then every tile launch's (entries, then the workgroup index) -- goes into
+    // ONE staged buffer and ONE upload, at 16-byte aligned offsets: one ring slot per call.  (One slot per group made a call with many
     // settings combinations -- rare in a corpus, routine in the fuzz: up to 96 groups -- wait in hipEventSynchronize for kernels this
     // same call had enqueued: the "asynchronous" call then drained its own work, and would deadlock under a caller whose stream is
     // gated on an event recorded after the call returns.  Three slots per call -- BC7 forward, BC7 inverse, the groups -- still let
     // the NEXT mixed call wait for this one's kernels; see the ring's comment.)
-    struct Placed {
-        int gi;
-        size_t at, entry_bytes;
-    };
-    std::vector<Placed> placed;
-    for (int gi = 0; gi < kGroups; ++gi) {
-        const Group& g = groups[gi];
-        if (g.entries.empty())
-            continue;
-        const size_t entry_bytes = (g.entries.size() * sizeof(BatchEntry) + 15) & ~(size_t)15;
-        placed.push_back({gi, table_bytes, entry_bytes});
-        table_bytes += entry_bytes + dxtlt::batch_index_bytes(g.wgs);
+    for (TileLaunch& l : plan.tiles) {
+        l.entry_bytes = padded(l.entries.size() * sizeof(BatchEntry), 16);
+        l.at = plan.table_bytes;
+        plan.table_bytes += l.entry_bytes + dxtlt::batch_index_bytes(l.wgs);
     }
-    if (table_bytes != 0) {
-        TableSlot* slot = nullptr;
-        hipError_t e = g_ring.acquire(table_bytes, &slot);
+    return kOk;
+}
+
+// Writes the plan's tables into `host` (plan.table_bytes bytes, 16-byte aligned) as the device reads them
+void fill_tables(BatchPlan& plan, uint8_t* host)
+{
+    for (const GranuleLaunch& p : plan.granules) {
+        uint8_t* h = host + p.at;
+        if (p.entry_bytes) std::memcpy(h, p.entries.data(), p.entry_bytes);
+        if (p.tail_bytes) std::memcpy(h + p.entry_bytes, p.tails.data(), p.tail_bytes);
+        if (!p.coarse.empty()) std::memcpy(h + p.entry_bytes + p.tail_bytes, p.coarse.data(), p.coarse.size() * sizeof(uint32_t));
+    }
+    for (TileLaunch& l : plan.tiles) {
+        std::memcpy(host + l.at, l.entries.data(), l.entries.size() * sizeof(BatchEntry));
+        l.wide = dxtlt::build_batch_index(l.entries.data(), l.entries.size(), l.wgs, host + l.at + l.entry_bytes);
+    }
+}
+
+// The device batch: planned whole, its tables staged in one slot, then its launches in the plan's order on the caller's stream
+int32_t batch_device(const DxtltBatchItem* items, size_t count, void* hip_stream, bool pixels_allowed)
+{
+    BatchPlan plan;
+    if (int32_t rc = plan_batch(items, count, pixels_allowed, plan); rc != kOk)
+        return rc;
+    hipStream_t user = static_cast<hipStream_t>(hip_stream);
+    if (plan.table_bytes != 0) {
+        StagedTables tables;
+        hipError_t e = tables.acquire(plan.table_bytes);
         if (e != hipSuccess)
             return fail(kDevice, "batch table staging", e);
-        for (const GranulePlan& p : granule_plans) {
-            if (p.bytes == 0)
-                continue;
-            uint8_t* h = static_cast<uint8_t*>(slot->host) + p.at;
-            if (p.entry_bytes) std::memcpy(h, p.entries.data(), p.entry_bytes);
-            if (p.tail_bytes) std::memcpy(h + p.entry_bytes, p.tails.data(), p.tail_bytes);
-            if (!p.coarse.empty()) std::memcpy(h + p.entry_bytes + p.tail_bytes, p.coarse.data(), p.coarse.size() * sizeof(uint32_t));
-        }
-        std::vector<bool> wide(placed.size());
-        for (size_t k = 0; k < placed.size(); ++k) {
-            const Group& g = groups[placed[k].gi];
-            uint8_t* h = static_cast<uint8_t*>(slot->host) + placed[k].at;
-            std::memcpy(h, g.entries.data(), g.entries.size() * sizeof(BatchEntry));
-            wide[k] = dxtlt::build_batch_index(g.entries.data(), g.entries.size(), g.wgs, h + placed[k].entry_bytes);
-        }
-        e = upload_table(slot, table_bytes, user);
+        fill_tables(plan, tables.host());
+        e = tables.upload(user);
         const char* what = "batch table copy / launch";
         for (int q = 0; q < 4 && e == hipSuccess; ++q) {
-            const GranulePlan& p = granule_plans[q];
-            const int inverse = q & 1, format = q < 2 ? 7 : 6;
+            const GranuleLaunch& p = plan.granules[q];
             if (p.bytes == 0)
                 continue;
-            const uint8_t* d = static_cast<const uint8_t*>(slot->dev) + p.at;
-            e = dxtlt::granule::launch_batch(format, inverse != 0, reinterpret_cast<const GranuleEntry*>(d),
+            const uint8_t* d = tables.dev() + p.at;
+            e = dxtlt::granule::launch_batch(granule_format(q), (q & 1) != 0, reinterpret_cast<const GranuleEntry*>(d),
                                              reinterpret_cast<const uint32_t*>(d + p.entry_bytes + p.tail_bytes), (uint32_t)p.entries.size(),
                                              (uint32_t)p.wgs, reinterpret_cast<const GranuleEntry*>(d + p.entry_bytes),
                                              (uint32_t)p.tails.size(), user);
             if (e != hipSuccess)
-                what = format == 7 ? "BC7 batch table copy / launch" : "BC6H batch table copy / launch";
+                what = granule_format(q) == 7 ? "BC7 batch table copy / launch" : "BC6H batch table copy / launch";
         }
-        for (size_t k = 0; k < placed.size() && e == hipSuccess; ++k) {
-            const int gi = placed[k].gi;
-            Group& g = groups[gi];
-            const size_t n = g.entries.size();
-            const bool uniform = g.uniform && !no_uniform;
-            // a regular array of buffers: one size and tile form, pointers a constant stride apart
-            bool strided = uniform && !no_strided;   // (one buffer is a regular array too)
-            const int64_t src_stride = n >= 2 ? (int64_t)(g.entries[1].src - g.entries[0].src) : 0;
-            const int64_t dst_stride = n >= 2 ? (int64_t)(g.entries[1].dst - g.entries[0].dst) : 0;
-            for (size_t i = 1; i < n && strided; ++i) {
-                const BatchEntry &a = g.entries[0], &b = g.entries[i];
-                strided = b.blocks == a.blocks && b.full_tiles == a.full_tiles && b.form == a.form && b.halo_vecs == a.halo_vecs &&
-                          std::memcmp(b.shift, a.shift, sizeof a.shift) == 0 && std::memcmp(b.gbase, a.gbase, sizeof a.gbase) == 0 &&
-                          b.src == a.src + (int64_t)i * src_stride && b.dst == a.dst + (int64_t)i * dst_stride;
-            }
-            const uint8_t* d = static_cast<const uint8_t*>(slot->dev) + placed[k].at;
-            e = dxtlt::launch_batch((dxtlt::Format)((gi >> 5) + 1), ((gi >> 4) & 1) != 0, group_settings(gi),
-                                    reinterpret_cast<const BatchEntry*>(d), d + placed[k].entry_bytes, (uint32_t)n, g.wgs,
-                                    uniform ? g.uniform_wgs : 0, wide[k], user, strided ? &g.entries[0] : nullptr, src_stride, dst_stride);
+        for (size_t k = 0; k < plan.tiles.size() && e == hipSuccess; ++k) {
+            const TileLaunch& l = plan.tiles[k];
+            const uint8_t* d = tables.dev() + l.at;
+            e = dxtlt::launch_batch(l.format(), l.inverse(), settings_of_code(l.key & 15), reinterpret_cast<const BatchEntry*>(d),
+                                    d + l.entry_bytes, (uint32_t)l.entries.size(), l.wgs, l.uniform_wgs, l.wide, user,
+                                    l.strided ? &l.entries[0] : nullptr, l.src_stride, l.dst_stride);
         }
-        // the event marks both the copy and the kernels that read the device table
-        hipError_t ev = hipEventRecord(slot->done, user);
-        slot->pending = ev == hipSuccess;
-        if (e != hipSuccess)
-            return fail(kDevice, what, e);
-        if (ev != hipSuccess)
-            return fail(kDevice, "batch event", ev);
+        if (int32_t rc = tables.finish(e, user, what, "batch event"); rc != kOk)
+            return rc;
     }
-    // buffers whose transformed-side pointer is not 8-byte aligned: the single-buffer call, one launch each
-    for (size_t i : singles) {
+    // buffers with a stream base off its element width: the single-buffer call, one launch each
+    for (size_t i : plan.singles) {
         const DxtltBatchItem& it = items[i];
-        dxtlt::Settings s{};
-        s.variant = it.decorrelation_mode;
-        s.split_alpha = it.split_alpha_endpoints != 0;
-        s.split_colour = it.split_colour_endpoints != 0;
-        s = dxtlt::effective_settings((dxtlt::Format)it.format, s);
         const uint64_t blocks = it.len / item_block_bytes(it.format);
-        const hipError_t e = dxtlt::launch_transform((dxtlt::Format)it.format, it.inverse != 0, s, it.d_input, it.d_output,
-                                                     dxtlt::Range{blocks, 0, blocks}, user);
-        if (e != hipSuccess)
-            return fail(kDevice, "batch item launch", e);
+        HIP_TRY(dxtlt::launch_transform((dxtlt::Format)it.format, it.inverse != 0, item_settings(it), it.d_input, it.d_output,
+                                        dxtlt::Range{blocks, 0, blocks}, user),
+                "batch item launch");
     }
-    // pixel items (formats 8, 9): one launch each, behind the rest
-    for (size_t i = 0; i < count; ++i)
-        if (is_pixel_format(items[i].format) && items[i].len != 0)
-            if (int32_t rc = launch_pixel_item(items[i], user); rc != kOk)
-                return rc;
+    for (size_t i : plan.pixels)
+        if (int32_t rc = launch_pixel_item(items[i], user); rc != kOk)
+            return rc;
     return kOk;
 }
+
+void* address(uint64_t a) { return reinterpret_cast<void*>(static_cast<uintptr_t>(a)); }
 
 }  // namespace
 
@@ -329,11 +356,12 @@ extern "C" int32_t dxtlt_transform_batch_device(const DxtltBatchItem* items, siz
     return batch_device(items, count, hip_stream, false);
 }
 
-// Test hook (no device needed, nothing is dereferenced): plans buffers of one format, direction and settings exactly as
-// dxtlt_transform_batch_device does for one launch -- plan_batch_entry per buffer, then build_batch_index -- and hands back the
-// planned entries and the workgroup -> entry index, so that the host logic can be checked on a machine without a GPU
-// (tests/test_batch_plan.py).  Returns the launch's workgroups; 0xFFFFFFFF when `index_capacity` is too small or a buffer is
-// one the batch kernel does not take (dxtlt_transform_batch_device launches those alone).
+// Test hooks (no device needed, nothing is dereferenced; include/dxtlt_gfx950.h): they run the call's own plan_batch and
+// fill_tables, into host memory, so that the host logic which ships can be checked on a machine without a GPU
+// (tests/test_batch_plan.py, tests/test_batch_call_plan.py).
+//
+// dxtlt_debug_plan_batch: buffers of one format, direction and settings, as items of one call -- which then has one tile launch
+// at the most.  Hands back every buffer's entry and the launch's workgroup -> entry index.
 extern "C" uint32_t dxtlt_debug_plan_batch(int32_t format, int32_t inverse, int32_t variant, int32_t split_alpha, int32_t split_colour,
                                            const uint64_t* src_addresses, const uint64_t* dst_addresses, const uint64_t* blocks, size_t count,
                                            DxtltDebugPlannedEntry* entries_out, uint8_t* index_out, size_t index_capacity,
@@ -343,26 +371,30 @@ extern "C" uint32_t dxtlt_debug_plan_batch(int32_t format, int32_t inverse, int3
         *index_is_wide_out = 0;
     if (format < 1 || format > 5 || (count != 0 && (!src_addresses || !dst_addresses || !blocks || !entries_out)))
         return 0xFFFFFFFFu;
-    dxtlt::Settings s{};
-    s.variant = variant;
-    s.split_alpha = split_alpha != 0;
-    s.split_colour = split_colour != 0;
-    s = dxtlt::effective_settings((dxtlt::Format)format, s);
-    std::vector<BatchEntry> entries;
-    uint32_t total = 0;
+    std::vector<DxtltBatchItem> items(count);
     for (size_t i = 0; i < count; ++i) {
-        BatchEntry e{};
-        e.src = reinterpret_cast<const uint8_t*>(static_cast<uintptr_t>(src_addresses[i]));
-        e.dst = reinterpret_cast<uint8_t*>(static_cast<uintptr_t>(dst_addresses[i]));
-        e.blocks = blocks[i];
-        e.first_wg = total;
-        const uint32_t wgs = dxtlt::plan_batch_entry((dxtlt::Format)format, inverse != 0, s, e);
-        if (wgs == 0xFFFFFFFFu || (uint64_t)total + wgs > 0xFFFFFFull)
+        if (blocks[i] >= (uint64_t(64) << 30) / item_block_bytes((uint8_t)format))
             return 0xFFFFFFFFu;
-        if (wgs == 0)
-            e.end_wg = e.first_wg;
-        total += wgs;
+        items[i] = DxtltBatchItem{address(src_addresses[i]), address(dst_addresses[i]), blocks[i] * item_block_bytes((uint8_t)format),
+                                  (uint8_t)format, (uint8_t)(inverse != 0), (uint8_t)std::min<uint32_t>((uint32_t)variant, 255),
+                                  (uint8_t)(split_alpha != 0), (uint8_t)(split_colour != 0), {0, 0, 0}};
+    }
+    BatchPlan plan;
+    if (plan_batch(items.data(), count, false, plan) != kOk || !plan.singles.empty())
+        return 0xFFFFFFFFu;
+    static const TileLaunch none;
+    const TileLaunch& l = plan.tiles.empty() ? none : plan.tiles[0];
+    if (l.wgs != 0 && (index_out == nullptr || index_capacity < dxtlt::batch_index_bytes(l.wgs)))
+        return 0xFFFFFFFFu;
+    size_t k = 0;
+    for (size_t i = 0; i < count; ++i) {
         DxtltDebugPlannedEntry& o = entries_out[i];
+        o = DxtltDebugPlannedEntry{};
+        if (blocks[i] == 0) {   // owns no workgroup, has no entry
+            o.first_wg = o.end_wg = k < l.entries.size() ? l.entries[k].first_wg : l.wgs;
+            continue;
+        }
+        const BatchEntry& e = l.entries[k++];
         o.first_wg = e.first_wg;
         o.end_wg = e.end_wg;
         o.full_tiles = e.full_tiles;
@@ -370,17 +402,90 @@ extern "C" uint32_t dxtlt_debug_plan_batch(int32_t format, int32_t inverse, int3
         o.halo_vecs = e.halo_vecs;
         std::memcpy(o.shift, e.shift, sizeof o.shift);
         std::memcpy(o.gbase, e.gbase, sizeof o.gbase);
-        if (wgs != 0)
-            entries.push_back(e);
     }
-    if (total != 0) {
-        if (index_out == nullptr || index_capacity < dxtlt::batch_index_bytes(total))
-            return 0xFFFFFFFFu;
-        const bool wide = dxtlt::build_batch_index(entries.data(), entries.size(), total, index_out);
+    if (l.wgs != 0) {
+        std::vector<uint8_t> tables(plan.table_bytes);
+        fill_tables(plan, tables.data());
+        std::memcpy(index_out, tables.data() + plan.tiles[0].at + plan.tiles[0].entry_bytes, dxtlt::batch_index_bytes(l.wgs));
         if (index_is_wide_out)
-            *index_is_wide_out = wide ? 1 : 0;
+            *index_is_wide_out = plan.tiles[0].wide ? 1 : 0;
     }
-    return total;
+    return l.wgs;
+}
+
+// dxtlt_debug_plan_batch_call: any batch; one record per launch, in the order in which the call enqueues them
+extern "C" int32_t dxtlt_debug_plan_batch_call(const DxtltBatchItem* items, size_t count, int32_t pixels_allowed, DxtltDebugBatchLaunch* out,
+                                               size_t cap, uint64_t* table_bytes_out)
+{
+    if (table_bytes_out)
+        *table_bytes_out = 0;
+    BatchPlan plan;
+    if (plan_batch(items, count, pixels_allowed != 0, plan) != kOk)
+        return -1;
+    std::vector<uint8_t> tables(plan.table_bytes);
+    fill_tables(plan, tables.data());
+    if (table_bytes_out)
+        *table_bytes_out = plan.table_bytes;
+    size_t n = 0;
+    auto put = [&](const DxtltDebugBatchLaunch& r) {
+        if (out != nullptr && n < cap)
+            out[n] = r;
+        ++n;
+    };
+    for (int q = 0; q < 4; ++q) {
+        const GranuleLaunch& p = plan.granules[q];
+        if (p.bytes == 0)
+            continue;
+        DxtltDebugBatchLaunch r{};
+        r.kind = 0, r.format = granule_format(q), r.inverse = q & 1;
+        r.items = (uint32_t)p.items, r.entries = (uint32_t)p.entries.size(), r.tails = (uint32_t)p.tails.size(), r.workgroups = (uint32_t)p.wgs;
+        r.table_offset = p.at, r.table_bytes = p.bytes;
+        put(r);
+    }
+    for (const TileLaunch& l : plan.tiles) {
+        DxtltDebugBatchLaunch r{};
+        r.kind = 1, r.format = l.format(), r.inverse = l.inverse() ? 1 : 0, r.settings_code = l.key & 15;
+        r.items = r.entries = (uint32_t)l.entries.size(), r.workgroups = l.wgs;
+        r.uniform_wgs = l.uniform_wgs, r.strided = l.strided ? 1 : 0, r.wide = l.wide ? 1 : 0;
+        r.src_stride = l.src_stride, r.dst_stride = l.dst_stride;
+        r.table_offset = l.at, r.table_bytes = l.entry_bytes + dxtlt::batch_index_bytes(l.wgs);
+        put(r);
+    }
+    for (int kind = 2; kind <= 3; ++kind)
+        for (size_t i : kind == 2 ? plan.singles : plan.pixels) {
+            DxtltDebugBatchLaunch r{};
+            r.kind = kind, r.format = items[i].format, r.inverse = items[i].inverse ? 1 : 0;
+            r.settings_code = kind == 2 ? settings_code(item_settings(items[i])) : 0;
+            r.items = r.entries = 1, r.first_item = i;
+            put(r);
+        }
+    return (int32_t)n;
+}
+
+// the granule launch of `format` (7, 6) and direction in the same plan: its entries and its coarse index, read back from the
+// tables as staged.  Returns the coarse index's elements (those beyond `coarse_cap`, and entries beyond `entry_cap`, are not
+// written); -1 for a batch the call would refuse or a format without granules.
+extern "C" int32_t dxtlt_debug_plan_batch_granules(const DxtltBatchItem* items, size_t count, int32_t format, int32_t inverse,
+                                                   uint32_t* first_wg_out, uint64_t* main_blocks_out, size_t entry_cap, uint32_t* coarse_out,
+                                                   size_t coarse_cap)
+{
+    BatchPlan plan;
+    if (!dxtlt::granule::is_granule_format(format) || plan_batch(items, count, false, plan) != kOk)
+        return -1;
+    std::vector<uint8_t> tables(plan.table_bytes);
+    fill_tables(plan, tables.data());
+    const GranuleLaunch& p = plan.granules[(format == 7 ? 0 : 2) + (inverse != 0 ? 1 : 0)];
+    if (p.bytes == 0)
+        return 0;
+    const GranuleEntry* entries = reinterpret_cast<const GranuleEntry*>(tables.data() + p.at);
+    const uint32_t* coarse = reinterpret_cast<const uint32_t*>(tables.data() + p.at + p.entry_bytes + p.tail_bytes);
+    for (size_t k = 0; k < p.entries.size() && k < entry_cap; ++k) {
+        if (first_wg_out) first_wg_out[k] = entries[k].first_wg;
+        if (main_blocks_out) main_blocks_out[k] = entries[k].main_blocks;
+    }
+    for (size_t k = 0; k < p.coarse.size() && k < coarse_cap && coarse_out != nullptr; ++k)
+        coarse_out[k] = coarse[k];
+    return (int32_t)p.coarse.size();
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -445,8 +550,6 @@ struct PinnedArenas {
     }
 };
 thread_local PinnedArenas g_pinned;
-#define g_pinned_in(c) (pinned_in[(c) & 1])
-#define g_pinned_out(c) (pinned_out[(c) & 1])
 
 struct HostBatchShared {
     std::mutex m;
@@ -476,20 +579,9 @@ extern "C" int32_t dxtlt_transform_batch_host(const DxtltBatchItem* items, size_
         return fail(kInvalidArgument, "NULL item array with count > 0");
     uint64_t total = 0;
     for (size_t i = 0; i < count; ++i) {
-        const DxtltBatchItem& it = items[i];
-        if (it.format < 1 || it.format > 9)
-            return fail(kInvalidArgument, kHostFormatText);
-        if (it.len % item_block_bytes(it.format) != 0)
-            return fail(kInvalidLength, "batch item: len is not a multiple of the block size");
-        if (it.decorrelation_mode > 3 && dxtlt::format_has_colour(it.format))
-            return fail(kInvalidArgument, "batch item: decorrelation_mode must be 0..3");
-        if (it.len > 0 && (it.d_input == nullptr || it.d_output == nullptr))
-            return fail(kInvalidArgument, "batch item: NULL buffer with len > 0");
-        if (pixel_item_overlaps(it))
-            return fail(kInvalidArgument, "batch item: pixel input and output overlap");
-        if (it.len >= (size_t(4) << 30))
-            return fail(kInvalidArgument, "batch item of 4 GiB or more: use the single-buffer entry point");
-        total += (it.len + 255) & ~uint64_t(255);
+        if (int32_t rc = batch_item_defect(items[i], 9, true); rc != kOk)
+            return rc;
+        total += (items[i].len + 255) & ~uint64_t(255);
     }
     if (total == 0)
         return kOk;
@@ -562,6 +654,8 @@ extern "C" int32_t dxtlt_transform_batch_host(const DxtltBatchItem* items, size_
     // worker threads do not see this thread's thread_local arenas: hand them the pointers
     void* const pinned_in[2] = {g_pinned.in[0], g_pinned.in[1]};
     void* const pinned_out[2] = {g_pinned.out[0], g_pinned.out[1]};
+    auto g_pinned_in = [&](int c) { return pinned_in[c & 1]; };
+    auto g_pinned_out = [&](int c) { return pinned_out[c & 1]; };
     int dev = 0;
     (void)hipGetDevice(&dev);
     hipStream_t down = nullptr;

@@ -6,8 +6,8 @@
 // non-empty regions are cut into the single call's groups (for_each_region_group), each group one entry whose covering range is
 // planned as the single call plans it (for_each_range_launch, granule_launch.h): the main part's granules it touches go into the
 // granule launch, its tail part, if it reaches one, into the tail launch.  The call then stages every table of the batch -- region tables, granule
-// entries, tail entries, the coarse index -- in ONE slot of the batch calls' ring (table_ring.h) and uploads it on the caller's
-// stream in front of the launches, as image_batch_api.cpp does.
+// entries, tail entries, the coarse index (build_coarse_index) -- in ONE slot of the batch calls' ring (StagedTables,
+// batch_tables.h) and uploads it on the caller's stream in front of the launches, as image_batch_api.cpp does.
 #include <hip/hip_runtime_api.h>
 
 #include <cstdio>
@@ -16,11 +16,11 @@
 
 #include "../../include/dxtlt_bc7_image.h"
 #include "../../include/dxtlt_gfx950.h"
+#include "batch_tables.h"
 #include "bc7_image_batch_launch.h"
 #include "granule_launch.h"   // for_each_range_launch
 #include "host_common.h"
 #include "image_host.h"       // image_regions_defect
-#include "table_ring.h"
 
 namespace {
 
@@ -136,18 +136,16 @@ extern "C" int32_t dxtlt_untransform_decode_bc7_images_batch_device(const DxtltB
     const size_t region_bytes = plan.regions.size() * sizeof(ImageBatchRegion);
     const size_t entries_at = region_bytes, tails_at = entries_at + n_granule_entries * sizeof(ImageBatchEntry);
     const size_t coarse_at = tails_at + (size_t)plan.tail_wgs * sizeof(ImageBatchEntry);
-    const size_t n_coarse = ((size_t)plan.granule_wgs + 63) / 64;
-    const size_t table_bytes = (coarse_at + n_coarse * sizeof(uint32_t) + 15) & ~(size_t)15;
-    TableSlot* slot = nullptr;
-    hipError_t e = thread_table_ring().acquire(table_bytes, &slot);
+    const size_t table_bytes = padded(coarse_at + coarse_index_count(plan.granule_wgs) * sizeof(uint32_t), 16);
+    StagedTables tables;
+    hipError_t e = tables.acquire(table_bytes);
     if (e != hipSuccess)
         return fail(kDevice, "bc7 image batch table staging", e);
-    uint8_t* host = static_cast<uint8_t*>(slot->host);
-    const uint8_t* dev = static_cast<const uint8_t*>(slot->dev);
+    uint8_t* host = tables.host();
+    const uint8_t* dev = tables.dev();
     std::memcpy(host, plan.regions.data(), region_bytes);
     ImageBatchEntry* granule_entries = reinterpret_cast<ImageBatchEntry*>(host + entries_at);
     ImageBatchEntry* tail_entries = reinterpret_cast<ImageBatchEntry*>(host + tails_at);
-    uint32_t* coarse = reinterpret_cast<uint32_t*>(host + coarse_at);
     size_t at = 0;
     for (const PlannedEntry& pe : plan.entries) {
         const DxtltBc7ImageBatchItem& it = items[pe.item];
@@ -159,26 +157,13 @@ extern "C" int32_t dxtlt_untransform_decode_bc7_images_batch_device(const DxtltB
         if (pe.tail_index >= 0)
             tail_entries[pe.tail_index] = ImageBatchEntry{src + main_blocks * 16, regions, main_blocks, 0, 0, pe.region_count, (uint32_t)tail, 0, {0, 0}};
     }
-    // coarse[k] = the entry that owns workgroup 64 k (GranulePlan, batch_api.cpp)
-    size_t cur = 0;
-    for (size_t k = 0; k < n_coarse; ++k) {
-        while (cur + 1 < n_granule_entries && granule_entries[cur + 1].first_wg <= (uint32_t)(k * 64))
-            ++cur;
-        coarse[k] = (uint32_t)cur;
-    }
-    e = upload_table(slot, table_bytes, user);
+    build_coarse_index(granule_entries, n_granule_entries, plan.granule_wgs, reinterpret_cast<uint32_t*>(host + coarse_at));
+    e = tables.upload(user);
     if (e == hipSuccess)
         e = dxtlt::bc7::launch_image_batch(reinterpret_cast<const ImageBatchEntry*>(dev + entries_at),
                                            reinterpret_cast<const uint32_t*>(dev + coarse_at), (uint32_t)n_granule_entries, plan.granule_wgs,
                                            reinterpret_cast<const ImageBatchEntry*>(dev + tails_at), plan.tail_wgs, user);
-    // the event marks both the upload and the kernels that read the device tables
-    const hipError_t ev = hipEventRecord(slot->done, user);
-    slot->pending = ev == hipSuccess;
-    if (e != hipSuccess)
-        return fail(kDevice, "bc7 image batch table upload / launch", e);
-    if (ev != hipSuccess)
-        return fail(kDevice, "bc7 image batch event", ev);
-    return kOk;
+    return tables.finish(e, user, "bc7 image batch table upload / launch", "bc7 image batch event");
 }
 
 extern "C" int32_t dxtlt_debug_plan_bc7_image_batch(const DxtltBc7ImageBatchItem* items, size_t count, DxtltDebugBc7ImageBatchEntry* out,

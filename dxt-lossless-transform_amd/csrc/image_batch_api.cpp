@@ -6,7 +6,7 @@
 // into groups of at most sixteen, each group one entry -- the inverse transform's plan for the range from the group's first block to the end of its last region
 // (plan_image_batch_entry) and the group's region table; entries of one format and settings share a launch.  The call then
 // stages every table of the batch -- region tables, entries, workgroup indexes -- in ONE slot of the batch calls' ring
-// (table_ring.h) and uploads it on the caller's stream in front of the launches, as dxtlt_transform_batch_device does.
+// (StagedTables, batch_tables.h) and uploads it on the caller's stream in front of the launches, as dxtlt_transform_batch_device does.
 #include <hip/hip_runtime_api.h>
 
 #include <cstdio>
@@ -15,11 +15,11 @@
 
 #include "../../include/dxtlt_gfx950.h"
 #include "../../include/dxtlt_image.h"
+#include "batch_tables.h"
 #include "host_common.h"
 #include "image_batch_launch.h"
 #include "image_host.h"
 #include "image_launch.h"
-#include "table_ring.h"
 
 namespace {
 
@@ -49,14 +49,6 @@ struct ImageBatchPlan {
 };
 
 inline dxtlt::Format key_format(int key) { return (dxtlt::Format)((key >> 4) + 1); }
-inline dxtlt::Settings key_settings(int key)
-{
-    dxtlt::Settings s{};
-    s.variant = (key >> 2) & 3;
-    s.split_alpha = ((key >> 1) & 1) != 0;
-    s.split_colour = (key & 1) != 0;
-    return s;
-}
 
 int32_t fail_item(size_t i, const char* why)
 {
@@ -90,7 +82,7 @@ int32_t plan_image_batch(const DxtltImageBatchItem* items, size_t count, ImageBa
         s.split_alpha = it.split_alpha_endpoints != 0;
         s.split_colour = it.split_colour_endpoints != 0;
         s = dxtlt::effective_settings(fmt, s);
-        const int key = ((it.format - 1) << 4) | (s.variant << 2) | ((s.split_alpha ? 1 : 0) << 1) | (s.split_colour ? 1 : 0);
+        const int key = ((it.format - 1) << 4) | settings_code(s);
         const uint32_t bpp = pixel_rule(it.format).bpp;
         for (uint32_t r = 0; r < it.region_count;) {
             // the next group: up to sixteen non-empty regions from region r on
@@ -159,7 +151,17 @@ dxtlt::ImageRegionTable alone_table(const ImageBatchPlan& plan, const PlannedEnt
     return tab;
 }
 
-inline size_t padded(size_t bytes, size_t to) { return (bytes + to - 1) & ~(to - 1); }
+// The workgroup index of a launch (batch_index_bytes(l.wgs) bytes at `index`); true when it has the wide form.  `spans`: scratch,
+// the first_wg / end_wg of the launch's entries for build_batch_index
+bool build_launch_index(const ImageBatchPlan& plan, const PlannedLaunch& l, std::vector<dxtlt::BatchEntry>& spans, uint8_t* index)
+{
+    spans.assign(l.entries.size(), dxtlt::BatchEntry{});
+    for (size_t j = 0; j < l.entries.size(); ++j) {
+        spans[j].first_wg = plan.entries[l.entries[j]].entry.first_wg;
+        spans[j].end_wg = plan.entries[l.entries[j]].entry.end_wg;
+    }
+    return dxtlt::build_batch_index(spans.data(), spans.size(), l.wgs, index);
+}
 
 }  // namespace
 
@@ -184,42 +186,34 @@ extern "C" int32_t dxtlt_untransform_decode_images_batch_device(const DxtltImage
             placed.push_back({table_bytes, entry_bytes});
             table_bytes += padded(entry_bytes + dxtlt::batch_index_bytes(l.wgs), 128);
         }
-        TableSlot* slot = nullptr;
-        hipError_t e = thread_table_ring().acquire(table_bytes, &slot);
+        StagedTables tables;
+        hipError_t e = tables.acquire(table_bytes);
         if (e != hipSuccess)
             return fail(kDevice, "image batch table staging", e);
-        uint8_t* host = static_cast<uint8_t*>(slot->host);
-        const uint8_t* dev = static_cast<const uint8_t*>(slot->dev);
+        uint8_t* host = tables.host();
+        const uint8_t* dev = tables.dev();
         std::memcpy(host, plan.regions.data(), region_bytes);
         std::vector<bool> wide(plan.launches.size());
-        std::vector<dxtlt::BatchEntry> spans;   // first_wg / end_wg of a launch's entries for build_batch_index
+        std::vector<dxtlt::BatchEntry> spans;
         for (size_t k = 0; k < plan.launches.size(); ++k) {
             const PlannedLaunch& l = plan.launches[k];
             ImageBatchEntry* out = reinterpret_cast<ImageBatchEntry*>(host + placed[k].at);
-            spans.assign(l.entries.size(), dxtlt::BatchEntry{});
             for (size_t j = 0; j < l.entries.size(); ++j) {
                 const PlannedEntry& pe = plan.entries[l.entries[j]];
                 out[j] = pe.entry;
                 out[j].regions = reinterpret_cast<const ImageBatchRegion*>(dev) + pe.regions_at;
-                spans[j].first_wg = pe.entry.first_wg;
-                spans[j].end_wg = pe.entry.end_wg;
             }
-            wide[k] = dxtlt::build_batch_index(spans.data(), spans.size(), l.wgs, host + placed[k].at + placed[k].entry_bytes);
+            wide[k] = build_launch_index(plan, l, spans, host + placed[k].at + placed[k].entry_bytes);
         }
-        e = upload_table(slot, table_bytes, user);
+        e = tables.upload(user);
         for (size_t k = 0; k < plan.launches.size() && e == hipSuccess; ++k) {
             const PlannedLaunch& l = plan.launches[k];
             const uint8_t* d = dev + placed[k].at;
-            e = dxtlt::launch_image_batch(key_format(l.key), key_settings(l.key), reinterpret_cast<const ImageBatchEntry*>(d),
+            e = dxtlt::launch_image_batch(key_format(l.key), settings_of_code(l.key & 15), reinterpret_cast<const ImageBatchEntry*>(d),
                                           d + placed[k].entry_bytes, (uint32_t)l.entries.size(), l.wgs, wide[k], user);
         }
-        // the event marks both the upload and the kernels that read the device tables
-        const hipError_t ev = hipEventRecord(slot->done, user);
-        slot->pending = ev == hipSuccess;
-        if (e != hipSuccess)
-            return fail(kDevice, "image batch table upload / launch", e);
-        if (ev != hipSuccess)
-            return fail(kDevice, "image batch event", ev);
+        if (int32_t rc = tables.finish(e, user, "image batch table upload / launch", "image batch event"); rc != kOk)
+            return rc;
     }
     // entries the batch kernel does not take: the single call's kernels, one group each, behind the batch launches
     for (const PlannedEntry& pe : plan.entries) {
@@ -245,13 +239,8 @@ extern "C" int32_t dxtlt_debug_plan_image_batch(const DxtltImageBatchItem* items
     std::vector<uint8_t> index;
     for (size_t k = 0; k < plan.launches.size(); ++k) {
         const PlannedLaunch& l = plan.launches[k];
-        spans.assign(l.entries.size(), dxtlt::BatchEntry{});
-        for (size_t j = 0; j < l.entries.size(); ++j) {
-            spans[j].first_wg = plan.entries[l.entries[j]].entry.first_wg;
-            spans[j].end_wg = plan.entries[l.entries[j]].entry.end_wg;
-        }
         index.assign(dxtlt::batch_index_bytes(l.wgs), 0);
-        wide[k] = dxtlt::build_batch_index(spans.data(), spans.size(), l.wgs, index.data()) ? 1 : 0;
+        wide[k] = build_launch_index(plan, l, spans, index.data()) ? 1 : 0;
     }
     for (size_t k = 0; k < plan.entries.size() && k < cap && out != nullptr; ++k) {
         const PlannedEntry& pe = plan.entries[k];

@@ -1,6 +1,7 @@
 // table_ring.h -- staging of the tables of the batch calls (batch_api.cpp: dxtlt_transform_batch_device; image_batch_api.cpp:
 // dxtlt_untransform_decode_images_batch_device; bc7_image_batch_api.cpp: dxtlt_untransform_decode_bc7_images_batch_device): pinned
-// host slots with device twins, one ring per calling thread.
+// host slots with device twins, one ring per calling thread.  The three calls take and give back their slot through StagedTables
+// (batch_tables.h), which alone records a slot's event and sets `pending`.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stddef.h>

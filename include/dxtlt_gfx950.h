@@ -188,8 +188,9 @@ int32_t dxtlt_transform_batch_device(const DxtltBatchItem *items, size_t count, 
  * == 1: more than 255 buffers begin inside some span of 4096 workgroups) little-endian uint16 each; base[w / 4096] +
  * delta[w / 64] (counting buffers that own workgroups) is the owner of workgroup 64 * (w / 64), and the owner of w is that
  * entry or one of the next w % 64: the first whose end_wg > w.  index_capacity: at least 4 * ceil(wgs / 4096) +
- * 2 * ceil(wgs / 64) + 15.  0xFFFFFFFF: index_capacity too small, or a buffer the batch kernel does not take (stream bases
- * off their element width: launched alone by the batch call). */
+ * 2 * ceil(wgs / 64) + 15.  0xFFFFFFFF: index_capacity too small, a buffer the batch kernel does not take (stream bases
+ * off their element width: launched alone by the batch call), or buffers the call itself refuses (a NULL address, a variant
+ * outside 0..3 for BC1..BC3, 64 GiB or 2^24 tiles).  The buffers are planned as the items of one call, by the call's planner. */
 typedef struct DxtltDebugPlannedEntry {
     uint32_t first_wg, end_wg;   /* workgroups [first_wg, end_wg): whole tiles first, then the edge tile if there is one */
     uint32_t full_tiles;
@@ -202,6 +203,40 @@ uint32_t dxtlt_debug_plan_batch(int32_t format, int32_t inverse, int32_t variant
                                 const uint64_t *src_addresses, const uint64_t *dst_addresses, const uint64_t *blocks, size_t count,
                                 DxtltDebugPlannedEntry *entries_out, uint8_t *index_out, size_t index_capacity,
                                 uint32_t *index_is_wide_out);
+/* Test hook, no device needed: what dxtlt_transform_batch_device (pixels_allowed = 0), or a chunk of dxtlt_transform_batch_host
+ * (pixels_allowed = 1: formats 8 and 9 too), would enqueue for these items -- the call's own planner, nothing is dereferenced.
+ * One record per launch, in stream order: the granule launches (BC7 forward, BC7 inverse, BC6H forward, BC6H inverse), the tile
+ * launches in ascending (format, direction, settings code), the items launched alone, the pixel items.  Returns the number of
+ * launches (records beyond `cap` are counted, not written); 0 for count == 0; -1 for a batch the call refuses.
+ * *table_bytes_out: the bytes of the ONE staged buffer that holds every launch's tables. */
+typedef struct DxtltDebugBatchLaunch {
+    int32_t kind;            /* 0 = granules of one format and direction (main parts in one kernel, tail parts in a second),
+                                1 = tile batch, 2 = one BC1..BC5 item alone (single-buffer kernels), 3 = one pixel item */
+    int32_t format;          /* 1..9 as in DxtltBatchItem */
+    int32_t inverse;
+    int32_t settings_code;   /* kinds 1, 2: variant << 2 | split_alpha << 1 | split_colour of the format's EFFECTIVE settings (what
+                                the format ignores is 0); kinds 0, 3: 0 */
+    uint32_t items;          /* batch items the launch serves */
+    uint32_t entries;        /* kind 0: items with a main part; kind 1: table entries = items */
+    uint32_t tails;          /* kind 0: items with a tail part */
+    uint32_t workgroups;     /* kind 0: granules; kind 1: tiles; kinds 2, 3: 0 (planned by the single-buffer launch) */
+    uint32_t uniform_wgs;    /* kind 1: workgroups per item when all items own the same number, else 0 */
+    uint32_t strided;        /* kind 1: 1 = a regular array (no table is read), src_stride / dst_stride bytes from item to item */
+    uint32_t wide;           /* kind 1: 1 = 16-bit deltas in the workgroup index */
+    int64_t src_stride, dst_stride;   /* kind 1: second item's pointers minus the first's (0 for one item) */
+    uint64_t table_offset;   /* kinds 0, 1: where the launch's tables start in the staged buffer (a multiple of 16) ... */
+    uint64_t table_bytes;    /* ... and their bytes: kind 0 entries, tails, coarse index; kind 1 entries, workgroup index */
+    uint64_t first_item;     /* kinds 2, 3: the item's index */
+} DxtltDebugBatchLaunch;
+int32_t dxtlt_debug_plan_batch_call(const DxtltBatchItem *items, size_t count, int32_t pixels_allowed, DxtltDebugBatchLaunch *out,
+                                    size_t cap, uint64_t *table_bytes_out);
+/* The granule launch of `format` (7 or 6) and direction of the same plan, read back from the staged tables: first_wg and main-part
+ * blocks of its entries (at most entry_cap are written) and its coarse index -- coarse[k] = the entry that owns workgroup 64 k; a
+ * workgroup w belongs to the first entry from coarse[w / 64] on with first_wg + blocks / 1024 > w.  Returns the coarse index's
+ * elements (at most coarse_cap are written), 0 when the batch has no such launch, -1 when the call refuses the batch. */
+int32_t dxtlt_debug_plan_batch_granules(const DxtltBatchItem *items, size_t count, int32_t format, int32_t inverse,
+                                        uint32_t *first_wg_out, uint64_t *main_blocks_out, size_t entry_cap, uint32_t *coarse_out,
+                                        size_t coarse_cap);
 
 /* Test hook, no device needed: what a single-buffer DEVICE call (dxtlt_{un,}transform_bcN_with_settings_device,
  * dxtlt_transform_range_device) on these addresses would enqueue -- addresses are numbers here, nothing is dereferenced.  One
