@@ -15,6 +15,7 @@
 // A pure 8 GiB fill runs at 0.86 (torch) / 0.79 (hipMemsetAsync).
 #include <hip/hip_runtime.h>
 
+#include "array_op_plan.h"
 #include "bcn_decode.h"
 #include "bcn_launch.h"
 #include "launch_grid.h"
@@ -26,10 +27,9 @@ namespace {
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
-constexpr int kDecThreads = 256;
+constexpr int kDecThreads = kArrayOpThreads;
 constexpr int kRowStride = 64 + 4;                 // u32x4 units: 64 lanes + 64 bytes of padding
 constexpr int kWaveStage = 4 * kRowStride;         // four pixel rows per wave
-constexpr uint64_t kDifferenceGrid = 256 * 16;    // workgroups of the difference count: 16 per CU
 
 __device__ __forceinline__ void store_streaming(void* p, u32x4 v) { store_streaming16(p, v); }   // streaming_store.h
 
@@ -148,22 +148,24 @@ pixel_difference_kernel(const uint8_t* __restrict__ a, const uint8_t* __restrict
         atomicAdd(count, mine);
 }
 
-inline bool aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+inline uint64_t address(const void* p) { return (uint64_t) reinterpret_cast<uintptr_t>(p); }
 
 template <int FMT>
 hipError_t decode_fmt(const void* in, void* out, uint64_t n, hipStream_t stream)
 {
+    ArrayOpPlan p;   // array_op_plan.h decides the route and the grid, nothing here does
+    if (!plan_array_op(kOpDecodeBc1 + (FMT - 1), address(in), address(out), 0, n, p))
+        return hipErrorInvalidValue;
     dim3 grid;
-    if (hipError_t e = grid_rows(n, kDecThreads, grid); e != hipSuccess)
+    if (hipError_t e = grid_of_workgroups(p.workgroups, grid); e != hipSuccess)
         return e;
-    const bool fast = aligned_to(in, FMT == 1 ? 8 : 16) && aligned_to(out, 16);
     // Workgroups per CU, capped with dynamic LDS nobody touches.  A decoder workgroup writes 16 KiB for 2-4 KiB read, and
     // on this memory system more bytes in flight per CU than it can take LOWER the rate (tools/shape_lab.hip; DESIGN.md
     // section 9): with the eight workgroups per CU the wave slots allow BC2 / BC3 decode at 0.745 of the HBM peak, with six
     // at 0.86-0.87 -- the speed of a plain fill -- (five and four: 0.845; seven: 0.82; three: 0.62).  BC1, which reads half
     // as much per block, is best left at eight (0.80; seven 0.80, six 0.76).  DXTLT_EXPERIMENT_WGS_PER_CU overrides (experiments).
     const unsigned pad_lds = lds_pad_for_wgs_per_cu(wgs_per_cu_or(FMT == 1 ? 8 : 6), kDecThreads, (unsigned)((kDecThreads / 64) * kWaveStage * 16));
-    if (fast)
+    if (p.vector)
         hipLaunchKernelGGL(decode_blocks_kernel<FMT>, grid, dim3(kDecThreads), pad_lds, stream,
                            static_cast<const uint8_t*>(in), static_cast<uint8_t*>(out), n);
     else
@@ -175,17 +177,14 @@ hipError_t decode_fmt(const void* in, void* out, uint64_t n, hipStream_t stream)
 template <int FMT>
 hipError_t difference_fmt(const void* a, const void* b, uint64_t n, unsigned long long* count, hipStream_t stream)
 {
-    // two blocks per lane and step: four loads in flight per lane.  Four blocks (eight loads) were slower on the sparse
-    // case -- BC2 0.673 against 0.697 of peak, BC3 0.626 against 0.666 -- and one block no better (0.667 / 0.652): more bytes
-    // in flight per CU than the memory system likes lower the rate (launch_grid.h)
-    constexpr int kBlocksPerLane = 2;
-    uint64_t wgs = (n + kDecThreads * kBlocksPerLane - 1) / (kDecThreads * kBlocksPerLane);
-    if (wgs > kDifferenceGrid)
-        wgs = kDifferenceGrid;
-    const uintptr_t al = FMT == 1 ? 8 : 16;
+    constexpr int kBlocksPerLane = kDifferenceBlocksPerLane;   // array_op_plan.h, with the measurements behind it
+    ArrayOpPlan p;
+    if (!plan_array_op(kOpDifferenceBc1 + (FMT - 1), address(a), address(b), 0, n, p))
+        return hipErrorInvalidValue;
+    const uint64_t wgs = p.workgroups;   // at most kDifferenceGrid: the kernel walks the rest
     const auto* pa = static_cast<const uint8_t*>(a);
     const auto* pb = static_cast<const uint8_t*>(b);
-    if (aligned_to(a, al) && aligned_to(b, al))
+    if (p.vector)
         hipLaunchKernelGGL((pixel_difference_kernel<FMT, true, kBlocksPerLane>), dim3((unsigned)wgs), dim3(kDecThreads), 0, stream, pa, pb, n, count);
     else
         hipLaunchKernelGGL((pixel_difference_kernel<FMT, false, kBlocksPerLane>), dim3((unsigned)wgs), dim3(kDecThreads), 0, stream, pa, pb, n, count);

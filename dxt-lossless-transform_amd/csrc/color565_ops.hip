@@ -7,6 +7,7 @@
 // are not 16-byte aligned and the last few colours take a one-colour (one-pair) path.  HBM bound, 2 * bytes.
 #include <hip/hip_runtime.h>
 
+#include "array_op_plan.h"
 #include "bcn_launch.h"
 #include "launch_grid.h"
 #include "streaming_store.h"
@@ -18,7 +19,7 @@ namespace {
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
-constexpr int kColThreads = 256;
+constexpr int kColThreads = kArrayOpThreads;
 
 template <int V, bool INVERSE>
 __device__ __forceinline__ uint32_t ycocg2(uint32_t v)
@@ -112,9 +113,15 @@ split_endpoints_kernel(const uint8_t* in, uint8_t* out, uint64_t num_pairs, uint
     }
 }
 
-inline bool aligned(const void* p, int a) { return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(a - 1)) == 0; }
+inline uint64_t address(const void* p) { return (uint64_t) reinterpret_cast<uintptr_t>(p); }
 
-inline hipError_t col_grid(uint64_t lanes, dim3& g) { return grid_rows(lanes, kColThreads, g); }
+// the route, the lanes and the grid of one launch: array_op_plan.h decides, nothing here does
+inline hipError_t col_plan(ArrayOp op, const void* p0, const void* p1, const void* p2, uint64_t count, ArrayOpPlan& p, dim3& g)
+{
+    if (!plan_array_op(op, address(p0), address(p1), address(p2), count, p))
+        return hipErrorInvalidValue;
+    return grid_of_workgroups(p.workgroups, g);
+}
 
 }  // namespace
 
@@ -126,14 +133,13 @@ hipError_t launch_color565_ycocg(bool inverse, const void* in, void* out, uint64
         return hipSuccess;
     if (variant == kNone)   // decorrelate_batch_ptr.rs:351-356: a copy, nothing when in place
         return in == out ? hipSuccess : hipMemcpyAsync(out, in, num_items * 2, hipMemcpyDeviceToDevice, stream);
-    const bool vec = aligned(in, 16) && aligned(out, 16);
-    const uint64_t vecs = vec ? num_items / 8 : 0, singles = num_items - 8 * vecs;
+    ArrayOpPlan p;
     dim3 g;
-    if (hipError_t e = col_grid(vecs + singles, g); e != hipSuccess)
+    if (hipError_t e = col_plan(kOpYcocg, in, out, nullptr, num_items, p, g); e != hipSuccess)
         return e;
     auto k = inverse ? ycocg_array_kernel<true> : ycocg_array_kernel<false>;
-    hipLaunchKernelGGL(k, g, dim3(kColThreads), 0, stream, static_cast<const uint8_t*>(in), static_cast<uint8_t*>(out), vecs,
-                       singles, variant);
+    hipLaunchKernelGGL(k, g, dim3(kColThreads), 0, stream, static_cast<const uint8_t*>(in), static_cast<uint8_t*>(out),
+                       p.vector_lanes, p.single_lanes, variant);
     return hipGetLastError();
 }
 
@@ -145,13 +151,12 @@ hipError_t launch_color565_recorrelate_split(const void* src0, const void* src1,
     if (num_items == 0)
         return hipSuccess;
     const uint64_t pairs = num_items / 2;
-    const bool vec = aligned(src0, 8) && aligned(src1, 8) && aligned(dst, 16);
-    const uint64_t vecs = vec ? pairs / 4 : 0, singles = pairs - 4 * vecs;
+    ArrayOpPlan p;
     dim3 g;
-    if (hipError_t e = col_grid(vecs + singles, g); e != hipSuccess)
+    if (hipError_t e = col_plan(kOpRecorrelateSplit, src0, src1, dst, pairs, p, g); e != hipSuccess)
         return e;
     hipLaunchKernelGGL(recorrelate_split_kernel, g, dim3(kColThreads), 0, stream, static_cast<const uint8_t*>(src0),
-                       static_cast<const uint8_t*>(src1), static_cast<uint8_t*>(dst), vecs, singles, variant);
+                       static_cast<const uint8_t*>(src1), static_cast<uint8_t*>(dst), p.vector_lanes, p.single_lanes, variant);
     return hipGetLastError();
 }
 
@@ -162,14 +167,12 @@ hipError_t launch_split_565_color_endpoints(const void* in, void* out, uint64_t 
     if (len_bytes == 0)
         return hipSuccess;
     const uint64_t pairs = len_bytes / 4;
-    // both halves of the output must be 16-byte aligned for the vector path: out and out + 2 * pairs
-    const bool vec = aligned(in, 16) && aligned(out, 16) && (pairs % 8 == 0);
-    const uint64_t vecs = vec ? pairs / 8 : 0, singles = pairs - 8 * vecs;
+    ArrayOpPlan p;
     dim3 g;
-    if (hipError_t e = col_grid(vecs + singles, g); e != hipSuccess)
+    if (hipError_t e = col_plan(kOpSplitEndpoints, in, out, nullptr, pairs, p, g); e != hipSuccess)
         return e;
     hipLaunchKernelGGL(split_endpoints_kernel, g, dim3(kColThreads), 0, stream, static_cast<const uint8_t*>(in),
-                       static_cast<uint8_t*>(out), pairs, vecs, singles);
+                       static_cast<uint8_t*>(out), pairs, p.vector_lanes, p.single_lanes);
     return hipGetLastError();
 }
 

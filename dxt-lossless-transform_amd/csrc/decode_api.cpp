@@ -5,6 +5,7 @@
 
 #include "../../include/dxtlt_decode.h"
 #include "../../include/dxtlt_gfx950.h"
+#include "array_op_plan.h"   // the plan behind dxtlt_debug_plan_array_op, the two slice sizes
 #include "bcn_launch.h"
 #include "host_common.h"
 #include "image_host.h"   // check_decode
@@ -16,8 +17,6 @@ using dxtlt_host::kInvalidLength;
 using dxtlt_host::kOk;
 
 namespace {
-
-constexpr size_t kSliceBlocks = size_t(4) << 20;   // 256 MiB of pixels per slice
 
 inline size_t block_bytes(int fmt) { return fmt == 1 ? 8 : 16; }
 
@@ -42,7 +41,7 @@ int32_t decode_host(int fmt, const uint8_t* in, size_t len, uint8_t* out, size_t
     const size_t bs = block_bytes(fmt), n = len / bs;
     if (n == 0)
         return kOk;
-    const size_t slice = n < kSliceBlocks ? n : kSliceBlocks;
+    const size_t slice = n < dxtlt::kDecodeSliceBlocks ? n : dxtlt::kDecodeSliceBlocks;
     void *d_in = nullptr, *d_out = nullptr;
     hipStream_t st = nullptr;
     if (int32_t rc = dxtlt_host::acquire_staging(slice * DXTLT_DECODED_BLOCK_BYTES, &d_in, &d_out, &st); rc != kOk)
@@ -108,7 +107,7 @@ int32_t dxtlt_count_pixel_differences(int32_t fmt, const uint8_t* a, const uint8
     *out_count = 0;
     if (len == 0)
         return kOk;
-    const size_t slice = len < (size_t(256) << 20) ? len : (size_t(256) << 20);   // a multiple of both block sizes
+    const size_t slice = len < dxtlt::kDifferenceSliceBytes ? len : dxtlt::kDifferenceSliceBytes;
     const size_t padded = (slice + 255) & ~size_t(255);
     void *d_a = nullptr, *d_b = nullptr;
     hipStream_t st = nullptr;
@@ -128,6 +127,23 @@ int32_t dxtlt_count_pixel_differences(int32_t fmt, const uint8_t* a, const uint8
     }
     *out_count = total;
     return kOk;
+}
+
+int32_t dxtlt_debug_plan_array_op(int32_t op, uint64_t addr0, uint64_t addr1, uint64_t addr2, uint64_t count, DxtltDebugArrayOpPlan* out)
+{
+    dxtlt::ArrayOpPlan p;
+    if (out == nullptr || !dxtlt::plan_array_op(op, addr0, addr1, addr2, count, p))
+        return -1;
+    *out = DxtltDebugArrayOpPlan{p.vector, p.threads, p.vector_lanes, p.single_lanes, p.workgroups, p.steps};
+    return 0;
+}
+
+void dxtlt_debug_array_op_slices(uint64_t* decode_slice_blocks, uint64_t* difference_slice_bytes)
+{
+    if (decode_slice_blocks != nullptr)
+        *decode_slice_blocks = dxtlt::kDecodeSliceBlocks;
+    if (difference_slice_bytes != nullptr)
+        *difference_slice_bytes = dxtlt::kDifferenceSliceBytes;
 }
 
 }  // extern "C"

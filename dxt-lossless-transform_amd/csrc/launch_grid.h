@@ -14,10 +14,9 @@ namespace dxtlt {
 
 constexpr uint64_t kGridRow = 1ull << 20;   // workgroups along x (x 1024 threads still fits 32 bits)
 
-// grid for `lanes` lanes in workgroups of `threads`
-inline hipError_t grid_rows(uint64_t lanes, unsigned threads, dim3& grid)
+// grid of `wgs` workgroups
+inline hipError_t grid_of_workgroups(uint64_t wgs, dim3& grid)
 {
-    const uint64_t wgs = (lanes + threads - 1) / threads;
     if (wgs <= kGridRow) {
         grid = dim3((unsigned)wgs, 1, 1);
         return hipSuccess;
@@ -27,6 +26,12 @@ inline hipError_t grid_rows(uint64_t lanes, unsigned threads, dim3& grid)
         return hipErrorInvalidValue;   // 2^36 workgroups
     grid = dim3((unsigned)kGridRow, (unsigned)rows, 1);
     return hipSuccess;
+}
+
+// grid for `lanes` lanes in workgroups of `threads`
+inline hipError_t grid_rows(uint64_t lanes, unsigned threads, dim3& grid)
+{
+    return grid_of_workgroups((lanes + threads - 1) / threads, grid);
 }
 
 // Dynamic LDS (touched by nobody) that caps a kernel of `threads` lanes and `static_lds` bytes of its own at

@@ -4,8 +4,12 @@ recorrelate_ycocg_r_ptr_split (decorrelate_batch_split_ptr.rs:324) and split_col
 (split_565_color_endpoints/mod.rs:110).
 
 CPU: argument validation needs no device.  GPU (-m gpu): all 65 536 colours x 3 variants against the oracle's scalar
-formulas and SURVEY.md section 8(c)'s hand-derived vectors, the reference's 3-pair split vector, in place, misaligned
-pointers and ragged counts, through the C ABI (host and device entry points)."""
+formulas and SURVEY.md section 8(c)'s hand-derived vectors, the reference's 3-pair split vector, in place, a few misaligned
+pointers and ragged counts, through the C ABI (host and device entry points) and the Python layer.
+
+The sweep of these kernels is tests/test_array_ops_sweep_gpu.py: every pointer residue pair (triple) mod 16 of the three
+operations, every count around the vector / single-lane and workgroup boundaries, every colour against chosen partners in the
+other half of its dword, each case's route proved without a device in tests/test_array_ops_cases.py."""
 import numpy as np
 import pytest
 

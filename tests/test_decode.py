@@ -4,7 +4,12 @@
 
 CPU: the oracle replays the reference's decoder unit vectors (so this row is PINNED); the device header
 csrc/bcn_decode.h built for the host equals the oracle on structured and random blocks; its small-divisor tricks are
-checked exhaustively.  GPU (-m gpu): every entry point through the C ABI against the oracle."""
+checked exhaustively.  GPU (-m gpu): every entry point through the C ABI against the oracle.
+
+The sweep of these kernels is tests/test_array_ops_sweep_gpu.py: decode_blocks at every (input, output) offset 0..16 and every
+count around a wave and a workgroup; count_pixel_differences at every length 1..1061 with the last block differing and not,
+across two passes of its capped grid with an exact expected count for every format and both load forms, and both host calls
+past their first slice.  tests/test_array_ops_cases.py proves each case's route without a device."""
 import ctypes
 import os
 import subprocess
