@@ -1,6 +1,6 @@
 // batch_tables.h -- what the batch calls that stage tables share (host only): the settings code of a launch, the coarse index of
 // a granule launch, and StagedTables, the one owner of the ring's slot protocol (table_ring.h).  Users: batch_api.cpp,
-// image_batch_api.cpp, bc7_image_batch_api.cpp.
+// image_batch_api.cpp, granule_image_batch_api.h (the BC7 and BC6H batch image calls).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

@@ -1,14 +1,13 @@
-// bc7_image_batch_launch.h -- the tables of the BC7 batch image call (bc7_image_batch_kernels.hip; include/dxtlt_bc7_image.h,
-// dxtlt_untransform_decode_bc7_images_batch_device; docs/IMAGE_DECODE.md, "Many BC7 buffers in one call") and its launch
-// interface for bc7_image_batch_api.cpp.  The entry and the launch limit are granule_image_batch_launch.h's, which BC6H shares;
-// here they keep their BC7 names.  Host and device code.
+// bc6h_image_batch_launch.h -- the launch interface of the BC6H batch image call (bc6h_image_batch_kernels.hip;
+// include/dxtlt_bc6h_image.h, dxtlt_untransform_decode_bc6h_images_batch_device; docs/IMAGE_DECODE.md, "Many BC6H buffers in one
+// call") for bc6h_image_batch_api.cpp.  The tables are granule_image_batch_launch.h's, which BC7 shares.  Host and device code.
 #pragma once
 #include "granule_image_batch_launch.h"
 
 namespace dxtlt {
-namespace bc7 {
+namespace bc6h {
 
-using ImageBatchEntry = granule::ImageBatchEntry;
+using granule::ImageBatchEntry;
 using granule::kMaxBatchWorkgroups;
 
 // d_entries: n_entries granule entries, granule_wgs workgroups in all; d_coarse[k] = the entry that owns workgroup 64 k;
@@ -16,5 +15,5 @@ using granule::kMaxBatchWorkgroups;
 hipError_t launch_image_batch(const ImageBatchEntry* d_entries, const uint32_t* d_coarse, uint32_t n_entries, uint32_t granule_wgs,
                               const ImageBatchEntry* d_tails, uint32_t n_tails, hipStream_t stream);
 
-}  // namespace bc7
+}  // namespace bc6h
 }  // namespace dxtlt

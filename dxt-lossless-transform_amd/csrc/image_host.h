@@ -1,6 +1,6 @@
 // image_host.h -- the host side of the image-decode entry points, stated once for every family: image_api.cpp (BC1 - BC3 ->
-// RGBA8888, BC4 / BC5 -> R8 / RG8), granule_image_api.h (BC7, BC6H) and the two batch calls (image_batch_api.cpp,
-// bc7_image_batch_api.cpp).  A family is a PixelRule; an entry point keeps the checks that are its own (format, decorrelation
+// RGBA8888, BC4 / BC5 -> R8 / RG8), granule_image_api.h (BC7, BC6H) and the batch calls (image_batch_api.cpp,
+// granule_image_batch_api.h).  A family is a PixelRule; an entry point keeps the checks that are its own (format, decorrelation
 // mode) and a lambda that names its launcher.  The order of the checks is the documented one (docs/IMAGE_DECODE.md, the public
 // headers).  The launch plan the two granule formats' debug calls report is here too.  Not installed.
 #pragma once

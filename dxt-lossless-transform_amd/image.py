@@ -19,8 +19,8 @@ region is ``(first_block, width, height)``, and ``mip_chain`` lists the regions 
 ``untransform_decode_bc7_images`` and ``decode_bc7_images`` are the same two calls for BC7 (no ``fmt``, no settings),
 ``untransform_decode_bc6h_images`` and ``decode_bc6h_images`` for BC6H (RGBA16F, the default pitch ``8 * width``).
 ``untransform_decode_images_batch`` does the same for MANY transformed device buffers in one call: one launch per (format,
-settings) present in the batch, whatever the number of buffers; ``untransform_decode_bc7_images_batch`` is that call for BC7:
-at most two launches, whatever the number of buffers."""
+settings) present in the batch, whatever the number of buffers; ``untransform_decode_bc7_images_batch`` and
+``untransform_decode_bc6h_images_batch`` are that call for BC7 and BC6H: at most two launches, whatever the number of buffers."""
 from __future__ import annotations
 
 import ctypes as C
@@ -51,6 +51,10 @@ class ImageBatchItem(C.Structure):   # DxtltImageBatchItem, include/dxtlt_image.
 class Bc7ImageBatchItem(C.Structure):   # DxtltBc7ImageBatchItem, include/dxtlt_bc7_image.h
     _fields_ = [("d_transformed", C.c_void_p), ("total_blocks", C.c_uint64), ("regions", C.c_void_p), ("region_count", C.c_uint32),
                 ("reserved", C.c_uint32)]
+
+
+class Bc6hImageBatchItem(C.Structure):   # DxtltBc6hImageBatchItem, include/dxtlt_bc6h_image.h
+    _fields_ = list(Bc7ImageBatchItem._fields_)
 
 
 class ImageRegion(C.Structure):   # DxtltImageRegion, include/dxtlt_image.h
@@ -90,8 +94,10 @@ def _l():
         l.dxtlt_untransform_decode_bc6h_images_device.argtypes = [vp, u64, rp, C.c_size_t, vp]
         l.dxtlt_decode_bc6h_images_device.argtypes = [vp, u64, rp, C.c_size_t, vp]
         l.dxtlt_untransform_decode_bc6h_images.argtypes = [vp, C.c_size_t, rp, C.c_size_t]
+        l.dxtlt_untransform_decode_bc6h_images_batch_device.argtypes = [C.POINTER(Bc6hImageBatchItem), C.c_size_t, vp]
         for f in (l.dxtlt_decode_bc6h_image_device, l.dxtlt_untransform_decode_bc6h_image_device, l.dxtlt_untransform_decode_bc6h_image,
-                  l.dxtlt_untransform_decode_bc6h_images_device, l.dxtlt_decode_bc6h_images_device, l.dxtlt_untransform_decode_bc6h_images):
+                  l.dxtlt_untransform_decode_bc6h_images_device, l.dxtlt_decode_bc6h_images_device, l.dxtlt_untransform_decode_bc6h_images,
+                  l.dxtlt_untransform_decode_bc6h_images_batch_device):
             f.restype = i32
         for f in (l.dxtlt_decode_bc7_image_device, l.dxtlt_untransform_decode_bc7_image_device, l.dxtlt_untransform_decode_bc7_image,
                   l.dxtlt_untransform_decode_bc7_images_device, l.dxtlt_decode_bc7_images_device, l.dxtlt_untransform_decode_bc7_images,
@@ -476,6 +482,36 @@ def untransform_decode_images_batch(items):
     return results
 
 
+def _untransform_decode_granule_images_batch(fmt, item_type, entry, items):
+    """``untransform_decode_bc7_images_batch`` / ``untransform_decode_bc6h_images_batch``: ``fmt`` is ``"bc7"`` / ``"bc6h"``"""
+    import torch
+
+    items = list(items)
+    table, keep, results, device = (item_type * max(1, len(items)))(), [], [], None
+    for k, item in enumerate(items):
+        transformed, regions = item[0], item[1]
+        kw = dict(item[2]) if len(item) > 2 and item[2] is not None else {}
+        src, total_blocks = _whole_buffer(fmt, transformed, kw.pop("total_blocks", None))
+        if src.device is None:
+            raise TypeError(f"untransform_decode_{fmt}_images_batch takes device tensors (the library has no host-pointer form of it)")
+        if device is None:
+            device = src.device
+        if src.device != device:
+            raise TypeError("all buffers of a batch must be tensors on one device")
+        outs, regions_c, count, dsts = _region_table(fmt, src, regions, kw.pop("outs", None), kw.pop("pitches", None))
+        if kw:
+            raise TypeError(f"unknown options of batch item {k}: {sorted(kw)}")
+        table[k] = item_type(src.ptr, total_blocks, C.cast(regions_c, C.c_void_p), count, 0)
+        keep.append((src, regions_c, dsts))
+        results.append(outs)
+    if not items:
+        return results
+    with torch.cuda.device(device):
+        _check(getattr(_l(), entry)(table, len(items), torch.cuda.current_stream(device).cuda_stream))
+    del keep
+    return results
+
+
 def untransform_decode_bc7_images_batch(items):
     """The images of many BC7 transformed buffers in ONE call (include/dxtlt_bc7_image.h): at most two launches, whatever the
     number of buffers.
@@ -484,29 +520,14 @@ def untransform_decode_bc7_images_batch(items):
     ``pitches`` as ``untransform_decode_bc7_images`` takes them.  Every ``transformed`` is a CUDA ``torch.uint8`` tensor, all on
     one device; the call is enqueued on torch's current stream of that device.  Returns one list of outputs per item, as
     ``untransform_decode_bc7_images`` returns them.  Items may differ in size and region layout; the images must not overlap."""
-    import torch
+    return _untransform_decode_granule_images_batch("bc7", Bc7ImageBatchItem, "dxtlt_untransform_decode_bc7_images_batch_device", items)
 
-    items = list(items)
-    table, keep, results, device = (Bc7ImageBatchItem * max(1, len(items)))(), [], [], None
-    for k, item in enumerate(items):
-        transformed, regions = item[0], item[1]
-        kw = dict(item[2]) if len(item) > 2 and item[2] is not None else {}
-        src, total_blocks = _whole_buffer("bc7", transformed, kw.pop("total_blocks", None))
-        if src.device is None:
-            raise TypeError("untransform_decode_bc7_images_batch takes device tensors (the library has no host-pointer form of it)")
-        if device is None:
-            device = src.device
-        if src.device != device:
-            raise TypeError("all buffers of a batch must be tensors on one device")
-        outs, regions_c, count, dsts = _region_table("bc7", src, regions, kw.pop("outs", None), kw.pop("pitches", None))
-        if kw:
-            raise TypeError(f"unknown options of batch item {k}: {sorted(kw)}")
-        table[k] = Bc7ImageBatchItem(src.ptr, total_blocks, C.cast(regions_c, C.c_void_p), count, 0)
-        keep.append((src, regions_c, dsts))
-        results.append(outs)
-    if not items:
-        return results
-    with torch.cuda.device(device):
-        _check(_l().dxtlt_untransform_decode_bc7_images_batch_device(table, len(items), torch.cuda.current_stream(device).cuda_stream))
-    del keep
-    return results
+
+def untransform_decode_bc6h_images_batch(items):
+    """The images of many BC6H transformed buffers in ONE call (include/dxtlt_bc6h_image.h): at most two launches, whatever the
+    number of buffers.
+
+    Items, options, conventions and errors are those of ``untransform_decode_bc7_images_batch``; the buffers are the ones
+    ``transform_bc6h`` made, the outputs ``uint8`` tensors of RGBA16F pixels, the default pitch ``8 * width``, as
+    ``untransform_decode_bc6h_images`` returns them."""
+    return _untransform_decode_granule_images_batch("bc6h", Bc6hImageBatchItem, "dxtlt_untransform_decode_bc6h_images_batch_device", items)

@@ -921,6 +921,12 @@ inline void untransform_decode_bc6h_images(const uint8_t* transformed, size_t le
 {
     detail::check_device(dxtlt_untransform_decode_bc6h_images(transformed, len, regions, region_count));
 }
+// ADDITIVE: the images of many BC6H transformed buffers in one call, at most two launches (dxtlt_bc6h_image.h, "many BC6H
+// transformed buffers in one call")
+inline void untransform_decode_bc6h_images_batch_device(const DxtltBc6hImageBatchItem* items, size_t count, void* hip_stream)
+{
+    detail::check_device(dxtlt_untransform_decode_bc6h_images_batch_device(items, count, hip_stream));
+}
 
 }  // namespace api
 }  // namespace dxt_lossless_transform

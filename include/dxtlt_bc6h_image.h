@@ -46,7 +46,23 @@
  *             decoded and dropped.  The block-array call is one launch per group.
  *   device    the *_device calls enqueue on `hip_stream` only, allocate nothing, copy nothing to the device but kernel
  *             arguments and do not synchronise: they can be captured into a HIP graph, the table frozen at capture.
- * There is no call over many BC6H buffers yet.
+ *
+ * The images of MANY BC6H transformed buffers in one call (docs/IMAGE_DECODE.md, "Many BC6H buffers in one call"):
+ * dxtlt_untransform_decode_bc6h_images_batch_device takes one DxtltBc6hImageBatchItem per buffer and writes, for every item,
+ * exactly the bytes dxtlt_untransform_decode_bc6h_images_device writes for that item alone.  Items may differ in size, alignment
+ * and region layout, and two items may name the same buffer; the images of a batch must not overlap (not checked).
+ *   checks    the whole batch before anything is enqueued -- it goes out whole or not at all: count == 0 is DXTLT_OK; a NULL
+ *             `items` with count > 0 is DXTLT_E_INVALID_ARGUMENT; then the items in list order, each with the checks of
+ *             dxtlt_untransform_decode_bc6h_images_device in their order.  The first failure is the answer and
+ *             dxtlt_last_error() names the item ("bc6h image batch item 7: ...").  An item without a non-empty region is
+ *             skipped, its buffer pointer unchecked.  A batch that needs more than 16777215 granules (of 1024 blocks) or more
+ *             than 16777215 tail parts is DXTLT_E_INVALID_ARGUMENT.
+ *   launches  every group of at most DXTLT_IMAGE_REGIONS_PER_LAUNCH non-empty regions of an item is one entry, covered as the
+ *             single call covers it; all entries' granules go out in ONE launch and all their tail parts in a second one: at
+ *             most two launches, whatever the number of items.
+ *   device    asynchronous on `hip_stream`, ordered like a single call.  The call stages its tables in pinned memory of the
+ *             calling thread (dxtlt_release_thread_resources frees it) and uploads them on the stream in front of the
+ *             launches; capture into a HIP graph is not promised.
  *
  * The RGBA image calls of dxtlt_image.h, their region and batch calls and the BC7 calls of dxtlt_bc7_image.h do not take BC6H.
  */
@@ -102,6 +118,36 @@ typedef struct DxtltBc6hImagesLaunch {
 
 int32_t dxtlt_debug_plan_bc6h_images(uint64_t total_blocks, const DxtltImageRegion *regions, size_t region_count,
                                      DxtltBc6hImagesLaunch *out, size_t cap);
+
+/* ---- many buffers in one call ------------------------------------------------------------------------------ */
+typedef struct DxtltBc6hImageBatchItem {
+    const void *d_transformed;        /* byte 0 of the item's WHOLE device buffer made by dxtlt_transform_bc6h, any alignment */
+    uint64_t total_blocks;
+    const DxtltImageRegion *regions;  /* host array; pixels = device pointers; the rules of the *_bc6h_images calls */
+    uint32_t region_count;
+    uint32_t reserved;                /* 0 */
+} DxtltBc6hImageBatchItem;
+
+int32_t dxtlt_untransform_decode_bc6h_images_batch_device(const DxtltBc6hImageBatchItem *items, size_t count, void *hip_stream);
+
+/* Test hook, no device needed: the entries the batch call would stage, in list order -- the records of
+ * dxtlt_debug_plan_bc7_image_batch (dxtlt_bc7_image.h), field for field.  Addresses are numbers; nothing is dereferenced but
+ * `items` and their `regions`.  Records beyond `cap` are counted, not written.  Returns the number of entries, or -1 for a
+ * batch the call would refuse. */
+typedef struct DxtltDebugBc6hImageBatchEntry {
+    uint32_t item;           /* index of the entry's item */
+    uint32_t first_region;   /* index in the item's list of the group's first non-empty region */
+    uint32_t region_count;   /* non-empty regions of the group */
+    int32_t tail_index;      /* the entry's workgroup in the tail launch, or -1 */
+    uint64_t first_granule;  /* of the buffer's main part (0 when granule_count is 0) */
+    uint32_t granule_count;  /* the entry's workgroups in the granule launch, 0 if none */
+    uint32_t first_wg;       /* its first workgroup there: the workgroups of all entries before it */
+    uint32_t granule_wgs;    /* workgroups of the whole granule launch (0: not launched) */
+    uint32_t tail_wgs;       /* workgroups of the whole tail launch (0: not launched) */
+} DxtltDebugBc6hImageBatchEntry;
+
+int32_t dxtlt_debug_plan_bc6h_image_batch(const DxtltBc6hImageBatchItem *items, size_t count, DxtltDebugBc6hImageBatchEntry *out,
+                                          size_t cap);
 
 #ifdef __cplusplus
 }
