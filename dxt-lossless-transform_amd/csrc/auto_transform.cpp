@@ -520,6 +520,14 @@ void dxtlt_host::auto_begin_device_call()
     t_section_bytes_downloaded = t_estimator_callbacks = 0;
 }
 
+bool dxtlt_host::auto_arena_disabled() { return t_no_arena; }
+
+void dxtlt_host::auto_count_estimation(uint64_t section_bytes_downloaded, uint64_t estimator_callbacks)
+{
+    t_section_bytes_downloaded += section_bytes_downloaded;
+    t_estimator_callbacks += estimator_callbacks;
+}
+
 // Where the sections of the callback flow's candidates come from, and with them how the winner reaches the output.
 enum class Source {
     kFused,        // BC1-3: every distinct section in the arena from one read (launch_auto_candidates); the winner is transformed once

@@ -1,6 +1,10 @@
 // estimate_api.cpp -- C ABI of the built-in size estimator (include/dxtlt_estimator.h) over estimate_kernels.hip, and the
-// per-thread counter block the auto transforms read their estimates back through (auto_transform.cpp).
+// per-thread counter block the auto transforms read their estimates back through (auto_transform.cpp).  The entropy estimator
+// (include/dxtlt_entropy_estimator.h, entropy_kernels.hip) has the same four entry points over the same counters, upload buffer
+// and stream.
+#include "../../include/dxtlt_entropy_estimator.h"
 #include "../../include/dxtlt_estimator.h"
+#include "entropy_launch.h"
 #include "estimate_launch.h"
 #include "host_common.h"
 
@@ -114,6 +118,17 @@ uint32_t builtin_estimate_compressed_size(void*, const uint8_t* input_ptr, size_
 
 const DltSizeEstimator kBuiltin = {nullptr, builtin_max_compressed_size, builtin_estimate_compressed_size};
 
+uint32_t entropy_estimate_compressed_size(void*, const uint8_t* input_ptr, size_t len_bytes, uint8_t*, size_t, size_t* out_size)
+{
+    uint64_t v = 0;
+    const int32_t rc = dxtlt_estimate_entropy_size(input_ptr, len_bytes, &v);
+    if (rc == DXTLT_OK && out_size)
+        *out_size = static_cast<size_t>(v);
+    return static_cast<uint32_t>(rc);
+}
+
+const DltSizeEstimator kBuiltinEntropy = {nullptr, builtin_max_compressed_size, entropy_estimate_compressed_size};
+
 }  // namespace
 
 void dxtlt_host::release_estimate_thread_counters()
@@ -128,6 +143,8 @@ bool dxtlt_host::is_builtin_estimator(const DltSizeEstimator* est)
            est->EstimateCompressedSize == builtin_estimate_compressed_size;
 }
 
+bool dxtlt_host::is_builtin_entropy_estimator(const DltSizeEstimator* est) { return est == &kBuiltinEntropy; }
+
 int32_t dxtlt_host::estimate_enqueue(const dxtlt::EstimateSection* sections, size_t count, hipStream_t st, size_t first_counter)
 {
     if (first_counter + count > kMaxCounters)
@@ -138,6 +155,19 @@ int32_t dxtlt_host::estimate_enqueue(const dxtlt::EstimateSection* sections, siz
     if (e == hipErrorInvalidValue)
         return fail(kInvalidArgument, "a section of more than 2^31 - 1 windows");
     HIP_TRY(e, "estimator launch");
+    return kOk;
+}
+
+int32_t dxtlt_host::entropy_enqueue(const dxtlt::EstimateSection* sections, size_t count, hipStream_t st, size_t first_counter)
+{
+    if (first_counter + count > kMaxCounters)
+        return fail(kInvalidArgument, "more estimates than this thread's counter block holds");
+    if (!g_counters.get())
+        return fail(kDevice, "estimator counters: allocation failed", hipErrorOutOfMemory);
+    hipError_t e = dxtlt::launch_entropy(sections, count, g_counters.d + first_counter, st);
+    if (e == hipErrorInvalidValue)
+        return fail(kInvalidArgument, "a section of more than 2^31 - 1 windows");
+    HIP_TRY(e, "entropy estimator launch");
     return kOk;
 }
 
@@ -247,6 +277,81 @@ int32_t dxtlt_estimate_size(const uint8_t* host_ptr, size_t len, uint64_t* out)
     } else {
         const dxtlt::EstimateSection s{g_upload.ptr, len};
         rc = estimate_enqueue(&s, 1, st, 0);
+        if (rc == kOk)
+            rc = estimate_read_back(1, st, out);
+    }
+    if (rc != kOk)
+        (void)hipStreamSynchronize(st);   // the upload buffer belongs to this thread's next call
+    return rc;
+}
+
+// ---- include/dxtlt_entropy_estimator.h ----------------------------------------------------------------------------------------
+uint32_t dxtlt_entropy_estimator_version(void) { return dxtlt::kEntropyEstimatorVersion; }
+
+const DltSizeEstimator* dxtlt_builtin_entropy_estimator(void) { return &kBuiltinEntropy; }
+
+uint32_t dxtlt_debug_entropy_table(uint32_t k) { return dxtlt::entropy_table_host(k); }
+
+int32_t dxtlt_estimate_entropy_sizes_device(const DxtltEstimateSection* sections, size_t count, void* hip_stream, uint64_t* d_out)
+{
+    using namespace dxtlt_host;
+    if (count == 0)
+        return kOk;
+    if (sections == nullptr || d_out == nullptr)
+        return fail(kInvalidArgument, "NULL sections / d_out with count > 0");
+    if (reinterpret_cast<uintptr_t>(d_out) % 8 != 0)
+        return fail(kInvalidArgument, "d_out is not 8-byte aligned");
+    if (int32_t rc = need_device())
+        return rc;
+    hipError_t e = dxtlt::launch_entropy(reinterpret_cast<const dxtlt::EstimateSection*>(sections), count, d_out,
+                                         static_cast<hipStream_t>(hip_stream));
+    if (e == hipErrorInvalidValue)
+        return fail(kInvalidArgument, "a section of more than 2^31 - 1 windows");
+    HIP_TRY(e, "entropy estimator launch");
+    return kOk;
+}
+
+int32_t dxtlt_estimate_entropy_size_device(const void* d_ptr, size_t len, void* hip_stream, uint64_t* out)
+{
+    using namespace dxtlt_host;
+    if (out == nullptr)
+        return fail(kInvalidArgument, "NULL out");
+    if (d_ptr == nullptr || len == 0) {   // nothing to count (docs/ESTIMATOR.md): nothing to ask a device
+        *out = 0;
+        return kOk;
+    }
+    if (int32_t rc = need_device())
+        return rc;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    if (stream_is_capturing(st))
+        return fail(kInvalidArgument,
+                    "dxtlt_estimate_entropy_size_device waits for its stream: not capturable (dxtlt_estimate_entropy_sizes_device is)");
+    const dxtlt::EstimateSection s{d_ptr, len};
+    if (int32_t rc = entropy_enqueue(&s, 1, st, 0))
+        return rc;
+    return estimate_read_back(1, st, out);
+}
+
+int32_t dxtlt_estimate_entropy_size(const uint8_t* host_ptr, size_t len, uint64_t* out)
+{
+    using namespace dxtlt_host;
+    if (out == nullptr)
+        return fail(kInvalidArgument, "NULL out");
+    if (host_ptr == nullptr || len == 0) {
+        *out = 0;
+        return kOk;
+    }
+    if (int32_t rc = need_device())
+        return rc;
+    HIP_TRY(g_upload.get(len), "estimator upload buffer / stream");
+    hipStream_t st = g_upload.stream;
+    hipError_t e = hipMemcpyAsync(g_upload.ptr, host_ptr, len, hipMemcpyHostToDevice, st);
+    int32_t rc = kOk;
+    if (e != hipSuccess) {
+        rc = fail(kDevice, "H2D copy", e);
+    } else {
+        const dxtlt::EstimateSection s{g_upload.ptr, len};
+        rc = entropy_enqueue(&s, 1, st, 0);
         if (rc == kOk)
             rc = estimate_read_back(1, st, out);
     }

@@ -18,20 +18,12 @@
 #include <cstdint>
 
 #include "estimate_launch.h"
+#include "estimate_sections.h"
 
 namespace dxtlt {
 namespace {
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kSectionsPerLaunch = 16;
-
-struct EstimateTable {
-    const uint8_t* base[kSectionsPerLaunch];
-    uint64_t len[kSectionsPerLaunch];
-    uint32_t end_wg[kSectionsPerLaunch];   // section s owns workgroups [end_wg[s - 1], end_wg[s]); unused entries: 0xFFFFFFFF
-    unsigned long long* out;               // the counter of section 0 of this launch
-};
 
 // T lanes per workgroup; W, BITS: the definition's constants.  The product's estimator is <*, kEstimatorWindow, kEstimatorBits>;
 // the other instances exist for the shape sweep of tools/estimator_bench.py (launch_estimate_shape) and define other numbers.
@@ -46,20 +38,7 @@ __global__ void __launch_bounds__(T) estimate_kernel(const EstimateTable tab)
     __shared__ uint32_t wg_matches;
 
     const uint32_t wg = blockIdx.x, tid = threadIdx.x;
-    // the section of this workgroup: the first whose end_wg is above wg (uniform: scalar compares and selects)
-    uint32_t s = 0, begin = 0;
-    const uint8_t* base = tab.base[0];
-    uint64_t len = tab.len[0];
-#pragma unroll
-    for (int k = 0; k < kSectionsPerLaunch - 1; ++k)
-        if (wg >= tab.end_wg[k]) {
-            s = k + 1;
-            begin = tab.end_wg[k];
-            base = tab.base[k + 1];
-            len = tab.len[k + 1];
-        }
-    const uint64_t off = uint64_t(wg - begin) * W;
-    const uint32_t w = len - off < W ? uint32_t(len - off) : W;
+    DXTLT_ESTIMATE_WINDOW_OF(W, tab, wg);   // s, base, off, w: the section table walk of estimate_sections.h
 
     if (base == nullptr || w < 4) {   // no gram: every byte counts
         if (tid == 0)
@@ -218,45 +197,14 @@ estimate_table_kernel(const EstimateTableEntry* __restrict__ tab, uint32_t entri
 template <uint32_t W, uint32_t BITS>
 hipError_t launch_shape(const EstimateSection* sections, size_t count, uint64_t* d_out, hipStream_t stream, int lanes)
 {
-    if (count == 0)
-        return hipSuccess;
-    for (size_t i = 0; i < count; ++i)
-        if ((sections[i].len + W - 1) / W > 0x7FFFFFFFu)   // more windows than one launch has workgroups
-            return hipErrorInvalidValue;
-    hipError_t e = hipMemsetAsync(d_out, 0, count * sizeof(uint64_t), stream);
-    for (size_t at = 0; at < count && e == hipSuccess;) {
-        EstimateTable tab;
-        for (int k = 0; k < kSectionsPerLaunch; ++k) {
-            tab.base[k] = nullptr;
-            tab.len[k] = 0;
-            tab.end_wg[k] = 0xFFFFFFFFu;
-        }
-        uint64_t wgs = 0;
-        int n = 0;
-        while (at + n < count && n < kSectionsPerLaunch) {
-            const uint64_t windows = (sections[at + n].len + W - 1) / W;
-            if (n > 0 && wgs + windows > 0x7FFFFFFFu)
-                break;   // the next launch takes it (the first section of a launch fits: checked above)
-            wgs += windows;
-            tab.base[n] = static_cast<const uint8_t*>(sections[at + n].d_ptr);
-            tab.len[n] = sections[at + n].len;
-            tab.end_wg[n] = uint32_t(wgs);
-            ++n;
-        }
-        tab.out = reinterpret_cast<unsigned long long*>(d_out + at);
-        if (wgs != 0) {
-            const dim3 grid{uint32_t(wgs)};
-            if (lanes == 256)
-                hipLaunchKernelGGL((estimate_kernel<256, W, BITS>), grid, dim3(256), 0, stream, tab);
-            else if (lanes == 512)
-                hipLaunchKernelGGL((estimate_kernel<512, W, BITS>), grid, dim3(512), 0, stream, tab);
-            else
-                hipLaunchKernelGGL((estimate_kernel<1024, W, BITS>), grid, dim3(1024), 0, stream, tab);
-            e = hipGetLastError();
-        }
-        at += n;
-    }
-    return e;
+    return launch_per_section_table<W>(sections, count, d_out, stream, [&](dim3 grid, const EstimateTable& tab) {
+        if (lanes == 256)
+            hipLaunchKernelGGL((estimate_kernel<256, W, BITS>), grid, dim3(256), 0, stream, tab);
+        else if (lanes == 512)
+            hipLaunchKernelGGL((estimate_kernel<512, W, BITS>), grid, dim3(512), 0, stream, tab);
+        else
+            hipLaunchKernelGGL((estimate_kernel<1024, W, BITS>), grid, dim3(1024), 0, stream, tab);
+    });
 }
 
 }  // namespace

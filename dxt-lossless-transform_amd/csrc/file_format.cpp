@@ -262,6 +262,7 @@ int bc45_of_header(uint32_t header, bool* split)
 // and sets reserved bits -- the layout in bits 4..3, this build's layout version in bits 11..5, the vendor tag of the BC7 words
 // above them -- that upstream's unpack refuses: such a file is rejected there, never misread.
 std::atomic<bool> g_pixels_enabled{false};
+std::atomic<bool> g_pixel_auto_enabled{false};   // dxtlt_file_formats_enable_pixel_auto: _auto chooses the setting
 constexpr uint32_t kPixelLayoutVersion = 1u;   // data bits 11..5: docs/PIXEL_FORMAT.md version
 inline uint32_t pixel_header(uint32_t code, bool decorrelate, uint32_t layout)
 {
@@ -338,15 +339,18 @@ int32_t dds_transform_common(const uint8_t* input, size_t input_len, uint8_t* ou
         return DXTLT_FF_OK;
     }
     if (const int code = dds_to_pixel_code(info.Format); code >= 0) {
-        // the settings triple read as the generic entry points read it; auto: the fixed setting (subtract-green, PLANAR_DELTA) --
-        // the estimator is never called (docs/PIXEL_FORMAT.md, "Out of scope")
-        const bool decorrelate = estimator != nullptr || dxtlt_host::pixel_decorrelate_of(mode);
-        const uint8_t layout = estimator != nullptr ? (uint8_t)DXTLT_PIXEL_LAYOUT_PLANAR_DELTA : dxtlt_host::pixel_layout_of(sa, sc);
+        // the settings triple read as the generic entry points read it; auto: the fixed setting (subtract-green, PLANAR_DELTA) and
+        // the estimator never called, unless dxtlt_file_formats_enable_pixel_auto is on: then the pixel auto transform chooses
+        // with the caller's estimator (docs/PIXEL_FORMAT.md, "The auto transform")
+        bool decorrelate = estimator != nullptr || dxtlt_host::pixel_decorrelate_of(mode);
+        uint8_t layout = estimator != nullptr ? (uint8_t)DXTLT_PIXEL_LAYOUT_PLANAR_DELTA : dxtlt_host::pixel_layout_of(sa, sc);
         const int B = pixel_code_bytes(code);
         if (length % (size_t)B != 0)
             return DXTLT_FF_INVALID_DATA_ALIGNMENT;
         std::memcpy(output, input, off);
-        const int32_t stp = dxtlt_host::pixel_host_call(B, false, input + off, output + off, length, decorrelate, layout);
+        const int32_t stp = estimator != nullptr && g_pixel_auto_enabled.load(std::memory_order_relaxed)
+                                ? dxtlt_transform_pixels_auto(input + off, output + off, length, B, estimator, &decorrelate, &layout)
+                                : dxtlt_host::pixel_host_call(B, false, input + off, output + off, length, decorrelate, layout);
         if (stp != dxtlt_host::kOk)
             return map_device_status(stp);
         if (input_len > off + length)
@@ -487,6 +491,8 @@ uint32_t dxtlt_transform_header_pack_bc45(int32_t transform_format, bool split_e
 }
 
 void dxtlt_file_formats_enable_pixels(bool enabled) { g_pixels_enabled.store(enabled, std::memory_order_relaxed); }
+
+void dxtlt_file_formats_enable_pixel_auto(bool enabled) { g_pixel_auto_enabled.store(enabled, std::memory_order_relaxed); }
 
 uint32_t dxtlt_transform_header_pack_pixels(int32_t transform_format, bool decorrelate, uint8_t layout)
 {

@@ -198,6 +198,10 @@ void* auto_thread_arena(size_t bytes);
 // dxtlt_debug_auto_last_totals nothing until the next single-buffer call.
 void auto_begin_device_call();
 void release_batch_auto_thread_buffers();   // batch_auto_api.cpp; through release_auto_thread_arena()
+// For the auto calls of other translation units (pixel_auto_api.cpp): whether dxtlt_debug_auto_use_arena(0) is in force on this
+// thread, and what a callback route adds to the figures of dxtlt_debug_auto_last_estimation.
+bool auto_arena_disabled();
+void auto_count_estimation(uint64_t section_bytes_downloaded, uint64_t estimator_callbacks);
 
 // ---- estimate_api.cpp: the built-in estimator (include/dxtlt_estimator.h) -----------------------------------------
 bool is_builtin_estimator(const DltSizeEstimator* estimator);   // by the identity of its two function pointers
@@ -207,6 +211,9 @@ bool is_builtin_estimator(const DltSizeEstimator* estimator);   // by the identi
 constexpr size_t kMaxCounters = 32;
 int32_t estimate_enqueue(const dxtlt::EstimateSection* sections, size_t count, hipStream_t stream, size_t first_counter);
 int32_t estimate_read_back(size_t count, hipStream_t stream, uint64_t* out);
+// The entropy estimator (include/dxtlt_entropy_estimator.h) into the same counters; recognised by the identity of its pointer.
+int32_t entropy_enqueue(const dxtlt::EstimateSection* sections, size_t count, hipStream_t stream, size_t first_counter);
+bool is_builtin_entropy_estimator(const DltSizeEstimator* estimator);
 bool stream_is_capturing(hipStream_t stream);
 void release_estimate_thread_counters();   // of dxtlt_release_thread_resources(), through release_auto_thread_arena()
 

@@ -17,5 +17,10 @@ enum Layout : int { kInterleaved = 0, kPlanar = 1, kPlanarDelta = 2 };
 hipError_t launch_range(int pixel_bytes, bool inverse, bool decorrelate, int layout, const void* src, void* dst, uint64_t total,
                         uint64_t first, uint64_t num, hipStream_t stream);
 
+// The fused candidate kernel of the pixel auto transform (pixel_auto_kernels.hip): from the `total` pixels at `src` (on a 16-byte
+// boundary) the forward transform with (decorrelate, PLANAR_DELTA), (decorrelate, PLANAR), (decorrelate, INTERLEAVED),
+// (plain, PLANAR_DELTA) and (plain, PLANAR), in this order, at arena + i * total * pixel_bytes.  Enqueues on `stream`.
+hipError_t launch_auto_candidates(int pixel_bytes, const void* src, void* arena, uint64_t total, hipStream_t stream);
+
 }  // namespace pixels
 }  // namespace dxtlt

@@ -68,6 +68,14 @@ def _l():
         l.dxtlt_debug_batch_auto_arena_cap.argtypes, l.dxtlt_debug_batch_auto_arena_cap.restype = [C.c_uint64], None
         l.dxtlt_debug_batch_auto_time_phases.argtypes, l.dxtlt_debug_batch_auto_time_phases.restype = [i32], None
         l.dxtlt_debug_batch_auto_last_phase_ms.argtypes, l.dxtlt_debug_batch_auto_last_phase_ms.restype = [C.POINTER(C.c_double)], None
+        # the entropy estimator (include/dxtlt_entropy_estimator.h)
+        l.dxtlt_entropy_estimator_version.argtypes, l.dxtlt_entropy_estimator_version.restype = [], C.c_uint32
+        l.dxtlt_estimate_entropy_sizes_device.argtypes = [C.POINTER(Section), sz, vp, vp]
+        l.dxtlt_estimate_entropy_sizes_device.restype = i32
+        l.dxtlt_estimate_entropy_size_device.argtypes, l.dxtlt_estimate_entropy_size_device.restype = [vp, sz, vp, u64p], i32
+        l.dxtlt_estimate_entropy_size.argtypes, l.dxtlt_estimate_entropy_size.restype = [vp, sz, u64p], i32
+        l.dxtlt_builtin_entropy_estimator.argtypes, l.dxtlt_builtin_entropy_estimator.restype = [], C.POINTER(DltSizeEstimator)
+        l.dxtlt_debug_entropy_table.argtypes, l.dxtlt_debug_entropy_table.restype = [C.c_uint32], C.c_uint32
         _own = l
     return _own
 
@@ -103,6 +111,57 @@ def estimate_size(data) -> int:
         with torch.cuda.device(src.device):
             _check(l.dxtlt_estimate_size_device(src.ptr, src.nbytes, torch.cuda.current_stream().cuda_stream, C.byref(out)))
     return int(out.value)
+
+
+def entropy_version() -> int:
+    """The version of the entropy estimator (docs/ESTIMATOR.md, "The entropy estimator, version 1")."""
+    return int(_l().dxtlt_entropy_estimator_version())
+
+
+def builtin_entropy_estimator():
+    """Pointer to the process-lifetime DltSizeEstimator of the entropy estimator; what pixels.transform_auto uses."""
+    return _l().dxtlt_builtin_entropy_estimator()
+
+
+def entropy_table(k: int) -> int:
+    """T[k] = floor(2^16 log2 k) as the kernels read it (host side, no device)."""
+    return int(_l().dxtlt_debug_entropy_table(int(k)))
+
+
+def estimate_entropy_size(data) -> int:
+    """The entropy estimate of one section: a host buffer (uploaded) or a device tensor (current stream; waits for it)."""
+    from . import _Buf
+
+    src = _Buf(data, False)
+    out = C.c_uint64()
+    l = _l()
+    if src.device is None:
+        _check(l.dxtlt_estimate_entropy_size(src.ptr, src.nbytes, C.byref(out)))
+    else:
+        import torch
+
+        with torch.cuda.device(src.device):
+            _check(l.dxtlt_estimate_entropy_size_device(src.ptr, src.nbytes, torch.cuda.current_stream().cuda_stream, C.byref(out)))
+    return int(out.value)
+
+
+def estimate_entropy_sizes(sections, out) -> None:
+    """dxtlt_estimate_entropy_sizes_device: `sections` are device tensors, `out` an int64 / uint64 device tensor of as many
+    elements.  Enqueues on the current stream and returns; nothing is synchronised."""
+    import torch
+
+    from . import _Buf
+
+    bufs = [_Buf(s, False) for s in sections]
+    if any(b.device is None for b in bufs) or not out.is_cuda:
+        raise TypeError("estimate_entropy_sizes takes device tensors")
+    if out.element_size() != 8 or out.numel() < len(bufs) or not out.is_contiguous():
+        raise TypeError("out must be a contiguous 8-byte integer tensor with one element per section")
+    table = (Section * max(1, len(bufs)))()
+    for t, b in zip(table, bufs):
+        t.d_ptr, t.len = b.ptr, b.nbytes
+    with torch.cuda.device(out.device):
+        _check(_l().dxtlt_estimate_entropy_sizes_device(table, len(bufs), torch.cuda.current_stream().cuda_stream, out.data_ptr()))
 
 
 def estimate_sizes(sections, out, shape=None) -> None:

@@ -91,6 +91,62 @@ def transform_pixels_range(inverse: bool, src, dst, total_pixels: int, first_pix
         raise DeviceError(rc, _lib.last_error())
 
 
+# the candidates of transform_auto as (decorrelate, layout), in the order they are compared; ties keep the earlier one
+AUTO_CANDIDATES = [(True, PLANAR_DELTA), (True, PLANAR), (True, INTERLEAVED), (False, PLANAR_DELTA), (False, PLANAR), (False, INTERLEAVED)]
+
+
+def transform_auto(input, output, pixel_bytes: int = 4, estimator=None):
+    """The pixel auto transform (dxtlt_transform_pixels_auto / _auto_device): the best of the six settings by the entropy
+    estimator, chosen on the device.  Host buffers or CUDA uint8 tensors (torch's current stream: waited for once, the winner's
+    transform left enqueued).  `estimator`: a pointer to a DltSizeEstimator for host buffers (default: the entropy estimator,
+    everything on the device; any other is called per candidate).  Returns (decorrelate, layout); `output` holds the data
+    transformed with them."""
+    from . import DeviceError, InvalidLength, OutputBufferTooSmall, _Buf
+    from . import estimator as _estimator
+
+    if pixel_bytes not in (3, 4):
+        raise ValueError("pixel_bytes must be 4 (RGBA8888, BGRA8888) or 3 (BGR888)")
+    src, dst = _Buf(input, False), _Buf(output, True)
+    if src.nbytes % pixel_bytes != 0:
+        raise InvalidLength(src.nbytes)
+    if dst.nbytes < src.nbytes:
+        raise OutputBufferTooSmall(src.nbytes, dst.nbytes)
+    if (src.device is None) != (dst.device is None):
+        raise TypeError("input and output must both be host buffers or both be device tensors")
+    l = _estimator._l()
+    vp, sz, i32 = C.c_void_p, C.c_size_t, C.c_int32
+    dec, lay = C.c_bool(), C.c_uint8()
+    if src.device is None:
+        est = estimator if estimator is not None else _estimator.builtin_entropy_estimator()
+        f = l.dxtlt_transform_pixels_auto
+        f.argtypes, f.restype = [vp, vp, sz, i32, vp, C.POINTER(C.c_bool), C.POINTER(C.c_uint8)], i32
+        rc = f(src.ptr, dst.ptr, src.nbytes, pixel_bytes, C.cast(est, vp), C.byref(dec), C.byref(lay))
+    else:
+        import torch
+
+        if estimator is not None:
+            raise TypeError("device tensors are ranked by the entropy estimator; an estimator of the caller's takes host buffers")
+        f = l.dxtlt_transform_pixels_auto_device
+        f.argtypes, f.restype = [vp, vp, sz, i32, vp, C.POINTER(C.c_bool), C.POINTER(C.c_uint8)], i32
+        with torch.cuda.device(src.device):
+            rc = f(src.ptr, dst.ptr, src.nbytes, pixel_bytes, torch.cuda.current_stream().cuda_stream, C.byref(dec), C.byref(lay))
+    if rc != _lib.OK:
+        raise DeviceError(rc, _lib.last_error())
+    return bool(dec.value), int(lay.value)
+
+
+def last_auto_totals():
+    """The six totals the last transform_auto of this thread compared, in the order of AUTO_CANDIDATES ([] after a call with an
+    estimator of the caller's, an empty buffer or a failed call)."""
+    from . import estimator as _estimator
+
+    l = _estimator._l()
+    l.dxtlt_debug_pixels_auto_last_totals.argtypes, l.dxtlt_debug_pixels_auto_last_totals.restype = [C.POINTER(C.c_uint64), C.c_int32], C.c_int32
+    buf = (C.c_uint64 * 6)()
+    n = l.dxtlt_debug_pixels_auto_last_totals(buf, 6)
+    return [int(v) for v in buf[:n]]
+
+
 def settings_triple(decorrelate: bool, layout: int):
     """(decorrelation_mode, split_alpha_endpoints, split_colour_endpoints) as the generic entry points -- the host batch call's
     format codes 8 / 9, dxtlt_transform_sharded, the DDS calls -- read these settings"""

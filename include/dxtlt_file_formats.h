@@ -179,6 +179,12 @@ uint32_t dxtlt_transform_header_pack_bc45(int32_t transform_format, bool split_e
  * dxtlt_dds_untransform accepts exactly the six tagged words per format code and nothing else (DXTLT_FF_CORRUPTED_EMBEDDED_DATA).
  * Only this build can read such files back. */
 void dxtlt_file_formats_enable_pixels(bool enabled);
+/* ADDITIVE, off by default (process-wide); means something only with dxtlt_file_formats_enable_pixels(true).  Off,
+ * dxtlt_dds_transform_auto treats a pixel payload as described above: the fixed setting, the estimator never called.  On, the
+ * payload goes through dxtlt_transform_pixels_auto (dxtlt_pixels.h) with the caller's estimator -- everything on the device for
+ * dxtlt_builtin_entropy_estimator() (dxtlt_entropy_estimator.h), per candidate one download and one callback for any other --
+ * and the header word records the setting it chose: one of the six tagged words, which dxtlt_dds_untransform reads back as ever. */
+void dxtlt_file_formats_enable_pixel_auto(bool enabled);
 /* The tagged header word of an RGBA8888 (5), BGRA8888 (6) or BGR888 (7) file written with this layout; 0 for any other code or
  * layout > 2. */
 uint32_t dxtlt_transform_header_pack_pixels(int32_t transform_format, bool decorrelate, uint8_t layout);
