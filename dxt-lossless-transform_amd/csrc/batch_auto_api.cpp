@@ -17,6 +17,7 @@
 #include "../../include/dxtlt_estimator.h"
 #include "../../include/dxtlt_gfx950.h"
 #include "auto_launch.h"
+#include "batch_auto_buffers.h"
 #include "bcn_launch.h"
 #include "estimate_launch.h"
 #include "host_common.h"
@@ -112,7 +113,7 @@ int32_t validate(const DxtltBatchAutoItem* items, size_t count)
 // arena slices, counters and chunks; the items are valid
 void make_plan(const DxtltBatchAutoItem* items, size_t count, Plan& plan)
 {
-    const uint64_t cap = t_arena_cap ? t_arena_cap : DXTLT_BATCH_AUTO_ARENA_CAP;
+    const uint64_t cap = batch_auto_arena_cap();
     plan.items.assign(count, PlannedItem{});
     PlannedChunk cur;
     for (size_t i = 0; i < count; ++i) {
@@ -151,72 +152,16 @@ void make_plan(const DxtltBatchAutoItem* items, size_t count, Plan& plan)
         plan.arena_bytes = std::max(plan.arena_bytes, c.arena_bytes);
 }
 
-// this thread's table staging (mapped pinned host memory and its device twin) and counters (device and pinned host): grow-only.
-// The call waits for its stream before it returns, so one of each is enough.
-struct Buffers {
-    void *table_host = nullptr, *table_mapped = nullptr, *table_dev = nullptr;
-    size_t table_cap = 0;
-    uint64_t *counters_dev = nullptr, *counters_host = nullptr;
-    size_t counters_cap = 0;
-    int device = -1;
-    ~Buffers() { release(); }
-    void release()
-    {
-        if (table_host) (void)hipHostFree(table_host);
-        if (table_dev) (void)hipFree(table_dev);
-        if (counters_dev) (void)hipFree(counters_dev);
-        if (counters_host) (void)hipHostFree(counters_host);
-        table_host = table_mapped = table_dev = nullptr;
-        counters_dev = counters_host = nullptr;
-        table_cap = counters_cap = 0;
-        device = -1;
-    }
-    hipError_t reserve(size_t table_bytes, size_t counters)
-    {
-        int dev = 0;
-        hipError_t e = hipGetDevice(&dev);
-        if (e != hipSuccess)
-            return e;
-        if (dev != device) {
-            release();
-            device = dev;
-        }
-        if (table_bytes > table_cap) {
-            if (table_host) (void)hipHostFree(table_host);
-            if (table_dev) (void)hipFree(table_dev);
-            table_host = table_mapped = table_dev = nullptr;
-            table_cap = 0;
-            const size_t want = (table_bytes + table_bytes / 2 + 4095) & ~size_t(4095);
-            e = hipHostMalloc(&table_host, want, hipHostMallocMapped);
-            if (e == hipSuccess)
-                e = hipHostGetDevicePointer(&table_mapped, table_host, 0);
-            if (e == hipSuccess)
-                e = hipMalloc(&table_dev, want);
-            if (e != hipSuccess)
-                return e;
-            table_cap = want;
-        }
-        if (counters > counters_cap) {
-            if (counters_dev) (void)hipFree(counters_dev);
-            if (counters_host) (void)hipHostFree(counters_host);
-            counters_dev = counters_host = nullptr;
-            counters_cap = 0;
-            const size_t want = counters + counters / 2 + 64;
-            e = hipMalloc(reinterpret_cast<void**>(&counters_dev), want * sizeof(uint64_t));
-            if (e == hipSuccess)
-                e = hipHostMalloc(reinterpret_cast<void**>(&counters_host), want * sizeof(uint64_t), hipHostMallocDefault);
-            if (e != hipSuccess)
-                return e;
-            counters_cap = want;
-        }
-        return hipSuccess;
-    }
-};
-thread_local Buffers g_buffers;
+// this thread's table staging and counters (batch_auto_buffers.h), shared with the batched pixel auto call
+thread_local BatchAutoBuffers g_buffers;
 
 }  // namespace
 
 void dxtlt_host::release_batch_auto_thread_buffers() { g_buffers.release(); }
+
+dxtlt_host::BatchAutoBuffers& dxtlt_host::batch_auto_thread_buffers() { return g_buffers; }
+
+uint64_t dxtlt_host::batch_auto_arena_cap() { return t_arena_cap ? t_arena_cap : DXTLT_BATCH_AUTO_ARENA_CAP; }
 
 extern "C" int32_t dxtlt_transform_batch_auto_device(DxtltBatchAutoItem* items, size_t count, void* hip_stream)
 {

@@ -1,6 +1,7 @@
 // batch_tables.h -- what the batch calls that stage tables share (host only): the settings code of a launch, the coarse index of
 // a granule launch, and StagedTables, the one owner of the ring's slot protocol (table_ring.h).  Users: batch_api.cpp,
-// image_batch_api.cpp, granule_image_batch_api.h (the BC7 and BC6H batch image calls).
+// image_batch_api.cpp, granule_image_batch_api.h (the BC7 and BC6H batch image calls), pixel_batch_api.cpp (the pixel batch call and
+// the winners of the batched pixel auto call), estimate_api.cpp (the entropy table launch's test hook).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

@@ -4,7 +4,10 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <cstdlib>
+#include <cstring>
+#include <vector>
 
 namespace dxtlt {
 
@@ -175,7 +178,37 @@ hipError_t launch_batch(Format fmt, bool inverse, const Settings& s, const Batch
 
 // the index (batch_index_bytes(total_wgs) bytes) from the entries (sorted by first_wg, each owning at least one workgroup, no
 // gaps); returns true when it chose the wide (16-bit delta) form
-bool build_batch_index(const BatchEntry* entries, size_t n_entries, uint32_t total_wgs, uint8_t* index);
+// (defined here, inline and pure: the planners that call it also run stand-alone under the host sanitizers)
+inline bool build_batch_index(const BatchEntry* entries, size_t n_entries, uint32_t total_wgs, uint8_t* index)
+{
+    const size_t n_base = batch_index_base_count(total_wgs), n_delta = batch_index_delta_count(total_wgs);
+    uint32_t* base = reinterpret_cast<uint32_t*>(index);
+    std::memset(index, 0, batch_index_bytes(total_wgs));
+    // owner of workgroup 64 j for every j, relative to the owner of the span's first workgroup
+    std::vector<uint32_t> d(n_delta);
+    uint32_t largest = 0;
+    size_t cur = 0;
+    for (size_t j = 0; j < n_delta; ++j) {
+        const uint32_t wg = (uint32_t)(j * kBatchIndexWgs);
+        while (cur + 1 < n_entries && entries[cur].end_wg <= wg)
+            ++cur;
+        if (wg % kBatchBaseWgs == 0)
+            base[wg / kBatchBaseWgs] = (uint32_t)cur;
+        d[j] = (uint32_t)(cur - base[wg / kBatchBaseWgs]);   // < 4096: every entry owns at least one workgroup
+        largest = std::max(largest, d[j]);
+    }
+    const bool wide = largest > 255;
+    uint8_t* delta = index + n_base * 4;
+    for (size_t j = 0; j < n_delta; ++j) {
+        if (wide) {
+            delta[2 * j] = (uint8_t)d[j];
+            delta[2 * j + 1] = (uint8_t)(d[j] >> 8);
+        } else {
+            delta[j] = (uint8_t)d[j];
+        }
+    }
+    return wide;
+}
 
 // A regular array of aligned buffers as the single-buffer aligned kernel with blockIdx.y = buffer (bcn_kernels.hip);
 // hipErrorNotSupported when the array does not have that shape.

@@ -38,6 +38,93 @@ const uint32_t h_entropy_table[kEntropyWindow + 1] = {
 #include "entropy_table.h"
 };
 
+// One window -- `w` > 0 bytes at byte `off` of the section at `base` -- counted by the workgroup, its q added to *(out): the steps of
+// both kernels below, expanded in place with `hist`, `wave_sum` and `tid` in scope.  A macro, not a function, for the reason
+// DXTLT_ESTIMATE_WINDOW_OF (estimate_sections.h) gives: entropy_kernel's code is pinned.
+#define DXTLT_ENTROPY_WINDOW(base, off, w, out) \
+    do {                                                                                                                                   \
+        const uintptr_t a = reinterpret_cast<uintptr_t>(base) + off;                                                                       \
+        const uint32_t to_line = uint32_t(-a) & 15;                                                                                        \
+        const uint32_t head = to_line < w ? to_line : w; /* bytes in front of the first 16-byte boundary */                                \
+        const uint32_t nvec = (w - head) >> 4; /* <= 2048 whole lines inside the window */                                                 \
+        const uint32_t tail = w - head - 16 * nvec; /* < 16 bytes behind the last of them */                                               \
+        /* (a pointer out of a by-value table is generic to the compiler: the address space is restored for global_load) */                \
+        typedef const u32x4 __attribute__((address_space(1))) * GlobalVec;                                                                 \
+        typedef const uint8_t __attribute__((address_space(1))) * GlobalByte;                                                              \
+        const GlobalVec src = reinterpret_cast<GlobalVec>(a + head);                                                                       \
+        const GlobalByte bytes = reinterpret_cast<GlobalByte>(a);                                                                          \
+                                                                                                                                           \
+        /* every load first.  A lane without a k-th vector loads the window's last one again (inside the section, never counted): no */    \
+        /* branch around a load, so all eight are in flight together. */                                                                   \
+        u32x4 v[kVectorsPerLane];                                                                                                          \
+        if (nvec != 0) {                                                                                                                   \
+        _Pragma("unroll")                                                                                                                  \
+            for (uint32_t k = 0; k < kVectorsPerLane; ++k) {                                                                               \
+                const uint32_t i = tid + k * kLanes;                                                                                       \
+                v[k] = __builtin_nontemporal_load(src + (i < nvec ? i : nvec - 1));                                                        \
+            }                                                                                                                              \
+        }                                                                                                                                  \
+        uint32_t edge = 0; /* lanes [0, head): a head byte; lanes [16, 16 + tail): a tail byte */                                          \
+        if (tid < head)                                                                                                                    \
+            edge = bytes[tid];                                                                                                             \
+        else if (tid >= 16 && tid - 16 < tail)                                                                                             \
+            edge = bytes[head + 16 * nvec + (tid - 16)];                                                                                   \
+                                                                                                                                           \
+        _Pragma("unroll")                                                                                                                  \
+        for (uint32_t k = 0; k < 256 * kCopies / 4 / kLanes; ++k)                                                                          \
+            reinterpret_cast<u32x4*>(hist)[tid + k * kLanes] = u32x4{0, 0, 0, 0};                                                          \
+        __syncthreads();                                                                                                                   \
+                                                                                                                                           \
+        uint32_t* mine = hist + (tid & (kCopies - 1));                                                                                     \
+        auto count_dword = [&](uint32_t x) {                                                                                               \
+            const uint32_t b0 = x & 0xFF;                                                                                                  \
+            if (x == b0 * 0x01010101u) {                                                                                                   \
+                atomicAdd(mine + b0 * kCopies, 4u);                                                                                        \
+            } else {                                                                                                                       \
+                atomicAdd(mine + b0 * kCopies, 1u);                                                                                        \
+                atomicAdd(mine + ((x >> 8) & 0xFF) * kCopies, 1u);                                                                         \
+                atomicAdd(mine + ((x >> 16) & 0xFF) * kCopies, 1u);                                                                        \
+                atomicAdd(mine + (x >> 24) * kCopies, 1u);                                                                                 \
+            }                                                                                                                              \
+        };                                                                                                                                 \
+        if (nvec != 0) {                                                                                                                   \
+        _Pragma("unroll")                                                                                                                  \
+            for (uint32_t k = 0; k < kVectorsPerLane; ++k)                                                                                 \
+                if (tid + k * kLanes < nvec) {                                                                                             \
+                    count_dword(v[k].x);                                                                                                   \
+                    count_dword(v[k].y);                                                                                                   \
+                    count_dword(v[k].z);                                                                                                   \
+                    count_dword(v[k].w);                                                                                                   \
+                }                                                                                                                          \
+        }                                                                                                                                  \
+        if (tid < head || (tid >= 16 && tid - 16 < tail))                                                                                  \
+            atomicAdd(mine + edge * kCopies, 1u);                                                                                          \
+        __syncthreads();                                                                                                                   \
+                                                                                                                                           \
+        /* lane v: c[v] from its sixteen copies, then c T[c] (c <= 32768, T < 2^20: the product needs 64 bits) */                          \
+        uint32_t c = 0;                                                                                                                    \
+        _Pragma("unroll")                                                                                                                  \
+        for (uint32_t k = 0; k < kCopies / 4; ++k) {                                                                                       \
+            const u32x4 part = reinterpret_cast<const u32x4*>(hist)[tid * (kCopies / 4) + k];                                              \
+            c += part.x + part.y + part.z + part.w;                                                                                        \
+        }                                                                                                                                  \
+        unsigned long long sum = (unsigned long long)c * d_entropy_table[c];                                                               \
+        for (int o = 32; o > 0; o >>= 1)                                                                                                   \
+            sum += __shfl_down(sum, o);                                                                                                    \
+        if ((tid & 63) == 0)                                                                                                               \
+            wave_sum[tid >> 6] = sum;                                                                                                      \
+        __syncthreads();                                                                                                                   \
+        if (tid == 0) {                                                                                                                    \
+            unsigned long long all = 0;                                                                                                    \
+        _Pragma("unroll")                                                                                                                  \
+            for (uint32_t k = 0; k < kLanes / 64; ++k)                                                                                     \
+                all += wave_sum[k];                                                                                                        \
+            const unsigned long long whole = (unsigned long long)w * d_entropy_table[w];                                                   \
+            if (whole > all)                                                                                                               \
+                atomicAdd(out, whole - all);                                                                                               \
+        }                                                                                                                                  \
+    } while (0)
+
 __global__ void __launch_bounds__(kLanes) entropy_kernel(const EstimateTable tab)
 {
     __shared__ __attribute__((aligned(16))) uint32_t hist[256 * kCopies];
@@ -47,87 +134,24 @@ __global__ void __launch_bounds__(kLanes) entropy_kernel(const EstimateTable tab
     DXTLT_ESTIMATE_WINDOW_OF(kEntropyWindow, tab, wg);   // s, base, off, w
     if (base == nullptr || w == 0)   // (uniform) nothing to count: the section's counter stays as it is
         return;
+    DXTLT_ENTROPY_WINDOW(base, off, w, tab.out + s);
+}
 
-    const uintptr_t a = reinterpret_cast<uintptr_t>(base) + off;
-    const uint32_t to_line = uint32_t(-a) & 15;
-    const uint32_t head = to_line < w ? to_line : w;   // bytes in front of the first 16-byte boundary
-    const uint32_t nvec = (w - head) >> 4;             // <= 2048 whole lines inside the window
-    const uint32_t tail = w - head - 16 * nvec;        // < 16 bytes behind the last of them
-    // (a pointer out of a by-value table is generic to the compiler: the address space is restored for global_load)
-    typedef const u32x4 __attribute__((address_space(1))) * GlobalVec;
-    typedef const uint8_t __attribute__((address_space(1))) * GlobalByte;
-    const GlobalVec src = reinterpret_cast<GlobalVec>(a + head);
-    const GlobalByte bytes = reinterpret_cast<GlobalByte>(a);
+// The same windows from a section table in DEVICE memory with any number of entries (the batched pixel auto transform: six
+// sections per buffer, thousands of buffers, one launch): the entry by the bisection of estimate_table_kernel
+// (DXTLT_ESTIMATE_TABLE_WINDOW_OF), then the window as above, q added to counters[entry.counter].  Sums only: the caller rounds
+// (launch_entropy_finish, or on the host).
+__global__ void __launch_bounds__(kLanes)
+entropy_table_kernel(const EstimateTableEntry* __restrict__ tab, uint32_t entries, unsigned long long* __restrict__ counters)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t hist[256 * kCopies];
+    __shared__ unsigned long long wave_sum[kLanes / 64];
 
-    // every load first.  A lane without a k-th vector loads the window's last one again (inside the section, never counted): no
-    // branch around a load, so all eight are in flight together.
-    u32x4 v[kVectorsPerLane];
-    if (nvec != 0) {
-#pragma unroll
-        for (uint32_t k = 0; k < kVectorsPerLane; ++k) {
-            const uint32_t i = tid + k * kLanes;
-            v[k] = __builtin_nontemporal_load(src + (i < nvec ? i : nvec - 1));
-        }
-    }
-    uint32_t edge = 0;   // lanes [0, head): a head byte; lanes [16, 16 + tail): a tail byte
-    if (tid < head)
-        edge = bytes[tid];
-    else if (tid >= 16 && tid - 16 < tail)
-        edge = bytes[head + 16 * nvec + (tid - 16)];
-
-#pragma unroll
-    for (uint32_t k = 0; k < 256 * kCopies / 4 / kLanes; ++k)
-        reinterpret_cast<u32x4*>(hist)[tid + k * kLanes] = u32x4{0, 0, 0, 0};
-    __syncthreads();
-
-    uint32_t* mine = hist + (tid & (kCopies - 1));
-    auto count_dword = [&](uint32_t x) {
-        const uint32_t b0 = x & 0xFF;
-        if (x == b0 * 0x01010101u) {
-            atomicAdd(mine + b0 * kCopies, 4u);
-        } else {
-            atomicAdd(mine + b0 * kCopies, 1u);
-            atomicAdd(mine + ((x >> 8) & 0xFF) * kCopies, 1u);
-            atomicAdd(mine + ((x >> 16) & 0xFF) * kCopies, 1u);
-            atomicAdd(mine + (x >> 24) * kCopies, 1u);
-        }
-    };
-    if (nvec != 0) {
-#pragma unroll
-        for (uint32_t k = 0; k < kVectorsPerLane; ++k)
-            if (tid + k * kLanes < nvec) {
-                count_dword(v[k].x);
-                count_dword(v[k].y);
-                count_dword(v[k].z);
-                count_dword(v[k].w);
-            }
-    }
-    if (tid < head || (tid >= 16 && tid - 16 < tail))
-        atomicAdd(mine + edge * kCopies, 1u);
-    __syncthreads();
-
-    // lane v: c[v] from its sixteen copies, then c T[c] (c <= 32768, T < 2^20: the product needs 64 bits)
-    uint32_t c = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < kCopies / 4; ++k) {
-        const u32x4 part = reinterpret_cast<const u32x4*>(hist)[tid * (kCopies / 4) + k];
-        c += part.x + part.y + part.z + part.w;
-    }
-    unsigned long long sum = (unsigned long long)c * d_entropy_table[c];
-    for (int o = 32; o > 0; o >>= 1)
-        sum += __shfl_down(sum, o);
-    if ((tid & 63) == 0)
-        wave_sum[tid >> 6] = sum;
-    __syncthreads();
-    if (tid == 0) {
-        unsigned long long all = 0;
-#pragma unroll
-        for (uint32_t k = 0; k < kLanes / 64; ++k)
-            all += wave_sum[k];
-        const unsigned long long whole = (unsigned long long)w * d_entropy_table[w];
-        if (whole > all)
-            atomicAdd(tab.out + s, whole - all);
-    }
+    const uint32_t wg = blockIdx.x, tid = threadIdx.x;
+    DXTLT_ESTIMATE_TABLE_WINDOW_OF(kEntropyWindow, tab, entries, counters, wg);   // base, off, w, out
+    if (base == nullptr || w == 0)
+        return;
+    DXTLT_ENTROPY_WINDOW(base, off, w, out);
 }
 
 __global__ void __launch_bounds__(64) entropy_finish_kernel(unsigned long long* __restrict__ sums, uint32_t count)
@@ -152,6 +176,29 @@ hipError_t launch_entropy(const EstimateSection* sections, size_t count, uint64_
         return e;
     hipLaunchKernelGGL(entropy_finish_kernel, dim3(uint32_t((count + 63) / 64)), dim3(64), 0, stream,
                        reinterpret_cast<unsigned long long*>(d_out), uint32_t(count));
+    return hipGetLastError();
+}
+
+hipError_t launch_entropy_table(const EstimateTableEntry* d_table, uint32_t entries, uint32_t workgroups, uint64_t* d_counters,
+                                hipStream_t stream)
+{
+    if (entries == 0 || workgroups == 0)
+        return hipSuccess;
+    if (workgroups > 0x7FFFFFFFu)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(entropy_table_kernel, dim3(workgroups), dim3(kLanes), 0, stream, d_table, entries,
+                       reinterpret_cast<unsigned long long*>(d_counters));
+    return hipGetLastError();
+}
+
+hipError_t launch_entropy_finish(uint64_t* d_counters, size_t count, hipStream_t stream)
+{
+    if (count == 0)
+        return hipSuccess;
+    if (count > 0x7FFFFFFFu)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(entropy_finish_kernel, dim3(uint32_t((count + 63) / 64)), dim3(64), 0, stream,
+                       reinterpret_cast<unsigned long long*>(d_counters), uint32_t(count));
     return hipGetLastError();
 }
 

@@ -4,6 +4,11 @@
 // and stream.
 #include "../../include/dxtlt_entropy_estimator.h"
 #include "../../include/dxtlt_estimator.h"
+
+#include <cstring>
+#include <vector>
+
+#include "batch_tables.h"
 #include "entropy_launch.h"
 #include "estimate_launch.h"
 #include "host_common.h"
@@ -309,6 +314,60 @@ int32_t dxtlt_estimate_entropy_sizes_device(const DxtltEstimateSection* sections
         return fail(kInvalidArgument, "a section of more than 2^31 - 1 windows");
     HIP_TRY(e, "entropy estimator launch");
     return kOk;
+}
+
+// the entropy estimates of `count` sections through launch_entropy_table: the table built here, staged in one slot of this
+// thread's table ring and uploaded on the stream, ONE estimator launch whatever `count` is, one finishing launch
+int32_t dxtlt_debug_estimate_entropy_table_counters_device(const DxtltEstimateSection* sections, const uint32_t* counters, size_t count,
+                                                           size_t counter_count, void* hip_stream, uint64_t* d_out)
+{
+    using namespace dxtlt_host;
+    if (count == 0 || counter_count == 0)
+        return kOk;
+    if (sections == nullptr || d_out == nullptr || reinterpret_cast<uintptr_t>(d_out) % 8 != 0)
+        return fail(kInvalidArgument, "NULL sections / d_out with count > 0, or d_out not 8-byte aligned");
+    if (counter_count > 0x7FFFFFFFu)
+        return fail(kInvalidArgument, "more than 2^31 - 1 counters");
+    std::vector<dxtlt::EstimateTableEntry> table;
+    uint64_t wgs = 0;
+    for (size_t i = 0; i < count; ++i) {
+        const size_t counter = counters ? counters[i] : i;
+        if (counter >= counter_count)
+            return fail(kInvalidArgument, "a section's counter is out of range");
+        if (sections[i].d_ptr == nullptr || sections[i].len == 0)
+            continue;   // nothing to count: owns no workgroup, its counter stays as the others leave it
+        wgs += (sections[i].len + dxtlt::kEntropyWindow - 1) / dxtlt::kEntropyWindow;
+        if (wgs > 0x7FFFFFFFull)
+            return fail(kInvalidArgument, "more than 2^31 - 1 windows in one launch");
+        table.push_back({static_cast<const uint8_t*>(sections[i].d_ptr), sections[i].len, (uint32_t)wgs, (uint32_t)counter});
+    }
+    if (int32_t rc = need_device())
+        return rc;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    if (stream_is_capturing(st))
+        return fail(kInvalidArgument, "the table launch hook stages its table in a per-thread ring that later calls rewrite: not capturable");
+    HIP_TRY(hipMemsetAsync(d_out, 0, counter_count * sizeof(uint64_t), st), "entropy counters clear");
+    if (table.empty())
+        return kOk;
+    StagedTables staged;
+    const size_t bytes = padded(table.size() * sizeof(dxtlt::EstimateTableEntry), 16);
+    hipError_t e = staged.acquire(bytes);
+    if (e != hipSuccess)
+        return fail(kDevice, "entropy table staging", e);
+    std::memset(staged.host(), 0, bytes);
+    std::memcpy(staged.host(), table.data(), table.size() * sizeof(dxtlt::EstimateTableEntry));
+    e = staged.upload(st);
+    if (e == hipSuccess)
+        e = dxtlt::launch_entropy_table(reinterpret_cast<const dxtlt::EstimateTableEntry*>(staged.dev()), (uint32_t)table.size(),
+                                        (uint32_t)wgs, d_out, st);
+    if (e == hipSuccess)
+        e = dxtlt::launch_entropy_finish(d_out, counter_count, st);
+    return staged.finish(e, st, "entropy table copy / launch", "entropy table event");
+}
+
+int32_t dxtlt_debug_estimate_entropy_table_device(const DxtltEstimateSection* sections, size_t count, void* hip_stream, uint64_t* d_out)
+{
+    return dxtlt_debug_estimate_entropy_table_counters_device(sections, nullptr, count, count, hip_stream, d_out);
 }
 
 int32_t dxtlt_estimate_entropy_size_device(const void* d_ptr, size_t len, void* hip_stream, uint64_t* out)

@@ -104,7 +104,7 @@ __global__ void __launch_bounds__(T) estimate_kernel(const EstimateTable tab)
 
 // The same windows from a section table in DEVICE memory with any number of entries (the batched auto transform: thousands of
 // sections in one launch).  Entries are in workgroup order; entry e owns workgroups [end_wg of entry e - 1, end_wg) and adds into
-// counters[counter].  A workgroup finds its entry by bisection over end_wg -- uniform: scalar loads and compares -- and then runs
+// counters[counter].  A workgroup finds its entry by bisection over end_wg (DXTLT_ESTIMATE_TABLE_WINDOW_OF, estimate_sections.h) and then runs
 // estimate_kernel's steps on its window, statement for statement.  (A copy, not a shared function: moving the steps into one
 // changes the block placement and scalar registers of estimate_kernel's own code, and that kernel's code is pinned.)
 template <int T, uint32_t W, uint32_t BITS>
@@ -119,20 +119,7 @@ estimate_table_kernel(const EstimateTableEntry* __restrict__ tab, uint32_t entri
     __shared__ uint32_t wg_matches;
 
     const uint32_t wg = blockIdx.x, tid = threadIdx.x;
-    uint32_t lo = 0, hi = entries - 1;   // the first entry whose end_wg is above wg: in [lo, hi] (the grid ends at the last end_wg)
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (tab[mid].end_wg > wg)
-            hi = mid;
-        else
-            lo = mid + 1;
-    }
-    const uint32_t begin = lo == 0 ? 0u : tab[lo - 1].end_wg;
-    const uint8_t* base = tab[lo].base;
-    const uint64_t len = tab[lo].len;
-    unsigned long long* out = counters + tab[lo].counter;
-    const uint64_t off = uint64_t(wg - begin) * W;
-    const uint32_t w = len - off < W ? uint32_t(len - off) : W;
+    DXTLT_ESTIMATE_TABLE_WINDOW_OF(W, tab, entries, counters, wg);   // base, off, w, out
 
     if (base == nullptr || w < 4) {   // no gram: every byte counts
         if (tid == 0)

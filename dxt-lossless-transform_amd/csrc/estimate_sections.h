@@ -39,6 +39,25 @@ struct EstimateTable {
     const uint64_t off = uint64_t((wg) - begin) * (W);                \
     const uint32_t w = len - off < (W) ? uint32_t(len - off) : (W)
 
+// The same for a section table in DEVICE memory (EstimateTableEntry, estimate_launch.h: any number of entries in workgroup order):
+// the entry is the first whose end_wg is above `wg`, found by bisection -- uniform: scalar loads and compares; the grid ends at the
+// last end_wg.  Declares `base`, `len`, `off` and `w` as above and `out`, the entry's counter in `counters`.
+#define DXTLT_ESTIMATE_TABLE_WINDOW_OF(W, tab, entries, counters, wg)            \
+    uint32_t lo = 0, hi = (entries) - 1;                                          \
+    while (lo < hi) {                                                             \
+        const uint32_t mid = (lo + hi) >> 1;                                      \
+        if ((tab)[mid].end_wg > (wg))                                             \
+            hi = mid;                                                             \
+        else                                                                      \
+            lo = mid + 1;                                                         \
+    }                                                                             \
+    const uint32_t begin = lo == 0 ? 0u : (tab)[lo - 1].end_wg;                   \
+    const uint8_t* base = (tab)[lo].base;                                         \
+    const uint64_t len = (tab)[lo].len;                                           \
+    unsigned long long* out = (counters) + (tab)[lo].counter;                     \
+    const uint64_t off = uint64_t((wg) - begin) * (W);                            \
+    const uint32_t w = len - off < (W) ? uint32_t(len - off) : (W)
+
 // d_out[i] receives the sum section i's windows add, i < count: zeroes the counters on `stream`, then calls
 // launch(grid, table) once per 16 sections (fewer where a launch would pass 2^31 - 1 workgroups; a launch of no windows is
 // skipped).  hipErrorInvalidValue, before anything is enqueued: a section of more than 2^31 - 1 windows.

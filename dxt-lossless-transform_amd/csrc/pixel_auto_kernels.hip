@@ -13,58 +13,19 @@
 // slices start wherever i * len falls: the stores are the same vectors at those addresses, single bytes in the last, short tile.
 #include <hip/hip_runtime.h>
 
-#include "pixel_device.h"
 #include "pixel_launch.h"
-#include "pixel_tile_io.h"
+#include "pixel_tile_body.h"
 
 namespace dxtlt {
 namespace pixels {
 namespace {
 
+// one tile per workgroup: pixel_candidates_tile (pixel_tile_body.h), which pixel_batch_candidates (pixel_batch_kernels.hip) runs too
 template <int B>
 __global__ void __launch_bounds__(kThreads) pixel_candidates(const uint8_t* __restrict__ src, uint8_t* __restrict__ arena, uint64_t total)
 {
     __shared__ __attribute__((aligned(16))) uint8_t lds[B * kTile];
-    const uint64_t tile_first = (uint64_t)blockIdx.x * kTile;
-    const uint32_t n = (uint32_t)(total - tile_first < kTile ? total - tile_first : kTile);
-    const uint32_t p0 = 16 * threadIdx.x;   // the lane's first pixel inside the tile
-    const uint32_t valid = p0 >= n ? 0 : (n - p0 < 16 ? n - p0 : 16);
-    const uint64_t len = total * B;
-    auto planes_of = [&](int candidate) { return arena + (uint64_t)candidate * len + tile_first + p0; };
-
-    stage_in(lds, src + tile_first * B, n * B);
-    __syncthreads();
-    uint32_t w[4 * B];
-    if (valid != 0) {
-        uint32_t pl[B][4], prev[B];
-        lds_read_pixels<B>(lds, w);
-        Pixels16<B>::deinterleave(w, pl);
-        // the pixel in front of the lane's first: the last one of the lane in front; the segment's first byte stays
-        for (int c = 0; c < B; ++c)
-            prev[c] = p0 == 0 ? 0u : lds[(p0 - 1) * B + c];
-        for (int c = 0; c < B; ++c)
-            plane_store(planes_of(4) + (uint64_t)c * total, pl[c], valid);
-        for (int c = 0; c < B; ++c) {
-            uint32_t d[4] = {pl[c][0], pl[c][1], pl[c][2], pl[c][3]};
-            delta16(d, prev[c]);
-            plane_store(planes_of(3) + (uint64_t)c * total, d, valid);
-        }
-        decorrelate_planes<B, false>(pl);
-        prev[0] = (prev[0] - prev[1]) & 0xFF;
-        prev[2] = (prev[2] - prev[1]) & 0xFF;
-        for (int c = 0; c < B; ++c)
-            plane_store(planes_of(1) + (uint64_t)c * total, pl[c], valid);
-        Pixels16<B>::interleave(pl, w);
-        for (int c = 0; c < B; ++c) {
-            delta16(pl[c], prev[c]);
-            plane_store(planes_of(0) + (uint64_t)c * total, pl[c], valid);
-        }
-    }
-    __syncthreads();   // every lane has read its pixels and the one in front of them
-    if (valid != 0)
-        lds_write_pixels<B>(lds, w);
-    __syncthreads();
-    stage_out(lds, arena + 2 * len + tile_first * B, n * B);
+    DXTLT_PIXEL_CANDIDATES_TILE(src, arena, total, blockIdx.x);
 }
 
 }  // namespace

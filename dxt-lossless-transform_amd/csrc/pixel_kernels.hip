@@ -26,108 +26,21 @@
 // checked: no access touches a byte outside the range's own.
 #include <hip/hip_runtime.h>
 
-#include "pixel_device.h"
 #include "pixel_launch.h"
-#include "pixel_tile_io.h"
+#include "pixel_tile_body.h"
 
 namespace dxtlt {
 namespace pixels {
 namespace {
 
-// Inclusive prefix sum over the tile's 4096 bytes of every plane; lane t holds bytes [16 t, 16 t + 16) of each.
-template <int B>
-__device__ __forceinline__ void scan_planes(uint32_t (&pl)[B][4], uint32_t* wave_totals)
-{
-    // in the lane; the B lane totals share one dword, a byte each
-    uint32_t totals = 0;
-    for (int c = 0; c < B; ++c)
-        totals |= scan16(pl[c]) << (8 * c);
-    // across the wave: inclusive, then the lane in front's value is what this lane has to add
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t incl = totals;
-    for (int d = 1; d < 64; d *= 2) {
-        const uint32_t up = __shfl_up(incl, d, 64);
-        if (lane >= (uint32_t)d)
-            incl = byte_add(incl, up);
-    }
-    uint32_t before = __shfl_up(incl, 1, 64);
-    if (lane == 0)
-        before = 0;
-    // across the four waves
-    if (lane == 63)
-        wave_totals[wave] = incl;
-    __syncthreads();
-    for (uint32_t w = 0; w < wave; ++w)
-        before = byte_add(before, wave_totals[w]);
-    for (int c = 0; c < B; ++c)
-        add_to_all16(pl[c], (before >> (8 * c)) & 0xFF);
-}
-
+// one tile per workgroup: pixel_tile (pixel_tile_body.h), which the batch kernels of pixel_batch_kernels.hip run too
 template <int B, bool INVERSE, bool DECORRELATE, int LAYOUT>
 __global__ void __launch_bounds__(kThreads)
 pixel_tiles(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, uint64_t total, uint64_t first, uint64_t num)
 {
     __shared__ __attribute__((aligned(16))) uint8_t lds[B * kTile];
     __shared__ uint32_t wave_totals[kThreads / 64];
-    const uint64_t tile_first = (uint64_t)blockIdx.x * kTile;   // inside the range
-    const uint32_t n = (uint32_t)(num - tile_first < kTile ? num - tile_first : kTile);
-    const uint32_t p0 = 16 * threadIdx.x;                       // the lane's first pixel inside the tile
-    const uint32_t valid = p0 >= n ? 0 : (n - p0 < 16 ? n - p0 : 16);
-    // where the tile lies on the transformed side: layout 0 keeps the pixels in place, else plane c starts at c * total
-    const uint64_t at = first + tile_first;
-
-    if constexpr (LAYOUT == kInterleaved) {
-        stage_in(lds, INVERSE ? src + at * B : src + tile_first * B, n * B);
-        if constexpr (DECORRELATE) {
-            __syncthreads();
-            if (valid != 0) {
-                uint32_t w[4 * B], pl[B][4];
-                lds_read_pixels<B>(lds, w);
-                Pixels16<B>::deinterleave(w, pl);
-                decorrelate_planes<B, INVERSE>(pl);
-                Pixels16<B>::interleave(pl, w);
-                lds_write_pixels<B>(lds, w);
-            }
-        }
-        __syncthreads();
-        stage_out(lds, INVERSE ? dst + tile_first * B : dst + at * B, n * B);
-    } else if constexpr (!INVERSE) {
-        stage_in(lds, src + tile_first * B, n * B);
-        __syncthreads();
-        if (valid != 0) {
-            uint32_t w[4 * B], pl[B][4];
-            lds_read_pixels<B>(lds, w);
-            Pixels16<B>::deinterleave(w, pl);
-            if constexpr (DECORRELATE)
-                decorrelate_planes<B, false>(pl);
-            if constexpr (LAYOUT == kPlanarDelta) {
-                // the pixel in front of the lane's first: the last one of the lane in front; the segment's first byte stays
-                uint32_t prev[B];
-                for (int c = 0; c < B; ++c)
-                    prev[c] = p0 == 0 ? 0u : lds[(p0 - 1) * B + c];
-                if constexpr (DECORRELATE) {
-                    prev[0] = (prev[0] - prev[1]) & 0xFF;
-                    prev[2] = (prev[2] - prev[1]) & 0xFF;
-                }
-                for (int c = 0; c < B; ++c)
-                    delta16(pl[c], prev[c]);
-            }
-            for (int c = 0; c < B; ++c)
-                plane_store(dst + (uint64_t)c * total + at + p0, pl[c], valid);
-        }
-    } else {
-        uint32_t w[4 * B], pl[B][4];
-        for (int c = 0; c < B; ++c)
-            plane_load(src + (uint64_t)c * total + at + p0, pl[c], valid);
-        if constexpr (LAYOUT == kPlanarDelta)
-            scan_planes<B>(pl, wave_totals);
-        if constexpr (DECORRELATE)
-            decorrelate_planes<B, true>(pl);
-        Pixels16<B>::interleave(pl, w);
-        lds_write_pixels<B>(lds, w);
-        __syncthreads();
-        stage_out(lds, dst + tile_first * B, n * B);
-    }
+    DXTLT_PIXEL_TILE(src, dst, total, first, num, blockIdx.x);
 }
 
 template <int B, bool INVERSE, bool DECORRELATE>

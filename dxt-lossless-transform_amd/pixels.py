@@ -147,6 +147,109 @@ def last_auto_totals():
     return [int(v) for v in buf[:n]]
 
 
+class PixelBatchItem(C.Structure):               # DxtltPixelBatchItem
+    _fields_ = [("d_input", C.c_void_p), ("d_output", C.c_void_p), ("len", C.c_uint64), ("pixel_bytes", C.c_uint8),
+                ("inverse", C.c_uint8), ("decorrelate", C.c_uint8), ("layout", C.c_uint8), ("reserved", C.c_uint8 * 4)]
+
+
+class PixelBatchAutoItem(C.Structure):           # DxtltPixelBatchAutoItem
+    _fields_ = [("d_input", C.c_void_p), ("d_output", C.c_void_p), ("len", C.c_uint64), ("pixel_bytes", C.c_uint8),
+                ("decorrelate", C.c_uint8), ("layout", C.c_uint8), ("reserved", C.c_uint8 * 5)]
+
+
+def _batch_buffers(name: str, k: int, src, dst, pixel_bytes: int, device):
+    """the two tensors of item `k` as (_Buf, _Buf, device), checked as the single calls check them"""
+    from . import InvalidLength, OutputBufferTooSmall, _Buf
+
+    s, d = _Buf(src, False), _Buf(dst, True)
+    if s.device is None or d.device is None:
+        raise TypeError(name + " takes device tensors")
+    device = s.device if device is None else device
+    if s.device != device or d.device != device:
+        raise ValueError("all tensors of a batch must live on one device")
+    if pixel_bytes not in (3, 4):
+        raise ValueError("pixel_bytes must be 4 (RGBA8888, BGRA8888) or 3 (BGR888)")
+    if s.nbytes % pixel_bytes != 0:
+        raise InvalidLength(s.nbytes)
+    if d.nbytes < s.nbytes:
+        raise OutputBufferTooSmall(s.nbytes, d.nbytes)
+    return s, d, device
+
+
+def _stream_of(stream):
+    import torch
+
+    if stream is None:
+        return torch.cuda.current_stream().cuda_stream
+    return stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
+
+
+def transform_pixels_batch(items, stream=None) -> None:
+    """dxtlt_transform_pixels_batch_device: items are (input tensor, output tensor, pixel_bytes, inverse, decorrelate, layout) with
+    CUDA uint8 tensors on one device.  Every item is transformed (inverse false) or untransformed exactly as the single calls do
+    it, with one launch per (pixel_bytes, inverse, decorrelate, layout) class present: enqueued on `stream` (a torch stream or a
+    raw handle; default torch's current stream), not waited for.  An output may overlap no other buffer of the batch."""
+    import torch
+
+    from . import DeviceError
+
+    if not items:
+        return
+    arr = (PixelBatchItem * len(items))()
+    device, keep = None, []
+    for k, (src, dst, pixel_bytes, inverse, decorrelate, layout) in enumerate(items):
+        _check_settings(pixel_bytes, layout)
+        s, d, device = _batch_buffers("transform_pixels_batch", k, src, dst, pixel_bytes, device)
+        arr[k].d_input, arr[k].d_output, arr[k].len = s.ptr, d.ptr, s.nbytes
+        arr[k].pixel_bytes, arr[k].inverse, arr[k].decorrelate, arr[k].layout = pixel_bytes, int(bool(inverse)), int(bool(decorrelate)), layout
+        keep.append((s, d))
+    l = _l()
+    l.dxtlt_transform_pixels_batch_device.argtypes = [C.POINTER(PixelBatchItem), C.c_size_t, C.c_void_p]
+    l.dxtlt_transform_pixels_batch_device.restype = C.c_int32
+    with torch.cuda.device(device):
+        rc = l.dxtlt_transform_pixels_batch_device(arr, len(arr), _stream_of(stream))
+    if rc != _lib.OK:
+        raise DeviceError(rc, _lib.last_error())
+
+
+def transform_batch_auto(items, stream=None):
+    """dxtlt_transform_pixels_batch_auto_device: items are (input tensor, output tensor, pixel_bytes) with CUDA uint8 tensors on
+    one device.  Chooses the best of the six settings for every item with the entropy estimator and transforms them all on `stream`
+    (default torch's current stream): one stream wait and a launch count that does not grow with the number of items.  Returns
+    the list of (decorrelate, layout), one per item; the transforms are enqueued, not waited for."""
+    import torch
+
+    from . import DeviceError
+
+    if not items:
+        return []
+    arr = (PixelBatchAutoItem * len(items))()
+    device, keep = None, []
+    for k, (src, dst, pixel_bytes) in enumerate(items):
+        s, d, device = _batch_buffers("transform_batch_auto", k, src, dst, pixel_bytes, device)
+        arr[k].d_input, arr[k].d_output, arr[k].len, arr[k].pixel_bytes = s.ptr, d.ptr, s.nbytes, pixel_bytes
+        keep.append((s, d))
+    l = _l()
+    l.dxtlt_transform_pixels_batch_auto_device.argtypes = [C.POINTER(PixelBatchAutoItem), C.c_size_t, C.c_void_p]
+    l.dxtlt_transform_pixels_batch_auto_device.restype = C.c_int32
+    with torch.cuda.device(device):
+        rc = l.dxtlt_transform_pixels_batch_auto_device(arr, len(arr), _stream_of(stream))
+    if rc != _lib.OK:
+        raise DeviceError(rc, _lib.last_error())
+    return [(bool(a.decorrelate), int(a.layout)) for a in arr]
+
+
+def last_batch_auto_totals(item: int):
+    """The six totals the last transform_batch_auto of this thread compared for item `item`, in the order of AUTO_CANDIDATES ([]
+    for an empty item, an item out of range or a failed call)."""
+    l = _l()
+    f = l.dxtlt_debug_pixels_batch_auto_last_totals
+    f.argtypes, f.restype = [C.c_size_t, C.POINTER(C.c_uint64), C.c_int32], C.c_int32
+    buf = (C.c_uint64 * 6)()
+    n = f(int(item), buf, 6)
+    return [int(v) for v in buf[:n]]
+
+
 def settings_triple(decorrelate: bool, layout: int):
     """(decorrelation_mode, split_alpha_endpoints, split_colour_endpoints) as the generic entry points -- the host batch call's
     format codes 8 / 9, dxtlt_transform_sharded, the DDS calls -- read these settings"""

@@ -349,6 +349,19 @@ inline void transform_batch_auto_device(DxtltBatchAutoItem* items, size_t count,
     detail::check_device(dxtlt_transform_batch_auto_device(items, count, hip_stream));
 }
 
+// Many uncompressed-pixel buffers in one call (dxtlt_pixels.h): one launch per (pixel_bytes, direction, decorrelate, layout) class.
+inline void transform_pixels_batch_device(const DxtltPixelBatchItem* items, size_t count, void* hip_stream)
+{
+    detail::check_device(dxtlt_transform_pixels_batch_device(items, count, hip_stream));
+}
+
+// The batched pixel auto transform (dxtlt_transform_pixels_batch_auto_device): the best of the six settings for every item, all of
+// them transformed, one stream wait.  The choices are written into the items' `decorrelate` and `layout`.
+inline void transform_pixels_batch_auto_device(DxtltPixelBatchAutoItem* items, size_t count, void* hip_stream)
+{
+    detail::check_device(dxtlt_transform_pixels_batch_auto_device(items, count, hip_stream));
+}
+
 // ---- dxt_lossless_transform_bc1::experimental::normalize_blocks (normalize.rs, transform.rs, mod.rs) ------------
 namespace experimental {
 

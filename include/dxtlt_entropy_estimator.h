@@ -35,6 +35,18 @@ uint32_t dxtlt_entropy_estimator_version(void);
  * none may overlap d_out. */
 int32_t dxtlt_estimate_entropy_sizes_device(const DxtltEstimateSection *sections, size_t count, void *hip_stream, uint64_t *d_out);
 
+/* Test and bench hooks: the same estimates through the table-driven launch the batched pixel auto transform uses
+ * (dxtlt_transform_pixels_batch_auto_device, dxtlt_pixels.h; docs/ESTIMATOR.md, "The table launch").  table_device: the section
+ * table of all `count` sections is built on the host, staged in one of the calling thread's four table slots and uploaded on
+ * `hip_stream`; then a clear of d_out, ONE estimator launch for any count, and one finishing launch.  d_out[i] equals what
+ * dxtlt_estimate_entropy_sizes_device writes.  table_counters_device: section i adds into d_out[counters[i]] (counters NULL: i),
+ * d_out holding counter_count numbers -- sections that share a counter are rounded up to bytes as ONE sum of q.  Both enqueue only,
+ * but are not capturable (the slot is rewritten by later calls): DXTLT_E_INVALID_ARGUMENT on a capturing stream, for a counter
+ * out of range, or for more than 2^31 - 1 windows in all. */
+int32_t dxtlt_debug_estimate_entropy_table_device(const DxtltEstimateSection *sections, size_t count, void *hip_stream, uint64_t *d_out);
+int32_t dxtlt_debug_estimate_entropy_table_counters_device(const DxtltEstimateSection *sections, const uint32_t *counters, size_t count,
+                                                           size_t counter_count, void *hip_stream, uint64_t *d_out);
+
 /* One section of device memory; waits for `hip_stream` and returns the number in *out. */
 int32_t dxtlt_estimate_entropy_size_device(const void *d_ptr, size_t len, void *hip_stream, uint64_t *out);
 

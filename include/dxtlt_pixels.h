@@ -105,6 +105,123 @@ void dxtlt_debug_pixels_auto_time_phases(int32_t on);
 void dxtlt_debug_pixels_auto_last_phase_ms(double out[3]);
 int32_t dxtlt_debug_pixels_auto_candidates_device(const void *d_input, size_t len, int32_t pixel_bytes, void *hip_stream);
 
+/* ---- many buffers in one call (docs/PIXEL_FORMAT.md, "Many buffers in one call") -------------------------------------------------
+ * dxtlt_transform_pixels_batch_device: for every item the bytes in d_output are exactly what dxtlt_transform_pixels_device
+ * (inverse = 0) or dxtlt_untransform_pixels_device (inverse = 1) writes for that item alone, and no byte outside an item's own len
+ * output bytes is written -- with ONE kernel launch per (pixel_bytes, inverse, decorrelate, layout) class present in the batch (at
+ * most 24) and one small table upload, however many items there are.  Any pointer alignment and any pixel count per item.
+ * Asynchronous: enqueues on `hip_stream` and does not wait for it; ordered like a single call.  count == 0 is a no-op; an item with
+ * len == 0 needs no pointers and owns no workgroup.
+ *
+ * The whole batch is checked before anything is enqueued.  DXTLT_E_INVALID_ARGUMENT: NULL `items` with count > 0; pixel_bytes not
+ * 3 or 4; layout > 2; a NULL buffer with len > 0; an item of 64 GiB or more; a d_output that overlaps any other d_output or any
+ * d_input of the batch (inputs may overlap one another); a class of 2^24 tiles of 4096 pixels or more -- 256 GiB of 4-byte,
+ * 192 GiB of 3-byte pixels: the limit of one launch of dxtlt_transform_batch_device; a capturing stream.  DXTLT_E_INVALID_LENGTH:
+ * len not a multiple of pixel_bytes.
+ *
+ * Not capturable.  Like dxtlt_transform_batch_device the call stages its tables in ONE of four per-thread slots of pinned host
+ * memory, which a small kernel copies to the device on `hip_stream`; taking a slot may wait (on the host) for the event of the
+ * call that used it last -- so do not enqueue more than four batch calls of one thread behind an event that is recorded later --
+ * and a replayed graph would copy whatever a later call has put into the slot.  So a capturing stream, or one whose capture state
+ * cannot be queried, is refused with nothing enqueued, as the auto calls refuse it. */
+typedef struct DxtltPixelBatchItem {
+    const void *d_input;
+    void *d_output;        /* len bytes */
+    uint64_t len;          /* a multiple of pixel_bytes; 0 is allowed */
+    uint8_t pixel_bytes;   /* 4 or 3 */
+    uint8_t inverse;       /* 0 = transform, 1 = untransform */
+    uint8_t decorrelate;   /* 0 / not 0 */
+    uint8_t layout;        /* DXTLT_PIXEL_LAYOUT_* */
+    uint8_t reserved[4];
+} DxtltPixelBatchItem;
+int32_t dxtlt_transform_pixels_batch_device(const DxtltPixelBatchItem *items, size_t count, void *hip_stream);
+
+/* Test hook, no device needed: what dxtlt_transform_pixels_batch_device would enqueue for these items -- the call's own planner,
+ * addresses are numbers, nothing is dereferenced.  One record per launch in stream order (4-byte pixels first; then forward before
+ * inverse, plain before decorrelate, layout 0, 1, 2).  Returns the number of launches (records beyond `cap` are counted, not
+ * written); 0 for count == 0; -1 for a batch the call refuses (dxtlt_last_error() says why).  *table_bytes_out: the bytes of the
+ * ONE staged buffer that holds every launch's entries (32 bytes per non-empty item) and workgroup index. */
+typedef struct DxtltDebugPixelBatchLaunch {
+    uint8_t pixel_bytes, inverse, decorrelate, layout;
+    uint32_t items;          /* non-empty items of the class = table entries */
+    uint32_t workgroups;     /* tiles of 4096 pixels */
+    uint32_t wide;           /* 1 = 16-bit deltas in the workgroup index (dxtlt_debug_plan_batch, dxtlt_gfx950.h) */
+    uint64_t table_offset;   /* where the launch's tables start in the staged buffer (a multiple of 16) ... */
+    uint64_t table_bytes;    /* ... and their bytes */
+} DxtltDebugPixelBatchLaunch;
+int32_t dxtlt_debug_plan_pixels_batch(const DxtltPixelBatchItem *items, size_t count, DxtltDebugPixelBatchLaunch *launches_out, size_t cap,
+                                      uint64_t *table_bytes_out);
+
+/* dxtlt_transform_pixels_batch_auto_device: dxtlt_transform_pixels_auto_device for every item of a batch -- the same six candidates
+ * in the same order, each candidate's whole output one section of the entropy estimator, strict `<` from UINT64_MAX; the same
+ * choice, totals and output bytes per item -- with ONE wait for `hip_stream` and a launch count that does not grow with the number
+ * of items.  Per chunk of the batch one candidate launch per pixel_bytes present (at most two; a d_input at any alignment is read
+ * once for its five candidates, into this thread's candidate arena) and ONE estimator launch over all six sections of all its
+ * items; all counters come back in one copy; the pick is made on the host and written into the items' result fields before the call
+ * returns; the winners go out through dxtlt_transform_pixels_batch_device's planner and kernels (at most 12 launches), enqueued
+ * and not waited for: they read the d_inputs only, so when the call returns nothing in flight touches the arena or the counters.
+ * An empty item keeps (decorrelate, PLANAR_DELTA) and nothing is written for it.
+ *
+ * Every item owns a 16-byte aligned slice of 5 * len bytes of the arena; a chunk is closed before the item that would push its
+ * slices past DXTLT_BATCH_AUTO_ARENA_CAP (dxtlt_estimator.h; the test hook dxtlt_debug_batch_auto_arena_cap governs this call
+ * too), and an item whose slice alone is larger is a chunk by itself.  The stream orders the reuse of the arena between chunks.
+ *
+ * Refused before anything is enqueued and with the result fields untouched: everything dxtlt_transform_pixels_batch_device
+ * refuses (a d_output may overlap no input or output of the batch); a capturing stream (DXTLT_E_INVALID_ARGUMENT: the call reads
+ * its estimates back and waits); a batch with 2^24 tiles or more of one pixel_bytes, whichever settings would win.  On every
+ * failure exit the stream is drained before the arena can be reused. */
+typedef struct DxtltPixelBatchAutoItem {
+    const void *d_input;
+    void *d_output;        /* len bytes, overlapping no input or output of the batch */
+    uint64_t len;
+    uint8_t pixel_bytes;
+    /* results, written before the call returns */
+    uint8_t decorrelate;
+    uint8_t layout;
+    uint8_t reserved[5];
+} DxtltPixelBatchAutoItem;
+int32_t dxtlt_transform_pixels_batch_auto_device(DxtltPixelBatchAutoItem *items, size_t count, void *hip_stream);
+
+/* Test hook, no device needed: the plan of dxtlt_transform_pixels_batch_auto_device for these items (nothing is dereferenced).
+ * items_out[i]: the item's chunk, its slice of the arena and its six sections in candidate order -- sections 0..4 at
+ * arena_offset + i * len of the arena (in_arena = 1), section 5 the item's d_input itself (in_arena = 0, offset 0); counter =
+ * 6 * item + section.  chunks_out[c] (at most chunk_capacity are written; *out_chunks receives how many there are).  Returns
+ * DXTLT_OK or the status the call would return before any device work. */
+typedef struct DxtltDebugPixelBatchAutoSection {
+    uint64_t offset;
+    uint64_t len;
+    uint32_t counter;
+    uint32_t in_arena;
+} DxtltDebugPixelBatchAutoSection;
+typedef struct DxtltDebugPixelBatchAutoPlanItem {
+    uint32_t chunk;
+    uint32_t reserved;
+    uint64_t arena_offset;   /* a multiple of 16 */
+    uint64_t arena_bytes;    /* 5 * len */
+    DxtltDebugPixelBatchAutoSection sections[6];
+} DxtltDebugPixelBatchAutoPlanItem;
+typedef struct DxtltDebugPixelBatchAutoPlanChunk {
+    uint64_t first_item, item_count;
+    uint64_t arena_bytes;
+    uint32_t candidate_launches;     /* 0..2: one per pixel_bytes with a non-empty item */
+    uint32_t estimator_workgroups;   /* 32 KiB windows of all six sections of all items */
+} DxtltDebugPixelBatchAutoPlanChunk;
+int32_t dxtlt_debug_plan_pixels_batch_auto(const DxtltPixelBatchAutoItem *items, size_t count, DxtltDebugPixelBatchAutoPlanItem *items_out,
+                                           DxtltDebugPixelBatchAutoPlanChunk *chunks_out, size_t chunk_capacity, size_t *out_chunks);
+
+/* Test hooks, per calling thread, read-only.  last: of this thread's last dxtlt_transform_pixels_batch_auto_device, out[0] the
+ * stream waits, out[1] the chunks, out[2] the candidate launches, out[3] the estimator launches (all 0 after a refused or an
+ * all-empty batch; the winners' launches are not counted).  last_totals: the six totals that call compared for `item`, in candidate
+ * order; returns how many there were (0 for an empty item, an item out of range or a failed call); writes at most cap. */
+void dxtlt_debug_pixels_batch_auto_last(uint64_t out[4]);
+int32_t dxtlt_debug_pixels_batch_auto_last_totals(size_t item, uint64_t *out, int32_t cap);
+/* Bench hooks, per calling thread.  time_phases: anything but 0 = the batched pixel auto calls record HIP events around the
+ * phases of every chunk and around the winners and wait for the winners before they return; last_phase_ms then reports, for the
+ * last such call, the milliseconds summed over its chunks: out[0] the candidate launches, out[1] the estimator launches, and
+ * out[2] the winners' launches. */
+void dxtlt_debug_pixels_batch_auto_time_phases(int32_t on);
+void dxtlt_debug_pixels_batch_auto_last_phase_ms(double out[3]);
+
 #ifdef __cplusplus
 }
 #endif

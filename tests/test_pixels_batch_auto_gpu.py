@@ -1,0 +1,227 @@
+"""dxtlt_transform_pixels_batch_auto_device on the MI355X (csrc/pixel_batch_auto_api.cpp; include/dxtlt_pixels.h) against its CPU
+statement -- tests/pixels_ref.py for the bytes, tests/entropy_ref.py (R.auto) for the six totals and the pick -- and against
+dxtlt_transform_pixels_auto_device on every item alone.  All outputs of a call lie in ONE arena between guard bytes."""
+import ctypes as C
+import threading
+
+import numpy as np
+import pytest
+
+import entropy_ref as R
+import pixels_auto_data as D
+import pixels_batch_util as U
+
+RESIDUES = [0, 1, 8, 15]
+
+
+@pytest.fixture(scope="module")
+def dev():
+    import torch
+
+    return torch.device("cuda:0")
+
+
+@pytest.fixture(scope="module")
+def lib(pkg):
+    return U.load(pkg)
+
+
+_INPUTS = {}
+
+
+def inputs():
+    """[(name, B, flat bytes, input residue)]: slices of the r2-256 mip chain (the first candidate wins) and of random walks (the
+    fourth) at every pixel count, a buffer of zeros (all six totals tie at 0: the first stays), a buffer of 0x7F (the last two tie at 0:
+    the fifth stays) and an empty item, for both pixel sizes"""
+    if not _INPUTS:
+        chain = np.ascontiguousarray(D.data_sets()[2][1])
+        assert chain.shape == (87381, 4)
+        items = []
+        for B in (4, 3):
+            walks = D.random_walks(B, 87381, 11 + B)
+            for k, P in enumerate(U.AUTO_COUNTS):
+                items.append((f"chain {B} {P}", B, np.ascontiguousarray(chain[:P, :B]).reshape(-1), RESIDUES[k % 4]))
+                items.append((f"walks {B} {P}", B, np.ascontiguousarray(walks[:P]).reshape(-1), RESIDUES[(k + 2) % 4]))
+            items.append((f"constant {B}", B, np.zeros(B * 5000, dtype=np.uint8), RESIDUES[B % 4]))
+            items.append((f"grey {B}", B, np.full(B * 5000, 0x7F, dtype=np.uint8), RESIDUES[(B + 1) % 4]))
+            items.append((f"empty {B}", B, np.zeros(0, dtype=np.uint8), 0))
+        _INPUTS["items"] = items
+        _INPUTS["ref"] = [R.auto(flat, B) if flat.size else ([], 0, flat) for _n, B, flat, _r in items]
+    return _INPUTS["items"], _INPUTS["ref"]
+
+
+def test_the_reference_picks_of_the_inputs_have_three_outcomes():
+    """no device: the first candidate alone at the top, the fourth, and a tie of all six that keeps the first"""
+    items, ref = inputs()
+    outcomes = set()
+    for (name, _B, flat, _r), (totals, at, _out) in zip(items, ref):
+        if flat.size:
+            outcomes.add((at, len(set(totals)) == 1))
+        if name.startswith("constant"):
+            assert len(set(totals)) == 1 and at == 0
+        if name.startswith("grey"):
+            assert totals[4] == totals[5] == min(totals) < totals[0] and at == 4
+    assert {(0, False), (3, False), (0, True), (4, False)} <= outcomes
+    assert ref[[n for n, *_ in items].index("chain 4 87381")][1] == 0 and ref[[n for n, *_ in items].index("walks 4 87381")][1] == 3
+    assert {r for *_x, r in items} == set(RESIDUES) and {B for _n, B, _f, _r in items} == {3, 4}
+
+
+def auto_items(arenas, specs):
+    arr = (U.AutoItem * len(specs))()
+    for k, (_name, B, flat, _r) in enumerate(specs):
+        arr[k].d_input, arr[k].d_output = (arenas.in_ptr(k), arenas.out_ptr(k)) if flat.size else (None, None)
+        arr[k].len, arr[k].pixel_bytes, arr[k].decorrelate, arr[k].layout = flat.size, B, 0xEE, 0xEE
+    return arr
+
+
+def totals_of(lib, k):
+    buf = (C.c_uint64 * 8)()
+    n = lib.dxtlt_debug_pixels_batch_auto_last_totals(k, buf, 8)
+    return [int(v) for v in buf[:n]]
+
+
+def last_of(lib):
+    out = (C.c_uint64 * 4)(9, 9, 9, 9)
+    lib.dxtlt_debug_pixels_batch_auto_last(out)
+    return list(out)
+
+
+def estimation_of(lib):
+    a, b = C.c_uint64(99), C.c_uint64(99)
+    lib.dxtlt_debug_auto_last_estimation(C.byref(a), C.byref(b))
+    return a.value, b.value
+
+
+def run_auto(lib, dev, specs, ref, stream=None):
+    """one call over `specs`; results, totals and bytes against the statement; returns (arenas, host arena, [(decorrelate, layout)])"""
+    import torch
+
+    arenas = U.Arenas(dev, [s[2] for s in specs], [s[3] for s in specs], [(3 * k + s[3]) % U.LINE for k, s in enumerate(specs)])
+    arr = auto_items(arenas, specs)
+    rc = lib.dxtlt_transform_pixels_batch_auto_device(arr, len(specs), stream if stream is not None else torch.cuda.current_stream().cuda_stream)
+    assert rc == 0, lib.dxtlt_last_error()
+    totals = [totals_of(lib, k) for k in range(len(specs))]
+    host = arenas.check()
+    choices = []
+    for k, ((name, _B, flat, _r), (want_totals, at, want)) in enumerate(zip(specs, ref)):
+        choices.append((bool(arr[k].decorrelate), int(arr[k].layout)))
+        assert totals[k] == want_totals, name
+        assert choices[k] == R.CANDIDATES[at], name
+        assert np.array_equal(arenas.output(host, k), want), name
+    return arenas, host, choices
+
+
+@pytest.mark.gpu
+def test_results_totals_and_bytes_equal_the_statement_and_the_single_call(lib, dev):
+    import torch
+
+    specs, ref = inputs()
+    arenas, host, choices = run_auto(lib, dev, specs, ref)
+    assert last_of(lib) == [1, 1, 2, 1] and estimation_of(lib) == (0, 0)
+    # every item alone through the single call: the same choice, totals and bytes
+    single = U.Arenas(dev, [s[2] for s in specs], [s[3] for s in specs], [(3 * k + s[3]) % U.LINE for k, s in enumerate(specs)])
+    stream = torch.cuda.current_stream().cuda_stream
+    for k, (name, B, flat, _r) in enumerate(specs):
+        dec, lay = C.c_bool(), C.c_uint8(9)
+        ptrs = (single.in_ptr(k), single.out_ptr(k)) if flat.size else (None, None)
+        assert lib.dxtlt_transform_pixels_auto_device(*ptrs, flat.size, B, stream, C.byref(dec), C.byref(lay)) == 0, lib.dxtlt_last_error()
+        buf = (C.c_uint64 * 8)()
+        n = lib.dxtlt_debug_pixels_auto_last_totals(buf, 8)
+        assert [int(v) for v in buf[:n]] == ref[k][0], name
+        assert (dec.value, lay.value) == choices[k], name
+    assert np.array_equal(single.check(), host)
+
+
+@pytest.mark.gpu
+def test_one_wait_and_the_same_launches_for_1_and_200_items(lib, dev):
+    specs, ref = inputs()
+    chain = specs[[s[0] for s in specs].index("chain 4 87381")][2]
+    one = [("one", 4, chain[:4 * 4097], 8)]
+    many = [(f"slice {k}", 4, chain[4 * 300 * k:4 * (300 * k + 200 + 19 * (k % 50))], RESIDUES[k % 4]) for k in range(200)]
+    counts = []
+    for batch in (one, many):
+        run_auto(lib, dev, batch, [R.auto(s[2], 4) for s in batch])
+        counts.append(last_of(lib))
+        assert estimation_of(lib) == (0, 0)                       # no estimation bytes downloaded, no callback
+    assert counts[0] == counts[1] == [1, 1, 1, 1]                 # waits, chunks, candidate launches, estimator launches
+
+
+@pytest.mark.gpu
+def test_chunks_give_the_same_totals_choices_and_bytes(lib, dev):
+    specs, ref = inputs()
+    by_name = {s[0]: k for k, s in enumerate(specs)}
+    small = [by_name[f"{kind} {B} 4097"] for kind in ("chain", "walks") for B in (4, 3)]
+    order = (small * 3) + [by_name["walks 4 87381"]]                  # 12 items of 16 388 or 12 291 bytes, then one of 349 524
+    batch = [specs[k] for k in order]
+    batch_ref = [ref[k] for k in order]
+    _a, whole, whole_choices = run_auto(lib, dev, batch, batch_ref)
+    assert last_of(lib) == [1, 1, 2, 1]
+    # slices of 81 940 and 61 455 bytes, padded to 81 952 and 61 456: four items -- one of each kind -- are 286 816 bytes; the last item's is 1 747 620
+    lib.dxtlt_debug_batch_auto_arena_cap(286_816)
+    try:
+        _a, cut, cut_choices = run_auto(lib, dev, batch, batch_ref)
+        assert last_of(lib) == [1, 4, 3 * 2 + 1, 4]
+    finally:
+        lib.dxtlt_debug_batch_auto_arena_cap(0)
+    assert cut_choices == whole_choices and np.array_equal(cut, whole)
+
+
+@pytest.mark.gpu
+def test_refusals_enqueue_nothing_and_leave_the_results_alone(lib, dev):
+    import torch
+
+    specs, _ref = inputs()
+    batch = [specs[0], specs[1], specs[2]]
+    stream = torch.cuda.current_stream().cuda_stream
+    # an output over the input of another item
+    arenas = U.Arenas(dev, [s[2] for s in batch], [0, 1, 8], [0, 3, 5])
+    arr = auto_items(arenas, batch)
+    arr[2].d_output = arenas.in_ptr(0) + 1
+    assert lib.dxtlt_transform_pixels_batch_auto_device(arr, 3, stream) == 2 and b"overlaps" in lib.dxtlt_last_error()
+    assert [(a.decorrelate, a.layout) for a in arr] == [(0xEE, 0xEE)] * 3 and last_of(lib) == [0, 0, 0, 0]
+    arenas.check(written=())
+    # a capturing stream
+    arr = auto_items(arenas, batch)
+    x = torch.arange(400, dtype=torch.uint8, device=dev)
+    y = torch.zeros_like(x)
+    assert lib.dxtlt_transform_pixels_device(x.data_ptr(), y.data_ptr(), 400, 4, False, 0, stream) == 0      # module load outside the capture
+    torch.cuda.synchronize()
+    y.zero_()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        s = torch.cuda.current_stream().cuda_stream
+        rc = lib.dxtlt_transform_pixels_batch_auto_device(arr, 3, s)
+        error = lib.dxtlt_last_error()
+        marker = lib.dxtlt_transform_pixels_device(x.data_ptr(), y.data_ptr(), 400, 4, False, 0, s)          # capturable
+    assert rc == 2 and b"capturable" in error and marker == 0
+    assert [(a.decorrelate, a.layout) for a in arr] == [(0xEE, 0xEE)] * 3 and last_of(lib) == [0, 0, 0, 0]
+    graph.replay()                                                                                        # the capture is still alive
+    torch.cuda.synchronize()
+    assert torch.equal(x, y)
+    arenas.check(written=())
+
+
+@pytest.mark.gpu
+def test_two_threads_with_their_own_streams(lib, dev):
+    import torch
+
+    specs, ref = inputs()
+    halves = [(specs[0::2], ref[0::2]), (specs[1::2], ref[1::2])]
+    errors = []
+
+    def work(half):
+        try:
+            torch.cuda.set_device(dev)
+            stream = torch.cuda.Stream(device=dev)
+            with torch.cuda.stream(stream):
+                for _ in range(2):
+                    run_auto(lib, dev, half[0], half[1], stream.cuda_stream)
+        except BaseException as e:          # carried to the test's thread
+            errors.append(e)
+
+    threads = [threading.Thread(target=work, args=(h,)) for h in halves]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    assert not errors, errors
