@@ -20,7 +20,27 @@ struct AutoSections {
     uint64_t bytes;
     uint64_t off[10], len[10];
 };
-AutoSections auto_sections(Format fmt, bool all_variants, uint64_t blocks);
+// (this and batch_auto_workgroups are defined here, inline and pure: the planner that calls them also runs stand-alone under the
+// host sanitizers)
+inline AutoSections auto_sections(Format fmt, bool all_variants, uint64_t blocks)
+{
+    AutoSections s{};
+    auto add = [&](int sections, uint64_t bytes_per_block) {
+        for (int k = 0; k < sections; ++k) {
+            s.off[s.count] = s.bytes;
+            s.len[s.count++] = bytes_per_block * blocks;
+            s.bytes += bytes_per_block * blocks;
+        }
+    };
+    if (fmt == kBc4 || fmt == kBc5)
+        add(fmt == kBc5 ? 4 : 2, 2);
+    else {
+        if (fmt == kBc3)
+            add(2, 2);
+        add(all_variants ? 8 : 4, 4);
+    }
+    return s;
+}
 // One read of d_in (the AoS blocks, 16-byte aligned) -> every section of BC1 - BC3, at d_arena.  Enqueues on `stream`.
 hipError_t launch_auto_candidates(Format fmt, bool all_variants, const void* d_in, void* d_arena, uint64_t blocks,
                                   hipStream_t stream);
@@ -37,7 +57,11 @@ struct BatchAutoEntry {
 static_assert(sizeof(BatchAutoEntry) == 32, "BatchAutoEntry layout is shared between host and device");
 
 // workgroups a buffer owns in the launch: one lane per 16-byte vector, the odd last block of BC1 / BC4 included
-uint32_t batch_auto_workgroups(Format fmt, uint64_t blocks);
+inline uint32_t batch_auto_workgroups(Format fmt, uint64_t blocks)
+{
+    const uint64_t lanes = fmt == kBc1 || fmt == kBc4 ? (blocks + 1) / 2 : blocks;
+    return (uint32_t)((lanes + 255) / 256);
+}
 // One read of every buffer of the table (device memory, `entries` entries, total_wgs = workgroups of all of them) -> every
 // section, at d_arena + arena_off.  fmt 1..5; all_variants is ignored for BC4 / BC5.  Enqueues on `stream`.
 hipError_t launch_batch_auto_candidates(Format fmt, bool all_variants, const BatchAutoEntry* d_table, uint32_t entries,

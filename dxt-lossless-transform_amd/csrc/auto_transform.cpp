@@ -475,26 +475,6 @@ int dxtlt_host::auto_candidate_order(int32_t format, bool use_all, AutoChoice* o
     return o.count;
 }
 
-dxtlt::AutoSections dxtlt::auto_sections(Format fmt, bool all_variants, uint64_t blocks)
-{
-    AutoSections s{};
-    auto add = [&](int sections, uint64_t bytes_per_block) {
-        for (int k = 0; k < sections; ++k) {
-            s.off[s.count] = s.bytes;
-            s.len[s.count++] = bytes_per_block * blocks;
-            s.bytes += bytes_per_block * blocks;
-        }
-    };
-    if (fmt == kBc4 || fmt == kBc5)
-        add(fmt == kBc5 ? 4 : 2, 2);
-    else {
-        if (fmt == kBc3)
-            add(2, 2);
-        add(all_variants ? 8 : 4, 4);
-    }
-    return s;
-}
-
 int dxtlt_host::auto_pick(int32_t format, bool use_all, bool per_candidate, const uint64_t* sizes, uint64_t* total)
 {
     const Order o = candidates_of(format, use_all);

@@ -86,12 +86,6 @@ batch_auto_candidates_kernel(const BatchAutoEntry* __restrict__ tab, uint32_t en
 
 }  // namespace
 
-uint32_t batch_auto_workgroups(Format fmt, uint64_t blocks)
-{
-    const uint64_t lanes = fmt == kBc1 || fmt == kBc4 ? (blocks + 1) / 2 : blocks;
-    return (uint32_t)((lanes + 255) / 256);
-}
-
 hipError_t launch_batch_auto_candidates(Format fmt, bool all_variants, const BatchAutoEntry* d_table, uint32_t entries,
                                         uint32_t total_wgs, void* d_arena, hipStream_t stream)
 {

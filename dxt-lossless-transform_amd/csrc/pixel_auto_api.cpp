@@ -25,31 +25,14 @@ namespace {
 
 using namespace dxtlt_host;
 
-struct PixelCandidate {
-    bool decorrelate;
-    uint8_t layout;
-};
-constexpr int kCandidates = 6;
-constexpr PixelCandidate kOrder[kCandidates] = {{true, 2}, {true, 1}, {true, 0}, {false, 2}, {false, 1}, {false, 0}};
+constexpr int kCandidates = dxtlt::pixels::kAutoCandidates;   // in the order of kAutoOrder (pixel_launch.h)
+constexpr auto& kOrder = dxtlt::pixels::kAutoOrder;
 constexpr int kIdentity = 5;   // (false, INTERLEAVED): the input itself, never written for an estimate
 
 thread_local uint64_t t_totals[kCandidates];
 thread_local int t_total_count = 0;   // dxtlt_debug_pixels_auto_last_totals
 thread_local bool t_time_phases = false;
 thread_local double t_phase_ms[3] = {0, 0, 0};
-
-// the first smallest total: from the first candidate with best = UINT64_MAX, replaced on strict `<`
-int pick_of(const uint64_t* totals)
-{
-    int pick = 0;
-    uint64_t best = UINT64_MAX;
-    for (int i = 0; i < kCandidates; ++i)
-        if (totals[i] < best) {
-            best = totals[i];
-            pick = i;
-        }
-    return pick;
-}
 
 int32_t check_arguments(int32_t pixel_bytes, size_t len)
 {
@@ -136,7 +119,7 @@ int32_t auto_on_device(int B, const void* d_in, void* d_out, size_t len, hipStre
     uint64_t totals[kCandidates];
     if (int32_t rc = estimate_read_back(kCandidates, st, totals))
         return rc;
-    *pick = pick_of(totals);
+    *pick = dxtlt::pixels::auto_pick_of(totals);
     if (*pick != last)
         if (int32_t rc = transform_candidate(B, *pick, d_in, d_out, pixels, st))
             return rc;

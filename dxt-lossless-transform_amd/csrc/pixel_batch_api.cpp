@@ -45,7 +45,7 @@ int32_t dxtlt_host::pixel_batch_enqueue(const pixel_batch::Plan& plan, hipStream
 extern "C" int32_t dxtlt_transform_pixels_batch_device(const DxtltPixelBatchItem* items, size_t count, void* hip_stream)
 {
     pb::Plan plan;
-    if (pb::Defect d = pb::plan_call(items, count, plan); d.code != kOk)
+    if (Defect d = pb::plan_call(items, count, plan); d.code != kOk)
         return fail(d.code, d.what);
     if (plan.launches.empty())
         return kOk;   // no item, or empty items only: nothing to enqueue, no device needed
@@ -65,7 +65,7 @@ extern "C" int32_t dxtlt_debug_plan_pixels_batch(const DxtltPixelBatchItem* item
     if (table_bytes_out)
         *table_bytes_out = 0;
     pb::Plan plan;
-    if (pb::Defect d = pb::plan_call(items, count, plan); d.code != kOk) {
+    if (Defect d = pb::plan_call(items, count, plan); d.code != kOk) {
         (void)fail(d.code, d.what);
         return -1;
     }

@@ -2,7 +2,8 @@
 // dxtlt_transform_pixels_batch_device; pixel_batch_auto_api.cpp: dxtlt_transform_pixels_batch_auto_device), pure host arithmetic:
 // they check a whole batch and say what the call enqueues without touching a device or dereferencing an address.  The calls and
 // the test hooks (dxtlt_debug_plan_pixels_batch, dxtlt_debug_plan_pixels_batch_auto) run these very functions; being pure, they
-// also run stand-alone under the host sanitizers (tests/cpp/pixel_batch_plan_main.cpp).
+// also run stand-alone under the host sanitizers (tests/cpp/pixel_batch_plan_main.cpp).  What the auto planner shares with the block
+// formats' (batch_auto_plan.h) -- the overlap rule, the chunk packer, the estimator's section table -- is batch_auto_common.h.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -12,6 +13,7 @@
 #include <vector>
 
 #include "../../include/dxtlt_pixels.h"
+#include "batch_auto_common.h"
 #include "bcn_launch.h"
 #include "entropy_launch.h"
 #include "host_common.h"
@@ -22,12 +24,6 @@ namespace dxtlt_host {
 namespace pixel_batch {
 
 using dxtlt::pixels::PixelBatchEntry;
-
-// why a batch is refused: the status and the text for dxtlt_last_error() (code kOk: not refused)
-struct Defect {
-    int32_t code = kOk;
-    const char* what = nullptr;
-};
 
 // a buffer as both calls' checks see it
 struct Buffer {
@@ -41,15 +37,10 @@ struct Buffer {
 inline uint64_t tiles_of(uint64_t pixels) { return (pixels + dxtlt::pixels::kTile - 1) / dxtlt::pixels::kTile; }
 
 // The checks of both calls, the whole batch before anything else happens: per item, in this order, pixel_bytes, layout, NULL
-// buffers, the length, the 64 GiB limit; then the rule that a d_output overlaps no other output and no input (inputs may overlap
-// one another): in order of their first bytes, a span overlaps an earlier one when it begins before that one ends.
+// buffers, the length, the 64 GiB limit; then the rule that a d_output overlaps no other output and no input (OverlapCheck).
 inline Defect check_buffers(const Buffer* b, size_t count)
 {
-    struct Span {
-        uintptr_t begin, end;
-        bool output;
-    };
-    std::vector<Span> spans;
+    OverlapCheck spans;
     for (size_t i = 0; i < count; ++i) {
         if (b[i].pixel_bytes != 3 && b[i].pixel_bytes != 4)
             return {kInvalidArgument, "pixel batch item: pixel_bytes must be 4 (RGBA8888, BGRA8888) or 3 (BGR888)"};
@@ -61,21 +52,10 @@ inline Defect check_buffers(const Buffer* b, size_t count)
             return {kInvalidLength, "pixel batch item: len is not a multiple of pixel_bytes"};
         if (b[i].len >= (uint64_t(64) << 30))
             return {kInvalidArgument, "pixel batch item of 64 GiB or more: use the single-buffer entry point"};
-        if (b[i].len > 0) {
-            const uintptr_t in = reinterpret_cast<uintptr_t>(b[i].in), out = reinterpret_cast<uintptr_t>(b[i].out);
-            spans.push_back({in, in + (uintptr_t)b[i].len, false});
-            spans.push_back({out, out + (uintptr_t)b[i].len, true});
-        }
+        spans.add(b[i].in, b[i].out, b[i].len);
     }
-    std::sort(spans.begin(), spans.end(), [](const Span& x, const Span& y) { return x.begin < y.begin; });
-    uintptr_t end_any = 0, end_output = 0;
-    for (const Span& s : spans) {
-        if (s.begin < (s.output ? end_any : end_output))
-            return {kInvalidArgument, "pixel batch item: a d_output overlaps another buffer of the batch"};
-        end_any = std::max(end_any, s.end);
-        if (s.output)
-            end_output = std::max(end_output, s.end);
-    }
+    if (spans.an_output_overlaps())
+        return {kInvalidArgument, "pixel batch item: a d_output overlaps another buffer of the batch"};
     return {};
 }
 
@@ -161,30 +141,25 @@ inline Defect plan_call(const DxtltPixelBatchItem* items, size_t count, Plan& pl
 }
 
 // ---- dxtlt_transform_pixels_batch_auto_device -----------------------------------------------------------------------------------
-constexpr int kCandidates = 6;   // pixel_auto_api.cpp's order; the sixth is the input itself
+constexpr int kCandidates = dxtlt::pixels::kAutoCandidates;   // in kAutoOrder (pixel_launch.h); the sixth is the input itself
+static_assert(dxtlt::kEntropyWindow == dxtlt::kEstimatorWindow, "the shared section table counts the gram estimator's windows");
 
-struct AutoItem {
-    uint32_t chunk = 0;
+struct AutoItem : PackedItem {   // slice_off: candidate i < 5 at slice_off + i * len; first_counter: 6 * item, counter i is candidate i's
     uint64_t pixels = 0, len = 0;
-    uint64_t slice_off = 0, slice_bytes = 0;   // inside the arena: 5 * len, candidate i < 5 at slice_off + i * len
-    uint64_t first_counter = 0;                // 6 * item; counter i is candidate i's
+    uint64_t slice_bytes = 0;    // inside the arena: 5 * len
 };
 
-struct AutoChunk {
-    size_t first = 0, count = 0;
-    uint64_t arena_bytes = 0;
+struct AutoChunk : PackedChunk {
     uint32_t entries[2] = {0, 0}, wgs[2] = {0, 0};   // the candidate launch of 4-byte ([0]) and of 3-byte ([1]) pixels
     bool wide[2] = {false, false};
     size_t at[2] = {0, 0}, entry_bytes[2] = {0, 0};  // in the call's table: entries, then the workgroup index
-    uint64_t estimator_wgs = 0;
-    uint32_t estimator_entries = 0;
-    size_t sections_at = 0;                          // in the call's table: the estimator's section table
     uint32_t candidate_launches() const { return (entries[0] != 0) + (entries[1] != 0); }
 };
 
 struct AutoPlan {
     std::vector<AutoItem> items;
     std::vector<AutoChunk> chunks;
+    bool any = false;           // a non-empty item
     uint64_t counters = 0;
     uint64_t arena_bytes = 0;   // the largest chunk
     size_t table_bytes = 0;     // ONE table for the whole call
@@ -215,36 +190,25 @@ inline Defect plan_auto_call(const DxtltPixelBatchAutoItem* items, size_t count,
             return {kInvalidArgument, "pixel batch auto: too large for one launch (2^24 tiles or more of one pixel_bytes)"};
 
     plan.items.assign(count, AutoItem{});
-    AutoChunk cur;
+    ChunkPacker<AutoChunk> pack{plan.chunks, cap};
     for (size_t i = 0; i < count; ++i) {
         AutoItem& p = plan.items[i];
         p.len = items[i].len;
         p.pixels = p.len / items[i].pixel_bytes;
         p.slice_bytes = 5 * p.len;
-        const uint64_t padded = (p.slice_bytes + 15) & ~uint64_t(15);
-        // a chunk is closed BEFORE the item that would push it past the cap: it holds at most the cap, or one larger item
-        if (cur.count > 0 && cur.arena_bytes + padded > cap) {
-            plan.chunks.push_back(cur);
-            cur = AutoChunk{};
-            cur.first = i;
-        }
-        p.chunk = (uint32_t)plan.chunks.size();
-        p.slice_off = cur.arena_bytes;
-        p.first_counter = plan.counters;
-        plan.counters += kCandidates;
-        cur.arena_bytes += padded;
-        cur.count++;
+        AutoChunk& cur = pack.add(p.slice_bytes, kCandidates, p);
         if (p.len != 0) {
             const int b = items[i].pixel_bytes == 4 ? 0 : 1;
+            plan.any = true;
             cur.entries[b]++;
             cur.wgs[b] += (uint32_t)tiles_of(p.pixels);   // (below a launch's limit: checked for the whole batch above)
-            cur.estimator_wgs += kCandidates * ((p.len + dxtlt::kEntropyWindow - 1) / dxtlt::kEntropyWindow);
-            cur.estimator_entries += kCandidates;
+            for (int k = 0; k < kCandidates; ++k)
+                cur.count_section(p.len);
         }
     }
-    plan.chunks.push_back(cur);
+    plan.counters = pack.counters;
+    plan.arena_bytes = pack.arena_bytes;
     for (AutoChunk& c : plan.chunks) {
-        plan.arena_bytes = std::max(plan.arena_bytes, c.arena_bytes);
         if (c.estimator_wgs > 0x7FFFFFFFull)
             return {kInvalidArgument, "pixel batch auto: a chunk of more than 2^31 - 1 estimator windows"};
         for (int b = 0; b < 2; ++b) {
@@ -253,8 +217,7 @@ inline Defect plan_auto_call(const DxtltPixelBatchAutoItem* items, size_t count,
             if (c.entries[b] != 0)
                 plan.table_bytes += c.entry_bytes[b] + dxtlt::batch_index_bytes(c.wgs[b]);
         }
-        c.sections_at = plan.table_bytes;
-        plan.table_bytes += ((size_t)c.estimator_entries * sizeof(dxtlt::EstimateTableEntry) + 15) & ~size_t(15);
+        plan.table_bytes = c.place_sections(plan.table_bytes);
     }
     if (plan.table_bytes > (size_t(1) << 31))
         return {kInvalidArgument, "pixel batch auto: too many items for one call (a table of more than 2 GiB)"};
@@ -288,14 +251,12 @@ inline void fill_auto_tables(AutoPlan& plan, const DxtltPixelBatchAutoItem* item
             }
             c.wide[b] = dxtlt::build_batch_index(spans.data(), spans.size(), c.wgs[b], host + c.at[b] + c.entry_bytes[b]);
         }
-        dxtlt::EstimateTableEntry* s = reinterpret_cast<dxtlt::EstimateTableEntry*>(host + c.sections_at);
-        uint32_t wgs = 0;
+        SectionWriter sections{reinterpret_cast<dxtlt::EstimateTableEntry*>(host + c.sections_at)};
         for (size_t i = c.first; i < c.first + c.count; ++i) {
             const AutoItem& p = plan.items[i];
             for (int k = 0; k < kCandidates && p.len != 0; ++k) {
-                wgs += (uint32_t)((p.len + dxtlt::kEntropyWindow - 1) / dxtlt::kEntropyWindow);
                 const uint8_t* base = k == kCandidates - 1 ? static_cast<const uint8_t*>(items[i].d_input) : arena + p.slice_off + (uint64_t)k * p.len;
-                *s++ = dxtlt::EstimateTableEntry{base, p.len, wgs, (uint32_t)(p.first_counter + (uint64_t)k)};
+                sections.add(base, p.len, p.first_counter + (uint64_t)k);
             }
         }
     }

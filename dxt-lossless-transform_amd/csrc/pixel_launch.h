@@ -22,5 +22,26 @@ hipError_t launch_range(int pixel_bytes, bool inverse, bool decorrelate, int lay
 // (plain, PLANAR_DELTA) and (plain, PLANAR), in this order, at arena + i * total * pixel_bytes.  Enqueues on `stream`.
 hipError_t launch_auto_candidates(int pixel_bytes, const void* src, void* arena, uint64_t total, hipStream_t stream);
 
+// The six candidates of the pixel auto transforms (include/dxtlt_pixels.h, "the auto transform") in the order they are compared:
+// the five above, then the input itself.
+struct AutoCandidate {
+    bool decorrelate;
+    uint8_t layout;
+};
+constexpr int kAutoCandidates = 6;
+constexpr AutoCandidate kAutoOrder[kAutoCandidates] = {{true, 2}, {true, 1}, {true, 0}, {false, 2}, {false, 1}, {false, 0}};
+// the first smallest total: from the first candidate with best = UINT64_MAX, replaced on strict `<`
+inline int auto_pick_of(const uint64_t* totals)
+{
+    int pick = 0;
+    uint64_t best = UINT64_MAX;
+    for (int i = 0; i < kAutoCandidates; ++i)
+        if (totals[i] < best) {
+            best = totals[i];
+            pick = i;
+        }
+    return pick;
+}
+
 }  // namespace pixels
 }  // namespace dxtlt

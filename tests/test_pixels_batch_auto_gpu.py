@@ -201,6 +201,82 @@ def test_refusals_enqueue_nothing_and_leave_the_results_alone(lib, dev):
     arenas.check(written=())
 
 
+def on_a_fresh_thread(fn):
+    """fn() on a thread of its own -- no table staging, counters or arena yet -- and its result or its exception here"""
+    box = []
+
+    def work():
+        try:
+            box.append((True, fn()))
+        except BaseException as e:          # carried to the test's thread
+            box.append((False, e))
+
+    t = threading.Thread(target=work)
+    t.start()
+    t.join()
+    if not box[0][0]:
+        raise box[0][1]
+    return box[0][1]
+
+
+@pytest.mark.gpu
+def test_the_block_and_the_pixel_call_share_one_threads_buffers(lib, dev, oracle, pkg):
+    """dxtlt_transform_batch_auto_device and this call stage their tables and read their counters back through the SAME per-thread
+    buffers (csrc/batch_auto_common.h): block, pixel, block, pixel on one thread and one stream, every batch in three chunks or
+    more, give what each batch gives alone on a fresh thread -- choices, totals, bytes and counts -- and what the CPU statements say."""
+    import torch
+
+    import batch_auto_util as BU
+    import test_batch_auto_gpu as BG
+
+    block_lib = BU.load(pkg)
+    cap = 20_000
+    # the 256-lane workgroup edges with two BC1 / BC4 blocks per lane, and an empty item per kind
+    kinds = [("bc1", True), ("bc3", False), ("bc4", False), ("bc5", False)]
+    block_specs = [(fmt, blocks, (i + j) % 4, 60 + i, use_all) for i, (fmt, use_all) in enumerate(kinds)
+                   for j, blocks in enumerate((0, 1, 2, 3, 511, 512, 513))]
+    blocks = BG.Batch(dev, block_specs, oracle)
+    specs, ref = inputs()
+    by_name = {s[0]: k for k, s in enumerate(specs)}
+    # (the empty item in front: behind an item larger than the cap it would be a chunk without an estimator launch)
+    first = [by_name["empty 4"]] + [by_name[f"chain {B} {P}"] for B in (4, 3) for P in U.AUTO_COUNTS[:3]]
+    second = ([by_name["empty 3"]] + [by_name[f"{kind} {B} {P}"] for kind in ("chain", "walks") for B in (4, 3) for P in U.AUTO_COUNTS[:4]]) * 3
+    # the second pixel batch outgrows the counters the block batch left behind (BatchAutoBuffers::reserve: half as many again and
+    # 64), and with them its tables: 144 bytes of sections per item against 120 sections and 24 entries in all
+    block_counters = sum(len(BU.shown_lengths(s[0], s[1] * BU.BLOCK[s[0]], s[4])) for s in block_specs)
+    assert len(first) < len(second) and 6 * len(first) < block_counters and 6 * len(second) > block_counters + block_counters // 2 + 64
+
+    def run_blocks(stream):
+        blocks.reset()
+        assert blocks.call(block_lib, stream.cuda_stream) == 0, block_lib.dxtlt_last_error()
+        torch.cuda.synchronize()
+        got = blocks.check_against_cpu(block_lib)
+        counts = BG.last(block_lib)
+        assert counts[0] == 1 and counts[1] >= 3 and counts[3] == counts[1], counts
+        return [(c, o.tobytes(), t) for c, o, t in got], counts
+
+    def run_pixels(which, stream):
+        batch = [specs[k] for k in which]
+        _a, host, choices = run_auto(lib, dev, batch, [ref[k] for k in which], stream.cuda_stream)
+        counts = last_of(lib)
+        assert counts[0] == 1 and counts[1] >= 3 and counts[3] == counts[1] and estimation_of(lib) == (0, 0), counts
+        return host.tobytes(), choices, [totals_of(lib, k) for k in range(len(batch))], counts
+
+    def on_one_thread(*runs):
+        def work():
+            torch.cuda.set_device(dev)
+            stream = torch.cuda.Stream(device=dev)
+            lib.dxtlt_debug_batch_auto_arena_cap(cap)            # per thread, for both calls
+            with torch.cuda.stream(stream):
+                return [run(stream) for run in runs]
+        return on_a_fresh_thread(work)
+
+    pixels_first, pixels_second = (lambda s: run_pixels(first, s)), (lambda s: run_pixels(second, s))
+    alone = [on_one_thread(run)[0] for run in (run_blocks, pixels_first, pixels_second)]
+    together = on_one_thread(run_blocks, pixels_first, run_blocks, pixels_second)
+    assert together == [alone[0], alone[1], alone[0], alone[2]]
+
+
 @pytest.mark.gpu
 def test_two_threads_with_their_own_streams(lib, dev):
     import torch
