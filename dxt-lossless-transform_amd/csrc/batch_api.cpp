@@ -10,7 +10,8 @@
 // launches batch_kernel (batch_kernels.hip), in which every workgroup looks its buffer up and runs one tile -- aligned, halo
 // or shifted, as the single-buffer call would choose for that buffer -- or the buffer's edge tile.  Asynchronous and ordered
 // like a single call on the caller's stream.  Uncompressed-pixel items (formats 8, 9: include/dxtlt_pixels.h) are taken by the
-// host batch only: checked with the rest there, they go out as one launch each, behind the batches of their chunk.
+// host batch only (dxtlt_transform_batch_host, batch_host_api.cpp, which runs batch_device here on every chunk it has uploaded):
+// checked with the rest there, they go out as one launch each, behind the batches of their chunk.
 //
 // Planning is pure host arithmetic: plan_batch checks the whole batch and says what the call enqueues -- the granule launches, the
 // tile launches, the items that go out alone, every table's place in the staged buffer -- without touching a device or an address;
@@ -19,12 +20,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
-#include <condition_variable>
-#include <cstdlib>
 #include <cstring>
-#include <exception>
-#include <mutex>
-#include <thread>
 #include <vector>
 
 #include "../../include/dxtlt_gfx950.h"
@@ -37,12 +33,6 @@ namespace {
 
 using namespace dxtlt_host;
 using dxtlt::BatchEntry;
-
-// bytes per block (8, 9: per pixel) of a batch item's format (1..9)
-inline uint32_t item_block_bytes(uint8_t format)
-{
-    return is_pixel_format(format) ? (uint32_t)pixel_bytes_of(format) : format == 1 || format == 4 ? 8u : 16u;
-}
 
 // dxtlt_transform_batch_device takes 1..7, as before; dxtlt_transform_batch_host also 8 and 9
 const char* const kDeviceFormatText = "batch item: format must be 1..5 (BC1..BC5), 6 (BC6H) or 7 (BC7; 6 and 7 are this build's own formats; "
@@ -86,11 +76,11 @@ hipError_t dxtlt_host::upload_table(TableSlot* slot, size_t bytes, hipStream_t s
     return dxtlt::launch_table_upload(slot->host_mapped, slot->dev, bytes, stream);
 }
 
-namespace {
+void dxtlt_host::release_batch_thread_tables() { g_ring.release(); }
 
 // The per-item checks of both batch calls, in the order in which defects are reported.  `host_call`: the texts of
 // dxtlt_transform_batch_host, whose items also stay below 4 GiB.  kOk, or the failure as fail() recorded it.
-int32_t batch_item_defect(const DxtltBatchItem& it, int max_format, bool host_call)
+int32_t dxtlt_host::batch_item_defect(const DxtltBatchItem& it, int max_format, bool host_call)
 {
     if (it.format < 1 || it.format > max_format)
         return fail(kInvalidArgument, host_call ? kHostFormatText : kDeviceFormatText);
@@ -106,6 +96,8 @@ int32_t batch_item_defect(const DxtltBatchItem& it, int max_format, bool host_ca
         return fail(kInvalidArgument, "batch item of 4 GiB or more: use the single-buffer entry point");
     return kOk;
 }
+
+namespace {
 
 // the settings a BC1..BC5 item's kernels are instantiated with (BC4 / BC5: no variant, no colour split; BC1 / BC2: no alpha split)
 inline dxtlt::Settings item_settings(const DxtltBatchItem& it)
@@ -296,8 +288,10 @@ void fill_tables(BatchPlan& plan, uint8_t* host)
     }
 }
 
+}  // namespace
+
 // The device batch: planned whole, its tables staged in one slot, then its launches in the plan's order on the caller's stream
-int32_t batch_device(const DxtltBatchItem* items, size_t count, void* hip_stream, bool pixels_allowed)
+int32_t dxtlt_host::batch_device(const DxtltBatchItem* items, size_t count, void* hip_stream, bool pixels_allowed)
 {
     BatchPlan plan;
     if (int32_t rc = plan_batch(items, count, pixels_allowed, plan); rc != kOk)
@@ -346,6 +340,8 @@ int32_t batch_device(const DxtltBatchItem* items, size_t count, void* hip_stream
             return rc;
     return kOk;
 }
+
+namespace {
 
 void* address(uint64_t a) { return reinterpret_cast<void*>(static_cast<uintptr_t>(a)); }
 
@@ -486,391 +482,4 @@ extern "C" int32_t dxtlt_debug_plan_batch_granules(const DxtltBatchItem* items, 
     for (size_t k = 0; k < p.coarse.size() && k < coarse_cap && coarse_out != nullptr; ++k)
         coarse_out[k] = coarse[k];
     return (int32_t)p.coarse.size();
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// dxtlt_transform_batch_host: the same, for HOST buffers -- the reference's actual call pattern: one call per file,
-// host pointers, textures of 0.1-20 MiB (tools/dxt-lossless-transform-cli/src/commands/transform/mod.rs:154-199).
-// Through the single-buffer entry points every texture pays a PCIe round trip of its own (1 MiB: 149 us = 6.6 GiB/s,
-// DESIGN.md section 5).  Here the batch is cut into chunks of about 64 MiB and every chunk takes five steps:
-//     pack      a few host threads copy the chunk's buffers side by side into a PINNED arena
-//     upload    one asynchronous copy of the whole chunk
-//     kernels   one batch launch per (format, direction) present in the chunk
-//     download  one asynchronous copy into a second pinned arena
-//     unpack    host threads copy every result to its caller's buffer
-// with two arenas per direction, so that packing chunk k + 1, moving chunk k and unpacking chunk k - 1 overlap and PCIe
-// runs in both directions at once.  (A first version let several threads issue one small pageable copy per buffer
-// straight from / to the callers' memory: 21 GiB/s at 1 MiB per buffer, 16 at 4 MiB -- the runtime pins pageable memory
-// on the fly above 1 MiB; profiles/r02_d_batch_host.txt.)  Synchronous; every failure exit joins the threads and drains
-// the streams before the arenas are released for reuse.
-// ---------------------------------------------------------------------------------------------------------------
-namespace {
-
-// chunk size and copy threads per direction; DXTLT_BATCH_CHUNK_MIB / DXTLT_BATCH_THREADS override them (experiments)
-size_t env_number(const char* name, size_t fallback)
-{
-    const char* v = std::getenv(name);
-    const unsigned long long x = v ? std::strtoull(v, nullptr, 10) : 0;
-    return x ? (size_t)x : fallback;
-}
-const size_t kHostBatchChunkBytes = env_number("DXTLT_BATCH_CHUNK_MIB", 64) << 20;
-const int kCopyThreads = (int)std::min<size_t>(64, env_number("DXTLT_BATCH_THREADS", 6));
-
-// pinned arenas of the calling thread: two per direction, grow-only
-struct PinnedArenas {
-    void* in[2] = {nullptr, nullptr};
-    void* out[2] = {nullptr, nullptr};
-    size_t cap = 0;
-    ~PinnedArenas() { release(); }
-    void release()
-    {
-        for (int i = 0; i < 2; ++i) {
-            if (in[i]) (void)hipHostFree(in[i]);
-            if (out[i]) (void)hipHostFree(out[i]);
-            in[i] = out[i] = nullptr;
-        }
-        cap = 0;
-    }
-    hipError_t reserve(size_t bytes)
-    {
-        if (bytes <= cap)
-            return hipSuccess;
-        release();
-        for (int i = 0; i < 2; ++i) {
-            hipError_t e = hipHostMalloc(&in[i], bytes, hipHostMallocDefault);
-            if (e == hipSuccess)
-                e = hipHostMalloc(&out[i], bytes, hipHostMallocDefault);
-            if (e != hipSuccess) {
-                release();
-                return e;
-            }
-        }
-        cap = bytes;
-        return hipSuccess;
-    }
-};
-thread_local PinnedArenas g_pinned;
-
-struct HostBatchShared {
-    std::mutex m;
-    std::condition_variable cv;
-    std::vector<int> packed;     // per chunk: packer threads that have finished it
-    std::vector<int> unpacked;   // per chunk: unpacker threads that have finished it
-    int uploaded_recorded = 0;   // chunks whose upload event has been recorded
-    int kernels_issued = 0;      // chunks whose upload and kernels have been enqueued (ev_kernels recorded)
-    int enqueued = 0;            // chunks whose download has been enqueued too (ev_downloaded recorded)
-    bool failed = false;
-    hipError_t error = hipSuccess;
-};
-
-}  // namespace
-
-void dxtlt_host::release_batch_thread_tables()
-{
-    g_ring.release();
-    g_pinned.release();
-}
-
-extern "C" int32_t dxtlt_transform_batch_host(const DxtltBatchItem* items, size_t count)
-{
-    if (count == 0)
-        return kOk;
-    if (items == nullptr)
-        return fail(kInvalidArgument, "NULL item array with count > 0");
-    uint64_t total = 0;
-    for (size_t i = 0; i < count; ++i) {
-        if (int32_t rc = batch_item_defect(items[i], 9, true); rc != kOk)
-            return rc;
-        total += (items[i].len + 255) & ~uint64_t(255);
-    }
-    if (total == 0)
-        return kOk;
-
-    // Items of two chunks or more do not belong in a chunk: the arenas (four pinned ones and two device slots per
-    // direction, all of the largest chunk's size) would grow to the item's size and the item would move as one unpipelined
-    // upload, kernel, download.  They go through the single-buffer host entry points instead, which run their own chunked
-    // pipeline from 96 MiB up; what is left keeps every arena below 3 x the chunk size.
-    const uint64_t big_item = 2 * (uint64_t)kHostBatchChunkBytes;
-    std::vector<DxtltBatchItem> small;
-    small.reserve(count);
-    for (size_t i = 0; i < count; ++i) {
-        const DxtltBatchItem& it = items[i];
-        if (it.len < big_item) {
-            small.push_back(it);
-            continue;
-        }
-        int32_t rc;
-        if (is_pixel_format(it.format))
-            rc = pixel_host_call(pixel_bytes_of(it.format), it.inverse != 0, static_cast<const uint8_t*>(it.d_input),
-                                 static_cast<uint8_t*>(it.d_output), it.len, pixel_decorrelate_of(it.decorrelation_mode),
-                                 pixel_layout_of(it.split_alpha_endpoints != 0, it.split_colour_endpoints != 0));
-        else if (dxtlt::granule::is_granule_format(it.format))
-            rc = dxtlt_host::granule_host_call(it.format, it.inverse != 0, static_cast<const uint8_t*>(it.d_input),
-                                               static_cast<uint8_t*>(it.d_output), it.len);
-        else
-            rc = dxtlt_host::transform(it.format, it.inverse != 0, static_cast<const uint8_t*>(it.d_input),
-                                       static_cast<uint8_t*>(it.d_output), it.len, it.decorrelation_mode,
-                                       dxtlt::format_has_alpha_split(it.format) && it.split_alpha_endpoints, it.split_colour_endpoints != 0);
-        if (rc != kOk)
-            return rc;
-    }
-    if (small.empty())
-        return kOk;
-    items = small.data();
-    count = small.size();
-
-    // chunks, and every item's 256-byte aligned slot inside its chunk (the same offset in all four arenas and on the device)
-    std::vector<uint64_t> slot(count);
-    std::vector<size_t> chunk_first;   // first item of every chunk, plus the end
-    std::vector<uint64_t> chunk_bytes;
-    {
-        uint64_t in_chunk = 0;
-        chunk_first.push_back(0);
-        for (size_t i = 0; i < count; ++i) {
-            const uint64_t padded = (items[i].len + 255) & ~uint64_t(255);
-            // a chunk is closed BEFORE the item that would push it past the cap (so a chunk holds at most the cap, or one
-            // item of less than two chunks): arena_bytes stays bounded whatever the item sizes
-            if (in_chunk > 0 && in_chunk + padded > kHostBatchChunkBytes) {
-                chunk_first.push_back(i);
-                chunk_bytes.push_back(in_chunk);
-                in_chunk = 0;
-            }
-            slot[i] = in_chunk;
-            in_chunk += padded;
-        }
-        chunk_first.push_back(count);
-        chunk_bytes.push_back(in_chunk);
-    }
-    const int nchunks = (int)chunk_bytes.size();
-    const uint64_t arena_bytes = *std::max_element(chunk_bytes.begin(), chunk_bytes.end());
-
-    // device: two chunk-sized slots per direction inside this thread's staging buffers
-    void *d_in = nullptr, *d_out = nullptr;
-    hipStream_t up = nullptr;
-    if (int32_t rc = acquire_staging((size_t)(2 * arena_bytes), &d_in, &d_out, &up); rc != kOk)
-        return rc;
-    if (hipError_t e = g_pinned.reserve((size_t)arena_bytes); e != hipSuccess)
-        return fail(kDevice, "hipHostMalloc(batch arenas)", e);
-    // worker threads do not see this thread's thread_local arenas: hand them the pointers
-    void* const pinned_in[2] = {g_pinned.in[0], g_pinned.in[1]};
-    void* const pinned_out[2] = {g_pinned.out[0], g_pinned.out[1]};
-    auto g_pinned_in = [&](int c) { return pinned_in[c & 1]; };
-    auto g_pinned_out = [&](int c) { return pinned_out[c & 1]; };
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    hipStream_t down = nullptr;
-    if (hipError_t e = hipStreamCreateWithFlags(&down, hipStreamNonBlocking); e != hipSuccess)
-        return fail(kDevice, "hipStreamCreate(download)", e);
-
-    std::vector<hipEvent_t> ev((size_t)nchunks * 3, nullptr);   // per chunk: uploaded, kernels done, downloaded
-    for (auto& e : ev)
-        if (hipError_t err = hipEventCreateWithFlags(&e, hipEventDisableTiming); err != hipSuccess) {
-            for (auto& e2 : ev) if (e2) (void)hipEventDestroy(e2);
-            (void)hipStreamDestroy(down);
-            return fail(kDevice, "hipEventCreate", err);
-        }
-    auto ev_uploaded = [&](int c) { return ev[(size_t)c * 3]; };
-    auto ev_kernels = [&](int c) { return ev[(size_t)c * 3 + 1]; };
-    auto ev_downloaded = [&](int c) { return ev[(size_t)c * 3 + 2]; };
-
-    HostBatchShared sh;
-    sh.packed.assign((size_t)nchunks, 0);
-    sh.unpacked.assign((size_t)nchunks, 0);
-    auto set_failed = [&](hipError_t e) {
-        std::lock_guard<std::mutex> lk(sh.m);
-        if (!sh.failed) {
-            sh.failed = true;
-            sh.error = e;
-        }
-        sh.cv.notify_all();
-    };
-
-    // item i of a chunk belongs to copy thread (i - chunk_first) % kCopyThreads
-    auto packer = [&](int tid) {
-        hipError_t e = hipSetDevice(dev);
-        for (int c = 0; c < nchunks && e == hipSuccess; ++c) {
-            if (c < 2) {   // (chunks 0 and 1 wait for nothing -- but not for a call that is already being abandoned)
-                std::lock_guard<std::mutex> lk(sh.m);
-                if (sh.failed)
-                    return;
-            }
-            if (c >= 2) {
-                // arena c % 2 is free once chunk c - 2 has left it
-                {
-                    std::unique_lock<std::mutex> lk(sh.m);
-                    sh.cv.wait(lk, [&] { return sh.uploaded_recorded > c - 2 || sh.failed; });
-                    if (sh.failed)
-                        return;
-                }
-                e = hipEventSynchronize(ev_uploaded(c - 2));
-                if (e != hipSuccess)
-                    break;
-            }
-            uint8_t* arena = static_cast<uint8_t*>(g_pinned_in(c));
-            for (size_t i = chunk_first[(size_t)c] + (size_t)tid; i < chunk_first[(size_t)c + 1]; i += kCopyThreads)
-                if (items[i].len)
-                    std::memcpy(arena + slot[i], items[i].d_input, items[i].len);
-            {
-                std::lock_guard<std::mutex> lk(sh.m);
-                sh.packed[(size_t)c]++;
-            }
-            sh.cv.notify_all();
-        }
-        if (e != hipSuccess)
-            set_failed(e);
-    };
-    auto unpacker = [&](int tid) {
-        hipError_t e = hipSetDevice(dev);
-        for (int c = 0; c < nchunks && e == hipSuccess; ++c) {
-            {
-                std::unique_lock<std::mutex> lk(sh.m);
-                sh.cv.wait(lk, [&] { return sh.enqueued > c || sh.failed; });
-                if (sh.enqueued <= c)
-                    return;
-            }
-            e = hipEventSynchronize(ev_downloaded(c));
-            if (e != hipSuccess)
-                break;
-            const uint8_t* arena = static_cast<const uint8_t*>(g_pinned_out(c));
-            for (size_t i = chunk_first[(size_t)c] + (size_t)tid; i < chunk_first[(size_t)c + 1]; i += kCopyThreads)
-                if (items[i].len)
-                    std::memcpy(items[i].d_output, arena + slot[i], items[i].len);
-            {
-                std::lock_guard<std::mutex> lk(sh.m);
-                sh.unpacked[(size_t)c]++;
-            }
-            sh.cv.notify_all();
-        }
-        if (e != hipSuccess)
-            set_failed(e);
-    };
-
-    // Thread creation can fail (EAGAIN under a process limit).  Every stage below waits on counts that only the full set
-    // of threads reaches, so a partial set is told to leave (failed), joined, the streams drained, and the call reports it.
-    std::vector<std::thread> threads;
-    bool spawn_failed = false;
-    auto spawn = [&](auto&& fn, auto... args) {
-        if (spawn_failed)
-            return;
-        try {
-            threads.emplace_back(fn, args...);
-        } catch (const std::exception&) {
-            spawn_failed = true;
-        }
-    };
-    for (int t = 0; t < kCopyThreads; ++t) spawn(packer, t);
-    for (int t = 0; t < kCopyThreads; ++t) spawn(unpacker, t);
-
-    // The downloads are issued by a thread of their own.  A chunk's download may only be enqueued once the unpackers have
-    // emptied its pinned output arena (chunk c - 2) -- a HOST-side condition -- and when this thread waited for that before
-    // it issued the chunk's upload, only two chunks were ever between upload and unpack: the steady state was
-    // (upload + kernels + download + unpack) / 2 per chunk, 33 GiB/s, not the slowest stage.
-    auto downloader = [&] {
-        hipError_t e = hipSetDevice(dev);
-        for (int c = 0; c < nchunks && e == hipSuccess; ++c) {
-            {
-                std::unique_lock<std::mutex> lk(sh.m);
-                sh.cv.wait(lk, [&] { return (sh.kernels_issued > c && (c < 2 || sh.unpacked[(size_t)c - 2] == kCopyThreads)) || sh.failed; });
-                if (sh.failed)
-                    return;
-            }
-            const uint8_t* dout = static_cast<const uint8_t*>(d_out) + (size_t)(c & 1) * arena_bytes;
-            e = hipStreamWaitEvent(down, ev_kernels(c), 0);
-            if (e == hipSuccess)
-                e = hipMemcpyAsync(g_pinned_out(c), dout, (size_t)chunk_bytes[(size_t)c], hipMemcpyDeviceToHost, down);
-            if (e == hipSuccess)
-                e = hipEventRecord(ev_downloaded(c), down);
-            if (e != hipSuccess)
-                break;
-            {
-                std::lock_guard<std::mutex> lk(sh.m);
-                sh.enqueued = c + 1;
-            }
-            sh.cv.notify_all();
-        }
-        if (e != hipSuccess)
-            set_failed(e);
-    };
-    spawn(downloader);
-    if (spawn_failed) {
-        set_failed(hipErrorOutOfMemory);
-        for (auto& t : threads)
-            t.join();
-        for (auto& e : ev) (void)hipEventDestroy(e);
-        (void)hipStreamDestroy(down);
-        return fail(kAllocation, "could not start the batch copy threads");
-    }
-
-    // this thread: upload and kernels of every chunk, as soon as it is packed and its device slots are free
-    int32_t rc = kOk;
-    hipError_t err = hipSuccess;
-    std::vector<DxtltBatchItem> dev_items;
-    for (int c = 0; c < nchunks && rc == kOk && err == hipSuccess; ++c) {
-        {
-            std::unique_lock<std::mutex> lk(sh.m);
-            // packed; and the download of chunk c - 2 has been ENQUEUED, so that its event exists to be waited for below
-            sh.cv.wait(lk, [&] { return (sh.packed[(size_t)c] == kCopyThreads && (c < 2 || sh.enqueued > c - 2)) || sh.failed; });
-            if (sh.failed)
-                break;
-        }
-        uint8_t* di = static_cast<uint8_t*>(d_in) + (size_t)(c & 1) * arena_bytes;
-        uint8_t* dout = static_cast<uint8_t*>(d_out) + (size_t)(c & 1) * arena_bytes;
-        // device input slot c % 2 is rewritten here: wait for chunk c - 2's kernels (same stream: already ordered; kept
-        // for clarity)
-        if (c >= 2)
-            err = hipStreamWaitEvent(up, ev_kernels(c - 2), 0);
-        if (err == hipSuccess)
-            err = hipMemcpyAsync(di, g_pinned_in(c), (size_t)chunk_bytes[(size_t)c], hipMemcpyHostToDevice, up);
-        if (err == hipSuccess)
-            err = hipEventRecord(ev_uploaded(c), up);
-        {
-            std::lock_guard<std::mutex> lk(sh.m);
-            if (err == hipSuccess)
-                sh.uploaded_recorded = c + 1;
-        }
-        sh.cv.notify_all();
-        if (err != hipSuccess)
-            break;
-        // the kernels write device output slot c % 2: chunk c - 2's download must have read it
-        if (c >= 2)
-            err = hipStreamWaitEvent(up, ev_downloaded(c - 2), 0);
-        if (err != hipSuccess)
-            break;
-        dev_items.clear();
-        for (size_t i = chunk_first[(size_t)c]; i < chunk_first[(size_t)c + 1]; ++i) {
-            DxtltBatchItem it = items[i];
-            it.d_input = di + slot[i];
-            it.d_output = dout + slot[i];
-            dev_items.push_back(it);
-        }
-        rc = batch_device(dev_items.data(), dev_items.size(), up, true);
-        if (rc != kOk)
-            break;
-        err = hipEventRecord(ev_kernels(c), up);
-        if (err != hipSuccess)
-            break;
-        {
-            std::lock_guard<std::mutex> lk(sh.m);
-            sh.kernels_issued = c + 1;
-        }
-        sh.cv.notify_all();
-    }
-    if (rc != kOk || err != hipSuccess) {
-        std::lock_guard<std::mutex> lk(sh.m);
-        sh.failed = true;
-        if (err != hipSuccess && sh.error == hipSuccess)
-            sh.error = err;
-        sh.cv.notify_all();
-    }
-    for (auto& t : threads)
-        t.join();
-    (void)hipStreamSynchronize(up);
-    (void)hipStreamSynchronize(down);
-    for (auto& e : ev) (void)hipEventDestroy(e);
-    (void)hipStreamDestroy(down);
-    if (rc != kOk)
-        return rc;
-    if (sh.failed)
-        return fail(kDevice, "host batch copy", sh.error);
-    return kOk;
 }

@@ -16,6 +16,7 @@
 #include "bcn_launch.h"
 #include "estimate_launch.h"
 #include "host_common.h"
+#include "host_pipeline.h"
 
 namespace dxtlt_host {
 
@@ -246,20 +247,8 @@ struct BatchAutoDebug {
 // the bench hooks' events: three per chunk -- in front of its candidate launches, between them and its estimator launch, behind
 // it -- and `extra` more behind those for the call's own marks; read once what they mark has been waited for
 struct PhaseEvents {
-    std::vector<hipEvent_t> ev;
-    ~PhaseEvents()
-    {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-    bool begin(size_t chunks, size_t extra)
-    {
-        ev.assign(chunks * 3 + extra, nullptr);
-        for (hipEvent_t& e : ev)
-            if (hipEventCreate(&e) != hipSuccess)
-                return false;
-        return true;
-    }
+    EventList ev;
+    bool begin(size_t chunks, size_t extra) { return ev.create(chunks * 3 + extra, hipEventDefault) == hipSuccess; }
     bool on() const { return !ev.empty(); }
     void mark(size_t k, hipStream_t st)
     {

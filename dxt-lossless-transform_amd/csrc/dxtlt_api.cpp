@@ -375,6 +375,7 @@ void dxtlt_release_thread_resources(void)
     dxtlt_host::release_idle_shard_contexts();   // process-wide: the idle per-device contexts of the sharded calls
     dxtlt_host::release_normalize_thread_flag();
     dxtlt_host::release_batch_thread_tables();
+    dxtlt_host::release_batch_host_thread_arenas();
     dxtlt_host::release_auto_thread_arena();
 }
 

@@ -155,6 +155,18 @@ int32_t pixel_device_range(int pixel_bytes, bool inverse, const void* d_src, voi
 int32_t pixel_sharded(int pixel_bytes, bool inverse, const uint8_t* in, uint8_t* out, size_t len, bool decorrelate, uint8_t layout,
                       int32_t num_shards, std::vector<DxtltShardStat>* stats);
 
+// ---- batch_api.cpp, for the host batch (batch_host_api.cpp) ----
+// bytes per block (8, 9: per pixel) of a batch item's format (1..9)
+inline uint32_t item_block_bytes(uint8_t format)
+{
+    return is_pixel_format(format) ? (uint32_t)pixel_bytes_of(format) : format == 1 || format == 4 ? 8u : 16u;
+}
+// The per-item checks of both batch calls, in the order in which defects are reported; `host_call`: the host batch's texts and its
+// 4 GiB limit.  kOk, or the failure as fail() recorded it.
+int32_t batch_item_defect(const DxtltBatchItem& it, int max_format, bool host_call);
+// The device batch on `stream`; `pixels_allowed`: items of formats 8 and 9 are taken too (the host batch's chunks).
+int32_t batch_device(const DxtltBatchItem* items, size_t count, void* stream, bool pixels_allowed);
+
 // Binds the calling thread -- one this library created for `device` -- to the CPUs local to the device (numa_affinity.cpp).
 // Returns the number of CPUs bound to, 0 when nothing was changed.
 int bind_this_thread_near_device(int device);
@@ -166,6 +178,7 @@ int32_t enqueue(int32_t format, bool inverse, const void* d_src, void* d_dst, ui
 // Per-thread device resources of the other translation units, freed by dxtlt_release_thread_resources().
 void release_normalize_thread_flag();   // normalize_api.cpp
 void release_batch_thread_tables();     // batch_api.cpp
+void release_batch_host_thread_arenas();   // batch_host_api.cpp
 void release_auto_thread_arena();       // auto_transform.cpp
 
 struct AutoChoice {

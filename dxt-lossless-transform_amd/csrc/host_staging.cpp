@@ -5,15 +5,13 @@
 
 #include <algorithm>
 #include <atomic>
-#include <condition_variable>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
 #include <thread>
-#include <vector>
 
 #include "granule_launch.h"
 #include "host_common.h"
+#include "host_pipeline.h"
 
 namespace {
 
@@ -168,13 +166,6 @@ uint64_t pipeline_chunk_bytes(const StreamLayout& L, uint64_t len)
 // dxtlt_debug_host_route_counts: which arm every host round trip and shard transfer of this process took (HostRoute)
 std::atomic<uint64_t> g_route_counts[kRouteCount];
 
-struct PipeShared {
-    std::mutex m;
-    std::condition_variable cv;
-    int launched = 0;     // chunks whose kernel (and event) have been enqueued
-    bool failed = false;  // uploader gave up
-};
-
 }  // namespace
 
 bool dxtlt_host::pipeline_pays(uint64_t bytes) { return bytes >= kPipelineMinBytes; }
@@ -211,29 +202,21 @@ int32_t dxtlt_host::pipelined_range(const StreamLayout& S, const Launch& launch,
     const int dev = d.dev;
     count_route(kRoutePipelinedRange);
 
-    hipStream_t down = nullptr;
-    HIP_TRY(hipStreamCreateWithFlags(&down, hipStreamNonBlocking), "hipStreamCreate(download)");
-    std::vector<hipEvent_t> ev((size_t)nchunks, nullptr);
-    for (auto& e : ev) {
-        hipError_t err = hipEventCreateWithFlags(&e, hipEventDisableTiming);
-        if (err != hipSuccess) {
-            for (auto& e2 : ev) if (e2) (void)hipEventDestroy(e2);
-            (void)hipStreamDestroy(down);
-            return fail(kDevice, "hipEventCreate", err);
-        }
-    }
+    // the download stream and one event per chunk; they go with this call, behind the drains at its end
+    OwnedStream down_stream;
+    HIP_TRY(down_stream.create(), "hipStreamCreate(download)");
+    const hipStream_t down = down_stream.stream;
+    EventList ev;
+    HIP_TRY(ev.create((size_t)nchunks, hipEventDisableTiming), "hipEventCreate");
 
-    PipeShared sh;
+    StageGate gate;     // fails when the uploader gives up
+    int launched = 0;   // chunks whose kernel (and event) have been enqueued
     hipError_t down_err = hipSuccess;
     std::thread downloader([&] {
         hipError_t e = hipSetDevice(dev);
         for (int k = 0; k < nchunks && e == hipSuccess; ++k) {
-            {
-                std::unique_lock<std::mutex> lk(sh.m);
-                sh.cv.wait(lk, [&] { return sh.launched > k || sh.failed; });
-                if (sh.launched <= k)
-                    break;  // uploader failed before this chunk
-            }
+            if (!gate.wait_reached([&] { return launched > k; }))
+                break;  // uploader failed before this chunk
             const uint64_t first = (uint64_t)k * chunk_blocks;
             const uint64_t count = std::min<uint64_t>(chunk_blocks, blocks - first);
             e = hipStreamWaitEvent(down, ev[(size_t)k], 0);
@@ -277,16 +260,11 @@ int32_t dxtlt_host::pipelined_range(const StreamLayout& S, const Launch& launch,
             up_err = hipEventRecord(ev[(size_t)k], d.up);
         if (up_err == hipSuccess && rc == kOk)
             count_route(kRoutePipelineChunk);
-        {
-            std::lock_guard<std::mutex> lk(sh.m);
-            if (up_err == hipSuccess && rc == kOk)
-                sh.launched = k + 1;
-            else
-                sh.failed = true;
-        }
-        sh.cv.notify_all();
-        if (up_err != hipSuccess || rc != kOk)
+        if (up_err != hipSuccess || rc != kOk) {
+            gate.fail(up_err);
             break;
+        }
+        gate.publish(launched, k + 1);
     }
     downloader.join();
     // every exit drains the upload stream before the events go away and the staging buffers can be reused
@@ -294,8 +272,6 @@ int32_t dxtlt_host::pipelined_range(const StreamLayout& S, const Launch& launch,
     const hipError_t drain = hipStreamSynchronize(d.up);
     if (up_err == hipSuccess && rc == kOk)
         up_err = drain;
-    for (auto& e : ev) (void)hipEventDestroy(e);
-    (void)hipStreamDestroy(down);
     if (rc != kOk)
         return rc;
     if (up_err != hipSuccess)

@@ -237,6 +237,16 @@ int32_t dxtlt_debug_plan_batch_call(const DxtltBatchItem *items, size_t count, i
 int32_t dxtlt_debug_plan_batch_granules(const DxtltBatchItem *items, size_t count, int32_t format, int32_t inverse,
                                         uint32_t *first_wg_out, uint64_t *main_blocks_out, size_t entry_cap, uint32_t *coarse_out,
                                         size_t coarse_cap);
+/* Test hook, no device needed: how dxtlt_transform_batch_host cuts items of these lengths into chunks of `chunk_cap_bytes` (the
+ * call's own planner, over lengths alone).  chunk_of_item_out[i]: item i's chunk, 0xFFFFFFFF for an item that goes out alone, through
+ * the single-buffer host entry point of its format (len >= 2 * chunk_cap_bytes); slot_out[i]: where the item starts inside its
+ * chunk, a multiple of 256 (0 for an item that goes out alone).  The other items keep their order; a chunk is closed before the item
+ * whose padded length would push it past chunk_cap_bytes, and only when it already holds bytes.  chunk_bytes_out[c]: the bytes of
+ * chunk c (those beyond `chunk_cap` are not written); *arena_bytes_out: the largest chunk, the size of every pinned arena and device
+ * slot.  Any of the four may be NULL.  Returns the number of chunks: 0 when no item travels in a chunk; -1 for a NULL `len` with
+ * count > 0. */
+int32_t dxtlt_debug_plan_batch_host(const uint64_t *len, size_t count, uint64_t chunk_cap_bytes, uint32_t *chunk_of_item_out,
+                                    uint64_t *slot_out, uint64_t *chunk_bytes_out, size_t chunk_cap, uint64_t *arena_bytes_out);
 
 /* Test hook, no device needed: what a single-buffer DEVICE call (dxtlt_{un,}transform_bcN_with_settings_device,
  * dxtlt_transform_range_device) on these addresses would enqueue -- addresses are numbers here, nothing is dereferenced.  One

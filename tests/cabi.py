@@ -69,6 +69,24 @@ def bind(lib):
     return lib
 
 
+BATCH_HOST_ALONE = 0xFFFFFFFF
+
+
+def plan_batch_host(lib, lens, cap):
+    """dxtlt_debug_plan_batch_host (no device): how dxtlt_transform_batch_host cuts items of these lengths at a chunk cap of `cap`
+    bytes.  (chunk per item -- BATCH_HOST_ALONE for one that goes out alone --, slot per item, bytes per chunk, arena bytes)"""
+    u64, sz = C.c_uint64, C.c_size_t
+    f = lib.dxtlt_debug_plan_batch_host
+    f.argtypes = [C.POINTER(u64), sz, u64, C.POINTER(C.c_uint32), C.POINTER(u64), C.POINTER(u64), sz, C.POINTER(u64)]
+    f.restype = C.c_int32
+    n = len(lens)
+    arr, chunk_of, slot, arena = (u64 * max(1, n))(*lens), (C.c_uint32 * max(1, n))(), (u64 * max(1, n))(), u64(99)
+    chunk_bytes = (u64 * max(1, n))()          # no more chunks than items
+    chunks = f(arr, n, cap, chunk_of, slot, chunk_bytes, n, C.byref(arena))
+    assert 0 <= chunks <= n
+    return list(chunk_of)[:n], list(slot)[:n], list(chunk_bytes)[:chunks], arena.value
+
+
 def make_estimator(kind: str, log=None):
     """kind: 'dummy' (size = len, like the reference's C dummy estimator, bc1 c_api/transform_auto.rs:200-231),
     'zlib' (zlib level 1 size), 'zstd' (the system libzstd at level 1 through tools/zstd_ratio.py: what the reference's
