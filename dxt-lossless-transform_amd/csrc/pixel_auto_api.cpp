@@ -300,4 +300,18 @@ int32_t dxtlt_debug_pixels_auto_candidates_device(const void* d_input, size_t le
     return kOk;
 }
 
+int32_t dxtlt_debug_pixels_auto_candidates_into_device(const void* d_input, size_t len, int32_t pixel_bytes, void* d_arena, void* hip_stream)
+{
+    if (int32_t rc = check_arguments(pixel_bytes, len))
+        return rc;
+    if (d_input == nullptr || len == 0 || (reinterpret_cast<uintptr_t>(d_input) & 15) != 0 || len > SIZE_MAX / 5)
+        return fail(kInvalidArgument, "a non-empty buffer on a 16-byte boundary");
+    if (d_arena == nullptr)
+        return fail(kInvalidArgument, "NULL arena");
+    HIP_TRY(dxtlt::pixels::launch_auto_candidates(pixel_bytes, d_input, d_arena, len / (size_t)pixel_bytes,
+                                                  static_cast<hipStream_t>(hip_stream)),
+            "pixel candidate kernel launch");
+    return kOk;
+}
+
 }  // extern "C"

@@ -32,6 +32,22 @@ using pb::kCandidates;
 // the dxtlt_debug_pixels_batch_auto_* hooks: six totals per item, three phase figures (the third: the winners)
 thread_local BatchAutoDebug t_debug(kCandidates);
 
+// the candidate launches of one chunk, one per pixel_bytes present, from the call's table at `dev` (fill_auto_tables)
+hipError_t launch_chunk_candidates(const pb::AutoChunk& ch, const uint8_t* dev, hipStream_t st, uint64_t& launched)
+{
+    for (int b = 0; b < 2; ++b) {
+        if (ch.entries[b] == 0)
+            continue;
+        const uint8_t* d = dev + ch.at[b];
+        if (hipError_t e = dxtlt::pixels::launch_pixel_batch_candidates(b == 0 ? 4 : 3, reinterpret_cast<const dxtlt::pixels::PixelBatchEntry*>(d),
+                                                                        d + ch.entry_bytes[b], ch.entries[b], ch.wgs[b], ch.wide[b], st);
+            e != hipSuccess)
+            return e;
+        launched++;
+    }
+    return hipSuccess;
+}
+
 }  // namespace
 
 extern "C" int32_t dxtlt_transform_pixels_batch_auto_device(DxtltPixelBatchAutoItem* items, size_t count, void* hip_stream)
@@ -68,20 +84,7 @@ extern "C" int32_t dxtlt_transform_pixels_batch_auto_device(DxtltPixelBatchAutoI
     PhaseEvents phases;   // and two marks around the winners
     if (t_debug.time_phases && !phases.begin(plan.chunks.size(), 2))
         return fail(kDevice, "pixel batch auto: hipEventCreate", hipErrorOutOfMemory);
-    auto candidates = [&](size_t c, uint64_t& launched) {
-        const pb::AutoChunk& ch = plan.chunks[c];
-        for (int b = 0; b < 2; ++b) {
-            if (ch.entries[b] == 0)
-                continue;
-            const uint8_t* d = dev + ch.at[b];
-            if (hipError_t e = dxtlt::pixels::launch_pixel_batch_candidates(b == 0 ? 4 : 3, reinterpret_cast<const dxtlt::pixels::PixelBatchEntry*>(d),
-                                                                            d + ch.entry_bytes[b], ch.entries[b], ch.wgs[b], ch.wide[b], st);
-                e != hipSuccess)
-                return e;
-            launched++;
-        }
-        return hipSuccess;
-    };
+    auto candidates = [&](size_t c, uint64_t& launched) { return launch_chunk_candidates(plan.chunks[c], dev, st, launched); };
     auto estimator = [&](size_t c, uint64_t& launched) {
         const pb::AutoChunk& ch = plan.chunks[c];
         if (ch.estimator_entries == 0)
@@ -173,6 +176,41 @@ extern "C" int32_t dxtlt_debug_plan_pixels_batch_auto(const DxtltPixelBatchAutoI
     }
     if (out_chunks)
         *out_chunks = plan.chunks.size();
+    return kOk;
+}
+
+extern "C" int32_t dxtlt_debug_pixels_batch_candidates_device(const DxtltPixelBatchAutoItem* items, size_t count, size_t chunk, void* d_arena,
+                                                              uint64_t arena_bytes, void* hip_stream)
+{
+    pb::AutoPlan plan;
+    if (Defect d = pb::plan_auto_call(items, count, batch_auto_arena_cap(), plan); d.code != kOk)
+        return fail(d.code, d.what);
+    if (chunk >= plan.chunks.size())
+        return fail(kInvalidArgument, "pixel batch candidates: no such chunk");
+    const pb::AutoChunk& ch = plan.chunks[chunk];
+    if (d_arena == nullptr || arena_bytes < ch.arena_bytes)
+        return fail(kInvalidArgument, "pixel batch candidates: an arena smaller than the chunk's arena_bytes");
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    if (int32_t rc = auto_call_device_check(st))
+        return rc;
+    if (ch.candidate_launches() == 0)
+        return kOk;
+    BatchAutoBuffers& buffers = batch_auto_thread_buffers();
+    HIP_TRY(buffers.reserve(plan.table_bytes, 0), "pixel batch candidates: tables");
+    pb::fill_auto_tables(plan, items, static_cast<uint8_t*>(d_arena), static_cast<uint8_t*>(buffers.table_host));
+    // every exit below drains the stream: the tables belong to this thread's next call
+    hipError_t e = dxtlt::launch_table_upload(buffers.table_mapped, buffers.table_dev, (plan.table_bytes + 15) & ~size_t(15), st);
+    const char* step = "pixel batch candidates: table upload";
+    if (e == hipSuccess) {
+        uint64_t launched = 0;
+        e = launch_chunk_candidates(plan.chunks[chunk], static_cast<const uint8_t*>(buffers.table_dev), st, launched);
+        step = "pixel batch candidates: candidate kernel launch";
+    }
+    const hipError_t waited = hipStreamSynchronize(st);
+    if (e != hipSuccess)
+        return fail(kDevice, step, e);
+    if (waited != hipSuccess)
+        return fail(kDevice, "stream synchronize", waited);
     return kOk;
 }
 

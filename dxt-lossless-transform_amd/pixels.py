@@ -250,6 +250,53 @@ def last_batch_auto_totals(item: int):
     return [int(v) for v in buf[:n]]
 
 
+def debug_auto_candidates_into(input, arena, pixel_bytes: int = 4) -> None:
+    """Test hook (dxtlt_debug_pixels_auto_candidates_into_device): the fused candidate kernel of transform_auto from the CUDA uint8
+    tensor `input` (on a 16-byte boundary) into the caller's `arena` of 5 * len bytes or more -- candidate i of AUTO_CANDIDATES[:5]
+    at arena[i * len:(i + 1) * len].  Enqueued on torch's current stream, not waited for."""
+    import torch
+
+    from . import DeviceError, OutputBufferTooSmall, _Buf
+
+    src, dst = _Buf(input, False), _Buf(arena, True)
+    if src.device is None or dst.device is None:
+        raise TypeError("debug_auto_candidates_into takes device tensors")
+    if dst.nbytes < 5 * src.nbytes:
+        raise OutputBufferTooSmall(5 * src.nbytes, dst.nbytes)
+    f = _l().dxtlt_debug_pixels_auto_candidates_into_device
+    f.argtypes, f.restype = [C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p, C.c_void_p], C.c_int32
+    with torch.cuda.device(src.device):
+        rc = f(src.ptr, src.nbytes, pixel_bytes, dst.ptr, torch.cuda.current_stream().cuda_stream)
+    if rc != _lib.OK:
+        raise DeviceError(rc, _lib.last_error())
+
+
+def debug_batch_candidates(items, chunk: int, arena, stream=None) -> None:
+    """Test hook (dxtlt_debug_pixels_batch_candidates_device): the candidate launches of chunk `chunk` of transform_batch_auto over
+    `items` -- (input tensor, output tensor, pixel_bytes), as there; no output is written -- into the caller's CUDA uint8 tensor
+    `arena`: item k's five candidates at the arena_offset dxtlt_debug_plan_pixels_batch_auto reports for it.  Waits for `stream`."""
+    import torch
+
+    from . import DeviceError, _Buf
+
+    arr = (PixelBatchAutoItem * max(1, len(items)))()
+    device, keep = None, []
+    for k, (src, dst, pixel_bytes) in enumerate(items):
+        s, d, device = _batch_buffers("debug_batch_candidates", k, src, dst, pixel_bytes, device)
+        arr[k].d_input, arr[k].d_output, arr[k].len, arr[k].pixel_bytes = s.ptr, d.ptr, s.nbytes, pixel_bytes
+        keep.append((s, d))
+    a = _Buf(arena, True)
+    if a.device is None:
+        raise TypeError("debug_batch_candidates takes a device tensor as its arena")
+    f = _l().dxtlt_debug_pixels_batch_candidates_device
+    f.argtypes = [C.POINTER(PixelBatchAutoItem), C.c_size_t, C.c_size_t, C.c_void_p, C.c_uint64, C.c_void_p]
+    f.restype = C.c_int32
+    with torch.cuda.device(a.device):
+        rc = f(arr, len(items), int(chunk), a.ptr, a.nbytes, _stream_of(stream))
+    if rc != _lib.OK:
+        raise DeviceError(rc, _lib.last_error())
+
+
 def settings_triple(decorrelate: bool, layout: int):
     """(decorrelation_mode, split_alpha_endpoints, split_colour_endpoints) as the generic entry points -- the host batch call's
     format codes 8 / 9, dxtlt_transform_sharded, the DDS calls -- read these settings"""

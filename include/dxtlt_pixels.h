@@ -104,6 +104,11 @@ int32_t dxtlt_debug_pixels_auto_last_totals(uint64_t *out, int32_t cap);
 void dxtlt_debug_pixels_auto_time_phases(int32_t on);
 void dxtlt_debug_pixels_auto_last_phase_ms(double out[3]);
 int32_t dxtlt_debug_pixels_auto_candidates_device(const void *d_input, size_t len, int32_t pixel_bytes, void *hip_stream);
+/* Test hook: the same kernel with the same checks, into 5 * len bytes of the CALLER's at d_arena (any alignment: in the thread's
+ * arena candidate i starts i * len past a 256-byte boundary, which reaches every residue) -- candidate i < 5 at d_arena + i * len,
+ * byte for byte what dxtlt_transform_pixels_device writes for that setting, and no other byte.  Enqueues only. */
+int32_t dxtlt_debug_pixels_auto_candidates_into_device(const void *d_input, size_t len, int32_t pixel_bytes, void *d_arena,
+                                                       void *hip_stream);
 
 /* ---- many buffers in one call (docs/PIXEL_FORMAT.md, "Many buffers in one call") -------------------------------------------------
  * dxtlt_transform_pixels_batch_device: for every item the bytes in d_output are exactly what dxtlt_transform_pixels_device
@@ -208,6 +213,16 @@ typedef struct DxtltDebugPixelBatchAutoPlanChunk {
 } DxtltDebugPixelBatchAutoPlanChunk;
 int32_t dxtlt_debug_plan_pixels_batch_auto(const DxtltPixelBatchAutoItem *items, size_t count, DxtltDebugPixelBatchAutoPlanItem *items_out,
                                            DxtltDebugPixelBatchAutoPlanChunk *chunks_out, size_t chunk_capacity, size_t *out_chunks);
+
+/* Test hook: the candidate launches of ONE chunk of dxtlt_transform_pixels_batch_auto_device into memory of the caller's.  Plans
+ * as the call does (at the arena cap in force on the thread), writes the call's tables for an arena at d_arena, uploads them, runs
+ * chunk `chunk`'s candidate launches -- one per pixel_bytes present -- and WAITS for `hip_stream`: item k of the chunk has its five
+ * candidates at d_arena + arena_offset (dxtlt_debug_plan_pixels_batch_auto) + i * len and no other byte of the arena is written.
+ * No d_output is touched (the items must still pass the call's checks) and no estimator is launched.  Refused with nothing
+ * enqueued: what the call refuses, with its status; DXTLT_E_INVALID_ARGUMENT for a chunk that does not exist, a NULL d_arena, an
+ * arena_bytes below that chunk's arena_bytes and a capturing stream. */
+int32_t dxtlt_debug_pixels_batch_candidates_device(const DxtltPixelBatchAutoItem *items, size_t count, size_t chunk, void *d_arena,
+                                                   uint64_t arena_bytes, void *hip_stream);
 
 /* Test hooks, per calling thread, read-only.  last: of this thread's last dxtlt_transform_pixels_batch_auto_device, out[0] the
  * stream waits, out[1] the chunks, out[2] the candidate launches, out[3] the estimator launches (all 0 after a refused or an

@@ -63,6 +63,61 @@ def data_sets():
     return out
 
 
+WINNER_PIXELS = 16384      # two windows interleaved for B = 4; a plane is half a window
+
+
+@functools.lru_cache(maxsize=None)
+def winner_sets():
+    """[(name, B, (16384, B) pixels, index of the candidate that wins STRICTLY under entropy_ref.auto)]: one input per candidate
+    and pixel size, B = 4 first.  Candidates 0 and 3 are the head of the r2-256 mip chain and random walks; the other four are
+    drawn from ONE default_rng(5), in this order (the seed and the order are part of the construction):
+      5 (plain, INTERLEAVED)        every channel uniform over 16 values, one set of 16 in the first half of the pixels and a disjoint
+                                    set in the second: interleaved windows see one set each, a plane sees both
+      1 (decorrelate, PLANAR)       green uniform bytes, red and blue green + 0..3, alpha 0..3: subtract-green leaves two bits, and
+                                    planes keep them away from green
+      2 (decorrelate, INTERLEAVED)  green from the two half-sets, red and blue green + one of four values of the half's own set,
+                                    alpha = green
+      4 (plain, PLANAR)             channel c uniform over eight multiples of c + 3: every plane has its own eight values"""
+    P, h = WINNER_PIXELS, WINNER_PIXELS // 2
+    rng = np.random.default_rng(5)
+    sets = (np.arange(16, dtype=np.uint8) * 3 + 10, np.arange(16, dtype=np.uint8) * 5 + 120)
+    assert not set(sets[0].tolist()) & set(sets[1].tolist())
+
+    def halves(channels, pools):
+        px = np.empty((P, channels), np.uint8)
+        px[:h] = rng.choice(pools[0], (h, channels))
+        px[h:] = rng.choice(pools[1], (P - h, channels))
+        return px
+
+    chain = np.ascontiguousarray(data_sets()[2][1])
+    out = []
+    for B in (4, 3):
+        interleaved = halves(B, sets)
+        green = rng.integers(0, 256, P).astype(np.uint8)
+        planar = np.empty((P, B), np.uint8)
+        planar[:, 1] = green
+        planar[:, 0] = green + rng.integers(0, 4, P).astype(np.uint8)
+        planar[:, 2] = green + rng.integers(0, 4, P).astype(np.uint8)
+        if B == 4:
+            planar[:, 3] = rng.integers(0, 4, P).astype(np.uint8)
+        green = halves(1, sets)[:, 0]
+        small = (sets[0][:4], sets[1][:4])
+        dec_interleaved = np.empty((P, B), np.uint8)
+        dec_interleaved[:, 1] = green
+        for c in (0, 2):
+            dec_interleaved[:, c] = green + np.concatenate([rng.choice(small[0], h), rng.choice(small[1], P - h)]).astype(np.uint8)
+        if B == 4:
+            dec_interleaved[:, 3] = green
+        plain_planar = np.stack([rng.choice(np.arange(8, dtype=np.uint8) * (c + 3), P) for c in range(B)], axis=1)
+        for name, px, want in ((f"mip chain {B}", chain[:P, :B], 0), (f"green + 0..3 {B}", planar, 1), (f"half sets + green {B}", dec_interleaved, 2),
+                               (f"random walks {B}", random_walks(B, P, 11 + B), 3), (f"multiples {B}", plain_planar, 4),
+                               (f"half sets {B}", interleaved, 5)):
+            px = np.ascontiguousarray(px)
+            px.setflags(write=False)
+            out.append((name, B, px, want))
+    return out
+
+
 @functools.lru_cache(maxsize=None)
 def small_sets():
     """the same sets at 128 x 128 (crops of the images, the mip chain of the crop, the first 16384 pixels of the walks)"""

@@ -67,6 +67,10 @@ def load(pkg):
     l.dxtlt_transform_pixels_auto_device.argtypes = [vp, vp, sz, i32, vp, C.POINTER(C.c_bool), C.POINTER(C.c_uint8)]
     l.dxtlt_transform_pixels_auto_device.restype = i32
     l.dxtlt_debug_pixels_auto_last_totals.argtypes, l.dxtlt_debug_pixels_auto_last_totals.restype = [u64p, i32], i32
+    l.dxtlt_debug_pixels_auto_candidates_into_device.argtypes = [vp, sz, i32, vp, vp]
+    l.dxtlt_debug_pixels_auto_candidates_into_device.restype = i32
+    l.dxtlt_debug_pixels_batch_candidates_device.argtypes = [C.POINTER(AutoItem), sz, sz, vp, C.c_uint64, vp]
+    l.dxtlt_debug_pixels_batch_candidates_device.restype = i32
     l.dxtlt_last_error.restype = C.c_char_p
     return l
 
@@ -234,3 +238,93 @@ def plan(lib, arr, count, cap=64):
     tb = C.c_uint64(77)
     n = lib.dxtlt_debug_plan_pixels_batch(arr, count, out, cap, C.byref(tb))
     return n, list(out[:max(0, min(n, cap))]), tb.value
+
+
+# ---- the fused candidate kernels: tests/test_pixels_candidates_gpu.py ------------------------------------------------------------------
+# Cases keep the tuple form above -- (pixels, B, 0, 0, 0, input residue, output residue) -- so that source_bytes, Arenas, fake_items and
+# lookup_arms take them: a candidate launch is one class per pixel size.
+ARENA_FILL = 0xEE
+CANDIDATE_COUNTS = [1, 15, 16, 17, 4095, 4096, 4097, 8193, 12287]      # the single kernel
+CANDIDATE_BATCH_COUNTS = [1, 17, 4096, 4097, 8193, 12287]
+CANDIDATE_RESIDUES = [0, 1, 8, 15]
+LONG_ITEM = 64 * TILE + 1
+CANDIDATE_CHUNK_CAP = 600_000        # test_forced_chunks: the mixed batch in seven chunks
+
+
+def candidate_case(pixels, B, in_res, k=0):
+    return (pixels, B, 0, 0, 0, in_res, (3 * k + in_res) % LINE)
+
+
+def cases_candidates_mixed():
+    """40 items, the pixel sizes mixed: every count of CANDIDATE_BATCH_COUNTS and every input residue with both sizes, an empty item in
+    the middle, and one item of 64 tiles and a pixel between one-tile items of its own size (both lookup arms of csrc/batch_lookup.h)"""
+    out = [candidate_case(CANDIDATE_BATCH_COUNTS[k % 6], (4, 3)[(k + k // 6) % 2], CANDIDATE_RESIDUES[(k + k // 4) % 4], k) for k in range(36)]
+    out[18:18] = [candidate_case(0, 4, 0, 36)]
+    out[9:9] = [candidate_case(17, 4, 8, 37), candidate_case(LONG_ITEM, 4, 1, 38), candidate_case(1, 4, 15, 39)]
+    return out
+
+
+def cases_candidates_wide():
+    """300 items of one to three tiles of 3-byte pixels, the counts of cases_wide_lookup: the wide index in ONE candidate launch"""
+    return [candidate_case(c[0], 3, CANDIDATE_RESIDUES[k % 4], k) for k, c in enumerate(cases_wide_lookup())]
+
+
+def last_lane_valid(pixels):
+    """`valid` of the last lane with a pixel in the buffer's last tile (DXTLT_PIXEL_CANDIDATES_TILE): 16 = the vector arm of plane_store"""
+    n = (pixels - 1) % TILE + 1
+    return (n - 1) % 16 + 1
+
+
+def candidates_of(flat, B):
+    """the statement of a candidate arena or slice: candidates 0..4 of entropy_ref.CANDIDATES side by side, 5 * len bytes"""
+    import entropy_ref
+
+    return np.concatenate([pixels_ref.forward(flat, B, d, l) for d, l in entropy_ref.CANDIDATES[:5]])
+
+
+def arena_differences(got, placed, fill=ARENA_FILL):
+    """THE comparison of the candidate tests.  placed: [(offset, expected bytes, tag)], disjoint.  [] when every range of `got`
+    equals its expectation and every other byte holds `fill`; else one line per range that differs and one for the strays."""
+    image, covered = np.full(got.size, fill, dtype=np.uint8), np.zeros(got.size, dtype=bool)
+    for off, want, tag in placed:
+        assert 0 <= off and off + want.size <= got.size and not covered[off:off + want.size].any(), tag
+        image[off:off + want.size] = want
+        covered[off:off + want.size] = True
+    if np.array_equal(got, image):
+        return []
+    out = []
+    for off, want, tag in placed:
+        bad = np.nonzero(got[off:off + want.size] != want)[0]
+        if bad.size:
+            i = int(bad[0])
+            out.append(f"{tag}: {bad.size} of {want.size} bytes differ, first at byte {i} (got {int(got[off + i])}, want {int(want[i])})")
+    stray = np.nonzero((got != fill) & ~covered)[0]
+    if stray.size:
+        out.append(f"{stray.size} bytes outside every slice were written, first at {int(stray[0])}")
+    return out
+
+
+def make_auto_items(cases, arenas):
+    arr = (AutoItem * max(1, len(cases)))()
+    for k, c in enumerate(cases):
+        n = c[0] * c[1]
+        arr[k].d_input, arr[k].d_output, arr[k].len = (arenas.in_ptr(k) if n else None), (arenas.out_ptr(k) if n else None), n
+        arr[k].pixel_bytes, arr[k].decorrelate, arr[k].layout = c[1], 0xEE, 0xEE
+    return arr
+
+
+def fake_auto_items(cases):
+    """the cases as auto items at made-up addresses with the cases' residues (the plan hook dereferences nothing)"""
+    fake = fake_items(cases)
+    arr = (AutoItem * max(1, len(cases)))()
+    for k, c in enumerate(cases):
+        arr[k].d_input, arr[k].d_output, arr[k].len, arr[k].pixel_bytes = fake[k].d_input, fake[k].d_output, fake[k].len, c[1]
+    return arr
+
+
+def auto_plan(lib, arr, count, chunk_capacity=64):
+    """(items, chunks) of dxtlt_debug_plan_pixels_batch_auto at the cap in force on the thread"""
+    items, chunks, n = (PlanItem * max(1, count))(), (PlanChunk * chunk_capacity)(), C.c_size_t(0)
+    rc = lib.dxtlt_debug_plan_pixels_batch_auto(arr, count, items, chunks, chunk_capacity, C.byref(n))
+    assert rc == 0 and n.value <= chunk_capacity, (rc, n.value, lib.dxtlt_last_error())
+    return list(items[:count]), list(chunks[:n.value])

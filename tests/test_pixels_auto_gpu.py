@@ -146,6 +146,25 @@ def test_the_pick_on_the_small_data_sets(lib, dev):
     assert picks == [1, 1, 1, 4, 4, 4, 4]
 
 
+@pytest.mark.parametrize("k", range(12))
+def test_every_candidate_wins_strictly_on_both_routes(lib, dev, k):
+    """the twelve inputs of pixels_auto_data.winner_sets: each of the six candidates is the one strict winner once per pixel size
+    (held to the statement without a device by tests/test_pixels_batch_auto_gpu.py)"""
+    name, B, px, winner = D.winner_sets()[k]
+    flat = px.reshape(-1)
+    totals, at, want = reference(("winner", name), flat, B)
+    assert at == winner and all(totals[at] < t for i, t in enumerate(totals) if i != at), name
+    for arena in (1, 0):
+        lib.dxtlt_debug_auto_use_arena(arena)
+        try:
+            choice, got, dev_totals = device_auto(lib, dev, flat, B)
+        finally:
+            lib.dxtlt_debug_auto_use_arena(1)
+        assert dev_totals == totals, (name, arena, dev_totals, totals)
+        assert choice == R.CANDIDATES[winner], (name, arena)
+        assert np.array_equal(got, want), (name, arena)
+
+
 def test_empty_buffer_and_ties_keep_the_first_candidate(lib, dev):
     dec, lay = C.c_bool(False), C.c_uint8(9)
     assert lib.dxtlt_transform_pixels_auto_device(None, None, 0, 4, None, C.byref(dec), C.byref(lay)) == 0

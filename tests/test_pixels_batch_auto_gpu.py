@@ -166,6 +166,58 @@ def test_chunks_give_the_same_totals_choices_and_bytes(lib, dev):
     assert cut_choices == whole_choices and np.array_equal(cut, whole)
 
 
+def winners():
+    """the twelve inputs of pixels_auto_data.winner_sets as specs, with their statement: every candidate the strict winner once per
+    pixel size"""
+    if "winners" not in _INPUTS:
+        specs = [(name, B, px.reshape(-1), RESIDUES[k % 4]) for k, (name, B, px, _want) in enumerate(D.winner_sets())]
+        _INPUTS["winners"] = (specs, [R.auto(flat, B) for _n, B, flat, _r in specs])
+    return _INPUTS["winners"]
+
+
+def test_the_reference_picks_every_candidate_strictly():
+    """no device: the six reference picks per pixel size are exactly {0, 1, 2, 3, 4, 5}, each with its total below every other"""
+    specs, ref = winners()
+    for B in (4, 3):
+        picks = []
+        for (name, b, flat, _r), (totals, at, _out), (_n, _b, _px, want) in zip(specs, ref, D.winner_sets()):
+            if b == B:
+                assert flat.size == B * D.WINNER_PIXELS and at == want, name
+                assert all(totals[at] < t for i, t in enumerate(totals) if i != at), (name, totals)
+                picks.append(at)
+        assert sorted(picks) == [0, 1, 2, 3, 4, 5], B
+
+
+@pytest.mark.gpu
+def test_every_candidate_wins_in_one_call_in_chunks_and_as_the_single_call(lib, dev):
+    import torch
+
+    specs, ref = winners()
+    arenas, whole, whole_choices = run_auto(lib, dev, specs, ref)
+    assert last_of(lib) == [1, 1, 2, 1]
+    assert {R.CANDIDATES.index(c) for c in whole_choices[:6]} == {R.CANDIDATES.index(c) for c in whole_choices[6:]} == set(range(6))
+    # slices of 327 680 and 245 760 bytes: five 4-byte items alone, the sixth with the first 3-byte item, then two, two and one
+    lib.dxtlt_debug_batch_auto_arena_cap(600_000)
+    try:
+        _a, cut, cut_choices = run_auto(lib, dev, specs, ref)
+        assert last_of(lib) == [1, 9, 10, 9]
+    finally:
+        lib.dxtlt_debug_batch_auto_arena_cap(0)
+    assert cut_choices == whole_choices and np.array_equal(cut, whole)
+    # every item alone through the single call: the same choice, totals and bytes
+    single = U.Arenas(dev, [s[2] for s in specs], [s[3] for s in specs], [(3 * k + s[3]) % U.LINE for k, s in enumerate(specs)])
+    stream = torch.cuda.current_stream().cuda_stream
+    for k, (name, B, flat, _r) in enumerate(specs):
+        dec, lay = C.c_bool(), C.c_uint8(9)
+        rc = lib.dxtlt_transform_pixels_auto_device(single.in_ptr(k), single.out_ptr(k), flat.size, B, stream, C.byref(dec), C.byref(lay))
+        assert rc == 0, lib.dxtlt_last_error()
+        buf = (C.c_uint64 * 8)()
+        n = lib.dxtlt_debug_pixels_auto_last_totals(buf, 8)
+        assert [int(v) for v in buf[:n]] == ref[k][0], name
+        assert (dec.value, lay.value) == whole_choices[k], name
+    assert np.array_equal(single.check(), whole)
+
+
 @pytest.mark.gpu
 def test_refusals_enqueue_nothing_and_leave_the_results_alone(lib, dev):
     import torch
