@@ -16,6 +16,7 @@
 #include <type_traits>
 
 #include "bc1_normalize.h"
+#include "bc23_normalize.h"
 #include "bcn_launch.h"
 #include "streaming_store.h"
 #include "ycocg_swar.h"
@@ -440,14 +441,31 @@ __device__ __forceinline__ uint64_t xcd_contiguous_tile(uint32_t orig, uint32_t 
 // BC1 block normalisation fused into the forward kernels (experimental module of the reference,
 // transform_bc1_with_normalize_blocks, experimental/normalize_blocks/transform.rs:65-166): the two blocks of the
 // lane's vector are normalised in registers right after the load, so the fused path moves the same 2*len bytes.
+//
+// BC2 / BC3 (transform_bc{2,3}_with_normalize_blocks): the lane's vector is ONE block -- q.x, q.y the alpha half, q.z, q.w the
+// colour half -- and normalize_block_bc23 (bc23_normalize.h) rewrites it.  BC3 has 11 non-trivial (alpha mode, colour mode)
+// pairs, so the modes are no template parameters here: NORM == kNormFromArgument says "the modes are a wave-uniform kernel
+// argument", norm_modes = alpha_mode << 2 | color_mode, and there is one kernel set more per (format, VARIANT, SA, SC).
+// The argument rides in bits the plain kernels never see set (kNormModesShift): of `xcd_remap` in fwd_tiled, of
+// Shifts::halo_vecs in the halo tiles (and, experiments build, in the first-form shifted tiles; the element kernel: the top
+// byte of `count`), so the kernels keep their signatures and every instantiation with another NORM compiles as before.
+constexpr int kNormFromArgument = 4;   // (behind bc1_normalize.h's kNormTransparentOnly = 3)
+constexpr int kNormModesShift = 8;
+__host__ __device__ constexpr int pack_norm_modes(int alpha_mode, int color_mode) { return (alpha_mode << 2) | color_mode; }
+
 template <int FMT, int NORM>
-__device__ __forceinline__ u32x4 normalize_vector(u32x4 q)
+__device__ __forceinline__ u32x4 normalize_vector(u32x4 q, int norm_modes = 0)
 {
     if constexpr (FMT == kBc1 && NORM != kNormNone) {
         uint32_t ca = q.x, xa = q.y, cb = q.z, xb = q.w;
         normalize_bc1_block<NORM>(ca, xa);
         normalize_bc1_block<NORM>(cb, xb);
         q = u32x4{ca, xa, cb, xb};
+    }
+    if constexpr ((FMT == kBc2 || FMT == kBc3) && NORM == kNormFromArgument) {
+        uint32_t b[4] = {q.x, q.y, q.z, q.w};
+        normalize_block_bc23<FMT>(norm_modes >> 2, norm_modes & 3, b);
+        q = u32x4{b[0], b[1], b[2], b[3]};
     }
     return q;
 }
@@ -460,12 +478,13 @@ constexpr int kTiledArray = 2;
 // `lds`: THREADS * 16 bytes.
 template <int FMT, int VARIANT, bool SA, bool SC, int THREADS, int NORM = kNormNone>
 __device__ __forceinline__ void fwd_aligned_tile(const uint8_t* __restrict__ aos, uint8_t* __restrict__ soa,
-                                                 uint64_t total_blocks, uint64_t first_block, uint64_t tile, uint8_t* lds)
+                                                 uint64_t total_blocks, uint64_t first_block, uint64_t tile, uint8_t* lds,
+                                                 int norm_modes = 0)
 {
     constexpr int T = tile_blocks(FMT, THREADS);
     const int t = threadIdx.x;
     WG_MARK(1);
-    const u32x4 q = normalize_vector<FMT, NORM>(gload16(aos + tile * (THREADS * 16) + t * 16));
+    const u32x4 q = normalize_vector<FMT, NORM>(gload16(aos + tile * (THREADS * 16) + t * 16), norm_modes);
     WG_MARK_LOADS_DONE(2);
     scatter_to_image<FMT, VARIANT, SA, SC, T>(lds, t, q);
     __syncthreads();
@@ -532,7 +551,10 @@ fwd_tiled(const uint8_t* __restrict__ aos, uint8_t* __restrict__ soa, uint64_t t
 #else
     const uint64_t tile = blockIdx.x;   // identity order: the XCD-contiguous one costs aligned tiles 0.01-0.03 (profiles/r01_i_*)
 #endif
-    fwd_aligned_tile<FMT, VARIANT, SA, SC, THREADS, NORM>(aos, soa, total_blocks, first_block, tile, lds);
+    if constexpr (NORM == kNormFromArgument)
+        fwd_aligned_tile<FMT, VARIANT, SA, SC, THREADS, NORM>(aos, soa, total_blocks, first_block, tile, lds, xcd_remap >> kNormModesShift);
+    else
+        fwd_aligned_tile<FMT, VARIANT, SA, SC, THREADS, NORM>(aos, soa, total_blocks, first_block, tile, lds);
 }
 
 template <int FMT, int VARIANT, bool SA, bool SC, int THREADS>
@@ -618,6 +640,14 @@ __device__ __forceinline__ bool shifts_skip_partial(const Shifts& sh)
     (void)sh;
     return false;
 #endif
+}
+
+// The NORM == kNormFromArgument kernels: takes the modes out of the bits above Shifts::halo_vecs and returns them
+__device__ __forceinline__ int take_norm_modes(Shifts& sh)
+{
+    const int norm_modes = sh.halo_vecs >> kNormModesShift;
+    sh.halo_vecs &= (1 << kNormModesShift) - 1;
+    return norm_modes;
 }
 
 template <typename STREAMS>
@@ -1186,7 +1216,7 @@ __device__ __forceinline__ void halo_copy_out_wave(uint8_t* __restrict__ soa, co
 template <int FMT, int VARIANT, bool SA, bool SC, int NORM, bool NAT, int THREADS = 256>
 __device__ __forceinline__ void fwd_halo_tile(const uint8_t* __restrict__ aos, uint8_t* __restrict__ soa,
                                               uint64_t /*total_blocks: in sh.gbase*/, uint64_t /*first_block: in sh.gbase*/, const Shifts& sh, uint64_t tile,
-                                              uint8_t* lds)
+                                              uint8_t* lds, int norm_modes = 0)
 {
     constexpr Streams S = make_streams(FMT, SA, SC);
     constexpr int T = tile_blocks(FMT, THREADS);
@@ -1215,11 +1245,11 @@ __device__ __forceinline__ void fwd_halo_tile(const uint8_t* __restrict__ aos, u
     if (has_halo) {
         // plain load: the previous tile has just fetched these lines
         const u32x4 qh = *reinterpret_cast<const u32x4*>(tile_aos - hv * 16 + t * 16);
-        scatter_shifted<FMT, VARIANT, SA, SC, NAT>(lds, t - hv, normalize_vector<FMT, NORM>(qh), base);
+        scatter_shifted<FMT, VARIANT, SA, SC, NAT>(lds, t - hv, normalize_vector<FMT, NORM>(qh, norm_modes), base);
     }
     static_assert(HV <= THREADS, "the halo is loaded by the first lanes of the workgroup");
     WG_MARK_LOADS_DONE(2);
-    scatter_shifted<FMT, VARIANT, SA, SC, NAT>(lds, t, normalize_vector<FMT, NORM>(q), base);
+    scatter_shifted<FMT, VARIANT, SA, SC, NAT>(lds, t, normalize_vector<FMT, NORM>(q, norm_modes), base);
     __syncthreads();
     WG_MARK(3);
 
@@ -1312,7 +1342,7 @@ __device__ __forceinline__ EdgeSlot edge_slot_behind_window(int s_sel, int k, co
 // the extra segments lanes 0 .. 4 n - 1 look after.
 template <int FMT, int VARIANT, bool SA, bool SC, int NORM, bool NAT, int THREADS = 256>
 __device__ __forceinline__ void fwd_halo_edge_tile(const uint8_t* __restrict__ aos, uint8_t* __restrict__ soa, const Shifts& sh,
-                                                   uint64_t tile, uint8_t* lds)
+                                                   uint64_t tile, uint8_t* lds, int norm_modes = 0)
 {
     constexpr Streams S = make_streams(FMT, SA, SC);
     constexpr int T = tile_blocks(FMT, THREADS);
@@ -1341,9 +1371,9 @@ __device__ __forceinline__ void fwd_halo_edge_tile(const uint8_t* __restrict__ a
     if (has_halo)
         qh = *reinterpret_cast<const u32x4*>(tile_aos - hv * 16 + t * 16);
     if (has_halo)
-        scatter_shifted<FMT, VARIANT, SA, SC, NAT>(lds, t - hv, normalize_vector<FMT, NORM>(qh), base);
+        scatter_shifted<FMT, VARIANT, SA, SC, NAT>(lds, t - hv, normalize_vector<FMT, NORM>(qh, norm_modes), base);
     if (whole_vec || half_vec)
-        scatter_shifted<FMT, VARIANT, SA, SC, NAT>(lds, t, normalize_vector<FMT, NORM>(q), base);
+        scatter_shifted<FMT, VARIANT, SA, SC, NAT>(lds, t, normalize_vector<FMT, NORM>(q, norm_modes), base);
     __syncthreads();
 
     uint64_t gb[6];
@@ -1405,6 +1435,15 @@ fwd_tiled_halo(const uint8_t* __restrict__ aos_arg, uint8_t* __restrict__ soa_ar
     // identity tile order: the halo is read again by the next tile, on another XCD, out of the memory-side cache (temporal loads)
     const uint64_t tile = !whole ? (uint64_t)sh.full_tiles : shifts_xcd_contiguous(sh, false) ? xcd_contiguous_tile(wg, sh.full_tiles) : (uint64_t)wg;
     const bool edge = !whole || tile == 0;
+    if constexpr (NORM == kNormFromArgument) {
+        Shifts plain = sh;
+        const int norm_modes = take_norm_modes(plain);
+        if (edge)
+            fwd_halo_edge_tile<FMT, VARIANT, SA, SC, NORM, NAT, THREADS>(aos, soa, plain, tile, lds, norm_modes);
+        else
+            fwd_halo_tile<FMT, VARIANT, SA, SC, NORM, NAT, THREADS>(aos, soa, total_blocks, first_block, plain, tile, lds, norm_modes);
+        return;
+    }
     if (edge)
         fwd_halo_edge_tile<FMT, VARIANT, SA, SC, NORM, NAT, THREADS>(aos, soa, sh, tile, lds);
     else
@@ -1659,6 +1698,26 @@ __device__ __forceinline__ uint64_t load_bytes(const uint8_t* p, bool natural)
 
 __device__ __forceinline__ bool aligned_to(const void* p, int a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
+
+// Host side: the kernels' types as launch_transform (bcn_kernels.hip) holds them
+using TiledFn = void (*)(const uint8_t*, uint8_t*, uint64_t, uint64_t, int, int64_t, int64_t);
+using ShiftFn = void (*)(const uint8_t*, uint8_t*, uint64_t, uint64_t, Shifts);
+#ifdef DXTLT_EXPERIMENTS
+using GenericFn = void (*)(const uint8_t*, uint8_t*, uint64_t, uint64_t, uint64_t, uint64_t);
+#endif
+
+// The BC2 / BC3 forward kernels with block normalisation fused in (NORM == kNormFromArgument; bcn_norm23_kernels.hip): one
+// aligned tile size, the format's default, and the halo tiles with their edge tiles (halo[1]: natural shifts); in the
+// experiments build also the first-form shifted tiles and the element kernel.  fmt kBc2 or kBc3, variant 0..3.
+struct FusedNormKernels {
+    TiledFn tiled;
+    ShiftFn halo[2];
+#ifdef DXTLT_EXPERIMENTS
+    ShiftFn shifted;
+    GenericFn generic;
+#endif
+};
+FusedNormKernels fused_norm_kernels_bc23(Format fmt, int variant, bool sa, bool sc);
 
 }  // namespace dxtlt
 

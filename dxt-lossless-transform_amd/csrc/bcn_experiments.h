@@ -39,7 +39,7 @@ __device__ __forceinline__ void shifted_segment(int o, const uint64_t (&gb)[6], 
 template <int FMT, int VARIANT, bool SA, bool SC, int NORM = kNormNone, int R = 1>
 __device__ __forceinline__ void fwd_shift_tile(const uint8_t* __restrict__ aos, uint8_t* __restrict__ soa,
                                                uint64_t /*total_blocks: in sh.gbase*/, uint64_t /*first_block: in sh.gbase*/, const Shifts& sh, uint64_t tile,
-                                               uint8_t* lds)
+                                               uint8_t* lds, int norm_modes = 0)
 {
     constexpr Streams S = make_streams(FMT, SA, SC);
     constexpr int T = tile_blocks(FMT, 256) * R;
@@ -55,7 +55,7 @@ __device__ __forceinline__ void fwd_shift_tile(const uint8_t* __restrict__ aos, 
         q[j] = gload16(aos + tile * (4096 * R) + (t + 256 * j) * 16);
 #pragma unroll
     for (int j = 0; j < R; ++j) {
-        const u32x4 v = normalize_vector<FMT, NORM>(q[j]);
+        const u32x4 v = normalize_vector<FMT, NORM>(q[j], norm_modes);
         if (sh.natural)
             scatter_shifted<FMT, VARIANT, SA, SC, true>(lds, t + 256 * j, v, base);
         else
@@ -111,7 +111,12 @@ fwd_tiled_shift(const uint8_t* __restrict__ aos, uint8_t* __restrict__ soa, uint
 {
     __shared__ __attribute__((aligned(16))) uint8_t lds[shift_lds_bytes(R)];
     const uint64_t tile = sh.xcd_remap ? xcd_contiguous_tile(blockIdx.x, gridDim.x) : (uint64_t)blockIdx.x;
-    fwd_shift_tile<FMT, VARIANT, SA, SC, NORM, R>(aos, soa, total_blocks, first_block, sh, tile, lds);
+    if constexpr (NORM == kNormFromArgument) {
+        const int norm_modes = take_norm_modes(sh);
+        fwd_shift_tile<FMT, VARIANT, SA, SC, NORM, R>(aos, soa, total_blocks, first_block, sh, tile, lds, norm_modes);
+    } else {
+        fwd_shift_tile<FMT, VARIANT, SA, SC, NORM, R>(aos, soa, total_blocks, first_block, sh, tile, lds);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -122,7 +127,7 @@ fwd_tiled_shift(const uint8_t* __restrict__ aos, uint8_t* __restrict__ soa, uint
 template <int FMT, int VARIANT, bool SA, bool SC, bool INVERSE, int NORM = kNormNone>
 __device__ __forceinline__ void generic_block(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
                                               uint64_t total_blocks, uint64_t first_block, uint64_t local_first,
-                                              uint64_t count, uint64_t i)
+                                              uint64_t count, uint64_t i, int norm_modes = 0)
 {
     // AoS side: block (local_first + i) of the range lives at aos + (local_first + i) * BLOCK.
     // SoA side: global block index first_block + local_first + i.
@@ -165,6 +170,14 @@ __device__ __forceinline__ void generic_block(const uint8_t* __restrict__ src, u
         indices = (uint32_t)load_bytes<4>(aos_c + CO + 4, aos4);
         if constexpr (FMT == kBc1 && NORM != kNormNone)
             normalize_bc1_block<NORM>(colours, indices);
+        if constexpr ((FMT == kBc2 || FMT == kBc3) && NORM == kNormFromArgument) {
+            normalize_colour_half_4c(norm_modes & 3, colours, indices);
+            if constexpr (FMT == kBc3) {
+                uint32_t w0 = a0 | (a1 << 8) | (i01 << 16), w1 = i23 | (i45 << 16);
+                normalize_alpha_half_bc3(norm_modes >> 2, w0, w1);
+                a0 = w0 & 255u, a1 = (w0 >> 8) & 255u, i01 = w0 >> 16, i23 = w1 & 0xFFFFu, i45 = w1 >> 16;
+            }
+        }
         colours = decorrelate2<VARIANT>(colours);
     }
 
@@ -256,8 +269,12 @@ __global__ void __launch_bounds__(kThreads)
 generic_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, uint64_t total_blocks,
                uint64_t first_block, uint64_t local_first, uint64_t count)
 {
-    generic_block<FMT, VARIANT, SA, SC, INVERSE, NORM>(src, dst, total_blocks, first_block, local_first, count,
-                                                       (uint64_t)blockIdx.x * kThreads + threadIdx.x);
+    if constexpr (NORM == kNormFromArgument)   // the modes: top byte of `count` (a launch holds at most 2^31 blocks)
+        generic_block<FMT, VARIANT, SA, SC, INVERSE, NORM>(src, dst, total_blocks, first_block, local_first, count & ((1ull << 56) - 1),
+                                                           (uint64_t)blockIdx.x * kThreads + threadIdx.x, (int)(count >> 56));
+    else
+        generic_block<FMT, VARIANT, SA, SC, INVERSE, NORM>(src, dst, total_blocks, first_block, local_first, count,
+                                                           (uint64_t)blockIdx.x * kThreads + threadIdx.x);
 }
 
 }  // namespace dxtlt

@@ -78,12 +78,6 @@ fill_splitmix64_kernel(uint8_t* __restrict__ dst, uint64_t len_bytes, uint64_t s
 // ------------------------------------------------------------------------------------------------
 namespace {
 
-using TiledFn = void (*)(const uint8_t*, uint8_t*, uint64_t, uint64_t, int, int64_t, int64_t);
-using ShiftFn = void (*)(const uint8_t*, uint8_t*, uint64_t, uint64_t, Shifts);
-#ifdef DXTLT_EXPERIMENTS
-using GenericFn = void (*)(const uint8_t*, uint8_t*, uint64_t, uint64_t, uint64_t, uint64_t);
-#endif
-
 struct KernelSet {
     TiledFn tiled[4];  // aligned tiles of 64, 128, 256, 512 threads
     ShiftFn shifted;   // inverse: shifted tiles + edge tile (shift_tile_threads(fmt) lanes); forward: nullptr (experiments build: the first form, 256)
@@ -166,6 +160,23 @@ KernelSet bc1_norm_kernels()
 #ifdef DXTLT_EXPERIMENTS
     ks.shifted = fwd_tiled_shift<kBc1, VARIANT, false, SC, NORM>;
     ks.generic = generic_kernel<kBc1, VARIANT, false, SC, false, NORM>;
+#endif
+    return ks;
+}
+
+// BC2 / BC3 forward with block normalisation fused in: the kernel sets of bcn_norm23_kernels.hip (a translation unit of their
+// own: with them in this one, the compiler schedules four instructions of one plain halo kernel in another order), with the
+// members bc1_norm_kernels has
+KernelSet bc23_norm_kernels(Format fmt, int variant, bool sa, bool sc)
+{
+    const FusedNormKernels f = fused_norm_kernels_bc23(fmt, variant, sa, sc);
+    KernelSet ks{};
+    ks.tiled[0] = ks.tiled[1] = ks.tiled[2] = ks.tiled[3] = f.tiled;
+    ks.halo[0] = f.halo[0];
+    ks.halo[1] = f.halo[1];
+#ifdef DXTLT_EXPERIMENTS
+    ks.shifted = f.shifted;
+    ks.generic = f.generic;
 #endif
     return ks;
 }
@@ -315,6 +326,22 @@ hipError_t plan_launches(Format fmt, bool inverse, bool sa, bool sc, const void*
 // are the same as in one launch): the AoS side advances, the SoA side is addressed through first_block as always.
 constexpr uint64_t kMaxBlocksPerLaunch = 1ull << 31;
 
+// Block normalisation is fused into the forward transforms of BC1 (colour modes 0..2 and the internal transparent-only mode 3,
+// bc1_normalize.h), BC2 (colour modes 0..2) and BC3 (colour modes 0..2, alpha modes 0..3); nothing else takes a mode.
+bool normalization_is_valid(Format fmt, bool inverse, const Settings& s)
+{
+    if (s.normalize == kNormNone && s.normalize_alpha == kAlphaNone)
+        return true;
+    if (inverse || s.normalize < 0 || s.normalize_alpha < 0)
+        return false;
+    switch (fmt) {
+    case kBc1: return s.normalize <= kNormTransparentOnly && s.normalize_alpha == kAlphaNone;
+    case kBc2: return s.normalize <= kNormReplicateColor && s.normalize_alpha == kAlphaNone;
+    case kBc3: return s.normalize <= kNormReplicateColor && s.normalize_alpha <= kAlphaOpaqueZeroAlphaMaxIndices;
+    default: return false;
+    }
+}
+
 int aligned_tile_threads(Format fmt, bool inverse, bool normalizing, const LaunchTuning* tuning)
 {
     int threads = default_tile_threads(fmt, inverse);
@@ -374,8 +401,8 @@ hipError_t launch_transform(Format fmt, bool inverse, const Settings& s_arg, con
     const Settings s = effective_settings(fmt, s_arg);   // (BC4 / BC5: variant and colour split do not apply)
     if (s.variant < 0 || s.variant > 3 || r.first_block + r.num_blocks > r.total_blocks)
         return hipErrorInvalidValue;
-    if (s.normalize != kNormNone && (fmt != kBc1 || inverse || s.normalize < 0 || s.normalize > kNormTransparentOnly))
-        return hipErrorInvalidValue;  // normalisation exists for the BC1 forward transform only
+    if (!normalization_is_valid(fmt, inverse, s))
+        return hipErrorInvalidValue;
 
     if (r.num_blocks > kMaxBlocksPerLaunch) {
         const uint64_t block_bytes = fmt_block(fmt);
@@ -392,7 +419,9 @@ hipError_t launch_transform(Format fmt, bool inverse, const Settings& s_arg, con
 
     const bool sa = s.split_alpha;
     const bool sc = s.split_colour;
-    const bool normalizing = s.normalize != kNormNone;
+    const bool normalizing = s.normalize != kNormNone || s.normalize_alpha != kAlphaNone;
+    // BC2 / BC3: the modes travel as an argument of the launch (bcn_device.h, kNormFromArgument); (None, None) is the plain transform
+    const int norm_modes = (fmt == kBc2 || fmt == kBc3) ? pack_norm_modes(s.normalize_alpha, s.normalize) : 0;
     KernelSet ks;
     switch (fmt) {
     case kBc1:
@@ -401,8 +430,8 @@ hipError_t launch_transform(Format fmt, bool inverse, const Settings& s_arg, con
         else if (s.normalize == kNormTransparentOnly) ks = pick_bc1_norm<kNormTransparentOnly>(s.variant, sc);
         else ks = pick_variant<kBc1>(s.variant, false, sc, inverse);
         break;
-    case kBc2: ks = pick_variant<kBc2>(s.variant, false, sc, inverse); break;
-    case kBc3: ks = pick_variant<kBc3>(s.variant, sa, sc, inverse); break;
+    case kBc2: ks = norm_modes ? bc23_norm_kernels(kBc2, s.variant, false, sc) : pick_variant<kBc2>(s.variant, false, sc, inverse); break;
+    case kBc3: ks = norm_modes ? bc23_norm_kernels(kBc3, s.variant, sa, sc) : pick_variant<kBc3>(s.variant, sa, sc, inverse); break;
     case kBc4: ks = pick_bc45<kBc4>(sa, inverse); break;
     case kBc5: ks = pick_bc45<kBc5>(sa, inverse); break;
     default: return hipErrorInvalidValue;
@@ -428,7 +457,7 @@ hipError_t launch_transform(Format fmt, bool inverse, const Settings& s_arg, con
             return hipSuccess;
         const uint64_t grid = (count + kThreads - 1) / kThreads;   // count <= 2^31 blocks, one per thread
         hipLaunchKernelGGL(ks.generic, dim3((unsigned)grid), dim3(kThreads), 0, stream, src8, dst8, r.total_blocks,
-                           r.first_block, local_first, count);
+                           r.first_block, local_first, count | ((uint64_t)norm_modes << 56));
         return hipGetLastError();
     };
     {
@@ -458,7 +487,7 @@ hipError_t launch_transform(Format fmt, bool inverse, const Settings& s_arg, con
             }
             fill_gbase(sh, S, r.total_blocks, r.first_block);
             sh.natural = (force_bits & 0x20) ? 0 : shifts_are_natural(S, sh.d);
-            sh.halo_vecs = halo ? (halo_blocks + 16 / fmt_block(fmt) - 1) / (16 / fmt_block(fmt)) : 0;
+            sh.halo_vecs = (halo ? (halo_blocks + 16 / fmt_block(fmt) - 1) / (16 / fmt_block(fmt)) : 0) | (norm_modes << kNormModesShift);
             sh.xcd_remap = remap_override >= 0 ? remap_override : halo ? 0 : 1;
             sh.skip_partial = (force_bits & 0x10) ? 1 : 0;
             sh.line_policy = !first_form ? ((force_bits & 0x800) ? 1 : 3) : (force_bits & 0x40) ? 0 : (force_bits & 0x80) ? 2 : 1;
@@ -485,16 +514,17 @@ hipError_t launch_transform(Format fmt, bool inverse, const Settings& s_arg, con
             const uint64_t tiles = r.num_blocks / T;
             if (tiles > 0) {
                 hipLaunchKernelGGL(ks.tiled[threads_slot(threads)], dim3((unsigned)tiles), dim3(threads), 0, stream, src8, dst8,
-                                   r.total_blocks, r.first_block, remap_override >= 0 ? remap_override : 0, (int64_t)0, (int64_t)0);
+                                   r.total_blocks, r.first_block, (remap_override >= 0 ? remap_override : 0) | (norm_modes << kNormModesShift),
+                                   (int64_t)0, (int64_t)0);
                 if (hipError_t e = hipGetLastError(); e != hipSuccess)
                     return e;
             }
             return element_range(tiles * T, r.num_blocks - tiles * T);
         }
     }
-    const int aligned_flags = remap_override >= 0 ? remap_override : 0;
+    const int aligned_flags = (remap_override >= 0 ? remap_override : 0) | (norm_modes << kNormModesShift);
 #else
-    const int aligned_flags = 0;
+    const int aligned_flags = norm_modes << kNormModesShift;
 #endif
 
     return plan_launches(fmt, inverse, sa, sc, soa, r, force_bits, threads, halo_threads_override, [&](const PlannedLaunch& l) {
@@ -504,6 +534,7 @@ hipError_t launch_transform(Format fmt, bool inverse, const Settings& s_arg, con
             return hipGetLastError();
         }
         Shifts sh = l.sh;
+        sh.halo_vecs |= norm_modes << kNormModesShift;   // (0 in every launch but those of the BC2 / BC3 normalising kernel sets)
 #ifdef DXTLT_EXPERIMENTS
         sh.xcd_remap = remap_override >= 0 ? remap_override : l.kind == 1 ? 0 : 1;
         sh.skip_partial = (force_bits & 0x10) ? 1 : 0;

@@ -31,7 +31,8 @@ struct Settings {
     int variant;        // core YCoCgVariant numbering: 0 None, 1..3 (BC4 / BC5: ignored, always 0)
     bool split_alpha;   // BC3; BC4 / BC5: split_endpoints
     bool split_colour;  // BC1 / BC2 / BC3 only
-    int normalize = 0;  // BC1 forward only: ColorNormalizationMode 0 None, 1 Color0Only, 2 ReplicateColor (fused)
+    int normalize = 0;  // BC1 / BC2 / BC3 forward only: ColorNormalizationMode 0 None, 1 Color0Only, 2 ReplicateColor (fused)
+    int normalize_alpha = 0;  // BC3 forward only: AlphaNormalizationMode 0..3 (bc23_normalize.h), fused; 0 for every other call
 };
 
 // One contiguous range of blocks of a larger block array (the whole array when first_block == 0 and

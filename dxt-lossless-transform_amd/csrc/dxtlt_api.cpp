@@ -76,8 +76,21 @@ int32_t check_common(int32_t format, size_t len, uint8_t mode, const void* a, co
     return DXTLT_OK;
 }
 
+// Block normalisation fused into a transform: BC1 / BC2 / BC3 forward only.  BC1: colour modes 0..2, and 3 = transparent blocks
+// only -- internal, used by the auto transform (bc1_normalize.h); the public entry points check color_mode <= 2 before they
+// get here.  BC2 / BC3 (normalize23_api.cpp): colour modes 0..2, and for BC3 alone an alpha mode 0..3.
+int32_t check_normalization(int32_t format, bool inverse, uint8_t normalize, uint8_t normalize_alpha)
+{
+    if ((normalize != 0 || normalize_alpha != 0) &&
+        (inverse || format < 1 || format > 3 || normalize > (format == 1 ? 3 : 2) || normalize_alpha > (format == 3 ? 3 : 0)))
+        return fail(DXTLT_E_INVALID_ARGUMENT,
+                    "block normalisation: BC1 / BC2 / BC3 forward only, color_mode 0..2, alpha_mode 0..3 for BC3 and 0 otherwise");
+    return DXTLT_OK;
+}
+
 int32_t device_range(int32_t format, bool inverse, const void* d_src, void* d_dst, uint64_t total, uint64_t first,
-                     uint64_t num, uint8_t mode, bool sa, bool sc, hipStream_t stream, uint8_t normalize = 0)
+                     uint64_t num, uint8_t mode, bool sa, bool sc, hipStream_t stream, uint8_t normalize = 0,
+                     uint8_t normalize_alpha = 0)
 {
     if (format < 1 || format > 5)
         return fail(DXTLT_E_INVALID_ARGUMENT, "format must be 1 (BC1), 2 (BC2), 3 (BC3), 4 (BC4) or 5 (BC5)");
@@ -91,21 +104,19 @@ int32_t device_range(int32_t format, bool inverse, const void* d_src, void* d_ds
         return DXTLT_OK;
     if (d_src == nullptr || d_dst == nullptr)
         return fail(DXTLT_E_INVALID_ARGUMENT, "NULL device buffer with a non-empty range");
-    // 3 = transparent blocks only: internal, used by the auto transform (bc1_normalize.h); the public entry points
-    // check color_mode <= 2 before they get here
-    if (normalize != 0 && (format != 1 || inverse || normalize > 3))
-        return fail(DXTLT_E_INVALID_ARGUMENT, "block normalisation: BC1 forward only, color_mode 0..2");
-    Settings s{(int)mode, sa, sc, (int)normalize};
+    if (int32_t rc = check_normalization(format, inverse, normalize, normalize_alpha); rc != DXTLT_OK)
+        return rc;
+    Settings s{(int)mode, sa, sc, (int)normalize, (int)normalize_alpha};
     Range r{total, first, num};
     dxtlt::LaunchTuning t = current_tuning();
     HIP_TRY(dxtlt::launch_transform((Format)format, inverse, s, d_src, d_dst, r, stream, &t), "kernel launch");
     return DXTLT_OK;
 }
 
-dxtlt_host::Launch launch_of(int32_t format, uint8_t mode, bool sa, bool sc, uint8_t normalize)
+dxtlt_host::Launch launch_of(int32_t format, uint8_t mode, bool sa, bool sc, uint8_t normalize, uint8_t normalize_alpha = 0)
 {
     return [=](bool inverse, const void* src, void* dst, uint64_t total, uint64_t first, uint64_t count, hipStream_t stream) {
-        return device_range(format, inverse, src, dst, total, first, count, mode, sa, sc, stream, normalize);
+        return device_range(format, inverse, src, dst, total, first, count, mode, sa, sc, stream, normalize, normalize_alpha);
     };
 }
 
@@ -126,13 +137,13 @@ dxtlt_host::StreamLayout dxtlt_host::block_layout(int32_t format, bool sa, bool 
 }
 
 int32_t dxtlt_host::enqueue(int32_t format, bool inverse, const void* d_src, void* d_dst, uint64_t blocks, uint8_t mode,
-                            bool sa, bool sc, hipStream_t stream, uint8_t normalize)
+                            bool sa, bool sc, hipStream_t stream, uint8_t normalize, uint8_t normalize_alpha)
 {
-    return device_range(format, inverse, d_src, d_dst, blocks, 0, blocks, mode, sa, sc, stream, normalize);
+    return device_range(format, inverse, d_src, d_dst, blocks, 0, blocks, mode, sa, sc, stream, normalize, normalize_alpha);
 }
 
 int32_t dxtlt_host::transform(int32_t format, bool inverse, const uint8_t* in, uint8_t* out, size_t len, uint8_t mode,
-                              bool sa, bool sc, uint8_t normalize)
+                              bool sa, bool sc, uint8_t normalize, uint8_t normalize_alpha)
 {
     int32_t rc = check_common(format, len, mode, in, out);
     if (rc != DXTLT_OK)
@@ -140,7 +151,7 @@ int32_t dxtlt_host::transform(int32_t format, bool inverse, const uint8_t* in, u
     if (len == 0)
         return DXTLT_OK;  // zero blocks: nothing to do, no device needed
     const StreamLayout S = block_layout(format, sa, sc);
-    return host_round_trip(S, launch_of(format, mode, sa, sc, normalize), inverse, in, out, len / S.block_bytes);
+    return host_round_trip(S, launch_of(format, mode, sa, sc, normalize, normalize_alpha), inverse, in, out, len / S.block_bytes);
 }
 
 extern "C" {
@@ -320,6 +331,11 @@ size_t dxtlt_host_route_threshold_bytes(void)
 void dxtlt_set_host_route_threshold_bytes(size_t bytes) { g_host_route_threshold.store(bytes); }
 
 int32_t dxtlt_tuning_mask(void) { return dxtlt::launch_force_mask(); }
+
+int32_t dxtlt_debug_check_normalization(int32_t format, int32_t inverse, uint8_t color_mode, uint8_t alpha_mode)
+{
+    return check_normalization(format, inverse != 0, color_mode, alpha_mode);
+}
 
 int32_t dxtlt_debug_plan_transform(int32_t format, int32_t inverse, int32_t variant, int32_t split_alpha, int32_t split_colour,
                                    uint64_t src_address, uint64_t dst_address, uint64_t total_blocks, uint64_t first_block,

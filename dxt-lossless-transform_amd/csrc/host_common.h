@@ -66,9 +66,10 @@ using Launch = std::function<int32_t(bool inverse, const void* d_src, void* d_ds
                                      uint64_t count, hipStream_t stream)>;
 
 // Host pointers in/out, whole buffer, synchronous (H2D + kernel + D2H on the current device).
-// `normalize` (BC1 forward only): ColorNormalizationMode fused into the transform, 0 = none.
+// `normalize` (BC1 / BC2 / BC3 forward only): ColorNormalizationMode fused into the transform, 0 = none;
+// `normalize_alpha` (BC3 forward only): AlphaNormalizationMode, 0 = none.
 int32_t transform(int32_t format, bool inverse, const uint8_t* in, uint8_t* out, size_t len, uint8_t mode,
-                  bool split_alpha, bool split_colour, uint8_t normalize = 0);
+                  bool split_alpha, bool split_colour, uint8_t normalize = 0, uint8_t normalize_alpha = 0);
 
 // ---- host_staging.cpp -------------------------------------------------------------------------------
 // This thread's staging context on the current device: two device buffers of at least `bytes` and a stream.
@@ -173,7 +174,7 @@ int bind_this_thread_near_device(int device);
 
 // Enqueue one whole-buffer transform on device pointers.
 int32_t enqueue(int32_t format, bool inverse, const void* d_src, void* d_dst, uint64_t blocks, uint8_t mode,
-                bool split_alpha, bool split_colour, hipStream_t stream, uint8_t normalize = 0);
+                bool split_alpha, bool split_colour, hipStream_t stream, uint8_t normalize = 0, uint8_t normalize_alpha = 0);
 
 // Per-thread device resources of the other translation units, freed by dxtlt_release_thread_resources().
 void release_normalize_thread_flag();   // normalize_api.cpp

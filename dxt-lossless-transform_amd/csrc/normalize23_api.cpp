@@ -122,9 +122,68 @@ int32_t all_modes_host(int fmt, const uint8_t* in, uint8_t* const* outs, size_t 
     return kOk;
 }
 
+// The fused normalise + transform calls answer every defect of their arguments -- a mode out of range, a length that is no
+// whole number of blocks, a NULL pointer with len > 0 -- with kInvalidArgument, before any device work.
+int32_t check_fused(int fmt, const void* in, const void* out, size_t len, uint8_t alpha_mode, uint8_t color_mode,
+                    uint8_t decorrelation_mode)
+{
+    if (int32_t rc = check_modes(fmt, alpha_mode, color_mode); rc != kOk)
+        return rc;
+    if (decorrelation_mode > 3)
+        return fail(kInvalidArgument, "decorrelation_mode must be 0..3");
+    if (len % 16 != 0)
+        return fail(kInvalidArgument, "len is not a multiple of 16");
+    if (len > 0 && (in == nullptr || out == nullptr))
+        return fail(kInvalidArgument, "NULL buffer with len > 0");
+    return kOk;
+}
+
+// transform_bcN_with_settings(normalize_blocks(input, modes), settings) in one pass over the data: the modes go into the forward
+// tile kernels (bcn_device.h, kNormFromArgument), the host call takes the common host paths (host_staging.cpp)
+int32_t fused_host(int fmt, const uint8_t* in, uint8_t* out, size_t len, uint8_t alpha_mode, uint8_t color_mode, uint8_t mode,
+                   bool sa, bool sc)
+{
+    if (int32_t rc = check_fused(fmt, in, out, len, alpha_mode, color_mode, mode); rc != kOk)
+        return rc;
+    return dxtlt_host::transform(fmt, false, in, out, len, mode, sa, sc, color_mode, alpha_mode);
+}
+
+int32_t fused_device(int fmt, const void* d_in, void* d_out, size_t len, uint8_t alpha_mode, uint8_t color_mode, uint8_t mode,
+                     bool sa, bool sc, void* stream)
+{
+    if (int32_t rc = check_fused(fmt, d_in, d_out, len, alpha_mode, color_mode, mode); rc != kOk)
+        return rc;
+    return dxtlt_host::enqueue(fmt, false, d_in, d_out, len / 16, mode, sa, sc, static_cast<hipStream_t>(stream), color_mode,
+                               alpha_mode);
+}
+
 }  // namespace
 
 extern "C" {
+
+int32_t dxtlt_transform_bc2_with_normalize_blocks(const uint8_t* i, uint8_t* o, size_t len, uint8_t color_mode,
+                                                  uint8_t decorrelation_mode, bool split_colour_endpoints)
+{
+    return fused_host(2, i, o, len, 0, color_mode, decorrelation_mode, false, split_colour_endpoints);
+}
+int32_t dxtlt_transform_bc2_with_normalize_blocks_device(const void* i, void* o, size_t len, uint8_t color_mode,
+                                                         uint8_t decorrelation_mode, bool split_colour_endpoints, void* st)
+{
+    return fused_device(2, i, o, len, 0, color_mode, decorrelation_mode, false, split_colour_endpoints, st);
+}
+int32_t dxtlt_transform_bc3_with_normalize_blocks(const uint8_t* i, uint8_t* o, size_t len, uint8_t alpha_mode, uint8_t color_mode,
+                                                  uint8_t decorrelation_mode, bool split_alpha_endpoints,
+                                                  bool split_colour_endpoints)
+{
+    return fused_host(3, i, o, len, alpha_mode, color_mode, decorrelation_mode, split_alpha_endpoints, split_colour_endpoints);
+}
+int32_t dxtlt_transform_bc3_with_normalize_blocks_device(const void* i, void* o, size_t len, uint8_t alpha_mode, uint8_t color_mode,
+                                                         uint8_t decorrelation_mode, bool split_alpha_endpoints,
+                                                         bool split_colour_endpoints, void* st)
+{
+    return fused_device(3, i, o, len, alpha_mode, color_mode, decorrelation_mode, split_alpha_endpoints, split_colour_endpoints,
+                        st);
+}
 
 int32_t dxtlt_bc2_normalize_blocks(const uint8_t* i, uint8_t* o, size_t len, uint8_t color_mode)
 {

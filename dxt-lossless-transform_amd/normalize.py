@@ -65,6 +65,14 @@ def _l():
         l.dxtlt_transform_bc1_with_normalize_blocks.restype = i32
         l.dxtlt_transform_bc1_with_normalize_blocks_device.argtypes = [vp, vp, sz, u8, u8, b, vp]
         l.dxtlt_transform_bc1_with_normalize_blocks_device.restype = i32
+        # BC2 / BC3 (include/dxtlt_bc23_normalize.h)
+        l.dxtlt_transform_bc2_with_normalize_blocks.argtypes = [vp, vp, sz, u8, u8, b]
+        l.dxtlt_transform_bc2_with_normalize_blocks_device.argtypes = [vp, vp, sz, u8, u8, b, vp]
+        l.dxtlt_transform_bc3_with_normalize_blocks.argtypes = [vp, vp, sz, u8, u8, u8, b, b]
+        l.dxtlt_transform_bc3_with_normalize_blocks_device.argtypes = [vp, vp, sz, u8, u8, u8, b, b, vp]
+        for fmt in ("bc2", "bc3"):
+            getattr(l, f"dxtlt_transform_{fmt}_with_normalize_blocks").restype = i32
+            getattr(l, f"dxtlt_transform_{fmt}_with_normalize_blocks_device").restype = i32
         _declared = True
     return l
 
@@ -175,3 +183,39 @@ def transform_bc1_with_normalize_blocks(input, output,
         with torch.cuda.device(src.device):
             _check(_l().dxtlt_transform_bc1_with_normalize_blocks_device(src.ptr, dst.ptr, src.nbytes, *args,
                                                                          _stream(src.device)))
+
+
+def _fused_bc23(fmt: str, input, output, mode_args: tuple, settings_args: tuple) -> None:
+    from . import InvalidLength, OutputBufferTooSmall, _Buf
+
+    src, dst = _Buf(input, False), _Buf(output, True)
+    if src.nbytes % 16 != 0:
+        raise InvalidLength(src.nbytes)
+    if dst.nbytes < src.nbytes:
+        raise OutputBufferTooSmall(src.nbytes, dst.nbytes)
+    if (src.device is None) != (dst.device is None):
+        raise TypeError("input and output must both be host buffers or both be device tensors")
+    name = f"dxtlt_transform_{fmt}_with_normalize_blocks"
+    if src.device is None:
+        _check(getattr(_l(), name)(src.ptr, dst.ptr, src.nbytes, *mode_args, *settings_args))
+    else:
+        import torch
+
+        with torch.cuda.device(src.device):
+            _check(getattr(_l(), name + "_device")(src.ptr, dst.ptr, src.nbytes, *mode_args, *settings_args, _stream(src.device)))
+
+
+def transform_bc2_with_normalize_blocks(input, output, color_mode: ColorNormalizationMode, decorrelation_mode: int = 1,
+                                        split_colour_endpoints: bool = True) -> None:
+    """``transform_bc2_with_settings(normalize_blocks(input, color_mode), settings)`` in one pass, normalisation fused into the
+    transform kernel (include/dxtlt_bc23_normalize.h; upstream has no such function).  ``decorrelation_mode`` in the core
+    YCoCgVariant numbering.  Undo with ``untransform_bc2_with_settings``: it yields the normalised blocks."""
+    _fused_bc23("bc2", input, output, (int(color_mode),), (int(decorrelation_mode), bool(split_colour_endpoints)))
+
+
+def transform_bc3_with_normalize_blocks(input, output, alpha_mode, color_mode: ColorNormalizationMode, decorrelation_mode: int = 1,
+                                        split_alpha_endpoints: bool = True, split_colour_endpoints: bool = True) -> None:
+    """``transform_bc3_with_settings(normalize_blocks(input, alpha_mode, color_mode), settings)`` in one pass; ``alpha_mode`` is a
+    ``normalize23.AlphaNormalizationMode``.  Undo with ``untransform_bc3_with_settings``: it yields the normalised blocks."""
+    _fused_bc23("bc3", input, output, (int(alpha_mode), int(color_mode)),
+                (int(decorrelation_mode), bool(split_alpha_endpoints), bool(split_colour_endpoints)))

@@ -443,6 +443,15 @@ inline void normalize_split_blocks_in_place(const uint8_t* alpha_ptr, uint8_t* c
     detail::check_device(dxtlt_bc2_normalize_split_blocks_in_place(alpha_ptr, colors_ptr, indices_ptr, num_blocks,
                                                                    static_cast<uint8_t>(color_mode)));
 }
+// transform_bc2_with_settings(normalize_blocks(input, color_mode), settings) in one pass, normalisation fused into the transform
+// kernel (dxtlt_bc23_normalize.h; no upstream counterpart); untransform_bc2_with_settings yields the normalised blocks
+inline void transform_bc2_with_normalize_blocks(const uint8_t* input_ptr, uint8_t* output_ptr, size_t len,
+                                                ColorNormalizationMode color_mode, Bc2TransformSettings s = {})
+{
+    detail::check_device(dxtlt_transform_bc2_with_normalize_blocks(input_ptr, output_ptr, len, static_cast<uint8_t>(color_mode),
+                                                                   static_cast<uint8_t>(s.decorrelation_mode),
+                                                                   s.split_colour_endpoints));
+}
 }  // namespace bc2
 
 namespace bc3 {
@@ -474,6 +483,17 @@ inline void normalize_split_blocks_in_place(uint8_t* alpha_endpoints_ptr, uint8_
                                                                    color_indices_ptr, num_blocks,
                                                                    static_cast<uint8_t>(alpha_mode),
                                                                    static_cast<uint8_t>(color_mode)));
+}
+// transform_bc3_with_settings(normalize_blocks(input, alpha_mode, color_mode), settings) in one pass (dxtlt_bc23_normalize.h; no
+// upstream counterpart); untransform_bc3_with_settings yields the normalised blocks
+inline void transform_bc3_with_normalize_blocks(const uint8_t* input_ptr, uint8_t* output_ptr, size_t len,
+                                                AlphaNormalizationMode alpha_mode, ColorNormalizationMode color_mode,
+                                                Bc3TransformSettings s = {})
+{
+    detail::check_device(dxtlt_transform_bc3_with_normalize_blocks(input_ptr, output_ptr, len, static_cast<uint8_t>(alpha_mode),
+                                                                   static_cast<uint8_t>(color_mode),
+                                                                   static_cast<uint8_t>(s.decorrelation_mode),
+                                                                   s.split_alpha_endpoints, s.split_colour_endpoints));
 }
 }  // namespace bc3
 

@@ -273,6 +273,10 @@ typedef struct DxtltDebugPlannedLaunch {
 int32_t dxtlt_debug_plan_transform(int32_t format, int32_t inverse, int32_t variant, int32_t split_alpha, int32_t split_colour,
                                    uint64_t src_address, uint64_t dst_address, uint64_t total_blocks, uint64_t first_block,
                                    uint64_t num_blocks, DxtltDebugPlannedLaunch *out, int32_t cap);
+/* A call that normalises blocks inside the transform (dxtlt_bc1_normalize.h, dxtlt_bc23_normalize.h) launches the plan above:
+ * the modes pick another kernel set, not another plan.  Test hook, no device needed: the launch layer's answer to a
+ * (format, direction, colour mode, alpha mode) -- DXTLT_OK, or DXTLT_E_INVALID_ARGUMENT and a dxtlt_last_error() text. */
+int32_t dxtlt_debug_check_normalization(int32_t format, int32_t inverse, uint8_t color_mode, uint8_t alpha_mode);
 
 /* The same for HOST buffers (d_input / d_output of every item are host pointers here) -- the reference's own call
  * pattern: one call per file, host pointers, textures of 0.1-20 MiB (tools/dxt-lossless-transform-cli/src/commands/

@@ -181,3 +181,17 @@ extern "C" {
     /// every item's best settings chosen and applied in one call: one stream wait, launches independent of `count`
     pub fn dxtlt_transform_batch_auto_device(items: *mut DxtltBatchAutoItem, count: usize, hip_stream: *mut c_void) -> i32;
 }
+
+// ---- include/dxtlt_bc23_normalize.h: BC2 / BC3 block normalisation fused into the forward transform (no upstream counterpart;
+// the output is transform_bcN_with_settings(normalize_blocks(input, modes), settings), byte for byte)
+extern "C" {
+    pub fn dxtlt_transform_bc2_with_normalize_blocks(input_ptr: *const u8, output_ptr: *mut u8, len: usize, color_mode: u8,
+        decorrelation_mode: u8, split_colour_endpoints: bool) -> i32;
+    pub fn dxtlt_transform_bc2_with_normalize_blocks_device(d_input: *const c_void, d_output: *mut c_void, len: usize,
+        color_mode: u8, decorrelation_mode: u8, split_colour_endpoints: bool, hip_stream: *mut c_void) -> i32;
+    pub fn dxtlt_transform_bc3_with_normalize_blocks(input_ptr: *const u8, output_ptr: *mut u8, len: usize, alpha_mode: u8,
+        color_mode: u8, decorrelation_mode: u8, split_alpha_endpoints: bool, split_colour_endpoints: bool) -> i32;
+    pub fn dxtlt_transform_bc3_with_normalize_blocks_device(d_input: *const c_void, d_output: *mut c_void, len: usize,
+        alpha_mode: u8, color_mode: u8, decorrelation_mode: u8, split_alpha_endpoints: bool, split_colour_endpoints: bool,
+        hip_stream: *mut c_void) -> i32;
+}
