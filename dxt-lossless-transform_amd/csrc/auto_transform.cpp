@@ -387,7 +387,7 @@ int32_t auto_on_device(int32_t format, const void* d_in, void* d_out, size_t len
         for (int i = 0; i < o.count; ++i) {
             const Candidate c = o.order[i];
             uint8_t* dst = arena != nullptr ? arena + (size_t)i * len : out8;
-            if (int32_t rc = enqueue(format, false, d_in, dst, blocks, c.mode, c.split_alpha, c.split_colour, st))
+            if (int32_t rc = enqueue(format, false, d_in, dst, blocks, dxtlt::Settings{c.mode, c.split_alpha, c.split_colour}, st))
                 return rc;
             if (arena == nullptr)
                 last = i;
@@ -402,7 +402,7 @@ int32_t auto_on_device(int32_t format, const void* d_in, void* d_out, size_t len
 
     *best = o.order[pick];
     if (pick != last) {
-        if (int32_t rc = enqueue(format, false, d_in, d_out, blocks, best->mode, best->split_alpha, best->split_colour, st))
+        if (int32_t rc = enqueue(format, false, d_in, d_out, blocks, dxtlt::Settings{best->mode, best->split_alpha, best->split_colour}, st))
             return rc;
     }
     std::copy(total, total + o.count, t_last_totals);
@@ -565,7 +565,7 @@ int32_t dxtlt_host::transform_auto(int32_t format, const uint8_t* in, uint8_t* o
         if (format >= 4 && !t_no_arena) {
             arena = static_cast<uint8_t*>(g_arena.get(2 * len));
             for (int i = 0; i < o.count && arena != nullptr; ++i)
-                if (int32_t rc = enqueue(format, false, d_in, arena + (size_t)i * len, blocks, 0, o.order[i].split_alpha, false, st))
+                if (int32_t rc = enqueue(format, false, d_in, arena + (size_t)i * len, blocks, dxtlt::Settings{0, o.order[i].split_alpha, false}, st))
                     return rc;
         } else if (format <= 3 && fused && !t_no_arena) {
             distinct = dxtlt::auto_sections((dxtlt::Format)format, use_all, blocks);
@@ -648,7 +648,7 @@ int32_t dxtlt_host::transform_auto(int32_t format, const uint8_t* in, uint8_t* o
                 seen[1] = slot(i) + second;
             } else if (len > 0) {
                 if (source == Source::kOneByOne) {
-                    if (int32_t rc = enqueue(format, false, d_in, d_out, blocks, c.mode, c.split_alpha, c.split_colour, st))
+                    if (int32_t rc = enqueue(format, false, d_in, d_out, blocks, dxtlt::Settings{c.mode, c.split_alpha, c.split_colour}, st))
                         return rc;
                     last = i;
                 }
@@ -672,7 +672,7 @@ int32_t dxtlt_host::transform_auto(int32_t format, const uint8_t* in, uint8_t* o
     const Candidate won = o.order[best];
     if (len > 0) {
         if (source == Source::kFused || (source == Source::kOneByOne && best != last))
-            if (int32_t rc = enqueue(format, false, d_in, d_out, blocks, won.mode, won.split_alpha, won.split_colour, st))
+            if (int32_t rc = enqueue(format, false, d_in, d_out, blocks, dxtlt::Settings{won.mode, won.split_alpha, won.split_colour}, st))
                 return rc;
         const void* result = source == Source::kSideBySide ? static_cast<const void*>(arena + (size_t)best * len) : d_out;
         HIP_TRY(hipMemcpyAsync(out, result, len, hipMemcpyDeviceToHost, st), "D2H result");

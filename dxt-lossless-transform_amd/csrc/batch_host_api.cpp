@@ -123,8 +123,9 @@ int32_t transform_alone(const DxtltBatchItem& it)
                                pixel_layout_of(it.split_alpha_endpoints != 0, it.split_colour_endpoints != 0));
     if (dxtlt::granule::is_granule_format(it.format))
         return granule_host_call(it.format, it.inverse != 0, in, out, it.len);
-    return transform(it.format, it.inverse != 0, in, out, it.len, it.decorrelation_mode,
-                     dxtlt::format_has_alpha_split(it.format) && it.split_alpha_endpoints, it.split_colour_endpoints != 0);
+    return transform(it.format, it.inverse != 0, in, out, it.len,
+                     dxtlt::Settings{it.decorrelation_mode, dxtlt::format_has_alpha_split(it.format) && it.split_alpha_endpoints,
+                                     it.split_colour_endpoints != 0});
 }
 
 // This thread's device slots, stream and pinned arenas, the download stream and the events of a call

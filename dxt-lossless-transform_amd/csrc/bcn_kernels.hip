@@ -334,13 +334,11 @@ bool normalization_is_valid(Format fmt, bool inverse, const Settings& s)
         return true;
     if (inverse || s.normalize < 0 || s.normalize_alpha < 0)
         return false;
-    switch (fmt) {
-    case kBc1: return s.normalize <= kNormTransparentOnly && s.normalize_alpha == kAlphaNone;
-    case kBc2: return s.normalize <= kNormReplicateColor && s.normalize_alpha == kAlphaNone;
-    case kBc3: return s.normalize <= kNormReplicateColor && s.normalize_alpha <= kAlphaOpaqueZeroAlphaMaxIndices;
-    default: return false;
-    }
+    return s.normalize <= norm_limits(fmt).colour_internal && s.normalize_alpha <= norm_limits(fmt).alpha;
 }
+static_assert(norm_limits(kBc1).colour_internal == kNormTransparentOnly && norm_limits(kBc3).colour == kNormReplicateColor &&
+                  norm_limits(kBc3).alpha == kAlphaOpaqueZeroAlphaMaxIndices,
+              "norm_limits (bcn_launch.h) against the mode enums of bc1_normalize.h / bc23_normalize.h");
 
 int aligned_tile_threads(Format fmt, bool inverse, bool normalizing, const LaunchTuning* tuning)
 {

@@ -35,6 +35,23 @@ struct Settings {
     int normalize_alpha = 0;  // BC3 forward only: AlphaNormalizationMode 0..3 (bc23_normalize.h), fused; 0 for every other call
 };
 
+// The legal block-normalisation modes, stated once: per format the highest ColorNormalizationMode a public entry point takes,
+// the highest the launch layer takes (BC1: 3 = transparent blocks only, internal to the auto transform, bc1_normalize.h) and the
+// highest AlphaNormalizationMode.  Every check -- the C ABI (normalize_api.cpp, dxtlt_api.cpp), launch_transform and the
+// launch_normalize_* calls -- reads it from here.
+struct NormLimits {
+    int colour, colour_internal, alpha;
+};
+constexpr NormLimits norm_limits(int fmt)
+{
+    return fmt == 1 ? NormLimits{2, 3, 0} : fmt == 2 ? NormLimits{2, 2, 0} : fmt == 3 ? NormLimits{2, 2, 3} : NormLimits{0, 0, 0};
+}
+// the modes of a stand-alone normalisation call of format 1..3
+constexpr bool norm_modes_in_range(int fmt, int alpha_mode, int color_mode)
+{
+    return alpha_mode >= 0 && alpha_mode <= norm_limits(fmt).alpha && color_mode >= 0 && color_mode <= norm_limits(fmt).colour;
+}
+
 // One contiguous range of blocks of a larger block array (the whole array when first_block == 0 and
 // num_blocks == total_blocks).  `aos` points at the AoS data of the RANGE's first block; `soa` points
 // at byte 0 of the WHOLE transformed buffer (stream bases are functions of total_blocks).
@@ -80,7 +97,7 @@ hipError_t launch_transform(Format fmt, bool inverse, const Settings& s, const v
 hipError_t launch_fill_splitmix64(void* dst, size_t len_bytes, uint64_t seed, uint64_t first_qword,
                                   hipStream_t stream);
 
-// BC1 block normalisation (bc1_normalize.hip; reference experimental/normalize_blocks/normalize.rs).  `mode` is the
+// BC1 block normalisation (normalize_kernels.hip; reference experimental/normalize_blocks/normalize.rs).  `mode` is the
 // ColorNormalizationMode (0 None, 1 Color0Only, 2 ReplicateColor).  All enqueue on `stream`.
 //   blocks:     in -> out, AoS blocks; in == out allowed (in place), partial overlap is not
 //   split:      colours (4 bytes per block) and indices (4 bytes per block) in two separate arrays, in place
@@ -106,7 +123,7 @@ hipError_t launch_color565_recorrelate_split(const void* src0, const void* src1,
                                              hipStream_t stream);
 hipError_t launch_split_565_color_endpoints(const void* in, void* out, uint64_t len_bytes, hipStream_t stream);
 
-// BC2 / BC3 block normalisation (bc23_normalize.hip; reference bc2/bc3 experimental/normalize_blocks/normalize.rs).
+// BC2 / BC3 block normalisation (normalize_kernels.hip; reference bc2/bc3 experimental/normalize_blocks/normalize.rs).
 // fmt 2 or 3; alpha_mode = AlphaNormalizationMode (BC3 only, 0 for BC2), color_mode = ColorNormalizationMode.
 //   all_modes: outs[3] for BC2 (colour modes), outs[12] for BC3 ([alpha_mode * 3 + colour_mode])
 //   split:     the reference's section layout -- BC2 colours / indices (4 + 4 bytes per block; alpha untouched),

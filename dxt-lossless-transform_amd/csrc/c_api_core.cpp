@@ -69,7 +69,7 @@ CoreResult run(int32_t format, bool inverse, const uint8_t* input, size_t input_
         return {kOutputBufferTooSmall};
     if (mode > 3)
         return {kTransformationError};  // not a YCoCgVariant; the reference would be UB here
-    return {map_status(dxtlt_host::transform(format, inverse, input, output, input_len, mode, sa, sc))};
+    return {map_status(dxtlt_host::transform(format, inverse, input, output, input_len, dxtlt::Settings{mode, sa, sc}))};
 }
 
 CoreResult run_auto(int32_t format, const uint8_t* data, size_t data_len, uint8_t* output, size_t output_len,

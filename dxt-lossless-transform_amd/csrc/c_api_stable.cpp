@@ -89,8 +89,8 @@ StableResult manual_run(int32_t format, bool inverse, const uint8_t* input, size
         return {kInvalidLength};
     if (output_len < input_len)
         return {kOutputBufferTooSmall};
-    return {map_status(dxtlt_host::transform(format, inverse, input, output, input_len, b->mode_core,
-                                             format == 3 && b->split_alpha, b->split_colour))};
+    return {map_status(dxtlt_host::transform(format, inverse, input, output, input_len,
+                                             dxtlt::Settings{b->mode_core, format == 3 && b->split_alpha, b->split_colour}))};
 }
 
 StableResult auto_run(int32_t format, AutoBuilder* b, const uint8_t* data, size_t data_len, uint8_t* output,

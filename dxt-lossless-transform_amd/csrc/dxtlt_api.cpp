@@ -63,7 +63,7 @@ dxtlt::LaunchTuning current_tuning()
 // BC4 / BC5 (formats 4, 5; include/dxtlt_bc45.h) have no colour endpoints: their decorrelation mode and colour split are ignored
 inline bool ignores_colour_settings(int32_t format) { return !dxtlt::format_has_colour(format); }
 
-int32_t check_common(int32_t format, size_t len, uint8_t mode, const void* a, const void* b)
+int32_t check_common(int32_t format, size_t len, int mode, const void* a, const void* b)
 {
     if (format < 1 || format > 5)
         return fail(DXTLT_E_INVALID_ARGUMENT, "format must be 1 (BC1), 2 (BC2), 3 (BC3), 4 (BC4) or 5 (BC5)");
@@ -76,27 +76,27 @@ int32_t check_common(int32_t format, size_t len, uint8_t mode, const void* a, co
     return DXTLT_OK;
 }
 
-// Block normalisation fused into a transform: BC1 / BC2 / BC3 forward only.  BC1: colour modes 0..2, and 3 = transparent blocks
-// only -- internal, used by the auto transform (bc1_normalize.h); the public entry points check color_mode <= 2 before they
-// get here.  BC2 / BC3 (normalize23_api.cpp): colour modes 0..2, and for BC3 alone an alpha mode 0..3.
-int32_t check_normalization(int32_t format, bool inverse, uint8_t normalize, uint8_t normalize_alpha)
+// Block normalisation fused into a transform: BC1 / BC2 / BC3 forward only, in the modes of dxtlt::norm_limits (bcn_launch.h).
+// BC1's colour mode 3 = transparent blocks only is internal, used by the auto transform (bc1_normalize.h): the public entry points
+// (normalize_api.cpp) check color_mode <= 2 before they get here.
+int32_t check_normalization(int32_t format, bool inverse, int normalize, int normalize_alpha)
 {
+    const dxtlt::NormLimits limits = dxtlt::norm_limits(format);
     if ((normalize != 0 || normalize_alpha != 0) &&
-        (inverse || format < 1 || format > 3 || normalize > (format == 1 ? 3 : 2) || normalize_alpha > (format == 3 ? 3 : 0)))
+        (inverse || normalize > limits.colour_internal || normalize_alpha > limits.alpha))
         return fail(DXTLT_E_INVALID_ARGUMENT,
                     "block normalisation: BC1 / BC2 / BC3 forward only, color_mode 0..2, alpha_mode 0..3 for BC3 and 0 otherwise");
     return DXTLT_OK;
 }
 
 int32_t device_range(int32_t format, bool inverse, const void* d_src, void* d_dst, uint64_t total, uint64_t first,
-                     uint64_t num, uint8_t mode, bool sa, bool sc, hipStream_t stream, uint8_t normalize = 0,
-                     uint8_t normalize_alpha = 0)
+                     uint64_t num, Settings s, hipStream_t stream)
 {
     if (format < 1 || format > 5)
         return fail(DXTLT_E_INVALID_ARGUMENT, "format must be 1 (BC1), 2 (BC2), 3 (BC3), 4 (BC4) or 5 (BC5)");
     if (ignores_colour_settings(format))
-        mode = 0, sc = false;
-    if (mode > 3)
+        s.variant = 0, s.split_colour = false;
+    if (s.variant > 3)
         return fail(DXTLT_E_INVALID_ARGUMENT, "decorrelation_mode must be 0..3");
     if (first > total || num > total - first)
         return fail(DXTLT_E_INVALID_ARGUMENT, "block range exceeds total_blocks");
@@ -104,19 +104,18 @@ int32_t device_range(int32_t format, bool inverse, const void* d_src, void* d_ds
         return DXTLT_OK;
     if (d_src == nullptr || d_dst == nullptr)
         return fail(DXTLT_E_INVALID_ARGUMENT, "NULL device buffer with a non-empty range");
-    if (int32_t rc = check_normalization(format, inverse, normalize, normalize_alpha); rc != DXTLT_OK)
+    if (int32_t rc = check_normalization(format, inverse, s.normalize, s.normalize_alpha); rc != DXTLT_OK)
         return rc;
-    Settings s{(int)mode, sa, sc, (int)normalize, (int)normalize_alpha};
     Range r{total, first, num};
     dxtlt::LaunchTuning t = current_tuning();
     HIP_TRY(dxtlt::launch_transform((Format)format, inverse, s, d_src, d_dst, r, stream, &t), "kernel launch");
     return DXTLT_OK;
 }
 
-dxtlt_host::Launch launch_of(int32_t format, uint8_t mode, bool sa, bool sc, uint8_t normalize, uint8_t normalize_alpha = 0)
+dxtlt_host::Launch launch_of(int32_t format, const Settings& s)
 {
     return [=](bool inverse, const void* src, void* dst, uint64_t total, uint64_t first, uint64_t count, hipStream_t stream) {
-        return device_range(format, inverse, src, dst, total, first, count, mode, sa, sc, stream, normalize, normalize_alpha);
+        return device_range(format, inverse, src, dst, total, first, count, s, stream);
     };
 }
 
@@ -136,22 +135,21 @@ dxtlt_host::StreamLayout dxtlt_host::block_layout(int32_t format, bool sa, bool 
     return S;
 }
 
-int32_t dxtlt_host::enqueue(int32_t format, bool inverse, const void* d_src, void* d_dst, uint64_t blocks, uint8_t mode,
-                            bool sa, bool sc, hipStream_t stream, uint8_t normalize, uint8_t normalize_alpha)
+int32_t dxtlt_host::enqueue(int32_t format, bool inverse, const void* d_src, void* d_dst, uint64_t blocks, const Settings& s,
+                            hipStream_t stream)
 {
-    return device_range(format, inverse, d_src, d_dst, blocks, 0, blocks, mode, sa, sc, stream, normalize, normalize_alpha);
+    return device_range(format, inverse, d_src, d_dst, blocks, 0, blocks, s, stream);
 }
 
-int32_t dxtlt_host::transform(int32_t format, bool inverse, const uint8_t* in, uint8_t* out, size_t len, uint8_t mode,
-                              bool sa, bool sc, uint8_t normalize, uint8_t normalize_alpha)
+int32_t dxtlt_host::transform(int32_t format, bool inverse, const uint8_t* in, uint8_t* out, size_t len, const Settings& s)
 {
-    int32_t rc = check_common(format, len, mode, in, out);
+    int32_t rc = check_common(format, len, s.variant, in, out);
     if (rc != DXTLT_OK)
         return rc;
     if (len == 0)
         return DXTLT_OK;  // zero blocks: nothing to do, no device needed
-    const StreamLayout S = block_layout(format, sa, sc);
-    return host_round_trip(S, launch_of(format, mode, sa, sc, normalize, normalize_alpha), inverse, in, out, len / S.block_bytes);
+    const StreamLayout S = block_layout(format, s.split_alpha, s.split_colour);
+    return host_round_trip(S, launch_of(format, s), inverse, in, out, len / S.block_bytes);
 }
 
 extern "C" {
@@ -159,7 +157,7 @@ extern "C" {
 // ---- host pointers ------------------------------------------------------------------------------
 static int32_t host_call(int32_t format, bool inverse, const uint8_t* in, uint8_t* out, size_t len, uint8_t mode, bool sa, bool sc)
 {
-    return dxtlt_host::transform(format, inverse, in, out, len, mode, sa, sc);
+    return dxtlt_host::transform(format, inverse, in, out, len, Settings{mode, sa, sc});
 }
 
 int32_t dxtlt_transform_bc1_with_settings(const uint8_t* i, uint8_t* o, size_t len, uint8_t mode, bool sc)
@@ -195,7 +193,7 @@ static int32_t device_whole(int32_t format, bool inverse, const void* d_in, void
     if (rc != DXTLT_OK)
         return rc;
     const uint64_t blocks = len / (size_t)dxtlt::block_bytes((Format)format);
-    return device_range(format, inverse, d_in, d_out, blocks, 0, blocks, mode, sa, sc, (hipStream_t)stream);
+    return device_range(format, inverse, d_in, d_out, blocks, 0, blocks, Settings{mode, sa, sc}, (hipStream_t)stream);
 }
 
 int32_t dxtlt_transform_bc1_with_settings_device(const void* i, void* o, size_t len, uint8_t mode, bool sc, void* st)
@@ -229,7 +227,7 @@ int32_t dxtlt_transform_range_device(int32_t format, bool inverse, const void* d
                                      uint64_t total_blocks, uint64_t first_block, uint64_t num_blocks, uint8_t mode,
                                      bool sa, bool sc, void* stream)
 {
-    return device_range(format, inverse, d_src, d_dst, total_blocks, first_block, num_blocks, mode, sa, sc,
+    return device_range(format, inverse, d_src, d_dst, total_blocks, first_block, num_blocks, Settings{mode, sa, sc},
                         (hipStream_t)stream);
 }
 
@@ -281,7 +279,7 @@ int32_t dxtlt_transform_sharded(int32_t format, bool inverse, const uint8_t* in,
     if (len == 0)
         return DXTLT_OK;
     const dxtlt_host::StreamLayout S = dxtlt_host::block_layout(format, sa, sc);
-    return dxtlt_host::run_sharded(S, launch_of(format, mode, sa, sc, 0), inverse, in, out, len / S.block_bytes, 0, num_devices,
+    return dxtlt_host::run_sharded(S, launch_of(format, Settings{mode, sa, sc}), inverse, in, out, len / S.block_bytes, 0, num_devices,
                                    &g_shard_stats);
 }
 

@@ -329,7 +329,7 @@ int32_t dds_transform_common(const uint8_t* input, size_t input_len, uint8_t* ou
             st45 = dxtlt_host::transform_auto(f45, input + off, output + off, length, estimator, false, &c);
             sa = c.split_alpha;
         } else {
-            st45 = dxtlt_host::transform(f45, false, input + off, output + off, length, 0, sa, false);
+            st45 = dxtlt_host::transform(f45, false, input + off, output + off, length, dxtlt::Settings{0, sa, false});
         }
         if (st45 != dxtlt_host::kOk)
             return map_device_status(st45);
@@ -377,7 +377,7 @@ int32_t dds_transform_common(const uint8_t* input, size_t input_len, uint8_t* ou
     } else {
         if (mode > 3)
             return DXTLT_FF_CORRUPTED_EMBEDDED_DATA;
-        st = dxtlt_host::transform(bcn, false, input + off, output + off, length, mode, sa, sc);
+        st = dxtlt_host::transform(bcn, false, input + off, output + off, length, dxtlt::Settings{mode, sa, sc});
     }
     if (st != dxtlt_host::kOk)
         return map_device_status(st);
@@ -580,7 +580,7 @@ int32_t dxtlt_dds_untransform(const uint8_t* input, size_t input_len, uint8_t* o
             return DXTLT_FF_INVALID_DATA_ALIGNMENT;
         wr32(output, kDdsMagic);
         std::memcpy(output + 4, input + 4, off - 4);
-        const int32_t st45 = dxtlt_host::transform(f45, true, input + off, output + off, length, 0, split45, false);
+        const int32_t st45 = dxtlt_host::transform(f45, true, input + off, output + off, length, dxtlt::Settings{0, split45, false});
         if (st45 != dxtlt_host::kOk)
             return map_device_status(st45);
         if (input_len > off + length)
@@ -614,7 +614,7 @@ int32_t dxtlt_dds_untransform(const uint8_t* input, size_t input_len, uint8_t* o
 
     wr32(output, kDdsMagic);
     std::memcpy(output + 4, input + 4, off - 4);
-    int32_t st = dxtlt_host::transform(bcn, true, input + off, output + off, length, mode, sa, sc);
+    int32_t st = dxtlt_host::transform(bcn, true, input + off, output + off, length, dxtlt::Settings{mode, sa, sc});
     if (st != dxtlt_host::kOk)
         return map_device_status(st);
     if (input_len > off + length)

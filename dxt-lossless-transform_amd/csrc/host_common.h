@@ -11,6 +11,7 @@
 
 #include "../../include/dlt_size_estimator.h"
 #include "../../include/dxtlt_gfx950.h"
+#include "bcn_launch.h"
 #include "estimate_launch.h"
 
 namespace dxtlt_host {
@@ -65,11 +66,9 @@ StreamLayout granule_layout(int format);
 using Launch = std::function<int32_t(bool inverse, const void* d_src, void* d_dst, uint64_t total, uint64_t first,
                                      uint64_t count, hipStream_t stream)>;
 
-// Host pointers in/out, whole buffer, synchronous (H2D + kernel + D2H on the current device).
-// `normalize` (BC1 / BC2 / BC3 forward only): ColorNormalizationMode fused into the transform, 0 = none;
-// `normalize_alpha` (BC3 forward only): AlphaNormalizationMode, 0 = none.
-int32_t transform(int32_t format, bool inverse, const uint8_t* in, uint8_t* out, size_t len, uint8_t mode,
-                  bool split_alpha, bool split_colour, uint8_t normalize = 0, uint8_t normalize_alpha = 0);
+// Host pointers in/out, whole buffer, synchronous (H2D + kernel + D2H on the current device).  `s` as the caller's arguments
+// gave it (bcn_launch.h): its decorrelation mode and fused normalisation modes are checked here.
+int32_t transform(int32_t format, bool inverse, const uint8_t* in, uint8_t* out, size_t len, const dxtlt::Settings& s);
 
 // ---- host_staging.cpp -------------------------------------------------------------------------------
 // This thread's staging context on the current device: two device buffers of at least `bytes` and a stream.
@@ -173,8 +172,8 @@ int32_t batch_device(const DxtltBatchItem* items, size_t count, void* stream, bo
 int bind_this_thread_near_device(int device);
 
 // Enqueue one whole-buffer transform on device pointers.
-int32_t enqueue(int32_t format, bool inverse, const void* d_src, void* d_dst, uint64_t blocks, uint8_t mode,
-                bool split_alpha, bool split_colour, hipStream_t stream, uint8_t normalize = 0, uint8_t normalize_alpha = 0);
+int32_t enqueue(int32_t format, bool inverse, const void* d_src, void* d_dst, uint64_t blocks, const dxtlt::Settings& s,
+                hipStream_t stream);
 
 // Per-thread device resources of the other translation units, freed by dxtlt_release_thread_resources().
 void release_normalize_thread_flag();   // normalize_api.cpp

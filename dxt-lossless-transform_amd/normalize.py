@@ -1,7 +1,8 @@
 """BC1 block normalisation -- host-side mirror of the reference's experimental module
 (``dxt_lossless_transform_bc1::experimental::normalize_blocks``, normalize.rs / transform.rs / mod.rs) over the C ABI of
 include/dxtlt_bc1_normalize.h.  Same buffer conventions as the BC1-3 functions: numpy/bytes-like host buffers or CUDA
-``torch.uint8`` tensors (device path, enqueued on torch's current stream).  No CPU fallback."""
+``torch.uint8`` tensors (device path, enqueued on torch's current stream).  No CPU fallback.  normalize23.py (BC2 / BC3) shares
+this module's prototype table and its buffer, size and call helpers."""
 from __future__ import annotations
 
 import ctypes as C
@@ -10,8 +11,6 @@ import enum
 from typing import Iterator, Sequence
 
 from . import _lib
-
-_declared = False
 
 
 class ColorNormalizationMode(enum.IntEnum):
@@ -45,118 +44,125 @@ class Bc1TransformDetailsWithNormalization:
         return Bc1TransformSettings(YCoCgVariant(self.decorrelation_mode), self.split_colour_endpoints)
 
 
+# One table of prototypes for both headers.  A `_device` twin takes the same arguments and a trailing stream unless it is listed.
+_VP, _SZ, _U8, _B = C.c_void_p, C.c_size_t, C.c_uint8, C.c_bool
+_PP = C.POINTER(_VP)
+_HOST = {
+    # include/dxtlt_bc1_normalize.h
+    "dxtlt_bc1_normalize_blocks": [_VP, _VP, _SZ, _U8],
+    "dxtlt_bc1_normalize_split_blocks_in_place": [_VP, _VP, _SZ, _U8],
+    "dxtlt_bc1_normalize_blocks_all_modes": [_VP, _PP, _SZ, C.POINTER(_B)],
+    "dxtlt_transform_bc1_with_normalize_blocks": [_VP, _VP, _VP, _SZ, _U8, _U8, _B],
+    # include/dxtlt_bc23_normalize.h
+    "dxtlt_bc2_normalize_blocks": [_VP, _VP, _SZ, _U8],
+    "dxtlt_bc3_normalize_blocks": [_VP, _VP, _SZ, _U8, _U8],
+    "dxtlt_bc2_normalize_split_blocks_in_place": [_VP, _VP, _VP, _SZ, _U8],
+    "dxtlt_bc3_normalize_split_blocks_in_place": [_VP, _VP, _VP, _VP, _SZ, _U8, _U8],
+    "dxtlt_bc2_normalize_blocks_all_modes": [_VP, _PP, _SZ],
+    "dxtlt_bc3_normalize_blocks_all_modes": [_VP, _PP, _SZ],
+    "dxtlt_transform_bc2_with_normalize_blocks": [_VP, _VP, _SZ, _U8, _U8, _B],
+    "dxtlt_transform_bc3_with_normalize_blocks": [_VP, _VP, _SZ, _U8, _U8, _U8, _B, _B],
+}
+_DEVICE = {   # the twins that differ: no work_ptr, a device flag word, no alpha array
+    "dxtlt_transform_bc1_with_normalize_blocks_device": [_VP, _VP, _SZ, _U8, _U8, _B, _VP],
+    "dxtlt_bc1_normalize_blocks_all_modes_device": [_VP, _PP, _SZ, _VP, _VP],
+    "dxtlt_bc2_normalize_split_blocks_in_place_device": [_VP, _VP, _SZ, _U8, _VP],
+}
+_declared = False
+
+
 def _l():
     global _declared
     l = _lib.load()
     if not _declared:
-        vp, sz, i32, u8, b = C.c_void_p, C.c_size_t, C.c_int32, C.c_uint8, C.c_bool
-        l.dxtlt_bc1_normalize_blocks.argtypes, l.dxtlt_bc1_normalize_blocks.restype = [vp, vp, sz, u8], i32
-        l.dxtlt_bc1_normalize_blocks_device.argtypes = [vp, vp, sz, u8, vp]
-        l.dxtlt_bc1_normalize_blocks_device.restype = i32
-        l.dxtlt_bc1_normalize_split_blocks_in_place.argtypes = [vp, vp, sz, u8]
-        l.dxtlt_bc1_normalize_split_blocks_in_place.restype = i32
-        l.dxtlt_bc1_normalize_split_blocks_in_place_device.argtypes = [vp, vp, sz, u8, vp]
-        l.dxtlt_bc1_normalize_split_blocks_in_place_device.restype = i32
-        l.dxtlt_bc1_normalize_blocks_all_modes.argtypes = [vp, C.POINTER(vp), sz, C.POINTER(b)]
-        l.dxtlt_bc1_normalize_blocks_all_modes.restype = i32
-        l.dxtlt_bc1_normalize_blocks_all_modes_device.argtypes = [vp, C.POINTER(vp), sz, vp, vp]
-        l.dxtlt_bc1_normalize_blocks_all_modes_device.restype = i32
-        l.dxtlt_transform_bc1_with_normalize_blocks.argtypes = [vp, vp, vp, sz, u8, u8, b]
-        l.dxtlt_transform_bc1_with_normalize_blocks.restype = i32
-        l.dxtlt_transform_bc1_with_normalize_blocks_device.argtypes = [vp, vp, sz, u8, u8, b, vp]
-        l.dxtlt_transform_bc1_with_normalize_blocks_device.restype = i32
-        # BC2 / BC3 (include/dxtlt_bc23_normalize.h)
-        l.dxtlt_transform_bc2_with_normalize_blocks.argtypes = [vp, vp, sz, u8, u8, b]
-        l.dxtlt_transform_bc2_with_normalize_blocks_device.argtypes = [vp, vp, sz, u8, u8, b, vp]
-        l.dxtlt_transform_bc3_with_normalize_blocks.argtypes = [vp, vp, sz, u8, u8, u8, b, b]
-        l.dxtlt_transform_bc3_with_normalize_blocks_device.argtypes = [vp, vp, sz, u8, u8, u8, b, b, vp]
-        for fmt in ("bc2", "bc3"):
-            getattr(l, f"dxtlt_transform_{fmt}_with_normalize_blocks").restype = i32
-            getattr(l, f"dxtlt_transform_{fmt}_with_normalize_blocks_device").restype = i32
+        for name, args in _HOST.items():
+            getattr(l, name).argtypes, getattr(l, name).restype = args, C.c_int32
+            twin = getattr(l, name + "_device")
+            twin.argtypes, twin.restype = _DEVICE.get(name + "_device", args + [_VP]), C.c_int32
         _declared = True
     return l
 
 
-def _check(rc: int) -> None:
-    from . import DeviceError
+def _bufs(items, writable):
+    from . import _Buf
 
-    if rc != _lib.OK:
-        raise DeviceError(rc, _lib.last_error())
+    return [_Buf(x, w) for x, w in zip(items, writable)]
 
 
-def _stream(device) -> int:
-    import torch
+def _device_of(bufs, mismatch="all buffers must be host buffers or all be tensors on one device"):
+    """None for host buffers, the device index for tensors; every buffer in the same place"""
+    if len({b.device for b in bufs}) != 1:
+        raise TypeError(mismatch)
+    return bufs[0].device
 
-    return torch.cuda.current_stream(device).cuda_stream
+
+def _sized(src, dst, block: int) -> None:
+    from . import InvalidLength, OutputBufferTooSmall
+
+    if src.nbytes % block != 0:
+        raise InvalidLength(src.nbytes)
+    if dst.nbytes < src.nbytes:
+        raise OutputBufferTooSmall(src.nbytes, dst.nbytes)
+
+
+def _run(name: str, device, host_args, device_args=None) -> None:
+    """The host entry point `name`, or -- for tensors -- its _device twin on their device and torch's current stream."""
+    from . import _check
+
+    if device is None:
+        _check(getattr(_l(), name)(*host_args))
+    else:
+        import torch
+
+        with torch.cuda.device(device):
+            args = host_args if device_args is None else device_args
+            _check(getattr(_l(), name + "_device")(*args, torch.cuda.current_stream(device).cuda_stream))
 
 
 def normalize_blocks(input, output, color_mode: ColorNormalizationMode) -> None:
     """normalize.rs:38.  ``output`` may be the same buffer as ``input`` (in place)."""
-    from . import InvalidLength, OutputBufferTooSmall, _Buf
-
-    src, dst = _Buf(input, False), _Buf(output, True)
-    if src.nbytes % 8 != 0:
-        raise InvalidLength(src.nbytes)
-    if dst.nbytes < src.nbytes:
-        raise OutputBufferTooSmall(src.nbytes, dst.nbytes)
-    if (src.device is None) != (dst.device is None):
-        raise TypeError("input and output must both be host buffers or both be device tensors")
-    if src.device is None:
-        _check(_l().dxtlt_bc1_normalize_blocks(src.ptr, dst.ptr, src.nbytes, int(color_mode)))
-    else:
-        import torch
-
-        with torch.cuda.device(src.device):
-            _check(_l().dxtlt_bc1_normalize_blocks_device(src.ptr, dst.ptr, src.nbytes, int(color_mode),
-                                                          _stream(src.device)))
+    src, dst = _bufs((input, output), (False, True))
+    _sized(src, dst, 8)
+    device = _device_of((src, dst), "input and output must both be host buffers or both be device tensors")
+    _run("dxtlt_bc1_normalize_blocks", device, (src.ptr, dst.ptr, src.nbytes, int(color_mode)))
 
 
 def normalize_split_blocks_in_place(colors, indices, color_mode: ColorNormalizationMode) -> None:
     """normalize.rs:286: colours (4 bytes per block) and indices (4 bytes per block), both modified in place."""
-    from . import InvalidLength, _Buf
+    from . import InvalidLength
 
-    c, x = _Buf(colors, True), _Buf(indices, True)
+    c, x = _bufs((colors, indices), (True, True))
     if c.nbytes % 4 != 0 or c.nbytes != x.nbytes:
         raise InvalidLength(c.nbytes)
-    if (c.device is None) != (x.device is None):
-        raise TypeError("colors and indices must both be host buffers or both be device tensors")
-    if c.device is None:
-        _check(_l().dxtlt_bc1_normalize_split_blocks_in_place(c.ptr, x.ptr, c.nbytes // 4, int(color_mode)))
-    else:
-        import torch
-
-        with torch.cuda.device(c.device):
-            _check(_l().dxtlt_bc1_normalize_split_blocks_in_place_device(c.ptr, x.ptr, c.nbytes // 4, int(color_mode),
-                                                                         _stream(c.device)))
+    device = _device_of((c, x), "colors and indices must both be host buffers or both be device tensors")
+    _run("dxtlt_bc1_normalize_split_blocks_in_place", device, (c.ptr, x.ptr, c.nbytes // 4, int(color_mode)))
 
 
 def normalize_blocks_all_modes(input, outputs: Sequence) -> bool:
     """normalize.rs:417: one output per ColorNormalizationMode, in enum order.  Returns whether any block was
     normalised.  Device tensors: synchronises the current stream to read the flag."""
-    from . import InvalidLength, OutputBufferTooSmall, _Buf
+    from . import InvalidLength, OutputBufferTooSmall
 
     if len(outputs) != len(ColorNormalizationMode):
         raise ValueError("one output buffer per ColorNormalizationMode is required")
-    src = _Buf(input, False)
-    outs = [_Buf(o, True) for o in outputs]
+    src, *outs = _bufs((input, *outputs), (False, True, True, True))
     if src.nbytes % 8 != 0:
         raise InvalidLength(src.nbytes)
     for o in outs:
         if o.nbytes < src.nbytes:
             raise OutputBufferTooSmall(src.nbytes, o.nbytes)
-        if (o.device is None) != (src.device is None):
-            raise TypeError("input and outputs must all be host buffers or all be device tensors")
+        _device_of((src, o), "input and outputs must all be host buffers or all be device tensors")
     ptrs = (C.c_void_p * 3)(*[o.ptr for o in outs])
+    name = "dxtlt_bc1_normalize_blocks_all_modes"
     if src.device is None:
         flag = C.c_bool(False)
-        _check(_l().dxtlt_bc1_normalize_blocks_all_modes(src.ptr, ptrs, src.nbytes, C.byref(flag)))
+        _run(name, None, (src.ptr, ptrs, src.nbytes, C.byref(flag)))
         return bool(flag.value)
     import torch
 
     with torch.cuda.device(src.device):
         any_word = torch.zeros(1, dtype=torch.int32, device=input.device)
-        _check(_l().dxtlt_bc1_normalize_blocks_all_modes_device(src.ptr, ptrs, src.nbytes, any_word.data_ptr(),
-                                                                _stream(src.device)))
+        _run(name, src.device, (src.ptr, ptrs, src.nbytes, any_word.data_ptr()))
         return bool(any_word.item() != 0)
 
 
@@ -165,44 +171,19 @@ def transform_bc1_with_normalize_blocks(input, output,
                                         ) -> None:
     """transform.rs:65 (the reference's ``work_ptr`` scratch buffer has no counterpart: normalisation is fused into
     the transform kernel).  Undo with ``untransform_bc1_with_settings(..., details.untransform_settings())``."""
-    from . import InvalidLength, OutputBufferTooSmall, _Buf
-
-    src, dst = _Buf(input, False), _Buf(output, True)
-    if src.nbytes % 8 != 0:
-        raise InvalidLength(src.nbytes)
-    if dst.nbytes < src.nbytes:
-        raise OutputBufferTooSmall(src.nbytes, dst.nbytes)
-    if (src.device is None) != (dst.device is None):
-        raise TypeError("input and output must both be host buffers or both be device tensors")
+    src, dst = _bufs((input, output), (False, True))
+    _sized(src, dst, 8)
+    device = _device_of((src, dst), "input and output must both be host buffers or both be device tensors")
     args = (int(details.color_normalization_mode), int(details.decorrelation_mode), bool(details.split_colour_endpoints))
-    if src.device is None:
-        _check(_l().dxtlt_transform_bc1_with_normalize_blocks(src.ptr, dst.ptr, None, src.nbytes, *args))
-    else:
-        import torch
-
-        with torch.cuda.device(src.device):
-            _check(_l().dxtlt_transform_bc1_with_normalize_blocks_device(src.ptr, dst.ptr, src.nbytes, *args,
-                                                                         _stream(src.device)))
+    _run("dxtlt_transform_bc1_with_normalize_blocks", device, (src.ptr, dst.ptr, None, src.nbytes, *args),
+         (src.ptr, dst.ptr, src.nbytes, *args))
 
 
 def _fused_bc23(fmt: str, input, output, mode_args: tuple, settings_args: tuple) -> None:
-    from . import InvalidLength, OutputBufferTooSmall, _Buf
-
-    src, dst = _Buf(input, False), _Buf(output, True)
-    if src.nbytes % 16 != 0:
-        raise InvalidLength(src.nbytes)
-    if dst.nbytes < src.nbytes:
-        raise OutputBufferTooSmall(src.nbytes, dst.nbytes)
-    if (src.device is None) != (dst.device is None):
-        raise TypeError("input and output must both be host buffers or both be device tensors")
-    name = f"dxtlt_transform_{fmt}_with_normalize_blocks"
-    if src.device is None:
-        _check(getattr(_l(), name)(src.ptr, dst.ptr, src.nbytes, *mode_args, *settings_args))
-    else:
-        import torch
-
-        with torch.cuda.device(src.device):
-            _check(getattr(_l(), name + "_device")(src.ptr, dst.ptr, src.nbytes, *mode_args, *settings_args, _stream(src.device)))
+    src, dst = _bufs((input, output), (False, True))
+    _sized(src, dst, 16)
+    device = _device_of((src, dst), "input and output must both be host buffers or both be device tensors")
+    _run(f"dxtlt_transform_{fmt}_with_normalize_blocks", device, (src.ptr, dst.ptr, src.nbytes, *mode_args, *settings_args))
 
 
 def transform_bc2_with_normalize_blocks(input, output, color_mode: ColorNormalizationMode, decorrelation_mode: int = 1,

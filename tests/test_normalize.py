@@ -302,14 +302,15 @@ def test_gpu_normalize_blocks(pkg, norm, oracle, mode):
             src.copy_(torch.from_numpy(x).to(dev))
             norm.normalize_blocks(src, dst, norm.ColorNormalizationMode(mode))
             assert np.array_equal(dst.cpu().numpy(), want), (n, mode, "misaligned")
-    # host pointers, separate and in place
-    x = crafted_blocks(oracle, 70_001, 9)
-    y = np.zeros_like(x)
-    norm.normalize_blocks(x, y, norm.ColorNormalizationMode(mode))
-    assert np.array_equal(y, oracle.normalize_bc1_blocks(x, mode))
-    z = x.copy()
-    norm.normalize_blocks(z, z, norm.ColorNormalizationMode(mode))
-    assert np.array_equal(z, y)
+    # host pointers, separate and in place; 32 blocks: a whole number of 256-byte staging slots, 33: not
+    for n in (32, 33, 70_001):
+        x = crafted_blocks(oracle, n, 9)
+        y = np.zeros_like(x)
+        norm.normalize_blocks(x, y, norm.ColorNormalizationMode(mode))
+        assert np.array_equal(y, oracle.normalize_bc1_blocks(x, mode)), (n, mode, "host")
+        z = x.copy()
+        norm.normalize_blocks(z, z, norm.ColorNormalizationMode(mode))
+        assert np.array_equal(z, y), (n, mode, "host, in place")
     with pytest.raises(pkg.InvalidLength):
         norm.normalize_blocks(np.zeros(12, np.uint8), np.zeros(12, np.uint8), norm.ColorNormalizationMode(mode))
 

@@ -1,6 +1,6 @@
 """The block-normalisation kernels at every pointer alignment and in every block slot, on the device, under byte comparison.
 
-csrc/bc1_normalize.hip, csrc/bc23_normalize.hip and the fused BC1 normalise+transform kernels of csrc/bcn_kernels.hip
+csrc/normalize_kernels.hip and the fused BC1 normalise+transform kernels of csrc/bcn_kernels.hip
 (bc1_norm_kernels<VARIANT, SC, NORM>) choose their code from pointer alignment -- 16-byte vectors of two or four blocks, 4-byte
 words, single bytes -- and, fused, from the byte address of every SoA stream as the plain tile kernels do.  tests/test_normalize*.py
 pin WHAT they compute at aligned pointers; this file runs every one of those choices, with guard bytes around every output.

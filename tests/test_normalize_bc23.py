@@ -272,12 +272,13 @@ def test_gpu_normalize_blocks_bc23(pkg, n23, oracle, fmt):
             n23.normalize_blocks(fmt, src, dst, n23.ColorNormalizationMode(c), n23.AlphaNormalizationMode(a))
             want = oracle.normalize_bc2_blocks(x, c) if fmt == "bc2" else oracle.normalize_bc3_blocks(x, a, c)
             assert np.array_equal(dst.cpu().numpy(), want)
-    # host pointers
-    x = test_blocks(fmt, 30_001, 77)
+    # host pointers; 16 blocks: a whole number of 256-byte staging slots, 17: not
     a, c = combos[-1]
-    y = np.zeros_like(x)
-    n23.normalize_blocks(fmt, x, y, n23.ColorNormalizationMode(c), n23.AlphaNormalizationMode(a))
-    assert np.array_equal(y, oracle.normalize_bc2_blocks(x, c) if fmt == "bc2" else oracle.normalize_bc3_blocks(x, a, c))
+    for n in (16, 17, 30_001):
+        x = test_blocks(fmt, n, 77)
+        y = np.zeros_like(x)
+        n23.normalize_blocks(fmt, x, y, n23.ColorNormalizationMode(c), n23.AlphaNormalizationMode(a))
+        assert np.array_equal(y, oracle.normalize_bc2_blocks(x, c) if fmt == "bc2" else oracle.normalize_bc3_blocks(x, a, c)), (fmt, n, "host")
     with pytest.raises(pkg.InvalidLength):
         n23.normalize_blocks(fmt, np.zeros(24, np.uint8), np.zeros(24, np.uint8), n23.ColorNormalizationMode(1))
 
@@ -287,7 +288,7 @@ def test_gpu_normalize_blocks_bc23(pkg, n23, oracle, fmt):
 def test_gpu_all_modes_bc23(n23, oracle, fmt):
     dev = torch.device("cuda:0")
     count = 3 if fmt == "bc2" else 12
-    for n in (1, 257, 20_003):
+    for n in (1, 16, 17, 257, 20_003):   # 16 blocks: the host call's staging slots lie back to back, 17: padded to 256 bytes
         x = test_blocks(fmt, n, n + 5)
         want = oracle.normalize_bc2_blocks_all_modes(x) if fmt == "bc2" else oracle.normalize_bc3_blocks_all_modes(x)
         xd = torch.from_numpy(x).to(dev)
