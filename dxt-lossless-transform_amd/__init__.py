@@ -163,7 +163,7 @@ def set_tuning(tile_threads: int = 0, force_path: int = 0) -> None:
 
 
 def tuning_mask() -> int:
-    """The force_path bits this build honours: 0x22 for the shipped library (the experiments side build knows more)."""
+    """The force_path bits this build honours: 0x22 (the experiment switches that used more bits were removed)."""
     return int(load().dxtlt_tuning_mask())
 
 

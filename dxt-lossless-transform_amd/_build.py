@@ -30,7 +30,7 @@ BASE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-
 
 
 def _extra_flags(extra_flags=None) -> list:
-    """Extra compiler flags of a SIDE build (A/B experiments: -DDXTLT_EXPERIMENTS, -DDXTLT_WG_TIMING): ONLY the argument.  The
+    """Extra compiler flags of a SIDE build (A/B experiments): ONLY the argument.  The
     environment is never read here: build() / __graft_entry__.build() always bring the SHIPPED library up to date, whatever is
     left set in a shell; $DXTLT_EXTRA_HIPCC_FLAGS is honoured by tools/ab_build_rev.sh alone, which passes it in explicitly.  A
     build with extra flags never touches the shipped library or its objects: it goes to build/side-<hash of the flags>/ (objects

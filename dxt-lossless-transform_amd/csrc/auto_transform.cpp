@@ -561,13 +561,12 @@ int32_t dxtlt_host::transform_auto(int32_t format, const uint8_t* in, uint8_t* o
             return rc;
         drain.armed = true;
         HIP_TRY(hipMemcpyAsync(d_in, in, len, hipMemcpyHostToDevice, st), "H2D copy");
-        static const bool fused = [] { const char* v = dxtlt::experiment_env("DXTLT_AUTO_FUSED"); return !(v && v[0] == '0'); }();
         if (format >= 4 && !t_no_arena) {
             arena = static_cast<uint8_t*>(g_arena.get(2 * len));
             for (int i = 0; i < o.count && arena != nullptr; ++i)
                 if (int32_t rc = enqueue(format, false, d_in, arena + (size_t)i * len, blocks, dxtlt::Settings{0, o.order[i].split_alpha, false}, st))
                     return rc;
-        } else if (format <= 3 && fused && !t_no_arena) {
+        } else if (format <= 3 && !t_no_arena) {
             distinct = dxtlt::auto_sections((dxtlt::Format)format, use_all, blocks);
             arena = static_cast<uint8_t*>(g_arena.get((size_t)distinct.bytes));
             if (arena != nullptr)

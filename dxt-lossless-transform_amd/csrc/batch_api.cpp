@@ -61,18 +61,13 @@ int32_t launch_pixel_item(const DxtltBatchItem& it, void* stream)
 // Table staging: table_ring.h, batch_tables.h (shared with the image batch calls)
 thread_local dxtlt_host::TableRing g_ring;
 
-// DXTLT_BATCH_TABLE_COPY=1: the table travels by hipMemcpyAsync (the first version; kept for the comparison in
-// profiles/r02_m_batch_kernel.txt)
-const bool kTableByCopyEngine = dxtlt::experiment_env("DXTLT_BATCH_TABLE_COPY") != nullptr && dxtlt::experiment_env("DXTLT_BATCH_TABLE_COPY")[0] == '1';
-
 }  // namespace
 
 dxtlt_host::TableRing& dxtlt_host::thread_table_ring() { return g_ring; }
 
+// By a kernel, not by the copy engine (the first version; the comparison is profiles/r02_m_batch_kernel.txt)
 hipError_t dxtlt_host::upload_table(TableSlot* slot, size_t bytes, hipStream_t stream)
 {
-    if (kTableByCopyEngine)
-        return hipMemcpyAsync(slot->dev, slot->host, bytes, hipMemcpyHostToDevice, stream);
     return dxtlt::launch_table_upload(slot->host_mapped, slot->dev, bytes, stream);
 }
 
@@ -214,13 +209,9 @@ int32_t plan_batch(const DxtltBatchItem* items, size_t count, bool pixels_allowe
             l.uniform_wgs = 0;   // (stays 0: no buffer owns 0 workgroups)
     }
     std::sort(plan.tiles.begin(), plan.tiles.end(), [](const TileLaunch& a, const TileLaunch& b) { return a.key < b.key; });
-    static const bool no_uniform = dxtlt::experiment_env("DXTLT_BATCH_NO_UNIFORM") != nullptr;   // A/B switches of the experiments build (tools/batch_kernel_probe.py)
-    static const bool no_strided = dxtlt::experiment_env("DXTLT_BATCH_NO_STRIDED") != nullptr;
     for (TileLaunch& l : plan.tiles) {
         const size_t n = l.entries.size();
-        if (no_uniform)
-            l.uniform_wgs = 0;
-        l.strided = l.uniform_wgs != 0 && !no_strided;   // (one buffer is a regular array too)
+        l.strided = l.uniform_wgs != 0;   // (one buffer is a regular array too)
         l.src_stride = n >= 2 ? (int64_t)(l.entries[1].src - l.entries[0].src) : 0;
         l.dst_stride = n >= 2 ? (int64_t)(l.entries[1].dst - l.entries[0].dst) : 0;
         for (size_t i = 1; i < n && l.strided; ++i) {

@@ -59,10 +59,6 @@ __device__ __forceinline__ BatchView load_batch_entry(const BatchEntry* entry)
 }
 __device__ __forceinline__ void pin_batch_view(BatchView& v)
 {
-#ifdef DXTLT_WG_TIMING
-    (void)v;   // (the experiment build's stores to its timing array make the table loads vector loads: nothing to pin)
-    return;
-#endif
     uint64_t s = reinterpret_cast<uintptr_t>(v.src), d = reinterpret_cast<uintptr_t>(v.dst);
     asm("" : "+s"(s), "+s"(d), "+s"(v.blocks));
     v.src = (const uint8_t*)(global_cptr)s;
@@ -94,37 +90,6 @@ struct StridedBatch {
     uint32_t on;
 };
 
-#ifdef DXTLT_WG_TIMING
-// EXPERIMENT build only (tools/wg_timing_probe.py): per workgroup {100 MHz ticks from its first instruction to the acknowledgement of
-// its last store, kind of tile, start tick (low 32 bits), XCC id}
-__device__ uint32_t g_wg_timing[4 << 20];
-extern "C" int dxtlt_debug_read_wg_timing(uint32_t* out, size_t count)
-{
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wg_timing), count * 4);
-}
-extern "C" int dxtlt_debug_read_wg_marks(uint32_t* out, size_t count)
-{
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(dxtlt::g_wg_marks), count * 4);
-}
-#define WG_TIMING_BEGIN const uint64_t t_begin = __builtin_amdgcn_s_memrealtime();
-#define WG_TIMING_END(kind)                                                                         \
-    do {                                                                                            \
-        __builtin_amdgcn_s_waitcnt(0);                                                              \
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                            \
-        if (threadIdx.x == 0 && blockIdx.x < (1u << 20)) {                                          \
-            uint32_t xcc;                                                                           \
-            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));                       \
-            g_wg_timing[4 * blockIdx.x] = (uint32_t)(__builtin_amdgcn_s_memrealtime() - t_begin);   \
-            g_wg_timing[4 * blockIdx.x + 1] = (kind);                                               \
-            g_wg_timing[4 * blockIdx.x + 2] = (uint32_t)t_begin;                                    \
-            g_wg_timing[4 * blockIdx.x + 3] = xcc & 0xF;                                            \
-        }                                                                                           \
-    } while (0)
-#else
-#define WG_TIMING_BEGIN
-#define WG_TIMING_END(kind)
-#endif
-
 // THREADS = batch_tile_threads(FMT, SC, INVERSE): the lanes of every tile of the launch (256; 128 for the forward launch of BC1
 // without the colour split -- bcn_device.h has both measurements)
 template <int FMT, int VARIANT, bool SA, bool SC, bool INVERSE, int THREADS = batch_tile_threads(FMT, SC, INVERSE)>
@@ -135,15 +100,12 @@ batch_kernel(const BatchEntry* __restrict__ entries_arg, const uint8_t* __restri
     constexpr int kLds = INVERSE ? shift_lds_bytes(1, THREADS) : halo_lds_bytes<FMT, THREADS>();
     __shared__ __attribute__((aligned(16))) uint8_t lds[kLds];
     const uint32_t wg = blockIdx.x;
-    WG_TIMING_BEGIN
     BatchView en;
     uint32_t e;   // index of the buffer in its launch
     // both table pointers in the FIRST scalar round trip (the compiler otherwise fetches `index` on the path that uses it, behind
     // the first wait); through integers: see fetched_now
     uint64_t entries_at = reinterpret_cast<uintptr_t>(entries_arg), index_at = reinterpret_cast<uintptr_t>(index_arg);
-#ifndef DXTLT_WG_TIMING
     asm("" : "+s"(entries_at), "+s"(index_at), "+s"(n_base), "+s"(uniform_wgs), "+s"(magic));
-#endif
     const BatchEntry* entries = (const BatchEntry*)(const __attribute__((address_space(1))) BatchEntry*)entries_at;
     const uint8_t* index = (const uint8_t*)(global_cptr)index_at;
     if (uniform_wgs != 0) {
@@ -173,7 +135,7 @@ batch_kernel(const BatchEntry* __restrict__ entries_arg, const uint8_t* __restri
         e = batch_entry_of_workgroup(entries, index, n_base, magic, wg, en);
     }
     // Which of the buffer's tiles this workgroup takes.  Workgroups go to the eight XCDs round robin (wg % 8), and an edge tile
-    // takes 1.2-1.9 x a whole tile's time (tools/wg_timing_probe.py): with buffers of 8 k workgroups each, launch order would put
+    // takes 1.2-1.9 x a whole tile's time (profiles/r04_batch_edge_tiles.txt): with buffers of 8 k workgroups each, launch order would put
     // EVERY buffer's last tile on one and the same XCD, which then runs 10 % behind the other seven -- the tail that made 4096
     // x (256 KiB - 1 block) run at 0.60 where 4096 x 16407 blocks (65 workgroups per buffer) ran at 0.71, and that round 3
     // built in by padding every buffer to a multiple of 8 workgroups (profiles/r04_batch_edge_tiles.txt section 7).  So the
@@ -191,7 +153,6 @@ batch_kernel(const BatchEntry* __restrict__ entries_arg, const uint8_t* __restri
             inv_aligned_tile<FMT, VARIANT, SA, SC, THREADS>(en.src, en.dst, en.blocks, 0, local, lds);
         else
             fwd_aligned_tile<FMT, VARIANT, SA, SC, THREADS>(en.src, en.dst, en.blocks, 0, local, lds);
-        WG_TIMING_END(1);
         return;
     }
     Shifts sh;
@@ -200,11 +161,6 @@ batch_kernel(const BatchEntry* __restrict__ entries_arg, const uint8_t* __restri
         sh.d[i] = (int)((en.shifts[i >> 2] >> (8 * (i & 3))) & 127u);
         sh.gbase[i] = en.gbase[i];
     }
-#ifdef DXTLT_EXPERIMENTS
-    sh.xcd_remap = 0;
-    sh.line_policy = INVERSE ? 1 : 3;
-    sh.skip_partial = 0;
-#endif
     sh.natural = 1;             // plan_batch_entry hands buffers with other shifts back to the host
     sh.halo_vecs = (int)(en.flags >> 8) & 0xFF;
     sh.full_tiles = en.full_tiles;
@@ -219,19 +175,15 @@ batch_kernel(const BatchEntry* __restrict__ entries_arg, const uint8_t* __restri
             // one XCD (but for the few workgroups the rotation wraps around).
             const uint64_t tile = xcd_contiguous_tile(local, en.full_tiles);
             inv_shift_tile<FMT, VARIANT, SA, SC, THREADS>(en.src, en.dst, en.blocks, 0, sh, tile, lds);
-            WG_TIMING_END(2);
             return;
         }
         inv_shift_edge_tile<FMT, VARIANT, SA, SC, THREADS>(en.src, en.dst, en.blocks, sh, en.full_tiles, lds);
-        WG_TIMING_END(4);
     } else {
         if (local != 0 && local < en.full_tiles) {
             fwd_halo_tile<FMT, VARIANT, SA, SC, kNormNone, true, THREADS>(en.src, en.dst, en.blocks, 0, sh, local, lds);
-            WG_TIMING_END(2);
             return;
         }
         fwd_halo_edge_tile<FMT, VARIANT, SA, SC, kNormNone, true, THREADS>(en.src, en.dst, sh, local, lds);
-        WG_TIMING_END(local == 0 ? 3 : 4);
     }
 }
 
@@ -330,8 +282,7 @@ hipError_t launch_batch(Format fmt, bool inverse, const Settings& s, const Batch
     // wg - 1 (0 for wg 0), the same compare makes it wg: e == wg without a table lookup.  General lookup: the entry count (the
     // bound of the kernel's bisection).
     const uint32_t magic = uniform_wgs > 1 ? (uint32_t)((1ull << 32) / uniform_wgs) : uniform_wgs == 1 ? 0xFFFFFFFFu : n_entries;
-    static const bool no_array = experiment_env("DXTLT_BATCH_NO_ARRAY") != nullptr;   // A/B switch (experiments build)
-    if (strided_first != nullptr && uniform_wgs != 0 && !no_array && strided_first->form == 1) {
+    if (strided_first != nullptr && uniform_wgs != 0 && strided_first->form == 1) {
         const hipError_t e = launch_tiled_array(fmt, inverse, s, strided_first->src, strided_first->dst, strided_first->blocks, n_entries,
                                                 src_stride, dst_stride, stream);
         if (e != hipErrorNotSupported)

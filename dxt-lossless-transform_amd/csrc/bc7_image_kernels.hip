@@ -76,7 +76,7 @@ hipError_t launch_decode_blocks(const void* blocks, void* pixels, uint64_t num_b
     const bool a = aligned16(blocks);
     if (aligned16(pixels)) {
         // six workgroups per CU, as the BC2 / BC3 block decoders (bcn_decode.hip, decode_fmt): the same 16 bytes in, 64 out
-        const unsigned pad = lds_pad_for_wgs_per_cu(wgs_per_cu_or(6), kThreads, (unsigned)((kThreads / 64) * kWaveStage * 16));
+        const unsigned pad = lds_pad_for_wgs_per_cu(6, kThreads, (unsigned)((kThreads / 64) * kWaveStage * 16));
         hipLaunchKernelGGL(a ? decode_bc7_blocks_kernel<true> : decode_bc7_blocks_kernel<false>, grid, dim3(kThreads), pad, stream, in, out,
                            num_blocks);
     } else {

@@ -65,19 +65,12 @@ bc7_batch_tails(const BatchEntry* __restrict__ tails)
         forward_granule<Bc7Codec, 256, true>(e.src, e.dst, e.tail, 0, (int)e.tail);
 }
 
-// Workgroup size: 256 lanes x 4 blocks per lane (DESIGN.md section 8 has the measurements; the experiments side build,
-// -DDXTLT_EXPERIMENTS, also carries the 512- and 1024-lane kernels behind DXTLT_BC7_LANES).
+// Workgroup size: 256 lanes x 4 blocks per lane (DESIGN.md section 8 has the measurements against 512 and 1024 lanes).
 hipError_t launch_range(bool inverse, const void* src, void* dst, uint64_t total_blocks, uint64_t first_block,
                         uint64_t num_blocks, hipStream_t stream)
 {
-#ifdef DXTLT_EXPERIMENTS
-    static const int lanes = [] { const char* v = std::getenv("DXTLT_BC7_LANES"); const int x = v ? std::atoi(v) : 0; return x == 512 || x == 1024 ? x : 256; }();
-    const granule::RangeKernel fwd = lanes == 1024 ? bc7_forward<1024, false> : lanes == 512 ? bc7_forward<512, false> : bc7_forward<256, false>;
-    const granule::RangeKernel inv = lanes == 1024 ? bc7_inverse<1024, false> : lanes == 512 ? bc7_inverse<512, false> : bc7_inverse<256, false>;
-#else
     constexpr int lanes = 256;
     const granule::RangeKernel fwd = bc7_forward<256, false>, inv = bc7_inverse<256, false>;
-#endif
     return granule::launch_range(lanes, fwd, inv, bc7_forward<256, true>, bc7_inverse<256, true>, inverse, src, dst, total_blocks,
                                  first_block, num_blocks, stream);
 }

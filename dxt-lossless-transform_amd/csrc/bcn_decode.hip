@@ -163,8 +163,8 @@ hipError_t decode_fmt(const void* in, void* out, uint64_t n, hipStream_t stream)
     // on this memory system more bytes in flight per CU than it can take LOWER the rate (tools/shape_lab.hip; DESIGN.md
     // section 9): with the eight workgroups per CU the wave slots allow BC2 / BC3 decode at 0.745 of the HBM peak, with six
     // at 0.86-0.87 -- the speed of a plain fill -- (five and four: 0.845; seven: 0.82; three: 0.62).  BC1, which reads half
-    // as much per block, is best left at eight (0.80; seven 0.80, six 0.76).  DXTLT_EXPERIMENT_WGS_PER_CU overrides (experiments).
-    const unsigned pad_lds = lds_pad_for_wgs_per_cu(wgs_per_cu_or(FMT == 1 ? 8 : 6), kDecThreads, (unsigned)((kDecThreads / 64) * kWaveStage * 16));
+    // as much per block, is best left at eight (0.80; seven 0.80, six 0.76).
+    const unsigned pad_lds = lds_pad_for_wgs_per_cu(FMT == 1 ? 8 : 6, kDecThreads, (unsigned)((kDecThreads / 64) * kWaveStage * 16));
     if (p.vector)
         hipLaunchKernelGGL(decode_blocks_kernel<FMT>, grid, dim3(kDecThreads), pad_lds, stream,
                            static_cast<const uint8_t*>(in), static_cast<uint8_t*>(out), n);

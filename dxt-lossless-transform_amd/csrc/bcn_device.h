@@ -2,12 +2,9 @@
 // tiles, shared by the single-buffer kernels (bcn_kernels.hip) and the batch kernels (batch_kernels.hip).  The design notes
 // are at the top of bcn_kernels.hip.
 //
-// -DDXTLT_EXPERIMENTS (a SIDE build, never the shipped library: `DXTLT_EXTRA_HIPCC_FLAGS=-DDXTLT_EXPERIMENTS tools/ab_build_rev.sh
-// WORKTREE exp`, run through DXTLT_LIB_PATH) adds what the measurements in profiles/ were taken with and the product does not
-// need: the element-granular kernel, the first form of the forward shifted tiles, run-time store policies and tile orders, and
-// a wrong-output timing switch (Shifts::skip_partial).  Without the flag none of that is compiled: the kernels carry no switch
-// that is not a property of the data.  The two retired kernel families live in bcn_experiments.h, included at the end of this file
-// in that build only.
+// The kernels carry no switch that is not a property of the data.  What the measurements in profiles/ compared them with -- the
+// element-granular kernel, the first form of the forward shifted tiles, run-time store policies and tile orders, per-workgroup
+// timing -- lost every comparison and was removed; DESIGN.md names the last commit that carries it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -26,7 +23,7 @@ namespace dxtlt {
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
-constexpr int kThreads = 256;        // element-granular / fill kernels
+constexpr int kThreads = 256;        // fill kernel
 // Default tile workgroup size (tile = threads * 16 bytes) per format and direction, chosen by measurement on the
 // 8 GiB workloads with the final store policy (profiles/r01_q_tile_threads_sweep_sc1_stores.txt): fraction of peak, fwd / inv
 //   BC1  64: .82/.83   128: .85/.84   256: .84/.82   512: .81/.78
@@ -40,48 +37,15 @@ constexpr int default_tile_threads(int fmt, bool inverse)
     return fmt == kBc1 || fmt == kBc4 ? 128 : 256;
 }
 
-#ifndef DXTLT_NONTEMPORAL
-#define DXTLT_NONTEMPORAL 1
-#endif
-
-#ifdef DXTLT_WG_TIMING
-// EXPERIMENT build only (tools/wg_timing_probe.py, tools/wg_phase_single.py; built by DXTLT_EXTRA_HIPCC_FLAGS=-DDXTLT_WG_TIMING
-// tools/ab_build_rev.sh WORKTREE timing): phase marks of lane 0 of every workgroup, 100 MHz ticks (low 32 bits).  Slot 0: kernel
-// start (single-buffer aligned kernels), 1: the tile begins, 2: its loads have arrived, 3: behind the barrier, 4: stores issued.
-__device__ uint32_t g_wg_marks[8 << 20];
-__device__ __forceinline__ void wg_mark(int i)
-{
-    if (threadIdx.x == 0 && blockIdx.x < (1u << 20))
-        g_wg_marks[8 * blockIdx.x + i] = (uint32_t)__builtin_amdgcn_s_memrealtime();
-}
-#define WG_MARK(i) wg_mark(i)
-#define WG_MARK_LOADS_DONE(i)                                  \
-    do {                                                       \
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       \
-        wg_mark(i);                                            \
-    } while (0)
-#else
-#define WG_MARK(i)
-#define WG_MARK_LOADS_DONE(i)
-#endif
-
 __device__ __forceinline__ u32x4 gload16(const void* p)
 {
-#if DXTLT_NONTEMPORAL
     return __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
-#else
-    return *reinterpret_cast<const u32x4*>(p);
-#endif
 }
 
 // Streaming 16-byte store: streaming_store.h (policy measurements and the wait states its inline asm needs)
 __device__ __forceinline__ void gstore16(void* p, u32x4 v)
 {
-#if DXTLT_NONTEMPORAL
     store_streaming16(p, v);
-#else
-    *reinterpret_cast<u32x4*>(p) = v;
-#endif
 }
 
 // AoS-side store of the inverse kernels: the write-through streaming store when the block array is 16-byte aligned (a
@@ -130,31 +94,13 @@ __host__ __device__ constexpr int fmt_block(int fmt) { return fmt == kBc1 || fmt
 // one 16-byte vector per lane: a THREADS-wide workgroup owns THREADS*16 bytes of blocks
 __host__ __device__ constexpr int tile_blocks(int fmt, int threads) { return threads * 16 / fmt_block(fmt); }
 
-// Byte offset, inside the whole transformed buffer, of LDS-image byte `o` (a lane's 16-byte segment) for
-// the tile whose first block is `blk0` (global block index).  Stream boundaries inside the image are
-// multiples of 256 bytes, so a 16-byte segment never straddles two streams.
-template <int FMT, bool SA, bool SC, int T>
-__device__ __forceinline__ uint64_t soa_offset_of_image_byte(int o, uint64_t total_blocks, uint64_t blk0)
-{
-    constexpr Streams S = make_streams(FMT, SA, SC);
-    uint64_t r = 0;
-#pragma unroll
-    for (int s = 0; s < S.n; ++s) {
-        const int lo = S.off[s] * T;
-        const int hi = lo + S.width[s] * T;
-        if (o >= lo && o < hi)
-            r = (uint64_t)S.off[s] * total_blocks + (uint64_t)S.width[s] * blk0 + (uint64_t)(o - lo);
-    }
-    return r;
-}
-
-// The same for a lane of wave W of the workgroup (W known at compile time: for_this_wave).  A wave's 1 KiB of the image meets at
-// most three streams (BC3 with split alphas, wave 0) and usually one, so the per-lane select chain over all streams -- six
-// compares and six 64-bit multiply-adds per lane, 40 % of the aligned inverse kernel's instructions, all in front of its load --
-// shrinks to the streams the wave can meet, and the stream bases stay on the scalar unit.
-#ifndef DXTLT_WAVE_OFFSETS
-#define DXTLT_WAVE_OFFSETS 1   // 0: the per-lane select chain of rounds 1-4 (A/B: profiles/r05_wave_offsets.txt)
-#endif
+// Byte offset, inside the whole transformed buffer, of LDS-image byte `o` (a lane's 16-byte segment) for the tile whose first
+// block is `blk0` (global block index), for a lane of wave W of the workgroup (W known at compile time: for_this_wave).  Stream
+// boundaries inside the image are multiples of 256 bytes, so a 16-byte segment never straddles two streams.  A wave's 1 KiB of
+// the image meets at most three streams (BC3 with split alphas, wave 0) and usually one, so the per-lane select chain over all
+// streams of rounds 1-4 -- six compares and six 64-bit multiply-adds per lane, 40 % of the aligned inverse kernel's
+// instructions, all in front of its load -- shrinks to the streams the wave can meet, and the stream bases stay on the scalar
+// unit (A/B: profiles/r05_wave_offsets.txt).
 template <int FMT, bool SA, bool SC, int T, int W>
 __device__ __forceinline__ uint64_t soa_offset_of_image_byte_in_wave(int o, uint64_t total_blocks, uint64_t blk0)
 {
@@ -179,15 +125,11 @@ template <int FMT, bool SA, bool SC, int THREADS>
 __device__ __forceinline__ uint64_t soa_offset_of_lane(int t, uint64_t total_blocks, uint64_t blk0)
 {
     constexpr int T = tile_blocks(FMT, THREADS);
-#if DXTLT_WAVE_OFFSETS
     uint64_t o = 0;
     for_this_wave<THREADS / 64>(t, [&](auto wi) {
         o = soa_offset_of_image_byte_in_wave<FMT, SA, SC, T, decltype(wi)::value>(t * 16, total_blocks, blk0);
     });
     return o;
-#else
-    return soa_offset_of_image_byte<FMT, SA, SC, T>(t * 16, total_blocks, blk0);
-#endif
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -209,22 +151,18 @@ __device__ __forceinline__ lds_halfword* lds_halfwords(uint8_t* lds, int byte_of
 
 // The 6-byte alpha-index record of a BC3 block (bytes 2..7 of the block) in the LDS image: records are 6 bytes apart, so a
 // record's address is a multiple of 4 for every other block and 2 further for the blocks in between.  Round 1 moved it as three
-// halfwords (three DS instructions per lane and direction); here it is TWO: an aligned dword and a halfword, the order picked
+// halfwords (three DS instructions per lane and direction; A/B: profiles/r05_bc3_record6.txt); here it is TWO: an aligned dword and a halfword, the order picked
 // by the address's bit 1 with selects (no divergent branch) going in, and one ds_read2_b32 of the two aligned dwords that
 // cover the record plus a funnel shift (v_alignbit) coming out.  Every access is naturally aligned (DS accesses at addresses
 // that are not multiples of their width run several times slower on gfx950, profiles/r01_s), and the pointers are volatile /
 // declared 4-byte aligned so that clang neither fuses them into such accesses nor widens the pair into a ds_read_b64.
 // Reference for the bytes: bc3/src/transform/standard/transform/portable32.rs:46-64 (alpha indices = block bytes 2..7, verbatim).
-#ifndef DXTLT_BC3_RECORD6
-#define DXTLT_BC3_RECORD6 1   // 0: the three-halfword form (A/B: profiles/r05_bc3_record6.txt)
-#endif
 typedef uint32_t u32x2_align4 __attribute__((ext_vector_type(2), aligned(4)));
 typedef volatile uint32_t __attribute__((address_space(3))) lds_dword;
 
 // `addr` even; lo16 = record bytes 0..1 (low half), hi32 = record bytes 2..5
 __device__ __forceinline__ void lds_put_record6(uint8_t* lds, int addr, uint32_t lo16, uint32_t hi32)
 {
-#if DXTLT_BC3_RECORD6
     const bool odd = (addr & 2) != 0;
     const int a32 = odd ? addr + 2 : addr;
     const int a16 = odd ? addr : addr + 4;
@@ -232,25 +170,15 @@ __device__ __forceinline__ void lds_put_record6(uint8_t* lds, int addr, uint32_t
     const uint32_t v16 = odd ? lo16 : hi32 >> 16;
     *(lds_dword*)(lds + a32) = v32;
     *lds_halfwords(lds, a16) = (uint16_t)v16;
-#else
-    lds_halfwords(lds, addr)[0] = (uint16_t)lo16;
-    lds_halfwords(lds, addr)[1] = (uint16_t)hi32;
-    lds_halfwords(lds, addr)[2] = (uint16_t)(hi32 >> 16);
-#endif
 }
 
 __device__ __forceinline__ void lds_get_record6(uint8_t* lds, int addr, uint32_t& lo16, uint32_t& hi32)
 {
-#if DXTLT_BC3_RECORD6
     const u32x2_align4 w = *reinterpret_cast<const u32x2_align4*>(lds + (addr & ~3));
     const uint32_t sh = (uint32_t)(addr & 2) * 8u;
     const uint32_t rec = __builtin_amdgcn_alignbit(w.y, w.x, sh);   // record bytes 0..3
     lo16 = rec & 0xFFFFu;
     hi32 = (rec >> 16) | ((w.y >> sh) << 16);                       // bytes 2..3, then bytes 4..5
-#else
-    lo16 = lds_at<uint16_t>(lds, addr + 0);
-    hi32 = (uint32_t)lds_at<uint16_t>(lds, addr + 2) | ((uint32_t)lds_at<uint16_t>(lds, addr + 4) << 16);
-#endif
 }
 
 // One BC4 block (an 8-byte BC3 alpha half: a0 a1 i0 i1 | i2 i3 i4 i5 = lo, hi) into the image of a stream table whose endpoint
@@ -446,9 +374,9 @@ __device__ __forceinline__ uint64_t xcd_contiguous_tile(uint32_t orig, uint32_t 
 // colour half -- and normalize_block_bc23 (bc23_normalize.h) rewrites it.  BC3 has 11 non-trivial (alpha mode, colour mode)
 // pairs, so the modes are no template parameters here: NORM == kNormFromArgument says "the modes are a wave-uniform kernel
 // argument", norm_modes = alpha_mode << 2 | color_mode, and there is one kernel set more per (format, VARIANT, SA, SC).
-// The argument rides in bits the plain kernels never see set (kNormModesShift): of `xcd_remap` in fwd_tiled, of
-// Shifts::halo_vecs in the halo tiles (and, experiments build, in the first-form shifted tiles; the element kernel: the top
-// byte of `count`), so the kernels keep their signatures and every instantiation with another NORM compiles as before.
+// The argument rides in bits the plain kernels never see set (kNormModesShift): of `flags` in fwd_tiled, of
+// Shifts::halo_vecs in the halo tiles, so the kernels keep their signatures and every instantiation with another NORM compiles
+// as before.
 constexpr int kNormFromArgument = 4;   // (behind bc1_normalize.h's kNormTransparentOnly = 3)
 constexpr int kNormModesShift = 8;
 __host__ __device__ constexpr int pack_norm_modes(int alpha_mode, int color_mode) { return (alpha_mode << 2) | color_mode; }
@@ -470,8 +398,8 @@ __device__ __forceinline__ u32x4 normalize_vector(u32x4 q, int norm_modes = 0)
     return q;
 }
 
-// bit 1 of the tiled kernels' `xcd_remap` argument (bit 0, experiments build only: XCD-contiguous tile order): the launch is two-dimensional, blockIdx.y numbers the buffers of a regular
-// array whose sources / destinations lie `*_stride` bytes apart (first pointer argument, second pointer argument)
+// bit 1 of the tiled kernels' `flags` argument (bit 0 is unused): the launch is two-dimensional, blockIdx.y numbers the buffers
+// of a regular array whose sources / destinations lie `*_stride` bytes apart (first pointer argument, second pointer argument)
 constexpr int kTiledArray = 2;
 
 // One aligned tile (the body of fwd_tiled / inv_tiled; the batch kernel runs it for buffers whose stream bases are aligned).
@@ -483,16 +411,12 @@ __device__ __forceinline__ void fwd_aligned_tile(const uint8_t* __restrict__ aos
 {
     constexpr int T = tile_blocks(FMT, THREADS);
     const int t = threadIdx.x;
-    WG_MARK(1);
     const u32x4 q = normalize_vector<FMT, NORM>(gload16(aos + tile * (THREADS * 16) + t * 16), norm_modes);
-    WG_MARK_LOADS_DONE(2);
     scatter_to_image<FMT, VARIANT, SA, SC, T>(lds, t, q);
     __syncthreads();
-    WG_MARK(3);
     const u32x4 v = lds_at<u32x4>(lds, t * 16);
     const uint64_t o = soa_offset_of_lane<FMT, SA, SC, THREADS>(t, total_blocks, first_block + tile * T);
     gstore16(soa + o, v);
-    WG_MARK(4);
 }
 
 // Where an inverse tile's blocks go.  A SINK has two members, called by every lane that holds blocks, with the lane's vector q
@@ -538,21 +462,16 @@ __device__ __forceinline__ void inv_aligned_tile(const uint8_t* __restrict__ soa
 template <int FMT, int VARIANT, bool SA, bool SC, int THREADS, int NORM = kNormNone>
 __global__ void __launch_bounds__(THREADS)
 fwd_tiled(const uint8_t* __restrict__ aos, uint8_t* __restrict__ soa, uint64_t total_blocks, uint64_t first_block,
-          int xcd_remap, int64_t aos_stride, int64_t soa_stride)
+          int flags, int64_t aos_stride, int64_t soa_stride)
 {
     __shared__ __attribute__((aligned(16))) uint8_t lds[THREADS * 16];
-    WG_MARK(0);
-    if (xcd_remap & kTiledArray) {   // a regular array of buffers: blockIdx.y is the buffer (launch_batch)
+    if (flags & kTiledArray) {   // a regular array of buffers: blockIdx.y is the buffer (launch_batch)
         aos += (int64_t)blockIdx.y * aos_stride;
         soa += (int64_t)blockIdx.y * soa_stride;
     }
-#ifdef DXTLT_EXPERIMENTS
-    const uint64_t tile = (xcd_remap & 1) ? xcd_contiguous_tile(blockIdx.x, gridDim.x) : (uint64_t)blockIdx.x;
-#else
     const uint64_t tile = blockIdx.x;   // identity order: the XCD-contiguous one costs aligned tiles 0.01-0.03 (profiles/r01_i_*)
-#endif
     if constexpr (NORM == kNormFromArgument)
-        fwd_aligned_tile<FMT, VARIANT, SA, SC, THREADS, NORM>(aos, soa, total_blocks, first_block, tile, lds, xcd_remap >> kNormModesShift);
+        fwd_aligned_tile<FMT, VARIANT, SA, SC, THREADS, NORM>(aos, soa, total_blocks, first_block, tile, lds, flags >> kNormModesShift);
     else
         fwd_aligned_tile<FMT, VARIANT, SA, SC, THREADS, NORM>(aos, soa, total_blocks, first_block, tile, lds);
 }
@@ -560,18 +479,14 @@ fwd_tiled(const uint8_t* __restrict__ aos, uint8_t* __restrict__ soa, uint64_t t
 template <int FMT, int VARIANT, bool SA, bool SC, int THREADS>
 __global__ void __launch_bounds__(THREADS)
 inv_tiled(const uint8_t* __restrict__ soa, uint8_t* __restrict__ aos, uint64_t total_blocks, uint64_t first_block,
-          int xcd_remap, int64_t soa_stride, int64_t aos_stride)
+          int flags, int64_t soa_stride, int64_t aos_stride)
 {
     __shared__ __attribute__((aligned(16))) uint8_t lds[THREADS * 16];
-    if (xcd_remap & kTiledArray) {
+    if (flags & kTiledArray) {
         soa += (int64_t)blockIdx.y * soa_stride;
         aos += (int64_t)blockIdx.y * aos_stride;
     }
-#ifdef DXTLT_EXPERIMENTS
-    const uint64_t tile = (xcd_remap & 1) ? xcd_contiguous_tile(blockIdx.x, gridDim.x) : (uint64_t)blockIdx.x;
-#else
     const uint64_t tile = blockIdx.x;
-#endif
     inv_aligned_tile<FMT, VARIANT, SA, SC, THREADS>(soa, aos, total_blocks, first_block, tile, lds);
 }
 
@@ -602,45 +517,7 @@ struct Shifts {
     // behind them (the rest, and forward the last bytes of every stream that the whole tiles' moved-back windows leave out).
     uint32_t full_tiles;
     uint64_t range_blocks;
-#ifdef DXTLT_EXPERIMENTS
-    int xcd_remap;    // 1: consecutive tiles stay on one XCD (see xcd_contiguous_tile); the product fixes it per kernel
-    int line_policy;  // forward store policy (first form: 1 = write-through for lines one wave instruction writes whole, 2 = plain
-                      // stores on shared lines; halo tiles: 3 = write-through, else plain nt); the product always runs 3
-    int skip_partial; // TIMING experiment, WRONG OUTPUT: 1 = leave out the partial head / tail segments and the halo load
-#endif
 };
-
-// The tile order of the halo (forward) and shifted (inverse) kernels, and the halo tiles' store policy: fixed in the product
-// (identity order + write-through forward -- every window starts on a 64-byte sector, nothing is shared; XCD-contiguous order
-// inverse -- neighbouring tiles share lines), run-time values in the experiments build.
-__device__ __forceinline__ bool shifts_xcd_contiguous(const Shifts& sh, bool product_default)
-{
-#ifdef DXTLT_EXPERIMENTS
-    (void)product_default;
-    return sh.xcd_remap != 0;
-#else
-    (void)sh;
-    return product_default;
-#endif
-}
-__device__ __forceinline__ bool shifts_halo_write_through(const Shifts& sh)
-{
-#ifdef DXTLT_EXPERIMENTS
-    return sh.line_policy == 3;
-#else
-    (void)sh;
-    return true;
-#endif
-}
-__device__ __forceinline__ bool shifts_skip_partial(const Shifts& sh)
-{
-#ifdef DXTLT_EXPERIMENTS
-    return sh.skip_partial != 0;
-#else
-    (void)sh;
-    return false;
-#endif
-}
 
 // The NORM == kNormFromArgument kernels: takes the modes out of the bits above Shifts::halo_vecs and returns them
 __device__ __forceinline__ int take_norm_modes(Shifts& sh)
@@ -685,15 +562,9 @@ __device__ __forceinline__ Shifts shifts_fetched_at_once(const Shifts& in)
 {
     Shifts s = in;
     // ONE statement: with several, the compiler fetches what the first one needs, waits, and only then asks for the next one's
-#ifdef DXTLT_EXPERIMENTS
-    asm("" : "+s"(s.d[0]), "+s"(s.d[1]), "+s"(s.d[2]), "+s"(s.d[3]), "+s"(s.d[4]), "+s"(s.d[5]), "+s"(s.gbase[0]), "+s"(s.gbase[1]),
-             "+s"(s.gbase[2]), "+s"(s.gbase[3]), "+s"(s.gbase[4]), "+s"(s.gbase[5]), "+s"(s.xcd_remap), "+s"(s.line_policy),
-             "+s"(s.skip_partial), "+s"(s.natural), "+s"(s.halo_vecs), "+s"(s.full_tiles), "+s"(s.range_blocks));
-#else
     asm("" : "+s"(s.d[0]), "+s"(s.d[1]), "+s"(s.d[2]), "+s"(s.d[3]), "+s"(s.d[4]), "+s"(s.d[5]), "+s"(s.gbase[0]), "+s"(s.gbase[1]),
              "+s"(s.gbase[2]), "+s"(s.gbase[3]), "+s"(s.gbase[4]), "+s"(s.gbase[5]), "+s"(s.natural), "+s"(s.halo_vecs),
              "+s"(s.full_tiles), "+s"(s.range_blocks));
-#endif
     return s;
 }
 
@@ -836,7 +707,7 @@ __device__ __forceinline__ void scatter_shifted_bc4_block(uint8_t* lds, int b, u
     } else {
         lds_put<2, NAT>(lds, base[ALPHA] + 2 * b, lo & 0xFFFF);
     }
-    if constexpr (NAT && DXTLT_BC3_RECORD6) {
+    if constexpr (NAT) {
         lds_put_record6(lds, base[AIDX] + 6 * b, lo >> 16, hi);   // (an even address: the shift is natural)
     } else {
         lds_put<2, NAT>(lds, base[AIDX] + 6 * b + 0, lo >> 16);
@@ -853,7 +724,7 @@ __device__ __forceinline__ void gather_shifted_bc4_block(uint8_t* lds, int b, ui
         a01 = (uint32_t)lds_get<1>(lds, base[ALPHA] + b) | ((uint32_t)lds_get<1>(lds, base[A1] + b) << 8);
     else
         a01 = (uint32_t)lds_get<2, NAT>(lds, base[ALPHA] + 2 * b);
-    if constexpr (NAT && DXTLT_BC3_RECORD6) {
+    if constexpr (NAT) {
         uint32_t i01;
         lds_get_record6(lds, base[AIDX] + 6 * b, i01, hi);   // (reads up to 2 bytes past the record: the next record or the padding)
         lo = a01 | (i01 << 16);
@@ -914,7 +785,7 @@ __device__ __forceinline__ void scatter_shifted(uint8_t* lds, int u, u32x4 q, co
             } else {
                 lds_put<2, NAT>(lds, base[F::alpha] + 2 * u, q.x & 0xFFFF);
             }
-            if constexpr (NAT && DXTLT_BC3_RECORD6) {
+            if constexpr (NAT) {
                 lds_put_record6(lds, base[F::aidx] + 6 * u, q.x >> 16, q.y);   // (an even address: the shift is natural)
             } else {
                 lds_put<2, NAT>(lds, base[F::aidx] + 6 * u + 0, q.x >> 16);
@@ -988,7 +859,7 @@ __device__ __forceinline__ u32x4 gather_shifted(uint8_t* lds, int u, const int (
                 a01 = (uint32_t)lds_get<1>(lds, base[F::alpha] + u) | ((uint32_t)lds_get<1>(lds, base[F::a1] + u) << 8);
             else
                 a01 = (uint32_t)lds_get<2, NAT>(lds, base[F::alpha] + 2 * u);
-            if constexpr (NAT && DXTLT_BC3_RECORD6) {
+            if constexpr (NAT) {
                 uint32_t i01, i2345;
                 lds_get_record6(lds, base[F::aidx] + 6 * u, i01, i2345);   // (reads up to 2 bytes past the record: the region's padding)
                 q.x = a01 | (i01 << 16);
@@ -1066,29 +937,25 @@ constexpr int kShiftLdsBytes = shift_lds_bytes(1);
 // shape the memory side's write path dislikes -- the ALIGNED kernel shows it as soon as it is run with 256 lanes (forward 0.810
 // against 0.861 with 128 lanes; with the split 0.839 / 0.846; +50 % TCC_EA0_WRREQ_STALL at identical request counts) -- and it is
 // what round 3 reported as "BC1 no-split halo forward -0.026, cause not found" (tools/bc1_nosplit_probe.py,
-// profiles/r05_bc1_nosplit.txt).  128 lanes for EVERY BC1 tile was measured too (-DDXTLT_BC1_SHIFT_THREADS=128: the size the
+// profiles/r05_bc1_nosplit.txt).  128 lanes for EVERY BC1 tile was measured too (kBc1ShiftThreads = 128: the size the
 // aligned BC1 tiles have had since round 1) and is not the default: single call +0.004 / -0.005, corpus batch -0.033 / -0.008
-// (twice the workgroups, twice the halo share, twice the lookups per byte).
-#ifndef DXTLT_BC1_SHIFT_THREADS
-#define DXTLT_BC1_SHIFT_THREADS 256
-#endif
-__host__ __device__ constexpr int shift_tile_threads(int fmt) { return fmt == kBc1 ? DXTLT_BC1_SHIFT_THREADS : 256; }
+// (twice the workgroups, twice the halo share, twice the lookups per byte; profiles/r05_bc1_nosplit.txt).
+constexpr int kBc1ShiftThreads = 256;
+__host__ __device__ constexpr int shift_tile_threads(int fmt) { return fmt == kBc1 ? kBc1ShiftThreads : 256; }
 __host__ __device__ constexpr int halo_tile_threads(int fmt, bool split_colour)
 {
     return fmt == kBc1 && !split_colour ? 128 : shift_tile_threads(fmt);
 }
 // Lanes of every tile of a BATCH launch, planned per (format, colour split, direction) like the single-buffer call's: the forward
 // launch of BC1 without the colour split takes the 128-lane tiles too (aligned, halo and edge tiles alike: the aligned tile shows the
-// 2 KiB + 2 KiB store shape just as the halo tile does).  Same-box A/B against -DDXTLT_BATCH_BC1_NOSPLIT_FWD_THREADS=256, the round-5
+// 2 KiB + 2 KiB store shape just as the halo tile does).  Same-box A/B against kBatchBc1NosplitFwdThreads = 256, the round-5
 // shape (tools/batch_nosplit_probe.py, profiles/r06_batch_bc1_nosplit.txt): 64 x (16 MiB - 1 block) 0.72 -> 0.79, 1024 x (1 MiB - 1
 // block) 0.69 -> 0.77, mixed aligned sizes 0.76 -> 0.78, the mip-chained corpus level (-0.015 with YCoCg-R, +0.013 without).  The same
 // record holds the negative for the SPLIT setting: 128 lanes lose 0.015-0.045 on every size class of the corpus, so 256 stay there.
-#ifndef DXTLT_BATCH_BC1_NOSPLIT_FWD_THREADS
-#define DXTLT_BATCH_BC1_NOSPLIT_FWD_THREADS 128
-#endif
+constexpr int kBatchBc1NosplitFwdThreads = 128;
 __host__ __device__ constexpr int batch_tile_threads(int fmt, bool split_colour, bool inverse)
 {
-    return !inverse && fmt == kBc1 && !split_colour ? DXTLT_BATCH_BC1_NOSPLIT_FWD_THREADS : shift_tile_threads(fmt);
+    return !inverse && fmt == kBc1 && !split_colour ? kBatchBc1NosplitFwdThreads : shift_tile_threads(fmt);
 }
 // R = sub-tiles of 256 lanes per workgroup.  Only R = 1 is instantiated: with misaligned stream bases every slice shares
 // its first and last 128-byte line with the neighbouring tiles (BC3, 256 blocks per tile: 12 of 38 lines), and R = 4
@@ -1099,7 +966,7 @@ __host__ __device__ constexpr int batch_tile_threads(int fmt, bool split_colour,
 
 // ------------------------------------------------------------------------------------------------
 // Forward HALO tiles: the tiled structure for transformed buffers whose stream bases are off their lines, forward direction.
-// The first form (bcn_experiments.h) kept each tile's slices where they fall and moved the partial first / last 16-byte segment
+// The first form (removed; DESIGN.md names the last commit that carries it) kept each tile's slices where they fall and moved the partial first / last 16-byte segment
 // of every slice with typed narrow stores; the counters on odd block counts (profiles/r02_a_shift_pmc.txt, BC3 default settings,
 // 2^26 + 1 blocks against 2^26) showed HBM requests identical and all of them full 64-byte ones, memory-side write stalls 50 x
 // LOWER -- but 5.5 x the vector-memory store instructions per wave, 2 x the VALU and 3.6 x the SALU instructions, 2.65 x the
@@ -1117,14 +984,13 @@ __host__ __device__ constexpr int batch_tile_threads(int fmt, bool split_colour,
 // read-modify-write -- with 16-byte boundaries such lines had to meet in one L2 (XCD-contiguous tile order, itself worth
 // -0.04) or cost 0.08 (profiles/r02_b_shift_probe.txt).  The halo grows to at most 63 bytes per stream = at most 63
 // blocks for a 1-byte stream; only as many vectors as some stream needs are fetched (Shifts::halo_vecs).
-#ifndef DXTLT_HALO_ALIGN
-#define DXTLT_HALO_ALIGN 64   // experiment: 128 = windows on 128-byte lines (no line shared between tiles, halo up to 127 bytes per stream)
-#endif
-constexpr int kHaloAlign = DXTLT_HALO_ALIGN;
+// (128 -- windows on 128-byte lines: no line shared between tiles, halo up to 127 bytes per stream -- and 32 were measured too:
+// profiles/r04_batch_edge_tiles.txt)
+constexpr int kHaloAlign = 64;
 constexpr int kHaloBlocks = kHaloAlign;
 constexpr int kHaloPad = kHaloAlign;   // bytes between the stream regions of the LDS image: room for d_s
-// THREADS: lanes of a halo tile -- 256; 128 for BC1 without the colour split (launch_transform); 512 in the experiments build
-// (round 5's attempt to halve the halo share per tile: BC3 +-0.005, BC1 -0.025, profiles/r05_halo_512.txt)
+// THREADS: lanes of a halo tile -- 256; 128 for BC1 without the colour split (launch_transform).  512 lanes, round 5's
+// attempt to halve the halo share per tile, lost: BC3 +-0.005, BC1 -0.025 (profiles/r05_halo_512.txt)
 template <int FMT, int THREADS = 256>
 constexpr int halo_lds_bytes() { return fmt_block(FMT) * (tile_blocks(FMT, THREADS) + kHaloBlocks) + kHaloPad * 6; }
 
@@ -1167,7 +1033,7 @@ __device__ __forceinline__ void copy_segment_bytes(uint8_t* dst, const uint8_t* 
 // the tile's alone 0.49; write-through except in the line where the stream begins or ends 0.55 (profiles/r04_batch_edge_tiles.txt).
 template <int FMT, bool SA, bool SC, int W, bool EDGE = false, int THREADS = 256>
 __device__ __forceinline__ void halo_copy_out_wave(uint8_t* __restrict__ soa, const uint8_t* lds, int t, const uint64_t (&gb)[6],
-                                                   const Shifts& sh, const int (&vlo)[6], const int (&vhi)[6])
+                                                   const int (&vlo)[6], const int (&vhi)[6])
 {
     constexpr Streams S = make_streams(FMT, SA, SC);
     constexpr int T = tile_blocks(FMT, THREADS);
@@ -1205,11 +1071,8 @@ __device__ __forceinline__ void halo_copy_out_wave(uint8_t* __restrict__ soa, co
         return;
     }
     // Every window starts on a 64-byte sector, so no sector is shared between tiles: write-through streaming stores as in the
-    // aligned tiles (the experiments build can ask for plain nt, which lets L2 merge the parts of a shared line)
-    if (shifts_halo_write_through(sh))
-        gstore16(soa + g, lds_at<u32x4>(const_cast<uint8_t*>(lds), la));
-    else
-        __builtin_nontemporal_store(lds_at<u32x4>(const_cast<uint8_t*>(lds), la), reinterpret_cast<u32x4*>(soa + g));
+    // aligned tiles
+    gstore16(soa + g, lds_at<u32x4>(const_cast<uint8_t*>(lds), la));
 }
 
 // one halo tile; `lds`: halo_lds_bytes<FMT, THREADS>() bytes
@@ -1236,39 +1099,35 @@ __device__ __forceinline__ void fwd_halo_tile(const uint8_t* __restrict__ aos, u
     // a 63-block halo), a line fetched temporally is still in the memory-side cache.  Found by accident -- the compiler
     // merged an experiment's two loads and dropped the hint -- and worth 0.05-0.07 of peak on large halos
     // (profiles/r02_b_shift_probe.txt); on small halos it costs nothing.
-    WG_MARK(1);
     const u32x4 q = *reinterpret_cast<const u32x4*>(tile_aos + t * 16);
     // Only the blocks that have bytes inside a window are fetched: max over the streams of ceil(d_s / w_s) blocks, at
     // most 16 (the whole halo costs 0.02 of peak on BC3 -- 6 % more bytes read -- profiles/r02_b_shift_probe.txt).
     const int hv = sh.halo_vecs;
-    const bool has_halo = tile > 0 && t < hv && !shifts_skip_partial(sh);
+    const bool has_halo = tile > 0 && t < hv;
     if (has_halo) {
         // plain load: the previous tile has just fetched these lines
         const u32x4 qh = *reinterpret_cast<const u32x4*>(tile_aos - hv * 16 + t * 16);
         scatter_shifted<FMT, VARIANT, SA, SC, NAT>(lds, t - hv, normalize_vector<FMT, NORM>(qh, norm_modes), base);
     }
     static_assert(HV <= THREADS, "the halo is loaded by the first lanes of the workgroup");
-    WG_MARK_LOADS_DONE(2);
     scatter_shifted<FMT, VARIANT, SA, SC, NAT>(lds, t, normalize_vector<FMT, NORM>(q, norm_modes), base);
     __syncthreads();
-    WG_MARK(3);
 
     uint64_t gb[6];
     slice_bases<FMT, SA, SC, T>(tile, sh, gb);
     const int none[6] = {0, 0, 0, 0, 0, 0};   // (tile 0 and the last tile of a range run fwd_halo_edge_tile)
     if constexpr (THREADS == 256) {
         switch (__builtin_amdgcn_readfirstlane(t >> 6)) {
-        case 0: halo_copy_out_wave<FMT, SA, SC, 0>(soa, lds, t, gb, sh, none, none); break;
-        case 1: halo_copy_out_wave<FMT, SA, SC, 1>(soa, lds, t, gb, sh, none, none); break;
-        case 2: halo_copy_out_wave<FMT, SA, SC, 2>(soa, lds, t, gb, sh, none, none); break;
-        default: halo_copy_out_wave<FMT, SA, SC, 3>(soa, lds, t, gb, sh, none, none); break;
+        case 0: halo_copy_out_wave<FMT, SA, SC, 0>(soa, lds, t, gb, none, none); break;
+        case 1: halo_copy_out_wave<FMT, SA, SC, 1>(soa, lds, t, gb, none, none); break;
+        case 2: halo_copy_out_wave<FMT, SA, SC, 2>(soa, lds, t, gb, none, none); break;
+        default: halo_copy_out_wave<FMT, SA, SC, 3>(soa, lds, t, gb, none, none); break;
         }
     } else {
         for_this_wave<THREADS / 64>(t, [&](auto wi) {
-            halo_copy_out_wave<FMT, SA, SC, decltype(wi)::value, false, THREADS>(soa, lds, t, gb, sh, none, none);
+            halo_copy_out_wave<FMT, SA, SC, decltype(wi)::value, false, THREADS>(soa, lds, t, gb, none, none);
         });
     }
-    WG_MARK(4);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1389,14 +1248,14 @@ __device__ __forceinline__ void fwd_halo_edge_tile(const uint8_t* __restrict__ a
     }
     if constexpr (THREADS == 256) {
         switch (__builtin_amdgcn_readfirstlane(t >> 6)) {
-        case 0: halo_copy_out_wave<FMT, SA, SC, 0, true>(soa, lds, t, gb, sh, vlo, vhi); break;
-        case 1: halo_copy_out_wave<FMT, SA, SC, 1, true>(soa, lds, t, gb, sh, vlo, vhi); break;
-        case 2: halo_copy_out_wave<FMT, SA, SC, 2, true>(soa, lds, t, gb, sh, vlo, vhi); break;
-        default: halo_copy_out_wave<FMT, SA, SC, 3, true>(soa, lds, t, gb, sh, vlo, vhi); break;
+        case 0: halo_copy_out_wave<FMT, SA, SC, 0, true>(soa, lds, t, gb, vlo, vhi); break;
+        case 1: halo_copy_out_wave<FMT, SA, SC, 1, true>(soa, lds, t, gb, vlo, vhi); break;
+        case 2: halo_copy_out_wave<FMT, SA, SC, 2, true>(soa, lds, t, gb, vlo, vhi); break;
+        default: halo_copy_out_wave<FMT, SA, SC, 3, true>(soa, lds, t, gb, vlo, vhi); break;
         }
     } else {
         for_this_wave<THREADS / 64>(t, [&](auto wi) {
-            halo_copy_out_wave<FMT, SA, SC, decltype(wi)::value, true, THREADS>(soa, lds, t, gb, sh, vlo, vhi);
+            halo_copy_out_wave<FMT, SA, SC, decltype(wi)::value, true, THREADS>(soa, lds, t, gb, vlo, vhi);
         });
     }
     constexpr int XS = kHaloAlign / 16;   // up to kHaloAlign - 1 bytes of a stream lie behind its window: XS more segments per stream
@@ -1426,14 +1285,13 @@ fwd_tiled_halo(const uint8_t* __restrict__ aos_arg, uint8_t* __restrict__ soa_ar
                Shifts sh_arg)
 {
     __shared__ __attribute__((aligned(16))) uint8_t lds[halo_lds_bytes<FMT, THREADS>()];
-    WG_MARK(0);
     const uint32_t wg = blockIdx.x;
     const Shifts sh = shifts_fetched_at_once(sh_arg);
     const uint8_t* __restrict__ aos = fetched_now(aos_arg);
     uint8_t* __restrict__ soa = fetched_now(soa_arg);
     const bool whole = wg < sh.full_tiles;
     // identity tile order: the halo is read again by the next tile, on another XCD, out of the memory-side cache (temporal loads)
-    const uint64_t tile = !whole ? (uint64_t)sh.full_tiles : shifts_xcd_contiguous(sh, false) ? xcd_contiguous_tile(wg, sh.full_tiles) : (uint64_t)wg;
+    const uint64_t tile = whole ? (uint64_t)wg : (uint64_t)sh.full_tiles;
     const bool edge = !whole || tile == 0;
     if constexpr (NORM == kNormFromArgument) {
         Shifts plain = sh;
@@ -1653,7 +1511,7 @@ inv_tiled_shift(const uint8_t* __restrict__ soa_arg, uint8_t* __restrict__ aos_a
     asm("" : "+s"(total_blocks));
     const bool whole = wg < sh.full_tiles;
     // XCD-contiguous tile order: neighbouring tiles share their first and last line
-    const uint64_t tile = !whole ? (uint64_t)sh.full_tiles : shifts_xcd_contiguous(sh, true) ? xcd_contiguous_tile(wg, sh.full_tiles) : (uint64_t)wg;
+    const uint64_t tile = whole ? xcd_contiguous_tile(wg, sh.full_tiles) : (uint64_t)sh.full_tiles;
     const bool edge = !whole;
     if (edge)
         inv_shift_edge_tile<FMT, VARIANT, SA, SC, THREADS>(soa, aos, total_blocks, sh, tile, lds);
@@ -1662,7 +1520,7 @@ inv_tiled_shift(const uint8_t* __restrict__ soa_arg, uint8_t* __restrict__ aos_a
 }
 
 // ------------------------------------------------------------------------------------------------
-// Byte-granular accessors (the synthetic-data fill kernel; the element-granular kernel of the experiments build).
+// Byte-granular accessors (the synthetic-data fill kernel).
 // ------------------------------------------------------------------------------------------------
 template <int W>
 __device__ __forceinline__ void store_bytes(uint8_t* p, uint64_t v, bool natural)
@@ -1680,47 +1538,20 @@ __device__ __forceinline__ void store_bytes(uint8_t* p, uint64_t v, bool natural
     }
 }
 
-template <int W>
-__device__ __forceinline__ uint64_t load_bytes(const uint8_t* p, bool natural)
-{
-    if (natural) {
-        if constexpr (W == 1) return *p;
-        if constexpr (W == 2) return *reinterpret_cast<const uint16_t*>(p);
-        if constexpr (W == 4) return *reinterpret_cast<const uint32_t*>(p);
-        if constexpr (W == 8) return *reinterpret_cast<const uint64_t*>(p);
-    }
-    uint64_t v = 0;
-#pragma unroll
-    for (int i = 0; i < W; ++i)
-        v |= (uint64_t)p[i] << (8 * i);
-    return v;
-}
-
 __device__ __forceinline__ bool aligned_to(const void* p, int a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 
 // Host side: the kernels' types as launch_transform (bcn_kernels.hip) holds them
 using TiledFn = void (*)(const uint8_t*, uint8_t*, uint64_t, uint64_t, int, int64_t, int64_t);
 using ShiftFn = void (*)(const uint8_t*, uint8_t*, uint64_t, uint64_t, Shifts);
-#ifdef DXTLT_EXPERIMENTS
-using GenericFn = void (*)(const uint8_t*, uint8_t*, uint64_t, uint64_t, uint64_t, uint64_t);
-#endif
 
 // The BC2 / BC3 forward kernels with block normalisation fused in (NORM == kNormFromArgument; bcn_norm23_kernels.hip): one
-// aligned tile size, the format's default, and the halo tiles with their edge tiles (halo[1]: natural shifts); in the
-// experiments build also the first-form shifted tiles and the element kernel.  fmt kBc2 or kBc3, variant 0..3.
+// aligned tile size, the format's default, and the halo tiles with their edge tiles (halo[1]: natural shifts).  fmt kBc2 or kBc3,
+// variant 0..3.
 struct FusedNormKernels {
     TiledFn tiled;
     ShiftFn halo[2];
-#ifdef DXTLT_EXPERIMENTS
-    ShiftFn shifted;
-    GenericFn generic;
-#endif
 };
 FusedNormKernels fused_norm_kernels_bc23(Format fmt, int variant, bool sa, bool sc);
 
 }  // namespace dxtlt
-
-#ifdef DXTLT_EXPERIMENTS
-#include "bcn_experiments.h"
-#endif

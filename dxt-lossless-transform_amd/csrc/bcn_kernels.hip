@@ -39,9 +39,8 @@
 //     pieces where a stream begins or ends inside one, nothing outside.  They run as one more workgroup of the same launch
 //     (halo / shifted) or as one more launch of one workgroup (behind aligned tiles).  There is no element-granular path.
 //
-// Experiments (the element-granular kernel, the first form of the forward shifted tiles, run-time store policies / tile orders
-// and the wrong-output timing switch the measurements in profiles/ were taken with) are compiled only with -DDXTLT_EXPERIMENTS,
-// a side build (bcn_device.h); this file then also honours the `force_path` bits documented at launch_transform.
+// The experiments the measurements in profiles/ were taken with (the element-granular kernel, the first form of the forward
+// shifted tiles, run-time store policies / tile orders) were removed; DESIGN.md names the last commit that carries them.
 #include "bcn_device.h"
 
 namespace dxtlt {
@@ -80,14 +79,8 @@ namespace {
 
 struct KernelSet {
     TiledFn tiled[4];  // aligned tiles of 64, 128, 256, 512 threads
-    ShiftFn shifted;   // inverse: shifted tiles + edge tile (shift_tile_threads(fmt) lanes); forward: nullptr (experiments build: the first form, 256)
+    ShiftFn shifted;   // inverse: shifted tiles + edge tile (shift_tile_threads(fmt) lanes); forward: nullptr
     ShiftFn halo[2];   // forward: halo tiles + edge tiles, halo_tile_threads(fmt, split_colour) lanes ([1]: natural shifts); inverse: nullptr
-#ifdef DXTLT_EXPERIMENTS
-    ShiftFn halo512;   // natural shifts: 512-lane halo tiles, dxtlt_set_tuning(512, ...) -- measured and not adopted (profiles/r05_halo_512.txt)
-#endif
-#ifdef DXTLT_EXPERIMENTS
-    GenericFn generic;
-#endif
 };
 
 inline int threads_slot(int threads) { return threads == 64 ? 0 : threads == 128 ? 1 : threads == 512 ? 3 : 2; }
@@ -109,18 +102,7 @@ KernelSet kernels_for(bool inverse)
         ks.tiled[3] = fwd_tiled<FMT, VARIANT, SA, SC, 512>;
         ks.halo[0] = fwd_tiled_halo<FMT, VARIANT, SA, SC, kNormNone, false, halo_tile_threads(FMT, SC)>;
         ks.halo[1] = fwd_tiled_halo<FMT, VARIANT, SA, SC, kNormNone, true, halo_tile_threads(FMT, SC)>;
-#ifdef DXTLT_EXPERIMENTS
-        ks.halo512 = fwd_tiled_halo<FMT, VARIANT, SA, SC, kNormNone, true, 512>;
-#endif
     }
-#ifdef DXTLT_EXPERIMENTS
-    if (inverse) {
-        ks.generic = generic_kernel<FMT, VARIANT, SA, SC, true>;
-    } else {
-        ks.shifted = fwd_tiled_shift<FMT, VARIANT, SA, SC>;
-        ks.generic = generic_kernel<FMT, VARIANT, SA, SC, false>;
-    }
-#endif
     return ks;
 }
 
@@ -157,10 +139,6 @@ KernelSet bc1_norm_kernels()
     ks.tiled[0] = ks.tiled[1] = ks.tiled[2] = ks.tiled[3] = tiled;
     ks.halo[0] = fwd_tiled_halo<kBc1, VARIANT, false, SC, NORM, false, halo_tile_threads(kBc1, SC)>;
     ks.halo[1] = fwd_tiled_halo<kBc1, VARIANT, false, SC, NORM, true, halo_tile_threads(kBc1, SC)>;
-#ifdef DXTLT_EXPERIMENTS
-    ks.shifted = fwd_tiled_shift<kBc1, VARIANT, false, SC, NORM>;
-    ks.generic = generic_kernel<kBc1, VARIANT, false, SC, false, NORM>;
-#endif
     return ks;
 }
 
@@ -174,10 +152,6 @@ KernelSet bc23_norm_kernels(Format fmt, int variant, bool sa, bool sc)
     ks.tiled[0] = ks.tiled[1] = ks.tiled[2] = ks.tiled[3] = f.tiled;
     ks.halo[0] = f.halo[0];
     ks.halo[1] = f.halo[1];
-#ifdef DXTLT_EXPERIMENTS
-    ks.shifted = f.shifted;
-    ks.generic = f.generic;
-#endif
     return ks;
 }
 
@@ -216,20 +190,10 @@ int cached_cu_count()
 
 }  // namespace
 
-// force_path bits of dxtlt_set_tuning as this build honours them (include/dxtlt_gfx950.h, dxtlt_tuning_mask()).
-//   product:      2 = halo / shifted tiles even for aligned stream bases; 0x20 = the generic (switch per access) LDS scatter /
-//                 gather of the halo / shifted tiles even for natural shifts.  Both are test levers: every path they select is
-//                 a path some address pattern selects by itself, and the results are exact.
-//   experiments:  1 = element-granular kernel; 0x10 = leave out partial segments / the halo load (TIMING ONLY, WRONG OUTPUT; also
-//                 needs DXTLT_TIMING_EXPERIMENTS in the environment); 0x40 / 0x80 = store policies of the first-form shifted
-//                 tiles; 0x100 / 0x200 = XCD-contiguous tile order off / on; 0x400 = first form of the forward shifted tiles;
-//                 0x800 = plain nt stores in the halo tiles; 0x1000 = round-1 rule (tiles only for a 16-byte aligned AoS
-//                 pointer); 0x2000 = round-3 routing (heads and tails through the element kernel).
-#ifdef DXTLT_EXPERIMENTS
-constexpr int kForceMask = 0x3CFF;
-#else
+// force_path bits of dxtlt_set_tuning (include/dxtlt_gfx950.h, dxtlt_tuning_mask()): 2 = halo / shifted tiles even for aligned
+// stream bases; 0x20 = the generic (switch per access) LDS scatter / gather of the halo / shifted tiles even for natural shifts.
+// Both are test levers: every path they select is a path some address pattern selects by itself, and the results are exact.
 constexpr int kForceMask = 2 | 0x20;
-#endif
 int launch_force_mask() { return kForceMask; }
 
 // ---- planning: which launches a range takes (pure host arithmetic on addresses; dxtlt_debug_plan_transform exposes it to the
@@ -244,11 +208,11 @@ struct PlannedLaunch {
     Shifts sh;            // kinds 1 and 2
 };
 
-// One range of at most 2^31 blocks.  `aligned_threads`: lanes of the aligned tiles (default or tuning); `halo_threads_override`:
-// 0, or the experiments build's 512.  emit(const PlannedLaunch&) -> hipError_t; the first error ends the walk.
+// One range of at most 2^31 blocks.  `aligned_threads`: lanes of the aligned tiles (default or tuning).
+// emit(const PlannedLaunch&) -> hipError_t; the first error ends the walk.
 template <typename Emit>
 hipError_t plan_launches(Format fmt, bool inverse, bool sa, bool sc, const void* soa, const Range& r, int force_bits,
-                         int aligned_threads, int halo_threads_override, Emit&& emit)
+                         int aligned_threads, Emit&& emit)
 {
     // Which tiles take the range?  (the table at the top of this file)  The AoS side may sit at any byte address: 16-byte vector
     // loads / stores at unaligned addresses are exact on gfx950 under ROCm's default memory mode and cost little
@@ -286,8 +250,7 @@ hipError_t plan_launches(Format fmt, bool inverse, bool sa, bool sc, const void*
     const int edge_threads = inverse ? shift_tile_threads(fmt) : halo_tile_threads(fmt, sc);
     if (use_shift) {
         Shifts sh = shifts_of(0, !inverse);
-        const int threads = (!inverse && halo_threads_override != 0 && sh.natural) ? halo_threads_override : edge_threads;
-        const uint64_t T = (uint64_t)tile_blocks(fmt, threads);
+        const uint64_t T = (uint64_t)tile_blocks(fmt, edge_threads);
         const uint64_t num_tiles = r.num_blocks / T, rest = r.num_blocks - num_tiles * T;
         // Forward: halo tiles + edge tiles in ONE launch -- tile 0 writes the head of every stream itself, and one more workgroup
         // takes the blocks behind the last whole tile and the last d_s bytes of every stream.  Identity tile order, write-through
@@ -300,7 +263,7 @@ hipError_t plan_launches(Format fmt, bool inverse, bool sa, bool sc, const void*
                 tail = tail || sh.d[i] > 0;
         sh.full_tiles = (uint32_t)num_tiles;
         sh.range_blocks = r.num_blocks;
-        return emit(PlannedLaunch{inverse ? 2 : 1, threads, (uint32_t)(num_tiles + (tail ? 1 : 0)), 0, sh});
+        return emit(PlannedLaunch{inverse ? 2 : 1, edge_threads, (uint32_t)(num_tiles + (tail ? 1 : 0)), 0, sh});
     }
     const uint64_t T = (uint64_t)tile_blocks(fmt, aligned_threads);
     const uint64_t num_tiles = r.num_blocks / T;
@@ -359,13 +322,13 @@ int debug_plan_transform(Format fmt, bool inverse, const Settings& s, uint64_t s
         return -1;
     const Settings es = effective_settings(fmt, s);
     const bool sa = es.split_alpha, sc = es.split_colour;
-    const int force_bits = (tuning ? tuning->force_generic : 0) & kForceMask & (2 | 0x20);   // (the product's levers)
+    const int force_bits = (tuning ? tuning->force_generic : 0) & kForceMask;
     const void* soa = reinterpret_cast<const void*>(static_cast<uintptr_t>(inverse ? src_address : dst_address));
     int n = 0;
     for (uint64_t off = 0; off < r.num_blocks; off += kMaxBlocksPerLaunch) {
         const Range sub{r.total_blocks, r.first_block + off, std::min(kMaxBlocksPerLaunch, r.num_blocks - off)};
         const uint64_t sub_aos = off * (uint64_t)fmt_block(fmt);
-        const hipError_t e = plan_launches(fmt, inverse, sa, sc, soa, sub, force_bits, aligned_tile_threads(fmt, inverse, false, tuning), 0,
+        const hipError_t e = plan_launches(fmt, inverse, sa, sc, soa, sub, force_bits, aligned_tile_threads(fmt, inverse, false, tuning),
                                            [&](const PlannedLaunch& l) {
                                                if (n < cap) {
                                                    DebugPlannedLaunch& o = out[n];
@@ -440,92 +403,9 @@ hipError_t launch_transform(Format fmt, bool inverse, const Settings& s_arg, con
     const void* soa = inverse ? src : (const void*)dst;
     const int force_bits = (tuning ? tuning->force_generic : 0) & kForceMask;
     const int threads = aligned_tile_threads(fmt, inverse, normalizing, tuning);
-    int halo_threads_override = 0;
-    ShiftFn halo_alt = nullptr;
-
-#ifdef DXTLT_EXPERIMENTS
-    // ---- experiments build: 512-lane halo tiles and the routes of earlier rounds ------------------------------------------------
-    if (!inverse && threads == 512 && ks.halo512 != nullptr) {
-        halo_threads_override = 512;
-        halo_alt = ks.halo512;
-    }
-    const int remap_override = tuning ? tuning->xcd_remap : -1;
-    auto element_range = [&](uint64_t local_first, uint64_t count) -> hipError_t {
-        if (count == 0)
-            return hipSuccess;
-        const uint64_t grid = (count + kThreads - 1) / kThreads;   // count <= 2^31 blocks, one per thread
-        hipLaunchKernelGGL(ks.generic, dim3((unsigned)grid), dim3(kThreads), 0, stream, src8, dst8, r.total_blocks,
-                           r.first_block, local_first, count | ((uint64_t)norm_modes << 56));
-        return hipGetLastError();
-    };
-    {
-        const Streams S = make_streams(fmt, sa, sc);
-        bool any_shift = false;
-        for (int i = 0; i < S.n; ++i)
-            any_shift = any_shift || ((reinterpret_cast<uintptr_t>(soa) + (uint64_t)S.off[i] * r.total_blocks +
-                                       (uint64_t)S.width[i] * r.first_block) & 127) != 0;
-        const bool use_shift = any_shift || (force_bits & 3) == 2;
-        const void* aos = inverse ? (const void*)dst : src;
-        const bool aos_ok = (reinterpret_cast<uintptr_t>(aos) & 15) == 0 || !(force_bits & 0x1000);
-        if (!aos_ok || (force_bits & 3) == 1)
-            return element_range(0, r.num_blocks);
-        const bool first_form = use_shift && !inverse && (force_bits & 0x400);
-        const bool old_routing = (force_bits & 0x2000) != 0;
-        if (first_form || (old_routing && use_shift)) {
-            const int route_threads = first_form ? 256 : inverse ? shift_tile_threads(fmt) : halo_tile_threads(fmt, sc);   // (the first form: 256 lanes only)
-            const uint64_t T = (uint64_t)tile_blocks(fmt, route_threads);
-            const uint64_t tiles = r.num_blocks / T;
-            const bool halo = !inverse && !first_form;
-            Shifts sh{};
-            int halo_blocks = 0;
-            for (int i = 0; i < S.n; ++i) {
-                const uint64_t base = reinterpret_cast<uintptr_t>(soa) + (uint64_t)S.off[i] * r.total_blocks + (uint64_t)S.width[i] * r.first_block;
-                sh.d[i] = (int)(base & (uint64_t)(halo ? kHaloAlign - 1 : 15));
-                halo_blocks = std::max(halo_blocks, (sh.d[i] + S.width[i] - 1) / S.width[i]);
-            }
-            fill_gbase(sh, S, r.total_blocks, r.first_block);
-            sh.natural = (force_bits & 0x20) ? 0 : shifts_are_natural(S, sh.d);
-            sh.halo_vecs = (halo ? (halo_blocks + 16 / fmt_block(fmt) - 1) / (16 / fmt_block(fmt)) : 0) | (norm_modes << kNormModesShift);
-            sh.xcd_remap = remap_override >= 0 ? remap_override : halo ? 0 : 1;
-            sh.skip_partial = (force_bits & 0x10) ? 1 : 0;
-            sh.line_policy = !first_form ? ((force_bits & 0x800) ? 1 : 3) : (force_bits & 0x40) ? 0 : (force_bits & 0x80) ? 2 : 1;
-            sh.full_tiles = (uint32_t)tiles;
-            sh.range_blocks = tiles * T;
-            if (tiles > 0) {
-                hipLaunchKernelGGL(first_form || inverse ? ks.shifted : ks.halo[sh.natural ? 1 : 0], dim3((unsigned)tiles),
-                                   dim3(route_threads), 0, stream, src8, dst8, r.total_blocks, r.first_block, sh);
-                if (hipError_t e = hipGetLastError(); e != hipSuccess)
-                    return e;
-            }
-            uint64_t done = tiles * T;
-            if (halo && tiles > 0) {
-                // what the halo tiles' windows leave out: the head of every stream of the range (records of its first 64 blocks)
-                // and everything behind the last window
-                if (hipError_t e = element_range(0, kHaloBlocks); e != hipSuccess)
-                    return e;
-                done -= kHaloBlocks;
-            }
-            return element_range(done, r.num_blocks - done);
-        }
-        if (old_routing) {
-            const uint64_t T = (uint64_t)tile_blocks(fmt, threads);
-            const uint64_t tiles = r.num_blocks / T;
-            if (tiles > 0) {
-                hipLaunchKernelGGL(ks.tiled[threads_slot(threads)], dim3((unsigned)tiles), dim3(threads), 0, stream, src8, dst8,
-                                   r.total_blocks, r.first_block, (remap_override >= 0 ? remap_override : 0) | (norm_modes << kNormModesShift),
-                                   (int64_t)0, (int64_t)0);
-                if (hipError_t e = hipGetLastError(); e != hipSuccess)
-                    return e;
-            }
-            return element_range(tiles * T, r.num_blocks - tiles * T);
-        }
-    }
-    const int aligned_flags = (remap_override >= 0 ? remap_override : 0) | (norm_modes << kNormModesShift);
-#else
     const int aligned_flags = norm_modes << kNormModesShift;
-#endif
 
-    return plan_launches(fmt, inverse, sa, sc, soa, r, force_bits, threads, halo_threads_override, [&](const PlannedLaunch& l) {
+    return plan_launches(fmt, inverse, sa, sc, soa, r, force_bits, threads, [&](const PlannedLaunch& l) {
         if (l.kind == 0) {
             hipLaunchKernelGGL(ks.tiled[threads_slot(l.threads)], dim3(l.grid), dim3(l.threads), 0, stream, src8, dst8, r.total_blocks,
                                r.first_block, aligned_flags, (int64_t)0, (int64_t)0);
@@ -533,17 +413,11 @@ hipError_t launch_transform(Format fmt, bool inverse, const Settings& s_arg, con
         }
         Shifts sh = l.sh;
         sh.halo_vecs |= norm_modes << kNormModesShift;   // (0 in every launch but those of the BC2 / BC3 normalising kernel sets)
-#ifdef DXTLT_EXPERIMENTS
-        sh.xcd_remap = remap_override >= 0 ? remap_override : l.kind == 1 ? 0 : 1;
-        sh.skip_partial = (force_bits & 0x10) ? 1 : 0;
-        sh.line_policy = l.kind == 1 ? ((force_bits & 0x800) ? 1 : 3) : 1;
-#endif
         if (l.kind == 2) {   // the AoS side is the destination
             hipLaunchKernelGGL(ks.shifted, dim3(l.grid), dim3(l.threads), 0, stream, src8, dst8 + l.aos_offset, r.total_blocks,
                                r.first_block, sh);
         } else {
-            const ShiftFn k = (halo_alt != nullptr && l.threads == halo_threads_override) ? halo_alt : ks.halo[sh.natural ? 1 : 0];
-            hipLaunchKernelGGL(k, dim3(l.grid), dim3(l.threads), 0, stream, src8 + l.aos_offset, dst8, r.total_blocks, r.first_block, sh);
+            hipLaunchKernelGGL(ks.halo[sh.natural ? 1 : 0], dim3(l.grid), dim3(l.threads), 0, stream, src8 + l.aos_offset, dst8, r.total_blocks, r.first_block, sh);
         }
         return hipGetLastError();
     });
@@ -580,13 +454,6 @@ hipError_t launch_tiled_array(Format fmt, bool inverse, const Settings& s_arg, c
                        src_stride, dst_stride);
     return hipGetLastError();
 }
-
-#ifdef DXTLT_WG_TIMING
-extern "C" int dxtlt_debug_read_wg_marks_single(uint32_t* out, size_t count)   // experiment build: bcn_device.h, WG_MARK
-{
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wg_marks), count * 4);
-}
-#endif
 
 // Table upload by a kernel: the lanes read the pinned host table over PCIe and write the device twin.  A copy engine
 // transfer in front of the batch kernel costs the stream two queue hand-overs (20-90 us measured per call, more than a

@@ -11,18 +11,6 @@
 
 namespace dxtlt {
 
-// A/B switches read from the environment exist in the experiments side build only (-DDXTLT_EXPERIMENTS, bcn_device.h): in the
-// shipped library the variable is never looked at.
-inline const char* experiment_env(const char* name)
-{
-#ifdef DXTLT_EXPERIMENTS
-    return std::getenv(name);
-#else
-    (void)name;
-    return nullptr;
-#endif
-}
-
 // kBc4 / kBc5: this build's BC4 / BC5 layout (docs/BC45_FORMAT.md) -- a BC4 block is the alpha half of a BC3 block, a BC5 block
 // two of them (red, green)
 enum Format : int { kBc1 = 1, kBc2 = 2, kBc3 = 3, kBc4 = 4, kBc5 = 5 };
@@ -64,10 +52,9 @@ struct Range {
 struct LaunchTuning {
     int tile_threads;   // aligned tiles: 0 = per-format default; 64, 128, 256, 512
     int force_generic;  // force_path bits of dxtlt_set_tuning, see launch_transform (bcn_kernels.hip); 2 = halo / shifted tiles always
-    int xcd_remap;      // experiments build only: -1 = default, 0 = off, 1 = XCD-contiguous tile order
 };
 
-// the force_path bits this build of the kernels honours (2 | 0x20 in the shipped library)
+// the force_path bits the kernels honour (2 | 0x20)
 int launch_force_mask();
 
 // What launch_transform would enqueue for a range, without enqueueing anything (addresses are numbers: nothing is dereferenced,

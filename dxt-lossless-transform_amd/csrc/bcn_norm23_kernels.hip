@@ -3,7 +3,7 @@
 //
 // A lane's 16-byte vector is one block; normalize_block_bc23 (bc23_normalize.h) rewrites it in registers between the load and the
 // LDS scatter, so the kernels move the plain transform's 2 * len bytes.  The modes are a wave-uniform kernel argument
-// (alpha_mode << 2 | color_mode, in spare bits of fwd_tiled's `xcd_remap` and of Shifts::halo_vecs), not template parameters: BC3
+// (alpha_mode << 2 | color_mode, in spare bits of fwd_tiled's `flags` and of Shifts::halo_vecs), not template parameters: BC3
 // has 11 non-trivial mode pairs over 16 settings combinations.  One kernel set per (format, VARIANT, SA, SC): 8 for BC2, 16 for BC3,
 // each with the members bc1_norm_kernels (bcn_kernels.hip) has.  launch_transform plans and launches them as it does the plain ones.
 //
@@ -21,10 +21,6 @@ FusedNormKernels kernels()
     k.tiled = fwd_tiled<FMT, VARIANT, SA, SC, default_tile_threads(FMT, false), kNormFromArgument>;
     k.halo[0] = fwd_tiled_halo<FMT, VARIANT, SA, SC, kNormFromArgument, false, halo_tile_threads(FMT, SC)>;
     k.halo[1] = fwd_tiled_halo<FMT, VARIANT, SA, SC, kNormFromArgument, true, halo_tile_threads(FMT, SC)>;
-#ifdef DXTLT_EXPERIMENTS
-    k.shifted = fwd_tiled_shift<FMT, VARIANT, SA, SC, kNormFromArgument>;
-    k.generic = generic_kernel<FMT, VARIANT, SA, SC, false, kNormFromArgument>;
-#endif
     return k;
 }
 

@@ -27,7 +27,6 @@ thread_local std::string g_last_error;
 thread_local std::vector<DxtltShardStat> g_shard_stats;   // of this thread's last dxtlt_transform_sharded call
 std::atomic<int> g_tile_threads{0};
 std::atomic<int> g_force_generic{0};
-std::atomic<int> g_xcd_remap{-1};
 
 }  // namespace
 
@@ -56,7 +55,6 @@ dxtlt::LaunchTuning current_tuning()
     dxtlt::LaunchTuning t;
     t.tile_threads = g_tile_threads.load(std::memory_order_relaxed);
     t.force_generic = g_force_generic.load(std::memory_order_relaxed);
-    t.xcd_remap = g_xcd_remap.load(std::memory_order_relaxed);
     return t;
 }
 
@@ -366,19 +364,10 @@ int32_t dxtlt_debug_plan_transform(int32_t format, int32_t inverse, int32_t vari
 void dxtlt_set_tuning(int32_t tile_threads, int32_t force_path)
 {
     g_tile_threads.store(tile_threads);
-    // Only the bits this build knows (bcn_kernels.hip, kForceMask): the shipped library honours 2 and 0x20 -- test levers that
-    // select paths some address pattern selects by itself, results exact -- and nothing else; in particular it contains no switch
-    // that changes results.  The experiments side build (-DDXTLT_EXPERIMENTS) adds the rest; its 0x10, a timing experiment with
-    // WRONG output, additionally needs DXTLT_TIMING_EXPERIMENTS in the environment.
-    int32_t allowed = dxtlt::launch_force_mask();
-#ifdef DXTLT_EXPERIMENTS
-    static const bool timing_experiments = std::getenv("DXTLT_TIMING_EXPERIMENTS") != nullptr;
-    if (!timing_experiments)
-        allowed &= ~0x10;
-#endif
-    const int32_t bits = force_path & allowed;
-    g_force_generic.store(bits);
-    g_xcd_remap.store((bits & 0x100) ? 0 : (bits & 0x200) ? 1 : -1);   // (experiments build: XCD-contiguous tile order off / on)
+    // Only the bits the kernels know (bcn_kernels.hip, kForceMask): 2 and 0x20 -- test levers that select paths some address
+    // pattern selects by itself, results exact -- and nothing else; in particular the library contains no switch that changes
+    // results.
+    g_force_generic.store(force_path & dxtlt::launch_force_mask());
 }
 
 const char* dxtlt_version(void) { return "dxtlt-gfx950 0.2.0"; }

@@ -107,11 +107,6 @@ __device__ __forceinline__ void batch_image_tile(const ImageBatchEntry* entries_
         sh.d[i] = (int)((en.shifts[i >> 2] >> (8 * (i & 3))) & 127u);
         sh.gbase[i] = en.gbase[i];
     }
-#ifdef DXTLT_EXPERIMENTS
-    sh.xcd_remap = 0;
-    sh.line_policy = 1;
-    sh.skip_partial = 0;
-#endif
     sh.natural = 1;   // plan_image_batch_entry hands ranges with other shifts back to the host
     sh.halo_vecs = 0;
     sh.full_tiles = en.full_tiles;

@@ -80,8 +80,7 @@ inv_tiled_shift_image(const uint8_t* __restrict__ soa_arg, PixelSink sink, uint6
     const Shifts sh = shifts_fetched_at_once(sh_arg);
     const uint8_t* __restrict__ soa = fetched_now(soa_arg);
     const bool whole = wg < sh.full_tiles;
-    const uint64_t tile = !whole ? (uint64_t)sh.full_tiles
-                          : shifts_xcd_contiguous(sh, true) ? xcd_contiguous_tile(wg, sh.full_tiles) : (uint64_t)wg;
+    const uint64_t tile = whole ? xcd_contiguous_tile(wg, sh.full_tiles) : (uint64_t)sh.full_tiles;
     if (!whole)
         inv_shift_edge_tile<FMT, VARIANT, SA, SC, THREADS, PixelSink>(soa, nullptr, total_blocks, sh, tile, lds, sink);
     else
@@ -143,8 +142,7 @@ inv_tiled_shift_channel_image(const uint8_t* __restrict__ soa_arg, ChannelSink s
     const Shifts sh = shifts_fetched_at_once(sh_arg);
     const uint8_t* __restrict__ soa = fetched_now(soa_arg);
     const bool whole = wg < sh.full_tiles;
-    const uint64_t tile = !whole ? (uint64_t)sh.full_tiles
-                          : shifts_xcd_contiguous(sh, true) ? xcd_contiguous_tile(wg, sh.full_tiles) : (uint64_t)wg;
+    const uint64_t tile = whole ? xcd_contiguous_tile(wg, sh.full_tiles) : (uint64_t)sh.full_tiles;
     if (!whole)
         inv_shift_edge_tile<FMT, kNone, SA, false, THREADS, ChannelSink>(soa, nullptr, total_blocks, sh, tile, lds, sink);
     else

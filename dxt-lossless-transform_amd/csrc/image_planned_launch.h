@@ -52,9 +52,6 @@ hipError_t launch_planned_image(Format fmt, const Settings& s, const ImageKernel
                 sh.halo_vecs = l.halo_vecs;
                 sh.full_tiles = l.full_tiles;
                 sh.range_blocks = l.range_blocks;
-#ifdef DXTLT_EXPERIMENTS
-                sh.xcd_remap = 1;
-#endif
                 hipLaunchKernelGGL(ks.shifted, dim3(l.workgroups), dim3(l.threads), 0, stream, soa8, sink, total_blocks, sub.first_block, sh);
             }
             if (hipError_t e = hipGetLastError(); e != hipSuccess)

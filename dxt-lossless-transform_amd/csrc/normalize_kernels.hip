@@ -344,7 +344,7 @@ hipError_t launch_normalize_bc1_all_modes(const void* in, void* const out[3], ui
     const Bc1Lanes l(all_aligned16(in, out[0], out[1], out[2]), num_blocks, 2);
     // 16 bytes read and 48 written per lane: six workgroups per CU instead of eight (1 GiB of blocks: 782 -> 696 us;
     // five 731, four 688, three 1011; profiles/r02_o_wgs_per_cu.txt)
-    return launch_lanes(normalize_all_modes_kernel, l.vectors + l.singles, lds_pad_for_wgs_per_cu(wgs_per_cu_or(6), kNormThreads, 0),
+    return launch_lanes(normalize_all_modes_kernel, l.vectors + l.singles, lds_pad_for_wgs_per_cu(6, kNormThreads, 0),
                         stream, static_cast<const uint8_t*>(in), static_cast<uint8_t*>(out[0]), static_cast<uint8_t*>(out[1]),
                         static_cast<uint8_t*>(out[2]), l.vectors, l.singles, d_any);
 }
@@ -389,7 +389,7 @@ hipError_t launch_normalize_bc23_all_modes(int fmt, const void* in, void* const*
     // BC2, 1 GiB of blocks: 764 us at eight, 658 at six, 681 / 672 at five / four, 908 at three; BC3, 256 MiB: 700 at eight,
     // 664 / 680 / 616 at six / five / four, 584 at three (profiles/r02_o_wgs_per_cu.txt)
     return launch_lanes(fmt == 2 ? normalize23_all_modes_kernel<2> : normalize23_all_modes_kernel<3>, num_blocks,
-                        lds_pad_for_wgs_per_cu(wgs_per_cu_or(fmt == 2 ? 6 : 3), kNormThreads, 0), stream,
+                        lds_pad_for_wgs_per_cu(fmt == 2 ? 6 : 3, kNormThreads, 0), stream,
                         static_cast<const uint8_t*>(in), o, num_blocks, vec);
 }
 

@@ -13,7 +13,7 @@
 // (cdna_hip_programming.md, inline-asm rules: "an asm ..._store_dwordx3/x4 ends with s_nop 1 inside the string").
 //
 // Use it only for 128-byte lines that one wave instruction writes completely; a line that another wave or workgroup
-// completes must stay in L2 until then (plain or `nt` store), see fwd_shift_tile in bcn_kernels.hip.
+// completes must stay in L2 until then (plain or `nt` store), see the edge tiles in bcn_device.h.
 #pragma once
 #include <hip/hip_runtime.h>
 

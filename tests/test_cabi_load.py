@@ -305,8 +305,8 @@ def test_rust_bodies_call_the_sys_crate_with_the_declared_argument_lists():
 
 def test_shipped_library_contains_no_experiment_code(pkg):
     """The experiment switches of rounds 1-4 (element-granular kernel, first-form shifted tiles, a wrong-output timing switch, the
-    per-workgroup timing arrays) are compiled only with -DDXTLT_EXPERIMENTS / -DDXTLT_WG_TIMING, into side builds under
-    build/side-*/ that never replace the shipped library (_build.py).  Checked on the shipped file itself: the tuning mask, the
+    per-workgroup timing arrays) were removed from the sources, and a build with extra flags (an A/B of two revisions) goes to
+    build/side-*/ and never replaces the shipped library (_build.py).  Checked on the shipped file itself: the tuning mask, the
     kernel names in its device code object, the debug exports."""
     if os.environ.get("DXTLT_LIB_PATH"):
         pytest.skip("another build of the library is under test")

@@ -178,8 +178,8 @@ def test_shifted_tiles(pkg, oracle, dev, fmt):
 
 @pytest.mark.parametrize("fmt", FORMATS)
 def test_forward_shifted_tiles_both_forms(pkg, oracle, dev, fmt):
-    """The forward halo tiles (whole 16-byte segments only) -- and, in the experiments side build, the first form with typed
-    partial segments (switch 0x400) -- must equal the oracle on odd counts, on ranges that start at odd blocks and on an SoA
+    """The forward halo tiles (whole 16-byte segments only) -- and, in a library whose mask has it, the removed first form with
+    typed partial segments (switch 0x400) -- must equal the oracle on odd counts, on ranges that start at odd blocks and on an SoA
     pointer that is itself misaligned."""
     t = TILE[fmt]
     B = BLOCK[fmt]
@@ -212,7 +212,7 @@ def test_forward_shifted_tiles_both_forms(pkg, oracle, dev, fmt):
 def test_shipped_library_has_no_experiment_switch(pkg, oracle, dev):
     """The shipped library honours two force_path bits (2: halo / shifted tiles always; 0x20: generic LDS accesses), both exact.
     Everything else -- the element kernel (1), the wrong-output timing switch (0x10), store policies, tile orders, old routings --
-    lives in the -DDXTLT_EXPERIMENTS side build: here those bits must be absent from the mask and inert."""
+    was removed with the experiments: those bits must be absent from the mask and inert."""
     import os
     if os.environ.get("DXTLT_LIB_PATH"):
         pytest.skip("another build of the library is under test")

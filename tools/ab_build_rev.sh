@@ -2,7 +2,7 @@
 # Same-box A/B of whole library versions: builds the library as of git revision REV (all sources) into ab/libdxtlt_NAME.so,
 # to be run beside the current one through DXTLT_LIB_PATH on ONE gpurun box (box-to-box spread is +-0.02 of peak).
 #     tools/ab_build_rev.sh HEAD~3 r3
-#     DXTLT_EXTRA_HIPCC_FLAGS=-DDXTLT_EXPERIMENTS tools/ab_build_rev.sh WORKTREE exp     (the experiments side build)
+#     DXTLT_EXTRA_HIPCC_FLAGS=-DNAME=VALUE tools/ab_build_rev.sh WORKTREE exp     (a compiler-flag experiment: a side build)
 #     gpurun -- 'for lib in ab/libdxtlt_r3.so dxt-lossless-transform_amd/libdxtlt_gfx950.so; do
 #                  DXTLT_LIB_PATH=$GRAFT_REPO_ROOT/$lib python tools/batch_shape_probe.py; done'
 # ab/ is git-ignored; remove it afterwards (it travels with every gpurun push).

@@ -1,11 +1,9 @@
 #!/usr/bin/env python3
-"""transform_bcN_auto, device side: the fused candidate kernel (one read of the input -> every endpoint section) against
-one full transform per candidate (DXTLT_AUTO_FUSED=0).  256 MiB per format, a constant-time estimator in C (the callback
+"""transform_bcN_auto, device side: the fused candidate kernel (one read of the input -> every endpoint section).  256 MiB per format, a constant-time estimator in C (the callback
 returns the length), so what is left is upload + kernels + the per-candidate section downloads.  Run under
 `rocprofv3 --kernel-trace --stats` to see the kernel list; prints wall time per call.
 
-    python tools/auto_bench.py            # fused (default)
-    DXTLT_AUTO_FUSED=0 python tools/auto_bench.py
+    python tools/auto_bench.py
 """
 import ctypes as C
 import json
@@ -22,7 +20,7 @@ import dxt_lossless_transform_amd as pkg  # noqa: E402
 from oracle import oracle_c  # noqa: E402
 
 lib = cabi.bind(C.CDLL(pkg._lib.lib_path()))
-out = {"fused": os.environ.get("DXTLT_AUTO_FUSED", "1") != "0"}
+out = {}
 nbytes = 256 << 20
 x = oracle_c.fill_splitmix64(nbytes, 0xA070)
 y = np.zeros_like(x)

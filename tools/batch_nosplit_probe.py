@@ -1,7 +1,7 @@
 """BC1 WITHOUT the colour split through the BATCH kernel, forward (and inverse beside it): the corpus shape (2130 mip-chained
 textures, every block count odd: halo + edge tiles) and regular arrays of equal buffers (aligned tiles through batch_kernel when the
 array route is off, odd counts otherwise).  Run once per library (DXTLT_LIB_PATH) on ONE box: the shipped one plans 128-lane tiles
-for this launch (batch_tile_threads), a side build with -DDXTLT_BATCH_BC1_NOSPLIT_FWD_THREADS=256 the round-5 shape.  Every case is
+for this launch (batch_tile_threads), a build with kBatchBc1NosplitFwdThreads = 256 (csrc/bcn_device.h) the round-5 shape.  Every case is
 checked: exact round trip, and forward bytes against the oracle on three textures.
     python tools/batch_nosplit_probe.py [--settings 1,0 | 0,0 | 1,1] [--reps 10]"""
 import argparse

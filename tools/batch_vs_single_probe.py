@@ -1,6 +1,6 @@
 """One big odd buffer (block count = 23 mod 64, like a square mip chain), forward / inverse fractions of the HBM peak:
-single-buffer call; batch call with that ONE buffer (regular-array path, no table); the same with DXTLT_BATCH_NO_STRIDED=1
-semantics emulated by two unequal buffers (table lookup path).  PROBE_FMT=bc3 PROBE_GIB=2"""
+single-buffer call; batch call with that ONE buffer (regular-array path, no table); two unequal buffers (table
+lookup path); three equal buffers at irregular offsets (one table load).  PROBE_FMT=bc3 PROBE_GIB=2"""
 import os, sys, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

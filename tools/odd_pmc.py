@@ -10,7 +10,7 @@ import torch  # noqa: E402
 import dxt_lossless_transform_amd as pkg  # noqa: E402
 
 extra = int(sys.argv[1]) if len(sys.argv) > 1 else 1
-force = int(sys.argv[2], 0) if len(sys.argv) > 2 else 0      # experiment switches of dxtlt_set_tuning (0x100: identity tile order)
+force = int(sys.argv[2], 0) if len(sys.argv) > 2 else 0      # force_path bits of dxtlt_set_tuning (2, 0x20)
 n = (1 << 26) + extra
 x = torch.empty(16 * n, dtype=torch.uint8, device="cuda:0")
 pkg.fill_splitmix64(x, 3)
