@@ -858,4 +858,23 @@ int32_t dxtlt_debug_auto_candidates_device(int32_t format, bool use_all_decorrel
     return kOk;
 }
 
+int32_t dxtlt_debug_auto_candidates_into_device(int32_t format, bool use_all_decorrelation_modes, const void* d_input, size_t len,
+                                                void* d_arena, uint64_t arena_bytes, void* hip_stream)
+{
+    using namespace dxtlt_host;
+    if (format < 1 || format > 3 || len % (format == 1 ? 8 : 16) != 0)
+        return fail(kInvalidArgument, "auto candidates: format 1..3, a whole number of blocks");
+    if (len == 0)
+        return kOk;
+    if (d_input == nullptr || d_arena == nullptr || ((reinterpret_cast<uintptr_t>(d_input) | reinterpret_cast<uintptr_t>(d_arena)) & 15) != 0)
+        return fail(kInvalidArgument, "auto candidates: input and arena on a 16-byte boundary");
+    const uint64_t blocks = len / (format == 1 ? 8 : 16);
+    if (arena_bytes < dxtlt::auto_sections((dxtlt::Format)format, use_all_decorrelation_modes, blocks).bytes)
+        return fail(kInvalidArgument, "auto candidates: an arena smaller than auto_sections' bytes");
+    HIP_TRY(dxtlt::launch_auto_candidates((dxtlt::Format)format, use_all_decorrelation_modes, d_input, d_arena, blocks,
+                                          static_cast<hipStream_t>(hip_stream)),
+            "candidate kernel launch");
+    return kOk;
+}
+
 }  // extern "C"

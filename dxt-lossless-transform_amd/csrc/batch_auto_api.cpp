@@ -30,6 +30,22 @@ thread_local BatchAutoDebug t_debug(16);      // the dxtlt_debug_batch_auto_* ho
 // this thread's table staging and counters (batch_auto_common.h), shared with the batched pixel auto call
 thread_local BatchAutoBuffers g_buffers;
 
+// the candidate launches of one chunk, one per (format, use_all) present, from the call's table at `dev` (fill_tables) into `arena`
+hipError_t launch_chunk_candidates(const ba::PlannedChunk& ch, const uint8_t* dev, uint8_t* arena, hipStream_t st, uint64_t& launched)
+{
+    for (int g = 0; g < ba::kGroups; ++g) {
+        if (ch.entries[g] == 0)
+            continue;
+        if (hipError_t e = dxtlt::launch_batch_auto_candidates((dxtlt::Format)(g / 2 + 1), (g & 1) != 0,
+                                                               reinterpret_cast<const dxtlt::BatchAutoEntry*>(dev + ch.at[g]),
+                                                               ch.entries[g], ch.wgs[g], arena, st);
+            e != hipSuccess)
+            return e;
+        launched++;
+    }
+    return hipSuccess;
+}
+
 }  // namespace
 
 void dxtlt_host::release_batch_auto_thread_buffers() { g_buffers.release(); }
@@ -78,20 +94,7 @@ extern "C" int32_t dxtlt_transform_batch_auto_device(DxtltBatchAutoItem* items, 
     PhaseEvents phases;
     if (t_debug.time_phases && !phases.begin(plan.chunks.size(), 0))
         return fail(kDevice, "batch auto: hipEventCreate", hipErrorOutOfMemory);
-    auto candidates = [&](size_t c, uint64_t& launched) {
-        const ba::PlannedChunk& ch = plan.chunks[c];
-        for (int g = 0; g < ba::kGroups; ++g) {
-            if (ch.entries[g] == 0)
-                continue;
-            if (hipError_t e = dxtlt::launch_batch_auto_candidates((dxtlt::Format)(g / 2 + 1), (g & 1) != 0,
-                                                                   reinterpret_cast<const dxtlt::BatchAutoEntry*>(dev + ch.at[g]),
-                                                                   ch.entries[g], ch.wgs[g], arena, st);
-                e != hipSuccess)
-                return e;
-            launched++;
-        }
-        return hipSuccess;
-    };
+    auto candidates = [&](size_t c, uint64_t& launched) { return launch_chunk_candidates(plan.chunks[c], dev, arena, st, launched); };
     auto estimator = [&](size_t c, uint64_t& launched) {
         const ba::PlannedChunk& ch = plan.chunks[c];
         if (ch.estimator_entries == 0)
@@ -163,6 +166,40 @@ extern "C" int32_t dxtlt_debug_plan_batch_auto(const DxtltBatchAutoItem* items, 
     }
     if (out_chunks)
         *out_chunks = plan.chunks.size();
+    return kOk;
+}
+
+extern "C" int32_t dxtlt_debug_batch_auto_candidates_device(const DxtltBatchAutoItem* items, size_t count, size_t chunk, void* d_arena,
+                                                            uint64_t arena_bytes, void* hip_stream)
+{
+    ba::Plan plan;
+    if (Defect d = ba::plan_call(items, count, batch_auto_arena_cap(), plan); d.code != kOk)
+        return fail(d.code, d.what);
+    if (chunk >= plan.chunks.size())
+        return fail(kInvalidArgument, "batch auto candidates: no such chunk");
+    const ba::PlannedChunk& ch = plan.chunks[chunk];
+    if (d_arena == nullptr || (reinterpret_cast<uintptr_t>(d_arena) & 15) != 0 || arena_bytes < ch.arena_bytes)
+        return fail(kInvalidArgument, "batch auto candidates: an arena off a 16-byte boundary or smaller than the chunk's arena_bytes");
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    if (int32_t rc = auto_call_device_check(st))
+        return rc;
+    if (ch.candidate_launches() == 0)
+        return kOk;
+    HIP_TRY(g_buffers.reserve(plan.table_bytes, 0), "batch auto candidates: tables");
+    ba::fill_tables(plan, items, static_cast<uint8_t*>(d_arena), static_cast<uint8_t*>(g_buffers.table_host));
+    // every exit below drains the stream: the tables belong to this thread's next call
+    hipError_t e = dxtlt::launch_table_upload(g_buffers.table_mapped, g_buffers.table_dev, (plan.table_bytes + 15) & ~size_t(15), st);
+    const char* step = "batch auto candidates: table upload";
+    if (e == hipSuccess) {
+        uint64_t launched = 0;
+        e = launch_chunk_candidates(ch, static_cast<const uint8_t*>(g_buffers.table_dev), static_cast<uint8_t*>(d_arena), st, launched);
+        step = "batch auto candidates: candidate kernel launch";
+    }
+    const hipError_t waited = hipStreamSynchronize(st);
+    if (e != hipSuccess)
+        return fail(kDevice, step, e);
+    if (waited != hipSuccess)
+        return fail(kDevice, "stream synchronize", waited);
     return kOk;
 }
 

@@ -248,16 +248,25 @@ def transform_batch_auto(items):
     items.  Returns the list of chosen settings objects, one per item; the transforms are enqueued, not waited for."""
     import torch
 
-    from . import _FMT_ID, BLOCK_BYTES, InvalidLength, OutputBufferTooSmall, _Buf
-
     if not items:
         return []
-    arr = (BatchAutoItem * len(items))()
+    arr, device, _keep = _batch_auto_items("transform_batch_auto", items)
+    with torch.cuda.device(device):
+        _check(_l().dxtlt_transform_batch_auto_device(arr, len(arr), torch.cuda.current_stream().cuda_stream))
+    return [_settings_of(fmt, a.decorrelation_mode, a.split_alpha_endpoints, a.split_colour_endpoints)
+            for (fmt, _s, _d, _u), a in zip(items, arr)]
+
+
+def _batch_auto_items(who: str, items):
+    """(the DxtltBatchAutoItem array, the device, the buffers kept alive) of (fmt, input, output, use_all) items"""
+    from . import _FMT_ID, BLOCK_BYTES, InvalidLength, OutputBufferTooSmall, _Buf
+
+    arr = (BatchAutoItem * max(1, len(items)))()
     device, keep = None, []
     for k, (fmt, src, dst, use_all) in enumerate(items):
         s, d = _Buf(src, False), _Buf(dst, True)
         if s.device is None or d.device is None:
-            raise TypeError("transform_batch_auto takes device tensors")
+            raise TypeError(f"{who} takes device tensors")
         device = s.device if device is None else device
         if s.device != device or d.device != device:
             raise ValueError("all tensors of a batch must live on one device")
@@ -268,10 +277,57 @@ def transform_batch_auto(items):
         arr[k].d_input, arr[k].d_output, arr[k].len = s.ptr, d.ptr, s.nbytes
         arr[k].format, arr[k].use_all_decorrelation_modes = _FMT_ID[fmt], int(bool(use_all))
         keep.append((s, d))
-    with torch.cuda.device(device):
-        _check(_l().dxtlt_transform_batch_auto_device(arr, len(arr), torch.cuda.current_stream().cuda_stream))
-    return [_settings_of(fmt, a.decorrelation_mode, a.split_alpha_endpoints, a.split_colour_endpoints)
-            for (fmt, _s, _d, _u), a in zip(items, arr)]
+    return arr, device, keep
+
+
+def auto_sections_bytes(fmt: str, nbytes: int, use_all_decorrelation_modes: bool = False) -> int:
+    """Bytes of the candidate sections of an input of `nbytes`: the single call's arena and a batch item's slice."""
+    from . import BLOCK_BYTES
+
+    per_block = {"bc1": 16, "bc2": 16, "bc3": 20, "bc4": 4, "bc5": 8}[fmt]
+    if use_all_decorrelation_modes and fmt in ("bc1", "bc2", "bc3"):
+        per_block += 16
+    return nbytes // BLOCK_BYTES[fmt] * per_block
+
+
+def debug_auto_candidates_into(fmt: str, input, arena, use_all_decorrelation_modes: bool = False) -> None:
+    """Test hook (dxtlt_debug_auto_candidates_into_device): the fused candidate kernel of transform_auto, fmt in bc1..bc3, from the
+    CUDA uint8 tensor `input` into the caller's `arena` of auto_sections_bytes(...) or more, both on a 16-byte boundary.  Enqueued
+    on torch's current stream, not waited for."""
+    import torch
+
+    from . import _FMT_ID, OutputBufferTooSmall, _Buf
+
+    src, dst = _Buf(input, False), _Buf(arena, True)
+    if src.device is None or dst.device is None:
+        raise TypeError("debug_auto_candidates_into takes device tensors")
+    need = auto_sections_bytes(fmt, src.nbytes, use_all_decorrelation_modes)
+    if dst.nbytes < need:
+        raise OutputBufferTooSmall(need, dst.nbytes)
+    f = _l().dxtlt_debug_auto_candidates_into_device
+    f.argtypes, f.restype = [C.c_int32, C.c_bool, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint64, C.c_void_p], C.c_int32
+    with torch.cuda.device(src.device):
+        _check(f(_FMT_ID[fmt], bool(use_all_decorrelation_modes), src.ptr, src.nbytes, dst.ptr, dst.nbytes,
+                 torch.cuda.current_stream().cuda_stream))
+
+
+def debug_batch_candidates(items, chunk: int, arena) -> None:
+    """Test hook (dxtlt_debug_batch_auto_candidates_device): the candidate launches of chunk `chunk` of transform_batch_auto over
+    `items` -- (fmt, input tensor, output tensor, use_all), as there; no output is written -- into the caller's CUDA uint8 tensor
+    `arena`: item k's sections at the arena_offset dxtlt_debug_plan_batch_auto reports for it.  Waits for torch's current stream."""
+    import torch
+
+    from . import _Buf
+
+    arr, _device, _keep = _batch_auto_items("debug_batch_candidates", items)
+    a = _Buf(arena, True)
+    if a.device is None:
+        raise TypeError("debug_batch_candidates takes a device tensor as its arena")
+    f = _l().dxtlt_debug_batch_auto_candidates_device
+    f.argtypes = [C.POINTER(BatchAutoItem), C.c_size_t, C.c_size_t, C.c_void_p, C.c_uint64, C.c_void_p]
+    f.restype = C.c_int32
+    with torch.cuda.device(a.device):
+        _check(f(arr, len(items), int(chunk), a.ptr, a.nbytes, torch.cuda.current_stream().cuda_stream))
 
 
 def last_batch_auto() -> tuple[int, int, int, int]:

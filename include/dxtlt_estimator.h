@@ -219,6 +219,28 @@ int32_t dxtlt_debug_estimate_sizes_shape(const DxtltEstimateSection *sections, s
 int32_t dxtlt_debug_auto_candidates_device(int32_t format, bool use_all_decorrelation_modes, const void *d_input, size_t len,
                                            void *hip_stream);
 
+/* Test hook: the same launch or launches -- launch_auto_candidates of the fused route: auto_candidates_kernel<format, fast | all>
+ * over the whole 16-byte vectors and, for an odd BC1 block count, auto_candidates_bc1_last_block -- into memory of the caller's:
+ * every section of format 1..3, laid out as the batched call's note on sections says (BC3's alpha pairs and alpha split, then per
+ * variant colour pairs and colour split), end to end from d_arena; 16 / 32 bytes per block for BC1 and BC2 (fast / all modes),
+ * 20 / 36 for BC3, and no other byte.  Only enqueues on `hip_stream`.  DXTLT_E_INVALID_ARGUMENT with nothing enqueued: another
+ * format, a len that is not a multiple of the block size, d_input or d_arena off a 16-byte boundary (the kernel's own
+ * requirement) or NULL with len != 0, arena_bytes below the sections' bytes.  len == 0: DXTLT_OK, nothing enqueued. */
+int32_t dxtlt_debug_auto_candidates_into_device(int32_t format, bool use_all_decorrelation_modes, const void *d_input, size_t len,
+                                                void *d_arena, uint64_t arena_bytes, void *hip_stream);
+
+/* Test hook: the candidate launches of ONE chunk of dxtlt_transform_batch_auto_device over `items`, into memory of the caller's.
+ * Plans as the call does, at the arena cap in force on the thread (dxtlt_debug_batch_auto_arena_cap), fills the call's tables for
+ * an arena whose first byte is d_arena, uploads them, runs chunk `chunk`'s candidate launches -- one per (format,
+ * use_all_decorrelation_modes) present, through the function the call runs them through -- and waits for `hip_stream`.  Item k of
+ * the chunk then has its slice at d_arena + arena_offset (dxtlt_debug_plan_batch_auto; offsets restart in every chunk), its sections
+ * where that hook lists them; no other byte of the arena, no d_output and no result field is written and no estimator runs.
+ * With nothing enqueued: whatever the call refuses, with the call's status; DXTLT_E_INVALID_ARGUMENT for a chunk the plan does not
+ * have (count == 0 has none), a NULL d_arena or one off a 16-byte boundary, arena_bytes below that chunk's arena_bytes, and a
+ * capturing stream. */
+int32_t dxtlt_debug_batch_auto_candidates_device(const DxtltBatchAutoItem *items, size_t count, size_t chunk, void *d_arena,
+                                                 uint64_t arena_bytes, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
