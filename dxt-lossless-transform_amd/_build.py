@@ -25,7 +25,8 @@ SOURCES = ["bcn_kernels.hip", "bcn_norm23_kernels.hip", "batch_kernels.hip", "dx
            "bc6h_image_kernels.hip", "bc6h_image_api.cpp",
            "bc6h_image_batch_kernels.hip", "bc6h_image_batch_api.cpp",
            "entropy_kernels.hip", "pixel_auto_kernels.hip", "pixel_auto_api.cpp",
-           "pixel_batch_kernels.hip", "pixel_batch_api.cpp", "pixel_batch_auto_api.cpp"]
+           "pixel_batch_kernels.hip", "pixel_batch_api.cpp", "pixel_batch_auto_api.cpp",
+           "auto_normalize_kernels.hip", "auto_normalize_api.cpp"]
 BASE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wextra", "-Wno-unused-command-line-argument"]
 
 

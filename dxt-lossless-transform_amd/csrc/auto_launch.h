@@ -45,6 +45,36 @@ inline AutoSections auto_sections(Format fmt, bool all_variants, uint64_t blocks
 hipError_t launch_auto_candidates(Format fmt, bool all_variants, const void* d_in, void* d_arena, uint64_t blocks,
                                   hipStream_t stream);
 
+// ---- the candidate kernel of transform_bcN_auto_with_normalization, BC1 and BC2 (auto_normalize_kernels.hip) -------------------
+// Three copies of the colour part of auto_sections, one per colour normalisation the candidates are estimated on:
+//     for norm in (None*, Color0Only, ReplicateColor):
+//         for variant in (None, Variant1[, Variant2, Variant3]):  [colour pairs 4N][colour split 4N]
+// None*: BC1 with its fully transparent blocks rewritten to 0xFF (kNormTransparentOnly), BC2 the input's own colours.  12 or 24
+// sections end to end, 48 or 96 bytes per block; section (norm, variant, split) has index norm * (count / 3) + 2 * variant + split.
+struct AutoNormalizeSections {
+    int count;   // 12 or 24
+    uint64_t bytes;
+    uint64_t off[24], len[24];
+};
+inline AutoNormalizeSections auto_normalize_sections(bool all_variants, uint64_t blocks)
+{
+    AutoNormalizeSections s{};
+    s.count = all_variants ? 24 : 12;
+    for (int k = 0; k < s.count; ++k) {
+        s.off[k] = s.bytes;
+        s.len[k] = 4 * blocks;
+        s.bytes += 4 * blocks;
+    }
+    return s;
+}
+// One read of d_in (the AoS blocks of BC1 or BC2, 16-byte aligned) -> every section, at d_arena (16-byte aligned).  Enqueues on
+// `stream`; *launches (optional) receives the number of kernels enqueued: BC1's odd last block is a launch of its own.
+hipError_t launch_auto_normalize_candidates(Format fmt, bool all_variants, const void* d_in, void* d_arena, uint64_t blocks,
+                                            hipStream_t stream, int* launches);
+// Read-only: *d_any (a device uint32 the caller has zeroed) = 1 when the colour half of any BC2 block is a normalisable solid
+// (solid_colour_4c); the twin of launch_bc1_any_normalizable.  Any alignment of `in`.
+hipError_t launch_bc2_any_normalizable(const void* in, uint64_t num_blocks, uint32_t* d_any, hipStream_t stream);
+
 // ---- the batched candidate kernel of dxtlt_transform_batch_auto_device (batch_auto_kernels.hip) -------------------------------
 // One entry per non-empty buffer of a launch, in workgroup order: entry e owns workgroups [first_wg, next entry's first_wg).
 struct BatchAutoEntry {

@@ -187,7 +187,7 @@ thread_local uint64_t t_section_bytes_downloaded = 0, t_estimator_callbacks = 0;
 thread_local uint32_t t_last_estimator_error = 0;   // dxtlt_debug_auto_last_estimator_error
 thread_local bool t_no_arena = false;   // dxtlt_debug_auto_use_arena(0): every auto route as if the arena could not be allocated
 // dxtlt_debug_auto_last_totals: the totals the last built-in-estimator auto call of this thread compared, in candidate order
-thread_local uint64_t t_last_totals[16];
+thread_local uint64_t t_last_totals[24];   // 24: the candidates of auto_normalize_api.cpp
 thread_local int t_last_total_count = 0;
 
 uint32_t call_max(const DltSizeEstimator* est, size_t len, size_t* out)
@@ -501,6 +501,12 @@ void dxtlt_host::auto_begin_device_call()
 }
 
 bool dxtlt_host::auto_arena_disabled() { return t_no_arena; }
+
+void dxtlt_host::auto_set_last_totals(const uint64_t* totals, int count)
+{
+    t_last_total_count = std::min(count, 24);
+    std::copy(totals, totals + t_last_total_count, t_last_totals);
+}
 
 void dxtlt_host::auto_count_estimation(uint64_t section_bytes_downloaded, uint64_t estimator_callbacks)
 {

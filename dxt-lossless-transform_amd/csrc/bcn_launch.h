@@ -34,6 +34,9 @@ constexpr NormLimits norm_limits(int fmt)
 {
     return fmt == 1 ? NormLimits{2, 3, 0} : fmt == 2 ? NormLimits{2, 2, 0} : fmt == 3 ? NormLimits{2, 2, 3} : NormLimits{0, 0, 0};
 }
+// The fused mode a candidate of colour mode `norm` of transform_bcN_auto_with_normalization is ESTIMATED with: BC1's `None`
+// candidates are estimated with their fully transparent blocks rewritten (normalize.rs:447-454), the internal mode
+constexpr int norm_estimation_mode(int fmt, int norm) { return fmt == 1 && norm == 0 ? norm_limits(1).colour_internal : norm; }
 // the modes of a stand-alone normalisation call of format 1..3
 constexpr bool norm_modes_in_range(int fmt, int alpha_mode, int color_mode)
 {

@@ -215,6 +215,23 @@ void release_batch_auto_thread_buffers();   // batch_auto_api.cpp; through relea
 // thread, and what a callback route adds to the figures of dxtlt_debug_auto_last_estimation.
 bool auto_arena_disabled();
 void auto_count_estimation(uint64_t section_bytes_downloaded, uint64_t estimator_callbacks);
+// what dxtlt_debug_auto_last_totals reports from now on: the `count` (at most 24) totals a device route of another translation
+// unit compared, in its candidate order
+void auto_set_last_totals(const uint64_t* totals, int count);
+
+// ---- auto_normalize_api.cpp: transform_bcN_auto_with_normalization on the device (include/dxtlt_auto_normalize.h) ----
+struct AutoNormalizeChoice {
+    uint8_t norm;   // ColorNormalizationMode
+    uint8_t mode;   // core numbering
+    bool split_colour;
+};
+// format 1 or 2, device pointers, the built-in estimator; the arguments are valid and len > 0.  Two waits for `stream` (the flag,
+// the counters); the winner's fused normalise + transform launch is left enqueued.  When it returns, successful or not, nothing in
+// flight uses this thread's flag word, arena or counters.
+int32_t auto_normalize_on_device(int32_t format, const void* d_in, void* d_out, size_t len, bool use_all_decorrelation_modes,
+                                 hipStream_t stream, AutoNormalizeChoice* choice);
+// normalize_api.cpp: this thread's flag word on the current device, zeroed on `stream`
+int32_t normalize_thread_flag(uint32_t** d_flag, hipStream_t stream);
 
 // ---- estimate_api.cpp: the built-in estimator (include/dxtlt_estimator.h) -----------------------------------------
 bool is_builtin_estimator(const DltSizeEstimator* estimator);   // by the identity of its two function pointers

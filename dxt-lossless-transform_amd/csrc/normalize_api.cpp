@@ -13,16 +13,21 @@
 //     {None, Variant1, split} with size usize::MAX;
 //   * the data is transformed once more with the winner.
 // GPU shape: the input is uploaded once; the classification is a read-only kernel that sets a flag; every candidate is
-// one fused normalise+transform launch on the resident copy and only its colour section travels back.
+// one fused normalise+transform launch on the resident copy and only its colour section travels back.  BC2 has the same call
+// (this build's extension: the colour section is [len / 2, + len / 4), the `None` candidates are the input's own colours).  Given
+// the built-in estimator both run the device flow of auto_normalize_api.cpp instead: no section travels and no callback is made.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
 #include <cstring>
 #include <memory>
 
+#include "../../include/dxtlt_auto_normalize.h"
 #include "../../include/dxtlt_bc1_normalize.h"
 #include "../../include/dxtlt_bc23_normalize.h"
+#include "../../include/dxtlt_estimator.h"
 #include "../../include/dxtlt_gfx950.h"
+#include "auto_launch.h"
 #include "bcn_launch.h"
 #include "host_common.h"
 
@@ -300,7 +305,161 @@ int32_t fused_device(const NormFormat& F, const void* d_in, void* d_out, size_t 
     return dxtlt_host::enqueue(F.fmt, false, d_in, d_out, len / F.block_bytes, s, static_cast<hipStream_t>(stream));
 }
 
+hipError_t launch_any_normalizable(const NormFormat& F, const void* d_in, size_t len, uint32_t* d_flag, hipStream_t st)
+{
+    return F.fmt == 1 ? dxtlt::launch_bc1_any_normalizable(d_in, len / 8, d_flag, st) : dxtlt::launch_bc2_any_normalizable(d_in, len / 16, d_flag, st);
+}
+
+// the built-in estimator (arguments validated by the caller): nothing but the input and the result crosses PCIe, no callback
+int32_t auto_with_normalization_builtin(const NormFormat& F, const uint8_t* in, uint8_t* out, size_t len, bool use_all, uint8_t* out_color_mode,
+                                        uint8_t* out_decorrelation_mode, bool* out_split_colour_endpoints)
+{
+    dxtlt_host::AutoNormalizeChoice c{DXTLT_NORMALIZE_NONE, 0, false};
+    if (len == 0) {
+        dxtlt_host::AutoChoice plain{};
+        if (int32_t rc = dxtlt_host::transform_auto(F.fmt, in, out, 0, dxtlt_builtin_size_estimator(), use_all, &plain); rc != kOk)
+            return rc;
+        c = {DXTLT_NORMALIZE_NONE, plain.mode, plain.split_colour};
+    } else {
+        void *d_in = nullptr, *d_out = nullptr;
+        hipStream_t st = nullptr;
+        if (int32_t rc = dxtlt_host::acquire_staging(len, &d_in, &d_out, &st); rc != kOk)
+            return rc;
+        hipError_t e = hipMemcpyAsync(d_in, in, len, hipMemcpyHostToDevice, st);
+        int32_t rc = e == hipSuccess ? dxtlt_host::auto_normalize_on_device(F.fmt, d_in, d_out, len, use_all, st, &c) : fail(kDevice, "H2D copy", e);
+        if (rc == kOk && (e = hipMemcpyAsync(out, d_out, len, hipMemcpyDeviceToHost, st)) != hipSuccess)
+            rc = fail(kDevice, "D2H result", e);
+        e = hipStreamSynchronize(st);   // on every exit: the staging buffers belong to this thread's next call
+        if (rc == kOk && e != hipSuccess)
+            rc = fail(kDevice, "stream synchronize", e);
+        if (rc != kOk)
+            return rc;
+    }
+    if (out_color_mode) *out_color_mode = c.norm;
+    if (out_decorrelation_mode) *out_decorrelation_mode = c.mode;
+    if (out_split_colour_endpoints) *out_split_colour_endpoints = c.split_colour;
+    return kOk;
+}
+
+// ---- transform_bcN_auto_with_normalization on host pointers, BC1 and BC2 (the header comment of this file; BC2: this build's
+// extension, include/dxtlt_auto_normalize.h).  The estimator is shown the colour section of a transformed buffer: BC1 [0, len / 2),
+// BC2 [len / 2, + len / 4).  The built-in estimator is recognised and never called: one upload, the device flow of
+// auto_normalize_api.cpp, one download.
+int32_t auto_with_normalization_host(const NormFormat& F, const uint8_t* input_ptr, uint8_t* output_ptr, size_t len,
+                                     const DltSizeEstimator* est, bool use_all, uint8_t* out_color_mode,
+                                     uint8_t* out_decorrelation_mode, bool* out_split_colour_endpoints, uint32_t* out_estimator_error)
+{
+    const size_t shown_off = F.fmt == 1 ? 0 : len / 2, shown_len = F.fmt == 1 ? len / 2 : len / 4;
+    if (out_estimator_error)
+        *out_estimator_error = 0;
+    if (len % F.block_bytes != 0)
+        return fail(kInvalidLength, F.bad_len);
+    if (est == nullptr || est->MaxCompressedSize == nullptr || est->EstimateCompressedSize == nullptr)
+        return fail(kInvalidArgument, "NULL estimator");
+    if (len > 0 && (input_ptr == nullptr || output_ptr == nullptr))
+        return fail(kInvalidArgument, "NULL buffer with len > 0");
+
+    if (dxtlt_host::is_builtin_estimator(est))
+        return auto_with_normalization_builtin(F, input_ptr, output_ptr, len, use_all, out_color_mode, out_decorrelation_mode,
+                                               out_split_colour_endpoints);
+
+    size_t max_comp = 0;
+    if (uint32_t rc_est = est->MaxCompressedSize(est->Context, shown_len, &max_comp); rc_est != 0) {
+        if (out_estimator_error)
+            *out_estimator_error = rc_est;
+        return fail(kEstimator, "size estimator: max_compressed_size failed");
+    }
+
+    // classification pass: would any block change?
+    uint32_t any = 0;
+    void *d_in = nullptr, *d_out = nullptr;
+    hipStream_t st = nullptr;
+    if (len > 0) {
+        if (int32_t rc = dxtlt_host::acquire_staging(len, &d_in, &d_out, &st); rc != kOk)
+            return rc;
+        uint32_t* d_flag = nullptr;
+        if (int32_t rc = g_flag.get(&d_flag, st); rc != kOk)
+            return rc;
+        if (int32_t rc = staged(st, Transfers().add(d_in, input_ptr, len),
+                                [&] { return launch_any_normalizable(F, d_in, len, d_flag, st); },
+                                Transfers().add(d_flag, &any, sizeof(uint32_t), "D2H flag"));
+            rc != kOk)
+            return rc;
+    }
+    if (any == 0) {
+        // transform.rs:321-331: nothing to normalise -> the regular brute force, mode None
+        dxtlt_host::AutoChoice c{};
+        const int32_t rc = dxtlt_host::transform_auto(F.fmt, input_ptr, output_ptr, len, est, use_all, &c);
+        if (out_estimator_error)
+            *out_estimator_error = c.estimator_error;
+        if (rc == kOk) {
+            if (out_color_mode) *out_color_mode = DXTLT_NORMALIZE_NONE;
+            if (out_decorrelation_mode) *out_decorrelation_mode = c.mode;
+            if (out_split_colour_endpoints) *out_split_colour_endpoints = c.split_colour;
+        }
+        return rc;
+    }
+
+    std::unique_ptr<uint8_t, decltype(&std::free)> scratch(nullptr, &std::free);
+    if (max_comp != 0) {
+        scratch.reset(static_cast<uint8_t*>(std::aligned_alloc(64, (max_comp + 63) / 64 * 64)));
+        if (scratch == nullptr)
+            return fail(kAllocation, "estimator scratch allocation failed");
+    }
+    struct Best {
+        uint8_t norm, variant;
+        bool split;
+    } best{DXTLT_NORMALIZE_NONE, 1, true}, last = best;
+    bool last_valid = false;
+    size_t best_size = SIZE_MAX;
+    dxtlt_host::AutoChoice order[16];   // bc1 settings.rs:81-86 (FAST_TEST_ORDER) or :89-98 (COMPREHENSIVE_TEST_ORDER)
+    const int count = dxtlt_host::auto_candidate_order(F.fmt, use_all, order);
+    const uint64_t blocks = len / F.block_bytes;
+    for (uint8_t norm = 0; norm <= DXTLT_NORMALIZE_REPLICATE_COLOR; ++norm) {
+        // BC1: the reference estimates on the buffers of normalize_blocks_all_modes, whose `None` buffer still has its
+        // fully transparent blocks rewritten (normalize.rs:447-454): internal fused mode 3 reproduces that
+        const uint8_t fused = (uint8_t)dxtlt::norm_estimation_mode(F.fmt, norm);
+        for (int i = 0; i < count; ++i) {
+            if (int32_t rc = dxtlt_host::enqueue(F.fmt, false, d_in, d_out, blocks, Settings{order[i].mode, false, order[i].split_colour, fused}, st);
+                rc != kOk)
+                return rc;
+            hipError_t herr = hipMemcpyAsync(output_ptr + shown_off, static_cast<const uint8_t*>(d_out) + shown_off, shown_len, hipMemcpyDeviceToHost, st);
+            if (herr == hipSuccess)
+                herr = hipStreamSynchronize(st);
+            if (herr != hipSuccess)
+                return fail(kDevice, "candidate transform / download", herr);
+            last = {norm, order[i].mode, order[i].split_colour};
+            last_valid = true;
+            size_t size = 0;
+            if (est->EstimateCompressedSize(est->Context, output_ptr + shown_off, shown_len, scratch.get(), max_comp, &size) != 0)
+                continue;   // transform.rs:403: a failing estimate skips the candidate
+            if (size < best_size) {
+                best_size = size;
+                best = last;
+            }
+        }
+    }
+
+    // the final transform uses the chosen mode as transform_bc1_with_normalize_blocks defines it (transform.rs:307-313),
+    // so a `None` winner is re-run without the transparent rewrite its candidates were estimated with
+    const bool resident = last_valid && dxtlt::norm_estimation_mode(F.fmt, best.norm) == best.norm && last.norm == best.norm &&
+                          last.variant == best.variant && last.split == best.split;
+    if (!resident) {
+        if (int32_t rc = dxtlt_host::enqueue(F.fmt, false, d_in, d_out, blocks, Settings{best.variant, false, best.split, best.norm}, st);
+            rc != kOk)
+            return rc;
+    }
+    HIP_TRY(hipMemcpyAsync(output_ptr, d_out, len, hipMemcpyDeviceToHost, st), "D2H result");
+    HIP_TRY(hipStreamSynchronize(st), "stream synchronize");
+    if (out_color_mode) *out_color_mode = best.norm;
+    if (out_decorrelation_mode) *out_decorrelation_mode = best.variant;
+    if (out_split_colour_endpoints) *out_split_colour_endpoints = best.split;
+    return kOk;
+}
+
 }  // namespace
+
+int32_t dxtlt_host::normalize_thread_flag(uint32_t** d_flag, hipStream_t stream) { return g_flag.get(d_flag, stream); }
 
 void dxtlt_host::release_normalize_thread_flag()
 {
@@ -355,107 +514,17 @@ int32_t dxtlt_transform_bc1_auto_with_normalization(const uint8_t* input_ptr, ui
                                                     uint8_t* out_decorrelation_mode, bool* out_split_colour_endpoints,
                                                     uint32_t* out_estimator_error)
 {
-    if (out_estimator_error)
-        *out_estimator_error = 0;
-    if (len % 8 != 0)
-        return fail(kInvalidLength, kBc1.bad_len);
-    if (est == nullptr || est->MaxCompressedSize == nullptr || est->EstimateCompressedSize == nullptr)
-        return fail(kInvalidArgument, "NULL estimator");
-    if (len > 0 && (input_ptr == nullptr || output_ptr == nullptr))
-        return fail(kInvalidArgument, "NULL buffer with len > 0");
+    return auto_with_normalization_host(kBc1, input_ptr, output_ptr, len, est, use_all, out_color_mode, out_decorrelation_mode,
+                                        out_split_colour_endpoints, out_estimator_error);
+}
 
-    size_t max_comp = 0;
-    if (uint32_t rc_est = est->MaxCompressedSize(est->Context, len / 2, &max_comp); rc_est != 0) {
-        if (out_estimator_error)
-            *out_estimator_error = rc_est;
-        return fail(kEstimator, "size estimator: max_compressed_size failed");
-    }
-
-    // classification pass: would any block change?
-    uint32_t any = 0;
-    void *d_in = nullptr, *d_out = nullptr;
-    hipStream_t st = nullptr;
-    if (len > 0) {
-        if (int32_t rc = dxtlt_host::acquire_staging(len, &d_in, &d_out, &st); rc != kOk)
-            return rc;
-        uint32_t* d_flag = nullptr;
-        if (int32_t rc = g_flag.get(&d_flag, st); rc != kOk)
-            return rc;
-        if (int32_t rc = staged(st, Transfers().add(d_in, input_ptr, len),
-                                [&] { return dxtlt::launch_bc1_any_normalizable(d_in, len / 8, d_flag, st); },
-                                Transfers().add(d_flag, &any, sizeof(uint32_t), "D2H flag"));
-            rc != kOk)
-            return rc;
-    }
-    if (any == 0) {
-        // transform.rs:321-331: nothing to normalise -> the regular brute force, mode None
-        dxtlt_host::AutoChoice c{};
-        const int32_t rc = dxtlt_host::transform_auto(1, input_ptr, output_ptr, len, est, use_all, &c);
-        if (out_estimator_error)
-            *out_estimator_error = c.estimator_error;
-        if (rc == kOk) {
-            if (out_color_mode) *out_color_mode = DXTLT_NORMALIZE_NONE;
-            if (out_decorrelation_mode) *out_decorrelation_mode = c.mode;
-            if (out_split_colour_endpoints) *out_split_colour_endpoints = c.split_colour;
-        }
-        return rc;
-    }
-
-    std::unique_ptr<uint8_t, decltype(&std::free)> scratch(nullptr, &std::free);
-    if (max_comp != 0) {
-        scratch.reset(static_cast<uint8_t*>(std::aligned_alloc(64, (max_comp + 63) / 64 * 64)));
-        if (scratch == nullptr)
-            return fail(kAllocation, "estimator scratch allocation failed");
-    }
-    struct Best {
-        uint8_t norm, variant;
-        bool split;
-    } best{DXTLT_NORMALIZE_NONE, 1, true}, last = best;
-    bool last_valid = false;
-    size_t best_size = SIZE_MAX;
-    dxtlt_host::AutoChoice order[16];   // bc1 settings.rs:81-86 (FAST_TEST_ORDER) or :89-98 (COMPREHENSIVE_TEST_ORDER)
-    const int count = dxtlt_host::auto_candidate_order(1, use_all, order);
-    const uint64_t blocks = len / 8;
-    for (uint8_t norm = 0; norm <= DXTLT_NORMALIZE_REPLICATE_COLOR; ++norm) {
-        // the reference estimates on the buffers of normalize_blocks_all_modes, whose `None` buffer still has its
-        // fully transparent blocks rewritten (normalize.rs:447-454): internal fused mode 3 reproduces that
-        const uint8_t fused = norm == DXTLT_NORMALIZE_NONE ? 3 : norm;
-        for (int i = 0; i < count; ++i) {
-            if (int32_t rc = dxtlt_host::enqueue(1, false, d_in, d_out, blocks, Settings{order[i].mode, false, order[i].split_colour, fused}, st);
-                rc != kOk)
-                return rc;
-            hipError_t herr = hipMemcpyAsync(output_ptr, d_out, len / 2, hipMemcpyDeviceToHost, st);
-            if (herr == hipSuccess)
-                herr = hipStreamSynchronize(st);
-            if (herr != hipSuccess)
-                return fail(kDevice, "candidate transform / download", herr);
-            last = {norm, order[i].mode, order[i].split_colour};
-            last_valid = true;
-            size_t size = 0;
-            if (est->EstimateCompressedSize(est->Context, output_ptr, len / 2, scratch.get(), max_comp, &size) != 0)
-                continue;   // transform.rs:403: a failing estimate skips the candidate
-            if (size < best_size) {
-                best_size = size;
-                best = last;
-            }
-        }
-    }
-
-    // the final transform uses the chosen mode as transform_bc1_with_normalize_blocks defines it (transform.rs:307-313),
-    // so a `None` winner is re-run without the transparent rewrite its candidates were estimated with
-    const bool resident = last_valid && best.norm != DXTLT_NORMALIZE_NONE && last.norm == best.norm &&
-                          last.variant == best.variant && last.split == best.split;
-    if (!resident) {
-        if (int32_t rc = dxtlt_host::enqueue(1, false, d_in, d_out, blocks, Settings{best.variant, false, best.split, best.norm}, st);
-            rc != kOk)
-            return rc;
-    }
-    HIP_TRY(hipMemcpyAsync(output_ptr, d_out, len, hipMemcpyDeviceToHost, st), "D2H result");
-    HIP_TRY(hipStreamSynchronize(st), "stream synchronize");
-    if (out_color_mode) *out_color_mode = best.norm;
-    if (out_decorrelation_mode) *out_decorrelation_mode = best.variant;
-    if (out_split_colour_endpoints) *out_split_colour_endpoints = best.split;
-    return kOk;
+int32_t dxtlt_transform_bc2_auto_with_normalization(const uint8_t* input_ptr, uint8_t* output_ptr, size_t len,
+                                                    const DltSizeEstimator* est, bool use_all, uint8_t* out_color_mode,
+                                                    uint8_t* out_decorrelation_mode, bool* out_split_colour_endpoints,
+                                                    uint32_t* out_estimator_error)
+{
+    return auto_with_normalization_host(kBc2, input_ptr, output_ptr, len, est, use_all, out_color_mode, out_decorrelation_mode,
+                                        out_split_colour_endpoints, out_estimator_error);
 }
 
 // ---- BC2 / BC3 (include/dxtlt_bc23_normalize.h) ---------------------------------------------------------------------

@@ -200,3 +200,65 @@ def transform_bc3_with_normalize_blocks(input, output, alpha_mode, color_mode: C
     ``normalize23.AlphaNormalizationMode``.  Undo with ``untransform_bc3_with_settings``: it yields the normalised blocks."""
     _fused_bc23("bc3", input, output, (int(alpha_mode), int(color_mode)),
                 (int(decorrelation_mode), bool(split_alpha_endpoints), bool(split_colour_endpoints)))
+
+
+# ---- the auto transform with block normalisation (include/dxtlt_auto_normalize.h; docs/ESTIMATOR.md) ---------------------------------
+_auto_declared = False
+
+
+def _auto_l():
+    global _auto_declared
+    l = _l()
+    if not _auto_declared:
+        u8p, bp = C.POINTER(_U8), C.POINTER(_B)
+        for fmt in ("bc1", "bc2"):
+            f = getattr(l, f"dxtlt_transform_{fmt}_auto_with_normalization")
+            f.argtypes, f.restype = [_VP, _VP, _SZ, _VP, _B, u8p, u8p, bp, C.POINTER(C.c_uint32)], C.c_int32
+            f = getattr(l, f"dxtlt_transform_{fmt}_auto_with_normalization_device")
+            f.argtypes, f.restype = [_VP, _VP, _SZ, _B, _VP, u8p, u8p, bp], C.c_int32
+        _auto_declared = True
+    return l
+
+
+def _auto_with_normalization(fmt: str, input, output, estimator, use_all_decorrelation_modes: bool):
+    from . import _check
+
+    src, dst = _bufs((input, output), (False, True))
+    _sized(src, dst, 8 if fmt == "bc1" else 16)
+    device = _device_of((src, dst), "input and output must both be host buffers or both be device tensors")
+    l = _auto_l()
+    norm, mode, split = _U8(), _U8(), _B()
+    outs = (C.byref(norm), C.byref(mode), C.byref(split))
+    use_all = bool(use_all_decorrelation_modes)
+    if device is None:
+        if estimator is None:
+            from . import estimator as _estimator
+
+            estimator = _estimator.builtin_size_estimator()
+        elif isinstance(estimator, C.Structure):
+            estimator = C.cast(C.pointer(estimator), _VP)
+        _check(getattr(l, f"dxtlt_transform_{fmt}_auto_with_normalization")(src.ptr, dst.ptr, src.nbytes, estimator, use_all, *outs, None))
+    else:
+        if estimator is not None:
+            raise TypeError("device tensors are estimated with the built-in estimator: pass no estimator")
+        import torch
+
+        with torch.cuda.device(device):
+            _check(getattr(l, f"dxtlt_transform_{fmt}_auto_with_normalization_device")(
+                src.ptr, dst.ptr, src.nbytes, use_all, torch.cuda.current_stream(device).cuda_stream, *outs))
+    return ColorNormalizationMode(norm.value), int(mode.value), bool(split.value)
+
+
+def transform_bc1_auto_with_normalization(input, output, estimator=None, use_all_decorrelation_modes: bool = False,
+                                          ) -> Bc1TransformDetailsWithNormalization:
+    """transform.rs:222: the colour normalisation mode and the transform settings whose colour section the estimator finds
+    smallest; ``output`` holds ``transform_bc1_with_normalize_blocks(input, result)``.  Host buffers (``estimator``: a
+    ``DltSizeEstimator`` structure or a pointer to one; None: the built-in estimator, everything on the device) or CUDA
+    ``torch.uint8`` tensors (the built-in estimator, on torch's current stream, which the call waits for twice)."""
+    return Bc1TransformDetailsWithNormalization(*_auto_with_normalization("bc1", input, output, estimator, use_all_decorrelation_modes))
+
+
+def transform_bc2_auto_with_normalization(input, output, estimator=None, use_all_decorrelation_modes: bool = False):
+    """BC2's twin (this build's extension, include/dxtlt_auto_normalize.h).  Returns (ColorNormalizationMode, decorrelation mode in
+    the core YCoCgVariant numbering, split_colour_endpoints); ``output`` holds ``transform_bc2_with_normalize_blocks`` with them."""
+    return _auto_with_normalization("bc2", input, output, estimator, use_all_decorrelation_modes)

@@ -26,6 +26,7 @@
 #include <string>
 #include <utility>
 
+#include "dxtlt_auto_normalize.h"
 #include "dxtlt_bc1_normalize.h"
 #include "dxtlt_bc23_normalize.h"
 #include "dxtlt_bc6h.h"
@@ -425,6 +426,18 @@ std::pair<Bc1TransformDetailsWithNormalization, DetermineBestTransformError> tra
     return {Bc1TransformDetailsWithNormalization{static_cast<ColorNormalizationMode>(norm), static_cast<YCoCgVariant>(mode), sc},
             detail_auto::map(rc)};
 }
+// the same on device pointers with the built-in estimator (dxtlt_auto_normalize.h): waits for `hip_stream` twice and leaves the
+// winner's transform enqueued on it
+inline Bc1TransformDetailsWithNormalization transform_bc1_auto_with_normalization_device(const void* d_input, void* d_output, size_t len,
+                                                                                         bool use_all_decorrelation_modes,
+                                                                                         void* hip_stream)
+{
+    uint8_t norm = 0, mode = 1;
+    bool sc = true;
+    detail::check_device(dxtlt_transform_bc1_auto_with_normalization_device(d_input, d_output, len, use_all_decorrelation_modes, hip_stream,
+                                                                            &norm, &mode, &sc));
+    return {static_cast<ColorNormalizationMode>(norm), static_cast<YCoCgVariant>(mode), sc};
+}
 
 // ---- dxt_lossless_transform_bc2 / _bc3 ::experimental::normalize_blocks (normalize.rs of those crates) ----------
 namespace bc2 {
@@ -451,6 +464,41 @@ inline void transform_bc2_with_normalize_blocks(const uint8_t* input_ptr, uint8_
     detail::check_device(dxtlt_transform_bc2_with_normalize_blocks(input_ptr, output_ptr, len, static_cast<uint8_t>(color_mode),
                                                                    static_cast<uint8_t>(s.decorrelation_mode),
                                                                    s.split_colour_endpoints));
+}
+// BC2's twin of transform_bc1_auto_with_normalization (dxtlt_auto_normalize.h; no upstream counterpart): the colour normalisation
+// mode and the settings whose colour section the estimator finds smallest; output = transform_bc2_with_normalize_blocks with them
+struct Bc2TransformDetailsWithNormalization {
+    ColorNormalizationMode color_normalization_mode = ColorNormalizationMode::None;
+    Bc2TransformSettings settings{};
+};
+template <class E>
+std::pair<Bc2TransformDetailsWithNormalization, DetermineBestTransformError> transform_bc2_auto_with_normalization(
+    const uint8_t* input_ptr, uint8_t* output_ptr, size_t len, EstimateSettings<E>& options)
+{
+    DltSizeEstimator v = detail_auto::make_vtable(options.size_estimator);
+    uint8_t norm = 0, mode = 1;
+    bool sc = true;
+    int32_t rc = dxtlt_transform_bc2_auto_with_normalization(input_ptr, output_ptr, len, &v, options.use_all_decorrelation_modes,
+                                                             &norm, &mode, &sc, nullptr);
+    Bc2TransformDetailsWithNormalization d;
+    d.color_normalization_mode = static_cast<ColorNormalizationMode>(norm);
+    d.settings.decorrelation_mode = static_cast<YCoCgVariant>(mode);
+    d.settings.split_colour_endpoints = sc;
+    return {d, detail_auto::map(rc)};
+}
+inline Bc2TransformDetailsWithNormalization transform_bc2_auto_with_normalization_device(const void* d_input, void* d_output, size_t len,
+                                                                                         bool use_all_decorrelation_modes,
+                                                                                         void* hip_stream)
+{
+    uint8_t norm = 0, mode = 1;
+    bool sc = true;
+    detail::check_device(dxtlt_transform_bc2_auto_with_normalization_device(d_input, d_output, len, use_all_decorrelation_modes, hip_stream,
+                                                                            &norm, &mode, &sc));
+    Bc2TransformDetailsWithNormalization d;
+    d.color_normalization_mode = static_cast<ColorNormalizationMode>(norm);
+    d.settings.decorrelation_mode = static_cast<YCoCgVariant>(mode);
+    d.settings.split_colour_endpoints = sc;
+    return d;
 }
 }  // namespace bc2
 

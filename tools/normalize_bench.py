@@ -14,7 +14,20 @@ transform and the stand-alone normalise kernel: ms and fraction of the 8 TB/s HB
         ms per call (median of the rounds) and the fraction of the 8 TB/s HBM peak on the algorithmic 2 * len of ONE pass (two_pass
         moves 4 * len: its figure is the rate a caller sees for the operation).  Acceptance: fused is faster than two_pass in every
         cell and every process by more than the cell's run-to-run spread (largest max - min of a leg's ms over the processes).
-    tools/normalize_bench.py bc23-cells --gib G                       one such process: a JSON line with every cell"""
+    tools/normalize_bench.py bc23-cells --gib G                       one such process: a JSON line with every cell
+
+    tools/normalize_bench.py auto [--mib 1,256,2048] [--processes 3] [--parent-lib PATH] [--out profiles/auto_normalize_bench.json]
+        the auto transform with block normalisation (include/dxtlt_auto_normalize.h).  Cells: BC1 / BC2 x fast / all modes x size x
+        data ("tenth": about 10 % normalisable blocks, "none": no such block).  Every cell is timed in `processes` fresh processes;
+        each times, alternating in rounds, host clock around work that ends in a device synchronise:
+          device      dxtlt_transform_bcN_auto_with_normalization_device
+          loop        the same work from the calls that existed before it: dxtlt_transform_bcN_with_normalize_blocks_device per
+                      candidate with dxtlt_estimate_sizes_device on its colour section, one readback, the winner once more
+          plain_auto  dxtlt_transform_bcN_auto_device ("none" data: what the flag-0 path costs on top of it)
+          host        the host call with the built-in estimator (sizes up to 256 MiB); host_parent: the same call of the library at
+                      --parent-lib (a build of the commit before this call existed on the device: it goes through the callbacks)
+        and, with HIP events, the parts of `device`: the candidate kernel, the estimator over its sections, the winner's transform.
+    tools/normalize_bench.py auto-cells --mib ... [--parent-lib PATH]   one such process: a JSON line with every cell"""
 import json
 import os
 import sys
@@ -129,6 +142,204 @@ def bc23_main(argv):
     print(json.dumps({"accepted": accepted, "out": a.out, "cells": len(cells)}))
 
 
+# ---- auto: the auto transform with block normalisation ---------------------------------------------------------------------------------
+def auto_data(fmt, nbytes, kind, dev):
+    """random blocks none of which any mode changes (c0 != c1, pixels 0 and 1 with different indices); "tenth": every 20th block a solid
+    colour by index 0 and every 20th a fully transparent block (BC1) / a solid by index 1 (BC2)"""
+    bb, at = (8, 0) if fmt == 1 else (16, 8)
+    n = nbytes // bb
+    x = torch.empty(n * bb, dtype=torch.uint8, device=dev)
+    pkg.fill_splitmix64(x, 0xA0700 + fmt)
+    b = x.view(-1, bb)
+    for lo in range(0, n, 1 << 24):
+        v = b[lo:min(n, lo + (1 << 24))]
+        v[:, at] |= 1
+        v[:, at + 2] &= 0xFE
+        v[:, at + 4] = (v[:, at + 4] & 0xF0) | 4
+    if kind == "tenth":
+        b[0::20, at + 4:at + 8] = 0
+        if fmt == 1:
+            b[10::20, at:at + 2] = 0
+            b[10::20, at + 4:at + 8] = 0xFF
+        else:
+            b[10::20, at + 4:at + 8] = 0x55
+    return x
+
+
+def auto_cells(mibs, parent_lib=None, rounds=3):
+    import ctypes as C
+    import statistics
+    import time
+
+    lib = C.CDLL(pkg._lib.lib_path())
+    parent = C.CDLL(parent_lib) if parent_lib else None
+    vp, sz, u8p, bp, u64p = C.c_void_p, C.c_size_t, C.POINTER(C.c_uint8), C.POINTER(C.c_bool), C.POINTER(C.c_uint64)
+
+    class Sec(C.Structure):
+        _fields_ = [("d_ptr", vp), ("len", C.c_uint64)]
+
+    for l in (lib, parent):
+        if l is None:
+            continue
+        l.dxtlt_builtin_size_estimator.restype = vp
+        l.dxtlt_transform_bc1_auto_with_normalization.argtypes = [vp, vp, sz, vp, C.c_bool, u8p, u8p, bp, C.POINTER(C.c_uint32)]
+    for n in (1, 2):
+        getattr(lib, f"dxtlt_transform_bc{n}_auto_with_normalization_device").argtypes = [vp, vp, sz, C.c_bool, vp, u8p, u8p, bp]
+        getattr(lib, f"dxtlt_transform_bc{n}_auto_with_normalization").argtypes = [vp, vp, sz, vp, C.c_bool, u8p, u8p, bp, C.POINTER(C.c_uint32)]
+        getattr(lib, f"dxtlt_transform_bc{n}_auto_device").argtypes = [vp, vp, sz, C.c_bool, vp, u8p, bp]
+        getattr(lib, f"dxtlt_transform_bc{n}_with_normalize_blocks_device").argtypes = [vp, vp, sz, C.c_uint8, C.c_uint8, C.c_bool, vp]
+    lib.dxtlt_estimate_sizes_device.argtypes = [C.POINTER(Sec), sz, vp, vp]
+    lib.dxtlt_debug_auto_normalization_candidates_into_device.argtypes = [C.c_int32, C.c_bool, vp, sz, vp, C.c_uint64, vp]
+    lib.dxtlt_debug_auto_normalization_last.argtypes = [u64p]
+    FAST = [(0, 0), (0, 1), (1, 0), (1, 1)]
+    ALL = [(2, 0), (0, 0), (0, 1), (3, 0), (3, 1), (2, 1), (1, 0), (1, 1)]
+    dev = torch.device("cuda:0")
+    stream = torch.cuda.current_stream().cuda_stream
+    out = {}
+
+    def ok(rc):
+        if rc != 0:
+            raise RuntimeError(f"status {rc}")
+
+    def wall_ms(fn, steps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / steps
+
+    for mib in mibs:
+        nbytes = int(mib * (1 << 20))
+        steps = 20 if mib <= 16 else 3
+        for fmt in (1, 2):
+            for kind in ("tenth", "none"):
+                x = auto_data(fmt, nbytes, kind, dev)
+                y = torch.empty_like(x)
+                shown = (y.data_ptr(), nbytes // 2) if fmt == 1 else (y.data_ptr() + nbytes // 2, nbytes // 4)
+                for use_all in (False, True):
+                    order = ALL if use_all else FAST
+                    cands = [(norm, v, sc) for norm in range(3) for v, sc in order]
+                    sizes = torch.zeros(len(cands), dtype=torch.int64, device=dev)
+                    choice = [C.c_uint8(), C.c_uint8(), C.c_bool()]
+                    refs = [C.byref(c) for c in choice]
+                    fused = getattr(lib, f"dxtlt_transform_bc{fmt}_with_normalize_blocks_device")
+
+                    def device():
+                        ok(getattr(lib, f"dxtlt_transform_bc{fmt}_auto_with_normalization_device")(x.data_ptr(), y.data_ptr(), nbytes, use_all, stream, *refs))
+
+                    def loop():
+                        sec = Sec(shown[0], shown[1])
+                        for i, (norm, v, sc) in enumerate(cands):
+                            ok(fused(x.data_ptr(), y.data_ptr(), nbytes, norm, v, bool(sc), stream))
+                            ok(lib.dxtlt_estimate_sizes_device(C.byref(sec), 1, stream, sizes.data_ptr() + 8 * i))
+                        got = sizes.cpu().tolist()                       # the one readback
+                        norm, v, sc = cands[got.index(min(got))]
+                        ok(fused(x.data_ptr(), y.data_ptr(), nbytes, norm, v, bool(sc), stream))
+
+                    def plain_auto():
+                        ok(getattr(lib, f"dxtlt_transform_bc{fmt}_auto_device")(x.data_ptr(), y.data_ptr(), nbytes, use_all, stream, refs[1], refs[2]))
+
+                    legs = {"device": device, "loop": loop, "plain_auto": plain_auto}
+                    if mib <= 256:
+                        hx = x.cpu().numpy()
+                        hy = hx.copy()
+
+                        def host(l=lib):
+                            f = getattr(l, f"dxtlt_transform_bc{fmt}_auto_with_normalization")
+                            ok(f(hx.ctypes.data, hy.ctypes.data, nbytes, l.dxtlt_builtin_size_estimator(), use_all, *refs, None))
+
+                        legs["host"] = host
+                        if parent is not None and fmt == 1:
+                            legs["host_parent"] = lambda: host(parent)
+                    for fn in legs.values():                             # warm up every leg: code objects, arenas, staging buffers
+                        fn()
+                        torch.cuda.synchronize()
+                    device()
+                    last = (C.c_uint64 * 4)()
+                    lib.dxtlt_debug_auto_normalization_last(last)
+                    picked = [int(c.value) for c in choice]
+                    ms = {k: [] for k in legs}
+                    for _ in range(rounds):
+                        for k, fn in legs.items():
+                            ms[k].append(wall_ms(fn, 1 if k.startswith("host") and mib > 16 else steps))
+                    cell = {k: {"ms": round(statistics.median(v), 4), "ms_min": round(min(v), 4), "ms_max": round(max(v), 4)} for k, v in ms.items()}
+                    cell["flag"], cell["choice"] = int(last[3]), picked
+                    if kind == "tenth":                                  # the parts of `device`, HIP events
+                        count = 24 if use_all else 12
+                        blocks = nbytes // (8 if fmt == 1 else 16)
+                        arena = torch.empty(count * 4 * blocks, dtype=torch.uint8, device=dev)
+                        secs = (Sec * count)(*[Sec(arena.data_ptr() + 4 * blocks * k, 4 * blocks) for k in range(count)])
+                        parts = {
+                            "candidates": lambda: ok(lib.dxtlt_debug_auto_normalization_candidates_into_device(fmt, use_all, x.data_ptr(), nbytes, arena.data_ptr(), arena.numel(), stream)),
+                            "estimator": lambda: ok(lib.dxtlt_estimate_sizes_device(secs, count, stream, sizes.data_ptr())),
+                            "winner": lambda: ok(fused(x.data_ptr(), y.data_ptr(), nbytes, picked[0], picked[1], bool(picked[2]), stream)),
+                        }
+                        for fn in parts.values():
+                            fn()
+                        cell["parts_event_ms"] = {k: round(statistics.median([event_ms(fn, steps) for _ in range(rounds)]), 4) for k, fn in parts.items()}
+                        del arena
+                    out[f"bc{fmt} {'all' if use_all else 'fast'} {mib:g}MiB {kind}"] = cell
+                del x, y
+                torch.cuda.empty_cache()
+    return out
+
+
+def auto_main(argv):
+    import argparse
+    import subprocess
+
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--mib", default="1,256,2048")
+    ap.add_argument("--processes", type=int, default=3)
+    ap.add_argument("--parent-lib", default=None)
+    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "auto_normalize_bench.json"))
+    a = ap.parse_args(argv)
+    runs = []
+    for _ in range(a.processes):   # one after the other: fresh processes, never two on the device at once
+        cmd = [sys.executable, os.path.abspath(__file__), "auto-cells", "--mib", a.mib] + (["--parent-lib", a.parent_lib] if a.parent_lib else [])
+        done = subprocess.run(cmd, capture_output=True, text=True, check=True)
+        runs.append(json.loads(done.stdout.strip().splitlines()[-1]))
+        print(f"process {len(runs)} of {a.processes} done", file=sys.stderr, flush=True)
+    cells, all_faster = {}, True
+    for name in runs[0]:
+        legs = {k: [r[name][k] for r in runs] for k in runs[0][name] if isinstance(runs[0][name][k], dict) and "ms" in runs[0][name][k]}
+        spread = max(max(p["ms"] for p in legs[k]) - min(p["ms"] for p in legs[k]) for k in ("device", "loop"))   # of the two legs compared
+        margins = [round(l["ms"] - d["ms"], 4) for d, l in zip(legs["device"], legs["loop"])]
+        faster = all(m > spread for m in margins)
+        cell = {"processes": legs, "spread_ms": round(spread, 4), "loop_minus_device_ms": margins,
+                "loop_over_device": [round(l["ms"] / d["ms"], 3) for d, l in zip(legs["device"], legs["loop"])],
+                "device_faster_than_loop_by_more_than_the_spread": faster, "flag": runs[0][name]["flag"], "choice": runs[0][name]["choice"]}
+        if name.endswith("none"):
+            cell["device_minus_plain_auto_ms"] = [round(d["ms"] - p["ms"], 4) for d, p in zip(legs["device"], legs["plain_auto"])]
+        else:
+            all_faster = all_faster and faster
+        if "host_parent" in legs:
+            cell["host_parent_over_host"] = [round(p["ms"] / h["ms"], 3) for h, p in zip(legs["host"], legs["host_parent"])]
+        if "parts_event_ms" in runs[0][name]:
+            parts = [r[name]["parts_event_ms"] for r in runs]
+            cell["parts_event_ms"] = parts
+            cell["estimator_share_of_device"] = [round(p["estimator"] / d["ms"], 3) for p, d in zip(parts, legs["device"])]
+        cells[name] = cell
+    res = {"workload": "auto transform with block normalisation, BC1 / BC2, fast / all modes; 'tenth': about 10 % normalisable blocks, 'none': no such block",
+           "legs": "ms per call, host clock around work that ends in a device synchronise; median / min / max of 3 rounds, the legs alternating; "
+                   "parts_event_ms: HIP events around the candidate kernel, the estimator over its 12 / 24 sections and the winner's transform",
+           "spread_ms": "the larger max - min over the processes of the device and the loop leg's ms",
+           "processes_per_cell": a.processes, "parent_lib_measured": bool(a.parent_lib),
+           "device_faster_than_loop_in_every_tenth_cell": all_faster, "cells": cells}
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps({"out": a.out, "cells": len(cells), "device_faster_than_loop_in_every_tenth_cell": all_faster}))
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "auto-cells":
+    _mibs = [float(v) for v in sys.argv[sys.argv.index("--mib") + 1].split(",")]
+    print(json.dumps(auto_cells(_mibs, sys.argv[sys.argv.index("--parent-lib") + 1] if "--parent-lib" in sys.argv else None)))
+    sys.exit(0)
+if len(sys.argv) > 1 and sys.argv[1] == "auto":
+    auto_main(sys.argv[2:])
+    sys.exit(0)
 if len(sys.argv) > 1 and sys.argv[1] == "bc23-cells":
     print(json.dumps(bc23_cells(float(sys.argv[sys.argv.index("--gib") + 1]) if "--gib" in sys.argv else 4.0)))
     sys.exit(0)
