@@ -32,6 +32,9 @@
 // orders (candidates_of), the section(s) of a transformed buffer the estimator is shown (shown_sections), the distinct sections of
 // a candidate arena (dxtlt::auto_sections) with the ones a candidate is the sum of (sections_of) and the pick over them
 // (auto_pick), and the estimator thread count (estimator_threads).
+// The frame around the flows -- the drain guard, the estimator scratch, the device-call guard, the staged host call and this thread's
+// auto state, which the other single-buffer auto calls (auto_normalize_api.cpp, pixel_auto_api.cpp) use too -- is auto_call.h; its
+// non-template definitions are below.
 //
 // The built-in estimator (include/dxtlt_estimator.h, estimate_kernels.hip) is recognised by the identity of its function
 // pointers and never called: auto_on_device() estimates every distinct section where the candidate kernel left it, with one
@@ -47,9 +50,9 @@
 #include "../../include/dxtlt_bc45.h"
 #include "../../include/dxtlt_estimator.h"
 #include "../../include/dxtlt_gfx950.h"
+#include "auto_call.h"
 #include "auto_launch.h"
 #include "bcn_launch.h"
-#include "host_common.h"
 
 namespace {
 
@@ -123,88 +126,27 @@ void sections_of(int32_t format, const Candidate& c, int* idx)
     }
 }
 
-// Estimator scratch of one thread: freed on every exit.
-struct HostScratch {
-    uint8_t* ptr = nullptr;
-    HostScratch() = default;
-    HostScratch(const HostScratch&) = delete;
-    ~HostScratch() { std::free(ptr); }
-    bool allocate(size_t max_comp)   // nothing for max_comp == 0
-    {
-        if (max_comp != 0)
-            ptr = static_cast<uint8_t*>(std::aligned_alloc(64, (max_comp + 63) / 64 * 64));
-        return max_comp == 0 || ptr != nullptr;
-    }
-};
+using dxtlt_host::EstimatorScratch;
+using dxtlt_host::StreamDrain;
 
-// THE invariant of every auto route: no exit returns while work that reads or writes this thread's staging buffers, pinned stage
-// or arena is in flight -- they belong to this thread's next call.  Armed once anything has been enqueued, the guard waits for the
-// stream on every exit; the success path waits itself (it has to report a failure of the wait) and disarms it.
-struct StreamDrain {
-    hipStream_t stream = nullptr;
-    bool armed = false;
-    ~StreamDrain()
-    {
-        if (armed) (void)hipStreamSynchronize(stream);
-    }
-};
-
-// per-thread candidate arena (grow-only, like the staging buffers)
-struct Arena {
-    void* ptr = nullptr;
-    size_t cap = 0;
-    int device = -1;
-    ~Arena() { release(); }
-    void release()
-    {
-        if (ptr) (void)hipFree(ptr);
-        ptr = nullptr;
-        cap = 0;
-        device = -1;
-    }
-    void* get(size_t bytes)
-    {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess)
-            return nullptr;
-        if (dev != device || bytes > cap) {
-            release();
-            if (hipMalloc(&ptr, bytes) != hipSuccess) {
-                (void)hipGetLastError();
-                ptr = nullptr;
-                return nullptr;
-            }
-            cap = bytes;
-            device = dev;
-        }
-        return ptr;
-    }
-};
-thread_local Arena g_arena;
-
-// dxtlt_debug_auto_last_estimation: what the last auto call of this thread downloaded and called for its estimates
-thread_local uint64_t t_section_bytes_downloaded = 0, t_estimator_callbacks = 0;
+thread_local dxtlt_host::AutoThreadState t_auto;
 thread_local uint32_t t_last_estimator_error = 0;   // dxtlt_debug_auto_last_estimator_error
-thread_local bool t_no_arena = false;   // dxtlt_debug_auto_use_arena(0): every auto route as if the arena could not be allocated
-// dxtlt_debug_auto_last_totals: the totals the last built-in-estimator auto call of this thread compared, in candidate order
-thread_local uint64_t t_last_totals[24];   // 24: the candidates of auto_normalize_api.cpp
-thread_local int t_last_total_count = 0;
 
 uint32_t call_max(const DltSizeEstimator* est, size_t len, size_t* out)
 {
-    ++t_estimator_callbacks;
+    ++t_auto.estimator_callbacks;
     return est->MaxCompressedSize(est->Context, len, out);
 }
 
 uint32_t call_estimate(const DltSizeEstimator* est, const uint8_t* in, size_t len, uint8_t* scratch, size_t max_comp, size_t* out)
 {
-    ++t_estimator_callbacks;
+    ++t_auto.estimator_callbacks;
     return est->EstimateCompressedSize(est->Context, in, len, scratch, max_comp, out);
 }
 
 hipError_t download_section(void* dst, const void* src, size_t len, hipStream_t st)
 {
-    t_section_bytes_downloaded += len;
+    t_auto.section_bytes_downloaded += len;
     return hipMemcpyAsync(dst, src, len, hipMemcpyDeviceToHost, st);
 }
 
@@ -232,32 +174,6 @@ int estimator_threads()
     return t_estimator_threads_cap > 0 ? std::min(threads, t_estimator_threads_cap) : threads;
 }
 
-struct HostStage {
-    void* ptr = nullptr;
-    size_t cap = 0;
-    ~HostStage() { release(); }
-    void release()
-    {
-        if (ptr) (void)hipHostFree(ptr);
-        ptr = nullptr;
-        cap = 0;
-    }
-    void* get(size_t bytes)
-    {
-        if (bytes > cap) {
-            release();
-            if (hipHostMalloc(&ptr, bytes, hipHostMallocDefault) != hipSuccess) {
-                (void)hipGetLastError();
-                ptr = nullptr;
-                return nullptr;
-            }
-            cap = bytes;
-        }
-        return ptr;
-    }
-};
-thread_local HostStage g_stage;
-
 struct Section {
     const uint8_t* d_src;   // in the arena
     size_t len;
@@ -282,15 +198,15 @@ bool estimate_sections_parallel(std::vector<Section>& sections, const DltSizeEst
         run += b;
         want = std::max(want, run);
     }
-    uint8_t* stage = static_cast<uint8_t*>(g_stage.get(want));
+    uint8_t* stage = static_cast<uint8_t*>(t_auto.stage.get(want));
     if (stage == nullptr) {
         *hip_error = hipErrorOutOfMemory;
         return false;
     }
     threads = std::max(1, std::min<int>(threads, (int)sections.size()));
-    std::vector<HostScratch> scratch((size_t)threads);
+    std::vector<EstimatorScratch> scratch((size_t)threads);
     bool ok = true;
-    for (HostScratch& p : scratch)
+    for (EstimatorScratch& p : scratch)
         ok = p.allocate(max_comp) && ok;
     *hip_error = ok ? hipSuccess : hipErrorOutOfMemory;
     size_t first = 0;
@@ -335,7 +251,7 @@ bool estimate_sections_parallel(std::vector<Section>& sections, const DltSizeEst
         worker(0);
         for (auto& t : pool)
             t.join();
-        t_estimator_callbacks += last - first;   // (the workers have counters of their own)
+        t_auto.estimator_callbacks += last - first;   // (the workers have counters of their own)
         first = last;
     }
     return ok;
@@ -367,8 +283,8 @@ int32_t auto_on_device(int32_t format, const void* d_in, void* d_out, size_t len
     const bool vector_aligned = (reinterpret_cast<uintptr_t>(d_in) & 15) == 0;
     const dxtlt::AutoSections distinct = dxtlt::auto_sections((dxtlt::Format)format, use_all, blocks);
     uint8_t* arena = nullptr;
-    if (!t_no_arena && (format >= 4 || vector_aligned))
-        arena = static_cast<uint8_t*>(g_arena.get(format >= 4 ? 2 * len : (size_t)distinct.bytes));
+    if (!t_auto.no_arena && (format >= 4 || vector_aligned))
+        arena = static_cast<uint8_t*>(t_auto.arena.get(format >= 4 ? 2 * len : (size_t)distinct.bytes));
     if (arena != nullptr && format <= 3) {
         // one read of the input -> every distinct section, estimated where it lies
         HIP_TRY(dxtlt::launch_auto_candidates((dxtlt::Format)format, use_all, d_in, arena, blocks, st), "candidate kernel launch");
@@ -405,8 +321,7 @@ int32_t auto_on_device(int32_t format, const void* d_in, void* d_out, size_t len
         if (int32_t rc = enqueue(format, false, d_in, d_out, blocks, dxtlt::Settings{best->mode, best->split_alpha, best->split_colour}, st))
             return rc;
     }
-    std::copy(total, total + o.count, t_last_totals);
-    t_last_total_count = o.count;
+    t_auto.set_last_totals(total, o.count);
     return kOk;
 }
 
@@ -416,32 +331,6 @@ void report(const Candidate& c, dxtlt_host::AutoChoice* choice)
     choice->split_alpha = c.split_alpha;
     choice->split_colour = c.split_colour;
     choice->estimator_error = 0;
-}
-
-// dxtlt_host::transform_auto given the built-in estimator (arguments validated by the caller)
-int32_t auto_builtin_host(int32_t format, const uint8_t* in, uint8_t* out, size_t len, bool use_all, dxtlt_host::AutoChoice* choice)
-{
-    using namespace dxtlt_host;
-    Candidate best = candidates_of(format, use_all).order[0];   // every estimate of an empty buffer is 0: the first candidate stays
-    if (len > 0) {
-        void *d_in = nullptr, *d_out = nullptr;
-        hipStream_t st = nullptr;
-        if (int32_t rc = acquire_staging(len, &d_in, &d_out, &st))
-            return rc;
-        hipError_t e = hipMemcpyAsync(d_in, in, len, hipMemcpyHostToDevice, st);
-        int32_t rc = e == hipSuccess ? auto_on_device(format, d_in, d_out, len, use_all, st, &best) : fail(kDevice, "H2D copy", e);
-        if (rc == kOk && (e = hipMemcpyAsync(out, d_out, len, hipMemcpyDeviceToHost, st)) != hipSuccess)
-            rc = fail(kDevice, "D2H result", e);
-        e = hipStreamSynchronize(st);   // on every exit: the staging buffers and the arena belong to this thread's next call
-        if (rc == kOk && e != hipSuccess)
-            rc = fail(kDevice, "stream synchronize", e);
-        if (rc != kOk) {
-            t_last_total_count = 0;
-            return rc;
-        }
-    }
-    report(best, choice);
-    return kOk;
 }
 }  // namespace
 
@@ -461,8 +350,8 @@ extern "C" int32_t dxtlt_set_auto_estimator_threads_for_this_thread(int32_t cap)
 
 void dxtlt_host::release_auto_thread_arena()
 {
-    g_arena.release();
-    g_stage.release();
+    t_auto.arena.release();
+    t_auto.stage.release();
     release_estimate_thread_counters();
     release_batch_auto_thread_buffers();
 }
@@ -492,26 +381,64 @@ int dxtlt_host::auto_pick(int32_t format, bool use_all, bool per_candidate, cons
     return pick;
 }
 
-void* dxtlt_host::auto_thread_arena(size_t bytes) { return g_arena.get(bytes); }
+dxtlt_host::AutoThreadState& dxtlt_host::auto_state() { return t_auto; }
 
-void dxtlt_host::auto_begin_device_call()
+void dxtlt_host::AutoArena::release()
 {
-    t_last_total_count = 0;
-    t_section_bytes_downloaded = t_estimator_callbacks = 0;
+    if (ptr) (void)hipFree(ptr);
+    ptr = nullptr;
+    cap = 0;
+    device = -1;
 }
 
-bool dxtlt_host::auto_arena_disabled() { return t_no_arena; }
-
-void dxtlt_host::auto_set_last_totals(const uint64_t* totals, int count)
+void* dxtlt_host::AutoArena::get(size_t bytes)
 {
-    t_last_total_count = std::min(count, 24);
-    std::copy(totals, totals + t_last_total_count, t_last_totals);
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess)
+        return nullptr;
+    if (dev != device || bytes > cap) {
+        release();
+        if (hipMalloc(&ptr, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            ptr = nullptr;
+            return nullptr;
+        }
+        cap = bytes;
+        device = dev;
+    }
+    return ptr;
 }
 
-void dxtlt_host::auto_count_estimation(uint64_t section_bytes_downloaded, uint64_t estimator_callbacks)
+void dxtlt_host::AutoHostStage::release()
 {
-    t_section_bytes_downloaded += section_bytes_downloaded;
-    t_estimator_callbacks += estimator_callbacks;
+    if (ptr) (void)hipHostFree(ptr);
+    ptr = nullptr;
+    cap = 0;
+}
+
+void* dxtlt_host::AutoHostStage::get(size_t bytes)
+{
+    if (bytes > cap) {
+        release();
+        if (hipHostMalloc(&ptr, bytes, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            ptr = nullptr;
+            return nullptr;
+        }
+        cap = bytes;
+    }
+    return ptr;
+}
+
+int32_t dxtlt_host::auto_device_preconditions(hipStream_t stream)
+{
+    int count = 0;
+    hipError_t e = hipGetDeviceCount(&count);
+    if (e != hipSuccess || count <= 0)
+        return fail(kNoDevice, "no HIP device available (this library has no CPU fallback)", e);
+    if (stream_is_capturing(stream))
+        return fail(kInvalidArgument, "the auto transforms read their estimates back and wait for the stream: not capturable");
+    return kOk;
 }
 
 // Where the sections of the callback flow's candidates come from, and with them how the winner reaches the output.
@@ -525,7 +452,7 @@ enum class Source {
 int32_t dxtlt_host::transform_auto(int32_t format, const uint8_t* in, uint8_t* out, size_t len,
                                    const DltSizeEstimator* est, bool use_all, AutoChoice* choice)
 {
-    t_last_total_count = 0;   // whatever this call does next: no totals of an earlier one
+    t_auto.last_total_count = 0;   // whatever this call does next: no totals of an earlier one
     if (format < 1 || format > 5)
         return fail(kInvalidArgument, "format must be 1..5 (BC1..BC5)");
     const size_t block = format == 1 || format == 4 ? 8 : 16;
@@ -537,9 +464,21 @@ int32_t dxtlt_host::transform_auto(int32_t format, const uint8_t* in, uint8_t* o
         return fail(kInvalidArgument, "NULL buffer with len > 0");
     use_all = use_all && format <= 3;
 
-    t_section_bytes_downloaded = t_estimator_callbacks = 0;
-    if (is_builtin_estimator(est))
-        return auto_builtin_host(format, in, out, len, use_all, choice);
+    t_auto.section_bytes_downloaded = t_auto.estimator_callbacks = 0;
+    if (is_builtin_estimator(est)) {   // never called: one upload, everything on the device, one download
+        Candidate best = candidates_of(format, use_all).order[0];   // every estimate of an empty buffer is 0: the first candidate stays
+        if (len > 0) {
+            const int32_t rc = auto_staged_call(in, out, len, [&](const void* d_in, void* d_out, hipStream_t st) {
+                return auto_on_device(format, d_in, d_out, len, use_all, st, &best);
+            });
+            if (rc != kOk) {
+                t_auto.last_total_count = 0;
+                return rc;
+            }
+        }
+        report(best, choice);
+        return kOk;
+    }
 
     const uint64_t blocks = len / block;
     const Order o = candidates_of(format, use_all);
@@ -553,7 +492,7 @@ int32_t dxtlt_host::transform_auto(int32_t format, const uint8_t* in, uint8_t* o
     size_t max_comp = 0;   // one query: len/2 for BC1, len/4 for BC2 / BC3, 2N for BC4 / BC5 -- the longest section shown
     if (uint32_t bad = call_max(est, std::max(shown.len[0], shown.len[1]), &max_comp))
         return fail_estimate(bad, "size estimator: max_compressed_size failed");
-    HostScratch scratch;
+    EstimatorScratch scratch;
     if (!scratch.allocate(max_comp))
         return fail(kAllocation, "estimator scratch allocation failed");
 
@@ -567,14 +506,14 @@ int32_t dxtlt_host::transform_auto(int32_t format, const uint8_t* in, uint8_t* o
             return rc;
         drain.armed = true;
         HIP_TRY(hipMemcpyAsync(d_in, in, len, hipMemcpyHostToDevice, st), "H2D copy");
-        if (format >= 4 && !t_no_arena) {
-            arena = static_cast<uint8_t*>(g_arena.get(2 * len));
+        if (format >= 4 && !t_auto.no_arena) {
+            arena = static_cast<uint8_t*>(t_auto.arena.get(2 * len));
             for (int i = 0; i < o.count && arena != nullptr; ++i)
                 if (int32_t rc = enqueue(format, false, d_in, arena + (size_t)i * len, blocks, dxtlt::Settings{0, o.order[i].split_alpha, false}, st))
                     return rc;
-        } else if (format <= 3 && !t_no_arena) {
+        } else if (format <= 3 && !t_auto.no_arena) {
             distinct = dxtlt::auto_sections((dxtlt::Format)format, use_all, blocks);
-            arena = static_cast<uint8_t*>(g_arena.get((size_t)distinct.bytes));
+            arena = static_cast<uint8_t*>(t_auto.arena.get((size_t)distinct.bytes));
             if (arena != nullptr)
                 HIP_TRY(dxtlt::launch_auto_candidates((dxtlt::Format)format, use_all, d_in, arena, blocks, st), "candidate kernel launch");
         }
@@ -630,7 +569,7 @@ int32_t dxtlt_host::transform_auto(int32_t format, const uint8_t* in, uint8_t* o
         const size_t slot_bytes = second + ((shown.len[shown.count - 1] + 255) & ~size_t(255));
         uint8_t* stage = nullptr;
         if (source == Source::kFused && slot_bytes <= kStageCapBytes)
-            stage = static_cast<uint8_t*>(g_stage.get(2 * slot_bytes));
+            stage = static_cast<uint8_t*>(t_auto.stage.get(2 * slot_bytes));
         auto download = [&](int i, uint8_t* first_to, uint8_t* second_to) -> hipError_t {
             hipError_t e = download_section(first_to, device_section(i, 0), shown.len[0], st);
             if (e == hipSuccess && shown.count == 2)
@@ -693,7 +632,7 @@ int32_t dxtlt_host::transform_auto(int32_t format, const uint8_t* in, uint8_t* o
 int32_t dxtlt_host::transform_auto_device(int32_t format, const void* d_in, void* d_out, size_t len, bool use_all, hipStream_t st,
                                           AutoChoice* choice)
 {
-    t_last_total_count = 0;   // whatever this call does next: no totals of an earlier one
+    t_auto.last_total_count = 0;   // whatever this call does next: no totals of an earlier one
     if (format < 1 || format > 5)
         return fail(kInvalidArgument, "format must be 1..5 (BC1..BC5)");
     if (len % (format == 1 || format == 4 ? 8 : 16) != 0)
@@ -702,21 +641,12 @@ int32_t dxtlt_host::transform_auto_device(int32_t format, const void* d_in, void
         return fail(kInvalidArgument, "NULL choice");
     if (len > 0 && (d_in == nullptr || d_out == nullptr))
         return fail(kInvalidArgument, "NULL buffer with len > 0");
-    t_section_bytes_downloaded = t_estimator_callbacks = 0;
+    t_auto.section_bytes_downloaded = t_auto.estimator_callbacks = 0;
     use_all = use_all && format <= 3;
     Candidate best = candidates_of(format, use_all).order[0];
-    if (len > 0) {
-        int count = 0;
-        hipError_t e = hipGetDeviceCount(&count);
-        if (e != hipSuccess || count <= 0)
-            return fail(kNoDevice, "no HIP device available (this library has no CPU fallback)", e);
-        if (stream_is_capturing(st))
-            return fail(kInvalidArgument, "the auto transforms read their estimates back and wait for the stream: not capturable");
-        if (int32_t rc = auto_on_device(format, d_in, d_out, len, use_all, st, &best)) {
-            (void)hipStreamSynchronize(st);   // the arena belongs to this thread's next call
+    if (len > 0)
+        if (int32_t rc = auto_device_call(st, [&] { return auto_on_device(format, d_in, d_out, len, use_all, st, &best); }))
             return rc;
-        }
-    }
     report(best, choice);
     return kOk;
 }
@@ -727,9 +657,9 @@ namespace {
 int32_t store_choice(int32_t rc, const dxtlt_host::AutoChoice& c, uint8_t* mode, bool* split_alpha, bool* split_colour)
 {
     if (rc == DXTLT_OK) {
-        if (mode) *mode = c.mode;
-        if (split_alpha) *split_alpha = c.split_alpha;
-        if (split_colour) *split_colour = c.split_colour;
+        dxtlt_host::store_if(mode, c.mode);
+        dxtlt_host::store_if(split_alpha, c.split_alpha);
+        dxtlt_host::store_if(split_colour, c.split_colour);
     }
     return rc;
 }
@@ -740,7 +670,7 @@ int32_t auto_host(int32_t format, const uint8_t* in, uint8_t* out, size_t len, c
     dxtlt_host::AutoChoice c{};
     const int32_t rc = dxtlt_host::transform_auto(format, in, out, len, estimator, use_all, &c);
     t_last_estimator_error = c.estimator_error;
-    if (estimator_error) *estimator_error = c.estimator_error;
+    dxtlt_host::store_if(estimator_error, c.estimator_error);
     return store_choice(rc, c, mode, split_alpha, split_colour);
 }
 
@@ -833,18 +763,18 @@ int32_t dxtlt_transform_bc5_auto_device(const void* d_input, void* d_output, siz
 
 void dxtlt_debug_auto_last_estimation(uint64_t* out_section_bytes_downloaded, uint64_t* out_estimator_callbacks)
 {
-    if (out_section_bytes_downloaded) *out_section_bytes_downloaded = t_section_bytes_downloaded;
-    if (out_estimator_callbacks) *out_estimator_callbacks = t_estimator_callbacks;
+    dxtlt_host::store_if(out_section_bytes_downloaded, t_auto.section_bytes_downloaded);
+    dxtlt_host::store_if(out_estimator_callbacks, t_auto.estimator_callbacks);
 }
 
 int32_t dxtlt_debug_auto_last_totals(uint64_t* out_totals, int32_t cap)
 {
-    for (int i = 0; out_totals != nullptr && i < t_last_total_count && i < cap; ++i)
-        out_totals[i] = t_last_totals[i];
-    return t_last_total_count;
+    for (int i = 0; out_totals != nullptr && i < t_auto.last_total_count && i < cap; ++i)
+        out_totals[i] = t_auto.last_totals[i];
+    return t_auto.last_total_count;
 }
 
-void dxtlt_debug_auto_use_arena(int32_t on) { t_no_arena = on == 0; }
+void dxtlt_debug_auto_use_arena(int32_t on) { t_auto.no_arena = on == 0; }
 
 uint32_t dxtlt_debug_auto_last_estimator_error(void) { return t_last_estimator_error; }
 
@@ -855,7 +785,7 @@ int32_t dxtlt_debug_auto_candidates_device(int32_t format, bool use_all_decorrel
     if (format < 1 || format > 3 || d_input == nullptr || len == 0 || len % (format == 1 ? 8 : 16) != 0)
         return fail(kInvalidArgument, "format 1..3, a non-empty whole number of blocks");
     const uint64_t blocks = len / (format == 1 ? 8 : 16);
-    void* arena = g_arena.get((size_t)dxtlt::auto_sections((dxtlt::Format)format, use_all_decorrelation_modes, blocks).bytes);
+    void* arena = t_auto.arena.get((size_t)dxtlt::auto_sections((dxtlt::Format)format, use_all_decorrelation_modes, blocks).bytes);
     if (arena == nullptr)
         return fail(kDevice, "candidate arena allocation failed", hipErrorOutOfMemory);
     HIP_TRY(dxtlt::launch_auto_candidates((dxtlt::Format)format, use_all_decorrelation_modes, d_input, arena, blocks,

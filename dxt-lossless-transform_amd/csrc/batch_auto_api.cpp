@@ -17,7 +17,7 @@
 #include "../../include/dxtlt_gfx950.h"
 #include "batch_auto_plan.h"
 #include "estimate_launch.h"
-#include "host_common.h"
+#include "auto_call.h"
 
 namespace {
 
@@ -57,7 +57,7 @@ uint64_t dxtlt_host::batch_auto_arena_cap() { return t_arena_cap ? t_arena_cap :
 extern "C" int32_t dxtlt_transform_batch_auto_device(DxtltBatchAutoItem* items, size_t count, void* hip_stream)
 {
     t_debug.begin_call();
-    auto_begin_device_call();
+    auto_state().begin_call();
     if (count == 0)
         return kOk;
     ba::Plan plan;
@@ -84,7 +84,7 @@ extern "C" int32_t dxtlt_transform_batch_auto_device(DxtltBatchAutoItem* items, 
         return kOk;
     }
 
-    uint8_t* arena = static_cast<uint8_t*>(auto_thread_arena((size_t)plan.arena_bytes));
+    uint8_t* arena = static_cast<uint8_t*>(auto_state().arena.get((size_t)plan.arena_bytes));
     if (arena == nullptr)
         return fail(kDevice, "candidate arena allocation failed", hipErrorOutOfMemory);
     HIP_TRY(g_buffers.reserve(plan.table_bytes, (size_t)plan.counters), "batch auto tables / counters");

@@ -205,32 +205,20 @@ int auto_candidate_order(int32_t format, bool use_all_decorrelation_modes, AutoC
 // and the pick, the first minimum of the order (strict `<`).  sizes: the distinct sections in dxtlt::auto_sections' order (auto_launch.h)
 // or, per_candidate, two slots per candidate (BC4 / BC5 on the single-buffer route, every format without the arena).
 int auto_pick(int32_t format, bool use_all_decorrelation_modes, bool per_candidate, const uint64_t* sizes, uint64_t* total);
-// This thread's candidate arena on the current device, grown to at least `bytes`; nullptr when it cannot be allocated.
-void* auto_thread_arena(size_t bytes);
-// An auto call that downloads no section and makes no callback begins: dxtlt_debug_auto_last_estimation reports (0, 0) and
-// dxtlt_debug_auto_last_totals nothing until the next single-buffer call.
-void auto_begin_device_call();
 void release_batch_auto_thread_buffers();   // batch_auto_api.cpp; through release_auto_thread_arena()
-// For the auto calls of other translation units (pixel_auto_api.cpp): whether dxtlt_debug_auto_use_arena(0) is in force on this
-// thread, and what a callback route adds to the figures of dxtlt_debug_auto_last_estimation.
-bool auto_arena_disabled();
-void auto_count_estimation(uint64_t section_bytes_downloaded, uint64_t estimator_callbacks);
-// what dxtlt_debug_auto_last_totals reports from now on: the `count` (at most 24) totals a device route of another translation
-// unit compared, in its candidate order
-void auto_set_last_totals(const uint64_t* totals, int count);
+// (the frame of the single-buffer auto calls and this thread's auto state: auto_call.h)
 
-// ---- auto_normalize_api.cpp: transform_bcN_auto_with_normalization on the device (include/dxtlt_auto_normalize.h) ----
-struct AutoNormalizeChoice {
-    uint8_t norm;   // ColorNormalizationMode
-    uint8_t mode;   // core numbering
-    bool split_colour;
+// ---- normalize_api.cpp, auto_normalize_api.cpp: block normalisation, alone, fused and in the auto transform ----
+// What the calls need to know about a format; its legal modes are dxtlt::norm_limits (bcn_launch.h)
+struct NormFormat {
+    int fmt;
+    size_t block_bytes;
+    int all_modes_outputs;   // one per (alpha mode, colour mode), [alpha_mode * 3 + colour_mode]
+    const char* bad_len;
 };
-// format 1 or 2, device pointers, the built-in estimator; the arguments are valid and len > 0.  Two waits for `stream` (the flag,
-// the counters); the winner's fused normalise + transform launch is left enqueued.  When it returns, successful or not, nothing in
-// flight uses this thread's flag word, arena or counters.
-int32_t auto_normalize_on_device(int32_t format, const void* d_in, void* d_out, size_t len, bool use_all_decorrelation_modes,
-                                 hipStream_t stream, AutoNormalizeChoice* choice);
-// normalize_api.cpp: this thread's flag word on the current device, zeroed on `stream`
+inline constexpr NormFormat kNormBc1{1, 8, 3, "len is not a multiple of 8"}, kNormBc2{2, 16, 3, "len is not a multiple of 16"},
+    kNormBc3{3, 16, 12, "len is not a multiple of 16"};
+// normalize_api.cpp: this thread's flag word ("any block normalised") on the current device, zeroed on `stream`
 int32_t normalize_thread_flag(uint32_t** d_flag, hipStream_t stream);
 
 // ---- estimate_api.cpp: the built-in estimator (include/dxtlt_estimator.h) -----------------------------------------

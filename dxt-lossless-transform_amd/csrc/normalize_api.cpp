@@ -3,54 +3,28 @@
 // src/experimental/normalize_blocks/{normalize.rs, transform.rs}, on the device.  Host-pointer calls stage through the calling
 // thread's device buffers (H2D, kernel, D2H, synchronous).  What every call answers to defective arguments, and in which order,
 // is pinned by tests/test_normalize_defects.py.
-//
-// transform_bc1_auto_with_normalization (transform.rs:222-333) as the reference runs it:
-//   * one max_compressed_size(len / 2) query up front (its failure is the only estimator error that propagates);
-//   * all blocks are classified once; if no block would change, the call IS transform_bc1_auto;
-//   * otherwise for mode in {None, Color0Only, ReplicateColor}, for (decorrelation, split) in the BC1 test order:
-//     the estimator sees the first len / 2 bytes (the colour section) of transform(normalize(input, mode));
-//     a failing estimate skips that candidate; strict `<` against the running best, which starts at
-//     {None, Variant1, split} with size usize::MAX;
-//   * the data is transformed once more with the winner.
-// GPU shape: the input is uploaded once; the classification is a read-only kernel that sets a flag; every candidate is
-// one fused normalise+transform launch on the resident copy and only its colour section travels back.  BC2 has the same call
-// (this build's extension: the colour section is [len / 2, + len / 4), the `None` candidates are the input's own colours).  Given
-// the built-in estimator both run the device flow of auto_normalize_api.cpp instead: no section travels and no callback is made.
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
 #include <cstring>
-#include <memory>
 
-#include "../../include/dxtlt_auto_normalize.h"
 #include "../../include/dxtlt_bc1_normalize.h"
 #include "../../include/dxtlt_bc23_normalize.h"
-#include "../../include/dxtlt_estimator.h"
 #include "../../include/dxtlt_gfx950.h"
-#include "auto_launch.h"
 #include "bcn_launch.h"
 #include "host_common.h"
 
 using dxtlt::Settings;
 using dxtlt_host::fail;
-using dxtlt_host::kAllocation;
-using dxtlt_host::kDevice;
-using dxtlt_host::kEstimator;
 using dxtlt_host::kInvalidArgument;
 using dxtlt_host::kInvalidLength;
 using dxtlt_host::kOk;
 
 namespace {
 
-// What the calls below need to know about a format; its legal modes are dxtlt::norm_limits (bcn_launch.h)
-struct NormFormat {
-    int fmt;
-    size_t block_bytes;
-    int all_modes_outputs;   // one per (alpha mode, colour mode), [alpha_mode * 3 + colour_mode]
-    const char* bad_len;
-};
-constexpr NormFormat kBc1{1, 8, 3, "len is not a multiple of 8"}, kBc2{2, 16, 3, "len is not a multiple of 16"},
-    kBc3{3, 16, 12, "len is not a multiple of 16"};
+using dxtlt_host::NormFormat;
+using dxtlt_host::kNormBc1;
+using dxtlt_host::kNormBc2;
+using dxtlt_host::kNormBc3;
 
 int32_t check_modes(const NormFormat& F, uint8_t alpha_mode, uint8_t color_mode)
 {
@@ -305,158 +279,6 @@ int32_t fused_device(const NormFormat& F, const void* d_in, void* d_out, size_t 
     return dxtlt_host::enqueue(F.fmt, false, d_in, d_out, len / F.block_bytes, s, static_cast<hipStream_t>(stream));
 }
 
-hipError_t launch_any_normalizable(const NormFormat& F, const void* d_in, size_t len, uint32_t* d_flag, hipStream_t st)
-{
-    return F.fmt == 1 ? dxtlt::launch_bc1_any_normalizable(d_in, len / 8, d_flag, st) : dxtlt::launch_bc2_any_normalizable(d_in, len / 16, d_flag, st);
-}
-
-// the built-in estimator (arguments validated by the caller): nothing but the input and the result crosses PCIe, no callback
-int32_t auto_with_normalization_builtin(const NormFormat& F, const uint8_t* in, uint8_t* out, size_t len, bool use_all, uint8_t* out_color_mode,
-                                        uint8_t* out_decorrelation_mode, bool* out_split_colour_endpoints)
-{
-    dxtlt_host::AutoNormalizeChoice c{DXTLT_NORMALIZE_NONE, 0, false};
-    if (len == 0) {
-        dxtlt_host::AutoChoice plain{};
-        if (int32_t rc = dxtlt_host::transform_auto(F.fmt, in, out, 0, dxtlt_builtin_size_estimator(), use_all, &plain); rc != kOk)
-            return rc;
-        c = {DXTLT_NORMALIZE_NONE, plain.mode, plain.split_colour};
-    } else {
-        void *d_in = nullptr, *d_out = nullptr;
-        hipStream_t st = nullptr;
-        if (int32_t rc = dxtlt_host::acquire_staging(len, &d_in, &d_out, &st); rc != kOk)
-            return rc;
-        hipError_t e = hipMemcpyAsync(d_in, in, len, hipMemcpyHostToDevice, st);
-        int32_t rc = e == hipSuccess ? dxtlt_host::auto_normalize_on_device(F.fmt, d_in, d_out, len, use_all, st, &c) : fail(kDevice, "H2D copy", e);
-        if (rc == kOk && (e = hipMemcpyAsync(out, d_out, len, hipMemcpyDeviceToHost, st)) != hipSuccess)
-            rc = fail(kDevice, "D2H result", e);
-        e = hipStreamSynchronize(st);   // on every exit: the staging buffers belong to this thread's next call
-        if (rc == kOk && e != hipSuccess)
-            rc = fail(kDevice, "stream synchronize", e);
-        if (rc != kOk)
-            return rc;
-    }
-    if (out_color_mode) *out_color_mode = c.norm;
-    if (out_decorrelation_mode) *out_decorrelation_mode = c.mode;
-    if (out_split_colour_endpoints) *out_split_colour_endpoints = c.split_colour;
-    return kOk;
-}
-
-// ---- transform_bcN_auto_with_normalization on host pointers, BC1 and BC2 (the header comment of this file; BC2: this build's
-// extension, include/dxtlt_auto_normalize.h).  The estimator is shown the colour section of a transformed buffer: BC1 [0, len / 2),
-// BC2 [len / 2, + len / 4).  The built-in estimator is recognised and never called: one upload, the device flow of
-// auto_normalize_api.cpp, one download.
-int32_t auto_with_normalization_host(const NormFormat& F, const uint8_t* input_ptr, uint8_t* output_ptr, size_t len,
-                                     const DltSizeEstimator* est, bool use_all, uint8_t* out_color_mode,
-                                     uint8_t* out_decorrelation_mode, bool* out_split_colour_endpoints, uint32_t* out_estimator_error)
-{
-    const size_t shown_off = F.fmt == 1 ? 0 : len / 2, shown_len = F.fmt == 1 ? len / 2 : len / 4;
-    if (out_estimator_error)
-        *out_estimator_error = 0;
-    if (len % F.block_bytes != 0)
-        return fail(kInvalidLength, F.bad_len);
-    if (est == nullptr || est->MaxCompressedSize == nullptr || est->EstimateCompressedSize == nullptr)
-        return fail(kInvalidArgument, "NULL estimator");
-    if (len > 0 && (input_ptr == nullptr || output_ptr == nullptr))
-        return fail(kInvalidArgument, "NULL buffer with len > 0");
-
-    if (dxtlt_host::is_builtin_estimator(est))
-        return auto_with_normalization_builtin(F, input_ptr, output_ptr, len, use_all, out_color_mode, out_decorrelation_mode,
-                                               out_split_colour_endpoints);
-
-    size_t max_comp = 0;
-    if (uint32_t rc_est = est->MaxCompressedSize(est->Context, shown_len, &max_comp); rc_est != 0) {
-        if (out_estimator_error)
-            *out_estimator_error = rc_est;
-        return fail(kEstimator, "size estimator: max_compressed_size failed");
-    }
-
-    // classification pass: would any block change?
-    uint32_t any = 0;
-    void *d_in = nullptr, *d_out = nullptr;
-    hipStream_t st = nullptr;
-    if (len > 0) {
-        if (int32_t rc = dxtlt_host::acquire_staging(len, &d_in, &d_out, &st); rc != kOk)
-            return rc;
-        uint32_t* d_flag = nullptr;
-        if (int32_t rc = g_flag.get(&d_flag, st); rc != kOk)
-            return rc;
-        if (int32_t rc = staged(st, Transfers().add(d_in, input_ptr, len),
-                                [&] { return launch_any_normalizable(F, d_in, len, d_flag, st); },
-                                Transfers().add(d_flag, &any, sizeof(uint32_t), "D2H flag"));
-            rc != kOk)
-            return rc;
-    }
-    if (any == 0) {
-        // transform.rs:321-331: nothing to normalise -> the regular brute force, mode None
-        dxtlt_host::AutoChoice c{};
-        const int32_t rc = dxtlt_host::transform_auto(F.fmt, input_ptr, output_ptr, len, est, use_all, &c);
-        if (out_estimator_error)
-            *out_estimator_error = c.estimator_error;
-        if (rc == kOk) {
-            if (out_color_mode) *out_color_mode = DXTLT_NORMALIZE_NONE;
-            if (out_decorrelation_mode) *out_decorrelation_mode = c.mode;
-            if (out_split_colour_endpoints) *out_split_colour_endpoints = c.split_colour;
-        }
-        return rc;
-    }
-
-    std::unique_ptr<uint8_t, decltype(&std::free)> scratch(nullptr, &std::free);
-    if (max_comp != 0) {
-        scratch.reset(static_cast<uint8_t*>(std::aligned_alloc(64, (max_comp + 63) / 64 * 64)));
-        if (scratch == nullptr)
-            return fail(kAllocation, "estimator scratch allocation failed");
-    }
-    struct Best {
-        uint8_t norm, variant;
-        bool split;
-    } best{DXTLT_NORMALIZE_NONE, 1, true}, last = best;
-    bool last_valid = false;
-    size_t best_size = SIZE_MAX;
-    dxtlt_host::AutoChoice order[16];   // bc1 settings.rs:81-86 (FAST_TEST_ORDER) or :89-98 (COMPREHENSIVE_TEST_ORDER)
-    const int count = dxtlt_host::auto_candidate_order(F.fmt, use_all, order);
-    const uint64_t blocks = len / F.block_bytes;
-    for (uint8_t norm = 0; norm <= DXTLT_NORMALIZE_REPLICATE_COLOR; ++norm) {
-        // BC1: the reference estimates on the buffers of normalize_blocks_all_modes, whose `None` buffer still has its
-        // fully transparent blocks rewritten (normalize.rs:447-454): internal fused mode 3 reproduces that
-        const uint8_t fused = (uint8_t)dxtlt::norm_estimation_mode(F.fmt, norm);
-        for (int i = 0; i < count; ++i) {
-            if (int32_t rc = dxtlt_host::enqueue(F.fmt, false, d_in, d_out, blocks, Settings{order[i].mode, false, order[i].split_colour, fused}, st);
-                rc != kOk)
-                return rc;
-            hipError_t herr = hipMemcpyAsync(output_ptr + shown_off, static_cast<const uint8_t*>(d_out) + shown_off, shown_len, hipMemcpyDeviceToHost, st);
-            if (herr == hipSuccess)
-                herr = hipStreamSynchronize(st);
-            if (herr != hipSuccess)
-                return fail(kDevice, "candidate transform / download", herr);
-            last = {norm, order[i].mode, order[i].split_colour};
-            last_valid = true;
-            size_t size = 0;
-            if (est->EstimateCompressedSize(est->Context, output_ptr + shown_off, shown_len, scratch.get(), max_comp, &size) != 0)
-                continue;   // transform.rs:403: a failing estimate skips the candidate
-            if (size < best_size) {
-                best_size = size;
-                best = last;
-            }
-        }
-    }
-
-    // the final transform uses the chosen mode as transform_bc1_with_normalize_blocks defines it (transform.rs:307-313),
-    // so a `None` winner is re-run without the transparent rewrite its candidates were estimated with
-    const bool resident = last_valid && dxtlt::norm_estimation_mode(F.fmt, best.norm) == best.norm && last.norm == best.norm &&
-                          last.variant == best.variant && last.split == best.split;
-    if (!resident) {
-        if (int32_t rc = dxtlt_host::enqueue(F.fmt, false, d_in, d_out, blocks, Settings{best.variant, false, best.split, best.norm}, st);
-            rc != kOk)
-            return rc;
-    }
-    HIP_TRY(hipMemcpyAsync(output_ptr, d_out, len, hipMemcpyDeviceToHost, st), "D2H result");
-    HIP_TRY(hipStreamSynchronize(st), "stream synchronize");
-    if (out_color_mode) *out_color_mode = best.norm;
-    if (out_decorrelation_mode) *out_decorrelation_mode = best.variant;
-    if (out_split_colour_endpoints) *out_split_colour_endpoints = best.split;
-    return kOk;
-}
-
 }  // namespace
 
 int32_t dxtlt_host::normalize_thread_flag(uint32_t** d_flag, hipStream_t stream) { return g_flag.get(d_flag, stream); }
@@ -473,134 +295,116 @@ extern "C" {
 // ---- BC1 (include/dxtlt_bc1_normalize.h) ----------------------------------------------------------------------------
 int32_t dxtlt_bc1_normalize_blocks(const uint8_t* i, uint8_t* o, size_t len, uint8_t color_mode)
 {
-    return blocks_host(kBc1, i, o, len, 0, color_mode);
+    return blocks_host(kNormBc1, i, o, len, 0, color_mode);
 }
 int32_t dxtlt_bc1_normalize_blocks_device(const void* i, void* o, size_t len, uint8_t color_mode, void* st)
 {
-    return blocks_device(kBc1, i, o, len, 0, color_mode, st);
+    return blocks_device(kNormBc1, i, o, len, 0, color_mode, st);
 }
 int32_t dxtlt_bc1_normalize_split_blocks_in_place(uint8_t* colors_ptr, uint8_t* indices_ptr, size_t num_blocks, uint8_t color_mode)
 {
-    return split2_host(kBc1, colors_ptr, indices_ptr, num_blocks, color_mode);
+    return split2_host(kNormBc1, colors_ptr, indices_ptr, num_blocks, color_mode);
 }
 int32_t dxtlt_bc1_normalize_split_blocks_in_place_device(void* d_colors, void* d_indices, size_t num_blocks, uint8_t color_mode,
                                                          void* st)
 {
-    return split2_device(kBc1, d_colors, d_indices, num_blocks, color_mode, st);
+    return split2_device(kNormBc1, d_colors, d_indices, num_blocks, color_mode, st);
 }
 int32_t dxtlt_bc1_normalize_blocks_all_modes(const uint8_t* i, uint8_t* const o[3], size_t len, bool* out_any_normalized)
 {
-    return all_modes_host(kBc1, i, o, len, out_any_normalized);
+    return all_modes_host(kNormBc1, i, o, len, out_any_normalized);
 }
 int32_t dxtlt_bc1_normalize_blocks_all_modes_device(const void* i, void* const o[3], size_t len, uint32_t* d_any_normalized,
                                                     void* st)
 {
-    return all_modes_device(kBc1, i, o, len, d_any_normalized, st);
+    return all_modes_device(kNormBc1, i, o, len, d_any_normalized, st);
 }
 int32_t dxtlt_transform_bc1_with_normalize_blocks(const uint8_t* i, uint8_t* o, uint8_t* work_ptr, size_t len, uint8_t color_mode,
                                                   uint8_t decorrelation_mode, bool split_colour_endpoints)
 {
     (void)work_ptr;  // the reference's CPU scratch buffer; the fused kernel needs none
-    return fused_host(kBc1, i, o, len, Settings{decorrelation_mode, false, split_colour_endpoints, color_mode});
+    return fused_host(kNormBc1, i, o, len, Settings{decorrelation_mode, false, split_colour_endpoints, color_mode});
 }
 int32_t dxtlt_transform_bc1_with_normalize_blocks_device(const void* i, void* o, size_t len, uint8_t color_mode,
                                                          uint8_t decorrelation_mode, bool split_colour_endpoints, void* st)
 {
-    return fused_device(kBc1, i, o, len, Settings{decorrelation_mode, false, split_colour_endpoints, color_mode}, st);
-}
-
-int32_t dxtlt_transform_bc1_auto_with_normalization(const uint8_t* input_ptr, uint8_t* output_ptr, size_t len,
-                                                    const DltSizeEstimator* est, bool use_all, uint8_t* out_color_mode,
-                                                    uint8_t* out_decorrelation_mode, bool* out_split_colour_endpoints,
-                                                    uint32_t* out_estimator_error)
-{
-    return auto_with_normalization_host(kBc1, input_ptr, output_ptr, len, est, use_all, out_color_mode, out_decorrelation_mode,
-                                        out_split_colour_endpoints, out_estimator_error);
-}
-
-int32_t dxtlt_transform_bc2_auto_with_normalization(const uint8_t* input_ptr, uint8_t* output_ptr, size_t len,
-                                                    const DltSizeEstimator* est, bool use_all, uint8_t* out_color_mode,
-                                                    uint8_t* out_decorrelation_mode, bool* out_split_colour_endpoints,
-                                                    uint32_t* out_estimator_error)
-{
-    return auto_with_normalization_host(kBc2, input_ptr, output_ptr, len, est, use_all, out_color_mode, out_decorrelation_mode,
-                                        out_split_colour_endpoints, out_estimator_error);
+    return fused_device(kNormBc1, i, o, len, Settings{decorrelation_mode, false, split_colour_endpoints, color_mode}, st);
 }
 
 // ---- BC2 / BC3 (include/dxtlt_bc23_normalize.h) ---------------------------------------------------------------------
 int32_t dxtlt_bc2_normalize_blocks(const uint8_t* i, uint8_t* o, size_t len, uint8_t color_mode)
 {
-    return blocks_host(kBc2, i, o, len, 0, color_mode);
+    return blocks_host(kNormBc2, i, o, len, 0, color_mode);
 }
 int32_t dxtlt_bc3_normalize_blocks(const uint8_t* i, uint8_t* o, size_t len, uint8_t alpha_mode, uint8_t color_mode)
 {
-    return blocks_host(kBc3, i, o, len, alpha_mode, color_mode);
+    return blocks_host(kNormBc3, i, o, len, alpha_mode, color_mode);
 }
 int32_t dxtlt_bc2_normalize_blocks_device(const void* i, void* o, size_t len, uint8_t color_mode, void* st)
 {
-    return blocks_device(kBc2, i, o, len, 0, color_mode, st);
+    return blocks_device(kNormBc2, i, o, len, 0, color_mode, st);
 }
 int32_t dxtlt_bc3_normalize_blocks_device(const void* i, void* o, size_t len, uint8_t alpha_mode, uint8_t color_mode, void* st)
 {
-    return blocks_device(kBc3, i, o, len, alpha_mode, color_mode, st);
+    return blocks_device(kNormBc3, i, o, len, alpha_mode, color_mode, st);
 }
 int32_t dxtlt_bc2_normalize_blocks_all_modes(const uint8_t* i, uint8_t* const o[3], size_t len)
 {
-    return all_modes_host(kBc2, i, o, len, nullptr);
+    return all_modes_host(kNormBc2, i, o, len, nullptr);
 }
 int32_t dxtlt_bc3_normalize_blocks_all_modes(const uint8_t* i, uint8_t* const o[12], size_t len)
 {
-    return all_modes_host(kBc3, i, o, len, nullptr);
+    return all_modes_host(kNormBc3, i, o, len, nullptr);
 }
 int32_t dxtlt_bc2_normalize_blocks_all_modes_device(const void* i, void* const o[3], size_t len, void* st)
 {
-    return all_modes_device(kBc2, i, o, len, nullptr, st);
+    return all_modes_device(kNormBc2, i, o, len, nullptr, st);
 }
 int32_t dxtlt_bc3_normalize_blocks_all_modes_device(const void* i, void* const o[12], size_t len, void* st)
 {
-    return all_modes_device(kBc3, i, o, len, nullptr, st);
+    return all_modes_device(kNormBc3, i, o, len, nullptr, st);
 }
 
 int32_t dxtlt_transform_bc2_with_normalize_blocks(const uint8_t* i, uint8_t* o, size_t len, uint8_t color_mode,
                                                   uint8_t decorrelation_mode, bool split_colour_endpoints)
 {
-    return fused_host(kBc2, i, o, len, Settings{decorrelation_mode, false, split_colour_endpoints, color_mode});
+    return fused_host(kNormBc2, i, o, len, Settings{decorrelation_mode, false, split_colour_endpoints, color_mode});
 }
 int32_t dxtlt_transform_bc2_with_normalize_blocks_device(const void* i, void* o, size_t len, uint8_t color_mode,
                                                          uint8_t decorrelation_mode, bool split_colour_endpoints, void* st)
 {
-    return fused_device(kBc2, i, o, len, Settings{decorrelation_mode, false, split_colour_endpoints, color_mode}, st);
+    return fused_device(kNormBc2, i, o, len, Settings{decorrelation_mode, false, split_colour_endpoints, color_mode}, st);
 }
 int32_t dxtlt_transform_bc3_with_normalize_blocks(const uint8_t* i, uint8_t* o, size_t len, uint8_t alpha_mode, uint8_t color_mode,
                                                   uint8_t decorrelation_mode, bool split_alpha_endpoints,
                                                   bool split_colour_endpoints)
 {
-    return fused_host(kBc3, i, o, len, Settings{decorrelation_mode, split_alpha_endpoints, split_colour_endpoints, color_mode, alpha_mode});
+    return fused_host(kNormBc3, i, o, len, Settings{decorrelation_mode, split_alpha_endpoints, split_colour_endpoints, color_mode, alpha_mode});
 }
 int32_t dxtlt_transform_bc3_with_normalize_blocks_device(const void* i, void* o, size_t len, uint8_t alpha_mode, uint8_t color_mode,
                                                          uint8_t decorrelation_mode, bool split_alpha_endpoints,
                                                          bool split_colour_endpoints, void* st)
 {
-    return fused_device(kBc3, i, o, len, Settings{decorrelation_mode, split_alpha_endpoints, split_colour_endpoints, color_mode, alpha_mode},
+    return fused_device(kNormBc3, i, o, len, Settings{decorrelation_mode, split_alpha_endpoints, split_colour_endpoints, color_mode, alpha_mode},
                         st);
 }
 
 int32_t dxtlt_bc2_normalize_split_blocks_in_place_device(void* d_colors, void* d_indices, size_t num_blocks, uint8_t color_mode,
                                                          void* st)
 {
-    return split2_device(kBc2, d_colors, d_indices, num_blocks, color_mode, st);
+    return split2_device(kNormBc2, d_colors, d_indices, num_blocks, color_mode, st);
 }
 int32_t dxtlt_bc2_normalize_split_blocks_in_place(const uint8_t* alpha_ptr, uint8_t* colors_ptr, uint8_t* indices_ptr,
                                                   size_t num_blocks, uint8_t color_mode)
 {
     (void)alpha_ptr;   // the colour decision ignores alpha (bc2 normalize.rs:131-150)
-    return split2_host(kBc2, colors_ptr, indices_ptr, num_blocks, color_mode);
+    return split2_host(kNormBc2, colors_ptr, indices_ptr, num_blocks, color_mode);
 }
 
 int32_t dxtlt_bc3_normalize_split_blocks_in_place_device(void* d_aep, void* d_aidx, void* d_cep, void* d_cidx, size_t num_blocks,
                                                          uint8_t alpha_mode, uint8_t color_mode, void* st)
 {
-    if (int32_t rc = check_modes(kBc3, alpha_mode, color_mode); rc != kOk)
+    if (int32_t rc = check_modes(kNormBc3, alpha_mode, color_mode); rc != kOk)
         return rc;
     if (num_blocks > 0 && (d_aep == nullptr || d_aidx == nullptr || d_cep == nullptr || d_cidx == nullptr))
         return fail(kInvalidArgument, "NULL device buffer with num_blocks > 0");
@@ -613,7 +417,7 @@ int32_t dxtlt_bc3_normalize_split_blocks_in_place_device(void* d_aep, void* d_ai
 int32_t dxtlt_bc3_normalize_split_blocks_in_place(uint8_t* aep, uint8_t* aidx, uint8_t* cep, uint8_t* cidx, size_t num_blocks,
                                                   uint8_t alpha_mode, uint8_t color_mode)
 {
-    if (int32_t rc = check_modes(kBc3, alpha_mode, color_mode); rc != kOk)
+    if (int32_t rc = check_modes(kNormBc3, alpha_mode, color_mode); rc != kOk)
         return rc;
     if (num_blocks == 0 || (alpha_mode == 0 && color_mode == 0))
         return kOk;

@@ -14,11 +14,9 @@
 // the other and the callbacks made in candidate order, as auto_transform.cpp does it.
 #include <hip/hip_runtime_api.h>
 
-#include <cstdlib>
-
 #include "../../include/dxtlt_entropy_estimator.h"
 #include "../../include/dxtlt_pixels.h"
-#include "host_common.h"
+#include "auto_call.h"
 #include "pixel_launch.h"
 
 namespace {
@@ -87,8 +85,8 @@ int32_t auto_on_device(int B, const void* d_in, void* d_out, size_t len, hipStre
 {
     const uint64_t pixels = len / (size_t)B;
     uint8_t* arena = nullptr;
-    if (!auto_arena_disabled() && (reinterpret_cast<uintptr_t>(d_in) & 15) == 0 && len <= SIZE_MAX / 5)
-        arena = static_cast<uint8_t*>(auto_thread_arena(5 * len));
+    if (!auto_state().no_arena && (reinterpret_cast<uintptr_t>(d_in) & 15) == 0 && len <= SIZE_MAX / 5)
+        arena = static_cast<uint8_t*>(auto_state().arena.get(5 * len));
     t_phase_ms[0] = t_phase_ms[1] = t_phase_ms[2] = 0;
     PhaseEvents phases;
     phases.begin(t_time_phases);
@@ -131,34 +129,22 @@ int32_t auto_on_device(int B, const void* d_in, void* d_out, size_t len, hipStre
     return kOk;
 }
 
-// no exit while work that touches this thread's staging buffers is in flight (auto_transform.cpp, StreamDrain)
-struct Drain {
-    hipStream_t stream = nullptr;
-    bool armed = false;
-    ~Drain()
-    {
-        if (armed) (void)hipStreamSynchronize(stream);
-    }
-};
-
 // any estimator but the entropy one: MaxCompressedSize once for `len`, then per candidate in order one full transform, its
 // download into `out` and EstimateCompressedSize on it (the last candidate is `in` itself); the winner is transformed and
 // downloaded again unless it was the last one written
 int32_t auto_with_callbacks(int B, const uint8_t* in, uint8_t* out, size_t len, const DltSizeEstimator* est, int* pick)
 {
     const uint64_t pixels = len / (size_t)B;
+    AutoThreadState& state = auto_state();
     size_t max_comp = 0;
-    auto_count_estimation(0, 1);
+    ++state.estimator_callbacks;
     if (est->MaxCompressedSize(est->Context, len, &max_comp) != 0)
         return fail(kEstimator, "size estimator: max_compressed_size failed");
-    struct Scratch {
-        uint8_t* ptr = nullptr;
-        ~Scratch() { std::free(ptr); }
-    } scratch;
-    if (max_comp != 0 && (scratch.ptr = static_cast<uint8_t*>(std::aligned_alloc(64, (max_comp + 63) / 64 * 64))) == nullptr)
+    EstimatorScratch scratch;
+    if (!scratch.allocate(max_comp))
         return fail(kAllocation, "estimator scratch allocation failed");
     void *d_in = nullptr, *d_out = nullptr;
-    Drain drain;
+    StreamDrain drain;
     if (int32_t rc = acquire_staging(len, &d_in, &d_out, &drain.stream))
         return rc;
     hipStream_t st = drain.stream;
@@ -172,13 +158,13 @@ int32_t auto_with_callbacks(int B, const uint8_t* in, uint8_t* out, size_t len, 
             if (int32_t rc = transform_candidate(B, i, d_in, d_out, pixels, st))
                 return rc;
             last = i;
-            auto_count_estimation(len, 0);
+            state.section_bytes_downloaded += len;
             HIP_TRY(hipMemcpyAsync(out, d_out, len, hipMemcpyDeviceToHost, st), "D2H candidate");
             HIP_TRY(hipStreamSynchronize(st), "stream synchronize");
             seen = out;
         }
         size_t size = 0;
-        auto_count_estimation(0, 1);
+        ++state.estimator_callbacks;
         if (est->EstimateCompressedSize(est->Context, seen, len, scratch.ptr, max_comp, &size) != 0)
             return fail(kEstimator, "size estimator: estimate_compressed_size failed");
         if (size < best_size) {
@@ -200,8 +186,8 @@ int32_t auto_with_callbacks(int B, const uint8_t* in, uint8_t* out, size_t len, 
 int32_t report(int32_t rc, int pick, bool* out_decorrelate, uint8_t* out_layout)
 {
     if (rc == kOk) {
-        if (out_decorrelate) *out_decorrelate = kOrder[pick].decorrelate;
-        if (out_layout) *out_layout = kOrder[pick].layout;
+        store_if(out_decorrelate, kOrder[pick].decorrelate);
+        store_if(out_layout, kOrder[pick].layout);
     }
     return rc;
 }
@@ -218,21 +204,12 @@ int32_t dxtlt_transform_pixels_auto_device(const void* d_input, void* d_output, 
         return rc;
     if (len > 0 && (d_input == nullptr || d_output == nullptr))
         return fail(kInvalidArgument, "NULL buffer with len > 0");
-    auto_begin_device_call();
+    auto_state().begin_call();
     int pick = 0;   // every estimate of an empty buffer is 0: the first candidate stays
-    if (len > 0) {
-        int count = 0;
-        hipError_t e = hipGetDeviceCount(&count);
-        if (e != hipSuccess || count <= 0)
-            return fail(kNoDevice, "no HIP device available (this library has no CPU fallback)", e);
-        hipStream_t st = static_cast<hipStream_t>(hip_stream);
-        if (stream_is_capturing(st))
-            return fail(kInvalidArgument, "the auto transforms read their estimates back and wait for the stream: not capturable");
-        if (int32_t rc = auto_on_device(pixel_bytes, d_input, d_output, len, st, &pick)) {
-            (void)hipStreamSynchronize(st);   // the arena belongs to this thread's next call
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    if (len > 0)
+        if (int32_t rc = auto_device_call(st, [&] { return auto_on_device(pixel_bytes, d_input, d_output, len, st, &pick); }))
             return rc;
-        }
-    }
     return report(kOk, pick, out_decorrelate, out_layout);
 }
 
@@ -246,7 +223,7 @@ int32_t dxtlt_transform_pixels_auto(const uint8_t* input_ptr, uint8_t* output_pt
         return fail(kInvalidArgument, "NULL estimator");
     if (len > 0 && (input_ptr == nullptr || output_ptr == nullptr))
         return fail(kInvalidArgument, "NULL buffer with len > 0");
-    auto_begin_device_call();
+    auto_state().begin_call();
     int pick = 0;
     if (len == 0)
         return report(kOk, pick, out_decorrelate, out_layout);
@@ -254,17 +231,9 @@ int32_t dxtlt_transform_pixels_auto(const uint8_t* input_ptr, uint8_t* output_pt
         return report(auto_with_callbacks(pixel_bytes, input_ptr, output_ptr, len, estimator, &pick), pick, out_decorrelate, out_layout);
 
     // one upload, everything on the device, one download
-    void *d_in = nullptr, *d_out = nullptr;
-    hipStream_t st = nullptr;
-    if (int32_t rc = acquire_staging(len, &d_in, &d_out, &st))
-        return rc;
-    hipError_t e = hipMemcpyAsync(d_in, input_ptr, len, hipMemcpyHostToDevice, st);
-    int32_t rc = e == hipSuccess ? auto_on_device(pixel_bytes, d_in, d_out, len, st, &pick) : fail(kDevice, "H2D copy", e);
-    if (rc == kOk && (e = hipMemcpyAsync(output_ptr, d_out, len, hipMemcpyDeviceToHost, st)) != hipSuccess)
-        rc = fail(kDevice, "D2H result", e);
-    e = hipStreamSynchronize(st);   // on every exit: the staging buffers and the arena belong to this thread's next call
-    if (rc == kOk && e != hipSuccess)
-        rc = fail(kDevice, "stream synchronize", e);
+    const int32_t rc = auto_staged_call(input_ptr, output_ptr, len, [&](const void* d_in, void* d_out, hipStream_t st) {
+        return auto_on_device(pixel_bytes, d_in, d_out, len, st, &pick);
+    });
     if (rc != kOk)
         t_total_count = 0;
     return report(rc, pick, out_decorrelate, out_layout);
@@ -291,7 +260,7 @@ int32_t dxtlt_debug_pixels_auto_candidates_device(const void* d_input, size_t le
         return rc;
     if (d_input == nullptr || len == 0 || (reinterpret_cast<uintptr_t>(d_input) & 15) != 0 || len > SIZE_MAX / 5)
         return fail(kInvalidArgument, "a non-empty buffer on a 16-byte boundary");
-    void* arena = auto_thread_arena(5 * len);
+    void* arena = auto_state().arena.get(5 * len);
     if (arena == nullptr)
         return fail(kDevice, "candidate arena allocation failed", hipErrorOutOfMemory);
     HIP_TRY(dxtlt::pixels::launch_auto_candidates(pixel_bytes, d_input, arena, len / (size_t)pixel_bytes,

@@ -17,7 +17,7 @@
 
 #include "../../include/dxtlt_pixels.h"
 #include "entropy_launch.h"
-#include "host_common.h"
+#include "auto_call.h"
 #include "pixel_batch_api.h"
 #include "pixel_batch_launch.h"
 #include "pixel_batch_plan.h"
@@ -54,7 +54,7 @@ extern "C" int32_t dxtlt_transform_pixels_batch_auto_device(DxtltPixelBatchAutoI
 {
     t_debug.begin_call();
     t_debug.clear_phase_ms();
-    auto_begin_device_call();
+    auto_state().begin_call();
     if (count == 0)
         return kOk;
     pb::AutoPlan plan;
@@ -73,7 +73,7 @@ extern "C" int32_t dxtlt_transform_pixels_batch_auto_device(DxtltPixelBatchAutoI
     if (int32_t rc = auto_call_device_check(st))
         return rc;
 
-    uint8_t* arena = static_cast<uint8_t*>(auto_thread_arena((size_t)plan.arena_bytes));
+    uint8_t* arena = static_cast<uint8_t*>(auto_state().arena.get((size_t)plan.arena_bytes));
     if (arena == nullptr)
         return fail(kDevice, "candidate arena allocation failed", hipErrorOutOfMemory);
     BatchAutoBuffers& buffers = batch_auto_thread_buffers();

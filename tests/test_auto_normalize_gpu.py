@@ -1,6 +1,7 @@
 """The auto transform with block normalisation on the device (include/dxtlt_auto_normalize.h), held to the CPU statements of
 tests/auto_normalize_ref.py: the candidate kernel's arena byte for byte, the whole device call -- choice, output bytes, totals and
-what it waited for and launched --, the routes without the arena, the host calls, a capturing stream and the Python wrappers.
+what it waited for and launched --, the routes without the arena, the host calls (BC2's callback route under a scripted estimator
+included), a capturing stream and the Python wrappers.
 Every comparison is exact equality; every buffer the library writes lies between 256 guard bytes."""
 import ctypes as C
 
@@ -232,6 +233,68 @@ def test_bc2_host_call_with_a_callers_estimator(lib, dev, oracle, use_all):
         choice, out = host_call(lib, 2, use_all, x, C.cast(C.pointer(est), C.c_void_p))
         assert log == [x.size // 4] * calls
         assert choice == want[0] and np.array_equal(out, want[1])
+
+
+SCRIPTED_BLOCKS = (2, 3, 513)                    # a lone pair, an odd count, one tile and a block: the smallest of each
+
+
+@pytest.mark.parametrize("use_all", [False, True])
+def test_bc2_callers_estimator_failures_skip_and_survivors_win(lib, dev, oracle, use_all):
+    """BC2's callback route under a scripted estimator, against the statement: every candidate is transformed and shown, a failing
+    estimate skips its candidate and is no error of the call, and the fold is strict `<` from (None, Variant1, split) with the
+    maximum size.  The statement has no failing estimate of its own: one is the answer SIZE_MAX, which under that fold never wins."""
+    from oracle import oracle_c
+
+    for n in SCRIPTED_BLOCKS:
+        x = A.blocks(2, "cycle", n)
+        bufs, any_normalized = A.normalized_buffers(2, x)
+        assert any_normalized
+        a, b = A.colour_span(2, x.size)
+        secs = [((norm, int(v), int(sc)), cabi.section_key(oracle_c.transform("bc2", bufs[norm], v, split_colour=bool(sc))[a:b]))
+                for norm, v, sc in A.candidates(2, use_all)]
+        assert len(secs) == (24 if use_all else 12)
+
+        def run(table, default, want_choice, what):
+            log, cpu_log = [], []
+            est = cabi.scripted_estimator(table, default, log)
+            cpu = cabi.scripted_estimate(table, default, cpu_log)
+
+            def skipping(buf):
+                try:
+                    return cpu(buf)
+                except cabi.ScriptedFailure:
+                    return A.U64_MAX
+
+            want = A.call_statement(2, use_all, x, estimate=skipping)
+            choice, out = host_call(lib, 2, use_all, x, C.cast(C.pointer(est), C.c_void_p))     # rc == 0, out_estimator_error == 0
+            assert choice == want[0] == want_choice, (n, what, choice, want[0], want_choice)
+            assert np.array_equal(out, want[1]), (n, what)
+            assert [key[0] for key in log] == [x.size // 4] * len(secs), (n, what)               # failing candidates included
+            assert log == cpu_log == [key for _c, key in secs], (n, what)
+
+        run({}, ("fail", 9), (A.NONE, 1, 1), "all fail")
+        for norm in range(3):                          # every estimate fails but one of this mode, which answers one below the maximum
+            cand, key = secs[norm * len(secs) // 3 + norm]
+            first = next(c for c, k in secs if k == key)       # (at two blocks the split and the unsplit section hold the same bytes)
+            assert first[0] == norm
+            run({key: cabi.SIZE_MAX - 1}, ("fail", 9), first, ("lone survivor", cand))
+        run({}, 7, secs[0][0], "all equal")
+
+
+def test_bc2_a_failing_max_compressed_size_is_reported_and_writes_nothing(lib, dev, oracle):
+    x = A.blocks(2, "cycle", 513)
+    log = []
+    est, _py = cabi.make_estimator("fail_max", log)
+    out = np.full(x.size + 2 * A.GUARD, GUARD_FILL, dtype=np.uint8)
+    src = np.array(x)
+    for use_all in (False, True):
+        norm, mode, split, err = C.c_uint8(0xEE), C.c_uint8(0xEE), C.c_bool(False), C.c_uint32(99)
+        rc = lib.dxtlt_transform_bc2_auto_with_normalization(src.ctypes.data, out.ctypes.data + A.GUARD, x.size, C.cast(C.pointer(est), C.c_void_p),
+                                                             use_all, C.byref(norm), C.byref(mode), C.byref(split), C.byref(err))
+        assert rc == 5 and err.value == 41, (rc, err.value, lib.dxtlt_last_error())              # DXTLT_E_ESTIMATOR, the callback's code
+        assert b"max_compressed_size" in lib.dxtlt_last_error()
+        assert (out == GUARD_FILL).all() and np.array_equal(src, x) and log == []
+        assert (norm.value, mode.value, split.value) == (0xEE, 0xEE, False)
 
 
 def test_a_capturing_stream_is_refused(lib, dev, oracle):
