@@ -56,7 +56,7 @@ struct AutoHostStage {
 };
 
 // What the auto calls of a thread keep between and about their calls.
-constexpr int kAutoTotalsCap = 24;   // the most candidates a single-buffer call compares (auto_normalize_api.cpp, all modes)
+constexpr int kAutoTotalsCap = 192;  // the most candidates a single-buffer call compares (auto_normalize_api.cpp, BC3, all modes)
 struct AutoThreadState {
     // dxtlt_debug_auto_last_estimation: what the last auto call of this thread downloaded and called for its estimates
     uint64_t section_bytes_downloaded = 0, estimator_callbacks = 0;

@@ -1,5 +1,6 @@
-// auto_normalize_kernels.hip -- transform_bcN_auto_with_normalization (BC1, BC2), candidate phase: the colour section of every
-// (normalisation mode, YCoCg-R variant, split) candidate from ONE read of the input.
+// auto_normalize_kernels.hip -- transform_bcN_auto_with_normalization (BC1, BC2, BC3), candidate phase: the colour section of every
+// (normalisation mode, YCoCg-R variant, split) candidate -- and, BC3, the alpha endpoint section of every (alpha mode, split) --
+// from ONE read of the input.
 //
 // The reference normalises the input three times (normalize_blocks_all_modes), transforms each copy once per settings candidate and
 // estimates the colour section only (bc1 experimental/normalize_blocks/transform.rs:222-333).  Normalisation changes a block's
@@ -8,6 +9,11 @@
 // the three modes and hands each to colour_sections of auto_candidate_lanes.h -- the body the plain candidate kernels run.  Layout:
 // auto_launch.h, auto_normalize_sections.  One 16-byte vector per lane, no LDS; traffic: len read once, 48 / 96 bytes per block
 // written.
+//
+// BC3 (this build's extension): the alpha half and the colour half of a block are normalised independently (bc23_normalize.h), so
+// the 96 / 192 candidates are sums over 8 alpha endpoint sections and BC2's 12 / 24 colour sections.  A lane classifies its alpha
+// half once (uniform_alpha_bc3), derives the endpoint pair under the four alpha modes and writes four endpoint_sections; its colour
+// half goes the BC2 way behind them.  Layout: auto_normalize_bc3_sections; 64 / 112 bytes per block written.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -55,6 +61,24 @@ __device__ __forceinline__ NormColours bc2_colours(uint32_t colours, uint32_t in
     return c;
 }
 
+// BC3: the alpha endpoint pair (a0 | a1 << 8) of one block under the four alpha modes (normalize_alpha_half_bc3's bytes 0-1)
+struct NormAlphaPairs {
+    uint32_t none, uniform, fill, zero;
+};
+
+__device__ __forceinline__ NormAlphaPairs bc3_alpha_pairs(uint32_t w0, uint32_t w1)
+{
+    const uint32_t pair = w0 & 0xFFFFu;
+    uint32_t alpha = 0;
+    NormAlphaPairs a{pair, pair, pair, pair};
+    if (uniform_alpha_bc3(w0, w1, alpha)) {
+        a.uniform = alpha;                               // (alpha, 0)
+        a.fill = alpha == 255 ? 0xFFFFu : alpha;         // opaque: eight 0xFF bytes
+        a.zero = alpha == 255 ? 0u : alpha;              // opaque: (0, 0), indices 0xFF
+    }
+    return a;
+}
+
 // every variant's sections of one normalisation mode, at `colour0`
 template <int FMT, bool ALL, bool HALF_LANES>
 __device__ __forceinline__ void variant_sections(uint8_t* colour0, uint64_t n, uint64_t v, uint32_t ca, uint32_t cb, bool half)
@@ -89,8 +113,16 @@ auto_normalize_candidates_kernel(const uint8_t* __restrict__ in, uint8_t* __rest
     const u32x4 q = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(in + 16 * v));
     if constexpr (FMT == kBc1)
         normalize_candidate_lane<kBc1, ALL, false>(arena, n, v, bc1_colours(q.x, q.y), bc1_colours(q.z, q.w), false);
-    else
+    else if constexpr (FMT == kBc2)
         normalize_candidate_lane<kBc2, ALL, false>(arena, n, v, bc2_colours(q.z, q.w), NormColours{0, 0, 0}, false);
+    else {
+        const NormAlphaPairs a = bc3_alpha_pairs(q.x, q.y);
+        endpoint_sections(arena, n, v, a.none);
+        endpoint_sections(arena + 4 * n, n, v, a.uniform);
+        endpoint_sections(arena + 8 * n, n, v, a.fill);
+        endpoint_sections(arena + 12 * n, n, v, a.zero);
+        normalize_candidate_lane<kBc3, ALL, false>(arena + 16 * n, n, v, bc2_colours(q.z, q.w), NormColours{0, 0, 0}, false);
+    }
 }
 
 // the odd last block of a BC1 buffer (half a vector): one lane
@@ -126,6 +158,31 @@ bc2_any_normalizable_kernel(const uint8_t* in, uint64_t n, uint32_t* d_any)
         *d_any = 1u;
 }
 
+// BC3: the same flag for a block whose alpha half is uniform or whose colour half is a normalisable solid; one block per lane
+__global__ void __launch_bounds__(256)
+bc3_any_normalizable_kernel(const uint8_t* in, uint64_t n, uint32_t* d_any)
+{
+    const uint64_t i = workgroup_index() * 256 + threadIdx.x;
+    bool changed = false;
+    if (i < n) {
+        const uint8_t* p = in + 16 * i;
+        uint32_t w[4];
+        if ((reinterpret_cast<uintptr_t>(in) & 15) == 0) {
+            const u32x4 q = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
+            w[0] = q.x, w[1] = q.y, w[2] = q.z, w[3] = q.w;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                w[k] = (uint32_t)p[4 * k] | ((uint32_t)p[4 * k + 1] << 8) | ((uint32_t)p[4 * k + 2] << 16) | ((uint32_t)p[4 * k + 3] << 24);
+        }
+        uint32_t alpha = 0, solid = 0;
+        changed = uniform_alpha_bc3(w[0], w[1], alpha) || solid_colour_4c(w[2], w[3], solid);
+    }
+    // one store per wave at most; every writer stores the same value
+    if (__ballot(changed) != 0 && (threadIdx.x & 63) == 0)
+        *d_any = 1u;
+}
+
 }  // namespace
 
 hipError_t launch_auto_normalize_candidates(Format fmt, bool all_variants, const void* d_in, void* d_arena, uint64_t blocks,
@@ -133,7 +190,7 @@ hipError_t launch_auto_normalize_candidates(Format fmt, bool all_variants, const
 {
     if (launches)
         *launches = 0;
-    if (fmt != kBc1 && fmt != kBc2)
+    if (fmt != kBc1 && fmt != kBc2 && fmt != kBc3)
         return hipErrorInvalidValue;
     if (blocks == 0)
         return hipSuccess;
@@ -149,7 +206,8 @@ hipError_t launch_auto_normalize_candidates(Format fmt, bool all_variants, const
 #define DXTLT_AUTO_NORM_LAUNCH(F, A) \
         hipLaunchKernelGGL((auto_normalize_candidates_kernel<F, A>), grid, dim3(256), 0, stream, in, arena, blocks, vectors)
         if (fmt == kBc1) { if (all_variants) DXTLT_AUTO_NORM_LAUNCH(kBc1, true); else DXTLT_AUTO_NORM_LAUNCH(kBc1, false); }
-        else { if (all_variants) DXTLT_AUTO_NORM_LAUNCH(kBc2, true); else DXTLT_AUTO_NORM_LAUNCH(kBc2, false); }
+        else if (fmt == kBc2) { if (all_variants) DXTLT_AUTO_NORM_LAUNCH(kBc2, true); else DXTLT_AUTO_NORM_LAUNCH(kBc2, false); }
+        else { if (all_variants) DXTLT_AUTO_NORM_LAUNCH(kBc3, true); else DXTLT_AUTO_NORM_LAUNCH(kBc3, false); }
 #undef DXTLT_AUTO_NORM_LAUNCH
         if (hipError_t e = hipGetLastError(); e != hipSuccess)
             return e;
@@ -177,6 +235,17 @@ hipError_t launch_bc2_any_normalizable(const void* in, uint64_t num_blocks, uint
     if (hipError_t e = grid_rows(num_blocks, 256, grid); e != hipSuccess)
         return e;
     hipLaunchKernelGGL(bc2_any_normalizable_kernel, grid, dim3(256), 0, stream, static_cast<const uint8_t*>(in), num_blocks, d_any);
+    return hipGetLastError();
+}
+
+hipError_t launch_bc3_any_normalizable(const void* in, uint64_t num_blocks, uint32_t* d_any, hipStream_t stream)
+{
+    if (num_blocks == 0)
+        return hipSuccess;
+    dim3 grid;
+    if (hipError_t e = grid_rows(num_blocks, 256, grid); e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(bc3_any_normalizable_kernel, grid, dim3(256), 0, stream, static_cast<const uint8_t*>(in), num_blocks, d_any);
     return hipGetLastError();
 }
 

@@ -226,7 +226,7 @@ bool is_builtin_estimator(const DltSizeEstimator* estimator);   // by the identi
 // This thread's counter block on the current device: kMaxCounters estimates (BC3 with every mode, one full transform per
 // candidate: 16 x 2).  estimate_enqueue puts the estimates of `count` sections into counters [first_counter, + count) on
 // `stream`; estimate_read_back copies counters [0, count) to `out` and waits for the stream.
-constexpr size_t kMaxCounters = 32;
+constexpr size_t kMaxCounters = 32;   // also the sections of BC3's auto transform with normalisation (8 alpha + 24 colour)
 int32_t estimate_enqueue(const dxtlt::EstimateSection* sections, size_t count, hipStream_t stream, size_t first_counter);
 int32_t estimate_read_back(size_t count, hipStream_t stream, uint64_t* out);
 // The entropy estimator (include/dxtlt_entropy_estimator.h) into the same counters; recognised by the identity of its pointer.

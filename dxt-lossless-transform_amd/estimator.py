@@ -346,6 +346,6 @@ def last_auto_estimation() -> tuple[int, int]:
 
 def last_auto_totals() -> list[int]:
     """The totals the last built-in-estimator auto transform called from this thread compared, in candidate order."""
-    buf = (C.c_uint64 * 24)()      # 24: normalize.transform_bcN_auto_with_normalization with every decorrelation mode
-    n = _l().dxtlt_debug_auto_last_totals(buf, 24)
+    buf = (C.c_uint64 * 192)()     # 192: normalize.transform_bc3_auto_with_normalization with every decorrelation mode
+    n = _l().dxtlt_debug_auto_last_totals(buf, 192)
     return [int(v) for v in buf[:n]]

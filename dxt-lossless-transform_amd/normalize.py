@@ -216,6 +216,10 @@ def _auto_l():
             f.argtypes, f.restype = [_VP, _VP, _SZ, _VP, _B, u8p, u8p, bp, C.POINTER(C.c_uint32)], C.c_int32
             f = getattr(l, f"dxtlt_transform_{fmt}_auto_with_normalization_device")
             f.argtypes, f.restype = [_VP, _VP, _SZ, _B, _VP, u8p, u8p, bp], C.c_int32
+        l.dxtlt_transform_bc3_auto_with_normalization.argtypes = [_VP, _VP, _SZ, _VP, _B, u8p, u8p, u8p, bp, bp, C.POINTER(C.c_uint32)]
+        l.dxtlt_transform_bc3_auto_with_normalization.restype = C.c_int32
+        l.dxtlt_transform_bc3_auto_with_normalization_device.argtypes = [_VP, _VP, _SZ, _B, _VP, u8p, u8p, u8p, bp, bp]
+        l.dxtlt_transform_bc3_auto_with_normalization_device.restype = C.c_int32
         _auto_declared = True
     return l
 
@@ -227,8 +231,10 @@ def _auto_with_normalization(fmt: str, input, output, estimator, use_all_decorre
     _sized(src, dst, 8 if fmt == "bc1" else 16)
     device = _device_of((src, dst), "input and output must both be host buffers or both be device tensors")
     l = _auto_l()
-    norm, mode, split = _U8(), _U8(), _B()
+    alpha, norm, mode, split_alpha, split = _U8(), _U8(), _U8(), _B(), _B()
     outs = (C.byref(norm), C.byref(mode), C.byref(split))
+    if fmt == "bc3":
+        outs = (C.byref(alpha), C.byref(norm), C.byref(mode), C.byref(split_alpha), C.byref(split))
     use_all = bool(use_all_decorrelation_modes)
     if device is None:
         if estimator is None:
@@ -246,6 +252,8 @@ def _auto_with_normalization(fmt: str, input, output, estimator, use_all_decorre
         with torch.cuda.device(device):
             _check(getattr(l, f"dxtlt_transform_{fmt}_auto_with_normalization_device")(
                 src.ptr, dst.ptr, src.nbytes, use_all, torch.cuda.current_stream(device).cuda_stream, *outs))
+    if fmt == "bc3":
+        return int(alpha.value), ColorNormalizationMode(norm.value), int(mode.value), bool(split_alpha.value), bool(split.value)
     return ColorNormalizationMode(norm.value), int(mode.value), bool(split.value)
 
 
@@ -262,3 +270,14 @@ def transform_bc2_auto_with_normalization(input, output, estimator=None, use_all
     """BC2's twin (this build's extension, include/dxtlt_auto_normalize.h).  Returns (ColorNormalizationMode, decorrelation mode in
     the core YCoCgVariant numbering, split_colour_endpoints); ``output`` holds ``transform_bc2_with_normalize_blocks`` with them."""
     return _auto_with_normalization("bc2", input, output, estimator, use_all_decorrelation_modes)
+
+
+def transform_bc3_auto_with_normalization(input, output, estimator=None, use_all_decorrelation_modes: bool = False):
+    """BC3's twin (this build's extension, include/dxtlt_auto_normalize.h): 4 alpha modes x 3 colour modes x BC3's 8 / 16 settings,
+    each the sum of its alpha and colour endpoint sections' estimates.  Returns (normalize23.AlphaNormalizationMode,
+    ColorNormalizationMode, decorrelation mode in the core YCoCgVariant numbering, split_alpha_endpoints, split_colour_endpoints);
+    ``output`` holds ``transform_bc3_with_normalize_blocks`` with them."""
+    from .normalize23 import AlphaNormalizationMode
+
+    alpha, norm, mode, split_alpha, split = _auto_with_normalization("bc3", input, output, estimator, use_all_decorrelation_modes)
+    return AlphaNormalizationMode(alpha), norm, mode, split_alpha, split

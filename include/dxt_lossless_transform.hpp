@@ -543,6 +543,47 @@ inline void transform_bc3_with_normalize_blocks(const uint8_t* input_ptr, uint8_
                                                                    static_cast<uint8_t>(s.decorrelation_mode),
                                                                    s.split_alpha_endpoints, s.split_colour_endpoints));
 }
+// BC3's twin of transform_bc2_auto_with_normalization (dxtlt_auto_normalize.h; no upstream counterpart): the alpha and colour
+// normalisation modes and the settings whose alpha + colour endpoint sections the estimator finds smallest; output =
+// transform_bc3_with_normalize_blocks with them
+struct Bc3TransformDetailsWithNormalization {
+    AlphaNormalizationMode alpha_normalization_mode = AlphaNormalizationMode::None;
+    ColorNormalizationMode color_normalization_mode = ColorNormalizationMode::None;
+    Bc3TransformSettings settings{};
+};
+namespace detail_bc3 {
+inline Bc3TransformDetailsWithNormalization details(uint8_t alpha, uint8_t norm, uint8_t mode, bool sa, bool sc)
+{
+    Bc3TransformDetailsWithNormalization d;
+    d.alpha_normalization_mode = static_cast<AlphaNormalizationMode>(alpha);
+    d.color_normalization_mode = static_cast<ColorNormalizationMode>(norm);
+    d.settings.decorrelation_mode = static_cast<YCoCgVariant>(mode);
+    d.settings.split_alpha_endpoints = sa;
+    d.settings.split_colour_endpoints = sc;
+    return d;
+}
+}  // namespace detail_bc3
+template <class E>
+std::pair<Bc3TransformDetailsWithNormalization, DetermineBestTransformError> transform_bc3_auto_with_normalization(
+    const uint8_t* input_ptr, uint8_t* output_ptr, size_t len, EstimateSettings<E>& options)
+{
+    DltSizeEstimator v = detail_auto::make_vtable(options.size_estimator);
+    uint8_t alpha = 0, norm = 0, mode = 1;
+    bool sa = true, sc = true;
+    int32_t rc = dxtlt_transform_bc3_auto_with_normalization(input_ptr, output_ptr, len, &v, options.use_all_decorrelation_modes,
+                                                             &alpha, &norm, &mode, &sa, &sc, nullptr);
+    return {detail_bc3::details(alpha, norm, mode, sa, sc), detail_auto::map(rc)};
+}
+inline Bc3TransformDetailsWithNormalization transform_bc3_auto_with_normalization_device(const void* d_input, void* d_output, size_t len,
+                                                                                         bool use_all_decorrelation_modes,
+                                                                                         void* hip_stream)
+{
+    uint8_t alpha = 0, norm = 0, mode = 1;
+    bool sa = true, sc = true;
+    detail::check_device(dxtlt_transform_bc3_auto_with_normalization_device(d_input, d_output, len, use_all_decorrelation_modes, hip_stream,
+                                                                            &alpha, &norm, &mode, &sa, &sc));
+    return detail_bc3::details(alpha, norm, mode, sa, sc);
+}
 }  // namespace bc3
 
 }  // namespace experimental

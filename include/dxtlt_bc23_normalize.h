@@ -112,8 +112,9 @@ int32_t dxtlt_bc3_normalize_blocks_all_modes_device(const void *d_input, void *c
  * instruction column, not the occupancy column: the BC3 kernels are 2.0-3.2 x the plain kernels' instructions, and in the
  * halo tiles the first wave normalises a second vector, the halo.  normalize_blocks + transform reaches 0.37-0.42 per cell.
  *
- * transform_bc2_auto_with_normalization, host and device: dxtlt_auto_normalize.h.  Out of scope:
- * transform_bc3_auto_with_normalization (upstream has none, and BC3's brute force would be 12 x 16 candidates); normalisation in the batch, sharded and DDS calls; the stand-alone normalisers above and the inverse kernels
+ * transform_bc2_auto_with_normalization and transform_bc3_auto_with_normalization, host and device: dxtlt_auto_normalize.h
+ * (upstream has no BC3 one; its 12 x 16 candidates are sums over 8 alpha and 24 colour sections, so no brute force is made).
+ * Out of scope: normalisation in the batch, sharded and DDS calls; the stand-alone normalisers above and the inverse kernels
  * are unchanged.
  */
 int32_t dxtlt_transform_bc2_with_normalize_blocks(const uint8_t *input_ptr, uint8_t *output_ptr, size_t len,

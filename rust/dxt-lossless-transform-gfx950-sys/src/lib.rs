@@ -195,3 +195,16 @@ extern "C" {
         alpha_mode: u8, color_mode: u8, decorrelation_mode: u8, split_alpha_endpoints: bool, split_colour_endpoints: bool,
         hip_stream: *mut c_void) -> i32;
 }
+
+// ---- include/dxtlt_auto_normalize.h: BC3's auto transform with block normalisation (no upstream counterpart): the alpha mode,
+// the colour mode and the settings whose alpha + colour endpoint sections the estimator finds smallest; the output is
+// dxtlt_transform_bc3_with_normalize_blocks(input, winner).  Every out-parameter may be null.
+extern "C" {
+    pub fn dxtlt_transform_bc3_auto_with_normalization_device(d_input: *const c_void, d_output: *mut c_void, len: usize,
+        use_all_decorrelation_modes: bool, hip_stream: *mut c_void, out_alpha_mode: *mut u8, out_color_mode: *mut u8,
+        out_decorrelation_mode: *mut u8, out_split_alpha_endpoints: *mut bool, out_split_colour_endpoints: *mut bool) -> i32;
+    pub fn dxtlt_transform_bc3_auto_with_normalization(input_ptr: *const u8, output_ptr: *mut u8, len: usize,
+        estimator: *const DltSizeEstimator, use_all_decorrelation_modes: bool, out_alpha_mode: *mut u8, out_color_mode: *mut u8,
+        out_decorrelation_mode: *mut u8, out_split_alpha_endpoints: *mut bool, out_split_colour_endpoints: *mut bool,
+        out_estimator_error: *mut u32) -> i32;
+}

@@ -27,7 +27,15 @@ transform and the stand-alone normalise kernel: ms and fraction of the 8 TB/s HB
           host        the host call with the built-in estimator (sizes up to 256 MiB); host_parent: the same call of the library at
                       --parent-lib (a build of the commit before this call existed on the device: it goes through the callbacks)
         and, with HIP events, the parts of `device`: the candidate kernel, the estimator over its sections, the winner's transform.
-    tools/normalize_bench.py auto-cells --mib ... [--parent-lib PATH]   one such process: a JSON line with every cell"""
+    tools/normalize_bench.py auto-cells --mib ... [--parent-lib PATH]   one such process: a JSON line with every cell
+
+    tools/normalize_bench.py auto-bc3 [--mib 1,256,2048] [--processes 3] [--out profiles/auto_normalize_bc3_bench.json]
+        the same for BC3 (dxtlt_transform_bc3_auto_with_normalization_device).  `loop` is the same work from the calls that existed
+        before it: the 12 / 24 fused dxtlt_transform_bc3_with_normalize_blocks_device launches, one per colour section k (the first
+        eight with alpha section k's alpha mode and split), dxtlt_estimate_sizes_device per shown section, one readback, the pick
+        over the 96 / 192 sums, the winner once more.  "tenth": every 20th block a solid colour, every 20th a solid by index 1,
+        every 20th a uniform alpha half, every 20th an opaque one.
+    tools/normalize_bench.py auto-bc3-cells --mib ...                   one such process"""
 import json
 import os
 import sys
@@ -148,6 +156,8 @@ def auto_data(fmt, nbytes, kind, dev):
     colour by index 0 and every 20th a fully transparent block (BC1) / a solid by index 1 (BC2)"""
     bb, at = (8, 0) if fmt == 1 else (16, 8)
     n = nbytes // bb
+    if fmt == 3:
+        return auto_data_bc3(n, kind, dev)
     x = torch.empty(n * bb, dtype=torch.uint8, device=dev)
     pkg.fill_splitmix64(x, 0xA0700 + fmt)
     b = x.view(-1, bb)
@@ -166,14 +176,67 @@ def auto_data(fmt, nbytes, kind, dev):
     return x
 
 
-def auto_cells(mibs, parent_lib=None, rounds=3):
+def auto_data_bc3(n, kind, dev):
+    """BC2's colour halves behind alpha halves no alpha mode changes (a0 >= 128 > 119 >= a1, pixels 0 and 1 with indices 0 and 1);
+    "tenth": every 20th block a uniform alpha half by index 0 and every 20th an opaque one, (255, a1) by index 0"""
+    x = auto_data(2, n * 16, kind, dev)
+    b = x.view(-1, 16)
+    for lo in range(0, n, 1 << 24):
+        v = b[lo:min(n, lo + (1 << 24))]
+        v[:, 0] |= 0x80
+        v[:, 1] &= 0x77
+        v[:, 2] = (v[:, 2] & 0xC0) | 0x08
+    if kind == "tenth":
+        b[5::20, 2:8] = 0
+        b[15::20, 2:8] = 0
+        b[15::20, 0] = 0xFF
+    return x
+
+
+# the test orders: BC1 / BC2 (variant, split colour), BC3 (variant, split alpha, split colour)
+AUTO_FAST = [(0, 0), (0, 1), (1, 0), (1, 1)]
+AUTO_ALL = [(2, 0), (0, 0), (0, 1), (3, 0), (3, 1), (2, 1), (1, 0), (1, 1)]
+AUTO_FAST3 = [(1, 1, 0), (1, 1, 1), (0, 1, 0), (0, 0, 1), (0, 1, 1), (1, 0, 1), (0, 0, 0), (1, 0, 0)]
+AUTO_ALL3 = [(2, 1, 0), (2, 1, 1), (3, 1, 1), (3, 1, 0), (1, 1, 0), (3, 0, 1), (1, 1, 1), (2, 0, 1),
+             (2, 0, 0), (3, 0, 0), (0, 1, 0), (0, 0, 1), (0, 1, 1), (1, 0, 1), (0, 0, 0), (1, 0, 0)]
+
+
+def auto_plan(fmt, use_all, nbytes, y_ptr):
+    """What the legs of auto_cells need to know about (format, depth), so that they are written once:
+      launches       the fused launches of the `loop` leg: (settings of dxtlt_transform_bcN_with_normalize_blocks_device behind
+                     `len`, [((address, length) of a section of the output to estimate after it, its counter)])
+      cands          the candidates in the order they are compared: (settings, the counters its total is the sum of)
+      section_lens   the candidate arena, end to end, in counter order
+      mode_outs      how many of the call's out-parameters are uint8 modes (the rest are bool splits); the plain auto call takes
+                     the last of them and the splits
+    BC1 / BC2: one launch, one colour section and one counter per candidate.  BC3: one launch per colour section k (counter 8 + k),
+    the first eight with alpha section k's mode and split (counter k); a candidate is alpha counter + colour counter."""
+    variants = 4 if use_all else 2
+    blocks = nbytes // (8 if fmt == 1 else 16)
+    colour = (y_ptr, nbytes // 2) if fmt == 1 else (y_ptr + nbytes // 2, nbytes // 4)
+    if fmt != 3:
+        settings = [(norm, v, bool(sc)) for norm in range(3) for v, sc in (AUTO_ALL if use_all else AUTO_FAST)]
+        return {"launches": [(st, [(colour, i)]) for i, st in enumerate(settings)], "cands": [(st, (i,)) for i, st in enumerate(settings)],
+                "section_lens": [4 * blocks] * len(settings), "mode_outs": 2}
+    alpha = (y_ptr, 2 * blocks)
+    launches = []
+    for k in range(6 * variants):
+        am, sa = (k // 2, k % 2) if k < 8 else (0, 0)
+        st = (am, k // (2 * variants), k // 2 % variants, bool(sa), bool(k % 2))
+        launches.append((st, [(colour, 8 + k)] + ([(alpha, k)] if k < 8 else [])))
+    cands = [((am, cm, v, bool(sa), bool(sc)), (2 * am + sa, 8 + cm * 2 * variants + 2 * v + sc))
+             for am in range(4) for cm in range(3) for v, sa, sc in (AUTO_ALL3 if use_all else AUTO_FAST3)]
+    return {"launches": launches, "cands": cands, "section_lens": [2 * blocks] * 8 + [4 * blocks] * (6 * variants), "mode_outs": 3}
+
+
+def auto_cells(mibs, parent_lib=None, rounds=3, fmts=(1, 2)):
     import ctypes as C
     import statistics
     import time
 
     lib = C.CDLL(pkg._lib.lib_path())
     parent = C.CDLL(parent_lib) if parent_lib else None
-    vp, sz, u8p, bp, u64p = C.c_void_p, C.c_size_t, C.POINTER(C.c_uint8), C.POINTER(C.c_bool), C.POINTER(C.c_uint64)
+    vp, sz, u8, b, u8p, bp, u64p = C.c_void_p, C.c_size_t, C.c_uint8, C.c_bool, C.POINTER(C.c_uint8), C.POINTER(C.c_bool), C.POINTER(C.c_uint64)
 
     class Sec(C.Structure):
         _fields_ = [("d_ptr", vp), ("len", C.c_uint64)]
@@ -182,17 +245,18 @@ def auto_cells(mibs, parent_lib=None, rounds=3):
         if l is None:
             continue
         l.dxtlt_builtin_size_estimator.restype = vp
-        l.dxtlt_transform_bc1_auto_with_normalization.argtypes = [vp, vp, sz, vp, C.c_bool, u8p, u8p, bp, C.POINTER(C.c_uint32)]
-    for n in (1, 2):
-        getattr(lib, f"dxtlt_transform_bc{n}_auto_with_normalization_device").argtypes = [vp, vp, sz, C.c_bool, vp, u8p, u8p, bp]
-        getattr(lib, f"dxtlt_transform_bc{n}_auto_with_normalization").argtypes = [vp, vp, sz, vp, C.c_bool, u8p, u8p, bp, C.POINTER(C.c_uint32)]
-        getattr(lib, f"dxtlt_transform_bc{n}_auto_device").argtypes = [vp, vp, sz, C.c_bool, vp, u8p, bp]
-        getattr(lib, f"dxtlt_transform_bc{n}_with_normalize_blocks_device").argtypes = [vp, vp, sz, C.c_uint8, C.c_uint8, C.c_bool, vp]
+        l.dxtlt_transform_bc1_auto_with_normalization.argtypes = [vp, vp, sz, vp, b, u8p, u8p, bp, C.POINTER(C.c_uint32)]
+    for n in fmts:
+        outs = [u8p, u8p, u8p, bp, bp] if n == 3 else [u8p, u8p, bp]
+        getattr(lib, f"dxtlt_transform_bc{n}_auto_with_normalization_device").argtypes = [vp, vp, sz, b, vp] + outs
+        getattr(lib, f"dxtlt_transform_bc{n}_auto_with_normalization").argtypes = [vp, vp, sz, vp, b] + outs + [C.POINTER(C.c_uint32)]
+        getattr(lib, f"dxtlt_transform_bc{n}_auto_device").argtypes = [vp, vp, sz, b, vp] + outs[-3 if n == 3 else -2:]
+        getattr(lib, f"dxtlt_transform_bc{n}_with_normalize_blocks_device").argtypes = [vp, vp, sz] + ([u8, u8, u8, b, b] if n == 3 else [u8, u8, b]) + [vp]
     lib.dxtlt_estimate_sizes_device.argtypes = [C.POINTER(Sec), sz, vp, vp]
-    lib.dxtlt_debug_auto_normalization_candidates_into_device.argtypes = [C.c_int32, C.c_bool, vp, sz, vp, C.c_uint64, vp]
+    lib.dxtlt_debug_auto_normalization_candidates_into_device.argtypes = [C.c_int32, b, vp, sz, vp, C.c_uint64, vp]
+    if 3 in fmts:
+        lib.dxtlt_debug_bc3_auto_normalization_candidates_into_device.argtypes = [b, vp, sz, vp, C.c_uint64, vp]
     lib.dxtlt_debug_auto_normalization_last.argtypes = [u64p]
-    FAST = [(0, 0), (0, 1), (1, 0), (1, 1)]
-    ALL = [(2, 0), (0, 0), (0, 1), (3, 0), (3, 1), (2, 1), (1, 0), (1, 1)]
     dev = torch.device("cuda:0")
     stream = torch.cuda.current_stream().cuda_stream
     out = {}
@@ -212,16 +276,15 @@ def auto_cells(mibs, parent_lib=None, rounds=3):
     for mib in mibs:
         nbytes = int(mib * (1 << 20))
         steps = 20 if mib <= 16 else 3
-        for fmt in (1, 2):
+        for fmt in fmts:
             for kind in ("tenth", "none"):
                 x = auto_data(fmt, nbytes, kind, dev)
                 y = torch.empty_like(x)
-                shown = (y.data_ptr(), nbytes // 2) if fmt == 1 else (y.data_ptr() + nbytes // 2, nbytes // 4)
                 for use_all in (False, True):
-                    order = ALL if use_all else FAST
-                    cands = [(norm, v, sc) for norm in range(3) for v, sc in order]
-                    sizes = torch.zeros(len(cands), dtype=torch.int64, device=dev)
-                    choice = [C.c_uint8(), C.c_uint8(), C.c_bool()]
+                    plan = auto_plan(fmt, use_all, nbytes, y.data_ptr())
+                    cands, lens = plan["cands"], plan["section_lens"]
+                    sizes = torch.zeros(len(lens), dtype=torch.int64, device=dev)
+                    choice = [u8() for _ in range(plan["mode_outs"])] + [b() for _ in range(len(cands[0][0]) - plan["mode_outs"])]
                     refs = [C.byref(c) for c in choice]
                     fused = getattr(lib, f"dxtlt_transform_bc{fmt}_with_normalize_blocks_device")
 
@@ -229,16 +292,16 @@ def auto_cells(mibs, parent_lib=None, rounds=3):
                         ok(getattr(lib, f"dxtlt_transform_bc{fmt}_auto_with_normalization_device")(x.data_ptr(), y.data_ptr(), nbytes, use_all, stream, *refs))
 
                     def loop():
-                        sec = Sec(shown[0], shown[1])
-                        for i, (norm, v, sc) in enumerate(cands):
-                            ok(fused(x.data_ptr(), y.data_ptr(), nbytes, norm, v, bool(sc), stream))
-                            ok(lib.dxtlt_estimate_sizes_device(C.byref(sec), 1, stream, sizes.data_ptr() + 8 * i))
+                        for settings, shown in plan["launches"]:
+                            ok(fused(x.data_ptr(), y.data_ptr(), nbytes, *settings, stream))
+                            for (at, length), counter in shown:
+                                ok(lib.dxtlt_estimate_sizes_device(C.byref(Sec(at, length)), 1, stream, sizes.data_ptr() + 8 * counter))
                         got = sizes.cpu().tolist()                       # the one readback
-                        norm, v, sc = cands[got.index(min(got))]
-                        ok(fused(x.data_ptr(), y.data_ptr(), nbytes, norm, v, bool(sc), stream))
+                        totals = [sum(got[c] for c in counters) for _settings, counters in cands]
+                        ok(fused(x.data_ptr(), y.data_ptr(), nbytes, *cands[totals.index(min(totals))][0], stream))
 
                     def plain_auto():
-                        ok(getattr(lib, f"dxtlt_transform_bc{fmt}_auto_device")(x.data_ptr(), y.data_ptr(), nbytes, use_all, stream, refs[1], refs[2]))
+                        ok(getattr(lib, f"dxtlt_transform_bc{fmt}_auto_device")(x.data_ptr(), y.data_ptr(), nbytes, use_all, stream, *refs[plan["mode_outs"] - 1:]))
 
                     legs = {"device": device, "loop": loop, "plain_auto": plain_auto}
                     if mib <= 256:
@@ -266,14 +329,17 @@ def auto_cells(mibs, parent_lib=None, rounds=3):
                     cell = {k: {"ms": round(statistics.median(v), 4), "ms_min": round(min(v), 4), "ms_max": round(max(v), 4)} for k, v in ms.items()}
                     cell["flag"], cell["choice"] = int(last[3]), picked
                     if kind == "tenth":                                  # the parts of `device`, HIP events
-                        count = 24 if use_all else 12
-                        blocks = nbytes // (8 if fmt == 1 else 16)
-                        arena = torch.empty(count * 4 * blocks, dtype=torch.uint8, device=dev)
-                        secs = (Sec * count)(*[Sec(arena.data_ptr() + 4 * blocks * k, 4 * blocks) for k in range(count)])
+                        arena = torch.empty(sum(lens), dtype=torch.uint8, device=dev)
+                        secs = (Sec * len(lens))(*[Sec(arena.data_ptr() + sum(lens[:k]), lens[k]) for k in range(len(lens))])
+                        winner = picked[:plan["mode_outs"]] + [bool(v) for v in picked[plan["mode_outs"]:]]
+                        if fmt == 3:
+                            hook = lambda *a: lib.dxtlt_debug_bc3_auto_normalization_candidates_into_device(use_all, *a)
+                        else:
+                            hook = lambda *a: lib.dxtlt_debug_auto_normalization_candidates_into_device(fmt, use_all, *a)
                         parts = {
-                            "candidates": lambda: ok(lib.dxtlt_debug_auto_normalization_candidates_into_device(fmt, use_all, x.data_ptr(), nbytes, arena.data_ptr(), arena.numel(), stream)),
-                            "estimator": lambda: ok(lib.dxtlt_estimate_sizes_device(secs, count, stream, sizes.data_ptr())),
-                            "winner": lambda: ok(fused(x.data_ptr(), y.data_ptr(), nbytes, picked[0], picked[1], bool(picked[2]), stream)),
+                            "candidates": lambda: ok(hook(x.data_ptr(), nbytes, arena.data_ptr(), arena.numel(), stream)),
+                            "estimator": lambda: ok(lib.dxtlt_estimate_sizes_device(secs, len(lens), stream, sizes.data_ptr())),
+                            "winner": lambda: ok(fused(x.data_ptr(), y.data_ptr(), nbytes, *winner, stream)),
                         }
                         for fn in parts.values():
                             fn()
@@ -285,7 +351,7 @@ def auto_cells(mibs, parent_lib=None, rounds=3):
     return out
 
 
-def auto_main(argv):
+def auto_main(argv, bc3=False):
     import argparse
     import subprocess
 
@@ -293,11 +359,12 @@ def auto_main(argv):
     ap.add_argument("--mib", default="1,256,2048")
     ap.add_argument("--processes", type=int, default=3)
     ap.add_argument("--parent-lib", default=None)
-    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "auto_normalize_bench.json"))
+    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                                  "auto_normalize_bc3_bench.json" if bc3 else "auto_normalize_bench.json"))
     a = ap.parse_args(argv)
     runs = []
     for _ in range(a.processes):   # one after the other: fresh processes, never two on the device at once
-        cmd = [sys.executable, os.path.abspath(__file__), "auto-cells", "--mib", a.mib] + (["--parent-lib", a.parent_lib] if a.parent_lib else [])
+        cmd = [sys.executable, os.path.abspath(__file__), "auto-bc3-cells" if bc3 else "auto-cells", "--mib", a.mib] + (["--parent-lib", a.parent_lib] if a.parent_lib else [])
         done = subprocess.run(cmd, capture_output=True, text=True, check=True)
         runs.append(json.loads(done.stdout.strip().splitlines()[-1]))
         print(f"process {len(runs)} of {a.processes} done", file=sys.stderr, flush=True)
@@ -321,9 +388,10 @@ def auto_main(argv):
             cell["parts_event_ms"] = parts
             cell["estimator_share_of_device"] = [round(p["estimator"] / d["ms"], 3) for p, d in zip(parts, legs["device"])]
         cells[name] = cell
-    res = {"workload": "auto transform with block normalisation, BC1 / BC2, fast / all modes; 'tenth': about 10 % normalisable blocks, 'none': no such block",
+    tenth = "10 % normalisable colour halves and 10 % normalisable alpha halves (20 % of blocks)" if bc3 else "about 10 % normalisable blocks"
+    res = {"workload": f"auto transform with block normalisation, {'BC3' if bc3 else 'BC1 / BC2'}, fast / all modes; 'tenth': {tenth}, 'none': no such block",
            "legs": "ms per call, host clock around work that ends in a device synchronise; median / min / max of 3 rounds, the legs alternating; "
-                   "parts_event_ms: HIP events around the candidate kernel, the estimator over its 12 / 24 sections and the winner's transform",
+                   f"parts_event_ms: HIP events around the candidate kernel, the estimator over its {'20 / 32' if bc3 else '12 / 24'} sections and the winner's transform",
            "spread_ms": "the larger max - min over the processes of the device and the loop leg's ms",
            "processes_per_cell": a.processes, "parent_lib_measured": bool(a.parent_lib),
            "device_faster_than_loop_in_every_tenth_cell": all_faster, "cells": cells}
@@ -339,6 +407,12 @@ if len(sys.argv) > 1 and sys.argv[1] == "auto-cells":
     sys.exit(0)
 if len(sys.argv) > 1 and sys.argv[1] == "auto":
     auto_main(sys.argv[2:])
+    sys.exit(0)
+if len(sys.argv) > 1 and sys.argv[1] == "auto-bc3-cells":
+    print(json.dumps(auto_cells([float(v) for v in sys.argv[sys.argv.index("--mib") + 1].split(",")], fmts=(3,))))
+    sys.exit(0)
+if len(sys.argv) > 1 and sys.argv[1] == "auto-bc3":
+    auto_main(sys.argv[2:], bc3=True)
     sys.exit(0)
 if len(sys.argv) > 1 and sys.argv[1] == "bc23-cells":
     print(json.dumps(bc23_cells(float(sys.argv[sys.argv.index("--gib") + 1]) if "--gib" in sys.argv else 4.0)))
