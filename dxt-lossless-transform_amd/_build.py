@@ -15,8 +15,8 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(_HERE, "libdxtlt_gfx950.so")
 _BUILD_DIR = os.path.join(os.path.dirname(_HERE), "build")
 
-SOURCES = ["bcn_kernels.hip", "bcn_norm23_kernels.hip", "batch_kernels.hip", "dxtlt_api.cpp", "host_staging.cpp", "host_sharded.cpp", "c_api_core.cpp", "c_api_stable.cpp", "auto_transform.cpp", "file_format.cpp",
-           "bc7_kernels.hip", "bc7_api.cpp", "bc6h_kernels.hip", "bc6h_api.cpp", "granule_launch.cpp", "granule_host.cpp", "normalize_kernels.hip", "normalize_api.cpp", "batch_api.cpp", "batch_host_api.cpp",
+SOURCES = ["bcn_kernels.hip", "bcn_norm23_kernels.hip", "batch_kernels.hip", "batch_norm_kernels.hip", "dxtlt_api.cpp", "host_staging.cpp", "host_sharded.cpp", "c_api_core.cpp", "c_api_stable.cpp", "auto_transform.cpp", "file_format.cpp",
+           "bc7_kernels.hip", "bc7_api.cpp", "bc6h_kernels.hip", "bc6h_api.cpp", "granule_launch.cpp", "granule_host.cpp", "normalize_kernels.hip", "normalize_api.cpp", "batch_api.cpp", "batch_normalize_api.cpp", "batch_host_api.cpp",
            "color565_ops.hip", "color565_api.cpp", "bcn_decode.hip", "decode_api.cpp",
            "auto_kernels.hip", "numa_affinity.cpp", "estimate_kernels.hip", "estimate_api.cpp", "batch_auto_kernels.hip", "batch_auto_api.cpp", "pixel_kernels.hip", "pixels_api.cpp",
            "image_kernels.hip", "image_regions_kernels.hip", "image_api.cpp", "image_batch_kernels.hip", "image_batch_api.cpp",

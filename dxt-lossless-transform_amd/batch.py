@@ -136,3 +136,91 @@ def transform_batch_auto(items):
     from . import estimator
 
     return estimator.transform_batch_auto(items)
+
+
+# ---- block normalisation, batched (include/dxtlt_batch_normalize.h) ----------------------------------------------------
+class DxtltBatchNormalizeItem(C.Structure):
+    _fields_ = [("d_input", C.c_void_p), ("d_output", C.c_void_p), ("len", C.c_uint64), ("format", C.c_uint8),
+                ("alpha_mode", C.c_uint8), ("color_mode", C.c_uint8), ("decorrelation_mode", C.c_uint8),
+                ("split_alpha_endpoints", C.c_uint8), ("split_colour_endpoints", C.c_uint8), ("reserved", C.c_uint8 * 2)]
+
+
+def prepare_batch_normalize(items, with_output: bool = True):
+    """The C item array of a normalising batch (and the tensors it points into).  items: (fmt, input tensor, output tensor,
+    (alpha_mode, color_mode), settings) with fmt "bc1" / "bc2" / "bc3"; alpha_mode counts for "bc3" only.  with_output False
+    (batch_any_normalizable): (fmt, input tensor) suffices, the rest is neither needed nor read."""
+    from . import _FMT_ID, BLOCK_BYTES, InvalidLength, OutputBufferTooSmall, _Buf, _settings_tuple
+
+    arr = (DxtltBatchNormalizeItem * len(items))()
+    device, keep = None, []
+    for k, item in enumerate(items):
+        fmt, src = item[0], item[1]
+        if fmt not in ("bc1", "bc2", "bc3"):
+            raise ValueError(f"block normalisation takes bc1, bc2 and bc3, not {fmt!r}")
+        s = _Buf(src, False)
+        if s.device is None:
+            raise TypeError("the normalising batch calls take device tensors")
+        device = s.device if device is None else device
+        if s.device != device:
+            raise ValueError("all tensors of a batch must live on one device")
+        fid, block = _FMT_ID[fmt], BLOCK_BYTES[fmt]
+        if s.nbytes % block != 0:
+            raise InvalidLength(s.nbytes)
+        arr[k].d_input, arr[k].len, arr[k].format = s.ptr, s.nbytes, fid
+        keep.append(s)
+        if not with_output:
+            continue
+        d = _Buf(item[2], True)
+        if d.device != device:
+            raise ValueError("all tensors of a batch must live on one device")
+        if d.nbytes < s.nbytes:
+            raise OutputBufferTooSmall(s.nbytes, d.nbytes)
+        alpha_mode, color_mode = item[3]
+        mode, sa, sc = _settings_tuple(fmt, item[4])
+        arr[k].d_output, arr[k].alpha_mode, arr[k].color_mode = d.ptr, int(alpha_mode), int(color_mode)
+        arr[k].decorrelation_mode = mode
+        arr[k].split_alpha_endpoints, arr[k].split_colour_endpoints = int(bool(sa)), int(bool(sc))
+        keep.append(d)
+    return arr, device, keep
+
+
+def transform_batch_with_normalize_blocks(items) -> None:
+    """items: (fmt, input tensor, output tensor, (alpha_mode, color_mode), settings) with CUDA uint8 tensors on one device: every
+    output receives transform(normalize_blocks(input, modes), settings), in a handful of launches for the whole batch
+    (dxtlt_transform_batch_with_normalize_blocks_device), on torch's current stream."""
+    import torch
+
+    from . import DeviceError
+
+    if not items:
+        return
+    arr, device, _keep = prepare_batch_normalize(items)
+    l = _lib.load()
+    fn = l.dxtlt_transform_batch_with_normalize_blocks_device
+    fn.argtypes, fn.restype = [C.POINTER(DxtltBatchNormalizeItem), C.c_size_t, C.c_void_p], C.c_int32
+    with torch.cuda.device(device):
+        rc = fn(arr, len(arr), torch.cuda.current_stream().cuda_stream)
+    if rc != _lib.OK:
+        raise DeviceError(rc, _lib.last_error())
+
+
+def batch_any_normalizable(items):
+    """items: (fmt, input tensor, ...) with CUDA uint8 tensors on one device.  Returns a CUDA int32 tensor of len(items) flags,
+    1 where the item holds a block that block normalisation would touch (or that is already in normal form), in one launch for
+    the whole batch (dxtlt_batch_any_normalizable_device), on torch's current stream."""
+    import torch
+
+    from . import DeviceError
+
+    if not items:
+        return torch.empty(0, dtype=torch.int32)
+    arr, device, _keep = prepare_batch_normalize(items, with_output=False)
+    flags = torch.empty(len(items), dtype=torch.int32, device=device)
+    l = _lib.load()
+    fn = l.dxtlt_batch_any_normalizable_device
+    fn.argtypes, fn.restype = [C.POINTER(DxtltBatchNormalizeItem), C.c_size_t, C.c_void_p, C.c_void_p], C.c_int32
+    with torch.cuda.device(device):
+        rc = fn(arr, len(arr), flags.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    if rc != _lib.OK:
+        raise DeviceError(rc, _lib.last_error())
+    return flags

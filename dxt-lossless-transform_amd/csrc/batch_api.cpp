@@ -25,6 +25,7 @@
 
 #include "../../include/dxtlt_gfx950.h"
 #include "batch_tables.h"
+#include "batch_tile_plan.h"
 #include "bcn_launch.h"
 #include "granule_launch.h"
 #include "host_common.h"
@@ -104,22 +105,7 @@ inline dxtlt::Settings item_settings(const DxtltBatchItem& it)
     return dxtlt::effective_settings((dxtlt::Format)it.format, s);
 }
 
-// One launch of batch_kernel: the BC1..BC5 items of one format, direction and settings code that the kernel takes.  The kernel is
-// instantiated per settings combination (no run-time switch in front of every tile): a corpus usually has one or two.
-struct TileLaunch {
-    int key = 0;                     // ((format - 1) * 2 + inverse) << 4 | settings_code
-    std::vector<BatchEntry> entries;
-    uint32_t wgs = 0;
-    uint32_t uniform_wgs = 0;        // workgroups per buffer when all buffers own the same number (the kernel then divides instead
-                                     // of looking the entry up), else 0
-    bool strided = false;            // a regular array of buffers: one size and tile form, pointers a constant stride apart
-    int64_t src_stride = 0, dst_stride = 0;
-    bool wide = false;               // the form of its workgroup index, known once fill_tables has built it
-    size_t at = 0, entry_bytes = 0;  // in the staged buffer: the entries, then the workgroup index
-
-    dxtlt::Format format() const { return (dxtlt::Format)((key >> 5) + 1); }
-    bool inverse() const { return ((key >> 4) & 1) != 0; }
-};
+// (TileLaunch, one launch of batch_kernel, and what is done with a plan's tile launches: batch_tile_plan.h)
 
 // BC7 items (format 7; no settings): their granules in one launch per direction, their tail parts in a second one.  BC6H items
 // (format 6) the same, in launches of their own.
@@ -193,34 +179,11 @@ int32_t plan_batch(const DxtltBatchItem* items, size_t count, bool pixels_allowe
             plan.singles.push_back(i);
             continue;
         }
-        if (li < 0) {
-            li = launch_of_key[key] = (int)plan.tiles.size();
-            plan.tiles.emplace_back();
-            plan.tiles.back().key = key;
-            plan.tiles.back().uniform_wgs = wgs;
-        }
-        TileLaunch& l = plan.tiles[(size_t)li];
         // one launch holds fewer than 2^32 threads = 2^24 workgroups of 256 (64 GiB of blocks per format, direction and settings)
-        if ((uint64_t)l.wgs + wgs > 0xFFFFFFull)
+        if (!add_tile_entry(plan.tiles, launch_of_key[key], key, 0, e, wgs))
             return fail(kInvalidArgument, "batch too large for one launch (64 GiB or more of one format, direction and settings)");
-        l.wgs += wgs;
-        l.entries.push_back(e);
-        if (wgs != l.uniform_wgs)
-            l.uniform_wgs = 0;   // (stays 0: no buffer owns 0 workgroups)
     }
-    std::sort(plan.tiles.begin(), plan.tiles.end(), [](const TileLaunch& a, const TileLaunch& b) { return a.key < b.key; });
-    for (TileLaunch& l : plan.tiles) {
-        const size_t n = l.entries.size();
-        l.strided = l.uniform_wgs != 0;   // (one buffer is a regular array too)
-        l.src_stride = n >= 2 ? (int64_t)(l.entries[1].src - l.entries[0].src) : 0;
-        l.dst_stride = n >= 2 ? (int64_t)(l.entries[1].dst - l.entries[0].dst) : 0;
-        for (size_t i = 1; i < n && l.strided; ++i) {
-            const BatchEntry &a = l.entries[0], &b = l.entries[i];
-            l.strided = b.blocks == a.blocks && b.full_tiles == a.full_tiles && b.form == a.form && b.halo_vecs == a.halo_vecs &&
-                        std::memcmp(b.shift, a.shift, sizeof a.shift) == 0 && std::memcmp(b.gbase, a.gbase, sizeof a.gbase) == 0 &&
-                        b.src == a.src + (int64_t)i * l.src_stride && b.dst == a.dst + (int64_t)i * l.dst_stride;
-        }
-    }
+    order_tile_launches(plan.tiles);
 
     for (int q = 0; q < 4; ++q) {
         GranuleLaunch& p = plan.granules[q];
@@ -256,11 +219,7 @@ int32_t plan_batch(const DxtltBatchItem* items, size_t count, bool pixels_allowe
     // same call had enqueued: the "asynchronous" call then drained its own work, and would deadlock under a caller whose stream is
     // gated on an event recorded after the call returns.  Three slots per call -- BC7 forward, BC7 inverse, the groups -- still let
     // the NEXT mixed call wait for this one's kernels; see the ring's comment.)
-    for (TileLaunch& l : plan.tiles) {
-        l.entry_bytes = padded(l.entries.size() * sizeof(BatchEntry), 16);
-        l.at = plan.table_bytes;
-        plan.table_bytes += l.entry_bytes + dxtlt::batch_index_bytes(l.wgs);
-    }
+    place_tile_tables(plan.tiles, plan.table_bytes);
     return kOk;
 }
 
@@ -273,10 +232,7 @@ void fill_tables(BatchPlan& plan, uint8_t* host)
         if (p.tail_bytes) std::memcpy(h + p.entry_bytes, p.tails.data(), p.tail_bytes);
         if (!p.coarse.empty()) std::memcpy(h + p.entry_bytes + p.tail_bytes, p.coarse.data(), p.coarse.size() * sizeof(uint32_t));
     }
-    for (TileLaunch& l : plan.tiles) {
-        std::memcpy(host + l.at, l.entries.data(), l.entries.size() * sizeof(BatchEntry));
-        l.wide = dxtlt::build_batch_index(l.entries.data(), l.entries.size(), l.wgs, host + l.at + l.entry_bytes);
-    }
+    fill_tile_tables(plan.tiles, host);
 }
 
 }  // namespace
@@ -429,15 +385,8 @@ extern "C" int32_t dxtlt_debug_plan_batch_call(const DxtltBatchItem* items, size
         r.table_offset = p.at, r.table_bytes = p.bytes;
         put(r);
     }
-    for (const TileLaunch& l : plan.tiles) {
-        DxtltDebugBatchLaunch r{};
-        r.kind = 1, r.format = l.format(), r.inverse = l.inverse() ? 1 : 0, r.settings_code = l.key & 15;
-        r.items = r.entries = (uint32_t)l.entries.size(), r.workgroups = l.wgs;
-        r.uniform_wgs = l.uniform_wgs, r.strided = l.strided ? 1 : 0, r.wide = l.wide ? 1 : 0;
-        r.src_stride = l.src_stride, r.dst_stride = l.dst_stride;
-        r.table_offset = l.at, r.table_bytes = l.entry_bytes + dxtlt::batch_index_bytes(l.wgs);
-        put(r);
-    }
+    for (const TileLaunch& l : plan.tiles)
+        put(tile_launch_record(l));
     for (int kind = 2; kind <= 3; ++kind)
         for (size_t i : kind == 2 ? plan.singles : plan.pixels) {
             DxtltDebugBatchLaunch r{};

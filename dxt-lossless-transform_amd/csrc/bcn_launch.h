@@ -140,7 +140,7 @@ struct BatchEntry {
     uint8_t form;           // 1: every stream base on a 128-byte line (aligned tiles); 0: halo tiles forward, shifted tiles inverse
     uint8_t halo_vecs;      // halo tiles: 16-byte vectors of blocks in front of a tile that have bytes in its windows
     uint8_t natural;        // every shift a multiple of its stream's element width (the kernel handles nothing else: plan_batch_entry)
-    uint8_t reserved;
+    uint8_t reserved;       // 0; launch_batch_norm, BC2 / BC3: the buffer's normalisation modes (batch_norm_entry_modes)
     uint8_t shift[6];       // misalignment of every stream base: mod 64 forward, mod 16 inverse
     uint8_t reserved2[2];
     uint64_t gbase[6];      // Shifts::gbase: off_s * blocks - shift[s], from the transformed-side pointer
@@ -183,6 +183,28 @@ hipError_t launch_table_upload(const void* host_mapped, void* dev, size_t bytes,
 hipError_t launch_batch(Format fmt, bool inverse, const Settings& s, const BatchEntry* d_entries, const uint8_t* d_index,
                         uint32_t n_entries, uint32_t total_wgs, uint32_t uniform_wgs, bool wide_index, hipStream_t stream,
                         const BatchEntry* strided_first = nullptr, int64_t src_stride = 0, int64_t dst_stride = 0);
+
+// The forward tile batch with block normalisation fused in (batch_norm_kernels.hip): launch_batch's tables and lookup, without
+// the strided shortcuts.  fmt 1..3.  BC2 / BC3: every entry carries its own modes, BatchEntry::reserved = pack_norm_modes(alpha_mode,
+// color_mode) (bcn_device.h); s.normalize / s.normalize_alpha are not read.  BC1: s.normalize = 1 | 2, the mode of the whole launch.
+uint8_t batch_norm_entry_modes(int alpha_mode, int color_mode);   // pack_norm_modes, for host code that does not see bcn_device.h
+hipError_t launch_batch_norm(Format fmt, const Settings& s, const BatchEntry* d_entries, const uint8_t* d_index, uint32_t n_entries,
+                             uint32_t total_wgs, uint32_t uniform_wgs, bool wide_index, hipStream_t stream);
+
+// "Does the item hold a block that normalisation would touch" for many items of formats 1..3 in one launch (batch_norm_kernels.hip):
+// one entry per non-empty item in ascending first_wg, an item owning ceil(blocks / 256) workgroups; d_flags[item] is set to 1 (never
+// cleared: the caller zeroes the flags first) when a block of the item is one launch_bc{1,2,3}_any_normalizable flags.
+struct BatchAnyEntry {
+    const uint8_t* src;
+    uint64_t blocks;
+    uint32_t first_wg;
+    uint32_t format;
+    uint32_t item;
+    uint32_t reserved;
+};
+static_assert(sizeof(BatchAnyEntry) == 32, "BatchAnyEntry layout is shared between host and device");
+hipError_t launch_batch_any_normalizable(const BatchAnyEntry* d_table, uint32_t entries, uint32_t total_wgs, uint32_t* d_flags,
+                                         hipStream_t stream);
 
 // the index (batch_index_bytes(total_wgs) bytes) from the entries (sorted by first_wg, each owning at least one workgroup, no
 // gaps); returns true when it chose the wide (16-bit delta) form

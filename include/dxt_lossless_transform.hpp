@@ -29,6 +29,7 @@
 #include "dxtlt_auto_normalize.h"
 #include "dxtlt_bc1_normalize.h"
 #include "dxtlt_bc23_normalize.h"
+#include "dxtlt_batch_normalize.h"
 #include "dxtlt_bc6h.h"
 #include "dxtlt_bc6h_image.h"
 #include "dxtlt_pixels.h"
@@ -348,6 +349,17 @@ inline bool transform_bc5_auto_device(const void* d_input, void* d_output, size_
 inline void transform_batch_auto_device(DxtltBatchAutoItem* items, size_t count, void* hip_stream)
 {
     detail::check_device(dxtlt_transform_batch_auto_device(items, count, hip_stream));
+}
+
+// Block normalisation fused into the forward transform for many buffers in one call, and which of many buffers hold a block that
+// normalisation would touch (dxtlt_batch_normalize.h): a handful of launches per call; d_flags = `count` device uint32.
+inline void transform_batch_with_normalize_blocks_device(const DxtltBatchNormalizeItem* items, size_t count, void* hip_stream)
+{
+    detail::check_device(dxtlt_transform_batch_with_normalize_blocks_device(items, count, hip_stream));
+}
+inline void batch_any_normalizable_device(const DxtltBatchNormalizeItem* items, size_t count, uint32_t* d_flags, void* hip_stream)
+{
+    detail::check_device(dxtlt_batch_any_normalizable_device(items, count, d_flags, hip_stream));
 }
 
 // Many uncompressed-pixel buffers in one call (dxtlt_pixels.h): one launch per (pixel_bytes, direction, decorrelate, layout) class.

@@ -114,8 +114,8 @@ int32_t dxtlt_bc3_normalize_blocks_all_modes_device(const void *d_input, void *c
  *
  * transform_bc2_auto_with_normalization and transform_bc3_auto_with_normalization, host and device: dxtlt_auto_normalize.h
  * (upstream has no BC3 one; its 12 x 16 candidates are sums over 8 alpha and 24 colour sections, so no brute force is made).
- * Out of scope: normalisation in the batch, sharded and DDS calls; the stand-alone normalisers above and the inverse kernels
- * are unchanged.
+ * Many device buffers per call: dxtlt_transform_batch_with_normalize_blocks_device (dxtlt_batch_normalize.h).  Out of scope:
+ * normalisation in the sharded, host-batch and DDS calls; the stand-alone normalisers above and the inverse kernels are unchanged.
  */
 int32_t dxtlt_transform_bc2_with_normalize_blocks(const uint8_t *input_ptr, uint8_t *output_ptr, size_t len,
                                                   uint8_t color_mode, uint8_t decorrelation_mode,
